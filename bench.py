@@ -23,6 +23,9 @@ Also reported in the same JSON line:
                   matrix pipe), timed separately: the north_star's ">= 50 Mpix/s AND arg-max-identical" measured in one mode
 `--config 2|3|4|5` run BASELINE.json's other configurations (ViT-B/16 slide; L/14 GEM + outlier suppression; L/14 + JBU; H/14 fp8 +
 cross-tile fusion) through the same steps; they are reported separately, never as the default line.
+`--dump-outputs DIR` writes what the last timed step computed, as float32 .npy files (dump_outputs): labels [1,H,W] and stitched logits
+[Q,H,W] of the canvas band, and the tower's per-tile logits.  The inputs are seeded, so two builds run with the same arguments can be
+compared array for array.
 """
 from __future__ import annotations
 
@@ -48,6 +51,7 @@ TILE_COLS, TILE_ROWS_PER_RANK = 17, 7        # the ViT-L/14 default: 119 tiles p
 STRONG_SCENE = 8192                          # strong scaling: one 8192 x 8192 scene = 31 x 31 = 961 tiles
 PEAK_BF16_TFLOPS = 2500.0                    # MI355X dense bf16 / f16 MFMA (MI355X_MICROARCH.md)
 PEAK_FP8_TFLOPS = 5000.0
+DUMP_BYTES = 64_000_000                      # --dump-outputs: bytes of array data over all files (all ranks); larger arrays are sampled
 SIM = dict(similarity_weight=1.0, temperature=1.0, add_self_similarity=True)
 
 # BASELINE.json `configs` as bench workloads (1-based as the tests name them; None = the headline line).  names = configs/cls_*.txt.
@@ -101,7 +105,13 @@ def parse_args(argv=None):
                     help="profiling runs only: skip the single-tile re-computations after the timed region, so that rocprofv3's per-kernel averages cover the timed launch shape alone")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for rehearsing ranks on one GPU)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal: every rank uses cuda:0")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32, at most 64 MB in all; a larger array is stored as a "
+                         "fixed seeded sample of its flattened elements)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def self_launch(args) -> None:
@@ -215,6 +225,35 @@ def parity_of(pipe, kept, oracle, device, mode):
             "against": "oracle (fp32 CPU restatement pinned to the reference), the cpu_baseline tiles, per-pixel logits after stitch; a tie = the "
                        "oracle's own top-2 class probabilities (or arg-max probability and prob_thd) within 1e-4",
             "mode": mode}
+
+
+def dump_sample(n: int, max_bytes: int):
+    """Flat indices of the float32 elements kept of an n-element array within max_bytes: None = all of them, else a sorted sample drawn
+    with a fixed seed (the same indices in every run with the same shapes)."""
+    import numpy as np
+    k = max(max_bytes // 4, 1)
+    if n <= k:
+        return None
+    return np.unique(np.random.default_rng(0).integers(0, n, size=k))
+
+
+def dump_outputs(out_dir, arrays, max_bytes):
+    """arrays: (name, tensor, share of max_bytes) -> out_dir/<name>.npy in float32, the whole array or a dump_sample of its flattened
+    elements.  Returns {name: {"shape", "stored"}} for the result line."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    info = {}
+    for name, t, share in arrays:
+        idx = dump_sample(t.numel(), int(max_bytes * share))
+        a = t.detach()
+        if idx is not None:
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        a = a.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        info[name] = {"shape": list(t.shape),
+                      "stored": "all" if idx is None else f"seeded sample of {a.size} flat elements (dump_sample)"}
+    return info
 
 
 def main():
@@ -336,6 +375,8 @@ def main():
         w_band[:, 0:2] -= y_lo
         canvas = ops.stitch(tiles, w_band, up, (t, l), (y_hi - y_lo, W))
         probs, labels = p.postprocess(canvas, want_probs=False)
+        if args.dump_outputs:
+            last["canvas"], last["labels"] = canvas, labels
         return labels
 
     def barrier():
@@ -361,6 +402,13 @@ def main():
         return dt_
 
     dt = timed(pipe, args.steps, args.warmup)
+    dumped = None
+    if args.dump_outputs:                                # before any later launch: what the last timed step returned
+        sfx = f".rank{rank}" if world > 1 else ""
+        arrays = [("tile_logits" + sfx, last["tl"], 0.13)]
+        if "labels" in last:
+            arrays += [("labels" + sfx, last["labels"], 0.60), ("seg_logits" + sfx, last["canvas"], 0.25)]
+        dumped = dump_outputs(args.dump_outputs, arrays, DUMP_BYTES // world)
 
     def prof(cat):
         ms, fl, n, dr = C.c_double(), C.c_double(), C.c_int64(), C.c_int64()
@@ -471,6 +519,8 @@ def main():
             "roofline": roof,
         }
         out["self_check"] = batched_check
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if jbu or args.config in (3, 4, 5) or w["ctf"]:
             out["cpu_baseline"] = None
             out["cpu_baseline_note"] = ("not timed for this configuration (the oracle's JBU needs ~12 GB and ~70 s per 512-pixel tile, its GEM forward ~9 s per tile: "

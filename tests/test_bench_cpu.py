@@ -5,6 +5,7 @@ import math
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -68,3 +69,38 @@ def test_tile_grids_fill_whole_rounds_of_the_persistent_gemm(bench):
             t = m_tiles * math.ceil(n_out / 256)
             eff = t / (math.ceil(t / 256) * 256)
             assert eff > 0.98, (vit, n_out, eff)
+
+
+def test_steps_and_warmup_are_validated(bench):
+    a = bench.parse_args(["--steps", "7", "--warmup", "0"])
+    assert a.steps == 7 and a.warmup == 0 and a.dump_outputs is None
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_dump_sample_is_fixed_and_bounded(bench):
+    assert bench.dump_sample(1000, 4000) is None                            # fits: the whole array
+    a, b = bench.dump_sample(10 ** 6, 4000), bench.dump_sample(10 ** 6, 4000)
+    assert a is not None and (a == b).all()                                # the same indices in every run
+    assert 0 < a.size <= 1000 and (np.diff(a) > 0).all() and a[0] >= 0 and a[-1] < 10 ** 6
+
+
+def test_dump_outputs_writes_float32_within_the_budget(bench, tmp_path):
+    import torch
+    g = torch.Generator().manual_seed(0)
+    labels = torch.randint(0, 6, (1, 300, 400), generator=g)               # int64, 120000 elements
+    logits = torch.randn(8, 300, 400, generator=g)
+    tiles = torch.randn(5, 8, 37, 37, generator=g)
+    budget = 1_000_000
+    info = bench.dump_outputs(str(tmp_path), [("tile_logits", tiles, 0.13), ("labels", labels, 0.60), ("seg_logits", logits, 0.25)], budget)
+    files = {p.name: p for p in tmp_path.iterdir()}
+    assert set(files) == {"tile_logits.npy", "labels.npy", "seg_logits.npy"}
+    assert sum(np.load(p).nbytes for p in files.values()) <= budget
+    lab, lg, tl = (np.load(files[n + ".npy"]) for n in ("labels", "seg_logits", "tile_logits"))
+    assert lab.dtype == lg.dtype == tl.dtype == np.float32
+    assert info["labels"]["shape"] == [1, 300, 400] and info["labels"]["stored"] == "all"
+    assert (lab == labels.numpy().astype(np.float32)).all()
+    assert info["seg_logits"]["stored"] != "all"                             # over its share: a seeded sample of the flat elements
+    idx = bench.dump_sample(logits.numel(), int(budget * 0.25))
+    assert (lg == logits.reshape(-1).numpy()[idx]).all()
