@@ -258,6 +258,183 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const float* __restric
   labels[i] = arg;
 }
 
+// ---- multi-canvas head: the canvases of N images in one launch ---------------------------------------------------------
+// The grid is flattened over (image, block): block_prefix[n] is the first block of image n (an exclusive prefix sum, N + 1
+// entries).  The image of a block is found by a wave-uniform binary search; no host loop over images.
+__device__ __forceinline__ int image_of_block(const int64_t* __restrict__ block_prefix, int N, int64_t blk) {
+  int lo = 0, hi = N;                                              // largest n with block_prefix[n] <= blk (skips empty images)
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (block_prefix[mid] <= blk) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// stitch_kernel for the tiles of many images: tiles [first, first + count) of image n, windows in that image's coordinates,
+// its canvas [Q,H,W] at canvas_offset[n].  The per-pixel arithmetic, the raster-order candidate list and the averaging order are
+// those of stitch_kernel, so every canvas is bit-identical to sg_stitch on that image alone.
+__global__ __launch_bounds__(256) void stitch_multi_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows,
+                                                           const int32_t* __restrict__ tile_image, int T, int Q, int gh, int gw,
+                                                           int up_h, int up_w, int pad_t, int pad_l, const int32_t* __restrict__ image_hw,
+                                                           const int32_t* __restrict__ image_tiles, const int64_t* __restrict__ canvas_offset,
+                                                           const int64_t* __restrict__ block_prefix, int N, int64_t canvas_elems,
+                                                           float* __restrict__ canvases) {
+  __shared__ int s_list[ST_MAXC];
+  __shared__ int s_count;
+  const int n = image_of_block(block_prefix, N, blockIdx.x);
+  const int H = image_hw[2 * n], W = image_hw[2 * n + 1];
+  const int t_first = image_tiles[2 * n], n_tiles = image_tiles[2 * n + 1];
+  const int64_t plane = (int64_t)H * W;
+  const int64_t off = canvas_offset[n];
+  // a descriptor that would read or write outside the buffers: the whole block leaves (block-uniform, before any barrier)
+  if (t_first < 0 || n_tiles <= 0 || t_first + n_tiles > T || off < 0 || off + Q * plane > canvas_elems) return;
+  const int64_t local = blockIdx.x - block_prefix[n];
+  const int bw = (W + 63) / 64;
+  const int bx0 = (int)(local % bw) * 64, by0 = (int)(local / bw) * 4;
+  const int lane = threadIdx.x & 63;
+  const int32_t* win = windows + (int64_t)t_first * 4;
+  if ((threadIdx.x >> 6) == 0) {
+    int base = 0;
+    for (int t0 = 0; t0 < n_tiles; t0 += 64) {
+      const int t = t0 + lane;
+      bool hit = false;
+      if (t < n_tiles && tile_image[t_first + t] == n) {
+        const int y1 = win[t * 4 + 0], y2 = win[t * 4 + 1], x1 = win[t * 4 + 2], x2 = win[t * 4 + 3];
+        hit = y1 < by0 + 4 && y2 > by0 && x1 < bx0 + 64 && x2 > bx0;
+      }
+      const unsigned long long m = __ballot(hit);
+      const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+      if (hit && pos < ST_MAXC) s_list[pos] = t;
+      base += __popcll(m);
+    }
+    if (lane == 0) s_count = base;
+  }
+  __syncthreads();
+  const int n_cand = s_count;
+  const bool use_list = n_cand <= ST_MAXC;
+  const int n_iter = use_list ? n_cand : n_tiles;
+  const int x = bx0 + lane;
+  const int y = __builtin_amdgcn_readfirstlane(by0 + (threadIdx.x >> 6));
+  if (y >= H) return;
+  const int64_t tile_sz = (int64_t)gh * gw;
+  float* canvas = canvases + off;
+  for (int q0 = 0; q0 < Q; q0 += ST_QC) {
+    float acc[ST_QC];
+#pragma unroll
+    for (int k = 0; k < ST_QC; ++k) acc[k] = 0.f;
+    float cnt = 0.f;
+    for (int it = 0; it < n_iter; ++it) {
+      const int t = use_list ? s_list[it] : it;
+      if (!use_list && tile_image[t_first + t] != n) continue;
+      const int y1 = win[t * 4 + 0], y2 = win[t * 4 + 1];
+      if (y < y1 || y >= y2) continue;
+      const int x1 = win[t * 4 + 2], x2 = win[t * 4 + 3];
+      if (x < x1 || x >= x2 || x >= W) continue;
+      int ya, yb, xa, xb; float wy0, wy1, wx0, wx1;
+      bilinear_tap(y - y1 + pad_t, gh, up_h, ya, yb, wy0, wy1);
+      bilinear_tap(x - x1 + pad_l, gw, up_w, xa, xb, wx0, wx1);
+      const float* base = tile_logits + ((int64_t)(t_first + t) * Q + q0) * tile_sz;
+#pragma unroll
+      for (int k = 0; k < ST_QC; ++k) {
+        if (q0 + k < Q) {
+          const float* p = base + (int64_t)k * tile_sz;
+          const float top = p[ya * gw + xa] * wx0 + p[ya * gw + xb] * wx1;
+          const float bot = p[yb * gw + xa] * wx0 + p[yb * gw + xb] * wx1;
+          acc[k] += top * wy0 + bot * wy1;
+        }
+      }
+      cnt += 1.f;
+    }
+    if (x < W) {
+#pragma unroll
+      for (int k = 0; k < ST_QC; ++k)
+        if (q0 + k < Q) canvas[(q0 + k) * plane + (int64_t)y * W + x] = cnt > 0.f ? acc[k] / cnt : 0.f;
+    }
+  }
+}
+
+// postprocess_kernel for N canvases, 256 output pixels per block: canvas n [Q,h,w] at canvas_offset[n]; its outputs are
+// labels [H,W] at out_offset[n] and probs [K,H,W] at K * out_offset[n].  When (H,W) != (h,w) the align_corners=False bilinear
+// resize of resize_bilinear_kernel is evaluated per output pixel (no resized canvas is written).  The arithmetic after the load is
+// postprocess_kernel's, so the outputs are bit-identical to sg_resize_bilinear + sg_postprocess per image.
+template <int QMAX>
+__global__ __launch_bounds__(256) void postprocess_multi_kernel(const float* __restrict__ canvases, const int32_t* __restrict__ canvas_hw,
+                                                                const int64_t* __restrict__ canvas_offset, const int32_t* __restrict__ out_hw,
+                                                                const int64_t* __restrict__ out_offset, const int64_t* __restrict__ block_prefix,
+                                                                int N, int64_t canvas_elems, int64_t out_pixels,
+                                                                const int32_t* __restrict__ query_idx, int Q, int K, float logit_scale,
+                                                                float prob_thd, int bg_idx, float* __restrict__ probs,
+                                                                int64_t* __restrict__ labels) {
+  const int n = image_of_block(block_prefix, N, blockIdx.x);
+  const int h = canvas_hw[2 * n], w = canvas_hw[2 * n + 1], H = out_hw[2 * n], W = out_hw[2 * n + 1];
+  const int64_t coff = canvas_offset[n], ooff = out_offset[n];
+  const int64_t hw = (int64_t)h * w, HW = (int64_t)H * W;
+  if (coff < 0 || coff + Q * hw > canvas_elems || ooff < 0 || ooff + HW > out_pixels) return;
+  const int64_t i = (blockIdx.x - block_prefix[n]) * 256 + threadIdx.x;
+  if (i >= HW) return;
+  const float* logits = canvases + coff;
+  const bool resize = h != H || w != W;
+  int ya = 0, yb = 0, xa = 0, xb = 0; float wy0 = 0.f, wy1 = 0.f, wx0 = 0.f, wx1 = 0.f;
+  if (resize) {
+    bilinear_tap((int)(i / W), h, H, ya, yb, wy0, wy1);
+    bilinear_tap((int)(i % W), w, W, xa, xb, wx0, wx1);
+  }
+  float v[QMAX];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int q = 0; q < QMAX; ++q)
+    if (q < Q) {
+      float l;
+      if (resize) {
+        // resize_bilinear_kernel's arithmetic exactly as it is compiled there, spelled out so that this kernel cannot contract it any
+        // other way.  Its channel loop is vectorised two channels at a time (v_pk_fma_f32: first product of each sum fused); an odd
+        // last channel runs through the loop's scalar remainder, which fuses the other product of `top` and rounds both products of
+        // the final blend.  Mirroring both keeps this bit-identical to sg_resize_bilinear for every Q (pinned by tests/test_gpu_batch.py
+        // for even and odd Q; a compiler that vectorised that loop differently would show up there).
+#pragma clang fp contract(off)
+        const float* p = logits + (int64_t)q * h * w;
+        if ((Q & 1) && q == Q - 1) {
+          const float top = __builtin_fmaf(p[ya * w + xb], wx1, p[ya * w + xa] * wx0);
+          const float bot = __builtin_fmaf(p[yb * w + xa], wx0, p[yb * w + xb] * wx1);
+          l = top * wy0 + bot * wy1;
+        } else {
+          const float top = __builtin_fmaf(p[ya * w + xa], wx0, p[ya * w + xb] * wx1);
+          const float bot = __builtin_fmaf(p[yb * w + xa], wx0, p[yb * w + xb] * wx1);
+          l = __builtin_fmaf(top, wy0, bot * wy1);
+        }
+        asm volatile("" : "+v"(l));     // opaque from here on, like a loaded value: the softmax below compiles as postprocess_kernel's
+      } else {
+        l = logits[q * hw + i];
+      }
+      v[q] = l * logit_scale; mx = fmaxf(mx, v[q]);
+    }
+  float sum = 0.f;
+#pragma unroll
+  for (int q = 0; q < QMAX; ++q)
+    if (q < Q) { v[q] = expf(v[q] - mx); sum += v[q]; }
+  float best = -INFINITY; int arg = 0;
+  float* pr = probs ? probs + K * ooff : nullptr;
+  for (int c = 0; c < K; ++c) {
+    float pc;
+    if (K == Q) {
+      pc = 0.f;
+#pragma unroll
+      for (int q = 0; q < QMAX; ++q) if (q == c) pc = v[q] / sum;
+    } else {
+      bool any_other = false;
+      float m = -INFINITY;
+#pragma unroll
+      for (int q = 0; q < QMAX; ++q)
+        if (q < Q) { if (query_idx[q] == c) m = fmaxf(m, v[q] / sum); else any_other = true; }
+      pc = any_other ? fmaxf(m, 0.f) : m;
+    }
+    if (pr) pr[c * HW + i] = pc;
+    if (pc > best) { best = pc; arg = c; }
+  }
+  if (best < prob_thd) arg = bg_idx;
+  labels[ooff + i] = arg;
+}
+
 // ---- label / confidence images (segmentor.py:501-531, 580-608) ---------------------------------------------------------
 // mask  = palette[clip(label, 0, K-1)]                                (_colorize_mask)
 // heat  = (g, 0, 255 - g), g = uint8(clip(nan_to_num(max_k probs), 0, 1) * 255)   (_to_colormap, the branch without OpenCV)
@@ -470,6 +647,39 @@ extern "C" int sg_postprocess(const float* logits, const int32_t* query_idx, int
   else
     hipLaunchKernelGGL(postprocess_kernel<PP_MAX_Q>, dim3((unsigned)cdiv(HW, 256)), dim3(256), 0, as_stream(s), logits, query_idx, Q, K, HW,
                        logit_scale, prob_thd, bg_idx, probs, labels);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_stitch_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh, int gw,
+                               int up_h, int up_w, int pad_t, int pad_l, const int32_t* image_hw, const int32_t* image_tiles,
+                               const int64_t* canvas_offset, const int64_t* block_prefix, int N, int64_t total_blocks, int64_t canvas_elems,
+                               float* canvases, sg_stream s) {
+  SG_REQUIRE(tile_logits && windows && tile_image && image_hw && image_tiles && canvas_offset && block_prefix && canvases,
+             "sg_stitch_multi: null pointer");
+  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && N > 0 && N <= T,
+             "sg_stitch_multi: bad shape T=%d Q=%d gh=%d gw=%d N=%d", T, Q, gh, gw, N);
+  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "sg_stitch_multi: total_blocks=%lld outside (0, 2^31)", (long long)total_blocks);
+  SG_REQUIRE(canvas_elems >= Q, "sg_stitch_multi: canvas_elems=%lld holds no canvas", (long long)canvas_elems);
+  hipLaunchKernelGGL(stitch_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q, gh, gw,
+                     up_h, up_w, pad_t, pad_l, image_hw, image_tiles, canvas_offset, block_prefix, N, canvas_elems, canvases);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_postprocess_multi(const float* canvases, const int32_t* canvas_hw, const int64_t* canvas_offset, const int32_t* out_hw,
+                                    const int64_t* out_offset, const int64_t* block_prefix, int N, int64_t total_blocks, int64_t canvas_elems,
+                                    int64_t out_pixels, const int32_t* query_idx, int Q, int K, float logit_scale, float prob_thd, int bg_idx,
+                                    float* probs, int64_t* labels, sg_stream s) {
+  SG_REQUIRE(canvases && canvas_hw && canvas_offset && out_hw && out_offset && block_prefix && query_idx && labels,
+             "sg_postprocess_multi: null pointer");
+  SG_REQUIRE(N > 0 && Q > 0 && Q <= PP_MAX_Q && K > 0 && K <= Q, "sg_postprocess_multi: N=%d Q=%d K=%d unsupported (Q <= %d)", N, Q, K, PP_MAX_Q);
+  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "sg_postprocess_multi: total_blocks=%lld outside (0, 2^31)", (long long)total_blocks);
+  SG_REQUIRE(canvas_elems >= Q && out_pixels > 0, "sg_postprocess_multi: canvas_elems=%lld out_pixels=%lld", (long long)canvas_elems,
+             (long long)out_pixels);
+  auto kern = Q <= 16 ? postprocess_multi_kernel<16> : postprocess_multi_kernel<PP_MAX_Q>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), canvases, canvas_hw, canvas_offset, out_hw, out_offset,
+                     block_prefix, N, canvas_elems, out_pixels, query_idx, Q, K, logit_scale, prob_thd, bg_idx, probs, labels);
   SG_LAUNCH_CHECK();
   return SG_OK;
 }

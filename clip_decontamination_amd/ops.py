@@ -304,6 +304,69 @@ def postprocess(logits, query_idx, num_classes: int, logit_scale: float, prob_th
     return probs, labels
 
 
+def _prefix(counts):
+    out = [0]
+    for c in counts:
+        out.append(out[-1] + int(c))
+    return out
+
+
+@on_tensor_device
+def stitch_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles):
+    """The canvases of N images in one launch (sg_stitch_multi).  tile_logits [T,Q,gh,gw]; windows [T,4] in each image's own
+    coordinates; tile_image [T] = image of each tile (0..N-1); image_hw [(H, W)] * N; image_tiles [(first, count)] * N.
+    -> (canvases: one flat f32 buffer, list of N views [Q,H,W] into it)."""
+    lib = _lib.load()
+    tile_logits = _f32(tile_logits)
+    _require_gpu(tile_logits)
+    dev = tile_logits.device
+    T, Q, gh, gw = tile_logits.shape
+    N = len(image_hw)
+    pix = _prefix(h * w for h, w in image_hw)
+    blocks = _prefix(-(-w // 64) * -(-h // 4) for h, w in image_hw)
+    canvases = torch.empty(Q * pix[-1], dtype=torch.float32, device=dev)
+    i32 = torch.tensor([list(hw) for hw in image_hw] + [list(ft) for ft in image_tiles], dtype=torch.int32).to(dev)
+    i64 = torch.tensor([Q * p for p in pix[:-1]] + blocks, dtype=torch.int64).to(dev)
+    windows = torch.as_tensor(windows, dtype=torch.int32).to(dev).contiguous()
+    tile_image = torch.as_tensor(tile_image, dtype=torch.int32).to(dev).contiguous()
+    check(lib.sg_stitch_multi(ptr(tile_logits), ptr(windows), ptr(tile_image), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1],
+                              ptr(i32), ptr(i32[N:]), ptr(i64), ptr(i64[N:]), N, blocks[-1], canvases.numel(), ptr(canvases), stream_ptr()),
+          "sg_stitch_multi")
+    views = [canvases[Q * pix[n]:Q * pix[n + 1]].view(Q, h, w) for n, (h, w) in enumerate(image_hw)]
+    return canvases, views
+
+
+@on_tensor_device
+def postprocess_multi(canvases, canvas_hw, query_idx, num_classes: int, logit_scale: float, prob_thd: float, bg_idx: int,
+                      out_hw=None, want_probs: bool = True, canvas_offsets=None):
+    """sg_postprocess_multi: N canvases [Q,h,w] in one flat buffer (packed back to back, or at ``canvas_offsets`` elements) ->
+    (list of probs [K,H,W] or None, list of labels int64 [1,H,W]); (H, W) = out_hw[n] (default: the canvas size) -- a different size
+    is the bilinear resize of sg_resize_bilinear, fused."""
+    lib = _lib.load()
+    _require_gpu(canvases)
+    if canvases.dtype != torch.float32 or not canvases.is_contiguous():
+        raise ValueError("postprocess_multi: canvases must be one contiguous f32 buffer")
+    dev = canvases.device
+    N = len(canvas_hw)
+    out_hw = list(canvas_hw) if out_hw is None else [tuple(s) for s in out_hw]
+    qi = query_idx.to(device=dev, dtype=torch.int32).contiguous()
+    Q, K = int(qi.numel()), int(num_classes)
+    if canvas_offsets is None:
+        canvas_offsets = [Q * p for p in _prefix(h * w for h, w in canvas_hw)[:-1]]
+    pix = _prefix(h * w for h, w in out_hw)
+    blocks = _prefix(-(-(h * w) // 256) for h, w in out_hw)
+    i32 = torch.tensor([list(hw) for hw in canvas_hw] + [list(hw) for hw in out_hw], dtype=torch.int32).to(dev)
+    i64 = torch.tensor(list(canvas_offsets) + pix[:-1] + blocks, dtype=torch.int64).to(dev)
+    labels = torch.empty(pix[-1], dtype=torch.int64, device=dev)
+    probs = torch.empty(K * pix[-1], dtype=torch.float32, device=dev) if want_probs else None
+    check(lib.sg_postprocess_multi(ptr(canvases), ptr(i32), ptr(i64), ptr(i32[N:]), ptr(i64[N:]), ptr(i64[2 * N:]), N, blocks[-1],
+                                   canvases.numel(), pix[-1], ptr(qi), Q, K, float(logit_scale), float(prob_thd), int(bg_idx), ptr(probs),
+                                   ptr(labels), stream_ptr()), "sg_postprocess_multi")
+    lab = [labels[pix[n]:pix[n + 1]].view(1, h, w) for n, (h, w) in enumerate(out_hw)]
+    prb = [probs[K * pix[n]:K * pix[n + 1]].view(K, h, w) if want_probs else None for n, (h, w) in enumerate(out_hw)]
+    return prb, lab
+
+
 @on_tensor_device
 def render_maps(labels, probs, palette, want_mask: bool = True, want_heat: bool = True):
     """labels int64 [1,H,W] or [H,W], probs [K,H,W], palette uint8 [K,3] -> (mask uint8 [H,W,3] | None, heat uint8 [H,W,3] | None)."""

@@ -8,7 +8,8 @@ point instead, only the tiles that straddle a canvas-band edge.  Every rank stit
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
+from dataclasses import dataclass, field
+from typing import Callable, List, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -188,6 +189,122 @@ def launch_chunks(n_tiles: int, limit: int) -> List[Tuple[int, int]]:
         out.append((a, b))
         a = b
     return out
+
+
+@dataclass
+class FlushGroup:
+    """A run of whole images of one tile-size group, images [img_lo, img_hi) and tiles [tile_lo, tile_hi) of the group, whose tile
+    logits and canvases are computed, stitched and handed on together; ``chunks`` = the tower launches over its tiles."""
+    img_lo: int
+    img_hi: int
+    tile_lo: int
+    tile_hi: int
+    chunks: List[Tuple[int, int]]
+
+
+@dataclass
+class TileSizeGroup:
+    """The images of a packed batch that share a window size (every window of one image has the same size, ``tile_windows``).
+    Tiles are image-major, raster order within an image; ``tile_image`` holds indices into the planner's ``shapes``."""
+    tile_hw: Tuple[int, int]
+    images: List[int]
+    shapes: List[Tuple[int, int]]
+    grids: List[Tuple[int, int]]
+    windows: List[Tuple[int, int, int, int]]
+    tile_image: List[int]
+    first_tile: List[int]
+    n_tiles: List[int]
+    chunks: List[Tuple[int, int]]
+    canvas_offsets: List[int]            # pixel offset of each image's canvas: prefix sum of H*W over ``images`` (len + 1 entries)
+    flush: List[FlushGroup] = field(default_factory=list)
+
+
+def plan_images(shapes: Sequence[Tuple[int, int]], stride, crop, patch: int, tiles_per_launch: int,
+                tile_bytes: Union[int, Callable[[Tuple[int, int]], int]] = 0, pixel_bytes: int = 0,
+                flush_bytes: Optional[int] = None) -> List[TileSizeGroup]:
+    """Packs the sliding windows of images of any sizes into equal tower launches (pure host logic, no device).
+
+    Images are grouped by window size (a launch shares one tile shape; images smaller than the crop form their own groups), groups
+    in order of first appearance.  Within a group the windows of all its images are concatenated and cut by ``launch_chunks``,
+    freely across image boundaries.  The group is further cut into flush groups: runs of whole images whose tile logits
+    (``tile_bytes`` per tile, or a function of the tile size) plus canvases (``pixel_bytes`` per pixel) stay within ``flush_bytes``;
+    an image that alone exceeds the bound is a flush group of its own.  ``patch`` is checked, the windows do not depend on it."""
+    stride = (stride, stride) if isinstance(stride, int) else tuple(stride)
+    crop = (crop, crop) if isinstance(crop, int) else tuple(crop)
+    if int(patch) <= 0:
+        raise ValueError(f"patch must be positive, got {patch}")
+    groups: dict = {}
+    for i, (H, W) in enumerate(shapes):
+        H, W = int(H), int(W)
+        if H <= 0 or W <= 0:
+            raise ValueError(f"image {i} has an empty shape {(H, W)}")
+        wins = tile_windows(H, W, stride, crop)
+        th, tw = wins[0][1] - wins[0][0], wins[0][3] - wins[0][2]
+        g = groups.get((th, tw))
+        if g is None:
+            g = groups[(th, tw)] = TileSizeGroup((th, tw), [], [], [], [], [], [], [], [], [0])
+        g.first_tile.append(len(g.windows))
+        g.n_tiles.append(len(wins))
+        g.images.append(i)
+        g.shapes.append((H, W))
+        g.grids.append((max(H - crop[0] + stride[0] - 1, 0) // stride[0] + 1, max(W - crop[1] + stride[1] - 1, 0) // stride[1] + 1))
+        g.windows.extend(wins)
+        g.tile_image.extend([i] * len(wins))
+        g.canvas_offsets.append(g.canvas_offsets[-1] + H * W)
+    out = list(groups.values())
+    for g in out:
+        g.chunks = launch_chunks(len(g.windows), tiles_per_launch)
+        tb = int(tile_bytes(g.tile_hw)) if callable(tile_bytes) else int(tile_bytes)
+        a, used = 0, 0
+        for k in range(len(g.images)):
+            H, W = g.shapes[k]
+            need = tb * g.n_tiles[k] + int(pixel_bytes) * H * W
+            if k > a and flush_bytes is not None and used + need > flush_bytes:
+                g.flush.append(_flush_group(g, a, k, tiles_per_launch))
+                a, used = k, 0
+            used += need
+        g.flush.append(_flush_group(g, a, len(g.images), tiles_per_launch))
+    return out
+
+
+def _flush_group(g: TileSizeGroup, a: int, b: int, tiles_per_launch: int) -> FlushGroup:
+    t0 = g.first_tile[a]
+    t1 = g.first_tile[b - 1] + g.n_tiles[b - 1]
+    return FlushGroup(a, b, t0, t1, [(t0 + i, t0 + j) for i, j in launch_chunks(t1 - t0, tiles_per_launch)])
+
+
+def pack_scenes(scenes, device, fill=None) -> Tuple[torch.Tensor, List[Tuple[int, int]]]:
+    """Images for a packed launch -> (one batch buffer, [(H, W)] per image).  A batch tensor ([B,3,H,W] f32 / [B,H,W,3] u8) is used in
+    place; a list of u8 [H,W,3] or f32 [3,H,W] images of any sizes is copied once into a buffer padded to the largest size (tiles
+    address it through ``scene_stride``).  The padding is never read -- windows stay inside each image -- and is left uninitialised
+    unless ``fill`` is given."""
+    if torch.is_tensor(scenes) and scenes.dim() == 4:
+        u8 = scenes.dtype == torch.uint8
+        buf = scenes if u8 else scenes.float()
+        buf = buf.to(device).contiguous()
+        H, W = (buf.shape[1], buf.shape[2]) if u8 else (buf.shape[2], buf.shape[3])
+        return buf, [(int(H), int(W))] * buf.shape[0]
+    scenes = [scenes] if torch.is_tensor(scenes) else list(scenes)
+    if not scenes:
+        raise ValueError("no images to segment")
+    u8 = scenes[0].dtype == torch.uint8
+    if any((s.dtype == torch.uint8) != u8 for s in scenes):
+        raise ValueError("packed images must all be u8 [H,W,3] or all f32 [3,H,W]")
+    if any(s.dim() != 3 or (s.shape[-1] if u8 else s.shape[0]) != 3 for s in scenes):
+        raise ValueError("packed images are u8 [H,W,3] or f32 [3,H,W]")
+    shapes = [(int(s.shape[0]), int(s.shape[1])) if u8 else (int(s.shape[1]), int(s.shape[2])) for s in scenes]
+    Hm, Wm = max(h for h, _ in shapes), max(w for _, w in shapes)
+    B = len(scenes)
+    shape = (B, Hm, Wm, 3) if u8 else (B, 3, Hm, Wm)
+    buf = torch.empty(shape, dtype=torch.uint8 if u8 else torch.float32, device=device)
+    if fill is not None:
+        buf.fill_(fill)
+    for b, (s, (h, w)) in enumerate(zip(scenes, shapes)):
+        if u8:
+            buf[b, :h, :w] = s
+        else:
+            buf[b, :, :h, :w] = s
+    return buf, shapes
 
 
 class SegPipeline:
@@ -419,6 +536,111 @@ class SegPipeline:
                                          padded_hw=(tile_hw[0] + t + b, tile_hw[1] + l + r))
         lg = ops.cosine_logits(tok, cls, self.text, f, self.cls_token_lambda if cls is not None else 0.0)
         return lg.reshape(n_real, self.num_queries, gh, gw)
+
+    # -- packed slide inference: the windows of many images in shared launches ----------------------------------------
+    flush_bytes = 4 << 30       # bound on the tile logits + canvases of one flush group (plan_images)
+    pack_fill = None            # value written into a ragged pack buffer's padding (None: left uninitialised -- it is never read)
+
+    def _packed_canvases(self, scenes, stride, crop):
+        """Yields (image indices, flat canvas buffer, its [Q,H,W] views) per flush group: the packed tower over the group's chunks,
+        cross-tile fusion per image, the head, and one sg_stitch_multi launch."""
+        if self.tile_group is not None:
+            raise ValueError("packed inference shards images over ranks, not tiles: with tile_group set use forward_slide / "
+                             "segment_scene per image")
+        buf, shapes = pack_scenes(scenes, self.device, self.pack_fill)
+        P, Q = self.visual.cfg.patch, self.num_queries
+
+        def tile_bytes(thw):
+            l, r, t, b = compute_padsize(thw[0], thw[1], P)
+            gh, gw = (thw[0] + t + b) // P, (thw[1] + l + r) // P
+            S = 256 if self.upsampler is not None else 1
+            tok = gh * gw * self.visual.cfg.embed_dim * 4 if self.cross_tile_fusion is not None else 0
+            return 4 * Q * gh * gw * S + tok
+
+        groups = plan_images(shapes, stride, crop, P, self.tiles_per_launch, tile_bytes, 4 * Q, self.flush_bytes)
+        for g in groups:
+            th, tw = g.tile_hw
+            l, r, t, b = compute_padsize(th, tw, P)
+            for f in g.flush:
+                tl = self._packed_tile_logits(buf, g, f)
+                imgs = range(f.img_lo, f.img_hi)
+                local = [k - f.img_lo for k in imgs for _ in range(g.n_tiles[k])]
+                canvases, views = ops.stitch_multi(tl, g.windows[f.tile_lo:f.tile_hi], local, (th + t + b, tw + l + r), (t, l),
+                                            [g.shapes[k] for k in imgs], [(g.first_tile[k] - f.tile_lo, g.n_tiles[k]) for k in imgs])
+                yield [g.images[k] for k in imgs], canvases, views
+
+    def _packed_tile_logits(self, buf, g: TileSizeGroup, f: FlushGroup) -> torch.Tensor:
+        v = self.visual
+        P = v.cfg.patch
+        th, tw = g.tile_hw
+        l, r, t, b = compute_padsize(th, tw, P)
+        gh, gw = (th + t + b) // P, (tw + l + r) // P
+        opts = v.forward_opts(self.model_type, self.ignore_residual, self.apply_similarity_enhancement, self.apply_layer_fusion,
+                              self.layer_fusion_lambda)
+        win = torch.tensor(g.windows[f.tile_lo:f.tile_hi], dtype=torch.int32, device=self.device).reshape(-1, 4)
+        sidx = torch.tensor(g.tile_image[f.tile_lo:f.tile_hi], dtype=torch.int32, device=self.device)
+
+        def head(tok, cls, w, si):
+            tok, fct = self._pre_head(tok, cls)
+            if self.upsampler is not None:
+                return self.upsampler.logits(tok, cls, buf, w, (th, tw), (l, t), (gh, gw), self.text, fct, self.cls_token_lambda, si,
+                                             padded_hw=(th + t + b, tw + l + r))
+            lg = ops.cosine_logits(tok, cls, self.text, fct, self.cls_token_lambda if cls is not None else 0.0)
+            return lg.reshape(w.shape[0], self.num_queries, gh, gw)
+
+        fused = [k for k in range(f.img_lo, f.img_hi) if g.grids[k][0] * g.grids[k][1] > 1]
+        if self.cross_tile_fusion is None or not fused:
+            outs = []
+            for i, j in f.chunks:
+                a, z = i - f.tile_lo, j - f.tile_lo
+                cls, tok = v.forward_tiles(buf, win[a:z], (th, tw), opts, sidx[a:z])
+                outs.append(head(tok, cls, win[a:z], sidx[a:z]))
+            return torch.cat(outs, 0) if len(outs) > 1 else outs[0]
+        # boundary fusion couples the tiles of one image's grid: the packed tower first, then the fusion on each image's contiguous
+        # token slice, then the head over the whole flush group
+        cls_all, tok_all = [], []
+        for i, j in f.chunks:
+            c_, t_ = v.forward_tiles(buf, win[i - f.tile_lo:j - f.tile_lo], (th, tw), opts, sidx[i - f.tile_lo:j - f.tile_lo])
+            cls_all.append(c_); tok_all.append(t_)
+        tok = torch.cat(tok_all, 0)
+        cf = self.cross_tile_fusion
+        for k in fused:
+            a = g.first_tile[k] - f.tile_lo
+            n = g.n_tiles[k]
+            tok[a:a + n] = ops.cross_tile_fusion(tok[a:a + n], g.grids[k][0], g.grids[k][1], gh, gw, cf.get("cache_boundary_width", 2),
+                                                 cf.get("fusion_mode", "weighted"), cf.get("fusion_strength", 0.3))
+        cls = None if cls_all[0] is None else torch.cat(cls_all, 0)
+        return head(tok, cls, win, sidx)
+
+    def forward_slide_many(self, scenes, stride, crop, ori_shapes=None) -> List[torch.Tensor]:
+        """``forward_slide`` for many images with their windows packed into shared tower launches (``plan_images``).  scenes: a list
+        of u8 [H,W,3] / f32 [3,H,W] images of any sizes, or one batch tensor.  Returns logits [1,Q,h,w] per image, (h, w) =
+        ori_shapes[i] or the image size.  In f32 these equal ``forward_slide`` per image bit for bit; in the 2-byte modes a different
+        launch size may take a different GEMM path, i.e. differ by 2-byte rounding."""
+        out: List[Optional[torch.Tensor]] = []
+        for idx, _, views in self._packed_canvases(scenes, stride, crop):
+            out.extend([None] * (max(idx) + 1 - len(out)))
+            for k, c in zip(idx, views):
+                ori = None if ori_shapes is None or ori_shapes[k] is None else tuple(ori_shapes[k])
+                out[k] = (ops.resize_bilinear(c, ori) if ori is not None and ori != tuple(c.shape[1:]) else c).unsqueeze(0)
+        return out
+
+    def segment_scenes(self, scenes, stride, crop, want_probs: bool = False, ori_shapes=None):
+        """The whole packed path to labels: per flush group one sg_stitch_multi and one sg_postprocess_multi launch (the resize to
+        ``ori_shapes`` fused into the latter).  -> list of labels [1,H,W], or (list of probs [K,H,W], list of labels) with
+        ``want_probs``."""
+        probs: List[Optional[torch.Tensor]] = []
+        labels: List[Optional[torch.Tensor]] = []
+        for idx, canvases, views in self._packed_canvases(scenes, stride, crop):
+            chw = [tuple(c.shape[1:]) for c in views]
+            ohw = [chw[n] if ori_shapes is None or ori_shapes[k] is None else tuple(ori_shapes[k]) for n, k in enumerate(idx)]
+            prb, lab = ops.postprocess_multi(canvases, chw, self.query_idx, self.num_classes, self.logit_scale, self.prob_thd, self.bg_idx,
+                                             ohw, want_probs)
+            for lst, vals in ((probs, prb), (labels, lab)):
+                lst.extend([None] * (max(idx) + 1 - len(lst)))
+                for k, x in zip(idx, vals):
+                    lst[k] = x
+        return (probs, labels) if want_probs else labels
 
     # -- reference forward_feature (whole image / explicit logit size) ------------------------------------------
     def forward_feature(self, img: torch.Tensor, logit_size=None) -> torch.Tensor:

@@ -245,6 +245,9 @@ class _HipSegmentorBase(_Base):
         if type(img) == list:
             img = img[0].unsqueeze(0)
         pipe = self._pipeline()
+        if getattr(self, "pack_images", False) and img.shape[0] > 1:        # opt-in: the windows of all B images in shared launches
+            ori = [tuple(m["ori_shape"][:2]) for m in img_metas] if img_metas is not None else None
+            return torch.cat(pipe.forward_slide_many(img.float(), stride, crop_size, ori), 0)
         outs = []
         for b in range(img.shape[0]):
             ori = img_metas[b]["ori_shape"][:2] if img_metas is not None else None
@@ -265,6 +268,35 @@ class _HipSegmentorBase(_Base):
         else:
             seg_logits = self.forward_feature(inputs, batch_img_metas[0]["ori_shape"])
         return self.postprocess_result(seg_logits, data_samples)
+
+    @torch.no_grad()
+    def predict_many(self, inputs, data_samples=None):
+        """``predict`` for many images with their sliding windows packed into shared tower launches and one stitch + one post-process
+        launch per flush group (SegPipeline.segment_scenes).  inputs: a list of [3,H,W] images of any sizes or a [B,3,H,W] batch.
+        Fills each data sample exactly as ``predict`` does (seg_logits, pred_sem_seg, result_dir / heatmap_dir PNGs) and returns
+        them; with ``data_samples=None`` returns one label map [1,H,W] per image.  In f32 the results equal ``predict`` per image bit
+        for bit; in the 2-byte modes a larger launch may take a different GEMM path and differ by 2-byte rounding."""
+        batch = torch.is_tensor(inputs)
+        imgs = inputs.float() if batch else [x[0].float() if x.dim() == 4 else x.float() for x in inputs]
+        n = imgs.shape[0] if batch else len(imgs)
+        if data_samples is not None and len(data_samples) != n:
+            raise ValueError(f"predict_many: {n} images but {len(data_samples)} data samples")
+        if self.slide_crop <= 0:                             # whole-image inference (forward_feature) has no windows to pack
+            if data_samples is None:
+                return [self.predict(imgs[i][None], None) for i in range(n)]
+            for i in range(n):
+                self.predict(imgs[i][None], [data_samples[i]])
+            return data_samples
+        pipe = self._pipeline()
+        if data_samples is None:
+            return pipe.segment_scenes(imgs, self.slide_stride, self.slide_crop, want_probs=False)
+        ori = [tuple(ds.metainfo["ori_shape"][:2]) for ds in data_samples]
+        probs, labels = pipe.segment_scenes(imgs, self.slide_stride, self.slide_crop, want_probs=True, ori_shapes=ori)
+        for i, ds in enumerate(data_samples):
+            ds.set_data({"seg_logits": PixelData(**{"data": probs[i]}), "pred_sem_seg": PixelData(**{"data": labels[i]})})
+            if getattr(self, "result_dir", None) or getattr(self, "heatmap_dir", None):
+                self._write_maps(probs[i], labels[i], ds, i)
+        return data_samples
 
     def postprocess_result(self, seg_logits, data_samples):
         """Reference segmentor.py:475-499: class probabilities [K,H,W] + labels [1,H,W] per image."""
@@ -344,7 +376,7 @@ class SegmentorEx(_HipSegmentorBase):
                  similarity_enhancement_cfg=None, result_dir=None, heatmap_dir=None,
                  # -- drop-in extras (see module docstring) --
                  checkpoint=None, text_features=None, text_encoder=None, precision="f16x2", synthetic_ok=False, tiles_per_launch=None,
-                 tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None):
+                 tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, pack_images=False):
         data_preprocessor = SegDataPreProcessor(mean=list(Wt.PIXEL_MEAN), std=list(Wt.PIXEL_STD), bgr_to_rgb=True)
         super().__init__(data_preprocessor=data_preprocessor)
         if model_type == "GEM":
@@ -376,6 +408,7 @@ class SegmentorEx(_HipSegmentorBase):
             c.update(outlier_suppression_cfg or {})
             visual.outlier_suppressor = OutlierSuppressionModule(top_k=c["top_k"])
         self.result_dir, self.heatmap_dir = result_dir, heatmap_dir
+        self.pack_images = _to_bool(pack_images)                          # predict / forward_slide with B > 1 on the packed path
 
 
 class Segmentor(_HipSegmentorBase):
@@ -386,7 +419,8 @@ class Segmentor(_HipSegmentorBase):
                  logit_scale=50, slide_stride=112, slide_crop=224, cls_token_lambda=0, bg_idx=0, apply_sim_feat_up=True,
                  sim_feat_up_cfg=dict(model_name="jbu_one", model_path="your/model/path"),
                  checkpoint=None, text_features=None, text_encoder=None, precision="f16x2", synthetic_ok=False, tiles_per_launch=None,
-                 tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, apply_outlier_suppression=False, outlier_suppression_cfg=None):
+                 tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, apply_outlier_suppression=False, outlier_suppression_cfg=None,
+                 pack_images=False):
         data_preprocessor = SegDataPreProcessor(mean=list(Wt.PIXEL_MEAN), std=list(Wt.PIXEL_STD), bgr_to_rgb=True)
         super().__init__(data_preprocessor=data_preprocessor)
         if model_type == "GEM" and cls_token_lambda != 0:
@@ -398,6 +432,7 @@ class Segmentor(_HipSegmentorBase):
         # opt-in extra: kwargs of the reference's CrossTileFusion (cross_tile_fusion.py:24-60), which the reference never calls (R2)
         self.cross_tile_fusion_cfg = cross_tile_fusion_cfg
         self.output_cls_token = cls_token_lambda != 0
+        self.pack_images = _to_bool(pack_images)                          # predict / forward_slide with B > 1 on the packed path
         self.apply_similarity_enhancement = False
         # opt-in extra (BASELINE configs[2]: "GEM self-self attn + outlier_suppression" in ONE forward).  The reference cannot run that
         # composition (SegmentorEx crashes on GEM and this class has no refiners); the definition built here -- detection on the

@@ -184,6 +184,28 @@ int sg_resize_bilinear(const float* src, int C, int h, int w, float* dst, int H,
  *   logits [Q,H,W]; query_idx int32 [Q]; probs [K,H,W] f32 (may be NULL); labels int64 [H,W]. */
 int sg_postprocess(const float* logits, const int32_t* query_idx, int Q, int K, int H, int W, float logit_scale,
                    float prob_thd, int bg_idx, float* probs, int64_t* labels, sg_stream s);
+/* ---- multi-canvas head: the images of a packed batch in one launch each ------------------------------------------------------
+ * sg_stitch_multi replaces segmentor.py:388-391,436-447 for N images at once: the tiles of image n are [first, first + count) of the
+ * call's tile list (image-major), windows are in that image's own coordinates and tile_image[t] names the image of tile t; its canvas
+ * [Q,H,W] is written at canvas_offset[n] (elements) of `canvases`.  All tiles of one call share gh, gw, up_h, up_w, pad_t, pad_l (one
+ * tile size).  The grid is flattened over (image, 64 x 4 pixel block): block_prefix [N+1] = exclusive prefix sum of
+ * ceil(W/64) * ceil(H/4), total_blocks = block_prefix[N].  Each canvas is bit-identical to sg_stitch on that image alone.
+ *   tile_logits [T,Q,gh,gw] f32, windows int32 [T][4], tile_image int32 [T], image_hw int32 [N][2] (H,W), image_tiles int32 [N][2]
+ *   (first, count), canvas_offset int64 [N], block_prefix int64 [N+1] -- all device memory; canvas_elems = size of `canvases`.
+ *   HBM-bound, write-once: reads the tile logits (~1x, overlapping windows re-read through L2) and writes Q*sum(H*W)*4 bytes. */
+int sg_stitch_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh, int gw,
+                    int up_h, int up_w, int pad_t, int pad_l, const int32_t* image_hw, const int32_t* image_tiles,
+                    const int64_t* canvas_offset, const int64_t* block_prefix, int N, int64_t total_blocks, int64_t canvas_elems,
+                    float* canvases, sg_stream s);
+/* sg_postprocess_multi replaces segmentor.py:449 + 475-489 for N canvases at once: canvas n [Q,h,w] at canvas_offset[n] ->
+ * labels int64 [H,W] at out_offset[n] and (probs != NULL) probs f32 [K,H,W] at K * out_offset[n], where (H,W) = out_hw[n] is the
+ * image's ori_shape.  When it differs from the canvas the align_corners=False bilinear resize is evaluated per output pixel (no
+ * resized canvas is written).  Bit-identical to sg_resize_bilinear + sg_postprocess per image.  block_prefix [N+1] = exclusive prefix
+ * sum of ceil(H*W/256); canvas_elems / out_pixels = sizes of `canvases` / `labels`.  Reads Q*h*w*4 B, writes (8 + 4K) B per pixel. */
+int sg_postprocess_multi(const float* canvases, const int32_t* canvas_hw, const int64_t* canvas_offset, const int32_t* out_hw,
+                         const int64_t* out_offset, const int64_t* block_prefix, int N, int64_t total_blocks, int64_t canvas_elems,
+                         int64_t out_pixels, const int32_t* query_idx, int Q, int K, float logit_scale, float prob_thd, int bg_idx,
+                         float* probs, int64_t* labels, sg_stream s);
 /* Label / confidence images of postprocess_result (segmentor.py:501-531): mask_rgb [H,W,3] = palette[clip(label)] (_colorize_mask,
  * :580-590); heat_rgb [H,W,3] = (g, 0, 255-g) with g = uint8(clip(max_k probs, 0, 1) * 255) (_to_colormap without OpenCV, :604-608;
  * OpenCV's JET table is not reproduced).  Either output may be NULL. */
