@@ -47,6 +47,7 @@ SIGNATURES = {
     "sg_version": (I, []),
     "sg_profile_enable": (I, [I]),
     "sg_profile_disable": (I, []),
+    "sg_gemm_persist_last_kstep": (I, []),
     "sg_set_gemm_config": (I, [I]),
     "sg_profile_read": (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(L), C.POINTER(L)]),
     "sg_create": (I, [C.POINTER(P), I, C.POINTER(VitDesc)]),

@@ -454,6 +454,8 @@ extern "C" int sg_set_gemm_config(int cfg) {
   return SG_OK;
 }
 extern "C" int sg_profile_disable(void) { g_prof.on = false; return SG_OK; }
+// K step in elements (64: gemm_bf16_persist_k64, 32: gemm_bf16_persist) of the calling thread's last persistent bf16 / f16 GEMM launch; 0 = none yet.
+extern "C" int sg_gemm_persist_last_kstep(void) { return gemm_persist_last_kstep(); }
 // category: 0 bf16 GEMM (non-persistent tile variants), 1 fused attention, 2 f32 GEMM, 3 the persistent bf16 GEMM (all instantiations), 4 fp8 GEMM,
 // 5 / 6 the persistent GEMM's folded-LayerNorm consumer / producer instantiations alone.  Call after the stream
 // has been synchronised.

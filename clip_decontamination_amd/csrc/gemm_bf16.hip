@@ -856,6 +856,8 @@ static int launch_pp32(const GemmBf16Args& a, hipStream_t s) {
   return SG_OK;
 }
 
+static thread_local int g_gemm_config = -1;                // -1 = pick per shape (tuning override, per calling thread)
+int get_gemm_config() { return g_gemm_config; }
 static thread_local int g_persist_grid_cap = 0;             // tuning (sg_set_gemm_config(2000 + n)): at most n workgroups for the persistent kernel (0 = one per CU)
 static thread_local int g_gemm_order = -1;                 // tuning (sg_set_gemm_config(1000 + v)): -1 automatic N-group size, 0 raster order, v > 0 forced N-group size
 // ---- persistent ping-pong: the production kernel for the large ViT linears ---------------------------------------------------------
@@ -1266,6 +1268,207 @@ __global__ __launch_bounds__(512) void gemm_bf16_persist(GemmBf16Args a, int act
 #undef SG_PS_SYNC
 }
 
+// ---- persistent ping-pong on 128-byte K steps: the production kernel for the large 2-byte linears -------------------------------------
+// gemm_bf16_persist's output tiling, epilogue forms, tile orders and blockIdx.y batching on gemm_fp8_persist's data movement.  A K step is
+// 64 elements = 128 bytes per row, so every LDS-DMA piece is 8 rows x 128 B: whole lines, where the 32-element kernel's 16 rows x 64 B
+// pieces touch 16 lines half each and request the other halves one K tile (32 KiB of traffic through the L1) later.
+// LDS, all 160 KiB: the A ring has 2 slots, the W ring 3 (32 KiB each, the 128-byte image of gemm_bf16_ring<BKT = 64>: chunk ^ ((row >> 1) & 7),
+// applied on the source side).  The hand-off rules, the tile switch and the prologue are gemm_fp8_persist's, comment for comment.
+// Two phases per K step, 32 MFMAs (512 cycles) each:
+//   READ0(s): W fragments of both K halves (kept for both phases) + A rows 0-63 of the group's half; issue A_g(s+1).   MFMA0(s): 4 x 4 x 2.
+//   READ1(s): A rows 64-127; issue this group's rows of W(s+2+g).                                                     MFMA1(s): the same.
+// Per wave and K step: 8 LDS-DMA pieces and 24 ds_read_b128 per 64 MFMAs.
+// Arithmetic: every accumulator gets its K 0-31 MFMA and then its K 32-63 one, with read_frag32's lane -> K-chunk mapping (chunk h * 4 +
+// lane / 16 of K half h), so its MFMA sequence is the one the 32-element kernel issues and the results are bit-identical to that kernel's
+// (tuning code 38 runs it).  Look-ahead is 3 K steps: K / 64 >= 4 keeps every load within the next output tile.  Operand rows must be
+// shorter than 2^21 elements: byte offsets inside a 256-row tile are 32-bit (checked by the dispatch).
+template <bool F16, int EPI = 0, int SPEC = 0>
+__global__ __launch_bounds__(512) void gemm_bf16_persist_k64(GemmBf16Args a, int act, int c_bf16) {
+  constexpr int PBM = 256, PBN = 256, KB = 128;                          // K step in bytes (64 elements)
+  constexpr int SLOT = 256 * KB;                                         // 32 KiB
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  char* ldsA = lds;                                                      // 2 slots
+  char* ldsW = lds + 2 * SLOT;                                           // 3 slots
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int g = wave >> 2, wi = wave & 3;
+  const int tiles_n = (a.N + PBN - 1) / PBN, tiles_m = (a.M + PBM - 1) / PBM;
+  const int nwg = tiles_m * tiles_n;
+  const int q8 = nwg >> 3, r8 = nwg & 7;
+  const int z = blockIdx.y;
+  const char* A = reinterpret_cast<const char*>(a.A + (int64_t)z * a.strideA);
+  const char* W = reinterpret_cast<const char*>(a.W + (int64_t)z * a.strideW);
+  const int64_t lda_b = a.lda * 2, ldw_b = a.ldw * 2;                    // row strides in bytes
+  const int nt = a.K / 64;
+  // tile order (a.ngroup > 0): XCD x = blockIdx.x & 7 owns M tiles [mlo, mlo + mcnt) and walks its mcnt * tiles_n tiles N-group by N-group
+  const int NG = a.ngroup;
+  const int wpx = (int)gridDim.x >> 3, wx = (int)blockIdx.x >> 3, xc = (int)blockIdx.x & 7;
+  const int mq8 = tiles_m >> 3, mr8 = tiles_m & 7;
+  const int mlo = xc * mq8 + (xc < mr8 ? xc : mr8), mcnt = mq8 + (xc < mr8 ? 1 : 0), xcnt = mcnt * tiles_n;
+  const int my_tiles = NG > 0 ? (xcnt - wx + wpx - 1) / wpx : (nwg - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int total = my_tiles * nt;                                       // length of this workgroup's K-step stream
+
+  const int srow = lane >> 3, cpos = lane & 7;
+  // pieces are 8 rows apart and start at a multiple of 32 rows, so the swizzle term depends on the lane and on the parity of the piece only
+  const int swz_e = (cpos ^ (srow >> 1)) << 4, swz_o = (cpos ^ (4 + (srow >> 1))) << 4;
+  struct Src { const char* Ab; const char* Wb; int m0, n0; };            // 64-bit tile bases (wave-uniform)
+  const int ra0 = 128 * g + 32 * wi + srow, rw0 = 64 * wi + 32 * g + srow;   // this lane's first piece row inside any tile
+  auto make_src = [&](int j) {
+    Src sp;
+    if (NG > 0) {
+      int Lx = wx + j * wpx;                                             // index inside this XCD's tile set
+      Lx = Lx < xcnt ? Lx : xcnt - 1;
+      const int gsz = mcnt * NG, ngroups = (tiles_n + NG - 1) / NG;
+      int grp = Lx / gsz; grp = grp < ngroups - 1 ? grp : ngroups - 1;
+      const int rem = Lx - grp * gsz;
+      const int ncols = grp == ngroups - 1 ? tiles_n - grp * NG : NG;
+      sp.m0 = (mlo + rem / ncols) * PBM; sp.n0 = (grp * NG + rem % ncols) * PBN;
+    } else {
+      const int v = (int)blockIdx.x + j * (int)gridDim.x;                // virtual id; XCD x = v & 7 walks a contiguous chunk of tile ids
+      const int xcd = v & 7, seq = v >> 3;
+      int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + seq;
+      tile = tile < nwg ? tile : nwg - 1;
+      sp.m0 = (tile / tiles_n) * PBM; sp.n0 = (tile % tiles_n) * PBN;
+    }
+    sp.Ab = A + (int64_t)sp.m0 * lda_b; sp.Wb = W + (int64_t)sp.n0 * ldw_b;
+    return sp;
+  };
+  Src cur = make_src(0);
+  Src nxt = make_src(my_tiles > 1 ? 1 : 0);
+  int cur_end = nt;                                                      // stream index where `nxt` begins
+  const int lda_i = (int)lda_b, ldw_i = (int)ldw_b;
+  auto load_a = [&](int u) {                                             // this wave's pieces of A_g(u)
+    if (u >= total) return;
+    const bool nx = u >= cur_end;
+    const Src& sp = nx ? nxt : cur;
+    const int kt = nx ? u - cur_end : u - (cur_end - nt);
+    const int rmax = a.M - 1 - sp.m0;                                    // rows past the edge re-read the last row (never stored)
+    char* base = ldsA + (u & 1) * SLOT + (128 * g + 32 * wi) * KB;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      int r = ra0 + 8 * p; r = r < rmax ? r : rmax;
+      const int off = r * lda_i + ((p & 1) ? swz_o : swz_e) + kt * KB;
+      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(sp.Ab + off), (lds_ptr_t)(base + p * 8 * KB), 16, 0, 0);
+    }
+  };
+  auto load_w = [&](int u) {                                             // this wave's rows of W(u)
+    if (u >= total) return;
+    const bool nx = u >= cur_end;
+    const Src& sp = nx ? nxt : cur;
+    const int kt = nx ? u - cur_end : u - (cur_end - nt);
+    const int rmax = a.N - 1 - sp.n0;
+    char* base = ldsW + (u % 3) * SLOT + (64 * wi + 32 * g) * KB;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      int r = rw0 + 8 * p; r = r < rmax ? r : rmax;
+      const int off = r * ldw_i + ((p & 1) ? swz_o : swz_e) + kt * KB;
+      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(sp.Wb + off), (lds_ptr_t)(base + p * 8 * KB), 16, 0, 0);
+    }
+  };
+#define SG_P64_SYNC()                                \
+  do {                                               \
+    __builtin_amdgcn_sched_barrier(0);               \
+    __builtin_amdgcn_s_barrier();                    \
+    __builtin_amdgcn_sched_barrier(0);               \
+  } while (0)
+
+  // prologue: A(0), W(0), W(1) from everybody, W(2) from group 1 (group 0 issues its rows of W(2) in READ1(0)).  Group 1 retires its rows of
+  // W(1) here as well: group 0 reads them in READ0(1), which runs while group 1 is in MFMA1(0), before group 1's first wait in the loop.
+  load_a(0); load_w(0); load_w(1);
+  if (g == 1) { load_w(2); if (2 < total) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
+  else { if (1 < total) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
+  SG_P64_SYNC();
+  if (g == 1) SG_P64_SYNC();
+
+  f32x4 acc[8][4];
+  bf16x8 fa[2][4], fw[2][4];                                             // [K half][fragment]
+  int s = 0;
+  for (int j = 0; j < my_tiles; ++j) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) acc[i][jj] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    int kt = 0;
+    // One K step.  STEADY: every piece this step requests (A(s+1), W(s+2+g)) belongs to the current output tile -- no source select, no
+    // end-of-stream test; the last three steps of a tile take the general form (measured: +1.0 % on the bench line against the general form
+    // throughout, which is 2-4 % faster on the run-time epilogue form alone)
+    auto kstep = [&](auto steady_tag) {
+      constexpr bool STEADY = decltype(steady_tag)::value;
+      const char* tA = ldsA + (s & 1) * SLOT;
+      const char* tW = ldsW + (s % 3) * SLOT;
+      // READ0(s): W fragments (kept for both phases) + A rows 0-63 of the group's half; issue A_g(s+1)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) fw[h][jj] = read_frag(tW, 64 * wi + 16 * jj + (lane & 15), h * 4 + (lane >> 4));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) fa[h][i] = read_frag(tA, 128 * g + 16 * i + (lane & 15), h * 4 + (lane >> 4));
+      }
+      if constexpr (STEADY) {
+        const int rmax = a.M - 1 - cur.m0;
+        char* base = ldsA + ((s + 1) & 1) * SLOT + (128 * g + 32 * wi) * KB;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          int r = ra0 + 8 * p; r = r < rmax ? r : rmax;
+          __builtin_amdgcn_global_load_lds((gbl_ptr_t)(cur.Ab + (r * lda_i + ((p & 1) ? swz_o : swz_e) + (kt + 1) * KB)), (lds_ptr_t)(base + p * 8 * KB), 16, 0, 0);
+        }
+      } else load_a(s + 1);
+      SG_P64_SYNC();
+      // MFMA0(s): K half 0 of every accumulator, then K half 1
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) acc[i][jj] = mfma_16x16x32<F16>(fw[h][jj], fa[h][i], acc[i][jj]);
+      __builtin_amdgcn_s_setprio(0);
+      SG_P64_SYNC();
+      // READ1(s): A rows 64-127; issue this group's rows of W(s+2) / W(s+3)
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) fa[h][i] = read_frag(tA, 128 * g + 64 + 16 * i + (lane & 15), h * 4 + (lane >> 4));
+      const int uw = s + 2 + g;
+      if constexpr (STEADY) {
+        const int rmax = a.N - 1 - cur.n0;
+        char* base = ldsW + (uw % 3) * SLOT + (64 * wi + 32 * g) * KB;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          int r = rw0 + 8 * p; r = r < rmax ? r : rmax;
+          __builtin_amdgcn_global_load_lds((gbl_ptr_t)(cur.Wb + (r * ldw_i + ((p & 1) ? swz_o : swz_e) + (kt + 2 + g) * KB)), (lds_ptr_t)(base + p * 8 * KB), 16, 0, 0);
+        }
+      } else load_w(uw);
+      SG_P64_SYNC();
+      // MFMA1(s)
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int jj = 0; jj < 4; ++jj) acc[4 + i][jj] = mfma_16x16x32<F16>(fw[h][jj], fa[h][i], acc[4 + i][jj]);
+      __builtin_amdgcn_s_setprio(0);
+      if (STEADY || uw < total) wait_vmcnt<4>(); else wait_vmcnt<0>();   // all but the W pieces just issued
+      SG_P64_SYNC();
+      ++kt; ++s;
+    };
+    for (; kt + 3 < nt; ) kstep(std::true_type{});
+    for (; kt < nt; ) kstep(std::false_type{});
+    // ---- tile end ----
+    if (g == 0) SG_P64_SYNC();                                           // align: every read of this tile's last K step has retired
+    {
+      float* pbase = reinterpret_cast<float*>(ldsA + ((s - 1) & 1) * SLOT);    // the consumed A slot: 8 patches of 8 rows x 68 floats (+pad), then
+      epilogue_store8<8, 4, F16, EPI, SPEC>(acc, a, act, c_bf16, z, cur.m0 + 128 * g, cur.n0 + 64 * wi, pbase + wave * 576, lane,   // 1 KiB
+                                            pbase + 8 * 576 + wave * 256);                                                          // per wave
+    }
+    cur = nxt; cur_end += nt;
+    if (j + 2 < my_tiles) nxt = make_src(j + 2);
+    SG_P64_SYNC();                                                       // the A slot used as patch is refilled from READ0 of the next step on
+    if (g == 1 && j + 1 < my_tiles) SG_P64_SYNC();                       // re-stagger
+  }
+#undef SG_P64_SYNC
+}
+
 
 
 // Epilogue of the persistent fp8 kernel.  Same patch transposition as epilogue_store8, but de-quantisation (acc * row_scale[m] *
@@ -1447,9 +1650,10 @@ __global__ __launch_bounds__(512) void gemm_fp8_persist(GemmBf16Args a, int act,
     __builtin_amdgcn_sched_barrier(0);               \
   } while (0)
 
-  // prologue: A(0), W(0), W(1) from everybody, W(2) from group 1 (group 0 issues its rows of W(2) in READ1(0))
+  // prologue: A(0), W(0), W(1) from everybody, W(2) from group 1 (group 0 issues its rows of W(2) in READ1(0)).  Group 1 retires its rows of
+  // W(1) here as well: group 0 reads them in READ0(1), which runs while group 1 is in MFMA1(0), before group 1's first wait in the loop.
   load_a(0); load_w(0); load_w(1);
-  if (g == 1) { load_w(2); if (2 < total) wait_vmcnt<8>(); else if (1 < total) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
+  if (g == 1) { load_w(2); if (2 < total) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
   else { if (1 < total) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
   SG_F8_SYNC();
   if (g == 1) SG_F8_SYNC();
@@ -1627,9 +1831,10 @@ __global__ __launch_bounds__(512) void gemm_h2_persist(GemmBf16Args a, int act, 
     __builtin_amdgcn_sched_barrier(0);               \
   } while (0)
 
-  // prologue: A(0), W(0), W(1) from everybody, W(2) from group 1 (group 0 issues its rows of W(2) in READ1(0))
+  // prologue: A(0), W(0), W(1) from everybody, W(2) from group 1 (group 0 issues its rows of W(2) in READ1(0)).  Group 1 retires its rows of
+  // W(1) here as well: group 0 reads them in READ0(1), which runs while group 1 is in MFMA1(0), before group 1's first wait in the loop.
   load_a(0); load_w(0); load_w(1);
-  if (g == 1) { load_w(2); if (2 < total) wait_vmcnt<8>(); else if (1 < total) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
+  if (g == 1) { load_w(2); if (2 < total) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
   else { if (1 < total) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
   SG_H2_SYNC();
   if (g == 1) SG_H2_SYNC();
@@ -1726,26 +1931,34 @@ static int launch_h2_persist(const GemmBf16Args& h, hipStream_t s) {
   return SG_OK;
 }
 
+// The persistent kernel of a launch: gemm_bf16_persist_k64 (128-byte K steps) when K % 64 == 0, K / 64 >= 4 and the operand rows are
+// shorter than 2^21 elements (its 32-bit in-tile offsets); otherwise, and under tuning code 38 (the same-process baseline), the
+// 32-element gemm_bf16_persist.  Both compute the same bits.
+using PersistKern = void (*)(GemmBf16Args, int, int);
+template <bool F16, int EPI, int SPEC>
+static PersistKern persist_kernel(bool k64) { return k64 ? gemm_bf16_persist_k64<F16, EPI, SPEC> : gemm_bf16_persist<F16, EPI, SPEC>; }
+static thread_local int g_persist_kstep = 0;              // K step of the calling thread's last persistent launch (sg_gemm_persist_last_kstep)
+int gemm_persist_last_kstep() { return g_persist_kstep; }
 static int launch_persist(const GemmBf16Args& a, hipStream_t s) {
-  const size_t lds = 4 * (256 + 256) * 32 * 2;
+  const bool k64 = g_gemm_config != 38 && a.K % 64 == 0 && a.K / 64 >= 4 && a.lda < (1 << 21) && a.ldw < (1 << 21);
+  const size_t lds = k64 ? 5 * 256 * 128 : 4 * (256 + 256) * 32 * 2;   // 160 KiB (A ring 2 + W ring 3 slots) / 128 KiB (4 slots)
   // instantiation: epilogue form (plain / folded-LayerNorm consumer / producer) x compile-time specialisation of the hot combinations
-  using Kern = void (*)(GemmBf16Args, int, int);
-  Kern kern;
+  PersistKern kern;
   if (a.ln_stats) {                                         // consumer: 2-byte output, activation per layer kind
-    kern = a.act == ACT_NONE ? (a.f16 ? gemm_bf16_persist<true, 1, 1> : gemm_bf16_persist<false, 1, 1>)
-         : a.act == ACT_QUICK_GELU ? (a.f16 ? gemm_bf16_persist<true, 1, 2> : gemm_bf16_persist<false, 1, 2>)
-                                   : (a.f16 ? gemm_bf16_persist<true, 1, 3> : gemm_bf16_persist<false, 1, 3>);
+    kern = a.act == ACT_NONE ? (a.f16 ? persist_kernel<true, 1, 1>(k64) : persist_kernel<false, 1, 1>(k64))
+         : a.act == ACT_QUICK_GELU ? (a.f16 ? persist_kernel<true, 1, 2>(k64) : persist_kernel<false, 1, 2>(k64))
+                                   : (a.f16 ? persist_kernel<true, 1, 3>(k64) : persist_kernel<false, 1, 3>(k64));
   } else if (a.copy16) {                                    // producer: f32 output + residual, no activation
     SG_REQUIRE(a.residual && a.act == ACT_NONE, "gemm_bf16: the folded-LayerNorm producer form is a residual GEMM without activation");
-    kern = a.f16 ? gemm_bf16_persist<true, 2, 1> : gemm_bf16_persist<false, 2, 1>;
+    kern = a.f16 ? persist_kernel<true, 2, 1>(k64) : persist_kernel<false, 2, 1>(k64);
   } else if (a.c_is_bf16 && !a.residual && !a.rowdot && a.act == ACT_NONE) {
-    kern = a.f16 ? gemm_bf16_persist<true, 0, 1> : gemm_bf16_persist<false, 0, 1>;
+    kern = a.f16 ? persist_kernel<true, 0, 1>(k64) : persist_kernel<false, 0, 1>(k64);
   } else if (!a.c_is_bf16 && a.residual && !a.rowdot && a.act == ACT_NONE) {
-    kern = a.f16 ? gemm_bf16_persist<true, 0, 4> : gemm_bf16_persist<false, 0, 4>;
+    kern = a.f16 ? persist_kernel<true, 0, 4>(k64) : persist_kernel<false, 0, 4>(k64);
   } else if (a.rowdot && a.rowdot_res_bf16 && !a.f16 && a.act == ACT_NONE) {
-    kern = gemm_bf16_persist<false, 0, 5>;
+    kern = persist_kernel<false, 0, 5>(k64);
   } else {
-    kern = a.f16 ? gemm_bf16_persist<true, 0, 0> : gemm_bf16_persist<false, 0, 0>;
+    kern = a.f16 ? persist_kernel<true, 0, 0>(k64) : persist_kernel<false, 0, 0>(k64);
   }
   SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
   const int n_cu = device_cu_count();
@@ -1766,11 +1979,10 @@ static int launch_persist(const GemmBf16Args& a, hipStream_t s) {
     if (ng >= 1 && tiles_n > ng) b.ngroup = g_gemm_order > 0 ? g_gemm_order : ng;
   }
   hipLaunchKernelGGL(kern, dim3(grid, (unsigned)a.batch), dim3(512), lds, s, b, a.act, a.c_is_bf16);
+  g_persist_kstep = k64 ? 64 : 32;
   return SG_OK;
 }
 
-static thread_local int g_gemm_config = -1;                // -1 = pick per shape (tuning override, per calling thread)
-int get_gemm_config() { return g_gemm_config; }
 // A launch whose 256 x 256 tiles would not even fill half the CUs (one or two image tiles per call: the reference's own tile-by-tile loop)
 // runs on the 128 x 128 ring kernel instead -- four times the workgroups, measured 1.4-2x faster there; tuning code 36 switches this off.
 static bool few_tiles(int M, int N) {
@@ -1907,7 +2119,8 @@ int gemm_bf16(const GemmBf16Args& a, hipStream_t s) {
     if (a.ln_stats) SG_REQUIRE(a.ln_c && a.alpha == 1.f && a.c_is_bf16 && !a.residual && !a.rowdot && ((((uintptr_t)a.ln_c) & 15) == 0) && ((((uintptr_t)a.ln_stats) & 7) == 0), "gemm_bf16: ln_stats needs ln_c and alpha 1");
   }
   int cfg = g_gemm_config;
-  if (cfg == 33 || cfg == 34 || cfg == 36 || cfg == 37) cfg = -1;                    // tuning codes read by capi.hip (MX hand-off / LayerNorm folding off), not tile configurations
+  if (cfg == 33 || cfg == 34 || cfg == 36 || cfg == 37 || cfg == 38) cfg = -1;       // tuning codes read by capi.hip (MX hand-off / LayerNorm folding off)
+                                                                                  // or by launch_persist (38: the 32-element K step), not tile configurations
   if (a.rowdot || ln_fold) cfg = 30;
   if (a.res_half) {                                          // 2-byte residual: the small-tile kernel's run-time epilogue only
     SG_REQUIRE(vec && a.residual && a.c_is_bf16 && !a.rowdot && !ln_fold && a.ldr % 8 == 0, "gemm_bf16: res_half needs a 2-byte C, N %% 8 == 0 and ldr %% 8 == 0");

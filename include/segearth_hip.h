@@ -132,9 +132,12 @@ int sg_version(void);
  *           Read after synchronising.  The state belongs to the calling thread (enable, launch and read on one thread). */
 int sg_profile_enable(int capacity);
 int sg_profile_disable(void);
+int sg_gemm_persist_last_kstep(void);   /* K step in elements of the calling thread's last persistent bf16 / f16 GEMM launch: 64 (gemm_bf16_persist_k64),
+                                         * 32 (gemm_bf16_persist: K / 64 < 4 or tuning code 38), 0 = none yet */
 int sg_set_gemm_config(int cfg);   /* tuning hook (calling thread only): bf16 GEMM tile variant, -1 = automatic; 33 = fp8 MLP without the MXFP8
                                     * hand-off, 34 = LayerNorm as its own pass (no folding), 36 = no small-launch dispatch (a few-tile GEMM stays on the
-                                    * persistent kernel); 1000+ = tile order of the persistent kernel */
+                                    * persistent kernel), 38 = the persistent kernel with 32-element K steps (same results as the default 64-element
+                                    * one); 1000+ = tile order of the persistent kernel */
 int sg_profile_read(int category, double* total_ms, double* total_flops, int64_t* launches, int64_t* dropped);
 
 /* ---- context and weights ------------------------------------------------------------------
