@@ -48,6 +48,7 @@ SIGNATURES = {
     "sg_profile_enable": (I, [I]),
     "sg_profile_disable": (I, []),
     "sg_gemm_persist_last_kstep": (I, []),
+    "sg_gemm_last_kernel": (C.c_char_p, []),
     "sg_set_gemm_config": (I, [I]),
     "sg_profile_read": (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(L), C.POINTER(L)]),
     "sg_create": (I, [C.POINTER(P), I, C.POINTER(VitDesc)]),
@@ -74,6 +75,7 @@ SIGNATURES = {
     "sg_similarity_map": (I, [P, L, I, I, I, I, F, I, I, P, P, Z, P]),
     "sg_op_linear": (I, [P, P, P, P, P, I, I, I, I, I, P, Z, P]),
     "sg_gemm_bf16_raw": (I, [P, P, P, P, P, I, I, I, I, I, P]),
+    "sg_gemm_raw": (I, [I, P, P, P, P, P, I, I, I, I, I, I, P]),
     "sg_gemm_fp8_raw": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P]),
     "sg_op_ln_chain_scratch_bytes": (Z, [I, I, I, I]),
     "sg_op_ln_chain": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, Z, P]),

@@ -232,12 +232,14 @@ static int run_attention(int bf16, const void* qkv, int B, int N, int D, int H, 
 }
 
 // y = act(A . W^T + bias) (+ residual) in the context's compute dtype; out_f32 forces an f32 C.
+// batch > 1 (2-byte / two-plane only): `batch` contiguous problems, strides M lda / N K / M ldc elements (the residual shares C's).
 static int linear(int bf16, const void* A, int64_t lda, const void* W, const float* bias, const float* residual, void* C,
-                  int64_t ldc, bool c_f32, int M, int N, int K, int act, hipStream_t s) {
+                  int64_t ldc, bool c_f32, int M, int N, int K, int act, hipStream_t s, int batch = 1) {
   if (bf16) {
     GemmBf16Args g{};
     g.A = (const bf16_t*)A; g.lda = lda; g.W = (const bf16_t*)W; g.ldw = K; g.bias = bias; g.residual = residual; g.ldr = ldc;
-    g.C = C; g.ldc = ldc; g.c_is_bf16 = c_f32 ? 0 : 1; g.M = M; g.N = N; g.K = K; g.batch = 1; g.act = act; g.alpha = 1.f;
+    g.C = C; g.ldc = ldc; g.c_is_bf16 = c_f32 ? 0 : 1; g.M = M; g.N = N; g.K = K; g.batch = batch; g.act = act; g.alpha = 1.f;
+    if (batch > 1) { g.strideA = (int64_t)M * lda; g.strideW = (int64_t)N * K; g.strideC = (int64_t)M * ldc; }
     g.f16 = bf16 == HK_F16; g.h2 = bf16 == HK_F16X2;
     return gemm_bf16(g, s);
   }
@@ -428,6 +430,15 @@ extern "C" int sg_gemm_bf16_raw(const void* A, const void* W, const float* bias,
   SG_REQUIRE(A && W && C, "sg_gemm_bf16_raw: null pointer");
   return linear(HK_BF16, A, K, W, bias, residual, C, N, !c_is_bf16, M, N, K, act, as_stream(st));
 }
+// The same for every 2-byte / two-plane storage (SG_PREC_BF16 / F16 / F16X2: A [batch][M][K], W [batch][N][K] in the precision's operand
+// storage, two-plane as common.h's 32-byte groups; K % 64 == 0, two-plane K % 32 == 0), C f32 or (c_packed) that storage, `batch` contiguous problems.
+extern "C" int sg_gemm_raw(int precision, const void* A, const void* W, const float* bias, const float* residual, void* C, int M, int N, int K,
+                           int batch, int act, int c_packed, sg_stream st) {
+  SG_REQUIRE(A && W && C, "sg_gemm_raw: null pointer");
+  SG_REQUIRE(precision == SG_PREC_BF16 || precision == SG_PREC_F16 || precision == SG_PREC_F16X2, "sg_gemm_raw: bad precision %d", precision);
+  SG_REQUIRE(batch >= 1 && (c_packed == 0 || c_packed == 1), "sg_gemm_raw: bad batch %d / c_packed %d", batch, c_packed);
+  return linear(hk_of_precision(precision), A, K, W, bias, residual, C, N, !c_packed, M, N, K, act, as_stream(st), batch);
+}
 // fp8 (OCP e4m3) GEMM on caller-quantised operands: A8 [M,K] with per-row scales sa [M], W8 [N,K] with per-row scales sw [N], K % 128 == 0.
 extern "C" int sg_gemm_fp8_raw(const void* A8, const float* sa, const void* W8, const float* sw, const float* bias, const float* residual,
                                void* C, int M, int N, int K, int act, int c_is_bf16, sg_stream st) {
@@ -456,6 +467,8 @@ extern "C" int sg_set_gemm_config(int cfg) {
 extern "C" int sg_profile_disable(void) { g_prof.on = false; return SG_OK; }
 // K step in elements (64: gemm_bf16_persist_k64, 32: gemm_bf16_persist) of the calling thread's last persistent bf16 / f16 GEMM launch; 0 = none yet.
 extern "C" int sg_gemm_persist_last_kstep(void) { return gemm_persist_last_kstep(); }
+// "<family> grid=<x> ngroup=<n>" of the calling thread's last GEMM launch through the 2-byte / two-plane / fp8 GEMM entry (thread-local text).
+extern "C" const char* sg_gemm_last_kernel(void) { return gemm_last_kernel(); }
 // category: 0 bf16 GEMM (non-persistent tile variants), 1 fused attention, 2 f32 GEMM, 3 the persistent bf16 GEMM (all instantiations), 4 fp8 GEMM,
 // 5 / 6 the persistent GEMM's folded-LayerNorm consumer / producer instantiations alone.  Call after the stream
 // has been synchronised.

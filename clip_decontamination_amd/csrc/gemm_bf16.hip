@@ -700,6 +700,18 @@ __global__ __launch_bounds__(512) void gemm_bf16_pingpong(GemmBf16Args a, int ac
   }
 }
 
+// The calling thread's last launch through gemm_bf16() (sg_gemm_last_kernel): a static kernel-family name, the grid's x extent (tiles, or
+// workgroups of a persistent kernel) and the persistent kernel's N-group size.  Three stores per launch; the text is made only when queried.
+struct GemmLaunchRecord { const char* name; int grid; int ngroup; };
+static thread_local GemmLaunchRecord g_last_launch = {nullptr, 0, 0};
+static inline void note_launch(const char* name, int64_t grid, int ngroup = 0) { g_last_launch = {name, (int)grid, ngroup}; }
+const char* gemm_last_kernel() {
+  static thread_local char text[96];
+  if (!g_last_launch.name) return "none";
+  snprintf(text, sizeof text, "%s grid=%d ngroup=%d", g_last_launch.name, g_last_launch.grid, g_last_launch.ngroup);
+  return text;
+}
+
 static int launch_pingpong(const GemmBf16Args& a, int vec, hipStream_t s) {
   const size_t lds = 2 * (256 + 256) * BK * 2;
   auto kern = a.h2 ? gemm_bf16_pingpong<true, true> : a.f16 ? gemm_bf16_pingpong<true> : gemm_bf16_pingpong<false>;
@@ -707,6 +719,7 @@ static int launch_pingpong(const GemmBf16Args& a, int vec, hipStream_t s) {
   const int64_t tiles = cdiv(a.M, 256) * cdiv(a.N, 256);
   SG_REQUIRE(tiles < (1ll << 31) && a.batch < 65536, "gemm_bf16: grid too large");
   hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)a.batch), dim3(512), lds, s, a, a.act, a.c_is_bf16, vec);
+  note_launch(a.h2 ? "h2_pingpong" : "pingpong", tiles);
   return SG_OK;
 }
 
@@ -853,12 +866,13 @@ static int launch_pp32(const GemmBf16Args& a, hipStream_t s) {
   const int64_t tiles = cdiv(a.M, 256) * cdiv(a.N, 256);
   SG_REQUIRE(tiles < (1ll << 31) && a.batch < 65536, "gemm_bf16: grid too large");
   hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)a.batch), dim3(512), lds, s, a, a.act, a.c_is_bf16, 1);
+  note_launch(ABLATE ? "pp32_ablation" : "pp32", tiles);
   return SG_OK;
 }
 
 static thread_local int g_gemm_config = -1;                // -1 = pick per shape (tuning override, per calling thread)
 int get_gemm_config() { return g_gemm_config; }
-static thread_local int g_persist_grid_cap = 0;             // tuning (sg_set_gemm_config(2000 + n)): at most n workgroups for the persistent kernel (0 = one per CU)
+static thread_local int g_persist_grid_cap = 0;             // tuning (sg_set_gemm_config(2000 + n)): at most n workgroups for every persistent kernel (0 = one per CU)
 static thread_local int g_gemm_order = -1;                 // tuning (sg_set_gemm_config(1000 + v)): -1 automatic N-group size, 0 raster order, v > 0 forced N-group size
 // ---- persistent ping-pong: the production kernel for the large ViT linears ---------------------------------------------------------
 // gemm_bf16_pp32's ring (K tile 32, four slots) with three changes measured to matter:
@@ -1736,8 +1750,10 @@ static int launch_fp8_persist(const GemmBf16Args& a, hipStream_t s) {
   const int n_cu = device_cu_count();
   const int64_t tiles = cdiv(a.M, 256) * cdiv(a.N, 256);
   SG_REQUIRE(tiles < (1ll << 31), "gemm_fp8: grid too large");
-  const unsigned grid = (unsigned)(tiles < n_cu ? tiles : n_cu);
+  unsigned grid = (unsigned)(tiles < n_cu ? tiles : n_cu);
+  if (g_persist_grid_cap > 0 && grid > (unsigned)g_persist_grid_cap) grid = (unsigned)g_persist_grid_cap;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, a, a.act, a.c_is_bf16);
+  note_launch("fp8_persist", grid);
   return SG_OK;
 }
 
@@ -1926,8 +1942,10 @@ static int launch_h2_persist(const GemmBf16Args& h, hipStream_t s) {
   const int n_cu = device_cu_count();
   const int64_t tiles = cdiv(h.M, 256) * cdiv(h.N, 256);
   SG_REQUIRE(tiles < (1ll << 31), "gemm_h2: grid too large");
-  const unsigned grid = (unsigned)(tiles < n_cu ? tiles : n_cu);
+  unsigned grid = (unsigned)(tiles < n_cu ? tiles : n_cu);
+  if (g_persist_grid_cap > 0 && grid > (unsigned)g_persist_grid_cap) grid = (unsigned)g_persist_grid_cap;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, h, h.act, h.c_is_bf16);
+  note_launch("h2_persist", grid);
   return SG_OK;
 }
 
@@ -1980,6 +1998,7 @@ static int launch_persist(const GemmBf16Args& a, hipStream_t s) {
   }
   hipLaunchKernelGGL(kern, dim3(grid, (unsigned)a.batch), dim3(512), lds, s, b, a.act, a.c_is_bf16);
   g_persist_kstep = k64 ? 64 : 32;
+  note_launch(k64 ? "persist_k64" : "persist_k32", grid, b.ngroup);
   return SG_OK;
 }
 
@@ -1991,12 +2010,24 @@ static bool few_tiles(int M, int N) {
 bool gemm_bf16_ln_fold_ok(int M, int N, int K) { return M >= 1024 && N >= 512 && N % 64 == 0 && K % 32 == 0 && K / 32 >= 4; }
 bool gemm_bf16_prefers_persistent(int M, int N) { return M >= 1024 && N >= 512 && !few_tiles(M, N); }
 void set_gemm_config(int c) {
-  if (c >= 2000) { g_persist_grid_cap = c - 2000; return; } // experiment: fewer persistent workgroups than CUs (2000 = no cap)
+  if (c >= 2000) { g_persist_grid_cap = c - 2000; return; } // experiment / tests: fewer persistent workgroups than CUs, every persistent kernel (2000 = no cap)
   if (c >= 1000) { g_gemm_order = c - 1001; return; }      // 1000 -> -1 (automatic), 1001 -> 0 (raster), 1001 + v -> N-group size v
   g_gemm_config = c;
 }
 
 
+// kernel-family name of a ring configuration (sg_gemm_last_kernel); ring128 is the default small-launch tile, the others are tuning codes
+template <int BM_, int BN_, int STAGES, int ABLATE, int BKT, bool FP8, bool SPLIT>
+constexpr const char* ring_name() {
+  if (ABLATE) return "ring_ablation";
+  if (FP8) return BM_ == 128 ? "fp8_ring128" : "fp8_ring256x256";
+  if (SPLIT) return "h2_ring128";
+  if (BKT == 32) return BM_ == 128 ? "ring128x256_k32" : "ring256x128_k32";
+  if (BM_ == 128 && BN_ == 128) return STAGES == 2 ? "ring128" : "ring128x128_s3";
+  if (BM_ == 256 && BN_ == 128) return STAGES == 2 ? "ring256x128" : "ring256x128_s3";
+  if (BM_ == 128 && BN_ == 256) return "ring128x256_s3";
+  return "ring256x256";
+}
 template <int BM_, int BN_, int WM, int WN, int STAGES, int ABLATE = 0, int BKT = 64, bool FP8 = false, bool F16 = false, bool MXA = false, int SPEC = 0, bool SPLIT = false>
 static int launch_ring(const GemmBf16Args& a, int vec, hipStream_t s) {
   auto kern = gemm_bf16_ring<BM_, BN_, WM, WN, STAGES, ABLATE, BKT, FP8, F16, MXA, SPEC, SPLIT>;
@@ -2005,6 +2036,7 @@ static int launch_ring(const GemmBf16Args& a, int vec, hipStream_t s) {
   const int64_t tiles = cdiv(a.M, BM_) * cdiv(a.N, BN_);
   SG_REQUIRE(tiles < (1ll << 31) && a.batch < 65536, "gemm_bf16: grid too large");
   hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)a.batch), dim3(WM * WN * 64), lds, s, a, a.act, a.c_is_bf16, vec);
+  note_launch(FP8 && (a.a_mx || a.c_mx) ? "fp8_mx_ring256x256" : ring_name<BM_, BN_, STAGES, ABLATE, BKT, FP8, SPLIT>(), tiles);
   return SG_OK;
 }
 
@@ -2096,6 +2128,7 @@ static int gemm_h2(const GemmBf16Args& a, hipStream_t s) {
 }
 
 int gemm_bf16(const GemmBf16Args& a, hipStream_t s) {
+  g_last_launch = {nullptr, 0, 0};
   SG_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0 && a.batch > 0, "gemm_bf16: empty problem M=%d N=%d K=%d", a.M, a.N, a.K);
   if (a.h2) return gemm_h2(a, s);
   if (a.fp8) return gemm_fp8(a, s);
@@ -2186,6 +2219,7 @@ int gemm_bf16(const GemmBf16Args& a, hipStream_t s) {
     case 5: launch<ACT_GELU, true>(a, vec, grid, s); break;
     default: return fail(SG_ERR_INVALID, "gemm_bf16: bad act %d", a.act);
   }
+  note_launch("generic", tiles);
   prof_end(PROF_GEMM_BF16, s);
   SG_LAUNCH_CHECK();
   return SG_OK;

@@ -46,7 +46,8 @@ enum sg_precision {       /* arithmetic the ViT GEMMs / attention run in */
   SG_PREC_F16 = 3,        /* throughput mode on IEEE f16 operands (v_mfma_*_f16: the bf16 rate, 3 more mantissa bits): the reference's own
                              GPU arithmetic (segmentor.py:467 .half(), open_clip/model.py:142 fp32 LayerNorm).  f32 accumulate, f32
                              residual stream / LN / softmax statistics as in bf16 mode; stores saturate at +-65504 */
-  SG_PREC_F16X2 = 4,      /* parity AT SPEED: every GEMM / attention operand is held as two f16 planes x = hi + lo (22 significant bits) and every
+  SG_PREC_F16X2 = 4,      /* parity AT SPEED: every GEMM / attention operand is held as two f16 planes x = hi + lo (within max(2^-22 |x|,
+                             2^-25): 22 significant bits from |x| = 2^-3 up, below that the 2^-25 floor of lo's f16 subnormals) and every
                              product is issued as hi.hi + hi.lo + lo.hi on the f16 matrix pipe into one f32 accumulator -- the error of an f32
                              fmaf chain (tools/h2_probe.hip) at a third of the f16 MFMA rate instead of the 1/16 of the f32 MFMA.  f32 residual
                              stream / LayerNorm / softmax statistics, exact expf / erff activations.  Logits within 1e-3 of the reference's fp32 CPU
@@ -134,10 +135,16 @@ int sg_profile_enable(int capacity);
 int sg_profile_disable(void);
 int sg_gemm_persist_last_kstep(void);   /* K step in elements of the calling thread's last persistent bf16 / f16 GEMM launch: 64 (gemm_bf16_persist_k64),
                                          * 32 (gemm_bf16_persist: K / 64 < 4 or tuning code 38), 0 = none yet */
+const char* sg_gemm_last_kernel(void);   /* the calling thread's last launch through the 2-byte / two-plane / fp8 GEMM: "<family> grid=<x> ngroup=<n>"
+                                          * with family persist_k64, persist_k32, h2_persist, fp8_persist, pingpong, h2_pingpong, pp32, ring128, ring...,
+                                          * h2_ring128, fp8_ring128, fp8_ring256x256, fp8_mx_ring256x256 or generic; grid = workgroups (persistent) or tiles
+                                          * along x; ngroup = the persistent kernel's N-group size (0 = raster order); "none" when its last GEMM call
+                                          * launched nothing.  The text stays valid until the thread's next query. */
 int sg_set_gemm_config(int cfg);   /* tuning hook (calling thread only): bf16 GEMM tile variant, -1 = automatic; 33 = fp8 MLP without the MXFP8
                                     * hand-off, 34 = LayerNorm as its own pass (no folding), 36 = no small-launch dispatch (a few-tile GEMM stays on the
                                     * persistent kernel), 38 = the persistent kernel with 32-element K steps (same results as the default 64-element
-                                    * one); 1000+ = tile order of the persistent kernel */
+                                    * one); 1000+ = tile order of the persistent kernel; 2000 + n = at most n workgroups for every persistent
+                                    * kernel (2000 = one per CU) */
 int sg_profile_read(int category, double* total_ms, double* total_flops, int64_t* launches, int64_t* dropped);
 
 /* ---- context and weights ------------------------------------------------------------------
@@ -265,6 +272,11 @@ int sg_op_ln_chain(const float* A, const float* W1, const float* b1, float* x, c
 /* bf16 GEMM on caller-packed operands: A [M,K], W [N,K] bf16 (K % 64 == 0), C bf16 or f32 */
 int sg_gemm_bf16_raw(const void* A, const void* W, const float* bias, const float* residual, void* C, int M, int N, int K,
                      int act, int c_is_bf16, sg_stream s);
+/* The same GEMM for SG_PREC_BF16 / SG_PREC_F16 / SG_PREC_F16X2 operands in the precision's own storage (two-plane: groups of 8 elements as
+ * [8 hi f16][8 lo f16], 32 bytes): A [batch][M][K], W [batch][N][K] (K % 64 == 0; two-plane K % 32 == 0), C [batch][M][N] f32 or, with
+ * c_packed, in that storage; residual f32 [batch][M][N] (f32 C).  C = act(A.W^T + bias) (+ residual) per problem. */
+int sg_gemm_raw(int precision, const void* A, const void* W, const float* bias, const float* residual, void* C, int M, int N, int K,
+                int batch, int act, int c_packed, sg_stream s);
 /* fp8 (OCP e4m3, v_mfma_f32_16x16x128_f8f6f4) GEMM on quantised operands: C = act((A8 . W8^T) * sa[m] * sw[n] + bias) (+ residual);
  * A8 [M,K], W8 [N,K] bytes, K % 128 == 0; sg_quantize_rows_fp8 produces an operand and its per-row scales (absmax / 448). */
 int sg_gemm_fp8_raw(const void* A8, const float* sa, const void* W8, const float* sw, const float* bias, const float* residual, void* C,
