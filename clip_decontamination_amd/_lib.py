@@ -49,6 +49,7 @@ SIGNATURES = {
     "sg_profile_disable": (I, []),
     "sg_gemm_persist_last_kstep": (I, []),
     "sg_gemm_last_kernel": (C.c_char_p, []),
+    "sg_attention_last_kernel": (C.c_char_p, []),
     "sg_set_gemm_config": (I, [I]),
     "sg_profile_read": (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(L), C.POINTER(L)]),
     "sg_create": (I, [C.POINTER(P), I, C.POINTER(VitDesc)]),
@@ -82,6 +83,8 @@ SIGNATURES = {
     "sg_gemm_fp8_mx_raw": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P]),
     "sg_quantize_rows_fp8": (I, [P, L, I, P, P, P]),
     "sg_op_layernorm": (I, [P, P, P, P, I, I, F, P]),
+    "sg_attention_raw": (I, [I, P, P, P, P, P, P, L, L, P, L, L, I, I, I, I, I, I, I, F, P, P, F, L, P, P, I, P, P, P, L, L, F, P]),
+    "sg_attention_stats_raw": (I, [I, P, L, L, P, I, I, I, I, F, P, P, P]),
     "sg_op_attention_scratch_bytes": (Z, [I, I, I, I, I]),
     "sg_op_attention": (I, [P, I, I, I, I, I, P, F, P, P, P, I, P, Z, P]),
     "sg_adaptive_conv": (I, [P, P, I, I, I, I, I, P, P]),

@@ -520,12 +520,15 @@ static int launch_attn(const AttnArgs& a, hipStream_t s) {
                                      : (multi ? attn_kernel<DH, TS, 0, CAN_MULTI, AF16, true> : attn_kernel<DH, TS, 0, false, AF16, true>))
                           : (generic ? attn_kernel<DH, TS, 1, false, AF16, false> : attn_kernel<DH, TS, 0, false, AF16, false>);
   SG_REQUIRE(a.ctx || !multi, "attention: a log-sum-exp-only pass has one stream");
-  if (lds > 64 * 1024) SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
   const int64_t nqb = cdiv(a.N, QB);
-  const int64_t nblk = (generic && a.bias) ? ((a.B >= 16 && (a.H & 3) == 0) ? cdiv((int64_t)a.B, 8) * 8 * a.H * nqb     // whole images per XCD (see the kernel)
-                                                                              : cdiv((int64_t)a.B * nqb, 8) * 8 * a.H)
-                                           : cdiv((int64_t)a.H * a.B, 8) * 8 * nqb;
-  SG_REQUIRE(nblk < (1ll << 31), "attention: grid too large");
+  const int order = (generic && a.bias) ? ((a.B >= 16 && (a.H & 3) == 0) ? 2 : 1) : 0;        // the kernel's workgroup order
+  const int64_t nblk = order == 2 ? cdiv((int64_t)a.B, 8) * 8 * a.H * nqb     // whole images per XCD (see the kernel)
+                     : order == 1 ? cdiv((int64_t)a.B * nqb, 8) * 8 * a.H
+                                  : cdiv((int64_t)a.H * a.B, 8) * 8 * nqb;
+  SG_REQUIRE(nblk < (1ll << 31), "attention: grid too large");                 // every check before the first HIP call
+  if (lds > 64 * 1024) SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
+  note_attn_launch({"attn", AH2 ? HK_F16X2 : AF16 ? HK_F16 : HK_BF16, DH, TS, exper ? 2 : generic ? 1 : 0, (a.ctx && multi) ? 1 : 0, a.ctx ? 1 : 0, order,
+                    lds2 > 160 * 1024 ? 1 : 2, 0, nblk});
   dim3 grid((unsigned)nblk);
   // algorithmic FLOPs: 2*N*N*dh per (term score) + 2*N*N*dh per stream PV, per (image, head)
   const int streams = a.sum_scores ? 1 : a.n_terms;
@@ -542,7 +545,22 @@ int attention_h2_impl(const AttnArgs& a, hipStream_t s) {   // strides arrive in
 #elif SG_ATTN_F16
 int attention_f16_impl(const AttnArgs& a, hipStream_t s) {
 #else
+static thread_local AttnLaunchRecord g_attn_last = {nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+void note_attn_launch(const AttnLaunchRecord& r) { g_attn_last = r; }
+const char* attention_last_kernel() {
+  static thread_local char text[160];
+  const AttnLaunchRecord& r = g_attn_last;
+  static const char* kinds[4] = {"f32", "bf16", "f16", "h2"};
+  static const char* orders[3] = {"head", "qblock", "images"};
+  if (!r.name) return "none";
+  if (r.name[0] == 's') snprintf(text, sizeof text, "%s lph=%d kind=%s grid=%lld", r.name, r.lph, kinds[r.kind & 3], (long long)r.grid);
+  else snprintf(text, sizeof text, "%s dh=%d ts=%d gk=%d multi=%d pv=%d kind=%s order=%s nb=%d grid=%lld", r.name, r.dh, r.ts, r.gk, r.multi, r.pv,
+                kinds[r.kind & 3], orders[r.order % 3], r.nb, (long long)r.grid);
+  return text;
+}
+
 int attention_bf16(const AttnArgs& a, hipStream_t s) {
+  g_attn_last.name = nullptr;                               // a refused call leaves "none", not the previous launch
   if (a.h2) return attention_h2_impl(a, s);
   if (a.f16) return attention_f16_impl(a, s);
 #endif
@@ -652,11 +670,13 @@ __global__ __launch_bounds__(256) void attn_stats_fast_kernel(const bf16_t* __re
 int attention_stats(const void* qkv, int is_bf16, int64_t sb, int64_t st, const float* lse, int B, int N, int H, int dh,
                     float scale, float* attn_cls, float* attn_diag, hipStream_t s) {
   dim3 grid((unsigned)cdiv(N, 4), (unsigned)B);
+  g_attn_last.name = nullptr;
   const bool aligned = (sb % 8 == 0) && (st % 8 == 0) && ((((uintptr_t)qkv) & 15) == 0);
 #define SG_STATS_FAST(LPH, F)                                                                                                      \
   hipLaunchKernelGGL((attn_stats_fast_kernel<LPH, F>), grid, dim3(256), 0, s, (const bf16_t*)qkv, sb, st, lse, N, H, scale, attn_cls, attn_diag)
   if (is_bf16 && is_bf16 != HK_F16X2 && aligned && (dh == 32 || dh == 64 || dh == 128)) {
     const bool h = is_bf16 == HK_F16;
+    note_attn_launch({"stats_fast", is_bf16, dh, 0, 0, 0, 0, 0, 0, dh / 8, (int64_t)grid.x * grid.y});
     if (dh == 32) { if (h) SG_STATS_FAST(4, true); else SG_STATS_FAST(4, false); }
     else if (dh == 64) { if (h) SG_STATS_FAST(8, true); else SG_STATS_FAST(8, false); }
     else { if (h) SG_STATS_FAST(16, true); else SG_STATS_FAST(16, false); }
@@ -664,6 +684,7 @@ int attention_stats(const void* qkv, int is_bf16, int64_t sb, int64_t st, const 
     return SG_OK;
   }
 #undef SG_STATS_FAST
+  note_attn_launch({"stats_generic", is_bf16, dh, 0, 0, 0, 0, 0, 0, 0, (int64_t)grid.x * grid.y});
   if (is_bf16 == HK_F16X2) hipLaunchKernelGGL(attn_stats_kernel<h2_t>, grid, dim3(256), 0, s, (const h2_t*)qkv, sb, st, lse, N, H, dh, scale, attn_cls, attn_diag);
   else if (is_bf16 == HK_F16) hipLaunchKernelGGL(attn_stats_kernel<f16_t>, grid, dim3(256), 0, s, (const f16_t*)qkv, sb, st, lse, N, H, dh, scale, attn_cls, attn_diag);
   else if (is_bf16) hipLaunchKernelGGL(attn_stats_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)qkv, sb, st, lse, N, H, dh, scale, attn_cls, attn_diag);

@@ -469,6 +469,46 @@ extern "C" int sg_profile_disable(void) { g_prof.on = false; return SG_OK; }
 extern "C" int sg_gemm_persist_last_kstep(void) { return gemm_persist_last_kstep(); }
 // "<family> grid=<x> ngroup=<n>" of the calling thread's last GEMM launch through the 2-byte / two-plane / fp8 GEMM entry (thread-local text).
 extern "C" const char* sg_gemm_last_kernel(void) { return gemm_last_kernel(); }
+// The fused attention on caller-packed operands: AttnArgs as they are, strides in elements (doubled here for two-plane storage, as
+// attn_generic does).  One attention_bf16() call: every check runs before the first HIP call, so a refused call launches nothing.
+extern "C" int sg_attention_raw(int precision, const void* q0, const void* q1, const void* q2, const void* k0, const void* k1, const void* k2,
+                                int64_t sb, int64_t st, const void* v, int64_t v_sb, int64_t v_st, int B, int N, int H, int dh, int n_terms,
+                                int sum_scores, int causal, float scale, const float* scale_per_image, const float* bias, float bias_w,
+                                int64_t bias_bstride, const float* bias_rn, const float* bias_cn, int resoftmax, const float* lse_in, float* lse_out,
+                                void* ctx, int64_t ctx_sb, int64_t ctx_st, float out_scale, sg_stream st_) {
+  SG_REQUIRE(precision == SG_PREC_BF16 || precision == SG_PREC_F16 || precision == SG_PREC_F16X2, "sg_attention_raw: bad precision %d", precision);
+  SG_REQUIRE(n_terms >= 1 && n_terms <= 3, "attention: n_terms=%d", n_terms);
+  const void* qs[3] = {q0, q1, q2};
+  const void* ks[3] = {k0, k1, k2};
+  const void* ptrs[7] = {qs[0], ks[0], qs[1], ks[1], qs[2], ks[2], ctx ? v : nullptr};
+  for (int i = 0; i < 7; ++i) {
+    const bool need = i < 2 * n_terms || (i == 6 && ctx);
+    SG_REQUIRE(!need || ptrs[i], "sg_attention_raw: null operand pointer");
+    SG_REQUIRE(((uintptr_t)ptrs[i] & 15) == 0, "sg_attention_raw: operands must be 16-byte aligned");
+  }
+  SG_REQUIRE(((uintptr_t)ctx & 7) == 0 && ctx_sb % 4 == 0 && ctx_st % 4 == 0, "sg_attention_raw: ctx must be 8-byte aligned (strides multiples of 4)");
+  AttnArgs a{};
+  for (int t = 0; t < n_terms; ++t) { a.q[t] = (const bf16_t*)qs[t]; a.k[t] = (const bf16_t*)ks[t]; }
+  a.v = (const bf16_t*)v; a.sb = sb; a.st = st; a.v_sb = v_sb; a.v_st = v_st;
+  a.n_terms = n_terms; a.sum_scores = sum_scores; a.causal = causal;
+  a.B = B; a.N = N; a.H = H; a.dh = dh; a.scale = scale; a.scale_per_image = scale_per_image;
+  a.bias = bias; a.bias_w = bias_w; a.bias_bstride = bias_bstride; a.bias_rn = bias_rn; a.bias_cn = bias_cn;
+  a.resoftmax = resoftmax; a.lse_in = lse_in; a.lse_out = lse_out;
+  a.ctx = (bf16_t*)ctx; a.ctx_sb = ctx_sb; a.ctx_st = ctx_st; a.out_scale = out_scale;
+  a.f16 = precision == SG_PREC_F16; a.h2 = precision == SG_PREC_F16X2;
+  if (a.h2) { a.sb *= 2; a.st *= 2; a.v_sb *= 2; a.v_st *= 2; a.ctx_sb *= 2; a.ctx_st *= 2; }
+  return attention_bf16(a, as_stream(st_));
+}
+// attention_stats() on caller-packed q | k rows (k D = H dh elements after q in a row; element strides sb / st) and a given lse [B,H,N].
+extern "C" int sg_attention_stats_raw(int precision, const void* qk, int64_t sb, int64_t st, const float* lse, int B, int N, int H, int dh,
+                                      float scale, float* attn_cls, float* attn_diag, sg_stream st_) {
+  SG_REQUIRE(precision == SG_PREC_BF16 || precision == SG_PREC_F16 || precision == SG_PREC_F16X2, "sg_attention_stats_raw: bad precision %d", precision);
+  SG_REQUIRE(qk && lse && attn_cls && attn_diag, "sg_attention_stats_raw: null pointer");
+  SG_REQUIRE(B > 0 && B < 65536 && N > 0 && H > 0 && dh > 0, "sg_attention_stats_raw: bad shape");
+  return attention_stats(qk, hk_of_precision(precision), sb, st, lse, B, N, H, dh, scale, attn_cls, attn_diag, as_stream(st_));
+}
+// "<kernel> ..." of the calling thread's last launch through the fused attention or its statistics (thread-local text).
+extern "C" const char* sg_attention_last_kernel(void) { return attention_last_kernel(); }
 // category: 0 bf16 GEMM (non-persistent tile variants), 1 fused attention, 2 f32 GEMM, 3 the persistent bf16 GEMM (all instantiations), 4 fp8 GEMM,
 // 5 / 6 the persistent GEMM's folded-LayerNorm consumer / producer instantiations alone.  Call after the stream
 // has been synchronised.

@@ -140,6 +140,12 @@ const char* sg_gemm_last_kernel(void);   /* the calling thread's last launch thr
                                           * h2_ring128, fp8_ring128, fp8_ring256x256, fp8_mx_ring256x256 or generic; grid = workgroups (persistent) or tiles
                                           * along x; ngroup = the persistent kernel's N-group size (0 = raster order); "none" when its last GEMM call
                                           * launched nothing.  The text stays valid until the thread's next query. */
+const char* sg_attention_last_kernel(void);   /* the calling thread's last launch through the fused attention (sg_attention_raw, sg_op_attention,
+                                              * the towers): "attn dh=<32|64|80|128> ts=<1|2> gk=<0 lean|1 generic|2 Experimental> multi=<0|1>
+                                              * pv=<0 log-sum-exp only|1> kind=<bf16|f16|h2> order=<head|qblock|images> nb=<LDS buffers> grid=<x>", or of
+                                              * its statistics kernel: "stats_fast lph=<4|8|16> kind=<bf16|f16> grid=<blocks>" / "stats_generic lph=0
+                                              * kind=<bf16|f16|h2> grid=<blocks>"; "none" when its last such call launched nothing.  Valid until the
+                                              * thread's next query. */
 int sg_set_gemm_config(int cfg);   /* tuning hook (calling thread only): bf16 GEMM tile variant, -1 = automatic; 33 = fp8 MLP without the MXFP8
                                     * hand-off, 34 = LayerNorm as its own pass (no folding), 36 = no small-launch dispatch (a few-tile GEMM stays on the
                                     * persistent kernel), 38 = the persistent kernel with 32-element K steps (same results as the default 64-element
@@ -294,6 +300,25 @@ int sg_op_layernorm(const float* x, const float* gamma, const float* beta, float
 /* multi-term attention over packed qkv [B,N,3D] (rows q|k|v, nn.MultiheadAttention order);
  * variant = enum sg_model_type (SG_VANILLA = ordinary softmax(q k^T) v). bias: [B,n,n] or NULL.
  * Optional outputs: attn_cls/attn_diag [B,N] head-averaged probabilities (vanilla only). */
+/* The fused attention kernel on caller-packed operands, for testing it directly (SG_PREC_BF16 / F16 / F16X2 storage; two-plane as the GEMM's).
+ * Term t (t < n_terms) scores Q_t[b, i] . K_t[b, j] per head h, element (b, i, h, d) of a Q / K operand at q + b sb + i st + h dh + d; V its
+ * own strides; strides in elements, multiples of 8, operands 16-byte aligned.  sum_scores = 1: the terms form one stream (at most 2);
+ * otherwise each term is a separately soft-maxed stream and the streams' contexts are summed.  Score of (i, j) in natural-log units:
+ *   s = scale_b sum_t Q_t[i].K_t[j]   (scale_b = scale_per_image[b] when given, else scale)
+ *   resoftmax: s <- exp(s - lse_in[b,h,i]);   bias: s += bias_w bias[b bias_bstride + (j-1)(N-1) + (i-1)] (bias_rn[b,h,i] bias_cn[b,h,j])
+ *   (bias read as [key][query]: the map must be symmetric; no bias for i = 0 or j = 0);  causal: keys j > i masked.
+ * ctx [b, i, h dh + d] (strides ctx_sb / ctx_st, nullable: a log-sum-exp-only pass) = out_scale sum_streams softmax_j(s) V[j, h, d];
+ * lse_out [B,H,N] (nullable) = the log-sum-exp of the last stream's scores.  Head dims 32 / 64 / 80 / 128. */
+int sg_attention_raw(int precision, const void* q0, const void* q1, const void* q2, const void* k0, const void* k1, const void* k2,
+                     int64_t sb, int64_t st, const void* v, int64_t v_sb, int64_t v_st, int B, int N, int H, int dh, int n_terms,
+                     int sum_scores, int causal, float scale, const float* scale_per_image, const float* bias, float bias_w,
+                     int64_t bias_bstride, const float* bias_rn, const float* bias_cn, int resoftmax, const float* lse_in, float* lse_out,
+                     void* ctx, int64_t ctx_sb, int64_t ctx_st, float out_scale, sg_stream s);
+/* The head-averaged statistics of an ordinary block on caller-packed rows: q at element 0 and k at element H dh of row (b, j) (strides sb /
+ * st in elements) and a given lse [B,H,N]:  attn_cls[b,j] = mean_h exp(scale q_0.k_j - lse[b,h,0]), attn_diag[b,j] = mean_h exp(scale
+ * q_j.k_j - lse[b,h,j]).  SG_PREC_BF16 / F16 / F16X2 storage. */
+int sg_attention_stats_raw(int precision, const void* qk, int64_t sb, int64_t st, const float* lse, int B, int N, int H, int dh,
+                           float scale, float* attn_cls, float* attn_diag, sg_stream s);
 size_t sg_op_attention_scratch_bytes(int B, int N, int D, int H, int precision);
 int sg_op_attention(const float* qkv, int B, int N, int D, int H, int variant, const float* sim, float sim_weight,
                     float* ctx, float* attn_cls, float* attn_diag, int precision, void* scratch, size_t scratch_bytes,

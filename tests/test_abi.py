@@ -125,3 +125,33 @@ def test_product_path_never_imports_the_oracle():
         inside = [n for f in ast.walk(tree) if isinstance(f, ast.FunctionDef) and f.name == allowed for n in ast.walk(f)]
         for h in hits:
             assert any(h is n for n in inside), f"{path}: oracle import outside {allowed}()"
+
+
+def test_attention_raw_refusals_without_gpu():
+    """sg_attention_raw runs every check of the fused attention before its first HIP call, so each refusal is visible on CPU."""
+    from clip_decontamination_amd import _lib
+    lib = _lib.load()
+    p = ctypes.c_void_p(1 << 20)                                   # never dereferenced: every call below is refused before any launch
+
+    def call(*, dh=64, st=128, n_terms=1, sum_scores=0, resoftmax=0, lse_in=None, lse_out=None, ctx=p, N=100, H=2):
+        qs = [p if t < n_terms else None for t in range(3)]
+        return lib.sg_attention_raw(1, *qs, *qs, N * st, st, p, N * st, st, 1, N, H, dh, n_terms, sum_scores, 0, 0.125, None, None, 0.0, 0,
+                                    None, None, resoftmax, lse_in, lse_out, ctx, N * H * dh, H * dh, 1.0, None)
+
+    cases = [
+        (dict(dh=96), b"head_dim 96 not built"),
+        (dict(st=132), b"multiples of 8"),
+        (dict(n_terms=0), b"n_terms=0"),
+        (dict(n_terms=4), b"n_terms=4"),
+        (dict(n_terms=3, sum_scores=1), b"at most 2 summed terms"),
+        (dict(resoftmax=1), b"resoftmax needs lse_in"),
+        (dict(ctx=None), b"nothing to compute"),
+        (dict(n_terms=2, ctx=None, lse_out=p), b"one stream"),
+        (dict(N=1000, st=((1 << 31) // 1128 // 8 + 1) * 8), b"token stride too large"),
+    ]
+    for kw, msg in cases:
+        assert call(**kw) != 0, kw
+        assert msg in lib.sg_last_error(), (kw, lib.sg_last_error())
+        assert lib.sg_attention_last_kernel() == b"none", kw
+    assert lib.sg_attention_stats_raw(0, p, 0, 0, p, 1, 1, 1, 64, 1.0, p, p, None) != 0
+    assert b"bad precision" in lib.sg_last_error()
