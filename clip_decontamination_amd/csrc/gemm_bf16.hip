@@ -14,13 +14,6 @@
 #include "common.h"
 #include <type_traits>
 
-#ifndef SG_PS_ABL
-#define SG_PS_ABL 0                                         // tuning builds only (tools/ablate_persist.sh): parts of the persistent GEMM switched off
-#endif
-
-#ifndef SG_H2_PROD_ABL
-#define SG_H2_PROD_ABL 0   // tuning builds only (tools): the two-plane producer epilogue without its copy (1), its statistics (2), both (3)
-#endif
 namespace sg {
 
 constexpr int BM = 128, BN = 128, BK = 64;
@@ -292,7 +285,7 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_
 // 128-byte K tile holds 32 elements as four [8 hi | 8 lo] groups.  The SOURCE-side chunk permutation also de-interleaves the planes: LDS
 // chunks 0-3 of a row are the four hi chunks, 4-7 the four lo chunks -- the fragment reads are then exactly the plain kernel's kk = 0 / 1
 // reads (conflict-free as they stand), and a K tile is ONE k-step of three MFMAs: W_hi.A_hi + W_lo.A_hi + W_hi.A_lo.
-template <int BM_, int BN_, int WM, int WN, int STAGES, int ABLATE = 0, int BKT = 64, bool FP8 = false, bool F16 = false, bool MXA = false, int SPEC = 0, bool SPLIT = false>   // ABLATE (tuning only): 1 = no loads in the loop, 2 = no MFMA
+template <int BM_, int BN_, int WM, int WN, int STAGES, int BKT = 64, bool FP8 = false, bool F16 = false, bool MXA = false, int SPEC = 0, bool SPLIT = false>
 __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_ring(GemmBf16Args a, int act, int c_bf16, int vec) {
   static_assert(!SPLIT || (BKT == 64 && F16 && !FP8 && !MXA), "two-plane f16: 128-byte K tiles on the f16 MFMA");
   constexpr int NW = WM * WN, TM = BM_ / WM, TN = BN_ / WN, MI = TM / 16, NI = TN / 16;
@@ -346,7 +339,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_ring(GemmBf16Args a
 #pragma unroll
     for (int j = 0; j < NI; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  const int nt = ABLATE == 4 ? 1 : a.K / BKT;
+  const int nt = a.K / BKT;
 #pragma unroll
   for (int sidx = 0; sidx < STAGES - 1; ++sidx)
     if (sidx < nt) stage(sidx, sidx);
@@ -358,7 +351,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_ring(GemmBf16Args a
     else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if (ABLATE != 1 && t + STAGES - 1 < nt) stage(t + STAGES - 1, (t + STAGES - 1) % STAGES);
+    if (t + STAGES - 1 < nt) stage(t + STAGES - 1, (t + STAGES - 1) % STAGES);
     const char* bufA = lds + (t % STAGES) * STAGE_BYTES;
     const char* bufW = bufA + BM_ * BKT * 2;
     if constexpr (FP8) {
@@ -431,20 +424,10 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_ring(GemmBf16Args a
       for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int j = 0; j < NI; ++j)
-          if (ABLATE != 2) acc[i][j] = mfma_16x16x32<F16>(fw[j], fa[i], acc[i][j]);
-          else { asm volatile("" ::"v"(fw[j]), "v"(fa[i])); }
+          acc[i][j] = mfma_16x16x32<F16>(fw[j], fa[i], acc[i][j]);
     }
   }
 
-  if (ABLATE == 3) {                                       // tuning only: keep the accumulators live, store (almost) nothing
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j) sum += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-    if (sum == 1234.5678f) reinterpret_cast<float*>(a.C)[0] = sum;
-    return;
-  }
   if (vec) {                                               // N % 8 == 0, aligned: coalesced path through an LDS patch
     __syncthreads();                                       // every wave is done reading the staging buffers
     epilogue_store<MI, NI, F16, SPEC, SPLIT>(acc, a, act, c_bf16, z, m0 + wave_m * TM, n0 + wave_n * TN, reinterpret_cast<float*>(lds) + wave * 16 * (TN + 4), lane);
@@ -737,7 +720,6 @@ static int launch_pingpong(const GemmBf16Args& a, int vec, hipStream_t s) {
 //           the barrier that closes slot 4t+3 (group 0: after MFMA(t,1); group 1: after READ(t,1)); tile t+1 is first read
 //           in slot 4t+4.
 
-template <int ABLATE>
 __global__ __launch_bounds__(512) void gemm_bf16_pp32(GemmBf16Args a, int act, int c_bf16, int vec) {
   constexpr int PBM = 256, PBN = 256, KT32 = 32;
   constexpr int TILE_B = (PBM + PBN) * KT32 * 2;             // 32 KiB per ring slot
@@ -752,7 +734,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp32(GemmBf16Args a, int act, i
   const int z = blockIdx.y;
   const bf16_t* A = a.A + (int64_t)z * a.strideA;
   const bf16_t* W = a.W + (int64_t)z * a.strideW;
-  const int nt = ABLATE == 4 ? 4 : a.K / KT32;
+  const int nt = a.K / KT32;
 
   // this lane's source rows: 2 A slabs and 2 W slabs (16 rows x 64 B each) per K tile
   const int srow = lane >> 2, cpos = lane & 3;
@@ -799,8 +781,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp32(GemmBf16Args a, int act, i
     __builtin_amdgcn_s_setprio(1);                                                                       \
     _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                        \
       _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                      \
-        if (ABLATE != 2) acc[4 * (MH) + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[j], fa[i], acc[4 * (MH) + i][j], 0, 0, 0); \
-        else asm volatile("" ::"v"(fw[j]), "v"(fa[i]));                                                  \
+        acc[4 * (MH) + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[j], fa[i], acc[4 * (MH) + i][j], 0, 0, 0); \
     __builtin_amdgcn_s_setprio(0);                                                                       \
   } while (0)
 #define SG_P32_WAIT(T)                                                                                   \
@@ -820,7 +801,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp32(GemmBf16Args a, int act, i
   for (int t = 0; t < nt; ++t) {
     const char* tA = lds + (t & 3) * TILE_B;
     const char* tW = tA + PBM * KT32 * 2;
-    const bool more = (ABLATE != 1) && (t + 3 < nt);
+    const bool more = t + 3 < nt;
     // phase 0: rows 0-63 of the group's half x the wave's 64 columns
 #pragma unroll
     for (int j = 0; j < 4; ++j) fw[j] = read_frag32(tW, 64 * wi + 16 * j + (lane & 15), lane >> 4);
@@ -845,28 +826,18 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp32(GemmBf16Args a, int act, i
 #undef SG_P32_MFMA
 #undef SG_P32_WAIT
 
-  if (ABLATE == 3) {
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) sum += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-    if (sum == 1234.5678f) reinterpret_cast<float*>(a.C)[0] = sum;
-    return;
-  }
   __syncthreads();
   epilogue_store<8, 4>(acc, a, act, c_bf16, z, m0 + 128 * g, n0 + 64 * wi, reinterpret_cast<float*>(lds) + wave * 16 * 68, lane);
 }
 
-template <int ABLATE>
 static int launch_pp32(const GemmBf16Args& a, hipStream_t s) {
   const size_t lds = 4 * (256 + 256) * 32 * 2;
-  auto kern = gemm_bf16_pp32<ABLATE>;
+  auto kern = gemm_bf16_pp32;
   SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
   const int64_t tiles = cdiv(a.M, 256) * cdiv(a.N, 256);
   SG_REQUIRE(tiles < (1ll << 31) && a.batch < 65536, "gemm_bf16: grid too large");
   hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)a.batch), dim3(512), lds, s, a, a.act, a.c_is_bf16, 1);
-  note_launch(ABLATE ? "pp32_ablation" : "pp32", tiles);
+  note_launch("pp32", tiles);
   return SG_OK;
 }
 
@@ -978,19 +949,6 @@ __device__ __forceinline__ void epilogue_store8(f32x4 (&acc)[MI][NI], const Gemm
       }
       v4[j] = make_float4(v[0], v[1], v[2], v[3]);
     }
-#if SG_PS_ABL == 6
-    // tuning build (WRONG element order by design): what would an epilogue cost that transposes in registers instead of through the LDS
-    // patch?  Same bytes, same full-line store pattern (8 rows x 128 B per instruction), no LDS round trip.
-    if (c_bf16 && NI == 4) {
-      uint4 o0, o1;
-      o0.x = pack_half2<F16>(v4[0].x, v4[0].y); o0.y = pack_half2<F16>(v4[0].z, v4[0].w); o0.z = pack_half2<F16>(v4[1].x, v4[1].y); o0.w = pack_half2<F16>(v4[1].z, v4[1].w);
-      o1.x = pack_half2<F16>(v4[2].x, v4[2].y); o1.y = pack_half2<F16>(v4[2].z, v4[2].w); o1.z = pack_half2<F16>(v4[3].x, v4[3].y); o1.w = pack_half2<F16>(v4[3].z, v4[3].w);
-      const int m = row0 + i * 16 + (lane >> 3), n = col0 + (lane & 7) * 8;
-      if (m < a.M && n < a.N) *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(a.C) + (int64_t)m * a.ldc + n) = o0;
-      if (m + 8 < a.M && n < a.N) *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(a.C) + (int64_t)(m + 8) * a.ldc + n) = o1;
-      continue;
-    }
-#endif
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {                       // two 8-row strips per 16-row MFMA tile
       if (((lane >> 3) & 1) == hh) {
@@ -1015,9 +973,6 @@ __device__ __forceinline__ void epilogue_store8(f32x4 (&acc)[MI][NI], const Gemm
             store_h2x8(reinterpret_cast<h2_t*>(a.C) + (int64_t)z * a.strideC + (int64_t)m * a.ldc + n, v8);
           } else {
           uint4 o; o.x = pack_half2<F16>(x0.x, x0.y); o.y = pack_half2<F16>(x0.z, x0.w); o.z = pack_half2<F16>(x1.x, x1.y); o.w = pack_half2<F16>(x1.z, x1.w);
-#if SG_PS_ABL == 5
-          if (o.x == 0x12345678u)                              // tuning build: the patch round trip and the packing stay, the store (almost) never happens
-#endif
           *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(a.C) + (int64_t)z * a.strideC + (int64_t)m * a.ldc + n) = o;
           }
         }
@@ -1046,9 +1001,6 @@ __device__ __forceinline__ void epilogue_store8(f32x4 (&acc)[MI][NI], const Gemm
             x.x += rr.x; x.y += rr.y; x.z += rr.z; x.w += rr.w;
           }
           if (r < 8 && m < a.M && n < a.N)
-#if SG_PS_ABL == 5
-            if (x.x == 1234.5678f)
-#endif
             *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.C) + (int64_t)z * a.strideC + (int64_t)m * a.ldc + n) = x;
           if constexpr (PROD) *reinterpret_cast<float4*>(patch + r * LDP + cq) = x;   // the finished values go back into the patch (same lane, same place)
         }
@@ -1064,18 +1016,12 @@ __device__ __forceinline__ void epilogue_store8(f32x4 (&acc)[MI][NI], const Gemm
           if (m8 < a.M && n8 < a.N) {
             if constexpr (SPLIT) {
               const float v8[8] = {y0.x, y0.y, y0.z, y0.w, y1.x, y1.y, y1.z, y1.w};
-#if SG_H2_PROD_ABL == 1 || SG_H2_PROD_ABL == 3
-              if (y0.x == 1234.5678f)
-#endif
               store_h2x8(reinterpret_cast<h2_t*>(a.copy16) + (int64_t)m8 * a.ld16 + n8, v8);
             } else {
               uint4 o; o.x = pack_half2<F16>(y0.x, y0.y); o.y = pack_half2<F16>(y0.z, y0.w); o.z = pack_half2<F16>(y1.x, y1.y); o.w = pack_half2<F16>(y1.z, y1.w);
               *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(a.copy16) + (int64_t)m8 * a.ld16 + n8) = o;
             }
           }
-#if SG_H2_PROD_ABL == 2 || SG_H2_PROD_ABL == 3
-          if constexpr (SPLIT) continue;
-#endif
           float sm = ((y0.x + y0.y) + (y0.z + y0.w)) + ((y1.x + y1.y) + (y1.z + y1.w));
           sm = sum8_dpp(sm);
           const float mu = sm * (1.0f / 64.0f);
@@ -1102,6 +1048,41 @@ __device__ __forceinline__ void epilogue_store8(f32x4 (&acc)[MI][NI], const Gemm
   }
 }
 
+// Output-tile order of the persistent kernels (256 x 256 tiles): workgroup w of the grid takes the tiles j = 0, 1, .. count - 1 of its own list.
+//   ngroup == 0: virtual id v = w + j * grid; XCD x = v & 7 walks a contiguous chunk of tile ids.
+//   ngroup > 0:  XCD x = w & 7 owns M tiles [mlo, mlo + mcnt) and walks its mcnt * tiles_n tiles N-group by N-group.
+// tile() clamps to the last tile, so the look-ahead past a stream's last tile stays in bounds (nothing of it is stored).
+struct PersistOrder {
+  int tiles_n, nwg, q8, r8, NG, wpx, wx, mlo, mcnt, xcnt, count;
+  __device__ __forceinline__ PersistOrder(const GemmBf16Args& a, int ngroup) {
+    tiles_n = (a.N + 255) / 256;
+    const int tiles_m = (a.M + 255) / 256;
+    nwg = tiles_m * tiles_n; q8 = nwg >> 3; r8 = nwg & 7;
+    NG = ngroup;
+    wpx = (int)gridDim.x >> 3; wx = (int)blockIdx.x >> 3;
+    const int xc = (int)blockIdx.x & 7, mq8 = tiles_m >> 3, mr8 = tiles_m & 7;
+    mlo = xc * mq8 + (xc < mr8 ? xc : mr8); mcnt = mq8 + (xc < mr8 ? 1 : 0); xcnt = mcnt * tiles_n;
+    count = NG > 0 ? (xcnt - wx + wpx - 1) / wpx : (nwg - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
+  }
+  __device__ __forceinline__ void tile(int j, int& m0, int& n0) const {
+    if (NG > 0) {
+      int Lx = wx + j * wpx;                                   // index inside this XCD's tile set
+      Lx = Lx < xcnt ? Lx : xcnt - 1;
+      const int gsz = mcnt * NG, ngroups = (tiles_n + NG - 1) / NG;
+      int grp = Lx / gsz; grp = grp < ngroups - 1 ? grp : ngroups - 1;
+      const int rem = Lx - grp * gsz;
+      const int ncols = grp == ngroups - 1 ? tiles_n - grp * NG : NG;
+      m0 = (mlo + rem / ncols) * 256; n0 = (grp * NG + rem % ncols) * 256;
+    } else {
+      const int v = (int)blockIdx.x + j * (int)gridDim.x;
+      const int xcd = v & 7, seq = v >> 3;
+      int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + seq;
+      tile = tile < nwg ? tile : nwg - 1;
+      m0 = (tile / tiles_n) * 256; n0 = (tile % tiles_n) * 256;
+    }
+  }
+};
+
 // EPI: 0 = the plain epilogue, 1 / 2 = the consumer / producer side of a folded LayerNorm (epilogue_store8's MODE): separate kernels, so
 // that the plain one keeps exactly the register allocation it was tuned with.
 template <bool F16, int EPI = 0, int SPEC = 0>
@@ -1111,40 +1092,19 @@ __global__ __launch_bounds__(512) void gemm_bf16_persist(GemmBf16Args a, int act
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = wave >> 2, wi = wave & 3;
-  const int tiles_n = (a.N + PBN - 1) / PBN, tiles_m = (a.M + PBM - 1) / PBM;
-  const int nwg = tiles_m * tiles_n;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
+  const PersistOrder order(a, a.ngroup);
   const int z = blockIdx.y;
   const bf16_t* A = a.A + (int64_t)z * a.strideA;
   const bf16_t* W = a.W + (int64_t)z * a.strideW;
   const int nt = a.K / KT32;
-  // tile order (a.ngroup > 0): XCD x = blockIdx.x & 7 owns M tiles [mlo, mlo + mcnt) and walks its mcnt * tiles_n tiles N-group by N-group
-  const int NG = a.ngroup;
-  const int wpx = (int)gridDim.x >> 3, wx = (int)blockIdx.x >> 3, xc = (int)blockIdx.x & 7;
-  const int mq8 = tiles_m >> 3, mr8 = tiles_m & 7;
-  const int mlo = xc * mq8 + (xc < mr8 ? xc : mr8), mcnt = mq8 + (xc < mr8 ? 1 : 0), xcnt = mcnt * tiles_n;
-  const int my_tiles = NG > 0 ? (xcnt - wx + wpx - 1) / wpx : (nwg - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int my_tiles = order.count;
   const int total = my_tiles * nt;                          // length of this workgroup's K-tile stream
 
   const int srow = lane >> 2, cpos = lane & 3;
   struct Src { const bf16_t* a[2]; const bf16_t* w[2]; int m0, n0; };
   auto make_src = [&](int j) {
     Src sp;
-    if (NG > 0) {
-      int Lx = wx + j * wpx;                                   // index inside this XCD's tile set
-      Lx = Lx < xcnt ? Lx : xcnt - 1;
-      const int gsz = mcnt * NG, ngroups = (tiles_n + NG - 1) / NG;
-      int grp = Lx / gsz; grp = grp < ngroups - 1 ? grp : ngroups - 1;
-      const int rem = Lx - grp * gsz;
-      const int ncols = grp == ngroups - 1 ? tiles_n - grp * NG : NG;
-      sp.m0 = (mlo + rem / ncols) * PBM; sp.n0 = (grp * NG + rem % ncols) * PBN;
-    } else {
-      const int v = (int)blockIdx.x + j * (int)gridDim.x;    // virtual id; XCD x = v & 7 walks a contiguous chunk of tile ids
-      const int xcd = v & 7, seq = v >> 3;
-      int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + seq;
-      tile = tile < nwg ? tile : nwg - 1;
-      sp.m0 = (tile / tiles_n) * PBM; sp.n0 = (tile % tiles_n) * PBN;
-    }
+    order.tile(j, sp.m0, sp.n0);
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
       const int ra = 128 * g + 32 * wi + 16 * p + srow;
@@ -1217,21 +1177,12 @@ __global__ __launch_bounds__(512) void gemm_bf16_persist(GemmBf16Args a, int act
       constexpr bool STEADY = decltype(steady_tag)::value;
       const char* tA = lds + (s & 3) * TILE_B;
       const char* tW = tA + PBM * KT32 * 2;
-      // READ(s)   (SG_PS_ABL, tuning builds only -- WRONG results by design: 1 = no LDS-DMA issue in the steady loop, 2 = no fragment reads,
-      //            3 = no MFMAs, 4 = no epilogue: what each part of a slot costs, tools/ablate_persist.sh)
-#if SG_PS_ABL == 2
-      if (!STEADY || kt == 0) {
-#endif
+      // READ(s)
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) fw[jj] = read_frag32(tW, 64 * wi + 16 * jj + (lane & 15), lane >> 4);
 #pragma unroll
       for (int i = 0; i < 8; ++i) fa[i] = read_frag32(tA, 128 * g + 16 * i + (lane & 15), lane >> 4);
-#if SG_PS_ABL == 2
-      }
-#endif
-      if constexpr (STEADY && SG_PS_ABL == 1) {
-        if (g == 1) wait_vmcnt<8>();
-      } else if constexpr (STEADY) {
+      if constexpr (STEADY) {
         auto piece = [&](const bf16_t* const (&src)[2], const int (&dst)[2], int ahead) {
           char* base = lds + ((s + ahead) & 3) * TILE_B;
 #pragma unroll
@@ -1250,12 +1201,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_persist(GemmBf16Args a, int act
 #pragma unroll
       for (int i = 0; i < 8; ++i)
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-#if SG_PS_ABL == 3
-          if (STEADY) { asm volatile("" ::"v"(fw[jj]), "v"(fa[i])); continue; }
-#endif
-          acc[i][jj] = mfma_16x16x32<F16>(fw[jj], fa[i], acc[i][jj]);
-        }
+        for (int jj = 0; jj < 4; ++jj) acc[i][jj] = mfma_16x16x32<F16>(fw[jj], fa[i], acc[i][jj]);
       __builtin_amdgcn_s_setprio(0);
       if (g == 0) { if constexpr (STEADY) wait_vmcnt<6>(); else wait_tile(s + 1); }
       SG_PS_SYNC();
@@ -1268,9 +1214,6 @@ __global__ __launch_bounds__(512) void gemm_bf16_persist(GemmBf16Args a, int act
     if (g == 0) SG_PS_SYNC();                               // align: every read of this tile's last K tile has retired
     {
       float* patch = reinterpret_cast<float*>(lds + ((s - 1) & 3) * TILE_B) + wave * 576;   // 8 rows x 68 floats (+pad) per wave
-#if SG_PS_ABL == 4
-      if (acc[0][0][0] == 1234.5678f)                                                       // keep the accumulators live, store (almost) nothing
-#endif
       epilogue_store8<8, 4, F16, EPI, SPEC>(acc, a, act, c_bf16, z, cur.m0 + 128 * g, cur.n0 + 64 * wi, patch, lane,
                                             reinterpret_cast<float*>(lds + ((s - 1) & 3) * TILE_B) + 8 * 576 + wave * 256);   // 1 KiB per wave behind the 8 patches
     }
@@ -1281,209 +1224,6 @@ __global__ __launch_bounds__(512) void gemm_bf16_persist(GemmBf16Args a, int act
   }
 #undef SG_PS_SYNC
 }
-
-// ---- persistent ping-pong on 128-byte K steps: the production kernel for the large 2-byte linears -------------------------------------
-// gemm_bf16_persist's output tiling, epilogue forms, tile orders and blockIdx.y batching on gemm_fp8_persist's data movement.  A K step is
-// 64 elements = 128 bytes per row, so every LDS-DMA piece is 8 rows x 128 B: whole lines, where the 32-element kernel's 16 rows x 64 B
-// pieces touch 16 lines half each and request the other halves one K tile (32 KiB of traffic through the L1) later.
-// LDS, all 160 KiB: the A ring has 2 slots, the W ring 3 (32 KiB each, the 128-byte image of gemm_bf16_ring<BKT = 64>: chunk ^ ((row >> 1) & 7),
-// applied on the source side).  The hand-off rules, the tile switch and the prologue are gemm_fp8_persist's, comment for comment.
-// Two phases per K step, 32 MFMAs (512 cycles) each:
-//   READ0(s): W fragments of both K halves (kept for both phases) + A rows 0-63 of the group's half; issue A_g(s+1).   MFMA0(s): 4 x 4 x 2.
-//   READ1(s): A rows 64-127; issue this group's rows of W(s+2+g).                                                     MFMA1(s): the same.
-// Per wave and K step: 8 LDS-DMA pieces and 24 ds_read_b128 per 64 MFMAs.
-// Arithmetic: every accumulator gets its K 0-31 MFMA and then its K 32-63 one, with read_frag32's lane -> K-chunk mapping (chunk h * 4 +
-// lane / 16 of K half h), so its MFMA sequence is the one the 32-element kernel issues and the results are bit-identical to that kernel's
-// (tuning code 38 runs it).  Look-ahead is 3 K steps: K / 64 >= 4 keeps every load within the next output tile.  Operand rows must be
-// shorter than 2^21 elements: byte offsets inside a 256-row tile are 32-bit (checked by the dispatch).
-template <bool F16, int EPI = 0, int SPEC = 0>
-__global__ __launch_bounds__(512) void gemm_bf16_persist_k64(GemmBf16Args a, int act, int c_bf16) {
-  constexpr int PBM = 256, PBN = 256, KB = 128;                          // K step in bytes (64 elements)
-  constexpr int SLOT = 256 * KB;                                         // 32 KiB
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  char* ldsA = lds;                                                      // 2 slots
-  char* ldsW = lds + 2 * SLOT;                                           // 3 slots
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int g = wave >> 2, wi = wave & 3;
-  const int tiles_n = (a.N + PBN - 1) / PBN, tiles_m = (a.M + PBM - 1) / PBM;
-  const int nwg = tiles_m * tiles_n;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int z = blockIdx.y;
-  const char* A = reinterpret_cast<const char*>(a.A + (int64_t)z * a.strideA);
-  const char* W = reinterpret_cast<const char*>(a.W + (int64_t)z * a.strideW);
-  const int64_t lda_b = a.lda * 2, ldw_b = a.ldw * 2;                    // row strides in bytes
-  const int nt = a.K / 64;
-  // tile order (a.ngroup > 0): XCD x = blockIdx.x & 7 owns M tiles [mlo, mlo + mcnt) and walks its mcnt * tiles_n tiles N-group by N-group
-  const int NG = a.ngroup;
-  const int wpx = (int)gridDim.x >> 3, wx = (int)blockIdx.x >> 3, xc = (int)blockIdx.x & 7;
-  const int mq8 = tiles_m >> 3, mr8 = tiles_m & 7;
-  const int mlo = xc * mq8 + (xc < mr8 ? xc : mr8), mcnt = mq8 + (xc < mr8 ? 1 : 0), xcnt = mcnt * tiles_n;
-  const int my_tiles = NG > 0 ? (xcnt - wx + wpx - 1) / wpx : (nwg - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-  const int total = my_tiles * nt;                                       // length of this workgroup's K-step stream
-
-  const int srow = lane >> 3, cpos = lane & 7;
-  // pieces are 8 rows apart and start at a multiple of 32 rows, so the swizzle term depends on the lane and on the parity of the piece only
-  const int swz_e = (cpos ^ (srow >> 1)) << 4, swz_o = (cpos ^ (4 + (srow >> 1))) << 4;
-  struct Src { const char* Ab; const char* Wb; int m0, n0; };            // 64-bit tile bases (wave-uniform)
-  const int ra0 = 128 * g + 32 * wi + srow, rw0 = 64 * wi + 32 * g + srow;   // this lane's first piece row inside any tile
-  auto make_src = [&](int j) {
-    Src sp;
-    if (NG > 0) {
-      int Lx = wx + j * wpx;                                             // index inside this XCD's tile set
-      Lx = Lx < xcnt ? Lx : xcnt - 1;
-      const int gsz = mcnt * NG, ngroups = (tiles_n + NG - 1) / NG;
-      int grp = Lx / gsz; grp = grp < ngroups - 1 ? grp : ngroups - 1;
-      const int rem = Lx - grp * gsz;
-      const int ncols = grp == ngroups - 1 ? tiles_n - grp * NG : NG;
-      sp.m0 = (mlo + rem / ncols) * PBM; sp.n0 = (grp * NG + rem % ncols) * PBN;
-    } else {
-      const int v = (int)blockIdx.x + j * (int)gridDim.x;                // virtual id; XCD x = v & 7 walks a contiguous chunk of tile ids
-      const int xcd = v & 7, seq = v >> 3;
-      int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + seq;
-      tile = tile < nwg ? tile : nwg - 1;
-      sp.m0 = (tile / tiles_n) * PBM; sp.n0 = (tile % tiles_n) * PBN;
-    }
-    sp.Ab = A + (int64_t)sp.m0 * lda_b; sp.Wb = W + (int64_t)sp.n0 * ldw_b;
-    return sp;
-  };
-  Src cur = make_src(0);
-  Src nxt = make_src(my_tiles > 1 ? 1 : 0);
-  int cur_end = nt;                                                      // stream index where `nxt` begins
-  const int lda_i = (int)lda_b, ldw_i = (int)ldw_b;
-  auto load_a = [&](int u) {                                             // this wave's pieces of A_g(u)
-    if (u >= total) return;
-    const bool nx = u >= cur_end;
-    const Src& sp = nx ? nxt : cur;
-    const int kt = nx ? u - cur_end : u - (cur_end - nt);
-    const int rmax = a.M - 1 - sp.m0;                                    // rows past the edge re-read the last row (never stored)
-    char* base = ldsA + (u & 1) * SLOT + (128 * g + 32 * wi) * KB;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      int r = ra0 + 8 * p; r = r < rmax ? r : rmax;
-      const int off = r * lda_i + ((p & 1) ? swz_o : swz_e) + kt * KB;
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(sp.Ab + off), (lds_ptr_t)(base + p * 8 * KB), 16, 0, 0);
-    }
-  };
-  auto load_w = [&](int u) {                                             // this wave's rows of W(u)
-    if (u >= total) return;
-    const bool nx = u >= cur_end;
-    const Src& sp = nx ? nxt : cur;
-    const int kt = nx ? u - cur_end : u - (cur_end - nt);
-    const int rmax = a.N - 1 - sp.n0;
-    char* base = ldsW + (u % 3) * SLOT + (64 * wi + 32 * g) * KB;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      int r = rw0 + 8 * p; r = r < rmax ? r : rmax;
-      const int off = r * ldw_i + ((p & 1) ? swz_o : swz_e) + kt * KB;
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(sp.Wb + off), (lds_ptr_t)(base + p * 8 * KB), 16, 0, 0);
-    }
-  };
-#define SG_P64_SYNC()                                \
-  do {                                               \
-    __builtin_amdgcn_sched_barrier(0);               \
-    __builtin_amdgcn_s_barrier();                    \
-    __builtin_amdgcn_sched_barrier(0);               \
-  } while (0)
-
-  // prologue: A(0), W(0), W(1) from everybody, W(2) from group 1 (group 0 issues its rows of W(2) in READ1(0)).  Group 1 retires its rows of
-  // W(1) here as well: group 0 reads them in READ0(1), which runs while group 1 is in MFMA1(0), before group 1's first wait in the loop.
-  load_a(0); load_w(0); load_w(1);
-  if (g == 1) { load_w(2); if (2 < total) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
-  else { if (1 < total) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
-  SG_P64_SYNC();
-  if (g == 1) SG_P64_SYNC();
-
-  f32x4 acc[8][4];
-  bf16x8 fa[2][4], fw[2][4];                                             // [K half][fragment]
-  int s = 0;
-  for (int j = 0; j < my_tiles; ++j) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) acc[i][jj] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    int kt = 0;
-    // One K step.  STEADY: every piece this step requests (A(s+1), W(s+2+g)) belongs to the current output tile -- no source select, no
-    // end-of-stream test; the last three steps of a tile take the general form (measured: +1.0 % on the bench line against the general form
-    // throughout, which is 2-4 % faster on the run-time epilogue form alone)
-    auto kstep = [&](auto steady_tag) {
-      constexpr bool STEADY = decltype(steady_tag)::value;
-      const char* tA = ldsA + (s & 1) * SLOT;
-      const char* tW = ldsW + (s % 3) * SLOT;
-      // READ0(s): W fragments (kept for both phases) + A rows 0-63 of the group's half; issue A_g(s+1)
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) fw[h][jj] = read_frag(tW, 64 * wi + 16 * jj + (lane & 15), h * 4 + (lane >> 4));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) fa[h][i] = read_frag(tA, 128 * g + 16 * i + (lane & 15), h * 4 + (lane >> 4));
-      }
-      if constexpr (STEADY) {
-        const int rmax = a.M - 1 - cur.m0;
-        char* base = ldsA + ((s + 1) & 1) * SLOT + (128 * g + 32 * wi) * KB;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-          int r = ra0 + 8 * p; r = r < rmax ? r : rmax;
-          __builtin_amdgcn_global_load_lds((gbl_ptr_t)(cur.Ab + (r * lda_i + ((p & 1) ? swz_o : swz_e) + (kt + 1) * KB)), (lds_ptr_t)(base + p * 8 * KB), 16, 0, 0);
-        }
-      } else load_a(s + 1);
-      SG_P64_SYNC();
-      // MFMA0(s): K half 0 of every accumulator, then K half 1
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) acc[i][jj] = mfma_16x16x32<F16>(fw[h][jj], fa[h][i], acc[i][jj]);
-      __builtin_amdgcn_s_setprio(0);
-      SG_P64_SYNC();
-      // READ1(s): A rows 64-127; issue this group's rows of W(s+2) / W(s+3)
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) fa[h][i] = read_frag(tA, 128 * g + 64 + 16 * i + (lane & 15), h * 4 + (lane >> 4));
-      const int uw = s + 2 + g;
-      if constexpr (STEADY) {
-        const int rmax = a.N - 1 - cur.n0;
-        char* base = ldsW + (uw % 3) * SLOT + (64 * wi + 32 * g) * KB;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-          int r = rw0 + 8 * p; r = r < rmax ? r : rmax;
-          __builtin_amdgcn_global_load_lds((gbl_ptr_t)(cur.Wb + (r * ldw_i + ((p & 1) ? swz_o : swz_e) + (kt + 2 + g) * KB)), (lds_ptr_t)(base + p * 8 * KB), 16, 0, 0);
-        }
-      } else load_w(uw);
-      SG_P64_SYNC();
-      // MFMA1(s)
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) acc[4 + i][jj] = mfma_16x16x32<F16>(fw[h][jj], fa[h][i], acc[4 + i][jj]);
-      __builtin_amdgcn_s_setprio(0);
-      if (STEADY || uw < total) wait_vmcnt<4>(); else wait_vmcnt<0>();   // all but the W pieces just issued
-      SG_P64_SYNC();
-      ++kt; ++s;
-    };
-    for (; kt + 3 < nt; ) kstep(std::true_type{});
-    for (; kt < nt; ) kstep(std::false_type{});
-    // ---- tile end ----
-    if (g == 0) SG_P64_SYNC();                                           // align: every read of this tile's last K step has retired
-    {
-      float* pbase = reinterpret_cast<float*>(ldsA + ((s - 1) & 1) * SLOT);    // the consumed A slot: 8 patches of 8 rows x 68 floats (+pad), then
-      epilogue_store8<8, 4, F16, EPI, SPEC>(acc, a, act, c_bf16, z, cur.m0 + 128 * g, cur.n0 + 64 * wi, pbase + wave * 576, lane,   // 1 KiB
-                                            pbase + 8 * 576 + wave * 256);                                                          // per wave
-    }
-    cur = nxt; cur_end += nt;
-    if (j + 2 < my_tiles) nxt = make_src(j + 2);
-    SG_P64_SYNC();                                                       // the A slot used as patch is refilled from READ0 of the next step on
-    if (g == 1 && j + 1 < my_tiles) SG_P64_SYNC();                       // re-stagger
-  }
-#undef SG_P64_SYNC
-}
-
-
 
 // Epilogue of the persistent fp8 kernel.  Same patch transposition as epilogue_store8, but de-quantisation (acc * row_scale[m] *
 // col_scale[n]), bias and activation are applied AFTER it, where a lane owns the same 4 (f32) / 8 (bf16) columns for every strip:
@@ -1574,254 +1314,130 @@ __device__ __forceinline__ void epilogue_store8_fp8(f32x4 (&acc)[MI][NI], const 
   }
 }
 
-// ---- persistent fp8 ping-pong (SG_PREC_FP8: the QKV / fc / proj linears of the ordinary blocks) ------------------------------------
-// The bf16 persistent kernel's structure carried to OCP e4m3 operands: 256 x 256 output tile, 8 waves in two groups that alternate READ /
-// MFMA segments, persistent workgroups whose K-step stream runs across output tiles, epilogue through a per-wave LDS patch.
-// A K step is 128 fp8 per row = ONE v_mfma_scale_f32_16x16x128_f8f6f4 per 16 x 16 output (32 cycles: twice the bf16 form at 4x the K).
-// An operand fragment is 32 B per lane, so the 12 fragments of a wave (8 A + 4 W) no longer fit next to 128 accumulators: a K step is
-// TWO phases (rows 0-63 / 64-127 of the group's half), the 4 W fragments stay in registers across both.
+// ---- persistent ping-pong on 128-byte K steps: the production kernel for every large linear -------------------------------------------
+// gemm_bf16_persist's output tiling (256 x 256, 8 waves in two groups that alternate READ / MFMA segments), persistent workgroups whose K-step
+// stream runs across output tiles, tile orders (PersistOrder), blockIdx.y batching and epilogue through a per-wave LDS patch -- with a K step of
+// 128 bytes per operand row, so every LDS-DMA piece is 8 rows x 128 B: whole lines, where the 32-element kernel's 16 rows x 64 B pieces touch
+// 16 lines half each and request the other halves one K tile (32 KiB of traffic through the L1) later.
+// ONE body, gemm_persist128<OP, EPI, SPEC>, for three operand kinds; each kind keeps its own entry point (the name the launch records, the
+// profiles and tools/pmc_summary.py key on).  What differs per kind:
+//                          bf16 / f16 (gemm_bf16_persist_k64)    fp8 (gemm_fp8_persist)                 two-plane f16 (gemm_h2_persist)
+//   K step of 128 bytes    64 elements                           128 OCP e4m3 elements                  32 elements: four [8 hi | 8 lo] groups
+//   LDS chunk c holds      source chunk c                        source chunk c                         source chunk gchunk(c): LDS chunks 0-3 of a
+//                                                                                                       row hold the four hi chunks, 4-7 the lo ones
+//   per 16 x 16 output     mfma_16x16x32 on K half 0, then on    ONE mfma_scale_f32_16x16x128_f8f6f4 on  W_hi.A_hi, W_lo.A_hi, W_hi.A_lo
+//   and K step             K half 1 (half 0 of all accumulators  the two halves concatenated, scales     (mfma_16x16x32<f16>, in that order)
+//                          of the phase first)                   0x7f = 2^0: plain fp8 x fp8
+//   tile end               epilogue_store8                       row scales fetched in the last K step, epilogue_store8<.., SPLIT>
+//                                                                vmcnt(0), epilogue_store8_fp8
+// `a` arrives with K, lda, ldw in 2-byte units (bf16 / f16; two-plane: f16 units, 2 x the element counts, as gemm_h2 prepares it) or in bytes
+// (fp8).  The fragment reads are the same for every kind: chunk h * 4 + lane / 16 of K half (two-plane: plane) h, h = 0 / 1.
+// LDS, all 160 KiB: the A ring has 2 slots, the W ring 3 (32 KiB each: 256 rows x 128 B, 16-byte chunk c of row r at position c ^ ((r >> 1) & 7),
+// the permutation applied on the source side).  A-half g is only ever read by group g, so two slots suffice; W is read by both groups, which
+// costs it one more slot.  A fragment pair is 32 B per lane, so the 12 pairs of a wave (8 A + 4 W) do not fit next to 128 accumulators: a K
+// step is TWO phases (rows 0-63 / 64-127 of the group's half), the 4 W pairs stay in registers across both.
 //   slots (barrier intervals), group 0: READ0(s) = 4s, MFMA0(s) = 4s+1, READ1(s) = 4s+2, MFMA1(s) = 4s+3; group 1 one later.
-// LDS, all 160 KiB: the A ring has 2 slots, the W ring 3 (32 KiB each: 256 rows x 128 B, 16-byte chunks XOR-swizzled as in the 128-byte
-// bf16 image).  A-half g is only ever read by group g, so two slots suffice; W is read by both groups, which costs it one more slot:
-//   loads : READ0(t): group g issues A_g(t+1)                    (position (t+1)&1, last read in READ1(t-1), retired at slot 4t-1+g)
-//           READ1(t): group 0 issues its rows of W(t+2), group 1 its rows of W(t+3)
-//             (W(t) is read in READ0(t) = slots 4t / 4t+1 and retired when slot 4t+2 opens: group 1 (slot 4t+3) may overwrite it, group 0
-//              (slot 4t+2) may not yet and refills the position of W(t-1) instead)
-//   RAW   : every wave ends MFMA1(t) with vmcnt(4): everything but the W pieces it issued in READ1(t) has landed -- its A(t+1) pieces and
-//           its pieces of W(t+1) (issued one or two steps earlier) -- before the barrier that precedes READ0(t+1).
-//   tile end: as in the bf16 kernel (group 0 takes one extra barrier, epilogue through a patch inside the just-consumed A slot, barrier,
-//           group 1 re-staggers).  Look-ahead is at most 3 K steps, so K >= 512 (4 steps per tile) keeps loads within the next tile.
-template <bool DUMMY = false>
-__global__ __launch_bounds__(512) void gemm_fp8_persist(GemmBf16Args a, int act, int c_bf16) {
-  constexpr int PBM = 256, PBN = 256, KB = 128;                          // K step in bytes (= fp8 elements)
-  constexpr int SLOT = 256 * KB;                                         // 32 KiB
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  char* ldsA = lds;                                                      // 2 slots
-  char* ldsW = lds + 2 * SLOT;                                           // 3 slots
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int g = wave >> 2, wi = wave & 3;
-  const int tiles_n = (a.N + PBN - 1) / PBN, tiles_m = (a.M + PBM - 1) / PBM;
-  const int nwg = tiles_m * tiles_n;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const uint8_t* A = reinterpret_cast<const uint8_t*>(a.A);
-  const uint8_t* W = reinterpret_cast<const uint8_t*>(a.W);
-  const int nt = a.K / KB;
-  const int my_tiles = (nwg - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-  const int total = my_tiles * nt;                                       // length of this workgroup's K-step stream
+//   loads : READ0(s): group g issues A_g(s+1)                    (position (s+1)&1, last read in READ1(s-1), retired at slot 4s-1+g)
+//           READ1(s): group 0 issues its rows of W(s+2), group 1 its rows of W(s+3)
+//             (W(s) is read in READ0(s) = slots 4s / 4s+1 and retired when slot 4s+2 opens: group 1 (slot 4s+3) may overwrite it, group 0
+//              (slot 4s+2) may not yet and refills the position of W(s-1) instead)
+//   RAW   : every wave ends MFMA1(s) with vmcnt(4): everything but the W pieces it issued in READ1(s) has landed -- its A(s+1) pieces and
+//           its pieces of W(s+1) (issued one or two steps earlier) -- before the barrier that precedes READ0(s+1).
+//   tile end: group 0 takes one extra barrier (both groups are then past every read of the tile's last K step), every wave runs the epilogue
+//           through a patch inside the just-consumed A slot, one barrier, group 1 re-staggers.
+// Per wave and K step: 8 LDS-DMA pieces and 24 ds_read_b128.  Look-ahead is 3 K steps: >= 4 K steps per tile keep every load within the next
+// output tile.  Operand rows of a tile are addressed from a 64-bit tile base with 32-bit byte offsets (row strides checked by the dispatch).
+// Arithmetic (bf16 / f16): every accumulator gets its K 0-31 MFMA and then its K 32-63 one, with read_frag32's lane -> K-chunk mapping, so its
+// MFMA sequence is the one the 32-element kernel issues and the results are bit-identical to that kernel's (tuning code 38 runs it).
+// fp8: the concatenated halves are the instruction's own K order (dwords 0-3 of lane block b are K 16b..16b+15, dwords 4-7 K 64+16b..;
+// tools/mx_probe.hip); the legacy v_mfma_f32_16x16x32_fp8_fp8 runs at the bf16 rate on gfx950 (tools/mfma_rate.hip), so it is not used.
+// Two-plane: 48 MFMAs = 768 cycles per phase against the same READ segments -- the matrix pipe has 1.5x the cover.
+enum PersistOp { OP_BF16, OP_F16, OP_FP8, OP_H2 };
+typedef __attribute__((ext_vector_type(8))) int i32x8;
+union FragPair { bf16x8 h[2]; i32x8 v; };                  // the lane's two K halves (two-plane: hi / lo plane); fp8: one 32-byte operand
 
-  const int srow = lane >> 3, cpos = lane & 7;
-  // Per tile a lane only keeps the first row of its 4 A pieces and of its 4 W pieces (pieces are 8 rows apart); the byte offset of a piece is
-  // rebuilt at issue time (row clamp + one 32-bit multiply: operands < 2 GiB, checked on the host), the swizzle term depends on the lane and on
-  // the parity of the piece only.  (Eight 64-bit pointers per tile for the current and the next tile do not fit next to 128 accumulators and
-  // 64 fragment registers.)
-  struct Src { int ra0, rw0, m0, n0; };
-  const int swz_e = (cpos ^ (srow >> 1)) << 4, swz_o = (cpos ^ (4 + (srow >> 1))) << 4;
-  auto make_src = [&](int j) {
-    Src sp;
-    const int v = (int)blockIdx.x + j * (int)gridDim.x;                  // XCD x = v & 7 walks a contiguous chunk of tile ids
-    const int xcd = v & 7, seq = v >> 3;
-    int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + seq;
-    tile = tile < nwg ? tile : nwg - 1;
-    sp.m0 = (tile / tiles_n) * PBM; sp.n0 = (tile % tiles_n) * PBN;
-    sp.ra0 = sp.m0 + 128 * g + 32 * wi + srow;
-    sp.rw0 = sp.n0 + 64 * wi + 32 * g + srow;
-    return sp;
-  };
-  Src cur = make_src(0);
-  Src nxt = make_src(my_tiles > 1 ? 1 : 0);
-  int cur_end = nt;                                                      // stream index where `nxt` begins
-  const int lda = (int)a.lda, ldw = (int)a.ldw, Mm1 = a.M - 1, Nm1 = a.N - 1;
-  auto load_a = [&](int u) {                                             // this wave's pieces of A_g(u)
-    if (u >= total) return;
-    const bool nx = u >= cur_end;
-    const int r0 = nx ? nxt.ra0 : cur.ra0;
-    const int kt = nx ? u - cur_end : u - (cur_end - nt);
-    char* base = ldsA + (u & 1) * SLOT + (128 * g + 32 * wi) * KB;
+// MFMA phase: the 16 accumulators of rows i0 .. i0 + 3 against the 4 A and 4 W fragment pairs
+template <int OP>
+__device__ __forceinline__ void persist128_mfma(f32x4 (&acc)[8][4], int i0, const FragPair (&fa)[4], const FragPair (&fw)[4]) {
+  __builtin_amdgcn_s_setprio(1);
+  if constexpr (OP == OP_FP8) {
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      int r = r0 + 8 * p; r = r < Mm1 ? r : Mm1;
-      const int off = r * lda + ((p & 1) ? swz_o : swz_e) + kt * KB;
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(A + off), (lds_ptr_t)(base + p * 8 * KB), 16, 0, 0);
-    }
-  };
-  auto load_w = [&](int u) {                                             // this wave's rows of W(u)
-    if (u >= total) return;
-    const bool nx = u >= cur_end;
-    const int r0 = nx ? nxt.rw0 : cur.rw0;
-    const int kt = nx ? u - cur_end : u - (cur_end - nt);
-    char* base = ldsW + (u % 3) * SLOT + (64 * wi + 32 * g) * KB;
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      int r = r0 + 8 * p; r = r < Nm1 ? r : Nm1;
-      const int off = r * ldw + ((p & 1) ? swz_o : swz_e) + kt * KB;
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(W + off), (lds_ptr_t)(base + p * 8 * KB), 16, 0, 0);
-    }
-  };
-#define SG_F8_SYNC()                                 \
-  do {                                               \
-    __builtin_amdgcn_sched_barrier(0);               \
-    __builtin_amdgcn_s_barrier();                    \
-    __builtin_amdgcn_sched_barrier(0);               \
-  } while (0)
-
-  // prologue: A(0), W(0), W(1) from everybody, W(2) from group 1 (group 0 issues its rows of W(2) in READ1(0)).  Group 1 retires its rows of
-  // W(1) here as well: group 0 reads them in READ0(1), which runs while group 1 is in MFMA1(0), before group 1's first wait in the loop.
-  load_a(0); load_w(0); load_w(1);
-  if (g == 1) { load_w(2); if (2 < total) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
-  else { if (1 < total) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
-  SG_F8_SYNC();
-  if (g == 1) SG_F8_SYNC();
-
-  typedef __attribute__((ext_vector_type(8))) int i32x8;
-  union Op { bf16x8 h[2]; i32x8 v; };
-  f32x4 acc[8][4];
-  Op fa8[4], fw8[4];
-  float rs_pre[2] = {1.f, 1.f};
-  int s = 0;
-  for (int j = 0; j < my_tiles; ++j) {
+      for (int jj = 0; jj < 4; ++jj)   // cbsz = blgp = 0: both operands e4m3; scales 0x7f = 2^0 (E8M0): plain fp8 x fp8
+        acc[i0 + i][jj] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw[jj].v, fa[i].v, acc[i0 + i][jj], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+  } else if constexpr (OP == OP_H2) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int jj = 0; jj < 4; ++jj) acc[i][jj] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int kt = 0; kt < nt; ++kt, ++s) {
-      const char* tA = ldsA + (s & 1) * SLOT;
-      const char* tW = ldsW + (s % 3) * SLOT;
-      // READ0(s): W fragments (kept for both phases) + A rows 0-63 of the group's half; issue A_g(s+1)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) fw8[jj].h[kk] = read_frag(tW, 64 * wi + 16 * jj + (lane & 15), kk * 4 + (lane >> 4));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) fa8[i].h[kk] = read_frag(tA, 128 * g + 16 * i + (lane & 15), kk * 4 + (lane >> 4));
+      for (int jj = 0; jj < 4; ++jj) {
+        acc[i0 + i][jj] = mfma_16x16x32<true>(fw[jj].h[0], fa[i].h[0], acc[i0 + i][jj]);
+        acc[i0 + i][jj] = mfma_16x16x32<true>(fw[jj].h[1], fa[i].h[0], acc[i0 + i][jj]);
+        acc[i0 + i][jj] = mfma_16x16x32<true>(fw[jj].h[0], fa[i].h[1], acc[i0 + i][jj]);
       }
-      load_a(s + 1);
-      SG_F8_SYNC();
-      // MFMA0(s)
-      __builtin_amdgcn_s_setprio(1);
+  } else {
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj)   // cbsz = blgp = 0: both operands e4m3; scales 0x7f = 2^0 (E8M0): plain fp8 x fp8
-          acc[i][jj] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw8[jj].v, fa8[i].v, acc[i][jj], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
-      __builtin_amdgcn_s_setprio(0);
-      SG_F8_SYNC();
-      // READ1(s): A rows 64-127; issue this group's rows of W(s+2) / W(s+3)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) fa8[i].h[kk] = read_frag(tA, 128 * g + 64 + 16 * i + (lane & 15), kk * 4 + (lane >> 4));
-      const int uw = s + 2 + g;
-      load_w(uw);
-      if (kt == nt - 1) {                                                  // last K step of the tile: this wave's 128 row scales for the epilogue
-#pragma unroll
-        for (int u2 = 0; u2 < 2; ++u2) { int m = cur.m0 + 128 * g + u2 * 64 + lane; m = m < a.M ? m : a.M - 1; rs_pre[u2] = a.row_scale[m]; }
-      }
-      SG_F8_SYNC();
-      // MFMA1(s)
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj)
-          acc[4 + i][jj] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw8[jj].v, fa8[i].v, acc[4 + i][jj], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
-      __builtin_amdgcn_s_setprio(0);
-      if (kt == nt - 1) wait_vmcnt<0>();                                 // tile end: the row scales too (they were issued after the W pieces)
-      else if (uw < total) wait_vmcnt<4>(); else wait_vmcnt<0>();        // all but the W pieces just issued
-      SG_F8_SYNC();
-    }
-    // ---- tile end ----
-    if (g == 0) SG_F8_SYNC();                                            // align: every read of this tile's last K step has retired
-    {
-      float* pbase = reinterpret_cast<float*>(ldsA + ((s - 1) & 1) * SLOT);    // the consumed A slot: 8 patches of 8 rows x 68 floats (+pad), then 8 x 128 row scales
-      epilogue_store8_fp8<8, 4>(acc, a, act, c_bf16, cur.m0 + 128 * g, cur.n0 + 64 * wi, pbase + wave * 576, pbase + 8 * 576 + wave * 128, lane, rs_pre);
-    }
-    cur = nxt; cur_end += nt;
-    if (j + 2 < my_tiles) nxt = make_src(j + 2);
-    SG_F8_SYNC();                                                        // the A slot used as patch is refilled from READ0 of the next step on
-    if (g == 1 && j + 1 < my_tiles) SG_F8_SYNC();                        // re-stagger
+        for (int jj = 0; jj < 4; ++jj) acc[i0 + i][jj] = mfma_16x16x32<OP == OP_F16>(fw[jj].h[h], fa[i].h[h], acc[i0 + i][jj]);
   }
-#undef SG_F8_SYNC
+  __builtin_amdgcn_s_setprio(0);
 }
 
-static int launch_fp8_persist(const GemmBf16Args& a, hipStream_t s) {
-  const size_t lds = 5 * 256 * 128;                                      // 160 KiB: the whole LDS of a CU
-  auto kern = gemm_fp8_persist<false>;
-  SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
-  const int n_cu = device_cu_count();
-  const int64_t tiles = cdiv(a.M, 256) * cdiv(a.N, 256);
-  SG_REQUIRE(tiles < (1ll << 31), "gemm_fp8: grid too large");
-  unsigned grid = (unsigned)(tiles < n_cu ? tiles : n_cu);
-  if (g_persist_grid_cap > 0 && grid > (unsigned)g_persist_grid_cap) grid = (unsigned)g_persist_grid_cap;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, a, a.act, a.c_is_bf16);
-  note_launch("fp8_persist", grid);
-  return SG_OK;
-}
-
-
-// ---- persistent two-plane f16 ping-pong (SG_PREC_F16X2: every large ViT linear of the exact mode) ------------------------------------------
-// gemm_fp8_persist's structure on two-plane f16 operands: a K step is again 128 bytes per row -- 32 elements as four [8 hi | 8 lo] storage
-// groups -- so the rings (A: 2 slots, W: 3 slots = all 160 KiB of LDS), the two MFMA phases per K step, the hand-off rules and the tile
-// switch are those of the fp8 kernel, comment for comment.  What differs:
-//   * the source-side chunk permutation also DE-INTERLEAVES the planes (as in gemm_bf16_ring<SPLIT>): LDS chunks 0-3 of a row hold the four
-//     hi chunks, 4-7 the four lo chunks, so fragment h[0] (chunk g) is the hi plane and h[1] (chunk 4 + g) the lo plane of the lane's 8 K values;
-//   * a 16 x 16 output takes THREE v_mfma_f32_16x16x32_f16 per K step (W_hi.A_hi + W_lo.A_hi + W_hi.A_lo): 48 MFMAs = 768 cycles per phase
-//     against the same READ segments as the fp8 kernel (16 / 8 ds_read_b128 + 4 LDS-DMA pieces) -- the matrix pipe has 1.5x the cover;
-//   * operand rows are 4 bytes per element (the fc output of a 128-tile launch is 2.9 GB), so a tile keeps a 64-bit base per operand and
-//     32-bit offsets inside its 256 rows;
-//   * the epilogue is epilogue_store8<.., SPLIT>: bias / exact activation / f32 residual / f32 or two-plane output, no scales.
-// `a` arrives as gemm_h2 prepared it: K, lda, ldw in f16 UNITS (2 x the element counts), C / residual strides in elements.
-// SPEC as epilogue_store8's: 0 = every choice at run time, 1 / 2 / 3 = two-plane output after no activation / QuickGELU / GELU (QKV, fc),
-// 4 = f32 output + f32 residual (out-proj, proj).
-template <int SPEC, int EPI = 0>
-__global__ __launch_bounds__(512) void gemm_h2_persist(GemmBf16Args a, int act, int c_bf16) {
-  constexpr int PBM = 256, PBN = 256, KB = 128;                          // K step in bytes
+template <int OP, int EPI, int SPEC>
+__device__ __forceinline__ void gemm_persist128(const GemmBf16Args& a, int act, int c_bf16) {
+  constexpr bool FP8 = OP == OP_FP8, H2 = OP == OP_H2;
+  static_assert(!FP8 || (EPI == 0 && SPEC == 0), "fp8: the run-time epilogue of epilogue_store8_fp8 only");
+  constexpr int EB = FP8 ? 1 : 2;                                        // bytes per unit of a.K / lda / ldw / strides
+  constexpr int KB = 128;                                                // K step in bytes
   constexpr int SLOT = 256 * KB;                                         // 32 KiB
   extern __shared__ __attribute__((aligned(16))) char lds[];
   char* ldsA = lds;                                                      // 2 slots
   char* ldsW = lds + 2 * SLOT;                                           // 3 slots
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = wave >> 2, wi = wave & 3;
-  const int tiles_n = (a.N + PBN - 1) / PBN, tiles_m = (a.M + PBM - 1) / PBM;
-  const int nwg = tiles_m * tiles_n;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const char* A = reinterpret_cast<const char*>(a.A);
-  const char* W = reinterpret_cast<const char*>(a.W);
-  const int64_t lda_b = a.lda * 2, ldw_b = a.ldw * 2;                    // row strides in bytes
-  const int nt = a.K * 2 / KB;
-  const int my_tiles = (nwg - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
+  const PersistOrder order(a, FP8 ? 0 : a.ngroup);                      // (fp8 launches never take the N-group order: a compile-time 0 keeps it at 0 B scratch)
+  const int z = blockIdx.y;
+  const char* A = reinterpret_cast<const char*>(a.A) + (int64_t)z * a.strideA * EB;
+  const char* W = reinterpret_cast<const char*>(a.W) + (int64_t)z * a.strideW * EB;
+  const int64_t lda_b = a.lda * EB, ldw_b = a.ldw * EB;                  // row strides in bytes
+  const int nt = a.K / (KB / EB);
+  const int my_tiles = order.count;
   const int total = my_tiles * nt;                                       // length of this workgroup's K-step stream
 
   const int srow = lane >> 3, cpos = lane & 7;
-  // plane-de-interleaving swizzle: LDS chunk cpos of row r holds logical chunk L = cpos ^ ((r >> 1) & 7) = 4 * plane + group, which lives at
-  // global chunk 2 * group + plane.  Pieces are 8 rows apart, so the swizzle term depends on the lane and on the parity of the piece only.
-  auto gchunk = [](int L) { return ((L & 3) << 1) | (L >> 2); };
+  // LDS chunk c of a row holds source chunk gchunk(c ^ ((row >> 1) & 7)).  Two-plane operands: that logical chunk L = 4 * plane + group lives
+  // at source chunk 2 * group + plane.  Pieces are 8 rows apart and start at a multiple of 32 rows, so the swizzle term depends on the lane and
+  // on the parity of the piece only.
+  auto gchunk = [](int L) { return H2 ? ((L & 3) << 1) | (L >> 2) : L; };
   const int swz_e = gchunk(cpos ^ (srow >> 1)) << 4, swz_o = gchunk(cpos ^ (4 + (srow >> 1))) << 4;
-  struct Src { const char* Ab; const char* Wb; int m0, n0; };            // 64-bit tile bases (wave-uniform)
+  // Rows are addressed from a 64-bit tile base with 32-bit offsets inside the tile.  fp8 addresses them from the operand base instead (absolute
+  // rows, 32-bit offsets: M * lda < 2^31, checked by the dispatch): the tile bases cost it scratch next to its 256 VGPRs.
+  struct Src { const char* Ab; const char* Wb; int m0, n0; };            // wave-uniform
   const int ra0 = 128 * g + 32 * wi + srow, rw0 = 64 * wi + 32 * g + srow;   // this lane's first piece row inside any tile
   auto make_src = [&](int j) {
     Src sp;
-    const int v = (int)blockIdx.x + j * (int)gridDim.x;                  // XCD x = v & 7 walks a contiguous chunk of tile ids
-    const int xcd = v & 7, seq = v >> 3;
-    int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + seq;
-    tile = tile < nwg ? tile : nwg - 1;
-    sp.m0 = (tile / tiles_n) * PBM; sp.n0 = (tile % tiles_n) * PBN;
-    sp.Ab = A + (int64_t)sp.m0 * lda_b; sp.Wb = W + (int64_t)sp.n0 * ldw_b;
+    order.tile(j, sp.m0, sp.n0);
+    sp.Ab = FP8 ? A : A + (int64_t)sp.m0 * lda_b; sp.Wb = FP8 ? W : W + (int64_t)sp.n0 * ldw_b;
     return sp;
   };
+  auto row_a = [&](const Src& sp, int p) { int r = (FP8 ? sp.m0 : 0) + ra0 + 8 * p; const int rmax = a.M - 1 - (FP8 ? 0 : sp.m0); return r < rmax ? r : rmax; };
+  auto row_w = [&](const Src& sp, int p) { int r = (FP8 ? sp.n0 : 0) + rw0 + 8 * p; const int rmax = a.N - 1 - (FP8 ? 0 : sp.n0); return r < rmax ? r : rmax; };
   Src cur = make_src(0);
   Src nxt = make_src(my_tiles > 1 ? 1 : 0);
   int cur_end = nt;                                                      // stream index where `nxt` begins
-  const int lda_i = (int)lda_b, ldw_i = (int)ldw_b;                      // < 2^23 (checked on the host): offsets inside a 256-row tile fit 32 bits
+  const int lda_i = (int)lda_b, ldw_i = (int)ldw_b;
   auto load_a = [&](int u) {                                             // this wave's pieces of A_g(u)
     if (u >= total) return;
     const bool nx = u >= cur_end;
     const Src& sp = nx ? nxt : cur;
     const int kt = nx ? u - cur_end : u - (cur_end - nt);
-    const int rmax = a.M - 1 - sp.m0;                                    // rows past the edge re-read the last row (never stored)
     char* base = ldsA + (u & 1) * SLOT + (128 * g + 32 * wi) * KB;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-      int r = ra0 + 8 * p; r = r < rmax ? r : rmax;
+      const int r = row_a(sp, p);                                        // rows past the edge re-read the last row (never stored)
       const int off = r * lda_i + ((p & 1) ? swz_o : swz_e) + kt * KB;
       __builtin_amdgcn_global_load_lds((gbl_ptr_t)(sp.Ab + off), (lds_ptr_t)(base + p * 8 * KB), 16, 0, 0);
     }
@@ -1831,16 +1447,15 @@ __global__ __launch_bounds__(512) void gemm_h2_persist(GemmBf16Args a, int act, 
     const bool nx = u >= cur_end;
     const Src& sp = nx ? nxt : cur;
     const int kt = nx ? u - cur_end : u - (cur_end - nt);
-    const int rmax = a.N - 1 - sp.n0;
     char* base = ldsW + (u % 3) * SLOT + (64 * wi + 32 * g) * KB;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-      int r = rw0 + 8 * p; r = r < rmax ? r : rmax;
+      const int r = row_w(sp, p);
       const int off = r * ldw_i + ((p & 1) ? swz_o : swz_e) + kt * KB;
       __builtin_amdgcn_global_load_lds((gbl_ptr_t)(sp.Wb + off), (lds_ptr_t)(base + p * 8 * KB), 16, 0, 0);
     }
   };
-#define SG_H2_SYNC()                                 \
+#define SG_P128_SYNC()                               \
   do {                                               \
     __builtin_amdgcn_sched_barrier(0);               \
     __builtin_amdgcn_s_barrier();                    \
@@ -1852,117 +1467,127 @@ __global__ __launch_bounds__(512) void gemm_h2_persist(GemmBf16Args a, int act, 
   load_a(0); load_w(0); load_w(1);
   if (g == 1) { load_w(2); if (2 < total) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
   else { if (1 < total) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
-  SG_H2_SYNC();
-  if (g == 1) SG_H2_SYNC();
+  SG_P128_SYNC();
+  if (g == 1) SG_P128_SYNC();
 
   f32x4 acc[8][4];
-  bf16x8 fah[4], fal[4], fwh[4], fwl[4];                                 // hi / lo planes of the lane's 8 K values
+  FragPair fa[4], fw[4];
+  float rs_pre[2] = {1.f, 1.f};                                          // fp8: this wave's 128 row scales, fetched in a tile's last K step
   int s = 0;
   for (int j = 0; j < my_tiles; ++j) {
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) acc[i][jj] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int kt = 0; kt < nt; ++kt, ++s) {
+    int kt = 0;
+    // One K step.  STEADY: every piece this step requests (A(s+1), W(s+2+g)) belongs to the current output tile -- no source select, no
+    // end-of-stream test; the last three steps of a tile take the general form (measured on bf16: +1.0 % on the bench line against the
+    // general form throughout, which is 2-4 % faster on the run-time epilogue form alone)
+    auto kstep = [&](auto steady_tag) {
+      constexpr bool STEADY = decltype(steady_tag)::value;
       const char* tA = ldsA + (s & 1) * SLOT;
       const char* tW = ldsW + (s % 3) * SLOT;
       // READ0(s): W fragments (kept for both phases) + A rows 0-63 of the group's half; issue A_g(s+1)
 #pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        fwh[jj] = read_frag(tW, 64 * wi + 16 * jj + (lane & 15), lane >> 4);
-        fwl[jj] = read_frag(tW, 64 * wi + 16 * jj + (lane & 15), 4 + (lane >> 4));
+      for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) fw[jj].h[h] = read_frag(tW, 64 * wi + 16 * jj + (lane & 15), h * 4 + (lane >> 4));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) fa[i].h[h] = read_frag(tA, 128 * g + 16 * i + (lane & 15), h * 4 + (lane >> 4));
       }
+      if constexpr (STEADY) {
+        char* base = ldsA + ((s + 1) & 1) * SLOT + (128 * g + 32 * wi) * KB;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        fah[i] = read_frag(tA, 128 * g + 16 * i + (lane & 15), lane >> 4);
-        fal[i] = read_frag(tA, 128 * g + 16 * i + (lane & 15), 4 + (lane >> 4));
-      }
-      load_a(s + 1);
-      SG_H2_SYNC();
-      // MFMA0(s)
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-          acc[i][jj] = mfma_16x16x32<true>(fwh[jj], fah[i], acc[i][jj]);
-          acc[i][jj] = mfma_16x16x32<true>(fwl[jj], fah[i], acc[i][jj]);
-          acc[i][jj] = mfma_16x16x32<true>(fwh[jj], fal[i], acc[i][jj]);
+        for (int p = 0; p < 4; ++p) {
+          const int r = row_a(cur, p);
+          __builtin_amdgcn_global_load_lds((gbl_ptr_t)(cur.Ab + (r * lda_i + ((p & 1) ? swz_o : swz_e) + (kt + 1) * KB)), (lds_ptr_t)(base + p * 8 * KB), 16, 0, 0);
         }
-      __builtin_amdgcn_s_setprio(0);
-      SG_H2_SYNC();
+      } else load_a(s + 1);
+      SG_P128_SYNC();
+      // MFMA0(s)
+      persist128_mfma<OP>(acc, 0, fa, fw);
+      SG_P128_SYNC();
       // READ1(s): A rows 64-127; issue this group's rows of W(s+2) / W(s+3)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        fah[i] = read_frag(tA, 128 * g + 64 + 16 * i + (lane & 15), lane >> 4);
-        fal[i] = read_frag(tA, 128 * g + 64 + 16 * i + (lane & 15), 4 + (lane >> 4));
-      }
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) fa[i].h[h] = read_frag(tA, 128 * g + 64 + 16 * i + (lane & 15), h * 4 + (lane >> 4));
       const int uw = s + 2 + g;
-      load_w(uw);
-      SG_H2_SYNC();
-      // MFMA1(s)
-      __builtin_amdgcn_s_setprio(1);
+      if constexpr (STEADY) {
+        char* base = ldsW + (uw % 3) * SLOT + (64 * wi + 32 * g) * KB;
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-          acc[4 + i][jj] = mfma_16x16x32<true>(fwh[jj], fah[i], acc[4 + i][jj]);
-          acc[4 + i][jj] = mfma_16x16x32<true>(fwl[jj], fah[i], acc[4 + i][jj]);
-          acc[4 + i][jj] = mfma_16x16x32<true>(fwh[jj], fal[i], acc[4 + i][jj]);
+        for (int p = 0; p < 4; ++p) {
+          const int r = row_w(cur, p);
+          __builtin_amdgcn_global_load_lds((gbl_ptr_t)(cur.Wb + (r * ldw_i + ((p & 1) ? swz_o : swz_e) + (kt + 2 + g) * KB)), (lds_ptr_t)(base + p * 8 * KB), 16, 0, 0);
         }
-      __builtin_amdgcn_s_setprio(0);
-      if (uw < total) wait_vmcnt<4>(); else wait_vmcnt<0>();             // all but the W pieces just issued
-      SG_H2_SYNC();
-    }
+      } else {
+        load_w(uw);
+        if (FP8 && kt == nt - 1) {                                        // last K step of the tile: the row scales for the epilogue
+#pragma unroll
+          for (int u2 = 0; u2 < 2; ++u2) { int m = cur.m0 + 128 * g + u2 * 64 + lane; m = m < a.M ? m : a.M - 1; rs_pre[u2] = a.row_scale[m]; }
+        }
+      }
+      SG_P128_SYNC();
+      // MFMA1(s)
+      persist128_mfma<OP>(acc, 4, fa, fw);
+      if (FP8 && !STEADY && kt == nt - 1) wait_vmcnt<0>();              // fp8 tile end: the row scales too (issued after the W pieces)
+      else if (STEADY || uw < total) wait_vmcnt<4>(); else wait_vmcnt<0>();   // all but the W pieces just issued
+      SG_P128_SYNC();
+      ++kt; ++s;
+    };
+    // steady split: bf16 / f16 only.  With it, fp8 spills 20 B and the two-plane run-time form <0,0> 132 B instead of 52
+    if constexpr (!FP8 && !H2) { while (kt + 3 < nt) kstep(std::true_type{}); }
+    while (kt < nt) kstep(std::false_type{});
     // ---- tile end ----
-    if (g == 0) SG_H2_SYNC();                                            // align: every read of this tile's last K step has retired
+    if (g == 0) SG_P128_SYNC();                                          // align: every read of this tile's last K step has retired
     {
-      float* pbase = reinterpret_cast<float*>(ldsA + ((s - 1) & 1) * SLOT);    // the consumed A slot: 8 patches of 8 rows x 68 floats (+pad)
-      epilogue_store8<8, 4, true, EPI, SPEC, true>(acc, a, act, c_bf16, 0, cur.m0 + 128 * g, cur.n0 + 64 * wi, pbase + wave * 576, lane, pbase + 8 * 576 + wave * 256);
+      float* pbase = reinterpret_cast<float*>(ldsA + ((s - 1) & 1) * SLOT);    // the consumed A slot: 8 patches of 8 rows x 68 floats (+pad), then
+      if constexpr (FP8)                                                       // 8 x 128 row scales (fp8) / 1 KiB per wave (statistics)
+        epilogue_store8_fp8<8, 4>(acc, a, act, c_bf16, cur.m0 + 128 * g, cur.n0 + 64 * wi, pbase + wave * 576, pbase + 8 * 576 + wave * 128, lane, rs_pre);
+      else
+        epilogue_store8<8, 4, OP != OP_BF16, EPI, SPEC, H2>(acc, a, act, c_bf16, z, cur.m0 + 128 * g, cur.n0 + 64 * wi, pbase + wave * 576, lane,
+                                                            pbase + 8 * 576 + wave * 256);
     }
     cur = nxt; cur_end += nt;
     if (j + 2 < my_tiles) nxt = make_src(j + 2);
-    SG_H2_SYNC();                                                        // the A slot used as patch is refilled from READ0 of the next step on
-    if (g == 1 && j + 1 < my_tiles) SG_H2_SYNC();                        // re-stagger
+    SG_P128_SYNC();                                                      // the A slot used as patch is refilled from READ0 of the next step on
+    if (g == 1 && j + 1 < my_tiles) SG_P128_SYNC();                      // re-stagger
   }
-#undef SG_H2_SYNC
+#undef SG_P128_SYNC
 }
 
-static int launch_h2_persist(const GemmBf16Args& h, hipStream_t s) {
-  const size_t lds = 5 * 256 * 128;                                      // 160 KiB: the whole LDS of a CU
-  using Kern = void (*)(GemmBf16Args, int, int);
-  // epilogue form: folded-LayerNorm consumer (two-plane output, activation per layer kind) / producer (f32 + residual, two-plane copy, slice
-  // statistics) / plain
-  Kern kern;
-  if (h.ln_stats) kern = h.act == ACT_NONE ? gemm_h2_persist<1, 1> : h.act == ACT_QUICK_GELU ? gemm_h2_persist<2, 1> : gemm_h2_persist<3, 1>;
-  else if (h.copy16) kern = gemm_h2_persist<1, 2>;
-  else kern = (h.c_is_bf16 && !h.residual) ? (h.act == ACT_NONE ? gemm_h2_persist<1> : h.act == ACT_QUICK_GELU ? gemm_h2_persist<2> : gemm_h2_persist<3>)
-            : (!h.c_is_bf16 && h.residual && h.act == ACT_NONE) ? gemm_h2_persist<4> : gemm_h2_persist<0>;
-  SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
-  const int n_cu = device_cu_count();
-  const int64_t tiles = cdiv(h.M, 256) * cdiv(h.N, 256);
-  SG_REQUIRE(tiles < (1ll << 31), "gemm_h2: grid too large");
-  unsigned grid = (unsigned)(tiles < n_cu ? tiles : n_cu);
-  if (g_persist_grid_cap > 0 && grid > (unsigned)g_persist_grid_cap) grid = (unsigned)g_persist_grid_cap;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, h, h.act, h.c_is_bf16);
-  note_launch("h2_persist", grid);
-  return SG_OK;
-}
+// The three entry points of gemm_persist128.  SPEC / EPI as epilogue_store8's MODE / SPEC: bf16 / f16 and two-plane take 0 = every choice at
+// run time, 1 / 2 / 3 = 2-byte (two-plane) output after no activation / QuickGELU / GELU, 4 = f32 output + f32 residual; bf16 also 5 = the
+// row-dot form.  EPI 1 / 2 = the consumer / producer side of a folded LayerNorm.  fp8 has the run-time form only.
+template <bool F16, int EPI = 0, int SPEC = 0>
+__global__ __launch_bounds__(512) void gemm_bf16_persist_k64(GemmBf16Args a, int act, int c_bf16) { gemm_persist128<F16 ? OP_F16 : OP_BF16, EPI, SPEC>(a, act, c_bf16); }
+template <bool DUMMY = false>
+__global__ __launch_bounds__(512) void gemm_fp8_persist(GemmBf16Args a, int act, int c_bf16) { gemm_persist128<OP_FP8, 0, 0>(a, act, c_bf16); }
+template <int SPEC, int EPI = 0>
+__global__ __launch_bounds__(512) void gemm_h2_persist(GemmBf16Args a, int act, int c_bf16) { gemm_persist128<OP_H2, EPI, SPEC>(a, act, c_bf16); }
 
-// The persistent kernel of a launch: gemm_bf16_persist_k64 (128-byte K steps) when K % 64 == 0, K / 64 >= 4 and the operand rows are
-// shorter than 2^21 elements (its 32-bit in-tile offsets); otherwise, and under tuning code 38 (the same-process baseline), the
-// 32-element gemm_bf16_persist.  Both compute the same bits.
+// The launch of every persistent kernel.  fp8 and two-plane operands run on their 128-byte kernels (the dispatch has checked K and the
+// strides).  bf16 / f16: gemm_bf16_persist_k64 when K % 64 == 0, K / 64 >= 4 and the operand rows are shorter than 2^21 elements (its 32-bit
+// in-tile offsets); otherwise, and under tuning code 38 (the same-process baseline), the 32-element gemm_bf16_persist.  Both compute the same bits.
 using PersistKern = void (*)(GemmBf16Args, int, int);
 template <bool F16, int EPI, int SPEC>
 static PersistKern persist_kernel(bool k64) { return k64 ? gemm_bf16_persist_k64<F16, EPI, SPEC> : gemm_bf16_persist<F16, EPI, SPEC>; }
-static thread_local int g_persist_kstep = 0;              // K step of the calling thread's last persistent launch (sg_gemm_persist_last_kstep)
+static thread_local int g_persist_kstep = 0;              // K step of the calling thread's last persistent bf16 / f16 launch (sg_gemm_persist_last_kstep)
 int gemm_persist_last_kstep() { return g_persist_kstep; }
 static int launch_persist(const GemmBf16Args& a, hipStream_t s) {
-  const bool k64 = g_gemm_config != 38 && a.K % 64 == 0 && a.K / 64 >= 4 && a.lda < (1 << 21) && a.ldw < (1 << 21);
+  const bool two_byte = !a.fp8 && !a.h2;
+  const bool k64 = !two_byte || (g_gemm_config != 38 && a.K % 64 == 0 && a.K / 64 >= 4 && a.lda < (1 << 21) && a.ldw < (1 << 21));
   const size_t lds = k64 ? 5 * 256 * 128 : 4 * (256 + 256) * 32 * 2;   // 160 KiB (A ring 2 + W ring 3 slots) / 128 KiB (4 slots)
   // instantiation: epilogue form (plain / folded-LayerNorm consumer / producer) x compile-time specialisation of the hot combinations
   PersistKern kern;
-  if (a.ln_stats) {                                         // consumer: 2-byte output, activation per layer kind
+  if (a.fp8) {
+    kern = gemm_fp8_persist<false>;
+  } else if (a.h2) {                                        // consumer (two-plane output, activation per layer kind) / producer / plain
+    if (a.ln_stats) kern = a.act == ACT_NONE ? gemm_h2_persist<1, 1> : a.act == ACT_QUICK_GELU ? gemm_h2_persist<2, 1> : gemm_h2_persist<3, 1>;
+    else if (a.copy16) kern = gemm_h2_persist<1, 2>;
+    else kern = (a.c_is_bf16 && !a.residual) ? (a.act == ACT_NONE ? gemm_h2_persist<1> : a.act == ACT_QUICK_GELU ? gemm_h2_persist<2> : gemm_h2_persist<3>)
+              : (!a.c_is_bf16 && a.residual && a.act == ACT_NONE) ? gemm_h2_persist<4> : gemm_h2_persist<0>;
+  } else if (a.ln_stats) {                                  // consumer: 2-byte output, activation per layer kind
     kern = a.act == ACT_NONE ? (a.f16 ? persist_kernel<true, 1, 1>(k64) : persist_kernel<false, 1, 1>(k64))
          : a.act == ACT_QUICK_GELU ? (a.f16 ? persist_kernel<true, 1, 2>(k64) : persist_kernel<false, 1, 2>(k64))
                                    : (a.f16 ? persist_kernel<true, 1, 3>(k64) : persist_kernel<false, 1, 3>(k64));
@@ -1981,24 +1606,24 @@ static int launch_persist(const GemmBf16Args& a, hipStream_t s) {
   SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
   const int n_cu = device_cu_count();
   const int64_t tiles = cdiv(a.M, 256) * cdiv(a.N, 256);
-  SG_REQUIRE(tiles < (1ll << 31) && a.batch < 65536, "gemm_bf16: grid too large");
+  SG_REQUIRE(tiles < (1ll << 31) && a.batch < 65536, "%s: grid too large", a.fp8 ? "gemm_fp8" : a.h2 ? "gemm_h2" : "gemm_bf16");
   unsigned grid = (unsigned)(tiles < n_cu ? tiles : n_cu);
   if (g_persist_grid_cap > 0 && grid > (unsigned)g_persist_grid_cap) grid = (unsigned)g_persist_grid_cap;
   GemmBf16Args b = a;
-  // W-panel-resident order where it pays: more N tiles than fit the L2 together and a short K (re-reading the A panels once per
+  // bf16 / f16: W-panel-resident order where it pays: more N tiles than fit the L2 together and a short K (re-reading the A panels once per
   // N-group must cost less than re-streaming every W panel once per round): the K = 1024 linears with N = 3072 / 4096
   const int64_t tiles_m = cdiv(a.M, 256), tiles_n = cdiv(a.N, 256);
   const int64_t panel = (int64_t)256 * a.K * 2;
   b.ngroup = 0;
-  if (g_gemm_order != 0 && a.batch == 1 && grid == (unsigned)n_cu && n_cu % 8 == 0 && (tiles_m / 8) * tiles_n >= n_cu / 8 && a.K <= 2048) {
+  if (two_byte && g_gemm_order != 0 && a.batch == 1 && grid == (unsigned)n_cu && n_cu % 8 == 0 && (tiles_m / 8) * tiles_n >= n_cu / 8 && a.K <= 2048) {
     const int ng = (int)((3 << 20) / panel);               // 3 MiB of W panels per XCD next to the streaming A panels (measured: 6 N tiles at K = 1024
                                                            // run at the raster order's speed with 40 % less fabric traffic; 4 and 2 are 3-7 % slower: the A
                                                            // panels are re-read once per N-group, so few large groups beat many small ones)
     if (ng >= 1 && tiles_n > ng) b.ngroup = g_gemm_order > 0 ? g_gemm_order : ng;
   }
   hipLaunchKernelGGL(kern, dim3(grid, (unsigned)a.batch), dim3(512), lds, s, b, a.act, a.c_is_bf16);
-  g_persist_kstep = k64 ? 64 : 32;
-  note_launch(k64 ? "persist_k64" : "persist_k32", grid, b.ngroup);
+  if (two_byte) g_persist_kstep = k64 ? 64 : 32;
+  note_launch(a.fp8 ? "fp8_persist" : a.h2 ? "h2_persist" : k64 ? "persist_k64" : "persist_k32", grid, b.ngroup);
   return SG_OK;
 }
 
@@ -2017,9 +1642,8 @@ void set_gemm_config(int c) {
 
 
 // kernel-family name of a ring configuration (sg_gemm_last_kernel); ring128 is the default small-launch tile, the others are tuning codes
-template <int BM_, int BN_, int STAGES, int ABLATE, int BKT, bool FP8, bool SPLIT>
+template <int BM_, int BN_, int STAGES, int BKT, bool FP8, bool SPLIT>
 constexpr const char* ring_name() {
-  if (ABLATE) return "ring_ablation";
   if (FP8) return BM_ == 128 ? "fp8_ring128" : "fp8_ring256x256";
   if (SPLIT) return "h2_ring128";
   if (BKT == 32) return BM_ == 128 ? "ring128x256_k32" : "ring256x128_k32";
@@ -2028,15 +1652,15 @@ constexpr const char* ring_name() {
   if (BM_ == 128 && BN_ == 256) return "ring128x256_s3";
   return "ring256x256";
 }
-template <int BM_, int BN_, int WM, int WN, int STAGES, int ABLATE = 0, int BKT = 64, bool FP8 = false, bool F16 = false, bool MXA = false, int SPEC = 0, bool SPLIT = false>
+template <int BM_, int BN_, int WM, int WN, int STAGES, int BKT = 64, bool FP8 = false, bool F16 = false, bool MXA = false, int SPEC = 0, bool SPLIT = false>
 static int launch_ring(const GemmBf16Args& a, int vec, hipStream_t s) {
-  auto kern = gemm_bf16_ring<BM_, BN_, WM, WN, STAGES, ABLATE, BKT, FP8, F16, MXA, SPEC, SPLIT>;
+  auto kern = gemm_bf16_ring<BM_, BN_, WM, WN, STAGES, BKT, FP8, F16, MXA, SPEC, SPLIT>;
   const size_t lds = (size_t)STAGES * ((BM_ + BN_) * BKT * 2 + (MXA ? BM_ * 4 : 0));
   if (lds > 48 * 1024) SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
   const int64_t tiles = cdiv(a.M, BM_) * cdiv(a.N, BN_);
   SG_REQUIRE(tiles < (1ll << 31) && a.batch < 65536, "gemm_bf16: grid too large");
   hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)a.batch), dim3(WM * WN * 64), lds, s, a, a.act, a.c_is_bf16, vec);
-  note_launch(FP8 && (a.a_mx || a.c_mx) ? "fp8_mx_ring256x256" : ring_name<BM_, BN_, STAGES, ABLATE, BKT, FP8, SPLIT>(), tiles);
+  note_launch(FP8 && (a.a_mx || a.c_mx) ? "fp8_mx_ring256x256" : ring_name<BM_, BN_, STAGES, BKT, FP8, SPLIT>(), tiles);
   return SG_OK;
 }
 
@@ -2069,11 +1693,11 @@ static int gemm_fp8(const GemmBf16Args& a, hipStream_t s) {
     // the tower's MLP hand-off runs on compile-time-specialised epilogues: fc -> MX output after the activation, proj <- MX operand, f32 + residual
     const bool proj_form = a.a_mx && !a.c_mx && !a.c_is_bf16 && a.residual && a.act == ACT_NONE;
     const bool fc_form = !a.a_mx && a.c_mx && (a.act == ACT_QUICK_GELU || a.act == ACT_GELU);
-    const int rcm = proj_form ? launch_ring<256, 256, 2, 4, 2, 0, 64, true, false, true, 4>(h, vec, s)
-                  : a.a_mx ? launch_ring<256, 256, 2, 4, 2, 0, 64, true, false, true>(h, vec, s)
-                  : fc_form ? (a.act == ACT_QUICK_GELU ? launch_ring<256, 256, 2, 4, 2, 0, 64, true, false, false, 2>(h, vec, s)
-                                                       : launch_ring<256, 256, 2, 4, 2, 0, 64, true, false, false, 3>(h, vec, s))
-                            : launch_ring<256, 256, 2, 4, 2, 0, 64, true>(h, vec, s);
+    const int rcm = proj_form ? launch_ring<256, 256, 2, 4, 2, 64, true, false, true, 4>(h, vec, s)
+                  : a.a_mx ? launch_ring<256, 256, 2, 4, 2, 64, true, false, true>(h, vec, s)
+                  : fc_form ? (a.act == ACT_QUICK_GELU ? launch_ring<256, 256, 2, 4, 2, 64, true, false, false, 2>(h, vec, s)
+                                                       : launch_ring<256, 256, 2, 4, 2, 64, true, false, false, 3>(h, vec, s))
+                            : launch_ring<256, 256, 2, 4, 2, 64, true>(h, vec, s);
     prof_end(PROF_GEMM_FP8, s);
     if (rcm != SG_OK) return rcm;
     SG_LAUNCH_CHECK();
@@ -2081,10 +1705,10 @@ static int gemm_fp8(const GemmBf16Args& a, hipStream_t s) {
   }
   const bool persist = vec && a.batch == 1 && a.M >= 1024 && a.N >= 512 && (a.K >= 2048 || g_gemm_config == 32) && a.K >= 512 && g_gemm_config != 31 &&
                        (int64_t)a.M * a.lda < (1ll << 31) && (int64_t)a.N * a.ldw < (1ll << 31);     // 32-bit byte offsets inside the kernel
-  const int rc = persist ? launch_fp8_persist(a, s)
-               : (a.M >= 1024 && a.N >= 256) ? ((vec && a.c_is_bf16 && !a.residual && a.act == ACT_NONE) ? launch_ring<256, 256, 2, 4, 2, 0, 64, true, false, false, 1>(h, vec, s)
-                                                                                                      : launch_ring<256, 256, 2, 4, 2, 0, 64, true>(h, vec, s))
-                                             : launch_ring<128, 128, 2, 2, 3, 0, 64, true>(h, vec, s);
+  const int rc = persist ? launch_persist(a, s)
+               : (a.M >= 1024 && a.N >= 256) ? ((vec && a.c_is_bf16 && !a.residual && a.act == ACT_NONE) ? launch_ring<256, 256, 2, 4, 2, 64, true, false, false, 1>(h, vec, s)
+                                                                                                      : launch_ring<256, 256, 2, 4, 2, 64, true>(h, vec, s))
+                                             : launch_ring<128, 128, 2, 2, 3, 64, true>(h, vec, s);
   prof_end(PROF_GEMM_FP8, s);
   if (rc != SG_OK) return rc;
   SG_LAUNCH_CHECK();
@@ -2120,7 +1744,7 @@ static int gemm_h2(const GemmBf16Args& a, hipStream_t s) {
   }
   const bool persist = ln_fold || (big && vec && hot_form && fits && g_gemm_config != 37);
   prof_begin(PROF_GEMM_H2, 2.0 * a.M * (double)a.N * a.K * a.batch, s);
-  const int rc = persist ? launch_h2_persist(h, s) : big ? launch_pingpong(h, vec, s) : launch_ring<128, 128, 2, 2, 2, 0, 64, false, true, false, 0, true>(h, vec, s);
+  const int rc = persist ? launch_persist(h, s) : big ? launch_pingpong(h, vec, s) : launch_ring<128, 128, 2, 2, 2, 64, false, true, false, 0, true>(h, vec, s);
   prof_end(PROF_GEMM_H2, s);
   if (rc != SG_OK) return rc;
   SG_LAUNCH_CHECK();
@@ -2173,7 +1797,7 @@ int gemm_bf16(const GemmBf16Args& a, hipStream_t s) {
         const int sp = !vec || a.c_mx || a.row_scale || a.col_scale ? 0
                      : (a.c_is_bf16 && !a.residual) ? (a.act == ACT_NONE ? 1 : a.act == ACT_QUICK_GELU ? 6 : 7)
                      : (!a.c_is_bf16 && a.residual && a.act == ACT_NONE) ? 4 : 0;
-#define SG_RING128(SP) (a.f16 ? launch_ring<128, 128, 2, 2, 2, 0, 64, false, true, false, SP>(a, vec, s) : launch_ring<128, 128, 2, 2, 2, 0, 64, false, false, false, SP>(a, vec, s))
+#define SG_RING128(SP) (a.f16 ? launch_ring<128, 128, 2, 2, 2, 64, false, true, false, SP>(a, vec, s) : launch_ring<128, 128, 2, 2, 2, 64, false, false, false, SP>(a, vec, s))
         rc = sp == 1 ? SG_RING128(1) : sp == 4 ? SG_RING128(4) : sp == 6 ? SG_RING128(6) : sp == 7 ? SG_RING128(7) : SG_RING128(0);
 #undef SG_RING128
         break;
@@ -2182,23 +1806,9 @@ int gemm_bf16(const GemmBf16Args& a, hipStream_t s) {
       case 6: rc = launch_ring<128, 256, 2, 4, 3>(a, vec, s); break;
       case 7: rc = launch_pingpong(a, vec, s); break;
       case 30: rc = (vec && a.K / 32 >= 4) ? launch_persist(a, s) : launch_pingpong(a, vec, s); break;
-      case 9: rc = launch_ring<128, 256, 1, 4, 3, 0, 32>(a, vec, s); break;    // 72 KiB LDS: two workgroups per CU
-      case 10: rc = launch_ring<256, 128, 4, 1, 3, 0, 32>(a, vec, s); break;
-      case 8: rc = vec ? launch_pp32<0>(a, s) : launch_pingpong(a, vec, s); break;
-#ifdef SG_GEMM_ABLATIONS                                   // tuning builds only: these variants drop loads / MFMAs / stores and return WRONG results
-      case 21: rc = launch_pp32<1>(a, s); break;          // ablations of the pp32 kernel (wrong results by design)
-      case 22: rc = launch_pp32<2>(a, s); break;
-      case 23: rc = launch_pp32<3>(a, s); break;
-      case 24: rc = launch_pp32<4>(a, s); break;
-      case 11: rc = launch_ring<256, 256, 2, 4, 2, 1>(a, vec, s); break;   // ablations (wrong results by design)
-      case 12: rc = launch_ring<256, 256, 2, 4, 2, 2>(a, vec, s); break;
-      case 13: rc = launch_ring<128, 128, 2, 2, 2, 1>(a, vec, s); break;
-      case 15: rc = launch_ring<256, 256, 2, 4, 2, 3>(a, vec, s); break;
-      case 16: rc = launch_ring<256, 256, 2, 4, 2, 4>(a, vec, s); break;
-      case 17: rc = launch_ring<128, 128, 2, 2, 2, 3>(a, vec, s); break;
-      case 18: rc = launch_ring<128, 128, 2, 2, 2, 4>(a, vec, s); break;
-      case 14: rc = launch_ring<128, 128, 2, 2, 2, 2>(a, vec, s); break;
-#endif
+      case 9: rc = launch_ring<128, 256, 1, 4, 3, 32>(a, vec, s); break;    // 72 KiB LDS: two workgroups per CU
+      case 10: rc = launch_ring<256, 128, 4, 1, 3, 32>(a, vec, s); break;
+      case 8: rc = vec ? launch_pp32(a, s) : launch_pingpong(a, vec, s); break;
       default: return fail(SG_ERR_INVALID, "gemm_bf16: unknown tile config %d", cfg);
     }
     prof_end(pcat, s);

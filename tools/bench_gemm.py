@@ -40,7 +40,7 @@ for name, m, n, k, act, cbf in SHAPES:
                 x = x + R
             ref = x
         err = ((out - ref).abs().max() / ref.abs().max()).item()
-        assert err < 2e-2 or (cfg >= 10 and cfg != 30) or os.environ.get("GEMM_NOCHECK"), (name, cfg, err)   # GEMM_NOCHECK: ablated builds (tools/ablate_persist.sh)
+        assert err < 2e-2, (name, cfg, err)   # every tile configuration computes the same GEMM
     for rnd in range(ROUNDS):
         for cfg in CONFIGS:
             lib.sg_set_gemm_config(cfg)

@@ -1,6 +1,6 @@
 // What does a CU's store path sustain?  The persistent GEMM's epilogue writes 128 KiB (bf16) / 256 KiB (f32) per output tile with
 // 16-byte-per-lane full-line stores and was measured at ~13.6 B/clk/CU while all 256 workgroups are in their epilogues together
-// (tools/ablate_persist.sh: the epilogue is 15-42 % of a launch).  Is that the CU's own limit or the chip's HBM write bandwidth?
+// (the retired ablation builds, profiles/r03_gemm_persist_ablations.log: the epilogue is 15-42 % of a launch).  Is that the CU's own limit or the chip's HBM write bandwidth?
 //   grid = 1, 8, 64, 256 workgroups of 8 waves; each wave writes STRIPS x 1 KiB (64 lanes x 16 B, row-contiguous 128-B lines as the
 //   epilogue does), plain / nontemporal, 16 B or 8 B per lane.
 //   hipcc --offload-arch=gfx950 -O3 tools/store_probe.hip -o tools/store_probe && tools/store_probe
