@@ -50,6 +50,7 @@ SIGNATURES = {
     "sg_gemm_persist_last_kstep": (I, []),
     "sg_gemm_last_kernel": (C.c_char_p, []),
     "sg_attention_last_kernel": (C.c_char_p, []),
+    "sg_attention_last_body": (C.c_char_p, []),
     "sg_set_gemm_config": (I, [I]),
     "sg_profile_read": (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(L), C.POINTER(L)]),
     "sg_create": (I, [C.POINTER(P), I, C.POINTER(VitDesc)]),

@@ -101,6 +101,35 @@ __device__ __forceinline__ void store_rows(bf16_t* lds, int ld, int tid, const u
   }
 }
 
+// x op x' of the other half-wave (lane l and l ^ 32) without the LDS queue: v_permlane32_swap leaves lanes l < 32 holding (x_l, x_l+32) and
+// lanes l >= 32 (x_l-32, x_l) in the two outputs, so their sum / maximum is what x + __shfl_xor(x, 32) gives (addition commutes: bit-identical).
+// The maximum is llvm.maximum (v_maximum3_f32): unlike fmaxf it needs no v_max_f32 x, x canonicalisation of MFMA results; the two agree on every
+// input without a NaN (the scores have none: masked keys are -inf).
+template <bool SUM>
+__device__ __forceinline__ float other_half(float x) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+  const float a0 = __uint_as_float(r[0]), a1 = __uint_as_float(r[1]);
+  return SUM ? a0 + a1 : __builtin_elementwise_maximum(a0, a1);
+}
+
+// LDS-DMA staging (the lean dh-64 body): a 64-key tile of one head is 64 rows x 128 B, stored UNPADDED and XOR-swizzled per 16-byte chunk:
+// physical chunk p of row r holds logical chunk p ^ swz(r).  K: swz = (r >> 1) & 7, so the 16 lanes of each ds_read_b128 group (rows c,
+// logical chunk 2 ks + h) hit 16 distinct 4-bank slots; V: swz = 4 ((r >> 1) & 1), so the four rows of a 32-lane ds_read_b64_tr_b16 block
+// cover the four 16-dword quarters of the 64 banks.  Wave w fills the 1 KiB pieces w and w + 4 (8 rows each: every 8 lanes read one whole
+// 128-byte row) with buffer_load_dwordx4 ... lds; the descriptor starts at the tile's first row and ends at row N, so rows past the end
+// come back as zero (masked to -inf in the scores; 0 x V in P V).
+__device__ __forceinline__ int dma_voff(int row, int lane, int row_bytes, bool vtile) {
+  const int pc = lane & 7, swz = vtile ? ((row >> 1) & 1) * 4 : (row >> 1) & 7;
+  return row * row_bytes + (pc ^ swz) * 16;
+}
+__device__ __forceinline__ void dma_tile(const bf16_t* row0, uint32_t rows_left, uint32_t row_bytes, bf16_t* lds_tile, int wave,
+                                         const int (&voff)[2]) {
+  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(row0), 0, (int)(rows_left * row_bytes), 0x00020000);
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(lds_tile + (wave + 4 * p) * 512), 16, voff[p], 0, 0, 0);
+}
+
 // GENERIC = additive bias and / or the 'Experimental' re-softmax (last block only); the 23 ordinary blocks run the lean path.
 // MULTI = several separately soft-maxed streams are summed (SCLIP / SegEarth / GEM); otherwise no second accumulator.
 // Lean variants are capped at 256 registers (VGPR-form MFMA, 2+ waves per SIMD); the register-hungry ones (bias + multi-stream,
@@ -109,13 +138,17 @@ __device__ __forceinline__ void store_rows(bf16_t* lds, int ld, int tid, const u
 // 2 = the 'Experimental' last block at compile time: similarity-map bias + re-softmax, no mask, no Gaussian factors.
 // H2: nothing but a name -- the two-plane translation unit instantiates the SAME <DH, TS, GK, MULTI, F16 = true, PV> combinations as the f16 one
 // with different bodies (AH2 is a file-level constant), so it must not share their symbols.
-template <int DH, int TS, int GK, bool MULTI, bool F16, bool PV, bool H2 = AH2>
+// DMA: the lean dh-64 body stages K / V by LDS-DMA into the swizzled image above and keeps -m_run resident (launch_attn); false = the
+// register-staged body (every other instantiation, and tuning code 39 for the same-process baseline).
+template <int DH, int TS, int GK, bool MULTI, bool F16, bool PV, bool H2 = AH2, bool DMA = false>
 // (two-plane form: twice the fragment registers -- the variants with a bias / two summed terms and every head_dim > 64 get the whole file too)
 __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 || MULTI || DH > 80)) || (AH2 && (DH > 64 || (GK != 0 && TS == 2)))) ? 1 : 2) void attn_kernel(AttnArgs a) {
   constexpr bool GENERIC = GK != 0, EXPER = GK == 2;
+  static_assert(!DMA || (GK == 0 && !AH2 && DH == 64), "attention: the LDS-DMA body is the lean dh-64 one");
   using C = AttnCfg<DH>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int BUF = TS * KT * C::K_LD + KT * C::V_LD;                 // elements per LDS buffer: [TS K tiles][V tile]
+  constexpr int K_LD = DMA ? DH : C::K_LD, V_LD = DMA ? DH : C::V_LD;  // LDS row strides (DMA: unpadded, swizzled)
+  constexpr int BUF = TS * KT * K_LD + KT * V_LD;                       // elements per LDS buffer: [TS K tiles][V tile]
   constexpr int NB = (size_t)2 * BUF * sizeof(bf16_t) > 160 * 1024 ? 1 : 2;   // two buffers unless they exceed the CU's LDS (two-plane form, two
                                                                         // summed terms at head_dim 128): then ONE buffer and a second barrier per tile
   bf16_t* sbuf = reinterpret_cast<bf16_t*>(smem);                       // [NB][BUF]
@@ -164,6 +197,15 @@ __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 ||
   const int g = lane >> 4, qq = (lane & 15) >> 2, pp = lane & 3;               // transposed-read lane roles
 
   const RowMap<DH> kmap = make_row_map<DH>(a.st, a.N, tid), vmap = make_row_map<DH>(a.v_st, a.N, tid);
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);                    // provably uniform: the LDS-DMA destination goes to M0
+  const uint32_t k_rb = (uint32_t)a.st * 2, v_rb = (uint32_t)a.v_st * 2;     // bytes per K / V row
+  int kvo[2], vvo[2];                                                          // this lane's source offsets of its two pieces
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const int row = 8 * (wave + 4 * p) + (lane >> 3);
+    kvo[p] = dma_voff(row, lane, (int)k_rb, false);
+    vvo[p] = dma_voff(row, lane, (int)v_rb, true);
+  }
 
   f32x16 o_tot[MULTI ? C::DVT : 1];
   if (MULTI) {
@@ -230,15 +272,32 @@ __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 ||
       for (int r = 0; r < 16; ++r) o_acc[t][r] = 0.f;
     m_run = -INFINITY; l_run = 0.f;
 
-    u32x4 kreg[TS][C::NL], vreg[C::NL];
+    auto dma_stage = [&](int k0n, bf16_t* dst) {              // DMA: K tiles + V tile of keys [k0n, k0n + 64) into one LDS buffer
+      const uint32_t left = (uint32_t)(a.N - k0n);
 #pragma unroll
-    for (int t = 0; t < TS; ++t) load_rows<DH>(kptr[t], a.st, 0, kmap, kreg[t]);
-    if (do_pv) load_rows<DH>(vbase, a.v_st, 0, vmap, vreg);
+      for (int t = 0; t < TS; ++t) dma_tile(kptr[t] + (int64_t)k0n * a.st, left, k_rb, dst + t * KT * K_LD, wave_u, kvo);
+      if (do_pv) dma_tile(vbase + (int64_t)k0n * a.v_st, left, v_rb, dst + TS * KT * K_LD, wave_u, vvo);
+    };
+    u32x4 kreg[DMA ? 1 : TS][DMA ? 1 : C::NL], vreg[DMA ? 1 : C::NL];
+    if constexpr (DMA) {
+      dma_stage(0, sbuf);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // LDS-DMA is not counted by the barrier: each wave retires its own pieces first
+    } else {
 #pragma unroll
-    for (int t = 0; t < TS; ++t) store_rows<DH>(sbuf + t * KT * C::K_LD, C::K_LD, tid, kreg[t], C::K_LO);
-    if (do_pv) store_rows<DH>(sbuf + TS * KT * C::K_LD, C::V_LD, tid, vreg, C::V_LO);
+      for (int t = 0; t < TS; ++t) load_rows<DH>(kptr[t], a.st, 0, kmap, kreg[t]);
+      if (do_pv) load_rows<DH>(vbase, a.v_st, 0, vmap, vreg);
+#pragma unroll
+      for (int t = 0; t < TS; ++t) store_rows<DH>(sbuf + t * KT * C::K_LD, C::K_LD, tid, kreg[t], C::K_LO);
+      if (do_pv) store_rows<DH>(sbuf + TS * KT * C::K_LD, C::V_LD, tid, vreg, C::V_LO);
+    }
     __syncthreads();
     int cur = 0;
+    // DMA: the score accumulator starts from this resident -m_run block (0 while m_run is -inf); it changes only where m_run does
+    f32x16 negm;
+    if constexpr (DMA) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) negm[r] = 0.f;
+    }
 
     // GENERIC: the additive bias (similarity map) of the NEXT key tile is fetched one tile ahead -- 32 coalesced dword loads per
     // lane (the map is symmetric, so it is read as bias[key][query] with the queries on the lanes)
@@ -261,22 +320,26 @@ __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 ||
     if (BIAS_AHEAD) fetch_bias(0);
     for (int k0 = 0; k0 < a.N; k0 += KT) {
       const bool has_next = k0 + KT < a.N;
-      if (has_next) {                                        // next tile's loads fly while this tile computes
+      if constexpr (!DMA) {
+        if (has_next) {                                      // next tile's loads fly while this tile computes
 #pragma unroll
-        for (int t = 0; t < TS; ++t) load_rows<DH>(kptr[t], a.st, k0 + KT, kmap, kreg[t]);
-        if (do_pv) load_rows<DH>(vbase, a.v_st, k0 + KT, vmap, vreg);
+          for (int t = 0; t < TS; ++t) load_rows<DH>(kptr[t], a.st, k0 + KT, kmap, kreg[t]);
+          if (do_pv) load_rows<DH>(vbase, a.v_st, k0 + KT, vmap, vreg);
+        }
       }
       const bf16_t* sK = sbuf + (NB == 2 ? cur * BUF : 0);
-      const bf16_t* sV = sK + TS * KT * C::K_LD;
+      const bf16_t* sV = sK + TS * KT * K_LD;
 
       // ---- scores of the whole 64-key tile: S^T[key][query], 2 sub-blocks x KS k-steps -----------------------------
       f32x16 sacc[2];
       {
         const float s_init = (!GENERIC && m_run != -INFINITY) ? -m_run : 0.f;
+        if constexpr (!DMA) {
 #pragma unroll
-        for (int sub = 0; sub < 2; ++sub)
+          for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) sacc[sub][r] = s_init;
+            for (int r = 0; r < 16; ++r) sacc[sub][r] = s_init;
+        }
         if constexpr (AH2) {
           // two-plane form: the fragments of one k-step at a time (both planes, both key sub-blocks = 16 registers), three MFMAs each
 #pragma unroll
@@ -305,14 +368,15 @@ __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 ||
           for (int t = 0; t < TS; ++t)
 #pragma unroll
             for (int ks = 0; ks < C::KS; ++ks)
-              kf[sub][t][ks] = *reinterpret_cast<const bf16x8*>(sK + t * KT * C::K_LD + (sub * 32 + c) * C::K_LD + ks * 16 + h * 8);
+              kf[sub][t][ks] = *reinterpret_cast<const bf16x8*>(sK + t * KT * K_LD + (sub * 32 + c) * K_LD +
+                                                                (DMA ? ((2 * ks + h) ^ ((c >> 1) & 7)) * 8 : ks * 16 + h * 8));
 #pragma unroll
         for (int t = 0; t < TS; ++t)
 #pragma unroll
           for (int ks = 0; ks < C::KS; ++ks)
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub)              // the two key sub-blocks alternate: no MFMA waits on its predecessor
-              sacc[sub] = mfma_32x32x16<F16>(kf[sub][t][ks], qf[t][ks], sacc[sub]);
+              sacc[sub] = mfma_32x32x16<F16>(kf[sub][t][ks], qf[t][ks], (DMA && t == 0 && ks == 0) ? negm : sacc[sub]);
         }
       }
       // (b) V^T fragments of the tile are fetched NOW (transposed LDS reads, lane 4q+p of a 16-lane group addresses row q,
@@ -332,12 +396,15 @@ __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 ||
 #pragma unroll
           for (int f = 0; f < 4; ++f) {
             const int key0 = f * 16 + 4 * h;
-            const bf16_t* p0 = sV + (key0 + qq) * C::V_LD + t * 32 + 16 * (g & 1) + 4 * pp;
+            const bf16_t* p0 = sV + (key0 + qq) * V_LD + (DMA ? (t ^ ((qq >> 1) & 1)) : t) * 32 + 16 * (g & 1) + 4 * pp;
             const short4_ lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(p0));
-            const short4_ hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(p0 + 8 * C::V_LD));
+            const short4_ hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(p0 + 8 * V_LD));
             vfr[t][f] = (short8_){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
           }
       }
+      // DMA: every LDS read of this tile is issued; the next tile's pieces go into the other buffer (last read one tile ago) now, and land
+      // under this tile's softmax and P V.  (Issued any earlier, the compiler's own vmcnt in front of this tile's reads would drain them.)
+      if (DMA && has_next) dma_stage(k0 + KT, sbuf + (cur ^ 1) * BUF);
       // log2-domain scores for query q_glob (lane); key of (sub, r) = k0 + 32 sub + (r&3) + 8 (r>>2) + 4 h
       float sc[32];
       float mloc;
@@ -363,9 +430,11 @@ __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 ||
         }
         mloc = sacc[0][0];
 #pragma unroll
-        for (int i = 1; i < 32; ++i) mloc = fmaxf(mloc, sacc[i >> 4][i & 15]);   // already relative to the running maximum
+        for (int i = 1; i < 32; ++i)                       // already relative to the running maximum
+          mloc = DMA ? __builtin_elementwise_maximum(mloc, sacc[i >> 4][i & 15]) : fmaxf(mloc, sacc[i >> 4][i & 15]);   // DMA: 16 v_maximum3
       }
-      mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
+      if constexpr (DMA) mloc = other_half<false>(mloc);
+      else mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
       // Lazy online softmax: the exponentials use a STALE maximum m_run that is only raised (and the accumulators rescaled) when some
       // row's maximum has outgrown it by more than 2^RESCALE_TAU -- probabilities stay <= 2^TAU, exact in the final O / l ratio.
       // The branch is wave-uniform and, after the first tiles, almost never taken (the 32 accumulator multiplies per tile go away).
@@ -398,6 +467,11 @@ __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 ||
             for (int i = 0; i < 32; ++i) sacc[i >> 4][i & 15] -= delta;
             m_run = first ? delta : m_run + delta;
           }
+          if constexpr (DMA) {
+            const float nm = m_run != -INFINITY ? -m_run : 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) negm[r] = nm;
+          }
 #pragma unroll
           for (int t = 0; t < C::DVT; ++t)
 #pragma unroll
@@ -407,10 +481,11 @@ __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 ||
 #pragma unroll
         for (int i = 0; i < 32; ++i) {
           sc[i] = __builtin_amdgcn_exp2f(sacc[i >> 4][i & 15]);
-          lsum += sc[i];
+          lsum = (DMA && i == 0) ? sc[0] : lsum + sc[i];     // DMA: 0 + p == p (p = exp2(.) is never -0): one v_add fewer
         }
       }
-      lsum += __shfl_xor(lsum, 32, 64);
+      if constexpr (DMA) lsum = other_half<true>(lsum);
+      else lsum += __shfl_xor(lsum, 32, 64);
       l_run += lsum;
       // P (bf16) is already the B operand: element j of k-step s2 of sub-block sub = sc[16 sub + 8 s2 + j]
       bf16x8 pf[4];                                          // (bit pattern: f16 values when F16; probabilities are <= 2^RESCALE_TAU)
@@ -455,7 +530,8 @@ __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 ||
             o_acc[t] = mfma_32x32x16<F16>(*reinterpret_cast<bf16x8*>(&vfr[t][f]), pf[f], o_acc[t]);
       }
       if (NB == 1) __syncthreads();                          // single buffer: every wave is done reading the tile before it is overwritten
-      if (has_next) {                                        // the other buffer was last read one iteration ago
+      if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the next tile have landed (before the barrier)
+      else if (has_next) {                                   // the other buffer was last read one iteration ago
         bf16_t* nK = sbuf + (NB == 2 ? (cur ^ 1) * BUF : 0);
 #pragma unroll
         for (int t = 0; t < TS; ++t) store_rows<DH>(nK + t * KT * C::K_LD, C::K_LD, tid, kreg[t], C::K_LO);
@@ -503,11 +579,13 @@ __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 ||
   }
 }
 
+// The lean dh-64 kernels of the bf16 / f16 forms run the LDS-DMA body unless tuning code 39 asks for the register-staged one (same-process
+// A/B and bit-identity checks against the previous body).
 template <int DH, int TS>
 static int launch_attn(const AttnArgs& a, hipStream_t s) {
   using C = AttnCfg<DH>;
   const size_t lds2 = (size_t)2 * (TS * KT * C::K_LD + KT * C::V_LD) * sizeof(bf16_t);
-  const size_t lds = lds2 > 160 * 1024 ? lds2 / 2 : lds2;                 // the kernel's NB
+  const size_t lds_staged = lds2 > 160 * 1024 ? lds2 / 2 : lds2;          // the kernel's NB
   const bool generic = a.bias != nullptr || a.resoftmax != 0 || a.causal != 0;
   const bool multi = !a.sum_scores && a.n_terms > 1;
   // TS == 2 means two SUMMED score terms = one stream: the multi-stream variants exist for TS == 1 only
@@ -515,10 +593,15 @@ static int launch_attn(const AttnArgs& a, hipStream_t s) {
   SG_REQUIRE(CAN_MULTI || !multi, "attention: summed terms and separate streams are exclusive");
   using Kern = void (*)(AttnArgs);
   const bool exper = generic && a.bias && a.resoftmax && !a.causal && !a.bias_cn && !a.bias_rn && !multi && a.ctx;
+  constexpr bool CAN_DMA = DH == 64 && !AH2;
+  const bool dma = CAN_DMA && !generic && get_gemm_config() != 39;
   const Kern kern = exper ? attn_kernel<DH, TS, 2, false, AF16, true>
                   : a.ctx ? (generic ? (multi ? attn_kernel<DH, TS, 1, CAN_MULTI, AF16, true> : attn_kernel<DH, TS, 1, false, AF16, true>)
-                                     : (multi ? attn_kernel<DH, TS, 0, CAN_MULTI, AF16, true> : attn_kernel<DH, TS, 0, false, AF16, true>))
-                          : (generic ? attn_kernel<DH, TS, 1, false, AF16, false> : attn_kernel<DH, TS, 0, false, AF16, false>);
+                                     : dma ? (multi ? attn_kernel<DH, TS, 0, CAN_MULTI, AF16, true, AH2, CAN_DMA> : attn_kernel<DH, TS, 0, false, AF16, true, AH2, CAN_DMA>)
+                                           : (multi ? attn_kernel<DH, TS, 0, CAN_MULTI, AF16, true> : attn_kernel<DH, TS, 0, false, AF16, true>))
+                          : (generic ? attn_kernel<DH, TS, 1, false, AF16, false>
+                                     : dma ? attn_kernel<DH, TS, 0, false, AF16, false, AH2, CAN_DMA> : attn_kernel<DH, TS, 0, false, AF16, false>);
+  const size_t lds = dma ? (size_t)2 * (TS + 1) * KT * DH * sizeof(bf16_t) : lds_staged;   // DMA: two unpadded buffers
   SG_REQUIRE(a.ctx || !multi, "attention: a log-sum-exp-only pass has one stream");
   const int64_t nqb = cdiv(a.N, QB);
   const int order = (generic && a.bias) ? ((a.B >= 16 && (a.H & 3) == 0) ? 2 : 1) : 0;        // the kernel's workgroup order
@@ -528,7 +611,7 @@ static int launch_attn(const AttnArgs& a, hipStream_t s) {
   SG_REQUIRE(nblk < (1ll << 31), "attention: grid too large");                 // every check before the first HIP call
   if (lds > 64 * 1024) SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
   note_attn_launch({"attn", AH2 ? HK_F16X2 : AF16 ? HK_F16 : HK_BF16, DH, TS, exper ? 2 : generic ? 1 : 0, (a.ctx && multi) ? 1 : 0, a.ctx ? 1 : 0, order,
-                    lds2 > 160 * 1024 ? 1 : 2, 0, nblk});
+                    lds2 > 160 * 1024 ? 1 : 2, 0, nblk, dma ? 1 : 0});
   dim3 grid((unsigned)nblk);
   // algorithmic FLOPs: 2*N*N*dh per (term score) + 2*N*N*dh per stream PV, per (image, head)
   const int streams = a.sum_scores ? 1 : a.n_terms;
@@ -545,7 +628,7 @@ int attention_h2_impl(const AttnArgs& a, hipStream_t s) {   // strides arrive in
 #elif SG_ATTN_F16
 int attention_f16_impl(const AttnArgs& a, hipStream_t s) {
 #else
-static thread_local AttnLaunchRecord g_attn_last = {nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static thread_local AttnLaunchRecord g_attn_last = {nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 void note_attn_launch(const AttnLaunchRecord& r) { g_attn_last = r; }
 const char* attention_last_kernel() {
   static thread_local char text[160];
@@ -557,6 +640,12 @@ const char* attention_last_kernel() {
   else snprintf(text, sizeof text, "%s dh=%d ts=%d gk=%d multi=%d pv=%d kind=%s order=%s nb=%d grid=%lld", r.name, r.dh, r.ts, r.gk, r.multi, r.pv,
                 kinds[r.kind & 3], orders[r.order % 3], r.nb, (long long)r.grid);
   return text;
+}
+
+const char* attention_last_body() {
+  const AttnLaunchRecord& r = g_attn_last;
+  if (!r.name) return "none";
+  return r.name[0] != 'a' ? "stats" : r.dma ? "dma" : "staged";
 }
 
 int attention_bf16(const AttnArgs& a, hipStream_t s) {

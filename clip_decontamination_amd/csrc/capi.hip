@@ -509,6 +509,8 @@ extern "C" int sg_attention_stats_raw(int precision, const void* qk, int64_t sb,
 }
 // "<kernel> ..." of the calling thread's last launch through the fused attention or its statistics (thread-local text).
 extern "C" const char* sg_attention_last_kernel(void) { return attention_last_kernel(); }
+// which body that launch ran: "dma" / "staged" (the fused attention), "stats", or "none"
+extern "C" const char* sg_attention_last_body(void) { return attention_last_body(); }
 // category: 0 bf16 GEMM (non-persistent tile variants), 1 fused attention, 2 f32 GEMM, 3 the persistent bf16 GEMM (all instantiations), 4 fp8 GEMM,
 // 5 / 6 the persistent GEMM's folded-LayerNorm consumer / producer instantiations alone.  Call after the stream
 // has been synchronised.

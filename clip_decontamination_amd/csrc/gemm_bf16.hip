@@ -1776,8 +1776,9 @@ int gemm_bf16(const GemmBf16Args& a, hipStream_t s) {
     if (a.ln_stats) SG_REQUIRE(a.ln_c && a.alpha == 1.f && a.c_is_bf16 && !a.residual && !a.rowdot && ((((uintptr_t)a.ln_c) & 15) == 0) && ((((uintptr_t)a.ln_stats) & 7) == 0), "gemm_bf16: ln_stats needs ln_c and alpha 1");
   }
   int cfg = g_gemm_config;
-  if (cfg == 33 || cfg == 34 || cfg == 36 || cfg == 37 || cfg == 38) cfg = -1;       // tuning codes read by capi.hip (MX hand-off / LayerNorm folding off)
-                                                                                  // or by launch_persist (38: the 32-element K step), not tile configurations
+  if (cfg == 33 || cfg == 34 || cfg == 36 || cfg == 37 || cfg == 38 || cfg == 39) cfg = -1;   // tuning codes read by capi.hip (MX hand-off / LayerNorm
+                                                                                  // folding off), by launch_persist (38: the 32-element K step) or by
+                                                                                  // the attention (39: register-staged lean body), not tile configurations
   if (a.rowdot || ln_fold) cfg = 30;
   if (a.res_half) {                                          // 2-byte residual: the small-tile kernel's run-time epilogue only
     SG_REQUIRE(vec && a.residual && a.c_is_bf16 && !a.rowdot && !ln_fold && a.ldr % 8 == 0, "gemm_bf16: res_half needs a 2-byte C, N %% 8 == 0 and ldr %% 8 == 0");

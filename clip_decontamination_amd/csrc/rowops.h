@@ -62,9 +62,11 @@ int attention_bf16(const AttnArgs& a, hipStream_t s);
 // The calling thread's last launch through attention_bf16() / attention_stats() (sg_attention_last_kernel).  `name` is null when the last call
 // launched nothing; kind 1 bf16, 2 f16, 3 two-plane (HalfKind); order 0 head-major, 1 query-block-major, 2 whole images per XCD; lph > 0 = the
 // fast statistics kernel with that many lanes per head, lph = 0 with name "stats_generic" = the generic one.
-struct AttnLaunchRecord { const char* name; int kind, dh, ts, gk, multi, pv, order, nb, lph; int64_t grid; };
+// dma = 1: the lean kernel's LDS-DMA body ran (attention_last_body: "dma"; "staged" for the register-staged one, "stats" for a statistics kernel).
+struct AttnLaunchRecord { const char* name; int kind, dh, ts, gk, multi, pv, order, nb, lph; int64_t grid; int dma; };
 void note_attn_launch(const AttnLaunchRecord& r);
 const char* attention_last_kernel();
+const char* attention_last_body();
 
 // head-averaged attention statistics of an ordinary block (outlier detection needs only these):
 //   attn_cls[b, j] = mean_h softmax(q k^T)[0, j],  attn_diag[b, j] = mean_h softmax(q k^T)[j, j]
