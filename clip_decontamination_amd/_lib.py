@@ -39,6 +39,20 @@ class TileBatch(C.Structure):
                 ("pad_l", C.c_int32), ("pad_t", C.c_int32), ("grid_h", C.c_int32), ("grid_w", C.c_int32)]
 
 
+class JbuCaptureSlot(C.Structure):
+    """sg_jbu_capture_slot (include/segearth_hip.h): caller's device buffer, its size, the bytes the last call copied."""
+    _fields_ = [("dst", C.c_void_p), ("cap", C.c_size_t), ("bytes", C.c_size_t)]
+
+
+JBU_CAP_STAGE = ("GS", "PROJ", "X", "X16", "H1", "KF", "SRC", "HR", "OUT", "OUT16")        # SG_JBU_CAP_* per stage, in enum order
+JBU_CAP_TAIL = ("FIN_A", "FIN_RES", "GEFF", "G0", "CLSL", "ROWDOT")
+
+
+class JbuCapture(C.Structure):
+    """sg_jbu_capture: per stage and tail slots (test instrumentation of the upsampler, sg_jbu_set_capture)."""
+    _fields_ = [("stage", (JbuCaptureSlot * len(JBU_CAP_STAGE)) * 4), ("tail", JbuCaptureSlot * len(JBU_CAP_TAIL))]
+
+
 P, I, F, Z, L = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
 
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
@@ -103,6 +117,8 @@ SIGNATURES = {
     "sg_jbu_workspace_bytes": (Z, [P, I, I, I]),
     "sg_jbu_upsample": (I, [P, P, P, I, I, I, I, I, I, P, P, Z, P]),
     "sg_jbu_logits": (I, [P, P, P, I, I, I, I, I, I, P, I, P, F, P, P, Z, P]),
+    "sg_jbu_set_capture": (I, [P, P]),
+    "sg_jbu_last_kernels": (C.c_char_p, []),
     "sg_extract_tiles": (I, [C.POINTER(TileBatch), I, I, P, P]),
     "sg_global_debias": (I, [P, P, I, I, I, F, P, P]),
 }

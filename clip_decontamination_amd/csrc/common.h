@@ -277,6 +277,7 @@ int gemm_bf16(const GemmBf16Args& a, hipStream_t s);
 int get_gemm_config();
 int gemm_persist_last_kstep();   // K step (64 / 32 elements) of the calling thread's last persistent bf16 / f16 GEMM launch, 0 = none yet
 const char* gemm_last_kernel();  // "<family> grid=<x> ngroup=<n>" of the calling thread's last gemm_bf16() launch, "none" if its last call launched nothing
+const char* gemm_last_family();  // the static kernel-family name of the calling thread's last gemm_bf16() launch, "none" as above
 bool gemm_bf16_ln_fold_ok(int M, int N, int K);   // the shapes the persistent kernel (home of the folded-LayerNorm epilogues) can run
 bool gemm_bf16_prefers_persistent(int M, int N);  // ... and whether the automatic dispatch would pick it (enough 256 x 256 tiles to fill the chip)
 void set_gemm_config(int c);   // tuning hook (per calling thread): -1 auto, 0 = 128x128x2-stage baseline, 1.. = ring variants

@@ -688,6 +688,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pingpong(GemmBf16Args a, int ac
 struct GemmLaunchRecord { const char* name; int grid; int ngroup; };
 static thread_local GemmLaunchRecord g_last_launch = {nullptr, 0, 0};
 static inline void note_launch(const char* name, int64_t grid, int ngroup = 0) { g_last_launch = {name, (int)grid, ngroup}; }
+const char* gemm_last_family() { return g_last_launch.name ? g_last_launch.name : "none"; }
 const char* gemm_last_kernel() {
   static thread_local char text[96];
   if (!g_last_launch.name) return "none";

@@ -1111,6 +1111,7 @@ struct sg_jbu {
   void* fin_w16;
   void* fin_wh2;                                           // two-plane f16 copy of the final 1x1 weight (C % 32 == 0)
   std::vector<uint8_t> have;
+  sg_jbu_capture* cap = nullptr;                           // test instrumentation (sg_jbu_set_capture): copies of every kernel's operands
 };
 
 namespace sg {
@@ -1247,6 +1248,61 @@ static size_t jbu_plan(const sg_jbu* j, int B, int gh, int gw, void* ws, bool dr
 }
 }  // namespace sg
 
+namespace sg {
+// The calling thread's last sg_jbu_upsample / sg_jbu_logits (sg_jbu_last_kernels): static names and grids stored in the branch that
+// launches each kernel, as gemm_bf16's record does; the text is made only when queried.
+struct JbuStageRecord { const char *range, *x16, *fixup0, *fixup1, *kf, *src, *bicubic, *hr, *conv, *out16; unsigned grid[3]; };
+struct JbuLaunchRecord { bool used; JbuStageRecord st[4]; const char *fin, *fin_a, *geff, *cls, *pix; };
+static thread_local JbuLaunchRecord g_jbu_rec = {};
+static void jbu_rec_start() { g_jbu_rec = {}; g_jbu_rec.used = true; }
+// capture (test instrumentation): copy `bytes` of `src` into the caller's slot on the call's stream; stage < 0 = a tail slot
+static int jbu_cap(sg_jbu* j, int stage, int slot, const void* src, size_t bytes, hipStream_t s) {
+  if (!j->cap) return SG_OK;
+  sg_jbu_capture_slot& c = stage < 0 ? j->cap->tail[slot] : j->cap->stage[stage][slot];
+  if (!c.dst) return SG_OK;
+  if (bytes > c.cap) return fail(SG_ERR_INVALID, "sg_jbu capture: stage %d slot %d needs %zu bytes, the buffer holds %zu", stage, slot, bytes, c.cap);
+  SG_HIP(hipMemcpyAsync(c.dst, src, bytes, hipMemcpyDeviceToDevice, s));
+  c.bytes = bytes;
+  return SG_OK;
+}
+static void jbu_cap_reset(sg_jbu* j) {
+  if (!j->cap) return;
+  for (auto& st : j->cap->stage) for (auto& c : st) c.bytes = 0;
+  for (auto& c : j->cap->tail) c.bytes = 0;
+}
+}  // namespace sg
+
+extern "C" int sg_jbu_set_capture(sg_jbu* j, sg_jbu_capture* cap) {
+  SG_REQUIRE(j, "sg_jbu_set_capture: null upsampler");
+  j->cap = cap;
+  return SG_OK;
+}
+
+extern "C" const char* sg_jbu_last_kernels(void) {
+  static thread_local std::string text;
+  if (!g_jbu_rec.used) return "none";
+  text.clear();
+  auto put = [&](const std::string& key, const char* v) {
+    if (!v) return;
+    if (!text.empty()) text += ' ';
+    text += key + "=" + v;
+  };
+  for (int k = 0; k < 4; ++k) {
+    const JbuStageRecord& R = g_jbu_rec.st[k];
+    const std::string sk = "s" + std::to_string(k) + ".";
+    put(sk + "range", R.range); put(sk + "x16", R.x16); put(sk + "fixup0", R.fixup0); put(sk + "fixup1", R.fixup1); put(sk + "kf", R.kf);
+    put(sk + "src", R.src); put(sk + "bicubic", R.bicubic); put(sk + "hr", R.hr); put(sk + "conv", R.conv);
+    if (R.conv) put(sk + "grid", (std::to_string(R.grid[0]) + "x" + std::to_string(R.grid[1]) + "x" + std::to_string(R.grid[2])).c_str());
+    put(sk + "out16", R.out16);
+  }
+  put("final", g_jbu_rec.fin); put("final.a", g_jbu_rec.fin_a);
+  if (g_jbu_rec.pix) {
+    std::string t = std::string(g_jbu_rec.geff) + (g_jbu_rec.cls ? std::string(",") + g_jbu_rec.cls : std::string()) + "," + g_jbu_rec.pix;
+    put("tail", t.c_str());
+  }
+  return text.c_str();
+}
+
 extern "C" size_t sg_jbu_workspace_bytes(const sg_jbu* j, int B, int gh, int gw) {
   if (!j || B <= 0 || gh <= 0 || gw <= 0) return 0;
   JbuPlan p;
@@ -1291,9 +1347,12 @@ static int jbu_stages(sg_jbu* j, const float* source, const float* guidance, int
     float* dst = (stg % 2 == 0) ? p.bufA : p.bufB;
     hipLaunchKernelGGL(jbu_pool_kernel, dim3((unsigned)cdiv(pixels * 3, 256)), dim3(256), 0, s, guidance, B, GH, GW, oh, ow, p.gs);
     SG_LAUNCH_CHECK();
+    SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_GS, p.gs, (size_t)pixels * 3 * 4, s));
+    JbuStageRecord& R = g_jbu_rec.st[stg];
     hipLaunchKernelGGL(jbu_range_proj_kernel, dim3((unsigned)cdiv(pixels, 256)), dim3(256), 0, s, p.gs, pixels, S.rp0_w, S.rp0_b, S.rp3_w,
                        S.rp3_b, p.proj);
     SG_LAUNCH_CHECK();
+    SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_PROJ, p.proj, (size_t)pixels * KEY_DIM * 4, s));
     const bool fast = precision == SG_PREC_BF16 && C % 8 == 0;       // throughput mode: bf16 MFMA for the fixup linears and the convolution
     const bool x2 = precision == SG_PREC_F16X2;                       // exact tower mode: f32 kernels, the three linears as two-plane f16 GEMMs (f32-grade, 3 f16 MFMAs per product)
     const int NP = jbu_np(r), KP1 = jbu_kp1(r), ldk = (fast || x2) ? NP : d2;
@@ -1307,31 +1366,44 @@ static int jbu_stages(sg_jbu* j, const float* source, const float* guidance, int
       using JK = void (*)(const float*, const float*, int, int, int, const float*, const float*, float*, bf16_t*, int);
       const JK jk = fast ? (r == 5 ? jbu_kernel_tiled_kernel<5, true> : r == 3 ? jbu_kernel_tiled_kernel<3, true> : jbu_kernel_tiled_kernel<0, true>)
                          : jbu_kernel_tiled_kernel<0, false>;
+      const char* jk_name = fast ? (r == 5 ? "jbu_kernel_tiled_kernel<5,true>" : r == 3 ? "jbu_kernel_tiled_kernel<3,true>" : "jbu_kernel_tiled_kernel<0,true>")
+                                 : "jbu_kernel_tiled_kernel<0,false>";
       if (x2 && (r == 5 || r == 3)) {                       // exact mode: two-plane keys, exact arithmetic, two-plane operand rows written directly
         const dim3 grid((unsigned)(cdiv(oh, AC_T) * cdiv(ow, AC_T)), (unsigned)B);
         constexpr size_t lds5 = JkmCfg<5, true>::LDS, lds3 = JkmCfg<3, true>::LDS;
         if (r == 5) {
           SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_kernel_mfma_kernel<5, true>), lds5));
           hipLaunchKernelGGL((jbu_kernel_mfma_kernel<5, true>), grid, dim3(256), lds5, s, p.proj, p.gs, oh, ow, S.range_temp, S.sigma, p.X, p.X16, KP1, 0);
+          R.range = "jbu_kernel_mfma_kernel<5,true>";
         } else {
           SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_kernel_mfma_kernel<3, true>), lds3));
           hipLaunchKernelGGL((jbu_kernel_mfma_kernel<3, true>), grid, dim3(256), lds3, s, p.proj, p.gs, oh, ow, S.range_temp, S.sigma, p.X, p.X16, KP1, 0);
+          R.range = "jbu_kernel_mfma_kernel<3,true>";
         }
+        R.x16 = "h2";
       } else if (fast && (r == 5 || r == 3)) {               // key dot products on the matrix pipe
         const dim3 grid((unsigned)(cdiv(oh, AC_T) * cdiv(ow, AC_T)), (unsigned)B);
         if (r == 5) {
           SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_kernel_mfma_kernel<5>), JkmCfg<5>::LDS));
           hipLaunchKernelGGL(jbu_kernel_mfma_kernel<5>, grid, dim3(256), JkmCfg<5>::LDS, s, p.proj, p.gs, oh, ow, S.range_temp, S.sigma, p.X, p.X16, KP1, h16 ? 1 : 0);
+          R.range = "jbu_kernel_mfma_kernel<5,false>";
         } else {
           SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_kernel_mfma_kernel<3>), JkmCfg<3>::LDS));
           hipLaunchKernelGGL(jbu_kernel_mfma_kernel<3>, grid, dim3(256), JkmCfg<3>::LDS, s, p.proj, p.gs, oh, ow, S.range_temp, S.sigma, p.X, p.X16, KP1, h16 ? 1 : 0);
+          R.range = "jbu_kernel_mfma_kernel<3,false>";
         }
+        R.x16 = h16 ? "f16" : "bf16";
       } else {
       SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jk), 64 * 1024));
       hipLaunchKernelGGL(jk, dim3((unsigned)(cdiv(oh, AC_T) * cdiv(ow, AC_T)), (unsigned)B), dim3(256), lds, s, p.proj, p.gs, oh,
                          ow, r, S.range_temp, S.sigma, p.X, fast ? p.X16 : nullptr, KP1);
+      R.range = jk_name;
+      R.x16 = fast ? "bf16" : "none";
       }
       SG_LAUNCH_CHECK();
+      if (!h16) SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_X, p.X, (size_t)pixels * (d2 + 3) * 4, s));
+      if (x2 && (r == 5 || r == 3)) SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_X16, p.X16, (size_t)pixels * KP1 * 4, s));
+      if (fast) SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_X16, p.X16, (size_t)pixels * KP1 * 2, s));
     }
     SG_REQUIRE(pixels < (1ll << 31), "sg_jbu_upsample: too many pixels");
     if (fast) {  // H1 = GELU(X . W0^T + b0) (bf16);  Kf = X[:, :d2] + 0.1 * (H1 . W3^T + b3), columns >= d2 are padding
@@ -1339,31 +1411,43 @@ static int jbu_stages(sg_jbu* j, const float* source, const float* guidance, int
       g.A = p.X16; g.lda = KP1; g.W = (const bf16_t*)(h16 ? S.fx0_w16h : S.fx0_w16); g.ldw = KP1; g.bias = S.fx0_bp; g.C = p.H116; g.ldc = NP; g.c_is_bf16 = 1;
       g.M = (int)pixels; g.N = NP; g.K = KP1; g.batch = 1; g.act = ACT_GELU; g.alpha = 1.f; g.f16 = h16 ? 1 : 0;
       SG_TRY(gemm_bf16(g, s));
+      R.fixup0 = gemm_last_family();
+      SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_H1, p.H116, (size_t)pixels * NP * 2, s));
       GemmBf16Args q{};
       q.A = p.H116; q.lda = NP; q.W = (const bf16_t*)(h16 ? S.fx3_w16h : S.fx3_w16); q.ldw = NP; q.bias = S.fx3_bp;
       q.C = p.Kf; q.ldc = NP; q.M = (int)pixels; q.N = NP; q.K = NP; q.batch = 1; q.act = ACT_NONE; q.alpha = 0.1f;
       if (h16) { q.residual = reinterpret_cast<const float*>(p.X16); q.ldr = KP1; q.res_half = 1; q.c_is_bf16 = 1; q.f16 = 1; }   // Kf rows in f16, residual = the operand rows
       else { q.residual = p.X; q.ldr = d2 + 3; q.c_is_bf16 = 0; }
       SG_TRY(gemm_bf16(q, s));
+      R.fixup1 = gemm_last_family(); R.kf = h16 ? "f16" : "f32";
+      SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_KF, p.Kf, (size_t)pixels * NP * (h16 ? 2 : 4), s));
     } else if (x2) {  // the same two linears on the two-plane GEMM: X rows packed to [KP1] two-plane, GELU output two-plane, Kf f32 rows of NP
       if (!(r == 5 || r == 3)) SG_TRY(pack_rows(p.X, pixels, d2 + 3, d2 + 3, p.X16, KP1, HK_F16X2, s));   // (r = 3 / 5: the range kernel wrote the two-plane rows itself)
       GemmBf16Args g{};
       g.A = p.X16; g.lda = KP1; g.W = (const bf16_t*)S.fx0_wh2; g.ldw = KP1; g.bias = S.fx0_bp; g.C = p.H116; g.ldc = NP; g.c_is_bf16 = 1;
       g.M = (int)pixels; g.N = NP; g.K = KP1; g.batch = 1; g.act = ACT_GELU; g.alpha = 1.f; g.h2 = 1;
       SG_TRY(gemm_bf16(g, s));
+      R.fixup0 = gemm_last_family();
+      SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_H1, p.H116, (size_t)pixels * NP * 4, s));
       GemmBf16Args q{};
       q.A = p.H116; q.lda = NP; q.W = (const bf16_t*)S.fx3_wh2; q.ldw = NP; q.bias = S.fx3_bp; q.residual = p.X; q.ldr = d2 + 3;
       q.C = p.Kf; q.ldc = NP; q.c_is_bf16 = 0; q.M = (int)pixels; q.N = NP; q.K = NP; q.batch = 1; q.act = ACT_NONE; q.alpha = 0.1f; q.h2 = 1;
       SG_TRY(gemm_bf16(q, s));
+      R.fixup1 = gemm_last_family(); R.kf = "f32";
+      SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_KF, p.Kf, (size_t)pixels * NP * 4, s));
     } else {  // fixup: H1 = GELU(X . W0^T + b0);  Kf = X[:, :d2] + 0.1 * (H1 . W3^T + b3)
       GemmF32Args g{};
       g.A = p.X; g.lda = d2 + 3; g.B = S.fx0_w; g.sbk = 1; g.sbn = d2 + 3; g.bias = S.fx0_b; g.C = p.H1; g.ldc = d2;
       g.M = (int)pixels; g.N = d2; g.K = d2 + 3; g.batch = 1; g.inner = 1; g.act = ACT_GELU; g.alpha = 1.f;
       SG_TRY(gemm_f32(g, s));
+      R.fixup0 = "gemm_f32";
+      SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_H1, p.H1, (size_t)pixels * d2 * 4, s));
       GemmF32Args q{};
       q.A = p.H1; q.lda = d2; q.B = S.fx3_w; q.sbk = 1; q.sbn = d2; q.bias = S.fx3_b; q.residual = p.X; q.ldr = d2 + 3; q.C = p.Kf; q.ldc = d2;
       q.M = (int)pixels; q.N = d2; q.K = d2; q.batch = 1; q.inner = 1; q.act = ACT_NONE; q.alpha = 0.1f;
       SG_TRY(gemm_f32(q, s));
+      R.fixup1 = "gemm_f32"; R.kf = "f32";
+      SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_KF, p.Kf, (size_t)pixels * d2 * 4, s));
     }
     if (x2 && x2low_ok && (r == 5 || r == 3)) {
       const h2_t* s2 = stg == 0 ? tok2 : o2[stg - 1];
@@ -1372,14 +1456,21 @@ static int jbu_stages(sg_jbu* j, const float* source, const float* guidance, int
       float* d32 = stg == 3 ? dst : nullptr;
       if (stg == 3 && x2_in_hr) *x2_in_hr = true;
       dim3 grid((unsigned)(cdiv(oh, AC_T) * cdiv(ow, AC_T)), (unsigned)B);
+      SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_SRC, s2, (size_t)B * h * w * C * 4, s));
+      R.src = "h2"; R.bicubic = "none"; R.hr = "none"; R.out16 = d2 ? "h2" : "none";
+      R.grid[0] = grid.x; R.grid[1] = grid.y; R.grid[2] = grid.z;
       if (r == 5) {
         SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_conv_lowres_x2_kernel<5>), LowX2Cfg<5>::LDS));
         hipLaunchKernelGGL(jbu_conv_lowres_x2_kernel<5>, grid, dim3(256), LowX2Cfg<5>::LDS, s, s2, p.Kf, ldk, h, w, C, d32, d2);
+        R.conv = "jbu_conv_lowres_x2_kernel<5>";
       } else {
         SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_conv_lowres_x2_kernel<3>), LowX2Cfg<3>::LDS));
         hipLaunchKernelGGL(jbu_conv_lowres_x2_kernel<3>, grid, dim3(256), LowX2Cfg<3>::LDS, s, s2, p.Kf, ldk, h, w, C, d32, d2);
+        R.conv = "jbu_conv_lowres_x2_kernel<3>";
       }
       SG_LAUNCH_CHECK();
+      if (d32) SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_OUT, d32, (size_t)pixels * C * 4, s));
+      if (d2) SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_OUT16, d2, (size_t)pixels * C * 4, s));
       src = dst; h = oh; w = ow;
       continue;
     }
@@ -1392,29 +1483,47 @@ static int jbu_stages(sg_jbu* j, const float* source, const float* guidance, int
       bf16_t* d16 = stg == 3 ? (bf16_t*)p.x16 : o16[stg];
       float* d32 = (stg == 3 && want_f32_x) ? dst : nullptr;   // the fused tail works from the bf16 copy alone: 4 B per element not written
       dim3 grid((unsigned)(cdiv(oh, AC_T) * cdiv(ow, AC_T)), (unsigned)B);
+      SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_SRC, s16, (size_t)B * h * w * C * 2, s));
+      R.src = "bf16"; R.bicubic = "none"; R.hr = "none"; R.out16 = "bf16";
+      R.grid[0] = grid.x; R.grid[1] = grid.y; R.grid[2] = grid.z;
       if (r == 5) {
         SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_conv_lowres_kernel<5>), LowCfg<5>::LDS));
         hipLaunchKernelGGL(jbu_conv_lowres_kernel<5>, grid, dim3(256), LowCfg<5>::LDS, s, s16, p.Kf, ldk, h, w, C, d32, d16, h16 ? 1 : 0);
+        R.conv = "jbu_conv_lowres_kernel<5>";
       } else {
         SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_conv_lowres_kernel<3>), LowCfg<3>::LDS));
         hipLaunchKernelGGL(jbu_conv_lowres_kernel<3>, grid, dim3(256), LowCfg<3>::LDS, s, s16, p.Kf, ldk, h, w, C, d32, d16, h16 ? 1 : 0);
+        R.conv = "jbu_conv_lowres_kernel<3>";
       }
       SG_LAUNCH_CHECK();
+      if (d32) SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_OUT, d32, (size_t)pixels * C * 4, s));
+      SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_OUT16, d16, (size_t)pixels * C * 2, s));
       src = dst; h = oh; w = ow;
       continue;
     }
-    if (mfma_conv) hipLaunchKernelGGL(jbu_bicubic_kernel<bf16_t>, dim3((unsigned)cdiv(pixels * (C / 4), 256)), dim3(256), 0, s, src, B, h, w, C, oh, ow, (bf16_t*)p.hr);
-    else hipLaunchKernelGGL(jbu_bicubic_kernel<float>, dim3((unsigned)cdiv(pixels * (C / 4), 256)), dim3(256), 0, s, src, B, h, w, C, oh, ow, p.hr);
+    SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_SRC, src, (size_t)B * h * w * C * 4, s));
+    R.src = "f32";
+    if (mfma_conv) {
+      hipLaunchKernelGGL(jbu_bicubic_kernel<bf16_t>, dim3((unsigned)cdiv(pixels * (C / 4), 256)), dim3(256), 0, s, src, B, h, w, C, oh, ow, (bf16_t*)p.hr);
+      R.bicubic = "jbu_bicubic_kernel<bf16_t>"; R.hr = "bf16";
+    } else {
+      hipLaunchKernelGGL(jbu_bicubic_kernel<float>, dim3((unsigned)cdiv(pixels * (C / 4), 256)), dim3(256), 0, s, src, B, h, w, C, oh, ow, p.hr);
+      R.bicubic = "jbu_bicubic_kernel<float>"; R.hr = "f32";
+    }
     SG_LAUNCH_CHECK();
+    SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_HR, p.hr, (size_t)pixels * C * (mfma_conv ? 2 : 4), s));
     if (mfma_conv) {                                         // throughput mode: the matrix-core formulation
       const int WT = AC_T + 2 * r, KP = (int)align_up((size_t)WT * WT, 32);
       const size_t lds = (size_t)(64 + ACM_CC) * (KP + 8) * sizeof(bf16_t);
       SG_REQUIRE(lds <= 160 * 1024, "sg_jbu_upsample: window %d needs %zu bytes of LDS", d, lds);
       SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_adaptive_conv_mfma_kernel), 160 * 1024));
       dim3 grid((unsigned)(cdiv(oh, AC_T) * cdiv(ow, AC_T)), (unsigned)B);
-      hipLaunchKernelGGL(jbu_adaptive_conv_mfma_kernel, grid, dim3(256), lds, s, (const bf16_t*)p.hr, p.Kf, ldk, oh, ow, C, r, KP, dst,
-                         (stg == 3 && C % 64 == 0) ? (bf16_t*)p.x16 : nullptr);
+      bf16_t* o16c = (stg == 3 && C % 64 == 0) ? (bf16_t*)p.x16 : nullptr;
+      hipLaunchKernelGGL(jbu_adaptive_conv_mfma_kernel, grid, dim3(256), lds, s, (const bf16_t*)p.hr, p.Kf, ldk, oh, ow, C, r, KP, dst, o16c);
       SG_LAUNCH_CHECK();
+      R.conv = "jbu_adaptive_conv_mfma_kernel"; R.out16 = o16c ? "bf16" : "none";
+      R.grid[0] = grid.x; R.grid[1] = grid.y; R.grid[2] = grid.z;
+      if (o16c) SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_OUT16, o16c, (size_t)pixels * C * 2, s));
     } else {
       const int WT = AC_T + 2 * r;
       const size_t lds = ((size_t)WT * WT * AC_LD + (size_t)d2 * 64) * sizeof(float);
@@ -1422,7 +1531,10 @@ static int jbu_stages(sg_jbu* j, const float* source, const float* guidance, int
       dim3 grid((unsigned)(cdiv(oh, AC_T) * cdiv(ow, AC_T)), (unsigned)cdiv(C, AC_CC), (unsigned)B);
       hipLaunchKernelGGL(jbu_adaptive_conv_kernel, grid, dim3(256), lds, s, p.hr, p.Kf, ldk, oh, ow, C, r, dst);
       SG_LAUNCH_CHECK();
+      R.conv = "jbu_adaptive_conv_kernel"; R.out16 = "none";
+      R.grid[0] = grid.x; R.grid[1] = grid.y; R.grid[2] = grid.z;
     }
+    SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_OUT, dst, (size_t)pixels * C * 4, s));
     src = dst; h = oh; w = ow;
   }
   *x_out = src;
@@ -1442,7 +1554,10 @@ extern "C" int sg_jbu_upsample(sg_jbu* j, const float* source, const float* guid
   const int C = j->C;
   const float* src = nullptr;
   bool x2_ready = false;
+  jbu_rec_start();
+  jbu_cap_reset(j);
   SG_TRY(jbu_stages(j, source, guidance, B, gh, gw, GH, GW, precision, p, &src, s, true, &x2_ready));
+  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_FIN_RES, src, (size_t)B * 256 * gh * gw * C * 4, s));
   // out = x + 0.1 * (x . Wf^T + bf)     (bias pre-scaled by 0.1 at load)
   const int64_t pixels = (int64_t)B * 16 * gh * 16 * gw;
   if (precision == SG_PREC_BF16 && C % 64 == 0) {
@@ -1450,19 +1565,28 @@ extern "C" int sg_jbu_upsample(sg_jbu* j, const float* source, const float* guid
     GemmBf16Args g{};
     g.A = (const bf16_t*)p.x16; g.lda = C; g.W = (const bf16_t*)j->fin_w16; g.ldw = C; g.bias = j->fin_b; g.residual = src; g.ldr = C;
     g.C = out; g.ldc = C; g.c_is_bf16 = 0; g.M = (int)pixels; g.N = C; g.K = C; g.batch = 1; g.act = 0; g.alpha = 0.1f;
-    return gemm_bf16(g, s);
+    SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_FIN_A, p.x16, (size_t)pixels * C * 2, s));
+    SG_TRY(gemm_bf16(g, s));
+    g_jbu_rec.fin = gemm_last_family(); g_jbu_rec.fin_a = "bf16";
+    return SG_OK;
   }
   if (precision == SG_PREC_F16X2 && C % 32 == 0 && pixels >= 1024) {   // exact tower mode: x packed to two-plane f16 (the hi-res scratch is free by now), f32-grade GEMM
     if (!x2_ready) SG_TRY(pack_rows(src, pixels, C, C, p.hr, C, HK_F16X2, s));   // (the two-plane low-res convolution wrote this copy itself)
     GemmBf16Args g{};
     g.A = (const bf16_t*)p.hr; g.lda = C; g.W = (const bf16_t*)j->fin_wh2; g.ldw = C; g.bias = j->fin_b; g.residual = src; g.ldr = C;
     g.C = out; g.ldc = C; g.c_is_bf16 = 0; g.M = (int)pixels; g.N = C; g.K = C; g.batch = 1; g.act = 0; g.alpha = 0.1f; g.h2 = 1;
-    return gemm_bf16(g, s);
+    SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_FIN_A, p.hr, (size_t)pixels * C * 4, s));
+    SG_TRY(gemm_bf16(g, s));
+    g_jbu_rec.fin = gemm_last_family(); g_jbu_rec.fin_a = "h2";
+    return SG_OK;
   }
   GemmF32Args g{};
   g.A = src; g.lda = C; g.B = j->fin_w; g.sbk = 1; g.sbn = C; g.bias = j->fin_b; g.residual = src; g.ldr = C; g.C = out; g.ldc = C;
   g.M = (int)pixels; g.N = C; g.K = C; g.batch = 1; g.inner = 1; g.act = 0; g.alpha = 0.1f;
-  return gemm_f32(g, s);
+  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_FIN_A, src, (size_t)pixels * C * 4, s));
+  SG_TRY(gemm_f32(g, s));
+  g_jbu_rec.fin = "gemm_f32"; g_jbu_rec.fin_a = "f32";
+  return SG_OK;
 }
 
 // ---- fused tail (throughput mode): per-pixel class logits WITHOUT writing the C x S^2 feature map ---------------------------------
@@ -1717,18 +1841,31 @@ extern "C" int sg_jbu_logits(sg_jbu* j, const float* source, const float* guidan
   const int64_t P = (int64_t)16 * gh * 16 * gw, pixels = (int64_t)B * P;
   SG_REQUIRE(pixels >= 1024 && pixels < (1ll << 31), "sg_jbu_logits: pixel count out of range");
   const float* x = nullptr;
+  jbu_rec_start();
+  jbu_cap_reset(j);
   SG_TRY(jbu_stages(j, source, guidance, B, gh, gw, GH, GW, precision, p, &x, s, /*want_f32_x=*/false));
   const bf16_t* x16 = (const bf16_t*)p.x16;                 // the 16x features exist in bf16 only: the conv's 4 B/element f32 store and its two re-reads are gone
   hipLaunchKernelGGL(jbu_geff_kernel, dim3((unsigned)cdiv(C, 64), (unsigned)Q), dim3(256), 0, s, text, j->fin_w, j->fin_b, C, Q, p.geff, p.g0);
   SG_LAUNCH_CHECK();
+  g_jbu_rec.geff = "jbu_geff_kernel";
+  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_GEFF, p.geff, (size_t)C * JBU_QMAX * 4, s));
+  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_G0, p.g0, (size_t)JBU_QMAX * 4, s));
   const bool use_cls = cls != nullptr && cls_token_lambda != 0.f;
-  if (use_cls) { hipLaunchKernelGGL(jbu_cls_logits_kernel, dim3(B), dim3(64), 0, s, cls, text, C, Q, p.clsl); SG_LAUNCH_CHECK(); }
+  if (use_cls) {
+    hipLaunchKernelGGL(jbu_cls_logits_kernel, dim3(B), dim3(64), 0, s, cls, text, C, Q, p.clsl);
+    SG_LAUNCH_CHECK();
+    g_jbu_rec.cls = "jbu_cls_logits_kernel";
+    SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_CLSL, p.clsl, (size_t)B * JBU_QMAX * 4, s));
+  }
+  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_FIN_A, x16, (size_t)pixels * C * 2, s));
   GemmBf16Args g{};
   g.A = x16; g.lda = C; g.W = (const bf16_t*)j->fin_w16; g.ldw = C; g.bias = j->fin_b; g.residual = (const float*)x16; g.ldr = C;
   g.C = p.rowdot; g.ldc = C; g.c_is_bf16 = 0; g.M = (int)pixels; g.N = C; g.K = C; g.batch = 1; g.act = 0; g.alpha = 0.1f;
   g.rowdot = p.rowdot; g.rowdot_ld = C / 64; g.rowdot_res_bf16 = 1;
   SG_TRY(gemm_bf16(g, s));
   const int slots = C / 64;
+  g_jbu_rec.fin = gemm_last_family(); g_jbu_rec.fin_a = "bf16";
+  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_ROWDOT, p.rowdot, (size_t)pixels * slots * 4, s));
   const unsigned grid = (unsigned)cdiv(pixels, 4 * 64 * PL_PPL);
 #define SG_JBU_PIX(QP)                                                                                                        \
   do {                                                                                                                         \
@@ -1736,12 +1873,14 @@ extern "C" int sg_jbu_logits(sg_jbu* j, const float* source, const float* guidan
     if (lds > 48 * 1024) SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_pixel_logits_kernel<QP, bf16_t>), lds)); \
     hipLaunchKernelGGL((jbu_pixel_logits_kernel<QP, bf16_t>), dim3(grid), dim3(256), lds, s, x16, p.rowdot, slots, p.geff, p.g0,  \
                        use_cls ? p.clsl : nullptr, cls_token_lambda, pixels, P, C, Q, logits);                                 \
+    g_jbu_rec.pix = "jbu_pixel_logits_kernel<" #QP ">";                                                                      \
   } while (0)
   if (Q <= 16 && C % 32 == 0) {                              // matrix-pipe form
     const size_t lds = (size_t)2 * 16 * (C + 8) * sizeof(bf16_t) + 4 * 64 * sizeof(float);
     SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_pixel_logits_mfma_kernel), lds));
     hipLaunchKernelGGL(jbu_pixel_logits_mfma_kernel, dim3((unsigned)cdiv(pixels, 4 * 64 * PLM_ROUNDS)), dim3(256), lds, s, x16, p.rowdot, slots, p.geff, p.g0,
                        use_cls ? p.clsl : nullptr, cls_token_lambda, pixels, P, C, Q, logits);
+    g_jbu_rec.pix = "jbu_pixel_logits_mfma_kernel";
   } else if (Q <= 8) SG_JBU_PIX(8); else if (Q <= 16) SG_JBU_PIX(16); else SG_JBU_PIX(32);
 #undef SG_JBU_PIX
   SG_LAUNCH_CHECK();

@@ -365,7 +365,10 @@ int  sg_text_encode(sg_text* t, const int32_t* tokens, int n_seq, float* out, vo
  * sg_jbu_upsample replaces self.upsampler(image_features, img) (segmentor.py:371 -> upsamplers.py:278-325):
  *   source [B, gh*gw, C] patch tokens (pixel-major), guidance [B,3,GH,GW] normalised tile -> out [B, 16gh*16gw, C].
  *   precision: SG_PREC_F32 (parity kernels), SG_PREC_F16X2 (f32-grade: the linears and the low-res adaptive convolution on three f16 MFMAs per
- *   product -- what an exact tower mode is paired with), SG_PREC_BF16 (throughput: low-res convolution on bf16 operands, f16 fixup chain). */
+ *   product -- what an exact tower mode is paired with), SG_PREC_BF16 (throughput: low-res convolution on bf16 operands, f16 fixup chain).
+ *   Precision, per kernel against f64 on its own operands (tests/jbu_reference.py): under SG_PREC_F16X2 the low-res convolution stays within
+ *   (2u 3 KP + 4u D + 2^-21) M + 2^-25 S_win (u = 2^-24, KP = 160 / 128 K slots, D = 2r + 1, M = sum_t |K_t| sum_s |w_s| |src_s|, S_win the
+ *   window's sum |src|), a median of <= 2.1e-4 of |out| in the tests; the two-plane fixup and final GEMMs within gemm_bound's two-plane terms. */
 typedef struct sg_jbu sg_jbu;
 int  sg_jbu_create(sg_jbu** out, int device, int kind, int feat_dim);
 void sg_jbu_destroy(sg_jbu* j);
@@ -383,6 +386,31 @@ int  sg_jbu_upsample(sg_jbu* j, const float* source, const float* guidance, int 
 int  sg_jbu_logits(sg_jbu* j, const float* source, const float* guidance, int B, int gh, int gw, int GH, int GW, int precision,
                    const float* text, int Q, const float* cls, float cls_token_lambda, float* logits, void* workspace, size_t workspace_bytes,
                    sg_stream s);
+
+/* Test instrumentation of the upsampler (tests/test_gpu_jbu_reference.py).  sg_jbu_set_capture(j, cap) with a non-NULL cap makes every later
+ * sg_jbu_upsample / sg_jbu_logits on j copy, on the call's stream, what each kernel of the unchanged kernel sequence read and wrote, in its
+ * stored format, into the caller's device buffers: slot.dst (NULL = not captured) must hold slot.cap bytes; the call sets slot.bytes to the
+ * bytes copied (0: that buffer did not exist in this dispatch) and fails with SG_ERR_INVALID if a region exceeds slot.cap.  cap must stay valid
+ * until capture is switched off with sg_jbu_set_capture(j, NULL).  Per stage (JBULearnedRange), in kernel order:
+ *   GS pooled guidance [px,3] f32 | PROJ range_proj [px,32] f32 | X range-kernel rows [px,d2+3] f32 | X16 operand rows [px,KP1] (bf16, f16 or
+ *   two-plane) | H1 GELU rows (f32 [px,d2], or [px,NP] 2-byte / two-plane) | KF kernel rows (f32 [px,d2] or [px,NP], f16 [px,NP]) |
+ *   SRC the convolution's source as stored, taken just before it (f32, bf16 or two-plane, [B,h,w,C]) | HR the bicubic output (f32 / bf16) |
+ *   OUT the stage's f32 output | OUT16 its bf16 / two-plane copy.
+ * Tail: FIN_A the final 1x1 GEMM's A operand | FIN_RES its f32 residual | GEFF [C,32] | G0 [32] | CLSL [B,32] | ROWDOT [px, C/64].
+ * sg_jbu_last_kernels(): the calling thread's last sg_jbu_upsample / sg_jbu_logits as space-separated key=value tokens: per stage k
+ * "sk.range= sk.x16= sk.fixup0= sk.fixup1= sk.kf= sk.src= sk.bicubic= sk.hr= sk.conv= sk.grid= sk.out16=", then "final=" (GEMM family) and
+ * "tail=" (comma-separated kernels); "none" before the first call on the thread (a call refused by its argument checks leaves the
+ * record as it was). */
+enum { SG_JBU_CAP_GS, SG_JBU_CAP_PROJ, SG_JBU_CAP_X, SG_JBU_CAP_X16, SG_JBU_CAP_H1, SG_JBU_CAP_KF, SG_JBU_CAP_SRC, SG_JBU_CAP_HR,
+       SG_JBU_CAP_OUT, SG_JBU_CAP_OUT16, SG_JBU_CAP_STAGE_SLOTS };
+enum { SG_JBU_CAP_FIN_A, SG_JBU_CAP_FIN_RES, SG_JBU_CAP_GEFF, SG_JBU_CAP_G0, SG_JBU_CAP_CLSL, SG_JBU_CAP_ROWDOT, SG_JBU_CAP_TAIL_SLOTS };
+typedef struct sg_jbu_capture_slot { void* dst; size_t cap; size_t bytes; } sg_jbu_capture_slot;
+typedef struct sg_jbu_capture {
+  sg_jbu_capture_slot stage[4][SG_JBU_CAP_STAGE_SLOTS];
+  sg_jbu_capture_slot tail[SG_JBU_CAP_TAIL_SLOTS];
+} sg_jbu_capture;
+int  sg_jbu_set_capture(sg_jbu* j, sg_jbu_capture* cap);
+const char* sg_jbu_last_kernels(void);
 
 /* the normalised, zero-padded tile planes [T,3,up_h,up_w] f32 the reference hands to the upsampler as `img`
  * (segmentor.py:424-431 crop + pad, :371) */

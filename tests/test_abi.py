@@ -155,3 +155,39 @@ def test_attention_raw_refusals_without_gpu():
         assert lib.sg_attention_last_kernel() == b"none", kw
     assert lib.sg_attention_stats_raw(0, p, 0, 0, p, 1, 1, 1, 64, 1.0, p, p, None) != 0
     assert b"bad precision" in lib.sg_last_error()
+
+
+def test_jbu_capture_and_launch_record_refusals():
+    """sg_jbu_set_capture refuses a null upsampler; sg_jbu_last_kernels is per thread, reads 'none' on a thread that never launched the
+    upsampler, and calls refused by their argument checks leave it as it was; the ctypes capture struct has the header's layout."""
+    import ctypes as C
+    import threading
+    from clip_decontamination_amd import _lib
+    lib = _lib.load()
+    seen = []
+
+    def fresh_thread():                      # a thread of its own: whatever earlier tests launched on this one does not matter
+        seen.append(lib.sg_jbu_last_kernels())
+        seen.append(lib.sg_jbu_upsample(None, None, None, 1, 2, 2, 32, 32, 0, None, None, 0, None))
+        seen.append(lib.sg_jbu_last_kernels())
+        seen.append(lib.sg_jbu_logits(None, None, None, 1, 2, 2, 32, 32, 2, None, 1, None, 0.0, None, None, 0, None))
+        seen.append(lib.sg_jbu_last_kernels())
+
+    t = threading.Thread(target=fresh_thread)
+    t.start()
+    t.join()
+    assert seen[0] == b"none" and seen[1] != 0 and seen[2] == b"none" and seen[3] != 0 and seen[4] == b"none", seen
+    before = lib.sg_jbu_last_kernels()
+    cap = _lib.JbuCapture()
+    assert lib.sg_jbu_set_capture(None, C.addressof(cap)) != 0
+    assert b"null upsampler" in lib.sg_last_error()
+    assert lib.sg_jbu_set_capture(None, None) != 0
+    assert lib.sg_jbu_upsample(None, None, None, 1, 2, 2, 32, 32, 0, None, None, 0, None) != 0
+    assert lib.sg_jbu_last_kernels() == before
+    assert C.sizeof(_lib.JbuCaptureSlot) == 3 * C.sizeof(C.c_size_t)
+    assert C.sizeof(cap) == (4 * len(_lib.JBU_CAP_STAGE) + len(_lib.JBU_CAP_TAIL)) * C.sizeof(_lib.JbuCaptureSlot)
+    src = open(HEADER).read()
+    stage = re.search(r"enum \{ (SG_JBU_CAP_GS[^}]*)\}", src).group(1)
+    assert [t.strip()[len("SG_JBU_CAP_"):] for t in stage.split(",")] == [*_lib.JBU_CAP_STAGE, "STAGE_SLOTS"]
+    tail = re.search(r"enum \{ (SG_JBU_CAP_FIN_A[^}]*)\}", src).group(1)
+    assert [t.strip()[len("SG_JBU_CAP_"):] for t in tail.split(",")] == [*_lib.JBU_CAP_TAIL, "TAIL_SLOTS"]
