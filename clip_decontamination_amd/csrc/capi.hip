@@ -1184,6 +1184,7 @@ extern "C" int sg_op_layernorm(const float* x, const float* gamma, const float* 
 extern "C" int sg_op_linear(const float* A, const float* W, const float* bias, const float* residual, float* C, int M, int N, int K,
                             int act, int precision, void* scratch, size_t scratch_bytes, sg_stream st) {
   SG_REQUIRE(A && W && C, "sg_op_linear: null pointer");
+  SG_REQUIRE(act >= ACT_NONE && act <= ACT_RELU, "sg_op_linear: act %d (0 none, 1 QuickGELU, 2 erf GELU, 3 ReLU)", act);
   hipStream_t s = as_stream(st);
   if (precision == SG_PREC_F32) return linear(HK_F32, A, K, W, bias, residual, C, N, true, M, N, K, act, s);
   const int hk = hk_of_precision(precision);

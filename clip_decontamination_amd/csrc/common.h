@@ -224,7 +224,7 @@ __device__ __forceinline__ float erf_gelu_fast(float x) {
   return 0.5f * x + 0.5f * fabsf(x) * e;                                                   // 0.5 x (1 + sign(x) erf(|x| / sqrt 2))
 }
 
-enum Act { ACT_NONE = 0, ACT_QUICK_GELU = 1, ACT_GELU = 2 };
+enum Act { ACT_NONE = 0, ACT_QUICK_GELU = 1, ACT_GELU = 2, ACT_RELU = 3 };
 
 // ---- optional live kernel timing (bench.py roofline): HIP events around the launches of one kernel family ----
 enum ProfCat { PROF_GEMM_BF16 = 0, PROF_ATTENTION = 1, PROF_GEMM_F32 = 2, PROF_GEMM_PERSIST = 3, PROF_GEMM_FP8 = 4, PROF_GEMM_PERSIST_LN_CONSUMER = 5,

@@ -114,6 +114,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmBf16Args a) {
         for (int e = 0; e < 4; ++e) {
           if (ACT == ACT_QUICK_GELU) v[e] = quick_gelu(v[e]);
           if (ACT == ACT_GELU) v[e] = erf_gelu_fast(v[e]);
+          if (ACT == ACT_RELU) v[e] = fmaxf(v[e], 0.f);
         }
         if (res) {
           const float4 r = *reinterpret_cast<const float4*>(res + (int64_t)m * a.ldr + n);
@@ -135,6 +136,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmBf16Args a) {
           if (a.bias) x += a.bias[n + e];
           if (ACT == ACT_QUICK_GELU) x = quick_gelu(x);
           if (ACT == ACT_GELU) x = erf_gelu_fast(x);
+          if (ACT == ACT_RELU) x = fmaxf(x, 0.f);
           if (res) x += res[(int64_t)m * a.ldr + n + e];
           if (C_BF16) reinterpret_cast<bf16_t*>(a.C)[(int64_t)z * a.strideC + (int64_t)m * a.ldc + n + e] = f2bf(x);
           else reinterpret_cast<float*>(a.C)[(int64_t)z * a.strideC + (int64_t)m * a.ldc + n + e] = x;
@@ -186,6 +188,9 @@ __device__ __forceinline__ void epilogue_store(f32x4 (&acc)[MI][NI], const GemmB
       } else if (act == ACT_GELU) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = SPLIT ? erf_gelu(v[e]) : erf_gelu_fast(v[e]);
+      } else if (act == ACT_RELU) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
       }
       *reinterpret_cast<float4*>(patch + (lane & 15) * LDP + j * 16 + (lane >> 4) * 4) = make_float4(v[0], v[1], v[2], v[3]);
     }
@@ -463,6 +468,9 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_ring(GemmBf16Args a
         } else if (act == ACT_GELU) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = erf_gelu_fast(v[e]);
+        } else if (SPEC == 0 && act == ACT_RELU) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
         }
         if (res) {
           const float4 r = *reinterpret_cast<const float4*>(res + (int64_t)m * a.ldr + n);
@@ -484,6 +492,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_ring(GemmBf16Args a
           if (a.bias) x += a.bias[n + e];
           if (act == ACT_QUICK_GELU) x = SPLIT ? quick_gelu_split(x) : quick_gelu(x);
           else if (act == ACT_GELU) x = SPLIT ? erf_gelu(x) : erf_gelu_fast(x);
+          else if (SPEC == 0 && act == ACT_RELU) x = fmaxf(x, 0.f);
           if (res) x += res[(int64_t)m * a.ldr + n + e];
           if (c_bf16) reinterpret_cast<bf16_t*>(a.C)[(int64_t)z * a.strideC + (int64_t)m * a.ldc + n + e] = F16 ? f2h(x).bits : f2bf(x);
           else reinterpret_cast<float*>(a.C)[(int64_t)z * a.strideC + (int64_t)m * a.ldc + n + e] = x;
@@ -653,6 +662,9 @@ __global__ __launch_bounds__(512) void gemm_bf16_pingpong(GemmBf16Args a, int ac
         } else if (act == ACT_GELU) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = erf_gelu_fast(v[e]);
+        } else if (act == ACT_RELU) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
         }
         if (res) {
           const float4 r = *reinterpret_cast<const float4*>(res + (int64_t)m * a.ldr + n);
@@ -674,6 +686,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pingpong(GemmBf16Args a, int ac
           if (a.bias) x += a.bias[n + e];
           if (act == ACT_QUICK_GELU) x = SPLIT ? quick_gelu_split(x) : quick_gelu(x);
           else if (act == ACT_GELU) x = SPLIT ? erf_gelu(x) : erf_gelu_fast(x);
+          else if (act == ACT_RELU) x = fmaxf(x, 0.f);
           if (res) x += res[(int64_t)m * a.ldr + n + e];
           if (c_bf16) reinterpret_cast<bf16_t*>(a.C)[(int64_t)z * a.strideC + (int64_t)m * a.ldc + n + e] = F16 ? f2h(x).bits : f2bf(x);
           else reinterpret_cast<float*>(a.C)[(int64_t)z * a.strideC + (int64_t)m * a.ldc + n + e] = x;
@@ -947,6 +960,9 @@ __device__ __forceinline__ void epilogue_store8(f32x4 (&acc)[MI][NI], const Gemm
       } else if (act == ACT_GELU) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = SPLIT ? erf_gelu(v[e]) : erf_gelu_fast(v[e]);
+      } else if (act == ACT_RELU) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
       }
       v4[j] = make_float4(v[0], v[1], v[2], v[3]);
     }
@@ -1261,6 +1277,9 @@ __device__ __forceinline__ void epilogue_store8_fp8(f32x4 (&acc)[MI][NI], const 
     } else if (act == ACT_GELU) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = erf_gelu_fast(v[e]);
+    } else if (act == ACT_RELU) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
     }
     return make_float4(v[0], v[1], v[2], v[3]);
   };
@@ -1723,7 +1742,7 @@ static int gemm_h2(const GemmBf16Args& a, hipStream_t s) {
   SG_REQUIRE(a.K % 32 == 0, "gemm_h2: K=%d must be a multiple of 32 (pad the operands)", a.K);
   SG_REQUIRE(a.lda % 8 == 0 && a.ldw % 8 == 0 && a.strideA % 8 == 0 && a.strideW % 8 == 0, "gemm_h2: operand strides must be multiples of 8 elements (32-byte storage groups)");
   SG_REQUIRE((((uintptr_t)a.A) & 31) == 0 && (((uintptr_t)a.W) & 31) == 0, "gemm_h2: operands must be 32-byte aligned");
-  SG_REQUIRE(a.act >= 0 && a.act <= 2, "gemm_h2: bad act %d", a.act);
+  SG_REQUIRE(a.act >= 0 && a.act <= 3, "gemm_h2: bad act %d", a.act);
   bool vec = (a.N % 8 == 0) && (a.ldc % 8 == 0) && (a.strideC % 8 == 0) && ((((uintptr_t)a.C) & 31) == 0);
   if (a.bias) vec = vec && ((((uintptr_t)a.bias) & 15) == 0);
   if (a.residual) vec = vec && (a.ldr % 4 == 0) && ((((uintptr_t)a.residual) & 15) == 0);
@@ -1766,7 +1785,7 @@ int gemm_bf16(const GemmBf16Args& a, hipStream_t s) {
   if (a.bias) vec = vec && ((((uintptr_t)a.bias) & 15) == 0);
   if (a.residual) vec = vec && (a.ldr % 4 == 0) && ((((uintptr_t)a.residual) & 15) == 0);
   (void)csz;
-  SG_REQUIRE(a.act >= 0 && a.act <= 2, "gemm_bf16: bad act %d", a.act);
+  SG_REQUIRE(a.act >= 0 && a.act <= 3, "gemm_bf16: bad act %d", a.act);
   if (a.rowdot)
     SG_REQUIRE(vec && a.residual && !a.c_is_bf16 && a.batch == 1 && a.M >= 1024 && a.N >= 512 && a.N % 64 == 0 && a.K / 32 >= 4,
                "gemm_bf16: the row-dot epilogue needs the persistent kernel (M >= 1024, N >= 512, N %% 64 == 0), an f32 residual and batch 1");
@@ -1829,6 +1848,8 @@ int gemm_bf16(const GemmBf16Args& a, hipStream_t s) {
     case 3: launch<ACT_QUICK_GELU, true>(a, vec, grid, s); break;
     case 4: launch<ACT_GELU, false>(a, vec, grid, s); break;
     case 5: launch<ACT_GELU, true>(a, vec, grid, s); break;
+    case 6: launch<ACT_RELU, false>(a, vec, grid, s); break;
+    case 7: launch<ACT_RELU, true>(a, vec, grid, s); break;
     default: return fail(SG_ERR_INVALID, "gemm_bf16: bad act %d", a.act);
   }
   note_launch("generic", tiles);

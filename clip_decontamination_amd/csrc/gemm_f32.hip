@@ -95,6 +95,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmF32Args a) {
         if (a.bias) x += a.bias[n];
         if (a.act == ACT_QUICK_GELU) x = quick_gelu_exact(x);
         else if (a.act == ACT_GELU) x = erf_gelu(x);
+        else if (a.act == ACT_RELU) x = fmaxf(x, 0.f);
         if (R) x += R[(int64_t)m * a.ldr + n];
         C[(int64_t)m * a.ldc + n] = x;
       }

@@ -117,17 +117,6 @@ __global__ __launch_bounds__(256) void cosine_logits_kernel(const float* __restr
   }
 }
 
-// ---- bilinear helpers (align_corners=False, ATen area_pixel_compute_source_index) ------------------------------------
-__device__ __forceinline__ void bilinear_tap(int dst, int in, int out, int& i0, int& i1, float& l0, float& l1) {
-  if (in == out) { i0 = i1 = dst; l0 = 1.f; l1 = 0.f; return; }            // same-size resize is an exact identity
-  const float scale = (float)in / (float)out;
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  i0 = (int)src; i0 = i0 > in - 1 ? in - 1 : i0;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = src - (float)i0; l0 = 1.f - l1;
-}
-
 // ---- stitch -------------------------------------------------------------------------------------------------------
 // Write-once: a pixel's contributions are summed in registers in raster order of the tiles (the reference's `preds[...] += `
 // order, so the f32 sum is bit-identical), divided by the count and stored a single time.  The row test of a tile is wave-uniform

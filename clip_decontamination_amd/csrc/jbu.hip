@@ -1098,6 +1098,7 @@ struct JbuStage {
 };
 static inline int jbu_np(int r) { const int d = 2 * r + 1; return (int)align_up((size_t)d * d, 64); }
 static inline int jbu_kp1(int r) { const int d = 2 * r + 1; return (int)align_up((size_t)d * d + 3, 64); }
+static inline size_t rc_kp(int C) { return align_up((size_t)C + 3, 64); }
 
 }  // namespace sg
 
@@ -1111,6 +1112,10 @@ struct sg_jbu {
   void* fin_w16;
   void* fin_wh2;                                           // two-plane f16 copy of the final 1x1 weight (C % 32 == 0)
   std::vector<uint8_t> have;
+  // kind 3 (resize_conv): conv{1..4} as f32 [C, C+3] (what the f32 GEMM reads) and packed [W_src | W_guid | 0] rows [C, KP] in bf16 and
+  // two-plane f16 (KP = align_up(C + 3, 64): the 2-byte GEMMs' K % 64 rule, the two-plane one's K % 32)
+  float *rc_w[4], *rc_b[4];
+  void *rc_w16[4], *rc_wh2[4];
   sg_jbu_capture* cap = nullptr;                           // test instrumentation (sg_jbu_set_capture): copies of every kernel's operands
 };
 
@@ -1133,9 +1138,39 @@ __global__ void scale_kernel(float* p, float a, int64_t n) {
 }  // namespace sg
 
 extern "C" int sg_jbu_create(sg_jbu** out, int device, int kind, int feat_dim) {
-  SG_REQUIRE(out && (kind == 0 || kind == 1) && feat_dim > 0 && feat_dim % 4 == 0, "sg_jbu_create: bad arguments (kind 0 = jbu_one, 1 = jbu_stack; feat_dim %% 4 == 0)");
+  SG_REQUIRE(out && kind >= 0 && kind <= 3 && feat_dim > 0 && feat_dim % 4 == 0 && (kind != SG_JBU_RESIZE_CONV || feat_dim % 8 == 0),
+             "sg_jbu_create: bad arguments (kind 0 = jbu_one, 1 = jbu_stack, 2 = bilinear, 3 = resize_conv; feat_dim %% 4 == 0, resize_conv %% 8)");
   DeviceGuard dg(device);
   sg_jbu* j = new sg_jbu();
+  if (kind == SG_JBU_BILINEAR) {                          // Bilinear (upsamplers.py:343-350) has no parameters: no arena, nothing to load
+    j->device = device; j->kind = kind; j->C = feat_dim; j->n_stage_sets = 0; j->arena = nullptr; j->arena_bytes = 0;
+    *out = j;
+    return SG_OK;
+  }
+  if (kind == SG_JBU_RESIZE_CONV) {                       // LayeredResizeConv(dim, 1) (upsamplers.py:178-200): four 1x1 convs over [src | guidance]
+    j->device = device; j->kind = kind; j->C = feat_dim; j->n_stage_sets = 0;
+    const size_t KP = rc_kp(feat_dim);
+    size_t off = 0;
+    auto take = [&](char* base, size_t n) { off = align_up(off, 256); void* p = base ? base + off : nullptr; off += n; return p; };
+    auto lay = [&](char* base) {
+      off = 0;
+      for (int k = 0; k < 4; ++k) {
+        j->rc_w[k] = (float*)take(base, (size_t)feat_dim * (feat_dim + 3) * 4);
+        j->rc_b[k] = (float*)take(base, (size_t)feat_dim * 4);
+        j->rc_w16[k] = take(base, (size_t)feat_dim * KP * 2);
+        j->rc_wh2[k] = take(base, (size_t)feat_dim * KP * 4);
+      }
+      return align_up(off, 256);
+    };
+    j->arena_bytes = lay(nullptr);
+    hipError_t e = hipMalloc(&j->arena, j->arena_bytes);
+    if (e != hipSuccess) { delete j; return fail(SG_ERR_HIP, "sg_jbu_create: hipMalloc(%zu) -> %s", j->arena_bytes, hipGetErrorString(e)); }
+    lay((char*)j->arena);
+    SG_HIP(hipMemset(j->arena, 0, j->arena_bytes));
+    j->have.assign(8, 0);
+    *out = j;
+    return SG_OK;
+  }
   j->device = device; j->kind = kind; j->C = feat_dim; j->n_stage_sets = kind == 0 ? 1 : 4;
   const int r = kind == 0 ? 5 : 3;                     // JBUOne radius 5, JBUStack radius 3 (upsamplers.py:281-284,308)
   size_t bytes = 0;
@@ -1176,8 +1211,30 @@ extern "C" void sg_jbu_destroy(sg_jbu* j) {
 
 extern "C" int sg_jbu_set_tensor(sg_jbu* j, const char* name, const float* src, int64_t numel, sg_stream st) {
   SG_REQUIRE(j && name && src, "sg_jbu_set_tensor: null argument");
+  if (j->kind == SG_JBU_BILINEAR) return fail(SG_ERR_INVALID, "sg_jbu_set_tensor: the bilinear upsampler has no tensor '%s'", name);
   DeviceGuard dg(j->device);
   hipStream_t s = as_stream(st);
+  if (j->kind == SG_JBU_RESIZE_CONV) {                    // "conv{1..4}.weight" [C, C+3, 1, 1] / "conv{1..4}.bias" [C]
+    const int C = j->C;
+    if (!strncmp(name, "conv", 4) && name[4] >= '1' && name[4] <= '4' && name[5] == '.') {
+      const int k = name[4] - '1';
+      if (!strcmp(name + 6, "weight")) {
+        SG_REQUIRE(numel == (int64_t)C * (C + 3), "sg_jbu_set_tensor(%s): expected %lld elements, got %lld", name, (long long)C * (C + 3), (long long)numel);
+        SG_HIP(hipMemcpyAsync(j->rc_w[k], src, (size_t)numel * 4, hipMemcpyDeviceToDevice, s));
+        SG_TRY(pack_rows(src, C, C + 3, C + 3, j->rc_w16[k], (int)rc_kp(C), HK_BF16, s));
+        SG_TRY(pack_rows(src, C, C + 3, C + 3, j->rc_wh2[k], (int)rc_kp(C), HK_F16X2, s));
+        j->have[2 * k] = 1;
+        return SG_OK;
+      }
+      if (!strcmp(name + 6, "bias")) {
+        SG_REQUIRE(numel == C, "sg_jbu_set_tensor(%s): expected %d elements, got %lld", name, C, (long long)numel);
+        SG_HIP(hipMemcpyAsync(j->rc_b[k], src, (size_t)C * 4, hipMemcpyDeviceToDevice, s));
+        j->have[2 * k + 1] = 1;
+        return SG_OK;
+      }
+    }
+    return fail(SG_ERR_INVALID, "sg_jbu_set_tensor: unknown tensor name '%s' for resize_conv", name);
+  }
   auto put = [&](float* dst, int64_t n) -> int {
     SG_REQUIRE(numel == n, "sg_jbu_set_tensor(%s): expected %lld elements, got %lld", name, (long long)n, (long long)numel);
     SG_HIP(hipMemcpyAsync(dst, src, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
@@ -1246,6 +1303,37 @@ static size_t jbu_plan(const sg_jbu* j, int B, int gh, int gw, void* ws, bool dr
   p.clsl = (float*)take((size_t)B * JBU_QMAX * 4);
   return align_up(off, 256);
 }
+// kind 2 (bilinear): the per-token prologue's outputs -- y = tokens . T^T [B*n, JBU_QMAX] and the Gram terms [B*n, BL_G] -- and the CLS logits
+constexpr int BL_G = 8;                              // 5 Gram terms per token, rows padded to 32 bytes
+struct BilinearPlan { float *y, *gram, *clsl; };
+static size_t bilinear_plan(int B, int gh, int gw, void* ws, bool dry, BilinearPlan& p) {
+  const size_t tokens = (size_t)B * gh * gw;
+  size_t off = 0;
+  auto take = [&](size_t n) { off = align_up(off, 256); void* q = dry ? nullptr : (char*)ws + off; off += n; return q; };
+  p.y = (float*)take(tokens * JBU_QMAX * 4);
+  p.gram = (float*)take(tokens * BL_G * 4);
+  p.clsl = (float*)take((size_t)B * JBU_QMAX * 4);
+  return align_up(off, 256);
+}
+static int bilinear_upsample(sg_jbu* j, const float* source, int B, int gh, int gw, int GH, int GW, float* out, hipStream_t s);
+// kind 3 (resize_conv): per stage the bilinear x2 source [P, C] f32 (the GEMM's residual), the GEMM's A rows [P, KP] (4 bytes per element
+// at most) and the stage outputs of stages 1..3 (stage 4 writes the caller's output)
+struct ResizeConvPlan { float *big, *s1, *s2, *s3; void* a; };
+static size_t resize_conv_plan(int C, int B, int gh, int gw, void* ws, bool dry, ResizeConvPlan& p) {
+  const size_t n = (size_t)B * gh * gw;
+  size_t off = 0;
+  auto take = [&](size_t b) { off = align_up(off, 256); void* q = dry ? nullptr : (char*)ws + off; off += b; return q; };
+  p.big = (float*)take(n * 256 * C * 4);
+  p.a = take(n * 256 * rc_kp(C) * 4);
+  p.s1 = (float*)take(n * 4 * C * 4);
+  p.s2 = (float*)take(n * 16 * C * 4);
+  p.s3 = (float*)take(n * 64 * C * 4);
+  return align_up(off, 256);
+}
+static int resize_conv_upsample(sg_jbu* j, const float* source, const float* guidance, int B, int gh, int gw, int GH, int GW, int precision,
+                                float* out, void* ws, size_t ws_bytes, hipStream_t s);
+static int bilinear_logits(sg_jbu* j, const float* source, int B, int gh, int gw, int GH, int GW, const float* text, int Q,
+                           const float* cls, float cls_token_lambda, float* logits, void* ws, size_t ws_bytes, hipStream_t s);
 }  // namespace sg
 
 namespace sg {
@@ -1305,6 +1393,8 @@ extern "C" const char* sg_jbu_last_kernels(void) {
 
 extern "C" size_t sg_jbu_workspace_bytes(const sg_jbu* j, int B, int gh, int gw) {
   if (!j || B <= 0 || gh <= 0 || gw <= 0) return 0;
+  if (j->kind == SG_JBU_BILINEAR) { BilinearPlan p; return bilinear_plan(B, gh, gw, nullptr, true, p); }
+  if (j->kind == SG_JBU_RESIZE_CONV) { ResizeConvPlan p; return resize_conv_plan(j->C, B, gh, gw, nullptr, true, p); }
   JbuPlan p;
   return jbu_plan(j, B, gh, gw, nullptr, true, p);
 }
@@ -1544,7 +1634,19 @@ static int jbu_stages(sg_jbu* j, const float* source, const float* guidance, int
 // source [B, gh*gw, C] (patch tokens), guidance [B,3,GH,GW] (the normalised, padded tile) -> out [B, (16gh*16gw), C]
 extern "C" int sg_jbu_upsample(sg_jbu* j, const float* source, const float* guidance, int B, int gh, int gw, int GH, int GW, int precision,
                                float* out, void* ws, size_t ws_bytes, sg_stream st) {
-  SG_REQUIRE(j && source && guidance && out && ws, "sg_jbu_upsample: null argument");
+  SG_REQUIRE(j && source && guidance && out, "sg_jbu_upsample: null argument");
+  if (j->kind == SG_JBU_BILINEAR) {
+    SG_REQUIRE(B > 0 && gh > 0 && gw > 0 && GH > 0 && GW > 0, "sg_jbu_upsample: bad shape");
+    DeviceGuard dg(j->device);
+    return bilinear_upsample(j, source, B, gh, gw, GH, GW, out, as_stream(st));
+  }
+  if (j->kind == SG_JBU_RESIZE_CONV) {
+    SG_REQUIRE(ws && B > 0 && gh > 0 && gw > 0 && GH > 0 && GW > 0, "sg_jbu_upsample: bad arguments");
+    for (size_t i = 0; i < j->have.size(); ++i) if (!j->have[i]) return fail(SG_ERR_STATE, "sg_jbu_upsample: upsampler weights incomplete");
+    DeviceGuard dg(j->device);
+    return resize_conv_upsample(j, source, guidance, B, gh, gw, GH, GW, precision, out, ws, ws_bytes, as_stream(st));
+  }
+  SG_REQUIRE(ws, "sg_jbu_upsample: null argument");
   for (size_t i = 0; i < j->have.size(); ++i) if (!j->have[i]) return fail(SG_ERR_STATE, "sg_jbu_upsample: upsampler weights incomplete");
   DeviceGuard dg(j->device);
   hipStream_t s = as_stream(st);
@@ -1830,6 +1932,13 @@ extern "C" int sg_jbu_logits(sg_jbu* j, const float* source, const float* guidan
                              sg_stream st) {
   SG_REQUIRE(j && source && guidance && text && logits && ws, "sg_jbu_logits: null argument");
   SG_REQUIRE(Q >= 1 && Q <= JBU_QMAX, "sg_jbu_logits: 1 <= Q <= %d", JBU_QMAX);
+  if (j->kind == SG_JBU_BILINEAR) {                       // every precision: the bilinear logits are f32 arithmetic throughout
+    SG_REQUIRE(B > 0 && gh > 0 && gw > 0 && GH > 0 && GW > 0, "sg_jbu_logits: bad shape");
+    DeviceGuard dg(j->device);
+    return bilinear_logits(j, source, B, gh, gw, GH, GW, text, Q, cls, cls_token_lambda, logits, ws, ws_bytes, as_stream(st));
+  }
+  if (j->kind == SG_JBU_RESIZE_CONV)
+    return fail(SG_ERR_INVALID, "sg_jbu_logits: resize_conv has no fused logits tail; use sg_jbu_upsample + sg_cosine_logits");
   SG_REQUIRE(precision == SG_PREC_BF16 && j->C % 64 == 0 && j->C >= 512, "sg_jbu_logits: the fused tail is the bf16 throughput path (C %% 64 == 0, C >= 512); use sg_jbu_upsample + sg_cosine_logits otherwise");
   for (size_t i = 0; i < j->have.size(); ++i) if (!j->have[i]) return fail(SG_ERR_STATE, "sg_jbu_logits: upsampler weights incomplete");
   DeviceGuard dg(j->device);
@@ -1886,6 +1995,252 @@ extern "C" int sg_jbu_logits(sg_jbu* j, const float* source, const float* guidan
   SG_LAUNCH_CHECK();
   return SG_OK;
 }
+
+namespace sg {
+// ---- kind 2: Bilinear (upsamplers.py:343-350) -------------------------------------------------------------------------------------
+// The reference resizes the patch features to the tile (F.interpolate(feats, (H, W), mode='bilinear')), normalises every pixel and takes
+// its product with the text features.  By linearity the [GH*GW, C] feature map is never needed: a pixel p interpolates the four corners
+// f_k of its cell with weights w_k, so  T . f(p) = sum_k w_k (T . f_k)  and  |f(p)|^2 = sum_k sum_l w_k w_l <f_k, f_l>.  A per-token
+// prologue computes y_k = T . f_k and the five Gram terms that cover the ten products of any cell; the per-pixel kernel then costs four
+// Q-wide row reads (cache-resident: a tile's y is <= 177 kB) per Q stored logits.
+
+// One wave per token (i, j): lanes walk the channels of f_ij and of its right, lower and lower-right neighbours (absent neighbours read
+// as zero) and reduce y (Q dots with the text rows) and  g = (|f_ij|^2, <f_ij, f_i,j+1>, <f_ij, f_i+1,j>, <f_ij, f_i+1,j+1>,
+// <f_i,j+1, f_i+1,j>).  f32 with f32 accumulation in every precision mode (~40 MFLOP per 512-pixel ViT-L/14 tile).
+__global__ __launch_bounds__(256) void bilinear_prologue_kernel(const float* __restrict__ tok, const float* __restrict__ text, int B, int gh,
+                                                                int gw, int C, int Q, float* __restrict__ y, float* __restrict__ gram) {
+  const int lane = threadIdx.x & 63;
+  const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int n = gh * gw;
+  if (t >= (int64_t)B * n) return;
+  const int k = (int)(t % n), i = k / gw, jx = k % gw;
+  const bool has_r = jx + 1 < gw, has_d = i + 1 < gh;
+  const float* f = tok + t * C;
+  const float* fr = f + C;
+  const float* fd = f + (int64_t)gw * C;
+  const float* fdr = fd + C;
+  float acc[JBU_QMAX];
+#pragma unroll
+  for (int q = 0; q < JBU_QMAX; ++q) acc[q] = 0.f;
+  float g0 = 0.f, g1 = 0.f, g2 = 0.f, g3 = 0.f, g4 = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    const float a = f[c];
+    const float r = has_r ? fr[c] : 0.f;
+    const float d = has_d ? fd[c] : 0.f;
+    const float dr = has_r && has_d ? fdr[c] : 0.f;
+    g0 += a * a; g1 += a * r; g2 += a * d; g3 += a * dr; g4 += r * d;
+#pragma unroll
+    for (int q = 0; q < JBU_QMAX; ++q)
+      if (q < Q) acc[q] += a * text[(int64_t)q * C + c];
+  }
+  g0 = wave_sum(g0); g1 = wave_sum(g1); g2 = wave_sum(g2); g3 = wave_sum(g3); g4 = wave_sum(g4);
+  float mine = 0.f;                                   // lane q keeps the reduced y_q: one coalesced 128-byte row store
+#pragma unroll
+  for (int q = 0; q < JBU_QMAX; ++q)
+    if (q < Q) {
+      const float v = wave_sum(acc[q]);
+      if (lane == q) mine = v;
+    }
+  if (lane < JBU_QMAX) y[t * JBU_QMAX + lane] = mine;
+  if (lane < BL_G) {
+    const float gv[BL_G] = {g0, g1, g2, g3, g4, 0.f, 0.f, 0.f};
+    float v = 0.f;
+#pragma unroll
+    for (int e = 0; e < BL_G; ++e) if (lane == e) v = gv[e];
+    gram[t * BL_G + lane] = v;
+  }
+}
+
+// the four corners of a pixel's cell along one axis: bilinear_tap (sg_resize_bilinear's / sg_stitch's align_corners=False arithmetic,
+// edge clamping included) with a clamped second index folded into the first, so that the cell is always (i0, i0 + 1) and the second weight
+// is exactly zero where the reference reads row i0 twice; i1c is the index to read (in range even where the weight is zero)
+__device__ __forceinline__ void bilinear_cell(int dst, int in, int out, int& i0, int& i1c, float& l0, float& l1) {
+  int i1;
+  bilinear_tap(dst, in, out, i0, i1, l0, l1);
+  if (i1 == i0) { l0 = l0 + l1; l1 = 0.f; }
+  i1c = i0 + 1 < in ? i0 + 1 : i0;
+}
+
+// out[b, q, Y*GW + X] = (sum_k w_k y_kq) / sqrt(sum_kl w_k w_l G_kl) + lambda * clsl[b, q].  64 x 4 pixels per block, one pixel per lane:
+// the stores of a query are 256 contiguous bytes per wave; the y rows are read as float4 (the Q loop runs in groups of 4).
+__global__ __launch_bounds__(256) void bilinear_pixel_logits_kernel(const float* __restrict__ y, const float* __restrict__ gram,
+                                                                    const float* __restrict__ clsl, float lambda, int gh, int gw, int GH,
+                                                                    int GW, int Q, float* __restrict__ out) {
+  const int X = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int Y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  const int b = blockIdx.z;
+  if (X >= GW || Y >= GH) return;
+  int r0, r1, c0, c1; float v0, v1, u0, u1;
+  bilinear_cell(Y, gh, GH, r0, r1, v0, v1);
+  bilinear_cell(X, gw, GW, c0, c1, u0, u1);
+  const int64_t base = (int64_t)b * gh * gw;
+  const int64_t t00 = base + (int64_t)r0 * gw + c0, t01 = base + (int64_t)r0 * gw + c1;
+  const int64_t t10 = base + (int64_t)r1 * gw + c0, t11 = base + (int64_t)r1 * gw + c1;
+  const float w00 = v0 * u0, w01 = v0 * u1, w10 = v1 * u0, w11 = v1 * u1;
+  const float4 ga = *reinterpret_cast<const float4*>(gram + t00 * BL_G);       // g0..g3 of the top-left corner
+  const float g4 = gram[t00 * BL_G + 4];
+  const float d01 = gram[t01 * BL_G], d10 = gram[t10 * BL_G], d11 = gram[t11 * BL_G];
+  const float r01 = gram[t01 * BL_G + 2], b10 = gram[t10 * BL_G + 1];          // <f01, f11>, <f10, f11>
+  float d2 = w00 * w00 * ga.x + w01 * w01 * d01 + w10 * w10 * d10 + w11 * w11 * d11;
+  d2 += 2.f * (w00 * (w01 * ga.y + w10 * ga.z + w11 * ga.w) + w01 * (w10 * g4 + w11 * r01) + w10 * w11 * b10);
+  const float inv = 1.0f / sqrtf(d2);
+  const int64_t plane = (int64_t)GH * GW;
+  float* o = out + (int64_t)b * Q * plane + (int64_t)Y * GW + X;
+  const float* cl = clsl ? clsl + b * JBU_QMAX : nullptr;
+  for (int q = 0; q < Q; q += 4) {
+    const float4 a = *reinterpret_cast<const float4*>(y + t00 * JBU_QMAX + q);
+    const float4 bq = *reinterpret_cast<const float4*>(y + t01 * JBU_QMAX + q);
+    const float4 c = *reinterpret_cast<const float4*>(y + t10 * JBU_QMAX + q);
+    const float4 d = *reinterpret_cast<const float4*>(y + t11 * JBU_QMAX + q);
+    const float num[4] = {w00 * a.x + w01 * bq.x + w10 * c.x + w11 * d.x, w00 * a.y + w01 * bq.y + w10 * c.y + w11 * d.y,
+                          w00 * a.z + w01 * bq.z + w10 * c.z + w11 * d.z, w00 * a.w + w01 * bq.w + w10 * c.w + w11 * d.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (q + e < Q) o[(int64_t)(q + e) * plane] = num[e] * inv + (cl ? lambda * cl[q + e] : 0.f);
+  }
+}
+
+// The plain feature output of kind 2 (sg_jbu_upsample: [B, GH*GW, C], the reference module's own result; the logits path never makes it):
+// one wave per output pixel, lanes over channels, torch's  (top * wy0 + bottom * wy1)  blend of the two rows.
+__global__ __launch_bounds__(256) void bilinear_features_kernel(const float* __restrict__ src, int B, int gh, int gw, int GH, int GW, int C,
+                                                                float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (p >= (int64_t)B * GH * GW) return;
+  const int b = (int)(p / ((int64_t)GH * GW)), rem = (int)(p % ((int64_t)GH * GW)), Y = rem / GW, X = rem % GW;
+  int ya, yb, xa, xb; float wy0, wy1, wx0, wx1;
+  bilinear_tap(Y, gh, GH, ya, yb, wy0, wy1);
+  bilinear_tap(X, gw, GW, xa, xb, wx0, wx1);
+  const float* s = src + (int64_t)b * gh * gw * C;
+  const float *p00 = s + ((int64_t)ya * gw + xa) * C, *p01 = s + ((int64_t)ya * gw + xb) * C;
+  const float *p10 = s + ((int64_t)yb * gw + xa) * C, *p11 = s + ((int64_t)yb * gw + xb) * C;
+  float* o = out + p * C;
+  for (int c = lane; c < C; c += 64) {
+    const float top = p00[c] * wx0 + p01[c] * wx1;
+    const float bot = p10[c] * wx0 + p11[c] * wx1;
+    o[c] = top * wy0 + bot * wy1;
+  }
+}
+
+static int bilinear_upsample(sg_jbu* j, const float* source, int B, int gh, int gw, int GH, int GW, float* out, hipStream_t s) {
+  const int64_t pixels = (int64_t)B * GH * GW;
+  SG_REQUIRE(cdiv(pixels, 4) < (1ll << 31), "sg_jbu_upsample: too many pixels");
+  jbu_rec_start();
+  jbu_cap_reset(j);
+  hipLaunchKernelGGL(bilinear_features_kernel, dim3((unsigned)cdiv(pixels, 4)), dim3(256), 0, s, source, B, gh, gw, GH, GW, j->C, out);
+  SG_LAUNCH_CHECK();
+  g_jbu_rec.fin = "bilinear_features_kernel";
+  return SG_OK;
+}
+
+static int bilinear_logits(sg_jbu* j, const float* source, int B, int gh, int gw, int GH, int GW, const float* text, int Q,
+                           const float* cls, float cls_token_lambda, float* logits, void* ws, size_t ws_bytes, hipStream_t s) {
+  BilinearPlan p;
+  const size_t need = bilinear_plan(B, gh, gw, ws, false, p);
+  if (need > ws_bytes) return fail(SG_ERR_STATE, "sg_jbu_logits: workspace %zu < required %zu", ws_bytes, need);
+  const int64_t tokens = (int64_t)B * gh * gw;
+  SG_REQUIRE(cdiv(tokens, 4) < (1ll << 31) && cdiv(GH, 4) < 65536 && B < 65536, "sg_jbu_logits: shape too large for one launch");
+  jbu_rec_start();
+  jbu_cap_reset(j);
+  hipLaunchKernelGGL(bilinear_prologue_kernel, dim3((unsigned)cdiv(tokens, 4)), dim3(256), 0, s, source, text, B, gh, gw, j->C, Q, p.y, p.gram);
+  SG_LAUNCH_CHECK();
+  g_jbu_rec.geff = "bilinear_prologue_kernel";
+  const bool use_cls = cls != nullptr && cls_token_lambda != 0.f;
+  if (use_cls) {
+    hipLaunchKernelGGL(jbu_cls_logits_kernel, dim3(B), dim3(64), 0, s, cls, text, j->C, Q, p.clsl);
+    SG_LAUNCH_CHECK();
+    g_jbu_rec.cls = "jbu_cls_logits_kernel";
+  }
+  hipLaunchKernelGGL(bilinear_pixel_logits_kernel, dim3((unsigned)cdiv(GW, 64), (unsigned)cdiv(GH, 4), (unsigned)B), dim3(256), 0, s, p.y,
+                     p.gram, use_cls ? p.clsl : nullptr, cls_token_lambda, gh, gw, GH, GW, Q, logits);
+  SG_LAUNCH_CHECK();
+  g_jbu_rec.pix = "bilinear_pixel_logits_kernel";
+  return SG_OK;
+}
+
+// ---- kind 3: LayeredResizeConv(dim, 1) (upsamplers.py:178-200) ---------------------------------------------------------------------
+// Per stage: big = bilinear x2 of the stage source (F.interpolate(scale_factor=2), align_corners=False), guid = the tile resized to big's
+// size (size-based, no antialias: at patch 14 the last stage upsamples it), out = act(conv1x1([big | guid])) + big.  The operand producer
+// writes big (f32, the GEMM's residual) and the GEMM's A rows [big (C) | guid (3) | 0] in the precision's storage; the 1x1 conv is one GEMM
+// with the epilogue act(acc + bias) + residual (ReLU on stages 1-3, none on stage 4).  One wave per output pixel, lanes over channels.
+template <typename T>
+__global__ __launch_bounds__(256) void resize_conv_operands_kernel(const float* __restrict__ src, const float* __restrict__ guid, int B, int h,
+                                                                   int w, int GH, int GW, int C, int KP, float* __restrict__ big, T* __restrict__ A) {
+  const int lane = threadIdx.x & 63;
+  const int H2 = 2 * h, W2 = 2 * w;
+  const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (p >= (int64_t)B * H2 * W2) return;
+  const int b = (int)(p / ((int64_t)H2 * W2)), rem = (int)(p % ((int64_t)H2 * W2)), Y = rem / W2, X = rem % W2;
+  int ya, yb, xa, xb; float wy0, wy1, wx0, wx1;
+  bilinear_tap(Y, h, H2, ya, yb, wy0, wy1);
+  bilinear_tap(X, w, W2, xa, xb, wx0, wx1);
+  const float* sb = src + (int64_t)b * h * w * C;
+  const float *p00 = sb + ((int64_t)ya * w + xa) * C, *p01 = sb + ((int64_t)ya * w + xb) * C;
+  const float *p10 = sb + ((int64_t)yb * w + xa) * C, *p11 = sb + ((int64_t)yb * w + xb) * C;
+  float* bo = big + p * C;
+  T* ar = A + p * KP;
+  for (int c = lane; c < C; c += 64) {
+    const float top = p00[c] * wx0 + p01[c] * wx1;
+    const float bot = p10[c] * wx0 + p11[c] * wx1;
+    const float v = top * wy0 + bot * wy1;
+    bo[c] = v;
+    st_elem<T>(ar, c, v);
+  }
+  for (int c = C + lane; c < KP; c += 64) {
+    float v = 0.f;
+    if (c < C + 3) {                                   // guidance channel c - C resized to (2h, 2w)
+      int ga, gb, gc, gd; float u0, u1, v0, v1;
+      bilinear_tap(Y, GH, H2, ga, gb, v0, v1);
+      bilinear_tap(X, GW, W2, gc, gd, u0, u1);
+      const float* g = guid + ((int64_t)b * 3 + (c - C)) * GH * GW;
+      const float top = g[(int64_t)ga * GW + gc] * u0 + g[(int64_t)ga * GW + gd] * u1;
+      const float bot = g[(int64_t)gb * GW + gc] * u0 + g[(int64_t)gb * GW + gd] * u1;
+      v = top * v0 + bot * v1;
+    }
+    st_elem<T>(ar, c, v);
+  }
+}
+
+static int resize_conv_upsample(sg_jbu* j, const float* source, const float* guidance, int B, int gh, int gw, int GH, int GW, int precision,
+                                float* out, void* ws, size_t ws_bytes, hipStream_t s) {
+  ResizeConvPlan p;
+  const size_t need = resize_conv_plan(j->C, B, gh, gw, ws, false, p);
+  if (need > ws_bytes) return fail(SG_ERR_STATE, "sg_jbu_upsample: workspace %zu < required %zu", ws_bytes, need);
+  const int C = j->C, KP = (int)rc_kp(C);
+  const int hk = precision == SG_PREC_F32 ? HK_F32 : precision == SG_PREC_F16X2 ? HK_F16X2 : HK_BF16;
+  SG_REQUIRE((int64_t)B * 256 * gh * gw < (1ll << 31), "sg_jbu_upsample: too many pixels");
+  jbu_rec_start();
+  jbu_cap_reset(j);
+  const float* src = source;
+  float* outs[4] = {p.s1, p.s2, p.s3, out};
+  int h = gh, w = gw;
+  for (int k = 0; k < 4; ++k) {
+    const int64_t P = (int64_t)B * 4 * h * w;
+    const dim3 grid((unsigned)cdiv(P, 4));
+    if (hk == HK_F32) hipLaunchKernelGGL(resize_conv_operands_kernel<float>, grid, dim3(256), 0, s, src, guidance, B, h, w, GH, GW, C, KP, p.big, (float*)p.a);
+    else if (hk == HK_F16X2) hipLaunchKernelGGL(resize_conv_operands_kernel<h2_t>, grid, dim3(256), 0, s, src, guidance, B, h, w, GH, GW, C, KP, p.big, (h2_t*)p.a);
+    else hipLaunchKernelGGL(resize_conv_operands_kernel<bf16_t>, grid, dim3(256), 0, s, src, guidance, B, h, w, GH, GW, C, KP, p.big, (bf16_t*)p.a);
+    SG_LAUNCH_CHECK();
+    const int act = k < 3 ? ACT_RELU : ACT_NONE;
+    if (hk == HK_F32) {
+      GemmF32Args g{};
+      g.A = (const float*)p.a; g.lda = KP; g.B = j->rc_w[k]; g.sbk = 1; g.sbn = C + 3; g.bias = j->rc_b[k]; g.residual = p.big; g.ldr = C;
+      g.C = outs[k]; g.ldc = C; g.M = (int)P; g.N = C; g.K = C + 3; g.batch = 1; g.inner = 1; g.act = act; g.alpha = 1.f;
+      SG_TRY(gemm_f32(g, s));
+    } else {
+      GemmBf16Args g{};
+      g.A = (const bf16_t*)p.a; g.lda = KP; g.W = (const bf16_t*)(hk == HK_F16X2 ? j->rc_wh2[k] : j->rc_w16[k]); g.ldw = KP; g.bias = j->rc_b[k];
+      g.residual = p.big; g.ldr = C; g.C = outs[k]; g.ldc = C; g.c_is_bf16 = 0; g.M = (int)P; g.N = C; g.K = KP; g.batch = 1; g.act = act;
+      g.alpha = 1.f; g.h2 = hk == HK_F16X2 ? 1 : 0;
+      SG_TRY(gemm_bf16(g, s));
+    }
+    src = outs[k];
+    h *= 2; w *= 2;
+  }
+  g_jbu_rec.fin = hk == HK_F32 ? "resize_conv:gemm_f32" : hk == HK_F16X2 ? "resize_conv:gemm_h2" : "resize_conv:gemm_bf16";
+  return SG_OK;
+}
+}  // namespace sg
 
 extern "C" int sg_extract_tiles(const sg_tile_batch* t, int up_h, int up_w, float* out, sg_stream s) {
   SG_REQUIRE(t && out && t->scene && t->windows && t->n_tiles > 0, "sg_extract_tiles: bad arguments");

@@ -88,4 +88,15 @@ int fusion_mask_normalize(float* A, const int32_t* idx, int B, int N, int k, hip
 int attn_mode_enhance(float* tokens, int64_t sb, int64_t st, float* A, int B, int N, int D, float strength, float threshold, float* tmp,
                       hipStream_t s);
 
+// ---- bilinear helpers (align_corners=False, ATen area_pixel_compute_source_index) ------------------------------------
+__device__ __forceinline__ void bilinear_tap(int dst, int in, int out, int& i0, int& i1, float& l0, float& l1) {
+  if (in == out) { i0 = i1 = dst; l0 = 1.f; l1 = 0.f; return; }            // same-size resize is an exact identity
+  const float scale = (float)in / (float)out;
+  float src = scale * ((float)dst + 0.5f) - 0.5f;
+  src = src < 0.f ? 0.f : src;
+  i0 = (int)src; i0 = i0 > in - 1 ? in - 1 : i0;
+  i1 = i0 + (i0 < in - 1 ? 1 : 0);
+  l1 = src - (float)i0; l0 = 1.f - l1;
+}
+
 }  // namespace sg

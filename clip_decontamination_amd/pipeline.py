@@ -529,7 +529,8 @@ class SegPipeline:
                                    cf.get("fusion_strength", 0.3), grid_of_tiles[1])
         tok = sharded_cross_tile_fusion(tok, steps, T, world, rank, group)
         if n_real == 0:
-            return tok.new_zeros((0, self.num_queries) + ((16 * gh, 16 * gw) if self.upsampler is not None else (gh, gw)))
+            up_hw = (tile_hw[0] + t + b, tile_hw[1] + l + r)
+            return tok.new_zeros((0, self.num_queries) + (self.upsampler.output_hw((gh, gw), up_hw) if self.upsampler is not None else (gh, gw)))
         tok, f = self._pre_head(tok, cls)
         if self.upsampler is not None:                   # fused tokens -> JBU -> per-pixel logits of this rank's tiles (they travel as halo tiles)
             return self.upsampler.logits(tok, cls, scene, win[:n_real], tile_hw, (l, t), (gh, gw), self.text, f, self.cls_token_lambda, None,
@@ -553,9 +554,9 @@ class SegPipeline:
         def tile_bytes(thw):
             l, r, t, b = compute_padsize(thw[0], thw[1], P)
             gh, gw = (thw[0] + t + b) // P, (thw[1] + l + r) // P
-            S = 256 if self.upsampler is not None else 1
+            oh, ow = self.upsampler.output_hw((gh, gw), (thw[0] + t + b, thw[1] + l + r)) if self.upsampler is not None else (gh, gw)
             tok = gh * gw * self.visual.cfg.embed_dim * 4 if self.cross_tile_fusion is not None else 0
-            return 4 * Q * gh * gw * S + tok
+            return 4 * Q * oh * ow + tok
 
         groups = plan_images(shapes, stride, crop, P, self.tiles_per_launch, tile_bytes, 4 * Q, self.flush_bytes)
         for g in groups:

@@ -58,6 +58,7 @@ VIT_CONFIGS: Dict[str, VitConfig] = {
     # tiny shapes used by the golden fixtures and CPU-side tests
     "tiny-8": VitConfig("tiny-8", 64, 4, 2, 8, 32, image_size=32),
     "tiny-16": VitConfig("tiny-16", 128, 5, 2, 16, 64, image_size=64),
+    "tiny-14": VitConfig("tiny-14", 64, 4, 2, 14, 32, image_size=56),     # patch 14 (the L/14 and H/14 geometry) at test size
     "tiny-gem": VitConfig("tiny-gem", 64, 8, 2, 8, 32, image_size=32),     # >= 7 layers for GEM depth 7
     "tiny-gelu": VitConfig("tiny-gelu", 64, 4, 2, 8, 32, image_size=32, quick_gelu=False),
     # ONE head: the only head count at which the reference's apply_layer_fusion + outlier suppressor path runs (R9) -- pins its semantics
@@ -232,6 +233,21 @@ def make_jbu_weights(model_name: str, feat_dim: int, seed: int = 3) -> Dict[str,
     w["fixup_proj.1.weight"] = _normal(seed, "fixup_proj.1.weight", (feat_dim, feat_dim, 1, 1), feat_dim ** -0.5)
     w["fixup_proj.1.bias"] = _normal(seed, "fixup_proj.1.bias", (feat_dim,), 0.05)
     return w
+
+
+def resize_conv_keys():
+    """state_dict() keys of the reference's LayeredResizeConv(dim, 1) (upsamplers.py:178-200)."""
+    return [f"conv{k}.{t}" for k in range(1, 5) for t in ("weight", "bias")]
+
+
+def make_resize_conv_weights(feat_dim: int, seed: int = 3) -> Dict[str, np.ndarray]:
+    """Deterministic LayeredResizeConv weights at nn.Conv2d's default-init scale: U(-1/sqrt(fan_in), 1/sqrt(fan_in)), fan_in = C + 3."""
+    b = 1.0 / np.sqrt(feat_dim + 3)
+    out = {}
+    for k in range(1, 5):
+        out[f"conv{k}.weight"] = _rng(seed, f"conv{k}.weight").uniform(-b, b, (feat_dim, feat_dim + 3, 1, 1)).astype(np.float32)
+        out[f"conv{k}.bias"] = _rng(seed, f"conv{k}.bias").uniform(-b, b, (feat_dim,)).astype(np.float32)
+    return out
 
 
 def make_tiles_u8(num_tiles: int, size: int = 512, seed: int = 1234, smooth: bool = False) -> np.ndarray:

@@ -266,7 +266,7 @@ int sg_similarity_map(const float* patches, int64_t batch_stride, int ld, int B,
 
 /* ---- building-block ops exported for unit parity tests -----------------------------------------
  * C[M,N] = act(A[M,K] . W[N,K]^T + bias) (+ residual); f32 in/out at the boundary, computed in
- * `precision`.  act: 0 none, 1 QuickGELU, 2 erf GELU. */
+ * `precision`.  act: 0 none, 1 QuickGELU, 2 erf GELU, 3 ReLU. */
 int sg_op_linear(const float* A, const float* W, const float* bias, const float* residual, float* C,
                  int M, int N, int K, int act, int precision, void* scratch, size_t scratch_bytes, sg_stream s);
 /* The residual GEMM -> LayerNorm -> GEMM chain of a transformer block (reference open_clip/transformer.py:234-254: x = x + out_proj(attn);
@@ -359,7 +359,7 @@ int  sg_text_set_tensor(sg_text* t, const char* name, const float* dev_f32, int6
 size_t sg_text_workspace_bytes(const sg_text* t, int n_seq);
 int  sg_text_encode(sg_text* t, const int32_t* tokens, int n_seq, float* out, void* workspace, size_t workspace_bytes, sg_stream s);
 
-/* JBU context.  sg_jbu_create replaces get_upsampler(name, dim) (upsamplers.py:353-369; kind 0 = 'jbu_one', 1 = 'jbu_stack');
+/* JBU context.  sg_jbu_create replaces get_upsampler(name, dim) (upsamplers.py:353-369; kind 0 = 'jbu_one', 1 = 'jbu_stack', 2 = 'bilinear');
  * sg_jbu_set_tensor takes the tensors by their state-dict names ("up.range_temp", "up2.fixup_proj.0.weight",
  * "fixup_proj.1.weight" ...), i.e. load_state_dict (segmentor.py:281-283);
  * sg_jbu_upsample replaces self.upsampler(image_features, img) (segmentor.py:371 -> upsamplers.py:278-325):
@@ -369,6 +369,23 @@ int  sg_text_encode(sg_text* t, const int32_t* tokens, int n_seq, float* out, vo
  *   Precision, per kernel against f64 on its own operands (tests/jbu_reference.py): under SG_PREC_F16X2 the low-res convolution stays within
  *   (2u 3 KP + 4u D + 2^-21) M + 2^-25 S_win (u = 2^-24, KP = 160 / 128 K slots, D = 2r + 1, M = sum_t |K_t| sum_s |w_s| |src_s|, S_win the
  *   window's sum |src|), a median of <= 2.1e-4 of |out| in the tests; the two-plane fixup and final GEMMs within gemm_bound's two-plane terms. */
+/* Kind 2 = 'bilinear' (upsamplers.py:343-350, Bilinear: F.interpolate(feats, (GH, GW), mode='bilinear'), align_corners=False) has no
+ * tensors: sg_jbu_set_tensor refuses every name (SG_ERR_INVALID).  sg_jbu_upsample writes the plain resize out [B, GH*GW, C] f32 (the module's
+ * own output, for tests); sg_jbu_logits (every precision, C % 4 == 0, Q <= 32) writes logits [B, Q, GH*GW] without that map: by linearity
+ * out_q(p) = (sum_k w_k y_kq) / sqrt(sum_kl w_k w_l G_kl) + lambda cls_q over the four corners k of p's cell, from y = tokens . T^T and five
+ * Gram terms per token, all in f32 with f32 accumulation whatever the precision argument.  Bound per element against f64 on the same
+ * operands (tests/upsampler_alt_reference.py, u = 2^-24, M = sum_k w_k |f_k|, D2 = |f(p)|^2, A_q = sum_k w_k sum_c |f_kc T_qc|):
+ *   |err| <= (g_C A_q + g_4 sum_k w_k |y_kq|) / sqrt(D2) + |N_q| / sqrt(D2) * (g_C + g_12) M^2 / (2 D2) + 4u |out_q| + |lambda| g_C' S_cls,
+ * g_n = n u / (1 - n u), N_q the numerator, S_cls the CLS logit's own dot bound.  The M^2 / D2 factor is the Gram form's price: neighbours
+ * that nearly cancel (|f(p)| << M) lose digits that interpolate-then-normalise keeps. */
+/* Kind 3 = 'resize_conv' (upsamplers.py:178-200, LayeredResizeConv(dim, 1); feat_dim % 8 == 0): tensors "conv{1..4}.weight" [C, C+3, 1, 1]
+ * and "conv{1..4}.bias" [C]; weights are packed at sg_jbu_set_tensor as [W_src | W_guid | 0] rows of KP = align_up(C + 3, 64).  Four stages of
+ * big = bilinear x2 (source), guid = tile resized to big's size (no antialias), out = act([big | guid] . W^T + b) + big (ReLU on stages 1-3);
+ * sg_jbu_upsample -> out [B, 16gh*16gw, C].  Each stage's 1x1 conv runs on the precision's GEMM (f32; two-plane f16 for SG_PREC_F16X2; bf16
+ * operands otherwise) and is bounded per element as that GEMM (tests/gemm_reference.py terms over K = C + 3); the operand producer's bilinear
+ * blends within 4u of sum |w_k||x_k| (tests/upsampler_alt_reference.py).  sg_jbu_logits refuses this kind (SG_ERR_INVALID): the host runs
+ * sg_jbu_upsample + sg_cosine_logits[_two_plane]. */
+enum { SG_JBU_ONE = 0, SG_JBU_STACK = 1, SG_JBU_BILINEAR = 2, SG_JBU_RESIZE_CONV = 3 };
 typedef struct sg_jbu sg_jbu;
 int  sg_jbu_create(sg_jbu** out, int device, int kind, int feat_dim);
 void sg_jbu_destroy(sg_jbu* j);
