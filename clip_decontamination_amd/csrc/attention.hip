@@ -139,7 +139,7 @@ __device__ __forceinline__ void dma_tile(const bf16_t* row0, uint32_t rows_left,
 // H2: nothing but a name -- the two-plane translation unit instantiates the SAME <DH, TS, GK, MULTI, F16 = true, PV> combinations as the f16 one
 // with different bodies (AH2 is a file-level constant), so it must not share their symbols.
 // DMA: the lean dh-64 body stages K / V by LDS-DMA into the swizzled image above and keeps -m_run resident (launch_attn); false = the
-// register-staged body (every other instantiation, and tuning code 39 for the same-process baseline).
+// register-staged body (every other instantiation, and under TUNE_ATTN_STAGED as the same-process baseline).
 template <int DH, int TS, int GK, bool MULTI, bool F16, bool PV, bool H2 = AH2, bool DMA = false>
 // (two-plane form: twice the fragment registers -- the variants with a bias / two summed terms and every head_dim > 64 get the whole file too)
 __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 || MULTI || DH > 80)) || (AH2 && (DH > 64 || (GK != 0 && TS == 2)))) ? 1 : 2) void attn_kernel(AttnArgs a) {
@@ -579,7 +579,7 @@ __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 ||
   }
 }
 
-// The lean dh-64 kernels of the bf16 / f16 forms run the LDS-DMA body unless tuning code 39 asks for the register-staged one (same-process
+// The lean dh-64 kernels of the bf16 / f16 forms run the LDS-DMA body unless TUNE_ATTN_STAGED asks for the register-staged one (same-process
 // A/B and bit-identity checks against the previous body).
 template <int DH, int TS>
 static int launch_attn(const AttnArgs& a, hipStream_t s) {
@@ -594,7 +594,7 @@ static int launch_attn(const AttnArgs& a, hipStream_t s) {
   using Kern = void (*)(AttnArgs);
   const bool exper = generic && a.bias && a.resoftmax && !a.causal && !a.bias_cn && !a.bias_rn && !multi && a.ctx;
   constexpr bool CAN_DMA = DH == 64 && !AH2;
-  const bool dma = CAN_DMA && !generic && get_gemm_config() != 39;
+  const bool dma = CAN_DMA && !generic && get_gemm_config() != TUNE_ATTN_STAGED;
   const Kern kern = exper ? attn_kernel<DH, TS, 2, false, AF16, true>
                   : a.ctx ? (generic ? (multi ? attn_kernel<DH, TS, 1, CAN_MULTI, AF16, true> : attn_kernel<DH, TS, 1, false, AF16, true>)
                                      : dma ? (multi ? attn_kernel<DH, TS, 0, CAN_MULTI, AF16, true, AH2, CAN_DMA> : attn_kernel<DH, TS, 0, false, AF16, true, AH2, CAN_DMA>)

@@ -459,11 +459,8 @@ extern "C" int sg_quantize_rows_fp8(const float* x, int64_t rows, int D, void* y
   SG_REQUIRE(x && y && scale && rows > 0 && D > 0, "sg_quantize_rows_fp8: bad arguments");
   return quantize_rows_fp8(x, 0, D, (uint8_t*)y, D, scale, rows, D, as_stream(st));
 }
-// Tuning hook for the bf16 GEMM tile configuration (-1 = automatic).
-extern "C" int sg_set_gemm_config(int cfg) {
-  set_gemm_config(cfg);
-  return SG_OK;
-}
+// Tuning hook (-1 = automatic, common.h Tuning for the codes); an unknown code is refused and leaves the setting as it was.
+extern "C" int sg_set_gemm_config(int cfg) { return set_gemm_config(cfg); }
 extern "C" int sg_profile_disable(void) { g_prof.on = false; return SG_OK; }
 // K step in elements (64: gemm_bf16_persist_k64, 32: gemm_bf16_persist) of the calling thread's last persistent bf16 / f16 GEMM launch; 0 = none yet.
 extern "C" int sg_gemm_persist_last_kstep(void) { return gemm_persist_last_kstep(); }
@@ -714,7 +711,7 @@ static int mlp_block(sg_context* c, const LayerW& L, float* x, const Plan& p, in
   const int act = d.quick_gelu ? ACT_QUICK_GELU : ACT_GELU;
   if (c->fp8 && p.x8 && L.w_fc8) {                          // fp8 linears: LN -> e4m3 + row scale; GELU output re-quantised per row
     SG_TRY(layernorm_fp8(x, D, L.ln2_g, L.ln2_b, p.x8, D, p.sx8, R, D, 1e-5f, s));
-    if (R >= 1024 && M % 128 == 0 && D % 256 == 0 && get_gemm_config() != 33) {
+    if (R >= 1024 && M % 128 == 0 && D % 256 == 0) {
       // MXFP8 hand-off: the fc epilogue writes GELU(h) as e4m3 with one power-of-two scale per 32 columns, which the proj GEMM's scaled MFMA
       // consumes directly -- no [R, M] 2-byte intermediate and no separate row-quantisation pass (finer-grained scales than one per row, too)
       SG_TRY(linear_fp8_mx(p.x8, p.sx8, nullptr, D, L.w_fc8, L.s_fc, L.b_fc, nullptr, nullptr, M, false, p.h8, p.hmx, (int)R, M, D, act, s));
@@ -749,10 +746,10 @@ static int std_block(sg_context* c, const LayerW& L, float* x, const Plan& p, in
   const int D = d.width, H = d.heads;
   const int64_t R = (int64_t)B * N;
   AttnBuffers ab{p.scores, p.probs, p.lse, p.lse1, p.omega, p.qnorm, p.knorm};
-  // LayerNorm folding: 2-byte modes, shapes that run on the persistent GEMM; cfg 34 (tuning) switches it off
+  // LayerNorm folding: 2-byte modes, shapes that run on the persistent GEMM; TUNE_LN_PASS switches it off
   // (small launches -- a tile or two per call -- run the residual GEMMs on smaller tiles instead, see gemm_bf16.hip few_tiles)
   const bool fold = c->hk && !c->fp8 && L.folded && p.ln_slice && R < (1ll << 31) && gemm_bf16_ln_fold_ok((int)R, D, D) && D % 256 == 0 &&
-                    gemm_bf16_prefers_persistent((int)R, D) && get_gemm_config() != 34;
+                    gemm_bf16_prefers_persistent((int)R, D) && get_gemm_config() != TUNE_LN_PASS;
   const bool ln1_folded = fold && x16_valid && *x16_valid;
   if (x16_valid) *x16_valid = false;
   if (c->fp8 && p.x8 && L.w_qkv8) {
@@ -879,7 +876,7 @@ extern "C" int sg_vit_forward(sg_context* c, const sg_tile_batch* tiles, const s
     const LayerW& LL = c->layers[L - 1];
     AttnBuffers ab{p.scores, p.probs, p.lse1, p.lse1, p.omega, p.qnorm, p.knorm};
     if (x16 && c->hk && !c->fp8 && LL.folded && p.ln_slice && R < (1ll << 31) && gemm_bf16_ln_fold_ok((int)R, D, D) && D % 256 == 0 &&
-        gemm_bf16_prefers_persistent((int)R, D) && get_gemm_config() != 34) {                                    // block L-2's proj GEMM left x's 2-byte copy and statistics: ln_1 folded here too
+        gemm_bf16_prefers_persistent((int)R, D) && get_gemm_config() != TUNE_LN_PASS) {                                    // block L-2's proj GEMM left x's 2-byte copy and statistics: ln_1 folded here too
       SG_TRY(ln_stats_finalize(p.ln_slice, R, D, 1e-5f, p.ln_rows, s));
       SG_TRY(linear_ln_consumer(c->hk, p.xn, D, LL.w_qkv_f, LL.bf_qkv, LL.c_qkv, p.ln_rows, p.qkv, 3 * D, (int)R, 3 * D, D, ACT_NONE, s));
     } else {

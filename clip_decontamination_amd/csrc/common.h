@@ -280,7 +280,17 @@ const char* gemm_last_kernel();  // "<family> grid=<x> ngroup=<n>" of the callin
 const char* gemm_last_family();  // the static kernel-family name of the calling thread's last gemm_bf16() launch, "none" as above
 bool gemm_bf16_ln_fold_ok(int M, int N, int K);   // the shapes the persistent kernel (home of the folded-LayerNorm epilogues) can run
 bool gemm_bf16_prefers_persistent(int M, int N);  // ... and whether the automatic dispatch would pick it (enough 256 x 256 tiles to fill the chip)
-void set_gemm_config(int c);   // tuning hook (per calling thread): -1 auto, 0 = 128x128x2-stage baseline, 1.. = ring variants
+// Tuning codes of set_gemm_config besides -1 (automatic), 1000 + v (the persistent kernels' tile order) and 2000 + n (their grid cap):
+// each selects one path for an experiment or as a same-process reference.
+enum Tuning {
+  TUNE_FP8_RING = 31,          // fp8 GEMM: the ring kernels on every shape
+  TUNE_FP8_PERSIST = 32,       // fp8 GEMM: the persistent kernel from K = 512 on, not only from K = 2048
+  TUNE_LN_PASS = 34,           // LayerNorm as its own pass (no folding into the GEMMs)
+  TUNE_NO_SMALL_LAUNCH = 36,   // no small-launch dispatch: a few-tile GEMM stays on the persistent kernel
+  TUNE_PERSIST_K32 = 38,       // the persistent bf16 / f16 GEMM on 32-element K steps (same results as the 64-element one)
+  TUNE_ATTN_STAGED = 39,       // the lean dh-64 attention with register-staged K / V instead of LDS-DMA (same results)
+};
+int set_gemm_config(int c);    // tuning hook (per calling thread): -1, a Tuning code, 1000 + v or 2000 + n; anything else is refused
 
 // f32 GEMM (f32 MFMA, exact fmaf chains), fully general strides: A(m,k) at A[m*lda + k];
 // B(k,n) at B[k*sbk + n*sbn]; two-level batch: z -> (z / inner, z % inner).

@@ -3,148 +3,44 @@
 // Reference ops replaced: F.linear inside nn.MultiheadAttention, mlp.c_fc / c_proj
 // (open_clip/transformer.py:204-215,234-254), conv1 as a GEMM (:560), `@ self.proj` (:768-770).
 //
-// Design (gfx950): 128x128x64 block tile, 4 waves (2x2), each wave 64x64 as 4x4 tiles of
-// v_mfma_f32_16x16x32_bf16.  Both operands are K-contiguous, staged HBM->LDS with
-// global_load_lds (16 B/lane, no VGPR round trip) into a lane-linear image whose 16-B chunks are
-// XOR-swizzled on the SOURCE side (chunk ^= (row>>1)&7) so the ds_read_b128 fragment reads of 16
-// different rows hit 16 different bank groups.  The MFMA operands are swapped (W rows feed the
-// A port, activation rows the B port) so every lane ends up owning 4 CONSECUTIVE output columns
-// of one output row: bias / residual / store are 8- or 16-byte vector accesses, no transpose.
-// Double-buffered LDS, one barrier per K tile.
+// The kernels, all gfx950 MFMA with both operands K-contiguous and the MFMA operands swapped (W rows feed the A port, activation
+// rows the B port) so every lane owns 4 CONSECUTIVE output columns of one output row: bias / residual / store are 8- or 16-byte
+// vector accesses, no transpose.
+//   * gemm_persist128 (gemm_bf16_persist_k64 / gemm_fp8_persist / gemm_h2_persist): the persistent 256 x 256 ping-pong on 128-byte K
+//     steps for bf16, f16, fp8 and two-plane f16 -- every large linear.  gemm_bf16_persist is its 32-element-K-step form, kept for
+//     K / 64 < 4 and operand row strides of 2^21 elements or more (the 128-byte kernel's in-tile offsets are 32-bit); tuning code
+//     TUNE_PERSIST_K32 forces it.
+//   * gemm_bf16_pingpong: the non-persistent 256 x 256 ping-pong (two groups of four waves alternating on the matrix pipe) for large
+//     launches the persistent kernel does not take: the scalar epilogue (ragged N / unaligned C) or K / 32 < 4.
+//   * gemm_bf16_ring: a ring of K tiles kept in flight across the barrier; the 128 x 128 tile for small launches and 2-byte residuals,
+//     and the fp8 128 x 128 / 256 x 256 tiles (with the MXFP8 forms).
+// Staging: HBM -> LDS by global_load_lds (16 B per lane, no VGPR round trip) into a lane-linear image of 128-byte rows (64 bf16 / f16,
+// 128 fp8) whose 16-byte chunks are XOR-swizzled on the SOURCE side (chunk ^= (row >> 1) & 7), so the ds_read_b128 fragment reads of
+// 16 different rows hit 16 different bank groups; the 32-element kernel's 64-byte rows use chunk ^= swz32(row).
+// Dispatch of a 2-byte GEMM (gemm_bf16): a 2-byte residual goes to the 128 x 128 ring; the row-dot form, a folded LayerNorm or a large
+// launch (M >= 1024, N >= 512 and not a batch-1 launch of too few 256 x 256 tiles to fill half the CUs) goes to the persistent kernel
+// when the vector epilogue applies and K / 32 >= 4, otherwise to the ping-pong; everything else to the 128 x 128 ring with its
+// compile-time epilogue specialisation.  fp8 (gemm_fp8) and two-plane (gemm_h2) operands have rules of their own, next to them below.
 #include "common.h"
 #include <type_traits>
 
 namespace sg {
 
-constexpr int BM = 128, BN = 128, BK = 64;
-constexpr int TILE_BYTES = BM * BK * 2;          // 16 KiB per operand tile
+constexpr int BK = 64;                                     // K tile of the 128-byte-row kernels, in 2-byte elements
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 
-// Stage a 128 x 64 bf16 tile: 4 passes, each wave-instruction writes 1 KiB = 8 rows x 128 B.
-__device__ __forceinline__ void stage_tile(const bf16_t* __restrict__ P, int64_t ld, int row0, int max_row, int k0,
-                                           char* lds_tile, int wave, int lane) {
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const int slab = p * 4 + wave;                         // 1 KiB slab index (wave-uniform)
-    const int r = slab * 8 + (lane >> 3);
-    const int c = lane & 7;
-    const int g = c ^ ((r >> 1) & 7);                      // source chunk that lives at LDS chunk c
-    int grow = row0 + r;
-    grow = grow < max_row ? grow : max_row;                // clamp: rows past the edge are never stored
-    const bf16_t* src = P + (int64_t)grow * ld + k0 + g * 8;
-    __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)(lds_tile + slab * 1024), 16, 0, 0);
-  }
-}
-
 __device__ __forceinline__ bf16x8 read_frag(const char* lds_tile, int row, int chunk) {
   return *reinterpret_cast<const bf16x8*>(lds_tile + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4));
 }
-
-template <int ACT, bool C_BF16, bool VEC>
-__global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmBf16Args a) {
-  __shared__ __attribute__((aligned(16))) char lds[4 * TILE_BYTES];   // [buf][A|W]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wave_m = wave >> 1, wave_n = wave & 1;
-  const int tiles_n = (a.N + BN - 1) / BN;
-  const int tile_m = blockIdx.x / tiles_n, tile_n = blockIdx.x % tiles_n;
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
-  const int z = blockIdx.y;
-  const bf16_t* A = a.A + (int64_t)z * a.strideA;
-  const bf16_t* W = a.W + (int64_t)z * a.strideW;
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  const int nt = a.K / BK;
-  stage_tile(A, a.lda, m0, a.M - 1, 0, lds, wave, lane);
-  stage_tile(W, a.ldw, n0, a.N - 1, 0, lds + TILE_BYTES, wave, lane);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  int cur = 0;
-  for (int t = 0; t < nt; ++t) {
-    char* bufA = lds + cur * 2 * TILE_BYTES;
-    char* bufW = bufA + TILE_BYTES;
-    if (t + 1 < nt) {
-      char* nA = lds + (cur ^ 1) * 2 * TILE_BYTES;
-      stage_tile(A, a.lda, m0, a.M - 1, (t + 1) * BK, nA, wave, lane);
-      stage_tile(W, a.ldw, n0, a.N - 1, (t + 1) * BK, nA + TILE_BYTES, wave, lane);
-    }
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int chunk = kk * 4 + (lane >> 4);
-      bf16x8 fa[4], fw[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) fa[i] = read_frag(bufA, wave_m * 64 + i * 16 + (lane & 15), chunk);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) fw[j] = read_frag(bufW, wave_n * 64 + j * 16 + (lane & 15), chunk);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[j], fa[i], acc[i][j], 0, 0, 0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    cur ^= 1;
-  }
-
-  // epilogue: lane owns row m = .. + (lane & 15), columns n = .. + (lane >> 4) * 4 + {0..3}
-  const float* res = a.residual ? a.residual + (int64_t)z * a.strideC : nullptr;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int m = m0 + wave_m * 64 + i * 16 + (lane & 15);
-    if (m >= a.M) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = n0 + wave_n * 64 + j * 16 + (lane >> 4) * 4;
-      if (n >= a.N) continue;
-      float v[4] = {acc[i][j][0] * a.alpha, acc[i][j][1] * a.alpha, acc[i][j][2] * a.alpha, acc[i][j][3] * a.alpha};
-      if (VEC) {
-        if (a.bias) {
-          const float4 b = *reinterpret_cast<const float4*>(a.bias + n);
-          v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (ACT == ACT_QUICK_GELU) v[e] = quick_gelu(v[e]);
-          if (ACT == ACT_GELU) v[e] = erf_gelu_fast(v[e]);
-          if (ACT == ACT_RELU) v[e] = fmaxf(v[e], 0.f);
-        }
-        if (res) {
-          const float4 r = *reinterpret_cast<const float4*>(res + (int64_t)m * a.ldr + n);
-          v[0] += r.x; v[1] += r.y; v[2] += r.z; v[3] += r.w;
-        }
-        if (C_BF16) {
-          bf16_t* C = reinterpret_cast<bf16_t*>(a.C) + (int64_t)z * a.strideC + (int64_t)m * a.ldc + n;
-          uint2 o; o.x = pack_bf2(v[0], v[1]); o.y = pack_bf2(v[2], v[3]);
-          *reinterpret_cast<uint2*>(C) = o;
-        } else {
-          float* C = reinterpret_cast<float*>(a.C) + (int64_t)z * a.strideC + (int64_t)m * a.ldc + n;
-          *reinterpret_cast<float4*>(C) = make_float4(v[0], v[1], v[2], v[3]);
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (n + e >= a.N) break;
-          float x = v[e];
-          if (a.bias) x += a.bias[n + e];
-          if (ACT == ACT_QUICK_GELU) x = quick_gelu(x);
-          if (ACT == ACT_GELU) x = erf_gelu_fast(x);
-          if (ACT == ACT_RELU) x = fmaxf(x, 0.f);
-          if (res) x += res[(int64_t)m * a.ldr + n + e];
-          if (C_BF16) reinterpret_cast<bf16_t*>(a.C)[(int64_t)z * a.strideC + (int64_t)m * a.ldc + n + e] = f2bf(x);
-          else reinterpret_cast<float*>(a.C)[(int64_t)z * a.strideC + (int64_t)m * a.ldc + n + e] = x;
-        }
-      }
-    }
-  }
+// 64-byte rows (gemm_bf16_persist): chunk c of row r sits at c ^ swz32(r), so every ds_read_b128 lane group of a 16-row fragment read
+// hits 16 distinct bank slots
+__device__ __forceinline__ int swz32(int r) { return (0 - (r >> 2)) & 3; }
+__device__ __forceinline__ bf16x8 read_frag32(const char* tile, int row, int chunk) {
+  return *reinterpret_cast<const bf16x8*>(tile + row * 64 + ((chunk ^ swz32(row)) << 4));
 }
+template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // ---- coalescing epilogue shared by the ring / ping-pong kernels ----------------------------------------------------------------
 // The MFMA fragment leaves each lane with 4 consecutive columns of one row: stored directly that is 32-byte (bf16) / 64-byte (f32)
@@ -266,19 +162,14 @@ __device__ __forceinline__ void epilogue_store(f32x4 (&acc)[MI][NI], const GemmB
   }
 }
 
-// ---- ring-buffered variant ---------------------------------------------------------------------------------------------
-// Same staging image, fragment reads and swapped-operand MFMAs as above, but (1) the block tile and wave grid are template
-// parameters (256x128 / 256x256 tiles with 8 waves halve the L2 bytes per FLOP), (2) the LDS is a ring of STAGES K-tiles
-// filled by global_load_lds that stay IN FLIGHT across the barrier: a counted `s_waitcnt vmcnt(N)` (never 0 in steady state)
-// retires only the tile about to be read, a raw s_barrier publishes it, and the slot freed by the previous iteration is
-// refilled immediately -- so STAGES-1 tiles of HBM/L2 latency are hidden behind the MFMA phase instead of one.
+// ---- ring kernel ---------------------------------------------------------------------------------------------------------
+// The block tile and wave grid are template parameters (a 256x256 tile with 8 waves halves the L2 bytes per FLOP of 128x128 with 4);
+// each wave owns a TM x TN sub-tile.  A K tile is 128 bytes per row, staged as the swizzled image described at the top of the file.
+// The LDS is a ring of STAGES K tiles filled by global_load_lds that stay IN FLIGHT across the barrier: a counted `s_waitcnt vmcnt(N)`
+// (never 0 in steady state) retires only the tile about to be read, a raw s_barrier publishes it, and the slot freed by the previous
+// iteration is refilled immediately -- so STAGES-1 tiles of HBM/L2 latency are hidden behind the MFMA phase instead of one.
 //   iteration t:  vmcnt((STAGES-2) * G) ; s_barrier ; stage(t + STAGES - 1) ; ds_read + MFMA on slot t % STAGES
 // Slot (t-1) % STAGES is rewritten only after every wave has passed the barrier that follows its last read of it.
-__device__ __forceinline__ int swz32(int r) { return (0 - (r >> 2)) & 3; }
-__device__ __forceinline__ bf16x8 read_frag32(const char* tile, int row, int chunk) {
-  return *reinterpret_cast<const bf16x8*>(tile + row * 64 + ((chunk ^ swz32(row)) << 4));
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // FP8: the operands are OCP e4m3 bytes.  The kernel is handed the SAME byte image as a bf16 matrix of half the width (K tile of
 // 64 'bf16' = 128 fp8 per row), so staging, swizzle and fragment reads are unchanged; the two 16-byte fragment reads of a K tile
@@ -290,14 +181,13 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_
 // 128-byte K tile holds 32 elements as four [8 hi | 8 lo] groups.  The SOURCE-side chunk permutation also de-interleaves the planes: LDS
 // chunks 0-3 of a row are the four hi chunks, 4-7 the four lo chunks -- the fragment reads are then exactly the plain kernel's kk = 0 / 1
 // reads (conflict-free as they stand), and a K tile is ONE k-step of three MFMAs: W_hi.A_hi + W_lo.A_hi + W_hi.A_lo.
-template <int BM_, int BN_, int WM, int WN, int STAGES, int BKT = 64, bool FP8 = false, bool F16 = false, bool MXA = false, int SPEC = 0, bool SPLIT = false>
+template <int BM_, int BN_, int WM, int WN, int STAGES, bool FP8 = false, bool F16 = false, bool MXA = false, int SPEC = 0, bool SPLIT = false>
 __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_ring(GemmBf16Args a, int act, int c_bf16, int vec) {
-  static_assert(!SPLIT || (BKT == 64 && F16 && !FP8 && !MXA), "two-plane f16: 128-byte K tiles on the f16 MFMA");
+  static_assert(!SPLIT || (F16 && !FP8 && !MXA), "two-plane f16: the f16 MFMA");
   constexpr int NW = WM * WN, TM = BM_ / WM, TN = BN_ / WN, MI = TM / 16, NI = TN / 16;
-  constexpr int RPS = BKT == 64 ? 8 : 16;                // rows per 1 KiB slab (row = BKT * 2 bytes)
-  constexpr int SLABS = (BM_ + BN_) / RPS;               // 1 KiB slabs per K tile
+  constexpr int SLABS = (BM_ + BN_) / 8;                 // 1 KiB slabs (8 rows of 128 B) per K tile
   constexpr int G = SLABS / NW + (MXA ? 1 : 0);          // global_load_lds per thread per K tile
-  constexpr int OPER_BYTES = (BM_ + BN_) * BKT * 2;
+  constexpr int OPER_BYTES = (BM_ + BN_) * BK * 2;
   constexpr int STAGE_BYTES = OPER_BYTES + (MXA ? BM_ * 4 : 0);
   static_assert(!MXA || (FP8 && BM_ == 256 && NW >= 4), "MX block scales: fp8 256-row tiles");
   static_assert(SLABS % NW == 0, "slabs must divide over the waves");
@@ -325,15 +215,15 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_ring(GemmBf16Args a
 #pragma unroll
     for (int p = 0; p < G - (MXA ? 1 : 0); ++p) {
       const int slab = p * NW + wave;                      // wave-uniform
-      const int r = slab * RPS + (BKT == 64 ? (lane >> 3) : (lane >> 2));   // row inside the stacked [A rows | W rows] image
-      const int c = BKT == 64 ? (lane & 7) : (lane & 3);
-      const bool is_a = slab * RPS < BM_;
+      const int r = slab * 8 + (lane >> 3);               // row inside the stacked [A rows | W rows] image
+      const int c = lane & 7;
+      const bool is_a = slab * 8 < BM_;
       const int rl = is_a ? r : r - BM_;                   // the swizzle is a function of the row inside its own tile
-      int gch = BKT == 64 ? (c ^ ((rl >> 1) & 7)) : (c ^ swz32(rl));
+      int gch = c ^ ((rl >> 1) & 7);
       if constexpr (SPLIT) gch = ((gch & 3) << 1) | (gch >> 2);   // logical chunk (plane p, group g) = 4 p + g lives at global chunk 2 g + p
       const bf16_t* src;
-      if (is_a) { int gr = m0 + r; gr = gr < a.M ? gr : a.M - 1; src = A + (int64_t)gr * a.lda + t * BKT + gch * 8; }
-      else { int gr = n0 + rl; gr = gr < a.N ? gr : a.N - 1; src = W + (int64_t)gr * a.ldw + t * BKT + gch * 8; }
+      if (is_a) { int gr = m0 + r; gr = gr < a.M ? gr : a.M - 1; src = A + (int64_t)gr * a.lda + t * BK + gch * 8; }
+      else { int gr = n0 + rl; gr = gr < a.N ? gr : a.N - 1; src = W + (int64_t)gr * a.ldw + t * BK + gch * 8; }
       __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)(base + slab * 1024), 16, 0, 0);
     }
   };
@@ -344,7 +234,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_ring(GemmBf16Args a
 #pragma unroll
     for (int j = 0; j < NI; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  const int nt = a.K / BKT;
+  const int nt = a.K / BK;
 #pragma unroll
   for (int sidx = 0; sidx < STAGES - 1; ++sidx)
     if (sidx < nt) stage(sidx, sidx);
@@ -358,9 +248,8 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_ring(GemmBf16Args a
     asm volatile("" ::: "memory");
     if (t + STAGES - 1 < nt) stage(t + STAGES - 1, (t + STAGES - 1) % STAGES);
     const char* bufA = lds + (t % STAGES) * STAGE_BYTES;
-    const char* bufW = bufA + BM_ * BKT * 2;
+    const char* bufW = bufA + BM_ * BK * 2;
     if constexpr (FP8) {
-      static_assert(!FP8 || BKT == 64, "fp8 uses the 128-byte K tile");
       typedef __attribute__((ext_vector_type(8))) int i32x8;
       union Op { bf16x8 h[2]; i32x8 v; };
       Op fa8[MI], fw8[NI];
@@ -416,15 +305,13 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_ring(GemmBf16Args a
       continue;
     }
 #pragma unroll
-    for (int kk = 0; kk < BKT / 32; ++kk) {
+    for (int kk = 0; kk < 2; ++kk) {
       const int chunk = kk * 4 + (lane >> 4);
       bf16x8 fa[MI], fw[NI];
 #pragma unroll
-      for (int i = 0; i < MI; ++i)
-        fa[i] = BKT == 64 ? read_frag(bufA, wave_m * TM + i * 16 + (lane & 15), chunk) : read_frag32(bufA, wave_m * TM + i * 16 + (lane & 15), chunk);
+      for (int i = 0; i < MI; ++i) fa[i] = read_frag(bufA, wave_m * TM + i * 16 + (lane & 15), chunk);
 #pragma unroll
-      for (int j = 0; j < NI; ++j)
-        fw[j] = BKT == 64 ? read_frag(bufW, wave_n * TN + j * 16 + (lane & 15), chunk) : read_frag32(bufW, wave_n * TN + j * 16 + (lane & 15), chunk);
+      for (int j = 0; j < NI; ++j) fw[j] = read_frag(bufW, wave_n * TN + j * 16 + (lane & 15), chunk);
 #pragma unroll
       for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -509,7 +396,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_ring(GemmBf16Args a
 //     MFMA  : 16 x v_mfma_f32_16x16x32_bf16
 // Group 1 runs ONE barrier behind group 0, so on every SIMD one wave is in its MFMA segment while its partner reads:
 // the matrix pipe never waits for LDS latency and the LDS/TA never wait for the MFMAs.
-// LDS: 2 buffers x [A 256x64 | W 256x64] bf16 = 128 KiB, same swizzled image as above.  Hand-off rules (slot = barrier interval;
+// LDS: 2 buffers x [A 256x64 | W 256x64] bf16 = 128 KiB, the swizzled image described at the top of the file.  Hand-off rules (slot = barrier interval;
 // group 0's READ(t,p) is slot 8t+2p, group 1's is 8t+2p+1):
 //   * who loads what for tile t+1: wave (g,i) loads A rows [128g+32i,+32) in READ(t,0) and W rows [64i+32g,+32) in READ(t,1).
 //     WAR: those A rows were last read by group g in READ(t-1,2) (>= 4 slots earlier); those W rows in READ(t-1,3) of either
@@ -720,149 +607,15 @@ static int launch_pingpong(const GemmBf16Args& a, int vec, hipStream_t s) {
   return SG_OK;
 }
 
-// ---- ping-pong, K tile 32, FOUR-deep LDS ring ---------------------------------------------------------------------------------
-// Same two-group alternation as gemm_bf16_pingpong, but a K tile is 32 deep (2 phases x 16 MFMAs) and the 128 KiB of LDS hold a
-// ring of 4 tiles, so the loads of tile t+3 are issued while tile t computes: three tiles (~3000 cycles) of HBM / fabric latency
-// are covered instead of one, with only 2 global_load_lds per wave per phase (their issue cost stays inside a 256-cycle segment).
-// LDS image per tile: [A 256 rows x 64 B | W 256 rows x 64 B]; 16-byte chunk c of row r sits at position c ^ swz(r),
-// swz(r) = (-(r >> 2)) & 3, which makes every ds_read_b128 lane group of a 16-row fragment read hit 16 distinct bank slots.
-// Slot = barrier interval; group 0: READ(t,0) = 4t, MFMA(t,0) = 4t+1, READ(t,1) = 4t+2, MFMA(t,1) = 4t+3; group 1 one later.
-//   loads : wave (g,i) issues for tile t+3   A rows [128g+32i,+32) in READ(t,0),   W rows [64i+32g,+32) in READ(t,1)
-//   WAR   : ring slot (t+3)&3 was last read for tile t-1: A-half g by group g in READ(t-1,1) (slot 4t-2+g, retired when the
-//           next segment opens), W rows in READ(t-1,0) (slots 4t-4 / 4t-3); the writes are issued at slots >= 4t+g / 4t+2+g.
-//   RAW   : each wave retires its own pieces of tile t+1 with a COUNTED vmcnt (tiles t+2, t+3 stay in flight) just before
-//           the barrier that closes slot 4t+3 (group 0: after MFMA(t,1); group 1: after READ(t,1)); tile t+1 is first read
-//           in slot 4t+4.
-
-__global__ __launch_bounds__(512) void gemm_bf16_pp32(GemmBf16Args a, int act, int c_bf16, int vec) {
-  constexpr int PBM = 256, PBN = 256, KT32 = 32;
-  constexpr int TILE_B = (PBM + PBN) * KT32 * 2;             // 32 KiB per ring slot
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int g = wave >> 2, wi = wave & 3;
-  const int tiles_n = (a.N + PBN - 1) / PBN, tiles_m = (a.M + PBM - 1) / PBM;
-  const int nwg = tiles_m * tiles_n;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
-  const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + seq;
-  const int m0 = (tile / tiles_n) * PBM, n0 = (tile % tiles_n) * PBN;
-  const int z = blockIdx.y;
-  const bf16_t* A = a.A + (int64_t)z * a.strideA;
-  const bf16_t* W = a.W + (int64_t)z * a.strideW;
-  const int nt = a.K / KT32;
-
-  // this lane's source rows: 2 A slabs and 2 W slabs (16 rows x 64 B each) per K tile
-  const int srow = lane >> 2, cpos = lane & 3;
-  const bf16_t* a_src[2]; const bf16_t* w_src[2]; int a_dst[2], w_dst[2];
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const int ra = 128 * g + 32 * wi + 16 * p + srow;
-    const int rw = 64 * wi + 32 * g + 16 * p + srow;
-    int gra = m0 + ra; gra = gra < a.M ? gra : a.M - 1;
-    int grw = n0 + rw; grw = grw < a.N ? grw : a.N - 1;
-    a_src[p] = A + (int64_t)gra * a.lda + ((cpos ^ swz32(ra)) << 3);
-    w_src[p] = W + (int64_t)grw * a.ldw + ((cpos ^ swz32(rw)) << 3);
-    a_dst[p] = (128 * g + 32 * wi + 16 * p) * 64;
-    w_dst[p] = PBM * KT32 * 2 + (64 * wi + 32 * g + 16 * p) * 64;
-  }
-  auto load_a = [&](int t) {
-    char* base = lds + (t & 3) * TILE_B;
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(a_src[p] + t * KT32), (lds_ptr_t)(base + a_dst[p]), 16, 0, 0);
-  };
-  auto load_w = [&](int t) {
-    char* base = lds + (t & 3) * TILE_B;
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(w_src[p] + t * KT32), (lds_ptr_t)(base + w_dst[p]), 16, 0, 0);
-  };
-
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  bf16x8 fa[4], fw[4];
-
-#define SG_P32_SYNC()                                \
-  do {                                               \
-    __builtin_amdgcn_sched_barrier(0);               \
-    __builtin_amdgcn_s_barrier();                    \
-    __builtin_amdgcn_sched_barrier(0);               \
-  } while (0)
-#define SG_P32_MFMA(MH)                                                                                  \
-  do {                                                                                                   \
-    __builtin_amdgcn_s_setprio(1);                                                                       \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                        \
-      _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                      \
-        acc[4 * (MH) + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[j], fa[i], acc[4 * (MH) + i][j], 0, 0, 0); \
-    __builtin_amdgcn_s_setprio(0);                                                                       \
-  } while (0)
-#define SG_P32_WAIT(T)                                                                                   \
-  do {                                                                                                   \
-    const int beyond = nt - 2 - (T);                                                                     \
-    if (beyond >= 2) wait_vmcnt<8>(); else if (beyond == 1) wait_vmcnt<4>(); else wait_vmcnt<0>();       \
-  } while (0)
-
-  // prologue: tiles 0..2 in flight, tile 0 retired; then the one-barrier stagger of group 1
-#pragma unroll
-  for (int t = 0; t < 3; ++t)
-    if (t < nt) { load_a(t); load_w(t); }
-  SG_P32_WAIT(-1);
-  SG_P32_SYNC();
-  if (g == 1) SG_P32_SYNC();
-
-  for (int t = 0; t < nt; ++t) {
-    const char* tA = lds + (t & 3) * TILE_B;
-    const char* tW = tA + PBM * KT32 * 2;
-    const bool more = t + 3 < nt;
-    // phase 0: rows 0-63 of the group's half x the wave's 64 columns
-#pragma unroll
-    for (int j = 0; j < 4; ++j) fw[j] = read_frag32(tW, 64 * wi + 16 * j + (lane & 15), lane >> 4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) fa[i] = read_frag32(tA, 128 * g + 16 * i + (lane & 15), lane >> 4);
-    if (more) load_a(t + 3);
-    SG_P32_SYNC();
-    SG_P32_MFMA(0);
-    SG_P32_SYNC();
-    // phase 1: rows 64-127
-#pragma unroll
-    for (int i = 0; i < 4; ++i) fa[i] = read_frag32(tA, 128 * g + 64 + 16 * i + (lane & 15), lane >> 4);
-    if (more) load_w(t + 3);
-    if (g == 1) SG_P32_WAIT(t);
-    SG_P32_SYNC();
-    SG_P32_MFMA(1);
-    if (g == 0) SG_P32_WAIT(t);
-    SG_P32_SYNC();
-  }
-  if (g == 0) SG_P32_SYNC();
-#undef SG_P32_SYNC
-#undef SG_P32_MFMA
-#undef SG_P32_WAIT
-
-  __syncthreads();
-  epilogue_store<8, 4>(acc, a, act, c_bf16, z, m0 + 128 * g, n0 + 64 * wi, reinterpret_cast<float*>(lds) + wave * 16 * 68, lane);
-}
-
-static int launch_pp32(const GemmBf16Args& a, hipStream_t s) {
-  const size_t lds = 4 * (256 + 256) * 32 * 2;
-  auto kern = gemm_bf16_pp32;
-  SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
-  const int64_t tiles = cdiv(a.M, 256) * cdiv(a.N, 256);
-  SG_REQUIRE(tiles < (1ll << 31) && a.batch < 65536, "gemm_bf16: grid too large");
-  hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)a.batch), dim3(512), lds, s, a, a.act, a.c_is_bf16, 1);
-  note_launch("pp32", tiles);
-  return SG_OK;
-}
-
-static thread_local int g_gemm_config = -1;                // -1 = pick per shape (tuning override, per calling thread)
+static thread_local int g_gemm_config = -1;                // -1 = pick per shape, or a Tuning code (common.h; per calling thread)
 int get_gemm_config() { return g_gemm_config; }
 static thread_local int g_persist_grid_cap = 0;             // tuning (sg_set_gemm_config(2000 + n)): at most n workgroups for every persistent kernel (0 = one per CU)
 static thread_local int g_gemm_order = -1;                 // tuning (sg_set_gemm_config(1000 + v)): -1 automatic N-group size, 0 raster order, v > 0 forced N-group size
-// ---- persistent ping-pong: the production kernel for the large ViT linears ---------------------------------------------------------
-// gemm_bf16_pp32's ring (K tile 32, four slots) with three changes measured to matter:
+// ---- persistent ping-pong on 32-element K steps (gemm_bf16_persist) ---------------------------------------------------------------
+// gemm_bf16_pingpong's two-group alternation on a ring of four 32-element K tiles (a slot = [A 256 rows x 64 B | W 256 rows x 64 B],
+// chunk c of row r at c ^ swz32(r)), with three changes measured to matter:
 //   * ONE phase of 32 MFMAs per K tile (12 ds_read_b128 + 4 global_load_lds per wave per READ segment): the barrier + LDS-latency
-//     overhead of a READ segment is amortised over a 512-cycle MFMA segment instead of 256;
+//     overhead of a READ segment is amortised over a 512-cycle MFMA segment instead of 256 (two phases of 16);
 //   * PERSISTENT workgroups (grid = #CUs): the K-tile stream runs straight across output tiles, so the loads of the next
 //     tile's first K tiles are already in flight while the current tile's epilogue drains -- no exposed prologue per tile;
 //   * asymmetric issue so every piece gets >= 3 slots of flight:   group 0 READ(s): W(s+2), A(s+3)    group 1 READ(s): A(s+3), W(s+3)
@@ -1596,7 +1349,7 @@ static thread_local int g_persist_kstep = 0;              // K step of the calli
 int gemm_persist_last_kstep() { return g_persist_kstep; }
 static int launch_persist(const GemmBf16Args& a, hipStream_t s) {
   const bool two_byte = !a.fp8 && !a.h2;
-  const bool k64 = !two_byte || (g_gemm_config != 38 && a.K % 64 == 0 && a.K / 64 >= 4 && a.lda < (1 << 21) && a.ldw < (1 << 21));
+  const bool k64 = !two_byte || (g_gemm_config != TUNE_PERSIST_K32 && a.K % 64 == 0 && a.K / 64 >= 4 && a.lda < (1 << 21) && a.ldw < (1 << 21));
   const size_t lds = k64 ? 5 * 256 * 128 : 4 * (256 + 256) * 32 * 2;   // 160 KiB (A ring 2 + W ring 3 slots) / 128 KiB (4 slots)
   // instantiation: epilogue form (plain / folded-LayerNorm consumer / producer) x compile-time specialisation of the hot combinations
   PersistKern kern;
@@ -1648,46 +1401,46 @@ static int launch_persist(const GemmBf16Args& a, hipStream_t s) {
 }
 
 // A launch whose 256 x 256 tiles would not even fill half the CUs (one or two image tiles per call: the reference's own tile-by-tile loop)
-// runs on the 128 x 128 ring kernel instead -- four times the workgroups, measured 1.4-2x faster there; tuning code 36 switches this off.
+// runs on the 128 x 128 ring kernel instead -- four times the workgroups, measured 1.4-2x faster there; TUNE_NO_SMALL_LAUNCH switches this off.
 static bool few_tiles(int M, int N) {
-  return g_gemm_config != 36 && (int64_t)cdiv(M, 256) * cdiv(N, 256) * 2 < device_cu_count();
+  return g_gemm_config != TUNE_NO_SMALL_LAUNCH && (int64_t)cdiv(M, 256) * cdiv(N, 256) * 2 < device_cu_count();
 }
 bool gemm_bf16_ln_fold_ok(int M, int N, int K) { return M >= 1024 && N >= 512 && N % 64 == 0 && K % 32 == 0 && K / 32 >= 4; }
 bool gemm_bf16_prefers_persistent(int M, int N) { return M >= 1024 && N >= 512 && !few_tiles(M, N); }
-void set_gemm_config(int c) {
-  if (c >= 2000) { g_persist_grid_cap = c - 2000; return; } // experiment / tests: fewer persistent workgroups than CUs, every persistent kernel (2000 = no cap)
-  if (c >= 1000) { g_gemm_order = c - 1001; return; }      // 1000 -> -1 (automatic), 1001 -> 0 (raster), 1001 + v -> N-group size v
-  g_gemm_config = c;
+int set_gemm_config(int c) {
+  if (c >= 2000) { g_persist_grid_cap = c - 2000; return SG_OK; } // experiment / tests: fewer persistent workgroups than CUs, every persistent kernel (2000 = no cap)
+  if (c >= 1000) { g_gemm_order = c - 1001; return SG_OK; }      // 1000 -> -1 (automatic), 1001 -> 0 (raster), 1001 + v -> N-group size v
+  switch (c) {
+    case -1: case TUNE_FP8_RING: case TUNE_FP8_PERSIST: case TUNE_LN_PASS: case TUNE_NO_SMALL_LAUNCH: case TUNE_PERSIST_K32: case TUNE_ATTN_STAGED:
+      g_gemm_config = c;
+      return SG_OK;
+  }
+  return fail(SG_ERR_INVALID, "sg_set_gemm_config: unknown tuning code %d", c);
 }
 
-
-// kernel-family name of a ring configuration (sg_gemm_last_kernel); ring128 is the default small-launch tile, the others are tuning codes
-template <int BM_, int BN_, int STAGES, int BKT, bool FP8, bool SPLIT>
+// kernel-family name of a ring configuration (sg_gemm_last_kernel): the 2-byte ring runs the 128 x 128 tile only
+template <int BM_, int BN_, bool FP8, bool SPLIT>
 constexpr const char* ring_name() {
+  static_assert(FP8 || (BM_ == 128 && BN_ == 128), "2-byte ring kernels: 128 x 128 tiles");
   if (FP8) return BM_ == 128 ? "fp8_ring128" : "fp8_ring256x256";
-  if (SPLIT) return "h2_ring128";
-  if (BKT == 32) return BM_ == 128 ? "ring128x256_k32" : "ring256x128_k32";
-  if (BM_ == 128 && BN_ == 128) return STAGES == 2 ? "ring128" : "ring128x128_s3";
-  if (BM_ == 256 && BN_ == 128) return STAGES == 2 ? "ring256x128" : "ring256x128_s3";
-  if (BM_ == 128 && BN_ == 256) return "ring128x256_s3";
-  return "ring256x256";
+  return SPLIT ? "h2_ring128" : "ring128";
 }
-template <int BM_, int BN_, int WM, int WN, int STAGES, int BKT = 64, bool FP8 = false, bool F16 = false, bool MXA = false, int SPEC = 0, bool SPLIT = false>
+template <int BM_, int BN_, int WM, int WN, int STAGES, bool FP8 = false, bool F16 = false, bool MXA = false, int SPEC = 0, bool SPLIT = false>
 static int launch_ring(const GemmBf16Args& a, int vec, hipStream_t s) {
-  auto kern = gemm_bf16_ring<BM_, BN_, WM, WN, STAGES, BKT, FP8, F16, MXA, SPEC, SPLIT>;
-  const size_t lds = (size_t)STAGES * ((BM_ + BN_) * BKT * 2 + (MXA ? BM_ * 4 : 0));
+  auto kern = gemm_bf16_ring<BM_, BN_, WM, WN, STAGES, FP8, F16, MXA, SPEC, SPLIT>;
+  const size_t lds = (size_t)STAGES * ((BM_ + BN_) * BK * 2 + (MXA ? BM_ * 4 : 0));
   if (lds > 48 * 1024) SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
   const int64_t tiles = cdiv(a.M, BM_) * cdiv(a.N, BN_);
   SG_REQUIRE(tiles < (1ll << 31) && a.batch < 65536, "gemm_bf16: grid too large");
   hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)a.batch), dim3(WM * WN * 64), lds, s, a, a.act, a.c_is_bf16, vec);
-  note_launch(FP8 && (a.a_mx || a.c_mx) ? "fp8_mx_ring256x256" : ring_name<BM_, BN_, STAGES, BKT, FP8, SPLIT>(), tiles);
+  note_launch(FP8 && (a.a_mx || a.c_mx) ? "fp8_mx_ring256x256" : ring_name<BM_, BN_, FP8, SPLIT>(), tiles);
   return SG_OK;
 }
 
-template <int ACT, bool C_BF16>
-static void launch(const GemmBf16Args& a, bool vec, dim3 grid, hipStream_t s) {
-  if (vec) hipLaunchKernelGGL((gemm_bf16_kernel<ACT, C_BF16, true>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((gemm_bf16_kernel<ACT, C_BF16, false>), grid, dim3(256), 0, s, a);
+// the 128 x 128 ring of the 2-byte GEMM: small launches and 2-byte residuals; SPEC (epilogue_store) fixes the hot epilogue forms
+template <int SPEC>
+static int launch_ring128(const GemmBf16Args& a, int vec, hipStream_t s) {
+  return a.f16 ? launch_ring<128, 128, 2, 2, 2, false, true, false, SPEC>(a, vec, s) : launch_ring<128, 128, 2, 2, 2, false, false, false, SPEC>(a, vec, s);
 }
 
 static int gemm_fp8(const GemmBf16Args& a, hipStream_t s) {
@@ -1704,7 +1457,7 @@ static int gemm_fp8(const GemmBf16Args& a, hipStream_t s) {
   h.K = a.K / 2; h.lda = a.lda / 2; h.ldw = a.ldw / 2; h.strideA = a.strideA / 2; h.strideW = a.strideW / 2;
   prof_begin(PROF_GEMM_FP8, 2.0 * a.M * (double)a.N * a.K * a.batch, s);
   // 256 x 256 x 128 B, two stages (1.47 / 1.32 / 1.64 PFLOP/s on the QKV / fc / proj shapes; the 256 x 128 three-stage tile 1.31 / 1.04 / 1.45)
-  // large shapes: the persistent ping-pong kernel (byte strides, original K); cfg 31 (tuning) forces the two-stage ring kernel instead
+  // large shapes: the persistent ping-pong kernel (byte strides, original K); TUNE_FP8_RING forces the two-stage ring kernel instead
   // measured (tools/bench_gemm_fp8.py, R = 175 360): proj (K 4096) 1.76 vs 1.65 PFLOP/s for the persistent kernel; QKV / fc (K 1024: 8 K steps
   // per tile, the tile switch weighs twice what it does in bf16) 1.25 / 1.23 vs 1.51 / 1.31 for the ring kernel -> persistent for long K only
   const bool mx = a.a_mx != nullptr || a.c_mx != nullptr;
@@ -1713,22 +1466,22 @@ static int gemm_fp8(const GemmBf16Args& a, hipStream_t s) {
     // the tower's MLP hand-off runs on compile-time-specialised epilogues: fc -> MX output after the activation, proj <- MX operand, f32 + residual
     const bool proj_form = a.a_mx && !a.c_mx && !a.c_is_bf16 && a.residual && a.act == ACT_NONE;
     const bool fc_form = !a.a_mx && a.c_mx && (a.act == ACT_QUICK_GELU || a.act == ACT_GELU);
-    const int rcm = proj_form ? launch_ring<256, 256, 2, 4, 2, 64, true, false, true, 4>(h, vec, s)
-                  : a.a_mx ? launch_ring<256, 256, 2, 4, 2, 64, true, false, true>(h, vec, s)
-                  : fc_form ? (a.act == ACT_QUICK_GELU ? launch_ring<256, 256, 2, 4, 2, 64, true, false, false, 2>(h, vec, s)
-                                                       : launch_ring<256, 256, 2, 4, 2, 64, true, false, false, 3>(h, vec, s))
-                            : launch_ring<256, 256, 2, 4, 2, 64, true>(h, vec, s);
+    const int rcm = proj_form ? launch_ring<256, 256, 2, 4, 2, true, false, true, 4>(h, vec, s)
+                  : a.a_mx ? launch_ring<256, 256, 2, 4, 2, true, false, true>(h, vec, s)
+                  : fc_form ? (a.act == ACT_QUICK_GELU ? launch_ring<256, 256, 2, 4, 2, true, false, false, 2>(h, vec, s)
+                                                       : launch_ring<256, 256, 2, 4, 2, true, false, false, 3>(h, vec, s))
+                            : launch_ring<256, 256, 2, 4, 2, true>(h, vec, s);
     prof_end(PROF_GEMM_FP8, s);
     if (rcm != SG_OK) return rcm;
     SG_LAUNCH_CHECK();
     return SG_OK;
   }
-  const bool persist = vec && a.batch == 1 && a.M >= 1024 && a.N >= 512 && (a.K >= 2048 || g_gemm_config == 32) && a.K >= 512 && g_gemm_config != 31 &&
+  const bool persist = vec && a.batch == 1 && a.M >= 1024 && a.N >= 512 && (a.K >= 2048 || g_gemm_config == TUNE_FP8_PERSIST) && a.K >= 512 && g_gemm_config != TUNE_FP8_RING &&
                        (int64_t)a.M * a.lda < (1ll << 31) && (int64_t)a.N * a.ldw < (1ll << 31);     // 32-bit byte offsets inside the kernel
   const int rc = persist ? launch_persist(a, s)
-               : (a.M >= 1024 && a.N >= 256) ? ((vec && a.c_is_bf16 && !a.residual && a.act == ACT_NONE) ? launch_ring<256, 256, 2, 4, 2, 64, true, false, false, 1>(h, vec, s)
-                                                                                                      : launch_ring<256, 256, 2, 4, 2, 64, true>(h, vec, s))
-                                             : launch_ring<128, 128, 2, 2, 3, 64, true>(h, vec, s);
+               : (a.M >= 1024 && a.N >= 256) ? ((vec && a.c_is_bf16 && !a.residual && a.act == ACT_NONE) ? launch_ring<256, 256, 2, 4, 2, true, false, false, 1>(h, vec, s)
+                                                                                                      : launch_ring<256, 256, 2, 4, 2, true>(h, vec, s))
+                                             : launch_ring<128, 128, 2, 2, 3, true>(h, vec, s);
   prof_end(PROF_GEMM_FP8, s);
   if (rc != SG_OK) return rc;
   SG_LAUNCH_CHECK();
@@ -1750,8 +1503,7 @@ static int gemm_h2(const GemmBf16Args& a, hipStream_t s) {
   GemmBf16Args h = a;
   h.K = a.K * 2; h.lda = a.lda * 2; h.ldw = a.ldw * 2; h.strideA = a.strideA * 2; h.strideW = a.strideW * 2; h.f16 = 1;
   const bool big = a.M >= 1024 && a.N >= 512 && !(few_tiles(a.M, a.N) && a.batch == 1);
-  // the persistent kernel: batch 1, the vector epilogue, >= 4 K steps per tile (its look-ahead is 3), tile-relative 32-bit offsets;
-  // tuning code 37 keeps the plain ping-pong kernel (A/B measurements)
+  // the persistent kernel: batch 1, the vector epilogue, >= 4 K steps per tile (its look-ahead is 3), tile-relative 32-bit offsets
   const bool hot_form = (a.c_is_bf16 && !a.residual) || (!a.c_is_bf16 && a.residual && a.act == ACT_NONE);   // the forms with a compile-time epilogue (the run-time one spills)
   const bool fits = a.batch == 1 && a.K >= 128 && a.lda * 4 < (1 << 23) && a.ldw * 4 < (1 << 23);
   const bool ln_fold = a.copy16 != nullptr || a.ln_stats != nullptr;   // folded LayerNorm (round 3): the persistent kernel's own epilogue forms, as in the 2-byte modes
@@ -1762,9 +1514,9 @@ static int gemm_h2(const GemmBf16Args& a, hipStream_t s) {
     if (a.ln_stats) SG_REQUIRE(a.ln_c && a.alpha == 1.f && a.c_is_bf16 && !a.residual && ((((uintptr_t)a.ln_c) & 15) == 0) && ((((uintptr_t)a.ln_stats) & 7) == 0),
                                "gemm_h2: ln_stats needs ln_c, alpha 1 and a two-plane C");
   }
-  const bool persist = ln_fold || (big && vec && hot_form && fits && g_gemm_config != 37);
+  const bool persist = ln_fold || (big && vec && hot_form && fits);
   prof_begin(PROF_GEMM_H2, 2.0 * a.M * (double)a.N * a.K * a.batch, s);
-  const int rc = persist ? launch_persist(h, s) : big ? launch_pingpong(h, vec, s) : launch_ring<128, 128, 2, 2, 2, 64, false, true, false, 0, true>(h, vec, s);
+  const int rc = persist ? launch_persist(h, s) : big ? launch_pingpong(h, vec, s) : launch_ring<128, 128, 2, 2, 2, false, true, false, 0, true>(h, vec, s);
   prof_end(PROF_GEMM_H2, s);
   if (rc != SG_OK) return rc;
   SG_LAUNCH_CHECK();
@@ -1780,11 +1532,9 @@ int gemm_bf16(const GemmBf16Args& a, hipStream_t s) {
   SG_REQUIRE(a.lda % 8 == 0 && a.ldw % 8 == 0 && a.strideA % 8 == 0 && a.strideW % 8 == 0,
              "gemm_bf16: operand strides must be multiples of 8 elements (16-byte chunks)");
   SG_REQUIRE((((uintptr_t)a.A) & 15) == 0 && (((uintptr_t)a.W) & 15) == 0, "gemm_bf16: operands must be 16-byte aligned");
-  const int csz = a.c_is_bf16 ? 2 : 4;
   bool vec = (a.N % 8 == 0) && (a.ldc % 8 == 0) && (a.strideC % 8 == 0) && ((((uintptr_t)a.C) & 15) == 0);
   if (a.bias) vec = vec && ((((uintptr_t)a.bias) & 15) == 0);
   if (a.residual) vec = vec && (a.ldr % 4 == 0) && ((((uintptr_t)a.residual) & 15) == 0);
-  (void)csz;
   SG_REQUIRE(a.act >= 0 && a.act <= 3, "gemm_bf16: bad act %d", a.act);
   if (a.rowdot)
     SG_REQUIRE(vec && a.residual && !a.c_is_bf16 && a.batch == 1 && a.M >= 1024 && a.N >= 512 && a.N % 64 == 0 && a.K / 32 >= 4,
@@ -1795,65 +1545,25 @@ int gemm_bf16(const GemmBf16Args& a, hipStream_t s) {
     if (a.copy16) SG_REQUIRE(a.row_stats && !a.c_is_bf16 && !a.rowdot && a.N % 64 == 0 && a.ld16 % 4 == 0 && ((((uintptr_t)a.copy16) & 7) == 0), "gemm_bf16: copy16 needs row_stats, an f32 C and N %% 64 == 0");
     if (a.ln_stats) SG_REQUIRE(a.ln_c && a.alpha == 1.f && a.c_is_bf16 && !a.residual && !a.rowdot && ((((uintptr_t)a.ln_c) & 15) == 0) && ((((uintptr_t)a.ln_stats) & 7) == 0), "gemm_bf16: ln_stats needs ln_c and alpha 1");
   }
-  int cfg = g_gemm_config;
-  if (cfg == 33 || cfg == 34 || cfg == 36 || cfg == 37 || cfg == 38 || cfg == 39) cfg = -1;   // tuning codes read by capi.hip (MX hand-off / LayerNorm
-                                                                                  // folding off), by launch_persist (38: the 32-element K step) or by
-                                                                                  // the attention (39: register-staged lean body), not tile configurations
-  if (a.rowdot || ln_fold) cfg = 30;
-  if (a.res_half) {                                          // 2-byte residual: the small-tile kernel's run-time epilogue only
+  if (a.res_half)                                            // 2-byte residual: the small-tile kernel's run-time epilogue only
     SG_REQUIRE(vec && a.residual && a.c_is_bf16 && !a.rowdot && !ln_fold && a.ldr % 8 == 0, "gemm_bf16: res_half needs a 2-byte C, N %% 8 == 0 and ldr %% 8 == 0");
-    cfg = 4;
+  // large: the persistent ping-pong (the plain one without the vector epilogue or below 4 K steps); small: 128 x 128 tiles (more workgroups)
+  const bool big = !a.res_half && (a.rowdot || ln_fold || (a.M >= 1024 && a.N >= 512 && !(few_tiles(a.M, a.N) && a.batch == 1)));
+  const bool persist = big && vec && a.K / 32 >= 4;
+  const int pcat = persist ? (a.ln_stats ? PROF_GEMM_PERSIST_LN_CONSUMER : a.copy16 ? PROF_GEMM_PERSIST_LN_PRODUCER : PROF_GEMM_PERSIST) : PROF_GEMM_BF16;
+  prof_begin(pcat, 2.0 * a.M * (double)a.N * a.K * a.batch, s);
+  int rc;
+  if (big) {
+    rc = persist ? launch_persist(a, s) : launch_pingpong(a, vec, s);
+  } else {
+    const int sp = !vec || a.c_mx || a.row_scale || a.col_scale ? 0
+                 : (a.c_is_bf16 && !a.residual) ? (a.act == ACT_NONE ? 1 : a.act == ACT_QUICK_GELU ? 6 : 7)
+                 : (!a.c_is_bf16 && a.residual && a.act == ACT_NONE) ? 4 : 0;
+    rc = sp == 1 ? launch_ring128<1>(a, vec, s) : sp == 4 ? launch_ring128<4>(a, vec, s) : sp == 6 ? launch_ring128<6>(a, vec, s)
+       : sp == 7 ? launch_ring128<7>(a, vec, s) : launch_ring128<0>(a, vec, s);
   }
-  if (!a.res_half && (cfg < 0 || a.f16)) cfg = (a.rowdot || ln_fold || (a.M >= 1024 && a.N >= 512 && !(few_tiles(a.M, a.N) && a.batch == 1))) ? 30 : 4;  // large: persistent ping-pong; small: 128x128 tiles (more workgroups); f16 operands: these two only
-  if (cfg > 0) {
-    const int pcat = (cfg == 30 && vec && a.K / 32 >= 4) ? (a.ln_stats ? PROF_GEMM_PERSIST_LN_CONSUMER : a.copy16 ? PROF_GEMM_PERSIST_LN_PRODUCER : PROF_GEMM_PERSIST)
-                                                         : PROF_GEMM_BF16;
-    prof_begin(pcat, 2.0 * a.M * (double)a.N * a.K * a.batch, s);
-    int rc;
-    switch (cfg) {
-      case 1: rc = launch_ring<128, 128, 2, 2, 3>(a, vec, s); break;
-      case 2: rc = launch_ring<256, 128, 4, 2, 3>(a, vec, s); break;
-      case 3: rc = launch_ring<256, 256, 2, 4, 2>(a, vec, s); break;
-      case 4: {                                             // 128 x 128 tiles: small shapes and small launches; hot epilogue combinations specialised
-        const int sp = !vec || a.c_mx || a.row_scale || a.col_scale ? 0
-                     : (a.c_is_bf16 && !a.residual) ? (a.act == ACT_NONE ? 1 : a.act == ACT_QUICK_GELU ? 6 : 7)
-                     : (!a.c_is_bf16 && a.residual && a.act == ACT_NONE) ? 4 : 0;
-#define SG_RING128(SP) (a.f16 ? launch_ring<128, 128, 2, 2, 2, 64, false, true, false, SP>(a, vec, s) : launch_ring<128, 128, 2, 2, 2, 64, false, false, false, SP>(a, vec, s))
-        rc = sp == 1 ? SG_RING128(1) : sp == 4 ? SG_RING128(4) : sp == 6 ? SG_RING128(6) : sp == 7 ? SG_RING128(7) : SG_RING128(0);
-#undef SG_RING128
-        break;
-      }
-      case 5: rc = launch_ring<256, 128, 4, 2, 2>(a, vec, s); break;
-      case 6: rc = launch_ring<128, 256, 2, 4, 3>(a, vec, s); break;
-      case 7: rc = launch_pingpong(a, vec, s); break;
-      case 30: rc = (vec && a.K / 32 >= 4) ? launch_persist(a, s) : launch_pingpong(a, vec, s); break;
-      case 9: rc = launch_ring<128, 256, 1, 4, 3, 32>(a, vec, s); break;    // 72 KiB LDS: two workgroups per CU
-      case 10: rc = launch_ring<256, 128, 4, 1, 3, 32>(a, vec, s); break;
-      case 8: rc = vec ? launch_pp32(a, s) : launch_pingpong(a, vec, s); break;
-      default: return fail(SG_ERR_INVALID, "gemm_bf16: unknown tile config %d", cfg);
-    }
-    prof_end(pcat, s);
-    if (rc != SG_OK) return rc;
-    SG_LAUNCH_CHECK();
-    return SG_OK;
-  }
-  const int64_t tiles = cdiv(a.M, BM) * cdiv(a.N, BN);
-  SG_REQUIRE(tiles < (1ll << 31) && a.batch < 65536, "gemm_bf16: grid too large");
-  dim3 grid((unsigned)tiles, (unsigned)a.batch);
-  prof_begin(PROF_GEMM_BF16, 2.0 * a.M * (double)a.N * a.K * a.batch, s);
-  switch (a.act * 2 + (a.c_is_bf16 ? 1 : 0)) {
-    case 0: launch<ACT_NONE, false>(a, vec, grid, s); break;
-    case 1: launch<ACT_NONE, true>(a, vec, grid, s); break;
-    case 2: launch<ACT_QUICK_GELU, false>(a, vec, grid, s); break;
-    case 3: launch<ACT_QUICK_GELU, true>(a, vec, grid, s); break;
-    case 4: launch<ACT_GELU, false>(a, vec, grid, s); break;
-    case 5: launch<ACT_GELU, true>(a, vec, grid, s); break;
-    case 6: launch<ACT_RELU, false>(a, vec, grid, s); break;
-    case 7: launch<ACT_RELU, true>(a, vec, grid, s); break;
-    default: return fail(SG_ERR_INVALID, "gemm_bf16: bad act %d", a.act);
-  }
-  note_launch("generic", tiles);
-  prof_end(PROF_GEMM_BF16, s);
+  prof_end(pcat, s);
+  if (rc != SG_OK) return rc;
   SG_LAUNCH_CHECK();
   return SG_OK;
 }

@@ -136,8 +136,8 @@ int sg_profile_disable(void);
 int sg_gemm_persist_last_kstep(void);   /* K step in elements of the calling thread's last persistent bf16 / f16 GEMM launch: 64 (gemm_bf16_persist_k64),
                                          * 32 (gemm_bf16_persist: K / 64 < 4 or tuning code 38), 0 = none yet */
 const char* sg_gemm_last_kernel(void);   /* the calling thread's last launch through the 2-byte / two-plane / fp8 GEMM: "<family> grid=<x> ngroup=<n>"
-                                          * with family persist_k64, persist_k32, h2_persist, fp8_persist, pingpong, h2_pingpong, pp32, ring128, ring...,
-                                          * h2_ring128, fp8_ring128, fp8_ring256x256, fp8_mx_ring256x256 or generic; grid = workgroups (persistent) or tiles
+                                          * with family persist_k64, persist_k32, h2_persist, fp8_persist, pingpong, h2_pingpong, ring128,
+                                          * h2_ring128, fp8_ring128, fp8_ring256x256 or fp8_mx_ring256x256; grid = workgroups (persistent) or tiles
                                           * along x; ngroup = the persistent kernel's N-group size (0 = raster order); "none" when its last GEMM call
                                           * launched nothing.  The text stays valid until the thread's next query. */
 const char* sg_attention_last_kernel(void);   /* the calling thread's last launch through the fused attention (sg_attention_raw, sg_op_attention,
@@ -149,12 +149,13 @@ const char* sg_attention_last_kernel(void);   /* the calling thread's last launc
 const char* sg_attention_last_body(void);     /* the body of that same launch: "dma" (the lean dh-64 kernel staging K / V by LDS-DMA), "staged"
                                               * (register-staged K / V: every other fused-attention kernel, and the lean dh-64 one under tuning
                                               * code 39), "stats" (a statistics kernel) or "none". */
-int sg_set_gemm_config(int cfg);   /* tuning hook (calling thread only): bf16 GEMM tile variant, -1 = automatic; 33 = fp8 MLP without the MXFP8
-                                    * hand-off, 34 = LayerNorm as its own pass (no folding), 36 = no small-launch dispatch (a few-tile GEMM stays on the
-                                    * persistent kernel), 38 = the persistent kernel with 32-element K steps (same results as the default 64-element
-                                    * one), 39 = the fused attention's lean dh-64 kernels with register-staged K / V instead of LDS-DMA (the previous
-                                    * body, bit-identical results); 1000+ = tile order of the persistent kernel; 2000 + n = at most n workgroups for every persistent
-                                    * kernel (2000 = one per CU) */
+int sg_set_gemm_config(int cfg);   /* tuning hook (calling thread only), -1 = automatic; 31 = the fp8 GEMM on its ring kernels at every shape,
+                                    * 32 = the fp8 GEMM's persistent kernel from K = 512 on (not only from K = 2048), 34 = LayerNorm as its own
+                                    * pass (no folding), 36 = no small-launch dispatch (a few-tile GEMM stays on the persistent kernel), 38 = the
+                                    * persistent kernel with 32-element K steps (same results as the default 64-element one), 39 = the fused
+                                    * attention's lean dh-64 kernels with register-staged K / V instead of LDS-DMA (the previous body, bit-identical
+                                    * results); 1000 + v = tile order of the persistent kernel; 2000 + n = at most n workgroups for every persistent
+                                    * kernel (2000 = one per CU).  Any other code is refused (SG_ERR_INVALID, the setting unchanged). */
 int sg_profile_read(int category, double* total_ms, double* total_flops, int64_t* launches, int64_t* dropped);
 
 /* ---- context and weights ------------------------------------------------------------------

@@ -157,6 +157,34 @@ def test_attention_raw_refusals_without_gpu():
     assert b"bad precision" in lib.sg_last_error()
 
 
+def test_gemm_tuning_codes_without_gpu():
+    """sg_set_gemm_config accepts -1, the named tuning codes, 1000 + v and 2000 + n, and refuses every other code with the code named in
+    the error (retired tile codes included); on a thread of its own, reset to -1 at the end."""
+    import threading
+    from clip_decontamination_amd import _lib
+    lib = _lib.load()
+    seen = []
+
+    def fresh_thread():
+        try:
+            for code in (0, 5, 8, 30, 33, 35, 37):
+                seen.append((code, lib.sg_set_gemm_config(code), lib.sg_last_error()))
+            for code in (-1, 31, 32, 34, 36, 38, 39, 1000, 1001, 1006, 2000, 2007):
+                seen.append((code, lib.sg_set_gemm_config(code), None))
+        finally:
+            seen.extend(("reset", lib.sg_set_gemm_config(c), None) for c in (-1, 1000, 2000))
+
+    t = threading.Thread(target=fresh_thread)
+    t.start()
+    t.join()
+    assert len(seen) == 22, seen
+    for code, rc, err in seen[:7]:
+        assert rc != 0, code
+        assert b"unknown tuning code %d" % code in err, (code, err)
+    for code, rc, _ in seen[7:]:
+        assert rc == 0, (code, rc)
+
+
 def test_jbu_capture_and_launch_record_refusals():
     """sg_jbu_set_capture refuses a null upsampler; sg_jbu_last_kernels is per thread, reads 'none' on a thread that never launched the
     upsampler, and calls refused by their argument checks leave it as it was; the ctypes capture struct has the header's layout."""

@@ -114,6 +114,26 @@ def test_raw_gemm_refuses_k_not_multiple_of_64():
             lib.sg_set_gemm_config(-1)
 
 
+def test_refused_code_keeps_the_setting():
+    """A refused tuning code (the retired tile code 5) leaves the thread's setting as it was: under code 38 the next persistent launch still
+    runs the 32-element kernel."""
+    lib = _lib()
+    M, N, K = 12 * 1370, 1024, 1024
+    A, W = rnd(M, K, seed=61).bfloat16(), rnd(N, K, seed=62, scale=K ** -0.5).bfloat16()
+    out = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    P = lambda t: C.c_void_p(t.data_ptr())
+    lib.sg_set_gemm_config(OLD)
+    try:
+        assert lib.sg_set_gemm_config(5) != 0
+        assert b"unknown tuning code 5" in lib.sg_last_error()
+        assert lib.sg_gemm_bf16_raw(P(A), P(W), None, None, P(out), M, N, K, 0, 1, stream) == 0, lib.sg_last_error()
+        assert lib.sg_gemm_persist_last_kstep() == 32
+    finally:
+        lib.sg_set_gemm_config(-1)
+    torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize("prec", ["bf16", "f16"])
 def test_batched_similarity_bit_identical(prec):
     """The blockIdx.y-batched form: the similarity map of 4 tiles (one GEMM launch, batch 4; n = 1288 rows: a multiple of 8 for the vector

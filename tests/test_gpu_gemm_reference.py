@@ -1,11 +1,11 @@
-"""Every GEMM kernel behind gemm_bf16() against a float64 reference of the same operation, element by element, with a per-element bound
-built from |A|.|W|^T (tests/gemm_reference.py: accumulation, two-plane representation, activation, output rounding -- no constant fitted
-to observed outputs).  Each case
+"""Every GEMM kernel the dispatch behind gemm_bf16() reaches, against a float64 reference of the same operation, element by element, with
+a per-element bound built from |A|.|W|^T (tests/gemm_reference.py: accumulation, two-plane representation, activation, output rounding --
+no constant fitted to observed outputs).  Each case
   * runs on the operands the kernel consumes (bf16 / f16 storage, two-plane storage of f32 values, e4m3 bytes + scales),
   * asserts from sg_gemm_last_kernel() that the intended kernel ran, with the intended grid and N-group size,
   * compares every output element (C is pre-filled with NaN, so an element never written fails),
   * checks that guard bands right before and after C are untouched,
-  * and resets the tile configuration, the tile order (1000) and the grid cap (2000) whatever happens.
+  * and resets the tuning code (-1), the tile order (1000) and the grid cap (2000) whatever happens.
 Ragged shapes (M = 4100, N = 2056: 153 tiles of 256 x 256, the last one 4 rows x 8 columns) and grid caps of 1 / 3 / 7 / 61 workgroups make
 one persistent workgroup run 1 to 153 tiles: the K-step stream across tile boundaries, the tile switch and the last steps of a tile all
 meet the reference."""
@@ -393,18 +393,9 @@ def test_large_offsets(prec):
         torch.cuda.empty_cache()
 
 
-# ---- the non-persistent kernels -------------------------------------------------------------------------------------------------------
+# ---- the non-persistent kernels: the 128 x 128 ring (few-tile launches) and the 256 x 256 ping-pong (large launches the persistent kernel
+# does not take: K / 32 < 4 or the scalar epilogue) ------------------------------------------------------------------------------------
 SM, SN, SK = 1100, 520, 256                                      # 5 x 3 tiles of 256 x 256: a few-tile launch
-RINGS = {1: ("ring128x128_s3", 128, 128), 2: ("ring256x128_s3", 256, 128), 3: ("ring256x256", 256, 256), 5: ("ring256x128", 256, 128),
-         6: ("ring128x256_s3", 128, 256), 9: ("ring128x256_k32", 128, 256), 10: ("ring256x128_k32", 256, 128)}
-
-
-@pytest.mark.parametrize("code", list(RINGS))
-@pytest.mark.parametrize("form", ["c2_act1", "f32_res"])
-def test_ring_codes(code, form):
-    fam, bm, bn = RINGS[code]
-    kw = dict(act=1) if form == "c2_act1" else dict(act=0, packed=False, residual=True)
-    run_raw("bf16", SM, SN, SK, codes=(code,), family=fam, grid=cdiv(SM, bm) * cdiv(SN, bn), seed=150 + code, **kw)
 
 
 @pytest.mark.parametrize("prec", ["bf16", "f16"])
@@ -414,23 +405,15 @@ def test_ring128_few_tiles(prec, form):
     run_raw(prec, SM, SN, SK, family="ring128", grid=cdiv(SM, 128) * cdiv(SN, 128), seed=170, **kw)
 
 
-@pytest.mark.parametrize("form", ["c2_act1", "f32_res"])
-def test_pingpong_and_pp32(form):
-    kw = dict(act=1) if form == "c2_act1" else dict(act=0, packed=False, residual=True)
-    run_raw("bf16", SM, SN, SK, codes=(7,), family="pingpong", grid=15, seed=180, **kw)
-    run_raw("bf16", SM, SN, SK, codes=(8,), family="pp32", grid=15, seed=181, **kw)
+PP_FORMS = {"c2_act2": dict(act=2), "c2_act1": dict(act=1), "f32_res": dict(act=0, packed=False, residual=True)}
 
 
 @pytest.mark.parametrize("prec", ["bf16", "f16"])
-def test_pingpong_short_k(prec):
-    """K = 64 at >= 128 tiles: K / 32 < 4 sends the persistent dispatch to the ping-pong kernel."""
-    run_raw(prec, RM, RN, 64, act=2, family="pingpong", grid=153, seed=190)
-
-
-def test_generic_kernel():
-    run_raw("bf16", SM, SN, SK, act=2, codes=(0,), family="generic", grid=cdiv(SM, 128) * cdiv(SN, 128), seed=200)
-    run_raw("bf16", SM, SN, SK, act=0, packed=False, residual=True, codes=(0,), family="generic", grid=cdiv(SM, 128) * cdiv(SN, 128),
-            seed=201)
+@pytest.mark.parametrize("form", list(PP_FORMS))
+def test_pingpong_short_k(prec, form):
+    """K = 64 at >= 128 tiles: K / 32 < 4 sends the persistent dispatch to the ping-pong kernel (its vector epilogue, 2-byte and f32 +
+    residual outputs)."""
+    run_raw(prec, RM, RN, 64, family="pingpong", grid=153, seed=190, **PP_FORMS[form])
 
 
 @pytest.mark.parametrize("prec", ["bf16", "f16"])

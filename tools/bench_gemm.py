@@ -1,4 +1,5 @@
-"""A/B of the bf16 GEMM tile variants on the ViT-L/14 shapes (interleaved rounds in ONE process, random data)."""
+"""A/B of bf16 GEMM tuning codes on the ViT-L/14 shapes (interleaved rounds in ONE process, random data).  Argument: a comma-separated
+list of sg_set_gemm_config codes, by default -1,38 (the automatic dispatch against the persistent kernel on 32-element K steps)."""
 import ctypes as C
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -9,8 +10,8 @@ lib = _lib.load()
 dev = "cuda:0"
 M = int(os.environ.get("GEMM_TILES", "32")) * 1370
 SHAPES = [("qkv", M, 3072, 1024, 0, 1), ("out", M, 1024, 1024, 0, 0), ("fc", M, 4096, 1024, 1, 1), ("proj", M, 1024, 4096, 0, 0)]
-CONFIGS = [int(c) for c in (sys.argv[1].split(",") if len(sys.argv) > 1 else "0,1,2,3,4,5,6".split(","))]
-# tile order of the persistent kernel (config 30): GEMM_ORDER = auto | raster | <N-group size>
+CONFIGS = [int(c) for c in (sys.argv[1].split(",") if len(sys.argv) > 1 else "-1,38".split(","))]
+# tile order of the persistent kernel: GEMM_ORDER = auto | raster | <N-group size>
 _order = os.environ.get("GEMM_ORDER", "auto")
 lib.sg_set_gemm_config(1000 if _order == "auto" else (1001 if _order == "raster" else 1001 + int(_order)))
 if os.environ.get("GEMM_GRID_CAP"):
@@ -40,7 +41,7 @@ for name, m, n, k, act, cbf in SHAPES:
                 x = x + R
             ref = x
         err = ((out - ref).abs().max() / ref.abs().max()).item()
-        assert err < 2e-2, (name, cfg, err)   # every tile configuration computes the same GEMM
+        assert err < 2e-2, (name, cfg, err)   # every tuning code computes the same GEMM
     for rnd in range(ROUNDS):
         for cfg in CONFIGS:
             lib.sg_set_gemm_config(cfg)
