@@ -71,19 +71,6 @@ void prof_end(int cat, hipStream_t s) {
   g_prof.used[cat]++;
 }
 
-// ---- a bump allocator over caller-provided (or arena) memory ------------------------------------------------
-struct Bump {
-  char* base; size_t off, cap; bool dry;
-  Bump(void* p, size_t c, bool d) : base((char*)p), off(0), cap(c), dry(d) {}
-  void* take(size_t bytes) {
-    off = align_up(off, 256);
-    void* p = dry ? nullptr : (void*)(base + off);
-    off += bytes;
-    return p;
-  }
-  template <typename T> T* get(size_t count) { return reinterpret_cast<T*>(take(count * sizeof(T))); }
-};
-
 struct LayerW {
   void *w_qkv, *w_out, *w_fc, *w_proj;                 // packed [N_out, K] in the compute dtype
   uint8_t *w_qkv8, *w_fc8, *w_proj8;                   // SG_PREC_FP8: e4m3 copies + per-output-channel scales

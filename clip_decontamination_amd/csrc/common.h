@@ -64,6 +64,19 @@ static inline hipStream_t as_stream(sg_stream s) { return reinterpret_cast<hipSt
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 
+// ---- a bump allocator over caller-provided (or arena) memory ------------------------------------------------
+struct Bump {
+  char* base; size_t off, cap; bool dry;
+  Bump(void* p, size_t c, bool d) : base((char*)p), off(0), cap(c), dry(d) {}
+  void* take(size_t bytes) {
+    off = align_up(off, 256);
+    void* p = dry ? nullptr : (void*)(base + off);
+    off += bytes;
+    return p;
+  }
+  template <typename T> T* get(size_t count) { return reinterpret_cast<T*>(take(count * sizeof(T))); }
+};
+
 // ---- bf16 <-> f32 -------------------------------------------------------------------------------
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 __device__ __forceinline__ bf16_t f2bf(float f) {                    // round-to-nearest-even, NaN kept

@@ -581,7 +581,7 @@ extern "C" int sg_cosine_logits(const float* tokens, const float* cls, const flo
   SG_REQUIRE((((uintptr_t)tokens) & 15) == 0, "sg_cosine_logits: tokens must be 16-byte aligned");
   const int nv = (E + 63) / 64;
   auto kern = nv <= 8 ? cosine_logits_kernel<8> : (nv <= 12 ? cosine_logits_kernel<12> : (nv <= 16 ? cosine_logits_kernel<16> : cosine_logits_kernel<CL_MAXV>));
-  if (lds > 48 * 1024) SG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (lds > 48 * 1024) SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
   hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(n, CL_TPB), (unsigned)B), dim3(256), lds, as_stream(s), tokens, cls, text,
                      n, E, Q, global_debias_factor, cls_token_lambda, logits);
   SG_LAUNCH_CHECK();
@@ -599,7 +599,7 @@ extern "C" int sg_cosine_logits_two_plane(const float* tokens, const float* cls,
   const size_t ldsm = (size_t)2 * 16 * (E + 8) * 2 + (4 * 64 + 16) * sizeof(float);
   if (!(Q <= 16 && E % 32 == 0 && n >= 4096 && (((uintptr_t)logits) & 15) == 0 && (((uintptr_t)tokens) & 15) == 0 && ldsm <= 160 * 1024))
     return sg_cosine_logits(tokens, cls, text, B, n, E, Q, 0.f, cls_token_lambda, logits, s);
-  if (ldsm > 48 * 1024) SG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sg::cosine_logits_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsm));
+  if (ldsm > 48 * 1024) SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(sg::cosine_logits_mfma_kernel), ldsm));
   hipLaunchKernelGGL(sg::cosine_logits_mfma_kernel, dim3((unsigned)cdiv(n, 4 * 64 * sg::CLM_ROUNDS), (unsigned)B), dim3(256), ldsm, as_stream(s), tokens, cls, text,
                      n, E, Q, cls_token_lambda, logits);
   SG_LAUNCH_CHECK();

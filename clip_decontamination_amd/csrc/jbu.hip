@@ -15,6 +15,7 @@
 // then  out = x + 0.1 * conv1x1_CxC(x)  (JBUOne/JBUStack.forward :301,325) as one GEMM with a residual epilogue.
 #include <string>
 #include <vector>
+#include <type_traits>
 #include "rowops.h"
 
 namespace sg {
@@ -1088,616 +1089,18 @@ __global__ __launch_bounds__(256) void global_debias_kernel(const float* __restr
   for (int i = lane; i < E; i += 64) o[i] = f[i] - cr[i] * ci * w;
 }
 
-struct JbuStage {
-  int r;
-  float *range_temp, *sigma, *rp0_w, *rp0_b, *rp3_w, *rp3_b, *fx0_w, *fx0_b, *fx3_w, *fx3_b;
-  // throughput mode: the two fixup linears on the bf16 MFMA GEMM, operands zero-padded to [NP, KP1] / [NP, NP] (NP, KP1 multiples of 64)
-  void *fx0_w16, *fx3_w16; float *fx0_bp, *fx3_bp;
-  void *fx0_w16h, *fx3_w16h;                              // the same operands in f16: the all-2-byte fixup chain of the low-res path (round 3)
-  void *fx0_wh2, *fx3_wh2;                                // ... and as two-plane f16 (SG_PREC_F16X2: f32-grade linears on the f16 matrix pipe)
-};
-static inline int jbu_np(int r) { const int d = 2 * r + 1; return (int)align_up((size_t)d * d, 64); }
-static inline int jbu_kp1(int r) { const int d = 2 * r + 1; return (int)align_up((size_t)d * d + 3, 64); }
-static inline size_t rc_kp(int C) { return align_up((size_t)C + 3, 64); }
-
-}  // namespace sg
-
-using namespace sg;
-
-struct sg_jbu {
-  int device, kind, C, n_stage_sets;
-  void* arena; size_t arena_bytes;
-  JbuStage st[4];
-  float *fin_w, *fin_b;
-  void* fin_w16;
-  void* fin_wh2;                                           // two-plane f16 copy of the final 1x1 weight (C % 32 == 0)
-  std::vector<uint8_t> have;
-  // kind 3 (resize_conv): conv{1..4} as f32 [C, C+3] (what the f32 GEMM reads) and packed [W_src | W_guid | 0] rows [C, KP] in bf16 and
-  // two-plane f16 (KP = align_up(C + 3, 64): the 2-byte GEMMs' K % 64 rule, the two-plane one's K % 32)
-  float *rc_w[4], *rc_b[4];
-  void *rc_w16[4], *rc_wh2[4];
-  sg_jbu_capture* cap = nullptr;                           // test instrumentation (sg_jbu_set_capture): copies of every kernel's operands
-};
-
-namespace sg {
-static const char* kStageTensor[10] = {"range_temp", "sigma_spatial", "range_proj.0.weight", "range_proj.0.bias", "range_proj.3.weight",
-                                       "range_proj.3.bias", "fixup_proj.0.weight", "fixup_proj.0.bias", "fixup_proj.3.weight",
-                                       "fixup_proj.3.bias"};
-static int64_t stage_numel(int slot, int r) {
-  const int64_t d2 = (int64_t)(2 * r + 1) * (2 * r + 1);
-  switch (slot) {
-    case 0: case 1: return 1;
-    case 2: return KEY_DIM * 3; case 3: return KEY_DIM; case 4: return KEY_DIM * KEY_DIM; case 5: return KEY_DIM;
-    case 6: return d2 * (d2 + 3); case 7: return d2; case 8: return d2 * d2; default: return d2;
-  }
-}
 __global__ void scale_kernel(float* p, float a, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] *= a;
 }
-}  // namespace sg
 
-extern "C" int sg_jbu_create(sg_jbu** out, int device, int kind, int feat_dim) {
-  SG_REQUIRE(out && kind >= 0 && kind <= 3 && feat_dim > 0 && feat_dim % 4 == 0 && (kind != SG_JBU_RESIZE_CONV || feat_dim % 8 == 0),
-             "sg_jbu_create: bad arguments (kind 0 = jbu_one, 1 = jbu_stack, 2 = bilinear, 3 = resize_conv; feat_dim %% 4 == 0, resize_conv %% 8)");
-  DeviceGuard dg(device);
-  sg_jbu* j = new sg_jbu();
-  if (kind == SG_JBU_BILINEAR) {                          // Bilinear (upsamplers.py:343-350) has no parameters: no arena, nothing to load
-    j->device = device; j->kind = kind; j->C = feat_dim; j->n_stage_sets = 0; j->arena = nullptr; j->arena_bytes = 0;
-    *out = j;
-    return SG_OK;
-  }
-  if (kind == SG_JBU_RESIZE_CONV) {                       // LayeredResizeConv(dim, 1) (upsamplers.py:178-200): four 1x1 convs over [src | guidance]
-    j->device = device; j->kind = kind; j->C = feat_dim; j->n_stage_sets = 0;
-    const size_t KP = rc_kp(feat_dim);
-    size_t off = 0;
-    auto take = [&](char* base, size_t n) { off = align_up(off, 256); void* p = base ? base + off : nullptr; off += n; return p; };
-    auto lay = [&](char* base) {
-      off = 0;
-      for (int k = 0; k < 4; ++k) {
-        j->rc_w[k] = (float*)take(base, (size_t)feat_dim * (feat_dim + 3) * 4);
-        j->rc_b[k] = (float*)take(base, (size_t)feat_dim * 4);
-        j->rc_w16[k] = take(base, (size_t)feat_dim * KP * 2);
-        j->rc_wh2[k] = take(base, (size_t)feat_dim * KP * 4);
-      }
-      return align_up(off, 256);
-    };
-    j->arena_bytes = lay(nullptr);
-    hipError_t e = hipMalloc(&j->arena, j->arena_bytes);
-    if (e != hipSuccess) { delete j; return fail(SG_ERR_HIP, "sg_jbu_create: hipMalloc(%zu) -> %s", j->arena_bytes, hipGetErrorString(e)); }
-    lay((char*)j->arena);
-    SG_HIP(hipMemset(j->arena, 0, j->arena_bytes));
-    j->have.assign(8, 0);
-    *out = j;
-    return SG_OK;
-  }
-  j->device = device; j->kind = kind; j->C = feat_dim; j->n_stage_sets = kind == 0 ? 1 : 4;
-  const int r = kind == 0 ? 5 : 3;                     // JBUOne radius 5, JBUStack radius 3 (upsamplers.py:281-284,308)
-  size_t bytes = 0;
-  auto lay = [&](char* base) {
-    size_t off = 0;
-    auto take = [&](size_t n) { off = align_up(off, 256); void* p = base ? base + off : nullptr; off += n; return p; };
-    for (int s = 0; s < j->n_stage_sets; ++s) {
-      JbuStage& S = j->st[s]; S.r = r;
-      float** slots[10] = {&S.range_temp, &S.sigma, &S.rp0_w, &S.rp0_b, &S.rp3_w, &S.rp3_b, &S.fx0_w, &S.fx0_b, &S.fx3_w, &S.fx3_b};
-      for (int t = 0; t < 10; ++t) *slots[t] = (float*)take((size_t)stage_numel(t, r) * 4);
-      S.fx0_w16 = take((size_t)jbu_np(r) * jbu_kp1(r) * 2); S.fx3_w16 = take((size_t)jbu_np(r) * jbu_np(r) * 2);
-      S.fx0_bp = (float*)take((size_t)jbu_np(r) * 4); S.fx3_bp = (float*)take((size_t)jbu_np(r) * 4);
-      S.fx0_w16h = take((size_t)jbu_np(r) * jbu_kp1(r) * 2); S.fx3_w16h = take((size_t)jbu_np(r) * jbu_np(r) * 2);
-      S.fx0_wh2 = take((size_t)jbu_np(r) * jbu_kp1(r) * 4); S.fx3_wh2 = take((size_t)jbu_np(r) * jbu_np(r) * 4);
-    }
-    j->fin_w = (float*)take((size_t)feat_dim * feat_dim * 4);
-    j->fin_b = (float*)take((size_t)feat_dim * 4);
-    j->fin_w16 = take((size_t)feat_dim * feat_dim * 2);
-    j->fin_wh2 = take((size_t)feat_dim * feat_dim * 4);
-    bytes = align_up(off, 256);
-  };
-  lay(nullptr);
-  j->arena_bytes = bytes;
-  hipError_t e = hipMalloc(&j->arena, bytes);
-  if (e != hipSuccess) { delete j; return fail(SG_ERR_HIP, "sg_jbu_create: hipMalloc(%zu) -> %s", bytes, hipGetErrorString(e)); }
-  lay((char*)j->arena);
-  SG_HIP(hipMemset(j->arena, 0, bytes));                  // the zero padding of the bf16 fixup operands
-  j->have.assign(j->n_stage_sets * 10 + 2, 0);
-  *out = j;
-  return SG_OK;
-}
-
-extern "C" void sg_jbu_destroy(sg_jbu* j) {
-  if (!j) return;
-  if (j->arena) (void)hipFree(j->arena);
-  delete j;
-}
-
-extern "C" int sg_jbu_set_tensor(sg_jbu* j, const char* name, const float* src, int64_t numel, sg_stream st) {
-  SG_REQUIRE(j && name && src, "sg_jbu_set_tensor: null argument");
-  if (j->kind == SG_JBU_BILINEAR) return fail(SG_ERR_INVALID, "sg_jbu_set_tensor: the bilinear upsampler has no tensor '%s'", name);
-  DeviceGuard dg(j->device);
-  hipStream_t s = as_stream(st);
-  if (j->kind == SG_JBU_RESIZE_CONV) {                    // "conv{1..4}.weight" [C, C+3, 1, 1] / "conv{1..4}.bias" [C]
-    const int C = j->C;
-    if (!strncmp(name, "conv", 4) && name[4] >= '1' && name[4] <= '4' && name[5] == '.') {
-      const int k = name[4] - '1';
-      if (!strcmp(name + 6, "weight")) {
-        SG_REQUIRE(numel == (int64_t)C * (C + 3), "sg_jbu_set_tensor(%s): expected %lld elements, got %lld", name, (long long)C * (C + 3), (long long)numel);
-        SG_HIP(hipMemcpyAsync(j->rc_w[k], src, (size_t)numel * 4, hipMemcpyDeviceToDevice, s));
-        SG_TRY(pack_rows(src, C, C + 3, C + 3, j->rc_w16[k], (int)rc_kp(C), HK_BF16, s));
-        SG_TRY(pack_rows(src, C, C + 3, C + 3, j->rc_wh2[k], (int)rc_kp(C), HK_F16X2, s));
-        j->have[2 * k] = 1;
-        return SG_OK;
-      }
-      if (!strcmp(name + 6, "bias")) {
-        SG_REQUIRE(numel == C, "sg_jbu_set_tensor(%s): expected %d elements, got %lld", name, C, (long long)numel);
-        SG_HIP(hipMemcpyAsync(j->rc_b[k], src, (size_t)C * 4, hipMemcpyDeviceToDevice, s));
-        j->have[2 * k + 1] = 1;
-        return SG_OK;
-      }
-    }
-    return fail(SG_ERR_INVALID, "sg_jbu_set_tensor: unknown tensor name '%s' for resize_conv", name);
-  }
-  auto put = [&](float* dst, int64_t n) -> int {
-    SG_REQUIRE(numel == n, "sg_jbu_set_tensor(%s): expected %lld elements, got %lld", name, (long long)n, (long long)numel);
-    SG_HIP(hipMemcpyAsync(dst, src, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-    return SG_OK;
-  };
-  if (!strcmp(name, "fixup_proj.1.weight")) {
-    SG_TRY(put(j->fin_w, (int64_t)j->C * j->C));
-    if (j->C % 64 == 0) SG_TRY(pack_rows(src, j->C, j->C, j->C, j->fin_w16, j->C, 1, s));
-    if (j->C % 32 == 0) SG_TRY(pack_rows(src, j->C, j->C, j->C, j->fin_wh2, j->C, HK_F16X2, s));
-    j->have[j->n_stage_sets * 10] = 1; return SG_OK;
-  }
-  if (!strcmp(name, "fixup_proj.1.bias")) {
-    SG_TRY(put(j->fin_b, j->C));
-    hipLaunchKernelGGL(scale_kernel, dim3((unsigned)cdiv(j->C, 256)), dim3(256), 0, s, j->fin_b, 0.1f, (int64_t)j->C);   // epilogue is alpha*acc + bias
-    SG_LAUNCH_CHECK();
-    j->have[j->n_stage_sets * 10 + 1] = 1; return SG_OK;
-  }
-  int set = -1; const char* rest = nullptr;
-  if (j->kind == 0 && !strncmp(name, "up.", 3)) { set = 0; rest = name + 3; }
-  else if (j->kind == 1 && !strncmp(name, "up", 2) && name[2] >= '1' && name[2] <= '4' && name[3] == '.') { set = name[2] - '1'; rest = name + 4; }
-  if (set >= 0) {
-    for (int t = 0; t < 10; ++t)
-      if (!strcmp(rest, kStageTensor[t])) {
-        JbuStage& S = j->st[set];
-        float* slots[10] = {S.range_temp, S.sigma, S.rp0_w, S.rp0_b, S.rp3_w, S.rp3_b, S.fx0_w, S.fx0_b, S.fx3_w, S.fx3_b};
-        SG_TRY(put(slots[t], stage_numel(t, S.r)));
-        if (t == 9) {                                  // K += 0.1 * (H.W3^T + b3): the GEMM epilogue computes 0.1*acc + bias
-          hipLaunchKernelGGL(scale_kernel, dim3((unsigned)cdiv(numel, 256)), dim3(256), 0, s, slots[t], 0.1f, numel);
-          SG_LAUNCH_CHECK();
-        }
-        const int d2s = (2 * S.r + 1) * (2 * S.r + 1);
-        if (t == 6) { SG_TRY(pack_rows(src, d2s, d2s + 3, d2s + 3, S.fx0_w16, jbu_kp1(S.r), 1, s)); SG_TRY(pack_rows(src, d2s, d2s + 3, d2s + 3, S.fx0_w16h, jbu_kp1(S.r), HK_F16, s)); SG_TRY(pack_rows(src, d2s, d2s + 3, d2s + 3, S.fx0_wh2, jbu_kp1(S.r), HK_F16X2, s)); }
-        if (t == 8) { SG_TRY(pack_rows(src, d2s, d2s, d2s, S.fx3_w16, jbu_np(S.r), 1, s)); SG_TRY(pack_rows(src, d2s, d2s, d2s, S.fx3_w16h, jbu_np(S.r), HK_F16, s)); SG_TRY(pack_rows(src, d2s, d2s, d2s, S.fx3_wh2, jbu_np(S.r), HK_F16X2, s)); }
-        if (t == 7) SG_HIP(hipMemcpyAsync(S.fx0_bp, slots[t], (size_t)d2s * 4, hipMemcpyDeviceToDevice, s));
-        if (t == 9) SG_HIP(hipMemcpyAsync(S.fx3_bp, slots[t], (size_t)d2s * 4, hipMemcpyDeviceToDevice, s));
-        j->have[set * 10 + t] = 1;
-        return SG_OK;
-      }
-  }
-  return fail(SG_ERR_INVALID, "sg_jbu_set_tensor: unknown tensor name '%s' for this upsampler kind", name);
-}
-
-namespace sg {
-struct JbuPlan { float *gs, *proj, *X, *H1, *Kf, *hr, *bufA, *bufB; void* x16; bf16_t *X16, *H116; float *rowdot, *geff, *g0, *clsl; };
 constexpr int JBU_QMAX = 32;                         // queries the fused logits tail keeps in registers
-static size_t jbu_plan(const sg_jbu* j, int B, int gh, int gw, void* ws, bool dry, JbuPlan& p) {
-  const int r = j->st[0].r, d2 = (2 * r + 1) * (2 * r + 1);
-  const int64_t pixels = (int64_t)B * 16 * gh * 16 * gw;              // final resolution
-  size_t off = 0;
-  auto take = [&](size_t n) { off = align_up(off, 256); void* q = dry ? nullptr : (char*)ws + off; off += n; return q; };
-  p.gs = (float*)take((size_t)pixels * 3 * 4);
-  p.proj = (float*)take((size_t)pixels * KEY_DIM * 4);
-  const int NP = jbu_np(r), KP1 = jbu_kp1(r);
-  p.X = (float*)take((size_t)pixels * (d2 + 3) * 4 + 1024);           // + slack: the padded fixup GEMM reads its residual NP columns wide
-  p.H1 = (float*)take((size_t)pixels * d2 * 4);
-  p.Kf = (float*)take((size_t)pixels * NP * 4);                       // row stride d2 (parity mode) or NP (throughput mode)
-  p.X16 = (bf16_t*)take((size_t)pixels * KP1 * 4);                      // 2-byte operand rows (throughput mode) or two-plane f16 ones (SG_PREC_F16X2: 4 bytes per element)
-  p.H116 = (bf16_t*)take((size_t)pixels * NP * 4);
-  p.hr = (float*)take((size_t)pixels * j->C * 4);
-  p.bufA = (float*)take((size_t)pixels / 4 * j->C * 4);                // stage-3 output (8x): ping
-  p.bufB = (float*)take((size_t)pixels * j->C * 4);                    // stage-2 / stage-4 output: pong
-  p.x16 = take((size_t)pixels * j->C * 2);
-  p.rowdot = (float*)take((size_t)pixels * (j->C / 64 + 1) * 4);       // fused tail: per-pixel partial |out|^2 - |x|^2, one slot per 64 columns
-  p.geff = (float*)take((size_t)j->C * JBU_QMAX * 4);
-  p.g0 = (float*)take((size_t)JBU_QMAX * 4);
-  p.clsl = (float*)take((size_t)B * JBU_QMAX * 4);
-  return align_up(off, 256);
-}
-// kind 2 (bilinear): the per-token prologue's outputs -- y = tokens . T^T [B*n, JBU_QMAX] and the Gram terms [B*n, BL_G] -- and the CLS logits
-constexpr int BL_G = 8;                              // 5 Gram terms per token, rows padded to 32 bytes
-struct BilinearPlan { float *y, *gram, *clsl; };
-static size_t bilinear_plan(int B, int gh, int gw, void* ws, bool dry, BilinearPlan& p) {
-  const size_t tokens = (size_t)B * gh * gw;
-  size_t off = 0;
-  auto take = [&](size_t n) { off = align_up(off, 256); void* q = dry ? nullptr : (char*)ws + off; off += n; return q; };
-  p.y = (float*)take(tokens * JBU_QMAX * 4);
-  p.gram = (float*)take(tokens * BL_G * 4);
-  p.clsl = (float*)take((size_t)B * JBU_QMAX * 4);
-  return align_up(off, 256);
-}
-static int bilinear_upsample(sg_jbu* j, const float* source, int B, int gh, int gw, int GH, int GW, float* out, hipStream_t s);
-// kind 3 (resize_conv): per stage the bilinear x2 source [P, C] f32 (the GEMM's residual), the GEMM's A rows [P, KP] (4 bytes per element
-// at most) and the stage outputs of stages 1..3 (stage 4 writes the caller's output)
-struct ResizeConvPlan { float *big, *s1, *s2, *s3; void* a; };
-static size_t resize_conv_plan(int C, int B, int gh, int gw, void* ws, bool dry, ResizeConvPlan& p) {
-  const size_t n = (size_t)B * gh * gw;
-  size_t off = 0;
-  auto take = [&](size_t b) { off = align_up(off, 256); void* q = dry ? nullptr : (char*)ws + off; off += b; return q; };
-  p.big = (float*)take(n * 256 * C * 4);
-  p.a = take(n * 256 * rc_kp(C) * 4);
-  p.s1 = (float*)take(n * 4 * C * 4);
-  p.s2 = (float*)take(n * 16 * C * 4);
-  p.s3 = (float*)take(n * 64 * C * 4);
-  return align_up(off, 256);
-}
-static int resize_conv_upsample(sg_jbu* j, const float* source, const float* guidance, int B, int gh, int gw, int GH, int GW, int precision,
-                                float* out, void* ws, size_t ws_bytes, hipStream_t s);
-static int bilinear_logits(sg_jbu* j, const float* source, int B, int gh, int gw, int GH, int GW, const float* text, int Q,
-                           const float* cls, float cls_token_lambda, float* logits, void* ws, size_t ws_bytes, hipStream_t s);
-}  // namespace sg
-
-namespace sg {
-// The calling thread's last sg_jbu_upsample / sg_jbu_logits (sg_jbu_last_kernels): static names and grids stored in the branch that
-// launches each kernel, as gemm_bf16's record does; the text is made only when queried.
-struct JbuStageRecord { const char *range, *x16, *fixup0, *fixup1, *kf, *src, *bicubic, *hr, *conv, *out16; unsigned grid[3]; };
-struct JbuLaunchRecord { bool used; JbuStageRecord st[4]; const char *fin, *fin_a, *geff, *cls, *pix; };
-static thread_local JbuLaunchRecord g_jbu_rec = {};
-static void jbu_rec_start() { g_jbu_rec = {}; g_jbu_rec.used = true; }
-// capture (test instrumentation): copy `bytes` of `src` into the caller's slot on the call's stream; stage < 0 = a tail slot
-static int jbu_cap(sg_jbu* j, int stage, int slot, const void* src, size_t bytes, hipStream_t s) {
-  if (!j->cap) return SG_OK;
-  sg_jbu_capture_slot& c = stage < 0 ? j->cap->tail[slot] : j->cap->stage[stage][slot];
-  if (!c.dst) return SG_OK;
-  if (bytes > c.cap) return fail(SG_ERR_INVALID, "sg_jbu capture: stage %d slot %d needs %zu bytes, the buffer holds %zu", stage, slot, bytes, c.cap);
-  SG_HIP(hipMemcpyAsync(c.dst, src, bytes, hipMemcpyDeviceToDevice, s));
-  c.bytes = bytes;
-  return SG_OK;
-}
-static void jbu_cap_reset(sg_jbu* j) {
-  if (!j->cap) return;
-  for (auto& st : j->cap->stage) for (auto& c : st) c.bytes = 0;
-  for (auto& c : j->cap->tail) c.bytes = 0;
-}
-}  // namespace sg
-
-extern "C" int sg_jbu_set_capture(sg_jbu* j, sg_jbu_capture* cap) {
-  SG_REQUIRE(j, "sg_jbu_set_capture: null upsampler");
-  j->cap = cap;
-  return SG_OK;
-}
-
-extern "C" const char* sg_jbu_last_kernels(void) {
-  static thread_local std::string text;
-  if (!g_jbu_rec.used) return "none";
-  text.clear();
-  auto put = [&](const std::string& key, const char* v) {
-    if (!v) return;
-    if (!text.empty()) text += ' ';
-    text += key + "=" + v;
-  };
-  for (int k = 0; k < 4; ++k) {
-    const JbuStageRecord& R = g_jbu_rec.st[k];
-    const std::string sk = "s" + std::to_string(k) + ".";
-    put(sk + "range", R.range); put(sk + "x16", R.x16); put(sk + "fixup0", R.fixup0); put(sk + "fixup1", R.fixup1); put(sk + "kf", R.kf);
-    put(sk + "src", R.src); put(sk + "bicubic", R.bicubic); put(sk + "hr", R.hr); put(sk + "conv", R.conv);
-    if (R.conv) put(sk + "grid", (std::to_string(R.grid[0]) + "x" + std::to_string(R.grid[1]) + "x" + std::to_string(R.grid[2])).c_str());
-    put(sk + "out16", R.out16);
-  }
-  put("final", g_jbu_rec.fin); put("final.a", g_jbu_rec.fin_a);
-  if (g_jbu_rec.pix) {
-    std::string t = std::string(g_jbu_rec.geff) + (g_jbu_rec.cls ? std::string(",") + g_jbu_rec.cls : std::string()) + "," + g_jbu_rec.pix;
-    put("tail", t.c_str());
-  }
-  return text.c_str();
-}
-
-extern "C" size_t sg_jbu_workspace_bytes(const sg_jbu* j, int B, int gh, int gw) {
-  if (!j || B <= 0 || gh <= 0 || gw <= 0) return 0;
-  if (j->kind == SG_JBU_BILINEAR) { BilinearPlan p; return bilinear_plan(B, gh, gw, nullptr, true, p); }
-  if (j->kind == SG_JBU_RESIZE_CONV) { ResizeConvPlan p; return resize_conv_plan(j->C, B, gh, gw, nullptr, true, p); }
-  JbuPlan p;
-  return jbu_plan(j, B, gh, gw, nullptr, true, p);
-}
-
-// The four 2x stages (JBULearnedRange.forward x 4): source [B, gh*gw, C] -> *x_out [B, 16gh*16gw, C] f32 inside the workspace
-// (and its bf16 copy in p.x16 in throughput mode when C % 64 == 0)
-static int jbu_stages(sg_jbu* j, const float* source, const float* guidance, int B, int gh, int gw, int GH, int GW, int precision,
-                      const JbuPlan& p, const float** x_out, hipStream_t s, bool want_f32_x = true, bool* x2_in_hr = nullptr) {
-  const int C = j->C;
-  const float* src = source;
-  int h = gh, w = gw;
-  // low-res adaptive convolution (throughput mode): its bf16 stage outputs live in the region the hi-res tensor would have used
-  const bool lowres_ok = precision == SG_PREC_BF16 && C % 64 == 0 && gh >= 2 && gw >= 2;
-  bf16_t* tok16 = (bf16_t*)p.hr;
-  bf16_t* o16[3];
-  {
-    size_t off = align_up((size_t)B * gh * gw * C * 2, 256);
-    for (int t = 0; t < 3; ++t) { o16[t] = (bf16_t*)((char*)p.hr + off); off += align_up((size_t)B * (gh << (t + 1)) * (gw << (t + 1)) * C * 2, 256); }
-  }
-  // exact tower mode: the same low-res formulation on two-plane f16 operands (jbu_conv_lowres_x2_kernel); its stage outputs (4 bytes per element)
-  // live where the hi-res tensor would have
-  const bool x2low_ok = precision == SG_PREC_F16X2 && C % 64 == 0 && gh >= 2 && gw >= 2;
-  h2_t* tok2 = (h2_t*)p.hr;
-  h2_t* o2[3];
-  {
-    size_t off = align_up((size_t)B * gh * gw * C * 4, 256);
-    for (int t = 0; t < 3; ++t) { o2[t] = (h2_t*)((char*)p.hr + off); off += align_up((size_t)B * (gh << (t + 1)) * (gw << (t + 1)) * C * 4, 256); }
-    // the 8x stage's output goes to the f32 path's 8x buffer (bufA: exactly pixels / 4 x C x 4 bytes, unused by this chain) instead: the hi-res
-    // region is then dead while the LAST stage runs, which writes the two-plane copy of x there for the final 1x1 GEMM -- no pack pass
-    o2[2] = (h2_t*)p.bufA;
-  }
-  if (x2_in_hr) *x2_in_hr = false;
-  for (int stg = 0; stg < 4; ++stg) {
-    const JbuStage& S = j->st[j->kind == 0 ? 0 : stg];
-    const int r = S.r, d = 2 * r + 1, d2 = d * d, oh = 2 * h, ow = 2 * w;
-    SG_REQUIRE(r < oh && r < ow, "sg_jbu_upsample: reflect padding %d needs a guidance grid larger than %dx%d", r, oh, ow);
-    SG_REQUIRE(d2 <= 128, "sg_jbu_upsample: window %d too large", d);
-    const int64_t pixels = (int64_t)B * oh * ow;
-    // ping-pong: source -> bufA (2x) -> bufB (4x) -> bufA (8x) -> bufB (16x)
-    float* dst = (stg % 2 == 0) ? p.bufA : p.bufB;
-    hipLaunchKernelGGL(jbu_pool_kernel, dim3((unsigned)cdiv(pixels * 3, 256)), dim3(256), 0, s, guidance, B, GH, GW, oh, ow, p.gs);
-    SG_LAUNCH_CHECK();
-    SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_GS, p.gs, (size_t)pixels * 3 * 4, s));
-    JbuStageRecord& R = g_jbu_rec.st[stg];
-    hipLaunchKernelGGL(jbu_range_proj_kernel, dim3((unsigned)cdiv(pixels, 256)), dim3(256), 0, s, p.gs, pixels, S.rp0_w, S.rp0_b, S.rp3_w,
-                       S.rp3_b, p.proj);
-    SG_LAUNCH_CHECK();
-    SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_PROJ, p.proj, (size_t)pixels * KEY_DIM * 4, s));
-    const bool fast = precision == SG_PREC_BF16 && C % 8 == 0;       // throughput mode: bf16 MFMA for the fixup linears and the convolution
-    const bool x2 = precision == SG_PREC_F16X2;                       // exact tower mode: f32 kernels, the three linears as two-plane f16 GEMMs (f32-grade, 3 f16 MFMAs per product)
-    const int NP = jbu_np(r), KP1 = jbu_kp1(r), ldk = (fast || x2) ? NP : d2;
-    // the low-res path (below) runs its fixup chain in f16 end to end: operand rows, GELU output, residual and the kernel rows the convolution
-    // converts to f16 anyway -- 3040 -> 1792 bytes of HBM traffic per pixel and stage, and f16's 11 bits in place of bf16's 8 on the way
-    const bool h16 = fast && (r == 5 || r == 3) && lowres_ok;
-    {
-      const int WT = AC_T + 2 * r;
-      const size_t lds = (size_t)WT * WT * JK_LD * sizeof(float);
-      SG_REQUIRE(lds <= 64 * 1024, "sg_jbu_upsample: window %d too large", d);
-      using JK = void (*)(const float*, const float*, int, int, int, const float*, const float*, float*, bf16_t*, int);
-      const JK jk = fast ? (r == 5 ? jbu_kernel_tiled_kernel<5, true> : r == 3 ? jbu_kernel_tiled_kernel<3, true> : jbu_kernel_tiled_kernel<0, true>)
-                         : jbu_kernel_tiled_kernel<0, false>;
-      const char* jk_name = fast ? (r == 5 ? "jbu_kernel_tiled_kernel<5,true>" : r == 3 ? "jbu_kernel_tiled_kernel<3,true>" : "jbu_kernel_tiled_kernel<0,true>")
-                                 : "jbu_kernel_tiled_kernel<0,false>";
-      if (x2 && (r == 5 || r == 3)) {                       // exact mode: two-plane keys, exact arithmetic, two-plane operand rows written directly
-        const dim3 grid((unsigned)(cdiv(oh, AC_T) * cdiv(ow, AC_T)), (unsigned)B);
-        constexpr size_t lds5 = JkmCfg<5, true>::LDS, lds3 = JkmCfg<3, true>::LDS;
-        if (r == 5) {
-          SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_kernel_mfma_kernel<5, true>), lds5));
-          hipLaunchKernelGGL((jbu_kernel_mfma_kernel<5, true>), grid, dim3(256), lds5, s, p.proj, p.gs, oh, ow, S.range_temp, S.sigma, p.X, p.X16, KP1, 0);
-          R.range = "jbu_kernel_mfma_kernel<5,true>";
-        } else {
-          SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_kernel_mfma_kernel<3, true>), lds3));
-          hipLaunchKernelGGL((jbu_kernel_mfma_kernel<3, true>), grid, dim3(256), lds3, s, p.proj, p.gs, oh, ow, S.range_temp, S.sigma, p.X, p.X16, KP1, 0);
-          R.range = "jbu_kernel_mfma_kernel<3,true>";
-        }
-        R.x16 = "h2";
-      } else if (fast && (r == 5 || r == 3)) {               // key dot products on the matrix pipe
-        const dim3 grid((unsigned)(cdiv(oh, AC_T) * cdiv(ow, AC_T)), (unsigned)B);
-        if (r == 5) {
-          SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_kernel_mfma_kernel<5>), JkmCfg<5>::LDS));
-          hipLaunchKernelGGL(jbu_kernel_mfma_kernel<5>, grid, dim3(256), JkmCfg<5>::LDS, s, p.proj, p.gs, oh, ow, S.range_temp, S.sigma, p.X, p.X16, KP1, h16 ? 1 : 0);
-          R.range = "jbu_kernel_mfma_kernel<5,false>";
-        } else {
-          SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_kernel_mfma_kernel<3>), JkmCfg<3>::LDS));
-          hipLaunchKernelGGL(jbu_kernel_mfma_kernel<3>, grid, dim3(256), JkmCfg<3>::LDS, s, p.proj, p.gs, oh, ow, S.range_temp, S.sigma, p.X, p.X16, KP1, h16 ? 1 : 0);
-          R.range = "jbu_kernel_mfma_kernel<3,false>";
-        }
-        R.x16 = h16 ? "f16" : "bf16";
-      } else {
-      SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jk), 64 * 1024));
-      hipLaunchKernelGGL(jk, dim3((unsigned)(cdiv(oh, AC_T) * cdiv(ow, AC_T)), (unsigned)B), dim3(256), lds, s, p.proj, p.gs, oh,
-                         ow, r, S.range_temp, S.sigma, p.X, fast ? p.X16 : nullptr, KP1);
-      R.range = jk_name;
-      R.x16 = fast ? "bf16" : "none";
-      }
-      SG_LAUNCH_CHECK();
-      if (!h16) SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_X, p.X, (size_t)pixels * (d2 + 3) * 4, s));
-      if (x2 && (r == 5 || r == 3)) SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_X16, p.X16, (size_t)pixels * KP1 * 4, s));
-      if (fast) SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_X16, p.X16, (size_t)pixels * KP1 * 2, s));
-    }
-    SG_REQUIRE(pixels < (1ll << 31), "sg_jbu_upsample: too many pixels");
-    if (fast) {  // H1 = GELU(X . W0^T + b0) (bf16);  Kf = X[:, :d2] + 0.1 * (H1 . W3^T + b3), columns >= d2 are padding
-      GemmBf16Args g{};
-      g.A = p.X16; g.lda = KP1; g.W = (const bf16_t*)(h16 ? S.fx0_w16h : S.fx0_w16); g.ldw = KP1; g.bias = S.fx0_bp; g.C = p.H116; g.ldc = NP; g.c_is_bf16 = 1;
-      g.M = (int)pixels; g.N = NP; g.K = KP1; g.batch = 1; g.act = ACT_GELU; g.alpha = 1.f; g.f16 = h16 ? 1 : 0;
-      SG_TRY(gemm_bf16(g, s));
-      R.fixup0 = gemm_last_family();
-      SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_H1, p.H116, (size_t)pixels * NP * 2, s));
-      GemmBf16Args q{};
-      q.A = p.H116; q.lda = NP; q.W = (const bf16_t*)(h16 ? S.fx3_w16h : S.fx3_w16); q.ldw = NP; q.bias = S.fx3_bp;
-      q.C = p.Kf; q.ldc = NP; q.M = (int)pixels; q.N = NP; q.K = NP; q.batch = 1; q.act = ACT_NONE; q.alpha = 0.1f;
-      if (h16) { q.residual = reinterpret_cast<const float*>(p.X16); q.ldr = KP1; q.res_half = 1; q.c_is_bf16 = 1; q.f16 = 1; }   // Kf rows in f16, residual = the operand rows
-      else { q.residual = p.X; q.ldr = d2 + 3; q.c_is_bf16 = 0; }
-      SG_TRY(gemm_bf16(q, s));
-      R.fixup1 = gemm_last_family(); R.kf = h16 ? "f16" : "f32";
-      SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_KF, p.Kf, (size_t)pixels * NP * (h16 ? 2 : 4), s));
-    } else if (x2) {  // the same two linears on the two-plane GEMM: X rows packed to [KP1] two-plane, GELU output two-plane, Kf f32 rows of NP
-      if (!(r == 5 || r == 3)) SG_TRY(pack_rows(p.X, pixels, d2 + 3, d2 + 3, p.X16, KP1, HK_F16X2, s));   // (r = 3 / 5: the range kernel wrote the two-plane rows itself)
-      GemmBf16Args g{};
-      g.A = p.X16; g.lda = KP1; g.W = (const bf16_t*)S.fx0_wh2; g.ldw = KP1; g.bias = S.fx0_bp; g.C = p.H116; g.ldc = NP; g.c_is_bf16 = 1;
-      g.M = (int)pixels; g.N = NP; g.K = KP1; g.batch = 1; g.act = ACT_GELU; g.alpha = 1.f; g.h2 = 1;
-      SG_TRY(gemm_bf16(g, s));
-      R.fixup0 = gemm_last_family();
-      SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_H1, p.H116, (size_t)pixels * NP * 4, s));
-      GemmBf16Args q{};
-      q.A = p.H116; q.lda = NP; q.W = (const bf16_t*)S.fx3_wh2; q.ldw = NP; q.bias = S.fx3_bp; q.residual = p.X; q.ldr = d2 + 3;
-      q.C = p.Kf; q.ldc = NP; q.c_is_bf16 = 0; q.M = (int)pixels; q.N = NP; q.K = NP; q.batch = 1; q.act = ACT_NONE; q.alpha = 0.1f; q.h2 = 1;
-      SG_TRY(gemm_bf16(q, s));
-      R.fixup1 = gemm_last_family(); R.kf = "f32";
-      SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_KF, p.Kf, (size_t)pixels * NP * 4, s));
-    } else {  // fixup: H1 = GELU(X . W0^T + b0);  Kf = X[:, :d2] + 0.1 * (H1 . W3^T + b3)
-      GemmF32Args g{};
-      g.A = p.X; g.lda = d2 + 3; g.B = S.fx0_w; g.sbk = 1; g.sbn = d2 + 3; g.bias = S.fx0_b; g.C = p.H1; g.ldc = d2;
-      g.M = (int)pixels; g.N = d2; g.K = d2 + 3; g.batch = 1; g.inner = 1; g.act = ACT_GELU; g.alpha = 1.f;
-      SG_TRY(gemm_f32(g, s));
-      R.fixup0 = "gemm_f32";
-      SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_H1, p.H1, (size_t)pixels * d2 * 4, s));
-      GemmF32Args q{};
-      q.A = p.H1; q.lda = d2; q.B = S.fx3_w; q.sbk = 1; q.sbn = d2; q.bias = S.fx3_b; q.residual = p.X; q.ldr = d2 + 3; q.C = p.Kf; q.ldc = d2;
-      q.M = (int)pixels; q.N = d2; q.K = d2; q.batch = 1; q.inner = 1; q.act = ACT_NONE; q.alpha = 0.1f;
-      SG_TRY(gemm_f32(q, s));
-      R.fixup1 = "gemm_f32"; R.kf = "f32";
-      SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_KF, p.Kf, (size_t)pixels * d2 * 4, s));
-    }
-    if (x2 && x2low_ok && (r == 5 || r == 3)) {
-      const h2_t* s2 = stg == 0 ? tok2 : o2[stg - 1];
-      if (stg == 0) SG_TRY(pack_rows(source, (int64_t)B * gh * gw, C, C, tok2, C, HK_F16X2, s));
-      h2_t* d2 = stg == 3 ? (x2_in_hr ? (h2_t*)p.hr : nullptr) : o2[stg];
-      float* d32 = stg == 3 ? dst : nullptr;
-      if (stg == 3 && x2_in_hr) *x2_in_hr = true;
-      dim3 grid((unsigned)(cdiv(oh, AC_T) * cdiv(ow, AC_T)), (unsigned)B);
-      SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_SRC, s2, (size_t)B * h * w * C * 4, s));
-      R.src = "h2"; R.bicubic = "none"; R.hr = "none"; R.out16 = d2 ? "h2" : "none";
-      R.grid[0] = grid.x; R.grid[1] = grid.y; R.grid[2] = grid.z;
-      if (r == 5) {
-        SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_conv_lowres_x2_kernel<5>), LowX2Cfg<5>::LDS));
-        hipLaunchKernelGGL(jbu_conv_lowres_x2_kernel<5>, grid, dim3(256), LowX2Cfg<5>::LDS, s, s2, p.Kf, ldk, h, w, C, d32, d2);
-        R.conv = "jbu_conv_lowres_x2_kernel<5>";
-      } else {
-        SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_conv_lowres_x2_kernel<3>), LowX2Cfg<3>::LDS));
-        hipLaunchKernelGGL(jbu_conv_lowres_x2_kernel<3>, grid, dim3(256), LowX2Cfg<3>::LDS, s, s2, p.Kf, ldk, h, w, C, d32, d2);
-        R.conv = "jbu_conv_lowres_x2_kernel<3>";
-      }
-      SG_LAUNCH_CHECK();
-      if (d32) SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_OUT, d32, (size_t)pixels * C * 4, s));
-      if (d2) SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_OUT16, d2, (size_t)pixels * C * 4, s));
-      src = dst; h = oh; w = ow;
-      continue;
-    }
-    const bool mfma_conv = fast;
-    const bool lowres = fast && (r == 5 || r == 3) && lowres_ok;   // bicubic folded into the per-pixel kernel: no hi-res tensor at all
-    if (lowres) {
-      // bf16 chain: tokens -> o16[0] (2x) -> o16[1] (4x) -> o16[2] (8x) -> x16 (16x); f32 only out of the last stage
-      bf16_t* s16 = stg == 0 ? tok16 : o16[stg - 1];
-      if (stg == 0) SG_TRY(pack_rows(source, (int64_t)B * gh * gw, C, C, tok16, C, 1, s));
-      bf16_t* d16 = stg == 3 ? (bf16_t*)p.x16 : o16[stg];
-      float* d32 = (stg == 3 && want_f32_x) ? dst : nullptr;   // the fused tail works from the bf16 copy alone: 4 B per element not written
-      dim3 grid((unsigned)(cdiv(oh, AC_T) * cdiv(ow, AC_T)), (unsigned)B);
-      SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_SRC, s16, (size_t)B * h * w * C * 2, s));
-      R.src = "bf16"; R.bicubic = "none"; R.hr = "none"; R.out16 = "bf16";
-      R.grid[0] = grid.x; R.grid[1] = grid.y; R.grid[2] = grid.z;
-      if (r == 5) {
-        SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_conv_lowres_kernel<5>), LowCfg<5>::LDS));
-        hipLaunchKernelGGL(jbu_conv_lowres_kernel<5>, grid, dim3(256), LowCfg<5>::LDS, s, s16, p.Kf, ldk, h, w, C, d32, d16, h16 ? 1 : 0);
-        R.conv = "jbu_conv_lowres_kernel<5>";
-      } else {
-        SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_conv_lowres_kernel<3>), LowCfg<3>::LDS));
-        hipLaunchKernelGGL(jbu_conv_lowres_kernel<3>, grid, dim3(256), LowCfg<3>::LDS, s, s16, p.Kf, ldk, h, w, C, d32, d16, h16 ? 1 : 0);
-        R.conv = "jbu_conv_lowres_kernel<3>";
-      }
-      SG_LAUNCH_CHECK();
-      if (d32) SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_OUT, d32, (size_t)pixels * C * 4, s));
-      SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_OUT16, d16, (size_t)pixels * C * 2, s));
-      src = dst; h = oh; w = ow;
-      continue;
-    }
-    SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_SRC, src, (size_t)B * h * w * C * 4, s));
-    R.src = "f32";
-    if (mfma_conv) {
-      hipLaunchKernelGGL(jbu_bicubic_kernel<bf16_t>, dim3((unsigned)cdiv(pixels * (C / 4), 256)), dim3(256), 0, s, src, B, h, w, C, oh, ow, (bf16_t*)p.hr);
-      R.bicubic = "jbu_bicubic_kernel<bf16_t>"; R.hr = "bf16";
-    } else {
-      hipLaunchKernelGGL(jbu_bicubic_kernel<float>, dim3((unsigned)cdiv(pixels * (C / 4), 256)), dim3(256), 0, s, src, B, h, w, C, oh, ow, p.hr);
-      R.bicubic = "jbu_bicubic_kernel<float>"; R.hr = "f32";
-    }
-    SG_LAUNCH_CHECK();
-    SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_HR, p.hr, (size_t)pixels * C * (mfma_conv ? 2 : 4), s));
-    if (mfma_conv) {                                         // throughput mode: the matrix-core formulation
-      const int WT = AC_T + 2 * r, KP = (int)align_up((size_t)WT * WT, 32);
-      const size_t lds = (size_t)(64 + ACM_CC) * (KP + 8) * sizeof(bf16_t);
-      SG_REQUIRE(lds <= 160 * 1024, "sg_jbu_upsample: window %d needs %zu bytes of LDS", d, lds);
-      SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_adaptive_conv_mfma_kernel), 160 * 1024));
-      dim3 grid((unsigned)(cdiv(oh, AC_T) * cdiv(ow, AC_T)), (unsigned)B);
-      bf16_t* o16c = (stg == 3 && C % 64 == 0) ? (bf16_t*)p.x16 : nullptr;
-      hipLaunchKernelGGL(jbu_adaptive_conv_mfma_kernel, grid, dim3(256), lds, s, (const bf16_t*)p.hr, p.Kf, ldk, oh, ow, C, r, KP, dst, o16c);
-      SG_LAUNCH_CHECK();
-      R.conv = "jbu_adaptive_conv_mfma_kernel"; R.out16 = o16c ? "bf16" : "none";
-      R.grid[0] = grid.x; R.grid[1] = grid.y; R.grid[2] = grid.z;
-      if (o16c) SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_OUT16, o16c, (size_t)pixels * C * 2, s));
-    } else {
-      const int WT = AC_T + 2 * r;
-      const size_t lds = ((size_t)WT * WT * AC_LD + (size_t)d2 * 64) * sizeof(float);
-      if (lds > 48 * 1024) SG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(jbu_adaptive_conv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      dim3 grid((unsigned)(cdiv(oh, AC_T) * cdiv(ow, AC_T)), (unsigned)cdiv(C, AC_CC), (unsigned)B);
-      hipLaunchKernelGGL(jbu_adaptive_conv_kernel, grid, dim3(256), lds, s, p.hr, p.Kf, ldk, oh, ow, C, r, dst);
-      SG_LAUNCH_CHECK();
-      R.conv = "jbu_adaptive_conv_kernel"; R.out16 = "none";
-      R.grid[0] = grid.x; R.grid[1] = grid.y; R.grid[2] = grid.z;
-    }
-    SG_TRY(jbu_cap(j, stg, SG_JBU_CAP_OUT, dst, (size_t)pixels * C * 4, s));
-    src = dst; h = oh; w = ow;
-  }
-  *x_out = src;
-  return SG_OK;
-}
-
-// source [B, gh*gw, C] (patch tokens), guidance [B,3,GH,GW] (the normalised, padded tile) -> out [B, (16gh*16gw), C]
-extern "C" int sg_jbu_upsample(sg_jbu* j, const float* source, const float* guidance, int B, int gh, int gw, int GH, int GW, int precision,
-                               float* out, void* ws, size_t ws_bytes, sg_stream st) {
-  SG_REQUIRE(j && source && guidance && out, "sg_jbu_upsample: null argument");
-  if (j->kind == SG_JBU_BILINEAR) {
-    SG_REQUIRE(B > 0 && gh > 0 && gw > 0 && GH > 0 && GW > 0, "sg_jbu_upsample: bad shape");
-    DeviceGuard dg(j->device);
-    return bilinear_upsample(j, source, B, gh, gw, GH, GW, out, as_stream(st));
-  }
-  if (j->kind == SG_JBU_RESIZE_CONV) {
-    SG_REQUIRE(ws && B > 0 && gh > 0 && gw > 0 && GH > 0 && GW > 0, "sg_jbu_upsample: bad arguments");
-    for (size_t i = 0; i < j->have.size(); ++i) if (!j->have[i]) return fail(SG_ERR_STATE, "sg_jbu_upsample: upsampler weights incomplete");
-    DeviceGuard dg(j->device);
-    return resize_conv_upsample(j, source, guidance, B, gh, gw, GH, GW, precision, out, ws, ws_bytes, as_stream(st));
-  }
-  SG_REQUIRE(ws, "sg_jbu_upsample: null argument");
-  for (size_t i = 0; i < j->have.size(); ++i) if (!j->have[i]) return fail(SG_ERR_STATE, "sg_jbu_upsample: upsampler weights incomplete");
-  DeviceGuard dg(j->device);
-  hipStream_t s = as_stream(st);
-  JbuPlan p;
-  const size_t need = jbu_plan(j, B, gh, gw, ws, false, p);
-  if (need > ws_bytes) return fail(SG_ERR_STATE, "sg_jbu_upsample: workspace %zu < required %zu", ws_bytes, need);
-  const int C = j->C;
-  const float* src = nullptr;
-  bool x2_ready = false;
-  jbu_rec_start();
-  jbu_cap_reset(j);
-  SG_TRY(jbu_stages(j, source, guidance, B, gh, gw, GH, GW, precision, p, &src, s, true, &x2_ready));
-  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_FIN_RES, src, (size_t)B * 256 * gh * gw * C * 4, s));
-  // out = x + 0.1 * (x . Wf^T + bf)     (bias pre-scaled by 0.1 at load)
-  const int64_t pixels = (int64_t)B * 16 * gh * 16 * gw;
-  if (precision == SG_PREC_BF16 && C % 64 == 0) {
-    if (C % 8 != 0) SG_TRY(pack_rows(src, pixels, C, C, p.x16, C, 1, s));    // (C % 64 == 0 implies the matrix-core conv wrote x16 already)
-    GemmBf16Args g{};
-    g.A = (const bf16_t*)p.x16; g.lda = C; g.W = (const bf16_t*)j->fin_w16; g.ldw = C; g.bias = j->fin_b; g.residual = src; g.ldr = C;
-    g.C = out; g.ldc = C; g.c_is_bf16 = 0; g.M = (int)pixels; g.N = C; g.K = C; g.batch = 1; g.act = 0; g.alpha = 0.1f;
-    SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_FIN_A, p.x16, (size_t)pixels * C * 2, s));
-    SG_TRY(gemm_bf16(g, s));
-    g_jbu_rec.fin = gemm_last_family(); g_jbu_rec.fin_a = "bf16";
-    return SG_OK;
-  }
-  if (precision == SG_PREC_F16X2 && C % 32 == 0 && pixels >= 1024) {   // exact tower mode: x packed to two-plane f16 (the hi-res scratch is free by now), f32-grade GEMM
-    if (!x2_ready) SG_TRY(pack_rows(src, pixels, C, C, p.hr, C, HK_F16X2, s));   // (the two-plane low-res convolution wrote this copy itself)
-    GemmBf16Args g{};
-    g.A = (const bf16_t*)p.hr; g.lda = C; g.W = (const bf16_t*)j->fin_wh2; g.ldw = C; g.bias = j->fin_b; g.residual = src; g.ldr = C;
-    g.C = out; g.ldc = C; g.c_is_bf16 = 0; g.M = (int)pixels; g.N = C; g.K = C; g.batch = 1; g.act = 0; g.alpha = 0.1f; g.h2 = 1;
-    SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_FIN_A, p.hr, (size_t)pixels * C * 4, s));
-    SG_TRY(gemm_bf16(g, s));
-    g_jbu_rec.fin = gemm_last_family(); g_jbu_rec.fin_a = "h2";
-    return SG_OK;
-  }
-  GemmF32Args g{};
-  g.A = src; g.lda = C; g.B = j->fin_w; g.sbk = 1; g.sbn = C; g.bias = j->fin_b; g.residual = src; g.ldr = C; g.C = out; g.ldc = C;
-  g.M = (int)pixels; g.N = C; g.K = C; g.batch = 1; g.inner = 1; g.act = 0; g.alpha = 0.1f;
-  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_FIN_A, src, (size_t)pixels * C * 4, s));
-  SG_TRY(gemm_f32(g, s));
-  g_jbu_rec.fin = "gemm_f32"; g_jbu_rec.fin_a = "f32";
-  return SG_OK;
-}
-
 // ---- fused tail (throughput mode): per-pixel class logits WITHOUT writing the C x S^2 feature map ---------------------------------
 // reference: out = x + 0.1 * fixup_proj(x) (upsamplers.py:301,325); feats /= |feats|; logits = feats . T^T (+ lambda * cls_logits)
 // (segmentor.py:374-379).  With z = 0.1 * (x Wf^T + bf):
 //     out . T[q]  = x . (T[q] + 0.1 Wf^T T[q]) + 0.1 bf . T[q]  =  x . Geff[:, q] + g0[q]          (f32, no GEMM: Q <= 32)
 //     |out|^2     = |x|^2 + sum_c z (2 x + z)                                                       (the GEMM's row-dot epilogue)
 // so the only C x C GEMM keeps its result in registers and HBM sees x once more (f32) plus Q floats per pixel.
-namespace sg {
 __global__ __launch_bounds__(256) void jbu_geff_kernel(const float* __restrict__ text, const float* __restrict__ Wf, const float* __restrict__ bf01,
                                                        int C, int Q, float* __restrict__ geff, float* __restrict__ g0) {
   // block = 64 channels x 4 K-quarters (one per wave): Wf[k][c] reads are coalesced over c, 8 independent partial sums per thread
@@ -1923,80 +1326,8 @@ __global__ __launch_bounds__(256, 2) void jbu_pixel_logits_mfma_kernel(const bf1
     __builtin_amdgcn_wave_barrier();                                      // myN is rewritten in the next round
   }
 }
-}  // namespace sg
 
-// sg_jbu_logits replaces, for a batch of tiles,  feats = upsampler(tokens, img) -> feats /= |feats| -> feats @ T^T (+ lambda * cls_logits)
-// (segmentor.py:368-379) without materialising the [S^2, C] feature map (throughput mode; SURVEY.md §7 step 7).
-extern "C" int sg_jbu_logits(sg_jbu* j, const float* source, const float* guidance, int B, int gh, int gw, int GH, int GW, int precision,
-                             const float* text, int Q, const float* cls, float cls_token_lambda, float* logits, void* ws, size_t ws_bytes,
-                             sg_stream st) {
-  SG_REQUIRE(j && source && guidance && text && logits && ws, "sg_jbu_logits: null argument");
-  SG_REQUIRE(Q >= 1 && Q <= JBU_QMAX, "sg_jbu_logits: 1 <= Q <= %d", JBU_QMAX);
-  if (j->kind == SG_JBU_BILINEAR) {                       // every precision: the bilinear logits are f32 arithmetic throughout
-    SG_REQUIRE(B > 0 && gh > 0 && gw > 0 && GH > 0 && GW > 0, "sg_jbu_logits: bad shape");
-    DeviceGuard dg(j->device);
-    return bilinear_logits(j, source, B, gh, gw, GH, GW, text, Q, cls, cls_token_lambda, logits, ws, ws_bytes, as_stream(st));
-  }
-  if (j->kind == SG_JBU_RESIZE_CONV)
-    return fail(SG_ERR_INVALID, "sg_jbu_logits: resize_conv has no fused logits tail; use sg_jbu_upsample + sg_cosine_logits");
-  SG_REQUIRE(precision == SG_PREC_BF16 && j->C % 64 == 0 && j->C >= 512, "sg_jbu_logits: the fused tail is the bf16 throughput path (C %% 64 == 0, C >= 512); use sg_jbu_upsample + sg_cosine_logits otherwise");
-  for (size_t i = 0; i < j->have.size(); ++i) if (!j->have[i]) return fail(SG_ERR_STATE, "sg_jbu_logits: upsampler weights incomplete");
-  DeviceGuard dg(j->device);
-  hipStream_t s = as_stream(st);
-  JbuPlan p;
-  const size_t need = jbu_plan(j, B, gh, gw, ws, false, p);
-  if (need > ws_bytes) return fail(SG_ERR_STATE, "sg_jbu_logits: workspace %zu < required %zu", ws_bytes, need);
-  const int C = j->C;
-  const int64_t P = (int64_t)16 * gh * 16 * gw, pixels = (int64_t)B * P;
-  SG_REQUIRE(pixels >= 1024 && pixels < (1ll << 31), "sg_jbu_logits: pixel count out of range");
-  const float* x = nullptr;
-  jbu_rec_start();
-  jbu_cap_reset(j);
-  SG_TRY(jbu_stages(j, source, guidance, B, gh, gw, GH, GW, precision, p, &x, s, /*want_f32_x=*/false));
-  const bf16_t* x16 = (const bf16_t*)p.x16;                 // the 16x features exist in bf16 only: the conv's 4 B/element f32 store and its two re-reads are gone
-  hipLaunchKernelGGL(jbu_geff_kernel, dim3((unsigned)cdiv(C, 64), (unsigned)Q), dim3(256), 0, s, text, j->fin_w, j->fin_b, C, Q, p.geff, p.g0);
-  SG_LAUNCH_CHECK();
-  g_jbu_rec.geff = "jbu_geff_kernel";
-  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_GEFF, p.geff, (size_t)C * JBU_QMAX * 4, s));
-  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_G0, p.g0, (size_t)JBU_QMAX * 4, s));
-  const bool use_cls = cls != nullptr && cls_token_lambda != 0.f;
-  if (use_cls) {
-    hipLaunchKernelGGL(jbu_cls_logits_kernel, dim3(B), dim3(64), 0, s, cls, text, C, Q, p.clsl);
-    SG_LAUNCH_CHECK();
-    g_jbu_rec.cls = "jbu_cls_logits_kernel";
-    SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_CLSL, p.clsl, (size_t)B * JBU_QMAX * 4, s));
-  }
-  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_FIN_A, x16, (size_t)pixels * C * 2, s));
-  GemmBf16Args g{};
-  g.A = x16; g.lda = C; g.W = (const bf16_t*)j->fin_w16; g.ldw = C; g.bias = j->fin_b; g.residual = (const float*)x16; g.ldr = C;
-  g.C = p.rowdot; g.ldc = C; g.c_is_bf16 = 0; g.M = (int)pixels; g.N = C; g.K = C; g.batch = 1; g.act = 0; g.alpha = 0.1f;
-  g.rowdot = p.rowdot; g.rowdot_ld = C / 64; g.rowdot_res_bf16 = 1;
-  SG_TRY(gemm_bf16(g, s));
-  const int slots = C / 64;
-  g_jbu_rec.fin = gemm_last_family(); g_jbu_rec.fin_a = "bf16";
-  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_ROWDOT, p.rowdot, (size_t)pixels * slots * 4, s));
-  const unsigned grid = (unsigned)cdiv(pixels, 4 * 64 * PL_PPL);
-#define SG_JBU_PIX(QP)                                                                                                        \
-  do {                                                                                                                         \
-    const size_t lds = ((size_t)C * QP + 4 * 64 * PL_PPL * PL_LD) * sizeof(float);                                             \
-    if (lds > 48 * 1024) SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_pixel_logits_kernel<QP, bf16_t>), lds)); \
-    hipLaunchKernelGGL((jbu_pixel_logits_kernel<QP, bf16_t>), dim3(grid), dim3(256), lds, s, x16, p.rowdot, slots, p.geff, p.g0,  \
-                       use_cls ? p.clsl : nullptr, cls_token_lambda, pixels, P, C, Q, logits);                                 \
-    g_jbu_rec.pix = "jbu_pixel_logits_kernel<" #QP ">";                                                                      \
-  } while (0)
-  if (Q <= 16 && C % 32 == 0) {                              // matrix-pipe form
-    const size_t lds = (size_t)2 * 16 * (C + 8) * sizeof(bf16_t) + 4 * 64 * sizeof(float);
-    SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_pixel_logits_mfma_kernel), lds));
-    hipLaunchKernelGGL(jbu_pixel_logits_mfma_kernel, dim3((unsigned)cdiv(pixels, 4 * 64 * PLM_ROUNDS)), dim3(256), lds, s, x16, p.rowdot, slots, p.geff, p.g0,
-                       use_cls ? p.clsl : nullptr, cls_token_lambda, pixels, P, C, Q, logits);
-    g_jbu_rec.pix = "jbu_pixel_logits_mfma_kernel";
-  } else if (Q <= 8) SG_JBU_PIX(8); else if (Q <= 16) SG_JBU_PIX(16); else SG_JBU_PIX(32);
-#undef SG_JBU_PIX
-  SG_LAUNCH_CHECK();
-  return SG_OK;
-}
-
-namespace sg {
+constexpr int BL_G = 8;                              // 5 Gram terms per token, rows padded to 32 bytes
 // ---- kind 2: Bilinear (upsamplers.py:343-350) -------------------------------------------------------------------------------------
 // The reference resizes the patch features to the tile (F.interpolate(feats, (H, W), mode='bilinear')), normalises every pixel and takes
 // its product with the text features.  By linearity the [GH*GW, C] feature map is never needed: a pixel p interpolates the four corners
@@ -2122,42 +1453,6 @@ __global__ __launch_bounds__(256) void bilinear_features_kernel(const float* __r
   }
 }
 
-static int bilinear_upsample(sg_jbu* j, const float* source, int B, int gh, int gw, int GH, int GW, float* out, hipStream_t s) {
-  const int64_t pixels = (int64_t)B * GH * GW;
-  SG_REQUIRE(cdiv(pixels, 4) < (1ll << 31), "sg_jbu_upsample: too many pixels");
-  jbu_rec_start();
-  jbu_cap_reset(j);
-  hipLaunchKernelGGL(bilinear_features_kernel, dim3((unsigned)cdiv(pixels, 4)), dim3(256), 0, s, source, B, gh, gw, GH, GW, j->C, out);
-  SG_LAUNCH_CHECK();
-  g_jbu_rec.fin = "bilinear_features_kernel";
-  return SG_OK;
-}
-
-static int bilinear_logits(sg_jbu* j, const float* source, int B, int gh, int gw, int GH, int GW, const float* text, int Q,
-                           const float* cls, float cls_token_lambda, float* logits, void* ws, size_t ws_bytes, hipStream_t s) {
-  BilinearPlan p;
-  const size_t need = bilinear_plan(B, gh, gw, ws, false, p);
-  if (need > ws_bytes) return fail(SG_ERR_STATE, "sg_jbu_logits: workspace %zu < required %zu", ws_bytes, need);
-  const int64_t tokens = (int64_t)B * gh * gw;
-  SG_REQUIRE(cdiv(tokens, 4) < (1ll << 31) && cdiv(GH, 4) < 65536 && B < 65536, "sg_jbu_logits: shape too large for one launch");
-  jbu_rec_start();
-  jbu_cap_reset(j);
-  hipLaunchKernelGGL(bilinear_prologue_kernel, dim3((unsigned)cdiv(tokens, 4)), dim3(256), 0, s, source, text, B, gh, gw, j->C, Q, p.y, p.gram);
-  SG_LAUNCH_CHECK();
-  g_jbu_rec.geff = "bilinear_prologue_kernel";
-  const bool use_cls = cls != nullptr && cls_token_lambda != 0.f;
-  if (use_cls) {
-    hipLaunchKernelGGL(jbu_cls_logits_kernel, dim3(B), dim3(64), 0, s, cls, text, j->C, Q, p.clsl);
-    SG_LAUNCH_CHECK();
-    g_jbu_rec.cls = "jbu_cls_logits_kernel";
-  }
-  hipLaunchKernelGGL(bilinear_pixel_logits_kernel, dim3((unsigned)cdiv(GW, 64), (unsigned)cdiv(GH, 4), (unsigned)B), dim3(256), 0, s, p.y,
-                     p.gram, use_cls ? p.clsl : nullptr, cls_token_lambda, gh, gw, GH, GW, Q, logits);
-  SG_LAUNCH_CHECK();
-  g_jbu_rec.pix = "bilinear_pixel_logits_kernel";
-  return SG_OK;
-}
-
 // ---- kind 3: LayeredResizeConv(dim, 1) (upsamplers.py:178-200) ---------------------------------------------------------------------
 // Per stage: big = bilinear x2 of the stage source (F.interpolate(scale_factor=2), align_corners=False), guid = the tile resized to big's
 // size (size-based, no antialias: at patch 14 the last stage upsamples it), out = act(conv1x1([big | guid])) + big.  The operand producer
@@ -2201,6 +1496,432 @@ __global__ __launch_bounds__(256) void resize_conv_operands_kernel(const float* 
   }
 }
 
+struct JbuStage {
+  int r;
+  float *range_temp, *sigma, *rp0_w, *rp0_b, *rp3_w, *rp3_b, *fx0_w, *fx0_b, *fx3_w, *fx3_b;
+  // throughput mode: the two fixup linears on the bf16 MFMA GEMM, operands zero-padded to [NP, KP1] / [NP, NP] (NP, KP1 multiples of 64)
+  void *fx0_w16, *fx3_w16; float *fx0_bp, *fx3_bp;
+  void *fx0_w16h, *fx3_w16h;                              // the same operands in f16: the all-2-byte fixup chain of the low-res path (round 3)
+  void *fx0_wh2, *fx3_wh2;                                // ... and as two-plane f16 (SG_PREC_F16X2: f32-grade linears on the f16 matrix pipe)
+};
+static inline int jbu_np(int r) { const int d = 2 * r + 1; return (int)align_up((size_t)d * d, 64); }
+static inline int jbu_kp1(int r) { const int d = 2 * r + 1; return (int)align_up((size_t)d * d + 3, 64); }
+static inline size_t rc_kp(int C) { return align_up((size_t)C + 3, 64); }
+
+}  // namespace sg
+
+using namespace sg;
+
+// ==== host side =======================================================================================================================
+struct sg_jbu {
+  int device, kind, C, n_stage_sets;
+  void* arena; size_t arena_bytes;
+  JbuStage st[4];
+  float *fin_w, *fin_b;
+  void* fin_w16;
+  void* fin_wh2;                                           // two-plane f16 copy of the final 1x1 weight (C % 32 == 0)
+  std::vector<uint8_t> have;
+  // kind 3 (resize_conv): conv{1..4} as f32 [C, C+3] (what the f32 GEMM reads) and packed [W_src | W_guid | 0] rows [C, KP] in bf16 and
+  // two-plane f16 (KP = align_up(C + 3, 64): the 2-byte GEMMs' K % 64 rule, the two-plane one's K % 32)
+  float *rc_w[4], *rc_b[4];
+  void *rc_w16[4], *rc_wh2[4];
+  sg_jbu_capture* cap = nullptr;                           // test instrumentation (sg_jbu_set_capture): copies of every kernel's operands
+};
+
+namespace sg {
+static const char* kStageTensor[10] = {"range_temp", "sigma_spatial", "range_proj.0.weight", "range_proj.0.bias", "range_proj.3.weight",
+                                       "range_proj.3.bias", "fixup_proj.0.weight", "fixup_proj.0.bias", "fixup_proj.3.weight",
+                                       "fixup_proj.3.bias"};
+static int64_t stage_numel(int slot, int r) {
+  const int64_t d2 = (int64_t)(2 * r + 1) * (2 * r + 1);
+  switch (slot) {
+    case 0: case 1: return 1;
+    case 2: return KEY_DIM * 3; case 3: return KEY_DIM; case 4: return KEY_DIM * KEY_DIM; case 5: return KEY_DIM;
+    case 6: return d2 * (d2 + 3); case 7: return d2; case 8: return d2 * d2; default: return d2;
+  }
+}
+
+struct JbuPlan { float *gs, *proj, *X, *H1, *Kf, *hr, *bufA, *bufB; void* x16; bf16_t *X16, *H116; float *rowdot, *geff, *g0, *clsl; };
+static size_t jbu_plan(const sg_jbu* j, int B, int gh, int gw, void* ws, bool dry, JbuPlan& p) {
+  const int r = j->st[0].r, d2 = (2 * r + 1) * (2 * r + 1);
+  const int64_t pixels = (int64_t)B * 16 * gh * 16 * gw;              // final resolution
+  Bump b(ws, 0, dry);
+  p.gs = (float*)b.take((size_t)pixels * 3 * 4);
+  p.proj = (float*)b.take((size_t)pixels * KEY_DIM * 4);
+  const int NP = jbu_np(r), KP1 = jbu_kp1(r);
+  p.X = (float*)b.take((size_t)pixels * (d2 + 3) * 4 + 1024);           // + slack: the padded fixup GEMM reads its residual NP columns wide
+  p.H1 = (float*)b.take((size_t)pixels * d2 * 4);
+  p.Kf = (float*)b.take((size_t)pixels * NP * 4);                       // row stride d2 (parity mode) or NP (throughput mode)
+  p.X16 = (bf16_t*)b.take((size_t)pixels * KP1 * 4);                      // 2-byte operand rows (throughput mode) or two-plane f16 ones (SG_PREC_F16X2: 4 bytes per element)
+  p.H116 = (bf16_t*)b.take((size_t)pixels * NP * 4);
+  p.hr = (float*)b.take((size_t)pixels * j->C * 4);
+  p.bufA = (float*)b.take((size_t)pixels / 4 * j->C * 4);                // stage-3 output (8x): ping
+  p.bufB = (float*)b.take((size_t)pixels * j->C * 4);                    // stage-2 / stage-4 output: pong
+  p.x16 = b.take((size_t)pixels * j->C * 2);
+  p.rowdot = (float*)b.take((size_t)pixels * (j->C / 64 + 1) * 4);       // fused tail: per-pixel partial |out|^2 - |x|^2, one slot per 64 columns
+  p.geff = (float*)b.take((size_t)j->C * JBU_QMAX * 4);
+  p.g0 = (float*)b.take((size_t)JBU_QMAX * 4);
+  p.clsl = (float*)b.take((size_t)B * JBU_QMAX * 4);
+  return align_up(b.off, 256);
+}
+// kind 2 (bilinear): the per-token prologue's outputs -- y = tokens . T^T [B*n, JBU_QMAX] and the Gram terms [B*n, BL_G] -- and the CLS logits
+struct BilinearPlan { float *y, *gram, *clsl; };
+static size_t bilinear_plan(int B, int gh, int gw, void* ws, bool dry, BilinearPlan& p) {
+  const size_t tokens = (size_t)B * gh * gw;
+  Bump b(ws, 0, dry);
+  p.y = (float*)b.take(tokens * JBU_QMAX * 4);
+  p.gram = (float*)b.take(tokens * BL_G * 4);
+  p.clsl = (float*)b.take((size_t)B * JBU_QMAX * 4);
+  return align_up(b.off, 256);
+}
+// kind 3 (resize_conv): per stage the bilinear x2 source [P, C] f32 (the GEMM's residual), the GEMM's A rows [P, KP] (4 bytes per element
+// at most) and the stage outputs of stages 1..3 (stage 4 writes the caller's output)
+struct ResizeConvPlan { float *big, *s1, *s2, *s3; void* a; };
+static size_t resize_conv_plan(int C, int B, int gh, int gw, void* ws, bool dry, ResizeConvPlan& p) {
+  const size_t n = (size_t)B * gh * gw;
+  Bump b(ws, 0, dry);
+  p.big = (float*)b.take(n * 256 * C * 4);
+  p.a = b.take(n * 256 * rc_kp(C) * 4);
+  p.s1 = (float*)b.take(n * 4 * C * 4);
+  p.s2 = (float*)b.take(n * 16 * C * 4);
+  p.s3 = (float*)b.take(n * 64 * C * 4);
+  return align_up(b.off, 256);
+}
+
+// The calling thread's last sg_jbu_upsample / sg_jbu_logits (sg_jbu_last_kernels): static names and grids stored in the branch that
+// launches each kernel, as gemm_bf16's record does; the text is made only when queried.
+struct JbuStageRecord { const char *range, *x16, *fixup0, *fixup1, *kf, *src, *bicubic, *hr, *conv, *out16; unsigned grid[3]; };
+struct JbuLaunchRecord { bool used; JbuStageRecord st[4]; const char *fin, *fin_a, *geff, *cls, *pix; };
+static thread_local JbuLaunchRecord g_jbu_rec = {};
+static void jbu_rec_start() { g_jbu_rec = {}; g_jbu_rec.used = true; }
+// capture (test instrumentation): copy `bytes` of `src` into the caller's slot on the call's stream; stage < 0 = a tail slot
+static int jbu_cap(sg_jbu* j, int stage, int slot, const void* src, size_t bytes, hipStream_t s) {
+  if (!j->cap) return SG_OK;
+  sg_jbu_capture_slot& c = stage < 0 ? j->cap->tail[slot] : j->cap->stage[stage][slot];
+  if (!c.dst) return SG_OK;
+  if (bytes > c.cap) return fail(SG_ERR_INVALID, "sg_jbu capture: stage %d slot %d needs %zu bytes, the buffer holds %zu", stage, slot, bytes, c.cap);
+  SG_HIP(hipMemcpyAsync(c.dst, src, bytes, hipMemcpyDeviceToDevice, s));
+  c.bytes = bytes;
+  return SG_OK;
+}
+static void jbu_cap_reset(sg_jbu* j) {
+  if (!j->cap) return;
+  for (auto& st : j->cap->stage) for (auto& c : st) c.bytes = 0;
+  for (auto& c : j->cap->tail) c.bytes = 0;
+}
+
+// One linear, C = act(alpha * A.W^T + bias) (+ residual), on operands stored as `fmt`: HK_F32 runs gemm_f32, HK_BF16 / HK_F16 / HK_F16X2
+// run gemm_bf16.  A [M, K] and W [N, K] are both in `fmt`; the residual [M, N] (or null) and C [M, N] are each f32 (HK_F32) or in `fmt`.
+// `rowdot` (persistent bf16 kernel only): the row-dot epilogue of the fused tail, one slot per 64 columns, in place of the store to C.
+// *family (if asked for) gets the kernel family that ran, for the launch record.
+static int jbu_linear(int fmt, const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, const void* residual, int64_t ldr,
+                      int res_fmt, void* C, int64_t ldc, int c_fmt, int64_t M, int N, int K, int act, float alpha, hipStream_t s,
+                      const char** family, float* rowdot = nullptr) {
+  if (fmt == HK_F32) {
+    GemmF32Args g{};
+    g.A = (const float*)A; g.lda = lda; g.B = (const float*)W; g.sbk = 1; g.sbn = ldw; g.bias = bias; g.residual = (const float*)residual; g.ldr = ldr;
+    g.C = (float*)C; g.ldc = ldc; g.M = (int)M; g.N = N; g.K = K; g.batch = 1; g.inner = 1; g.act = act; g.alpha = alpha;
+    SG_TRY(gemm_f32(g, s));
+    if (family) *family = "gemm_f32";
+    return SG_OK;
+  }
+  GemmBf16Args g{};
+  g.A = (const bf16_t*)A; g.lda = lda; g.W = (const bf16_t*)W; g.ldw = ldw; g.bias = bias; g.residual = (const float*)residual; g.ldr = ldr;
+  g.C = C; g.ldc = ldc; g.c_is_bf16 = c_fmt != HK_F32; g.M = (int)M; g.N = N; g.K = K; g.batch = 1; g.act = act; g.alpha = alpha;
+  g.f16 = fmt == HK_F16; g.h2 = fmt == HK_F16X2;
+  if (rowdot) { g.rowdot = rowdot; g.rowdot_ld = N / 64; g.rowdot_res_bf16 = res_fmt != HK_F32; }
+  else g.res_half = residual && res_fmt != HK_F32;
+  SG_TRY(gemm_bf16(g, s));
+  if (family) *family = gemm_last_family();
+  return SG_OK;
+}
+
+// The window radius is 5 (jbu_one) or 3 (jbu_stack), nothing else (sg_jbu_create; jbu_stages checks it): f(integral_constant<int, r>)
+template <typename F>
+static int with_radius(int r, F&& f) {
+  return r == 5 ? f(std::integral_constant<int, 5>{}) : f(std::integral_constant<int, 3>{});
+}
+
+// ---- the four 2x stages ---------------------------------------------------------------------------------------------------------------
+// A call runs ONE of five precision chains, chosen here from (precision, C) and nowhere else; the three steps of a stage switch on it.
+//   chain            range kernel (-> X / X16)                        fixup linears (-> Kf)                 convolution (-> stage output)
+//   JBU_F32          jbu_kernel_tiled_kernel<0,false>, f32 rows       gemm_f32 x2                           jbu_bicubic_kernel<float> + jbu_adaptive_conv_kernel
+//   JBU_BF16_HIRES   jbu_kernel_mfma_kernel<R,false>, + bf16 rows     bf16 GEMMs, f32 residual, f32 Kf      jbu_bicubic_kernel<bf16_t> + jbu_adaptive_conv_mfma_kernel
+//   JBU_BF16_LOWRES  jbu_kernel_mfma_kernel<R,false>, f16 rows only   f16 GEMMs, f16 residual, f16 Kf       jbu_conv_lowres_kernel<R> (bicubic folded in, bf16 stage outputs)
+//   JBU_H2_LOWRES    jbu_kernel_mfma_kernel<R,true>, + two-plane rows two-plane GEMMs, f32 residual and Kf  jbu_conv_lowres_x2_kernel<R> (two-plane stage outputs)
+//   JBU_H2_HIRES     as JBU_H2_LOWRES                                 as JBU_H2_LOWRES                      as JBU_F32
+enum JbuChain { JBU_F32, JBU_BF16_HIRES, JBU_BF16_LOWRES, JBU_H2_LOWRES, JBU_H2_HIRES };
+// (The low-res convolutions also need a token grid of 2 x 2 or more.  No extra clause: every chain refuses a smaller grid before its first
+// launch, because reflect padding needs r < 2 * gh and r < 2 * gw with r >= 3 -- the SG_REQUIRE at the top of the stage loop.)
+static JbuChain jbu_chain(int precision, int C) {
+  if (precision == SG_PREC_BF16 && C % 8 == 0) return C % 64 == 0 ? JBU_BF16_LOWRES : JBU_BF16_HIRES;   // throughput mode; C % 8 != 0: f32
+  if (precision == SG_PREC_F16X2) return C % 64 == 0 ? JBU_H2_LOWRES : JBU_H2_HIRES;                    // exact tower mode
+  return JBU_F32;
+}
+
+// What one jbu_stages call works with: the chain, where each stage reads and writes, and the stage the loop is at.
+struct JbuCall {
+  sg_jbu* j; const JbuPlan& p; hipStream_t s;
+  JbuChain chain;
+  int B, C;
+  const float* source;                 // the patch tokens [B, gh*gw, C] f32
+  bool want_f32_x;                     // JBU_BF16_LOWRES: also write the last stage's output in f32 (the fused tail works from the bf16 copy alone)
+  bool* x2_in_hr;                      // JBU_H2_LOWRES: if non-null, the last stage leaves a two-plane copy of its output in p.hr and sets *x2_in_hr
+  // the low-res chains keep no hi-res tensor; the region it would have used (p.hr) holds their 2-byte (JBU_BF16_LOWRES) / two-plane
+  // (JBU_H2_LOWRES) tokens and, behind them, the stage outputs: tokens (p.hr) -> lo[0] (2x) -> lo[1] (4x) -> lo[2] (8x) -> last stage
+  void* lo[3];
+  // the stage at hand (advanced by the loop in jbu_stages)
+  int stg, h, w;                       // stage 0..3 and its INPUT grid; it writes (2h, 2w)
+  const float* src;                    // f32 input of the stage (the hi-res chains read it)
+  const JbuStage& S() const { return j->st[j->kind == 0 ? 0 : stg]; }
+  int64_t pixels() const { return (int64_t)B * 2 * h * 2 * w; }
+  float* dst() const { return (stg % 2 == 0) ? p.bufA : p.bufB; }   // ping-pong: source -> bufA (2x) -> bufB (4x) -> bufA (8x) -> bufB (16x)
+};
+
+// range kernel: X = [K | guidance] rows (f32) and / or the fixup GEMM's operand rows X16
+static int jbu_range_step(const JbuCall& c) {
+  const JbuPlan& p = c.p;
+  const JbuStage& S = c.S();
+  const int r = S.r, d2 = (2 * r + 1) * (2 * r + 1), oh = 2 * c.h, ow = 2 * c.w, KP1 = jbu_kp1(r);
+  const int64_t pixels = c.pixels();
+  JbuStageRecord& R = g_jbu_rec.st[c.stg];
+  const dim3 grid((unsigned)(cdiv(oh, AC_T) * cdiv(ow, AC_T)), (unsigned)c.B);
+  switch (c.chain) {
+    case JBU_F32: {
+      const int WT = AC_T + 2 * r;
+      const size_t lds = (size_t)WT * WT * JK_LD * sizeof(float);
+      SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_kernel_tiled_kernel<0, false>), 64 * 1024));
+      hipLaunchKernelGGL((jbu_kernel_tiled_kernel<0, false>), grid, dim3(256), lds, c.s, p.proj, p.gs, oh, ow, r, S.range_temp, S.sigma, p.X,
+                         (bf16_t*)nullptr, KP1);
+      R.range = "jbu_kernel_tiled_kernel<0,false>"; R.x16 = "none";
+      break;
+    }
+    case JBU_BF16_HIRES: case JBU_BF16_LOWRES: {           // key dot products on the matrix pipe
+      // the low-res chain runs its fixup linears in f16 end to end: operand rows, GELU output, residual and the kernel rows the convolution
+      // converts to f16 anyway -- 3040 -> 1792 bytes of HBM traffic per pixel and stage, and f16's 11 bits in place of bf16's 8 on the way
+      const int rows_f16 = c.chain == JBU_BF16_LOWRES ? 1 : 0;
+      SG_TRY(with_radius(r, [&](auto rc) {
+        constexpr int RR = decltype(rc)::value;
+        SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_kernel_mfma_kernel<RR>), JkmCfg<RR>::LDS));
+        hipLaunchKernelGGL(jbu_kernel_mfma_kernel<RR>, grid, dim3(256), JkmCfg<RR>::LDS, c.s, p.proj, p.gs, oh, ow, S.range_temp, S.sigma, p.X, p.X16, KP1, rows_f16);
+        R.range = RR == 5 ? "jbu_kernel_mfma_kernel<5,false>" : "jbu_kernel_mfma_kernel<3,false>";
+        return (int)SG_OK;
+      }));
+      R.x16 = rows_f16 ? "f16" : "bf16";
+      break;
+    }
+    case JBU_H2_LOWRES: case JBU_H2_HIRES:                 // exact mode: two-plane keys, exact arithmetic, two-plane operand rows written directly
+      SG_TRY(with_radius(r, [&](auto rc) {
+        constexpr int RR = decltype(rc)::value;
+        constexpr size_t lds = JkmCfg<RR, true>::LDS;
+        SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_kernel_mfma_kernel<RR, true>), lds));
+        hipLaunchKernelGGL((jbu_kernel_mfma_kernel<RR, true>), grid, dim3(256), lds, c.s, p.proj, p.gs, oh, ow, S.range_temp, S.sigma, p.X, p.X16, KP1, 0);
+        R.range = RR == 5 ? "jbu_kernel_mfma_kernel<5,true>" : "jbu_kernel_mfma_kernel<3,true>";
+        return (int)SG_OK;
+      }));
+      R.x16 = "h2";
+      break;
+  }
+  SG_LAUNCH_CHECK();
+  if (c.chain != JBU_BF16_LOWRES) SG_TRY(jbu_cap(c.j, c.stg, SG_JBU_CAP_X, p.X, (size_t)pixels * (d2 + 3) * 4, c.s));
+  if (c.chain != JBU_F32)
+    SG_TRY(jbu_cap(c.j, c.stg, SG_JBU_CAP_X16, p.X16, (size_t)pixels * KP1 * (c.chain == JBU_H2_LOWRES || c.chain == JBU_H2_HIRES ? 4 : 2), c.s));
+  return SG_OK;
+}
+
+// fixup: H1 = GELU(X . W0^T + b0);  Kf = X[:, :d2] + 0.1 * (H1 . W3^T + b3)   (b3 pre-scaled by 0.1 at load)
+static int jbu_fixup_step(const JbuCall& c) {
+  const JbuPlan& p = c.p;
+  const JbuStage& S = c.S();
+  const int r = S.r, d2 = (2 * r + 1) * (2 * r + 1);
+  const int64_t pixels = c.pixels();
+  JbuStageRecord& R = g_jbu_rec.st[c.stg];
+  SG_REQUIRE(pixels < (1ll << 31), "sg_jbu_upsample: too many pixels");
+  if (c.chain == JBU_F32) {                                 // rows of d2 (+3), unpadded
+    SG_TRY(jbu_linear(HK_F32, p.X, d2 + 3, S.fx0_w, d2 + 3, S.fx0_b, nullptr, 0, HK_F32, p.H1, d2, HK_F32, pixels, d2, d2 + 3, ACT_GELU, 1.f, c.s, &R.fixup0));
+    SG_TRY(jbu_cap(c.j, c.stg, SG_JBU_CAP_H1, p.H1, (size_t)pixels * d2 * 4, c.s));
+    SG_TRY(jbu_linear(HK_F32, p.H1, d2, S.fx3_w, d2, S.fx3_b, p.X, d2 + 3, HK_F32, p.Kf, d2, HK_F32, pixels, d2, d2, ACT_NONE, 0.1f, c.s, &R.fixup1));
+    R.kf = "f32";
+    return jbu_cap(c.j, c.stg, SG_JBU_CAP_KF, p.Kf, (size_t)pixels * d2 * 4, c.s);
+  }
+  // the matrix-core GEMMs: operands zero-padded to [NP, KP1] / [NP, NP], columns >= d2 are padding; H1 stays in the operands' format
+  const int NP = jbu_np(r), KP1 = jbu_kp1(r);
+  const int fmt = c.chain == JBU_BF16_HIRES ? HK_BF16 : c.chain == JBU_BF16_LOWRES ? HK_F16 : HK_F16X2;
+  const void* w0 = fmt == HK_BF16 ? S.fx0_w16 : fmt == HK_F16 ? S.fx0_w16h : S.fx0_wh2;
+  const void* w3 = fmt == HK_BF16 ? S.fx3_w16 : fmt == HK_F16 ? S.fx3_w16h : S.fx3_wh2;
+  SG_TRY(jbu_linear(fmt, p.X16, KP1, w0, KP1, S.fx0_bp, nullptr, 0, HK_F32, p.H116, NP, fmt, pixels, NP, KP1, ACT_GELU, 1.f, c.s, &R.fixup0));
+  SG_TRY(jbu_cap(c.j, c.stg, SG_JBU_CAP_H1, p.H116, (size_t)pixels * NP * hk_esz(fmt), c.s));
+  if (c.chain == JBU_BF16_LOWRES) {                         // Kf rows in f16, residual = the operand rows
+    SG_TRY(jbu_linear(fmt, p.H116, NP, w3, NP, S.fx3_bp, p.X16, KP1, fmt, p.Kf, NP, fmt, pixels, NP, NP, ACT_NONE, 0.1f, c.s, &R.fixup1));
+    R.kf = "f16";
+    return jbu_cap(c.j, c.stg, SG_JBU_CAP_KF, p.Kf, (size_t)pixels * NP * 2, c.s);
+  }
+  SG_TRY(jbu_linear(fmt, p.H116, NP, w3, NP, S.fx3_bp, p.X, d2 + 3, HK_F32, p.Kf, NP, HK_F32, pixels, NP, NP, ACT_NONE, 0.1f, c.s, &R.fixup1));
+  R.kf = "f32";
+  return jbu_cap(c.j, c.stg, SG_JBU_CAP_KF, p.Kf, (size_t)pixels * NP * 4, c.s);
+}
+
+// adaptive convolution of the 2x bicubic source with the per-pixel kernels Kf -> the stage's output
+static int jbu_conv_step(const JbuCall& c) {
+  const JbuPlan& p = c.p;
+  const int B = c.B, C = c.C, stg = c.stg, h = c.h, w = c.w, oh = 2 * h, ow = 2 * w;
+  const int r = c.S().r, d = 2 * r + 1, d2 = d * d, ldk = c.chain == JBU_F32 ? d2 : jbu_np(r);
+  const int64_t pixels = c.pixels();
+  float* dst = c.dst();
+  hipStream_t s = c.s;
+  JbuStageRecord& R = g_jbu_rec.st[stg];
+  dim3 grid((unsigned)(cdiv(oh, AC_T) * cdiv(ow, AC_T)), (unsigned)B);
+  switch (c.chain) {
+    case JBU_H2_LOWRES: {
+      const h2_t* s2 = (const h2_t*)(stg == 0 ? p.hr : c.lo[stg - 1]);
+      if (stg == 0) SG_TRY(pack_rows(c.source, (int64_t)B * h * w, C, C, p.hr, C, HK_F16X2, s));
+      h2_t* d2p = (h2_t*)(stg == 3 ? (c.x2_in_hr ? p.hr : nullptr) : c.lo[stg]);
+      float* d32 = stg == 3 ? dst : nullptr;
+      if (stg == 3 && c.x2_in_hr) *c.x2_in_hr = true;
+      SG_TRY(jbu_cap(c.j, stg, SG_JBU_CAP_SRC, s2, (size_t)B * h * w * C * 4, s));
+      R.src = "h2"; R.bicubic = "none"; R.hr = "none"; R.out16 = d2p ? "h2" : "none";
+      SG_TRY(with_radius(r, [&](auto rc) {
+        constexpr int RR = decltype(rc)::value;
+        SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_conv_lowres_x2_kernel<RR>), LowX2Cfg<RR>::LDS));
+        hipLaunchKernelGGL(jbu_conv_lowres_x2_kernel<RR>, grid, dim3(256), LowX2Cfg<RR>::LDS, s, s2, p.Kf, ldk, h, w, C, d32, d2p);
+        R.conv = RR == 5 ? "jbu_conv_lowres_x2_kernel<5>" : "jbu_conv_lowres_x2_kernel<3>";
+        return (int)SG_OK;
+      }));
+      SG_LAUNCH_CHECK();
+      if (d32) SG_TRY(jbu_cap(c.j, stg, SG_JBU_CAP_OUT, d32, (size_t)pixels * C * 4, s));
+      if (d2p) SG_TRY(jbu_cap(c.j, stg, SG_JBU_CAP_OUT16, d2p, (size_t)pixels * C * 4, s));
+      break;
+    }
+    case JBU_BF16_LOWRES: {                                 // bicubic folded into the per-pixel kernel: no hi-res tensor at all
+      const bf16_t* s16 = (const bf16_t*)(stg == 0 ? p.hr : c.lo[stg - 1]);
+      if (stg == 0) SG_TRY(pack_rows(c.source, (int64_t)B * h * w, C, C, p.hr, C, 1, s));
+      bf16_t* d16 = (bf16_t*)(stg == 3 ? p.x16 : c.lo[stg]);           // the last stage writes the final GEMM's / the fused tail's bf16 operand
+      float* d32 = (stg == 3 && c.want_f32_x) ? dst : nullptr;   // the fused tail works from the bf16 copy alone: 4 B per element not written
+      SG_TRY(jbu_cap(c.j, stg, SG_JBU_CAP_SRC, s16, (size_t)B * h * w * C * 2, s));
+      R.src = "bf16"; R.bicubic = "none"; R.hr = "none"; R.out16 = "bf16";
+      SG_TRY(with_radius(r, [&](auto rc) {
+        constexpr int RR = decltype(rc)::value;
+        SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_conv_lowres_kernel<RR>), LowCfg<RR>::LDS));
+        hipLaunchKernelGGL(jbu_conv_lowres_kernel<RR>, grid, dim3(256), LowCfg<RR>::LDS, s, s16, p.Kf, ldk, h, w, C, d32, d16, 1);   // 1: Kf rows are f16
+        R.conv = RR == 5 ? "jbu_conv_lowres_kernel<5>" : "jbu_conv_lowres_kernel<3>";
+        return (int)SG_OK;
+      }));
+      SG_LAUNCH_CHECK();
+      if (d32) SG_TRY(jbu_cap(c.j, stg, SG_JBU_CAP_OUT, d32, (size_t)pixels * C * 4, s));
+      SG_TRY(jbu_cap(c.j, stg, SG_JBU_CAP_OUT16, d16, (size_t)pixels * C * 2, s));
+      break;
+    }
+    case JBU_BF16_HIRES: case JBU_F32: case JBU_H2_HIRES: {   // 2x bicubic into a hi-res tensor (bf16 for the matrix-core convolution), then the convolution
+      const bool hr16 = c.chain == JBU_BF16_HIRES;
+      const dim3 bgrid((unsigned)cdiv(pixels * (C / 4), 256));
+      SG_TRY(jbu_cap(c.j, stg, SG_JBU_CAP_SRC, c.src, (size_t)B * h * w * C * 4, s));
+      R.src = "f32";
+      if (hr16) hipLaunchKernelGGL(jbu_bicubic_kernel<bf16_t>, bgrid, dim3(256), 0, s, c.src, B, h, w, C, oh, ow, (bf16_t*)p.hr);
+      else hipLaunchKernelGGL(jbu_bicubic_kernel<float>, bgrid, dim3(256), 0, s, c.src, B, h, w, C, oh, ow, p.hr);
+      R.bicubic = hr16 ? "jbu_bicubic_kernel<bf16_t>" : "jbu_bicubic_kernel<float>"; R.hr = hr16 ? "bf16" : "f32";
+      SG_LAUNCH_CHECK();
+      SG_TRY(jbu_cap(c.j, stg, SG_JBU_CAP_HR, p.hr, (size_t)pixels * C * (hr16 ? 2 : 4), s));
+      const int WT = AC_T + 2 * r;
+      if (hr16) {
+        const int KP = (int)align_up((size_t)WT * WT, 32);
+        const size_t lds = (size_t)(64 + ACM_CC) * (KP + 8) * sizeof(bf16_t);
+        SG_REQUIRE(lds <= 160 * 1024, "sg_jbu_upsample: window %d needs %zu bytes of LDS", d, lds);
+        SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_adaptive_conv_mfma_kernel), 160 * 1024));
+        // no bf16 copy of the output: only C % 64 == 0 has a consumer for it (the bf16 final GEMM), and that is the low-res chain
+        hipLaunchKernelGGL(jbu_adaptive_conv_mfma_kernel, grid, dim3(256), lds, s, (const bf16_t*)p.hr, p.Kf, ldk, oh, ow, C, r, KP, dst, (bf16_t*)nullptr);
+        R.conv = "jbu_adaptive_conv_mfma_kernel";
+      } else {
+        const size_t lds = ((size_t)WT * WT * AC_LD + (size_t)d2 * 64) * sizeof(float);
+        if (lds > 48 * 1024) SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_adaptive_conv_kernel), lds));
+        grid = dim3(grid.x, (unsigned)cdiv(C, AC_CC), (unsigned)B);
+        hipLaunchKernelGGL(jbu_adaptive_conv_kernel, grid, dim3(256), lds, s, p.hr, p.Kf, ldk, oh, ow, C, r, dst);
+        R.conv = "jbu_adaptive_conv_kernel";
+      }
+      SG_LAUNCH_CHECK();
+      R.out16 = "none";
+      SG_TRY(jbu_cap(c.j, stg, SG_JBU_CAP_OUT, dst, (size_t)pixels * C * 4, s));
+      break;
+    }
+  }
+  R.grid[0] = grid.x; R.grid[1] = grid.y; R.grid[2] = grid.z;
+  return SG_OK;
+}
+
+// The four 2x stages (JBULearnedRange.forward x 4): source [B, gh*gw, C] -> *x_out [B, 16gh*16gw, C] f32 inside the workspace
+// (and its bf16 copy in p.x16 on the bf16 low-res chain)
+static int jbu_stages(sg_jbu* j, const float* source, const float* guidance, int B, int gh, int gw, int GH, int GW, int precision,
+                      const JbuPlan& p, const float** x_out, hipStream_t s, bool want_f32_x = true, bool* x2_in_hr = nullptr) {
+  const int C = j->C;
+  JbuCall c{j, p, s, jbu_chain(precision, C), B, C, source, want_f32_x, x2_in_hr};
+  const size_t esz = c.chain == JBU_H2_LOWRES ? 4 : 2;
+  size_t off = align_up((size_t)B * gh * gw * C * esz, 256);
+  for (int t = 0; t < 3; ++t) { c.lo[t] = (char*)p.hr + off; off += align_up((size_t)B * (gh << (t + 1)) * (gw << (t + 1)) * C * esz, 256); }
+  // two-plane: the 8x stage's output goes to the f32 path's 8x buffer (bufA: exactly pixels / 4 x C x 4 bytes, unused by this chain) instead: the
+  // hi-res region is then dead while the LAST stage runs, which writes the two-plane copy of x there for the final 1x1 GEMM -- no pack pass
+  if (c.chain == JBU_H2_LOWRES) c.lo[2] = p.bufA;
+  if (x2_in_hr) *x2_in_hr = false;
+  c.h = gh; c.w = gw; c.src = source;
+  for (c.stg = 0; c.stg < 4; ++c.stg) {
+    const JbuStage& S = c.S();
+    const int r = S.r, oh = 2 * c.h, ow = 2 * c.w;
+    const int64_t pixels = c.pixels();
+    // every <R> kernel is instantiated for these two radii alone, and their window (d^2 <= 128) and LDS sizes are known to fit
+    SG_REQUIRE(r == 3 || r == 5, "sg_jbu_upsample: no kernels for window radius %d", r);
+    SG_REQUIRE(r < oh && r < ow, "sg_jbu_upsample: reflect padding %d needs a guidance grid larger than %dx%d", r, oh, ow);
+    hipLaunchKernelGGL(jbu_pool_kernel, dim3((unsigned)cdiv(pixels * 3, 256)), dim3(256), 0, s, guidance, B, GH, GW, oh, ow, p.gs);
+    SG_LAUNCH_CHECK();
+    SG_TRY(jbu_cap(j, c.stg, SG_JBU_CAP_GS, p.gs, (size_t)pixels * 3 * 4, s));
+    hipLaunchKernelGGL(jbu_range_proj_kernel, dim3((unsigned)cdiv(pixels, 256)), dim3(256), 0, s, p.gs, pixels, S.rp0_w, S.rp0_b, S.rp3_w,
+                       S.rp3_b, p.proj);
+    SG_LAUNCH_CHECK();
+    SG_TRY(jbu_cap(j, c.stg, SG_JBU_CAP_PROJ, p.proj, (size_t)pixels * KEY_DIM * 4, s));
+    SG_TRY(jbu_range_step(c));
+    SG_TRY(jbu_fixup_step(c));
+    SG_TRY(jbu_conv_step(c));
+    c.src = c.dst(); c.h = oh; c.w = ow;
+  }
+  *x_out = c.src;
+  return SG_OK;
+}
+
+// ---- kind 2: Bilinear ------------------------------------------------------------------------------------------------------------------
+static int bilinear_upsample(sg_jbu* j, const float* source, int B, int gh, int gw, int GH, int GW, float* out, hipStream_t s) {
+  const int64_t pixels = (int64_t)B * GH * GW;
+  SG_REQUIRE(cdiv(pixels, 4) < (1ll << 31), "sg_jbu_upsample: too many pixels");
+  jbu_rec_start();
+  jbu_cap_reset(j);
+  hipLaunchKernelGGL(bilinear_features_kernel, dim3((unsigned)cdiv(pixels, 4)), dim3(256), 0, s, source, B, gh, gw, GH, GW, j->C, out);
+  SG_LAUNCH_CHECK();
+  g_jbu_rec.fin = "bilinear_features_kernel";
+  return SG_OK;
+}
+
+static int bilinear_logits(sg_jbu* j, const float* source, int B, int gh, int gw, int GH, int GW, const float* text, int Q,
+                           const float* cls, float cls_token_lambda, float* logits, void* ws, size_t ws_bytes, hipStream_t s) {
+  BilinearPlan p;
+  const size_t need = bilinear_plan(B, gh, gw, ws, false, p);
+  if (need > ws_bytes) return fail(SG_ERR_STATE, "sg_jbu_logits: workspace %zu < required %zu", ws_bytes, need);
+  const int64_t tokens = (int64_t)B * gh * gw;
+  SG_REQUIRE(cdiv(tokens, 4) < (1ll << 31) && cdiv(GH, 4) < 65536 && B < 65536, "sg_jbu_logits: shape too large for one launch");
+  jbu_rec_start();
+  jbu_cap_reset(j);
+  hipLaunchKernelGGL(bilinear_prologue_kernel, dim3((unsigned)cdiv(tokens, 4)), dim3(256), 0, s, source, text, B, gh, gw, j->C, Q, p.y, p.gram);
+  SG_LAUNCH_CHECK();
+  g_jbu_rec.geff = "bilinear_prologue_kernel";
+  const bool use_cls = cls != nullptr && cls_token_lambda != 0.f;
+  if (use_cls) {
+    hipLaunchKernelGGL(jbu_cls_logits_kernel, dim3(B), dim3(64), 0, s, cls, text, j->C, Q, p.clsl);
+    SG_LAUNCH_CHECK();
+    g_jbu_rec.cls = "jbu_cls_logits_kernel";
+  }
+  hipLaunchKernelGGL(bilinear_pixel_logits_kernel, dim3((unsigned)cdiv(GW, 64), (unsigned)cdiv(GH, 4), (unsigned)B), dim3(256), 0, s, p.y,
+                     p.gram, use_cls ? p.clsl : nullptr, cls_token_lambda, gh, gw, GH, GW, Q, logits);
+  SG_LAUNCH_CHECK();
+  g_jbu_rec.pix = "bilinear_pixel_logits_kernel";
+  return SG_OK;
+}
+
+// ---- kind 3: LayeredResizeConv(dim, 1): per stage the operand producer, then the 1x1 conv as one GEMM ----------------------------------
 static int resize_conv_upsample(sg_jbu* j, const float* source, const float* guidance, int B, int gh, int gw, int GH, int GW, int precision,
                                 float* out, void* ws, size_t ws_bytes, hipStream_t s) {
   ResizeConvPlan p;
@@ -2222,18 +1943,9 @@ static int resize_conv_upsample(sg_jbu* j, const float* source, const float* gui
     else hipLaunchKernelGGL(resize_conv_operands_kernel<bf16_t>, grid, dim3(256), 0, s, src, guidance, B, h, w, GH, GW, C, KP, p.big, (bf16_t*)p.a);
     SG_LAUNCH_CHECK();
     const int act = k < 3 ? ACT_RELU : ACT_NONE;
-    if (hk == HK_F32) {
-      GemmF32Args g{};
-      g.A = (const float*)p.a; g.lda = KP; g.B = j->rc_w[k]; g.sbk = 1; g.sbn = C + 3; g.bias = j->rc_b[k]; g.residual = p.big; g.ldr = C;
-      g.C = outs[k]; g.ldc = C; g.M = (int)P; g.N = C; g.K = C + 3; g.batch = 1; g.inner = 1; g.act = act; g.alpha = 1.f;
-      SG_TRY(gemm_f32(g, s));
-    } else {
-      GemmBf16Args g{};
-      g.A = (const bf16_t*)p.a; g.lda = KP; g.W = (const bf16_t*)(hk == HK_F16X2 ? j->rc_wh2[k] : j->rc_w16[k]); g.ldw = KP; g.bias = j->rc_b[k];
-      g.residual = p.big; g.ldr = C; g.C = outs[k]; g.ldc = C; g.c_is_bf16 = 0; g.M = (int)P; g.N = C; g.K = KP; g.batch = 1; g.act = act;
-      g.alpha = 1.f; g.h2 = hk == HK_F16X2 ? 1 : 0;
-      SG_TRY(gemm_bf16(g, s));
-    }
+    // the f32 GEMM reads the unpacked weight [C, C + 3]; the 2-byte ones the rows packed to KP
+    if (hk == HK_F32) SG_TRY(jbu_linear(hk, p.a, KP, j->rc_w[k], C + 3, j->rc_b[k], p.big, C, HK_F32, outs[k], C, HK_F32, P, C, C + 3, act, 1.f, s, nullptr));
+    else SG_TRY(jbu_linear(hk, p.a, KP, hk == HK_F16X2 ? j->rc_wh2[k] : j->rc_w16[k], KP, j->rc_b[k], p.big, C, HK_F32, outs[k], C, HK_F32, P, C, KP, act, 1.f, s, nullptr));
     src = outs[k];
     h *= 2; w *= 2;
   }
@@ -2241,6 +1953,291 @@ static int resize_conv_upsample(sg_jbu* j, const float* source, const float* gui
   return SG_OK;
 }
 }  // namespace sg
+
+// ==== C entry points ======================================================================================================================
+extern "C" int sg_jbu_create(sg_jbu** out, int device, int kind, int feat_dim) {
+  SG_REQUIRE(out && kind >= 0 && kind <= 3 && feat_dim > 0 && feat_dim % 4 == 0 && (kind != SG_JBU_RESIZE_CONV || feat_dim % 8 == 0),
+             "sg_jbu_create: bad arguments (kind 0 = jbu_one, 1 = jbu_stack, 2 = bilinear, 3 = resize_conv; feat_dim %% 4 == 0, resize_conv %% 8)");
+  DeviceGuard dg(device);
+  sg_jbu* j = new sg_jbu();
+  if (kind == SG_JBU_BILINEAR) {                          // Bilinear (upsamplers.py:343-350) has no parameters: no arena, nothing to load
+    j->device = device; j->kind = kind; j->C = feat_dim; j->n_stage_sets = 0; j->arena = nullptr; j->arena_bytes = 0;
+    *out = j;
+    return SG_OK;
+  }
+  if (kind == SG_JBU_RESIZE_CONV) {                       // LayeredResizeConv(dim, 1) (upsamplers.py:178-200): four 1x1 convs over [src | guidance]
+    j->device = device; j->kind = kind; j->C = feat_dim; j->n_stage_sets = 0;
+    const size_t KP = rc_kp(feat_dim);
+    auto lay = [&](Bump b) {
+      for (int k = 0; k < 4; ++k) {
+        j->rc_w[k] = (float*)b.take((size_t)feat_dim * (feat_dim + 3) * 4);
+        j->rc_b[k] = (float*)b.take((size_t)feat_dim * 4);
+        j->rc_w16[k] = b.take((size_t)feat_dim * KP * 2);
+        j->rc_wh2[k] = b.take((size_t)feat_dim * KP * 4);
+      }
+      return align_up(b.off, 256);
+    };
+    j->arena_bytes = lay(Bump(nullptr, 0, true));
+    hipError_t e = hipMalloc(&j->arena, j->arena_bytes);
+    if (e != hipSuccess) { delete j; return fail(SG_ERR_HIP, "sg_jbu_create: hipMalloc(%zu) -> %s", j->arena_bytes, hipGetErrorString(e)); }
+    lay(Bump(j->arena, j->arena_bytes, false));
+    SG_HIP(hipMemset(j->arena, 0, j->arena_bytes));
+    j->have.assign(8, 0);
+    *out = j;
+    return SG_OK;
+  }
+  j->device = device; j->kind = kind; j->C = feat_dim; j->n_stage_sets = kind == 0 ? 1 : 4;
+  // JBUOne radius 5, JBUStack radius 3 (upsamplers.py:281-284,308).  These are the ONLY radii: the <R> kernels are instantiated for 5 and 3
+  // and jbu_stages refuses anything else.
+  const int r = kind == 0 ? 5 : 3;
+  auto lay = [&](Bump b) {
+    for (int s = 0; s < j->n_stage_sets; ++s) {
+      JbuStage& S = j->st[s]; S.r = r;
+      float** slots[10] = {&S.range_temp, &S.sigma, &S.rp0_w, &S.rp0_b, &S.rp3_w, &S.rp3_b, &S.fx0_w, &S.fx0_b, &S.fx3_w, &S.fx3_b};
+      for (int t = 0; t < 10; ++t) *slots[t] = (float*)b.take((size_t)stage_numel(t, r) * 4);
+      S.fx0_w16 = b.take((size_t)jbu_np(r) * jbu_kp1(r) * 2); S.fx3_w16 = b.take((size_t)jbu_np(r) * jbu_np(r) * 2);
+      S.fx0_bp = (float*)b.take((size_t)jbu_np(r) * 4); S.fx3_bp = (float*)b.take((size_t)jbu_np(r) * 4);
+      S.fx0_w16h = b.take((size_t)jbu_np(r) * jbu_kp1(r) * 2); S.fx3_w16h = b.take((size_t)jbu_np(r) * jbu_np(r) * 2);
+      S.fx0_wh2 = b.take((size_t)jbu_np(r) * jbu_kp1(r) * 4); S.fx3_wh2 = b.take((size_t)jbu_np(r) * jbu_np(r) * 4);
+    }
+    j->fin_w = (float*)b.take((size_t)feat_dim * feat_dim * 4);
+    j->fin_b = (float*)b.take((size_t)feat_dim * 4);
+    j->fin_w16 = b.take((size_t)feat_dim * feat_dim * 2);
+    j->fin_wh2 = b.take((size_t)feat_dim * feat_dim * 4);
+    return align_up(b.off, 256);
+  };
+  const size_t bytes = lay(Bump(nullptr, 0, true));
+  j->arena_bytes = bytes;
+  hipError_t e = hipMalloc(&j->arena, bytes);
+  if (e != hipSuccess) { delete j; return fail(SG_ERR_HIP, "sg_jbu_create: hipMalloc(%zu) -> %s", bytes, hipGetErrorString(e)); }
+  lay(Bump(j->arena, bytes, false));
+  SG_HIP(hipMemset(j->arena, 0, bytes));                  // the zero padding of the bf16 fixup operands
+  j->have.assign(j->n_stage_sets * 10 + 2, 0);
+  *out = j;
+  return SG_OK;
+}
+
+extern "C" void sg_jbu_destroy(sg_jbu* j) {
+  if (!j) return;
+  if (j->arena) (void)hipFree(j->arena);
+  delete j;
+}
+
+extern "C" int sg_jbu_set_tensor(sg_jbu* j, const char* name, const float* src, int64_t numel, sg_stream st) {
+  SG_REQUIRE(j && name && src, "sg_jbu_set_tensor: null argument");
+  if (j->kind == SG_JBU_BILINEAR) return fail(SG_ERR_INVALID, "sg_jbu_set_tensor: the bilinear upsampler has no tensor '%s'", name);
+  DeviceGuard dg(j->device);
+  hipStream_t s = as_stream(st);
+  if (j->kind == SG_JBU_RESIZE_CONV) {                    // "conv{1..4}.weight" [C, C+3, 1, 1] / "conv{1..4}.bias" [C]
+    const int C = j->C;
+    if (!strncmp(name, "conv", 4) && name[4] >= '1' && name[4] <= '4' && name[5] == '.') {
+      const int k = name[4] - '1';
+      if (!strcmp(name + 6, "weight")) {
+        SG_REQUIRE(numel == (int64_t)C * (C + 3), "sg_jbu_set_tensor(%s): expected %lld elements, got %lld", name, (long long)C * (C + 3), (long long)numel);
+        SG_HIP(hipMemcpyAsync(j->rc_w[k], src, (size_t)numel * 4, hipMemcpyDeviceToDevice, s));
+        SG_TRY(pack_rows(src, C, C + 3, C + 3, j->rc_w16[k], (int)rc_kp(C), HK_BF16, s));
+        SG_TRY(pack_rows(src, C, C + 3, C + 3, j->rc_wh2[k], (int)rc_kp(C), HK_F16X2, s));
+        j->have[2 * k] = 1;
+        return SG_OK;
+      }
+      if (!strcmp(name + 6, "bias")) {
+        SG_REQUIRE(numel == C, "sg_jbu_set_tensor(%s): expected %d elements, got %lld", name, C, (long long)numel);
+        SG_HIP(hipMemcpyAsync(j->rc_b[k], src, (size_t)C * 4, hipMemcpyDeviceToDevice, s));
+        j->have[2 * k + 1] = 1;
+        return SG_OK;
+      }
+    }
+    return fail(SG_ERR_INVALID, "sg_jbu_set_tensor: unknown tensor name '%s' for resize_conv", name);
+  }
+  auto put = [&](float* dst, int64_t n) -> int {
+    SG_REQUIRE(numel == n, "sg_jbu_set_tensor(%s): expected %lld elements, got %lld", name, (long long)n, (long long)numel);
+    SG_HIP(hipMemcpyAsync(dst, src, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    return SG_OK;
+  };
+  if (!strcmp(name, "fixup_proj.1.weight")) {
+    SG_TRY(put(j->fin_w, (int64_t)j->C * j->C));
+    if (j->C % 64 == 0) SG_TRY(pack_rows(src, j->C, j->C, j->C, j->fin_w16, j->C, 1, s));
+    if (j->C % 32 == 0) SG_TRY(pack_rows(src, j->C, j->C, j->C, j->fin_wh2, j->C, HK_F16X2, s));
+    j->have[j->n_stage_sets * 10] = 1; return SG_OK;
+  }
+  if (!strcmp(name, "fixup_proj.1.bias")) {
+    SG_TRY(put(j->fin_b, j->C));
+    hipLaunchKernelGGL(scale_kernel, dim3((unsigned)cdiv(j->C, 256)), dim3(256), 0, s, j->fin_b, 0.1f, (int64_t)j->C);   // epilogue is alpha*acc + bias
+    SG_LAUNCH_CHECK();
+    j->have[j->n_stage_sets * 10 + 1] = 1; return SG_OK;
+  }
+  int set = -1; const char* rest = nullptr;
+  if (j->kind == 0 && !strncmp(name, "up.", 3)) { set = 0; rest = name + 3; }
+  else if (j->kind == 1 && !strncmp(name, "up", 2) && name[2] >= '1' && name[2] <= '4' && name[3] == '.') { set = name[2] - '1'; rest = name + 4; }
+  if (set >= 0) {
+    for (int t = 0; t < 10; ++t)
+      if (!strcmp(rest, kStageTensor[t])) {
+        JbuStage& S = j->st[set];
+        float* slots[10] = {S.range_temp, S.sigma, S.rp0_w, S.rp0_b, S.rp3_w, S.rp3_b, S.fx0_w, S.fx0_b, S.fx3_w, S.fx3_b};
+        SG_TRY(put(slots[t], stage_numel(t, S.r)));
+        if (t == 9) {                                  // K += 0.1 * (H.W3^T + b3): the GEMM epilogue computes 0.1*acc + bias
+          hipLaunchKernelGGL(scale_kernel, dim3((unsigned)cdiv(numel, 256)), dim3(256), 0, s, slots[t], 0.1f, numel);
+          SG_LAUNCH_CHECK();
+        }
+        const int d2s = (2 * S.r + 1) * (2 * S.r + 1);
+        if (t == 6) { SG_TRY(pack_rows(src, d2s, d2s + 3, d2s + 3, S.fx0_w16, jbu_kp1(S.r), 1, s)); SG_TRY(pack_rows(src, d2s, d2s + 3, d2s + 3, S.fx0_w16h, jbu_kp1(S.r), HK_F16, s)); SG_TRY(pack_rows(src, d2s, d2s + 3, d2s + 3, S.fx0_wh2, jbu_kp1(S.r), HK_F16X2, s)); }
+        if (t == 8) { SG_TRY(pack_rows(src, d2s, d2s, d2s, S.fx3_w16, jbu_np(S.r), 1, s)); SG_TRY(pack_rows(src, d2s, d2s, d2s, S.fx3_w16h, jbu_np(S.r), HK_F16, s)); SG_TRY(pack_rows(src, d2s, d2s, d2s, S.fx3_wh2, jbu_np(S.r), HK_F16X2, s)); }
+        if (t == 7) SG_HIP(hipMemcpyAsync(S.fx0_bp, slots[t], (size_t)d2s * 4, hipMemcpyDeviceToDevice, s));
+        if (t == 9) SG_HIP(hipMemcpyAsync(S.fx3_bp, slots[t], (size_t)d2s * 4, hipMemcpyDeviceToDevice, s));
+        j->have[set * 10 + t] = 1;
+        return SG_OK;
+      }
+  }
+  return fail(SG_ERR_INVALID, "sg_jbu_set_tensor: unknown tensor name '%s' for this upsampler kind", name);
+}
+
+extern "C" int sg_jbu_set_capture(sg_jbu* j, sg_jbu_capture* cap) {
+  SG_REQUIRE(j, "sg_jbu_set_capture: null upsampler");
+  j->cap = cap;
+  return SG_OK;
+}
+
+extern "C" const char* sg_jbu_last_kernels(void) {
+  static thread_local std::string text;
+  if (!g_jbu_rec.used) return "none";
+  text.clear();
+  auto put = [&](const std::string& key, const char* v) {
+    if (!v) return;
+    if (!text.empty()) text += ' ';
+    text += key + "=" + v;
+  };
+  for (int k = 0; k < 4; ++k) {
+    const JbuStageRecord& R = g_jbu_rec.st[k];
+    const std::string sk = "s" + std::to_string(k) + ".";
+    put(sk + "range", R.range); put(sk + "x16", R.x16); put(sk + "fixup0", R.fixup0); put(sk + "fixup1", R.fixup1); put(sk + "kf", R.kf);
+    put(sk + "src", R.src); put(sk + "bicubic", R.bicubic); put(sk + "hr", R.hr); put(sk + "conv", R.conv);
+    if (R.conv) put(sk + "grid", (std::to_string(R.grid[0]) + "x" + std::to_string(R.grid[1]) + "x" + std::to_string(R.grid[2])).c_str());
+    put(sk + "out16", R.out16);
+  }
+  put("final", g_jbu_rec.fin); put("final.a", g_jbu_rec.fin_a);
+  if (g_jbu_rec.pix) {
+    std::string t = std::string(g_jbu_rec.geff) + (g_jbu_rec.cls ? std::string(",") + g_jbu_rec.cls : std::string()) + "," + g_jbu_rec.pix;
+    put("tail", t.c_str());
+  }
+  return text.c_str();
+}
+
+extern "C" size_t sg_jbu_workspace_bytes(const sg_jbu* j, int B, int gh, int gw) {
+  if (!j || B <= 0 || gh <= 0 || gw <= 0) return 0;
+  if (j->kind == SG_JBU_BILINEAR) { BilinearPlan p; return bilinear_plan(B, gh, gw, nullptr, true, p); }
+  if (j->kind == SG_JBU_RESIZE_CONV) { ResizeConvPlan p; return resize_conv_plan(j->C, B, gh, gw, nullptr, true, p); }
+  JbuPlan p;
+  return jbu_plan(j, B, gh, gw, nullptr, true, p);
+}
+
+// source [B, gh*gw, C] (patch tokens), guidance [B,3,GH,GW] (the normalised, padded tile) -> out [B, (16gh*16gw), C]
+extern "C" int sg_jbu_upsample(sg_jbu* j, const float* source, const float* guidance, int B, int gh, int gw, int GH, int GW, int precision,
+                               float* out, void* ws, size_t ws_bytes, sg_stream st) {
+  SG_REQUIRE(j && source && guidance && out, "sg_jbu_upsample: null argument");
+  if (j->kind == SG_JBU_BILINEAR) {
+    SG_REQUIRE(B > 0 && gh > 0 && gw > 0 && GH > 0 && GW > 0, "sg_jbu_upsample: bad shape");
+    DeviceGuard dg(j->device);
+    return bilinear_upsample(j, source, B, gh, gw, GH, GW, out, as_stream(st));
+  }
+  if (j->kind == SG_JBU_RESIZE_CONV) {
+    SG_REQUIRE(ws && B > 0 && gh > 0 && gw > 0 && GH > 0 && GW > 0, "sg_jbu_upsample: bad arguments");
+    for (size_t i = 0; i < j->have.size(); ++i) if (!j->have[i]) return fail(SG_ERR_STATE, "sg_jbu_upsample: upsampler weights incomplete");
+    DeviceGuard dg(j->device);
+    return resize_conv_upsample(j, source, guidance, B, gh, gw, GH, GW, precision, out, ws, ws_bytes, as_stream(st));
+  }
+  SG_REQUIRE(ws, "sg_jbu_upsample: null argument");
+  for (size_t i = 0; i < j->have.size(); ++i) if (!j->have[i]) return fail(SG_ERR_STATE, "sg_jbu_upsample: upsampler weights incomplete");
+  DeviceGuard dg(j->device);
+  hipStream_t s = as_stream(st);
+  JbuPlan p;
+  const size_t need = jbu_plan(j, B, gh, gw, ws, false, p);
+  if (need > ws_bytes) return fail(SG_ERR_STATE, "sg_jbu_upsample: workspace %zu < required %zu", ws_bytes, need);
+  const int C = j->C;
+  const float* src = nullptr;
+  bool x2_ready = false;
+  jbu_rec_start();
+  jbu_cap_reset(j);
+  SG_TRY(jbu_stages(j, source, guidance, B, gh, gw, GH, GW, precision, p, &src, s, true, &x2_ready));
+  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_FIN_RES, src, (size_t)B * 256 * gh * gw * C * 4, s));
+  // out = x + 0.1 * (x . Wf^T + bf)     (bias pre-scaled by 0.1 at load); the residual is the f32 x in every format
+  const int64_t pixels = (int64_t)B * 16 * gh * 16 * gw;
+  int fmt = HK_F32; const void* A = src; const void* W = j->fin_w;
+  if (precision == SG_PREC_BF16 && C % 64 == 0) {                       // the bf16 low-res chain wrote x16 itself
+    fmt = HK_BF16; A = p.x16; W = j->fin_w16;
+  } else if (precision == SG_PREC_F16X2 && C % 32 == 0 && pixels >= 1024) {   // exact tower mode: x packed to two-plane f16 (the hi-res scratch is free by now), f32-grade GEMM
+    if (!x2_ready) SG_TRY(pack_rows(src, pixels, C, C, p.hr, C, HK_F16X2, s));   // (the two-plane low-res convolution wrote this copy itself)
+    fmt = HK_F16X2; A = p.hr; W = j->fin_wh2;
+  }
+  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_FIN_A, A, (size_t)pixels * C * hk_esz(fmt), s));
+  SG_TRY(jbu_linear(fmt, A, C, W, C, j->fin_b, src, C, HK_F32, out, C, HK_F32, pixels, C, C, ACT_NONE, 0.1f, s, &g_jbu_rec.fin));
+  g_jbu_rec.fin_a = fmt == HK_BF16 ? "bf16" : fmt == HK_F16X2 ? "h2" : "f32";
+  return SG_OK;
+}
+
+// sg_jbu_logits replaces, for a batch of tiles,  feats = upsampler(tokens, img) -> feats /= |feats| -> feats @ T^T (+ lambda * cls_logits)
+// (segmentor.py:368-379) without materialising the [S^2, C] feature map (throughput mode; SURVEY.md §7 step 7).
+extern "C" int sg_jbu_logits(sg_jbu* j, const float* source, const float* guidance, int B, int gh, int gw, int GH, int GW, int precision,
+                             const float* text, int Q, const float* cls, float cls_token_lambda, float* logits, void* ws, size_t ws_bytes,
+                             sg_stream st) {
+  SG_REQUIRE(j && source && guidance && text && logits && ws, "sg_jbu_logits: null argument");
+  SG_REQUIRE(Q >= 1 && Q <= JBU_QMAX, "sg_jbu_logits: 1 <= Q <= %d", JBU_QMAX);
+  if (j->kind == SG_JBU_BILINEAR) {                       // every precision: the bilinear logits are f32 arithmetic throughout
+    SG_REQUIRE(B > 0 && gh > 0 && gw > 0 && GH > 0 && GW > 0, "sg_jbu_logits: bad shape");
+    DeviceGuard dg(j->device);
+    return bilinear_logits(j, source, B, gh, gw, GH, GW, text, Q, cls, cls_token_lambda, logits, ws, ws_bytes, as_stream(st));
+  }
+  if (j->kind == SG_JBU_RESIZE_CONV)
+    return fail(SG_ERR_INVALID, "sg_jbu_logits: resize_conv has no fused logits tail; use sg_jbu_upsample + sg_cosine_logits");
+  SG_REQUIRE(precision == SG_PREC_BF16 && j->C % 64 == 0 && j->C >= 512, "sg_jbu_logits: the fused tail is the bf16 throughput path (C %% 64 == 0, C >= 512); use sg_jbu_upsample + sg_cosine_logits otherwise");
+  for (size_t i = 0; i < j->have.size(); ++i) if (!j->have[i]) return fail(SG_ERR_STATE, "sg_jbu_logits: upsampler weights incomplete");
+  DeviceGuard dg(j->device);
+  hipStream_t s = as_stream(st);
+  JbuPlan p;
+  const size_t need = jbu_plan(j, B, gh, gw, ws, false, p);
+  if (need > ws_bytes) return fail(SG_ERR_STATE, "sg_jbu_logits: workspace %zu < required %zu", ws_bytes, need);
+  const int C = j->C;
+  const int64_t P = (int64_t)16 * gh * 16 * gw, pixels = (int64_t)B * P;
+  SG_REQUIRE(pixels >= 1024 && pixels < (1ll << 31), "sg_jbu_logits: pixel count out of range");
+  const float* x = nullptr;
+  jbu_rec_start();
+  jbu_cap_reset(j);
+  SG_TRY(jbu_stages(j, source, guidance, B, gh, gw, GH, GW, precision, p, &x, s, /*want_f32_x=*/false));
+  const bf16_t* x16 = (const bf16_t*)p.x16;                 // the 16x features exist in bf16 only: the conv's 4 B/element f32 store and its two re-reads are gone
+  hipLaunchKernelGGL(jbu_geff_kernel, dim3((unsigned)cdiv(C, 64), (unsigned)Q), dim3(256), 0, s, text, j->fin_w, j->fin_b, C, Q, p.geff, p.g0);
+  SG_LAUNCH_CHECK();
+  g_jbu_rec.geff = "jbu_geff_kernel";
+  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_GEFF, p.geff, (size_t)C * JBU_QMAX * 4, s));
+  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_G0, p.g0, (size_t)JBU_QMAX * 4, s));
+  const bool use_cls = cls != nullptr && cls_token_lambda != 0.f;
+  if (use_cls) {
+    hipLaunchKernelGGL(jbu_cls_logits_kernel, dim3(B), dim3(64), 0, s, cls, text, C, Q, p.clsl);
+    SG_LAUNCH_CHECK();
+    g_jbu_rec.cls = "jbu_cls_logits_kernel";
+    SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_CLSL, p.clsl, (size_t)B * JBU_QMAX * 4, s));
+  }
+  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_FIN_A, x16, (size_t)pixels * C * 2, s));
+  // the final 1x1 with the row-dot epilogue: residual = the bf16 x itself, nothing stored but the per-slot |out|^2 - |x|^2
+  SG_TRY(jbu_linear(HK_BF16, x16, C, j->fin_w16, C, j->fin_b, x16, C, HK_BF16, p.rowdot, C, HK_F32, pixels, C, C, ACT_NONE, 0.1f, s, &g_jbu_rec.fin,
+                    p.rowdot));
+  const int slots = C / 64;
+  g_jbu_rec.fin_a = "bf16";
+  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_ROWDOT, p.rowdot, (size_t)pixels * slots * 4, s));
+  if (Q <= 16) {                                             // matrix-pipe form (its C % 32 == 0 is implied by the fused tail's C % 64 == 0)
+    const size_t lds = (size_t)2 * 16 * (C + 8) * sizeof(bf16_t) + 4 * 64 * sizeof(float);
+    SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_pixel_logits_mfma_kernel), lds));
+    hipLaunchKernelGGL(jbu_pixel_logits_mfma_kernel, dim3((unsigned)cdiv(pixels, 4 * 64 * PLM_ROUNDS)), dim3(256), lds, s, x16, p.rowdot, slots, p.geff, p.g0,
+                       use_cls ? p.clsl : nullptr, cls_token_lambda, pixels, P, C, Q, logits);
+    g_jbu_rec.pix = "jbu_pixel_logits_mfma_kernel";
+  } else {                                                   // 17 <= Q <= 32: the VALU form with all JBU_QMAX queries in registers
+    const size_t lds = ((size_t)C * 32 + 4 * 64 * PL_PPL * PL_LD) * sizeof(float);
+    if (lds > 48 * 1024) SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_pixel_logits_kernel<32, bf16_t>), lds));
+    hipLaunchKernelGGL((jbu_pixel_logits_kernel<32, bf16_t>), dim3((unsigned)cdiv(pixels, 4 * 64 * PL_PPL)), dim3(256), lds, s, x16, p.rowdot, slots, p.geff,
+                       p.g0, use_cls ? p.clsl : nullptr, cls_token_lambda, pixels, P, C, Q, logits);
+    g_jbu_rec.pix = "jbu_pixel_logits_kernel<32>";
+  }
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
 
 extern "C" int sg_extract_tiles(const sg_tile_batch* t, int up_h, int up_w, float* out, sg_stream s) {
   SG_REQUIRE(t && out && t->scene && t->windows && t->n_tiles > 0, "sg_extract_tiles: bad arguments");

@@ -62,7 +62,7 @@ int select_topk(const float* attn_cls, const float* attn_diag, int B, int N, int
   SG_REQUIRE(k >= 1 && k <= n, "select_topk: k=%d out of range for %d patches", k, n);
   SG_REQUIRE((size_t)n * 4 <= 160 * 1024 - 256, "select_topk: %d patches exceed LDS", n);
   const size_t lds = (size_t)n * sizeof(float);
-  if (lds > 48 * 1024) SG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(select_topk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (lds > 48 * 1024) SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(select_topk_kernel), lds));
   hipLaunchKernelGGL(select_topk_kernel, dim3(B), dim3(256), lds, s, attn_cls, attn_diag, N, k, mode, idx);
   SG_LAUNCH_CHECK();
   return SG_OK;
@@ -391,7 +391,7 @@ static int ctf_fuse(const float* tokens, const float* nbr_strips, int n_local, i
                     float strength, int pass, float* result, hipStream_t s) {
   const int S = pass == 0 ? gh * bw : bw * gw;
   const size_t lds = ((size_t)S * (mode == 0 ? S : 2 * S) + 2 * S) * sizeof(float);
-  if (lds > 48 * 1024) SG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ctf_fuse_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (lds > 48 * 1024) SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(ctf_fuse_kernel), lds));
   hipLaunchKernelGGL(ctf_fuse_kernel, dim3(n_local), dim3(256), lds, s, tokens, nbr_strips, tile0, wg, gh, gw, C, bw, mode, strength, pass, result);
   SG_LAUNCH_CHECK();
   return SG_OK;
