@@ -17,6 +17,7 @@ PREC_F32, PREC_BF16, PREC_FP8, PREC_F16, PREC_F16X2 = 0, 1, 2, 3, 4
 MODEL_TYPES = {"vanilla": 0, "MaskCLIP": 1, "ClearCLIP": 2, "SCLIP": 3, "SegEarth": 4, "SFP": 5, "Experimental": 6,
                "NACLIP": 7, "NOnly": 8, "GAV": 9, "GEM": 10}
 IMG_F32_NCHW, IMG_U8_NHWC = 0, 1
+GT_U8, GT_I64 = 0, 1
 
 
 class VitDesc(C.Structure):
@@ -121,6 +122,7 @@ SIGNATURES = {
     "sg_jbu_last_kernels": (C.c_char_p, []),
     "sg_extract_tiles": (I, [C.POINTER(TileBatch), I, I, P, P]),
     "sg_global_debias": (I, [P, P, I, I, I, F, P, P]),
+    "sg_confusion_accumulate": (I, [P, P, I, L, I, I, I, P, P]),
 }
 
 _lib = None

@@ -338,10 +338,11 @@ def stitch_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, imag
 
 @on_tensor_device
 def postprocess_multi(canvases, canvas_hw, query_idx, num_classes: int, logit_scale: float, prob_thd: float, bg_idx: int,
-                      out_hw=None, want_probs: bool = True, canvas_offsets=None):
+                      out_hw=None, want_probs: bool = True, canvas_offsets=None, flat_labels: bool = False):
     """sg_postprocess_multi: N canvases [Q,h,w] in one flat buffer (packed back to back, or at ``canvas_offsets`` elements) ->
     (list of probs [K,H,W] or None, list of labels int64 [1,H,W]); (H, W) = out_hw[n] (default: the canvas size) -- a different size
-    is the bilinear resize of sg_resize_bilinear, fused."""
+    is the bilinear resize of sg_resize_bilinear, fused.  ``flat_labels`` adds a third result: the one int64 buffer the label maps
+    are views of, images back to back (what sg_confusion_accumulate takes for a whole flush group)."""
     lib = _lib.load()
     _require_gpu(canvases)
     if canvases.dtype != torch.float32 or not canvases.is_contiguous():
@@ -364,7 +365,44 @@ def postprocess_multi(canvases, canvas_hw, query_idx, num_classes: int, logit_sc
                                    ptr(labels), stream_ptr()), "sg_postprocess_multi")
     lab = [labels[pix[n]:pix[n + 1]].view(1, h, w) for n, (h, w) in enumerate(out_hw)]
     prb = [probs[K * pix[n]:K * pix[n + 1]].view(K, h, w) if want_probs else None for n, (h, w) in enumerate(out_hw)]
-    return prb, lab
+    return (prb, lab, labels) if flat_labels else (prb, lab)
+
+
+def _same_pixels(a, b) -> bool:
+    """Equal shapes up to leading singleton dimensions ([1,H,W] labels against [H,W] truth; flat buffers against flat buffers)."""
+    sa, sb = list(a.shape), list(b.shape)
+    while len(sa) > 1 and sa[0] == 1:
+        sa.pop(0)
+    while len(sb) > 1 and sb[0] == 1:
+        sb.pop(0)
+    return sa == sb
+
+
+@on_tensor_device
+def confusion_accumulate(labels, gt, table, K: int, ignore_index: int = 255, reduce_zero_label: bool = False):
+    """sg_confusion_accumulate on the current stream: adds the confusion counts of (labels, gt) to ``table`` int64 [(K+1),(K+1)] (row =
+    prediction, column = ground truth, index K = outside [0,K)) in place and returns it.  labels int64, gt uint8 or int64, of one shape
+    up to leading 1s: an image, or the flat label buffer of a flush group.  mmseg's intersect_and_union, counted on the device."""
+    lib = _lib.load()
+    _require_gpu(labels, gt, table)
+    K = int(K)
+    if labels.dtype != torch.int64:
+        raise TypeError(f"confusion_accumulate: labels must be int64, got {labels.dtype}")
+    if gt.dtype not in (torch.uint8, torch.int64):
+        raise TypeError(f"confusion_accumulate: gt must be uint8 or int64, got {gt.dtype}")
+    if not _same_pixels(labels, gt):
+        raise ValueError(f"confusion_accumulate: labels {tuple(labels.shape)} and gt {tuple(gt.shape)} differ in shape")
+    if table.dtype != torch.int64 or not table.is_contiguous() or table.numel() != (K + 1) * (K + 1):
+        raise ValueError(f"confusion_accumulate: table must be contiguous int64 with {(K + 1) * (K + 1)} elements for K={K}")
+    if gt.device != labels.device or table.device != labels.device:
+        raise ValueError("confusion_accumulate: labels, gt and table must live on one device")
+    if labels.numel() == 0:                # nothing to count; an empty tensor has no storage (a null data pointer, which the entry refuses)
+        return table
+    labels, gt = labels.contiguous(), gt.contiguous()
+    fmt = _lib.GT_U8 if gt.dtype == torch.uint8 else _lib.GT_I64
+    check(lib.sg_confusion_accumulate(ptr(labels), ptr(gt), fmt, labels.numel(), K, int(ignore_index), int(bool(reduce_zero_label)),
+                                      ptr(table), stream_ptr()), "sg_confusion_accumulate")
+    return table
 
 
 @on_tensor_device

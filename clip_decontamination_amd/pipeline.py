@@ -626,17 +626,23 @@ class SegPipeline:
                 out[k] = (ops.resize_bilinear(c, ori) if ori is not None and ori != tuple(c.shape[1:]) else c).unsqueeze(0)
         return out
 
-    def segment_scenes(self, scenes, stride, crop, want_probs: bool = False, ori_shapes=None):
-        """The whole packed path to labels: per flush group one sg_stitch_multi and one sg_postprocess_multi launch (the resize to
-        ``ori_shapes`` fused into the latter).  -> list of labels [1,H,W], or (list of probs [K,H,W], list of labels) with
-        ``want_probs``."""
-        probs: List[Optional[torch.Tensor]] = []
-        labels: List[Optional[torch.Tensor]] = []
+    def label_groups(self, scenes, stride, crop, want_probs: bool = False, ori_shapes=None):
+        """The whole packed path to labels, flush group by flush group: one sg_stitch_multi and one sg_postprocess_multi launch each
+        (the resize to ``ori_shapes`` fused into the latter).  Yields (image indices, list of probs [K,H,W] or None, list of labels
+        [1,H,W], the flat int64 buffer those label maps are views of, in that order of images)."""
         for idx, canvases, views in self._packed_canvases(scenes, stride, crop):
             chw = [tuple(c.shape[1:]) for c in views]
             ohw = [chw[n] if ori_shapes is None or ori_shapes[k] is None else tuple(ori_shapes[k]) for n, k in enumerate(idx)]
-            prb, lab = ops.postprocess_multi(canvases, chw, self.query_idx, self.num_classes, self.logit_scale, self.prob_thd, self.bg_idx,
-                                             ohw, want_probs)
+            prb, lab, flat = ops.postprocess_multi(canvases, chw, self.query_idx, self.num_classes, self.logit_scale, self.prob_thd,
+                                                   self.bg_idx, ohw, want_probs, flat_labels=True)
+            yield idx, prb, lab, flat
+
+    def segment_scenes(self, scenes, stride, crop, want_probs: bool = False, ori_shapes=None):
+        """``label_groups`` collected per image -> list of labels [1,H,W], or (list of probs [K,H,W], list of labels) with
+        ``want_probs``."""
+        probs: List[Optional[torch.Tensor]] = []
+        labels: List[Optional[torch.Tensor]] = []
+        for idx, prb, lab, _ in self.label_groups(scenes, stride, crop, want_probs, ori_shapes):
             for lst, vals in ((probs, prb), (labels, lab)):
                 lst.extend([None] * (max(idx) + 1 - len(lst)))
                 for k, x in zip(idx, vals):

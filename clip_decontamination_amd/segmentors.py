@@ -298,6 +298,59 @@ class _HipSegmentorBase(_Base):
                 self._write_maps(probs[i], labels[i], ds, i)
         return data_samples
 
+    @torch.no_grad()
+    def evaluate(self, inputs, gt_maps, metric=None, reduce_zero_label=False, ignore_index=255, iou_metrics=("mIoU",)):
+        """Labels to score without leaving the device: what the reference's ``test_evaluator = dict(type='IoUMetric', ...)`` reports.
+        inputs: as ``predict_many``; gt_maps: one [H,W] / [1,H,W] uint8 or int64 tensor or numpy array per image, of the image's size.
+        Returns ``(metric.compute(), metric)``; pass ``metric`` back in to accumulate over the calls of a dataset loop (its own
+        ignore_index / reduce_zero_label / iou_metrics then hold).  The packed labels-only path produces the labels (no probabilities
+        are written), the ground truth goes to the device once per call, the counts are taken with ONE sg_confusion_accumulate launch
+        per flush group over its flat label buffer, and only the (K+1) x (K+1) table comes back.  Whole-image inference
+        (``slide_crop <= 0``) goes image by image through ``predict``.  ``tile_group`` sharding is refused here (counting each rank's
+        band against the matching rows of the truth is not built yet: DESIGN.md section 8); score per rank over whole images and call
+        ``metric.reduce(group)``."""
+        from .metrics import IoUMetric
+        if getattr(self, "tile_group", None) is not None:
+            raise ValueError("evaluate: tile_group sharding is not supported (each rank would have to count its own band against the "
+                             "matching rows of the truth); evaluate whole images per rank and call metric.reduce(group)")
+        if metric is None:
+            metric = IoUMetric(ignore_index=ignore_index, iou_metrics=list(iou_metrics), num_classes=self.num_classes,
+                               reduce_zero_label=reduce_zero_label)
+        elif metric.num_classes is None:
+            metric.num_classes = self.num_classes
+        elif metric.num_classes != self.num_classes:
+            raise ValueError(f"evaluate: the metric counts {metric.num_classes} classes, the class file has {self.num_classes}")
+        batch = torch.is_tensor(inputs)
+        imgs = inputs.float() if batch else [x[0].float() if x.dim() == 4 else x.float() for x in inputs]
+        n = imgs.shape[0] if batch else len(imgs)
+        if len(gt_maps) != n:
+            raise ValueError(f"evaluate: {n} images but {len(gt_maps)} ground-truth maps")
+        dev = self.query_features.device
+        gts = [torch.as_tensor(g) for g in gt_maps]
+        for i, g in enumerate(gts):
+            hw = tuple(imgs[i].shape[-2:])
+            if tuple(g.shape) not in (hw, (1,) + hw):
+                raise ValueError(f"evaluate: ground truth {i} has shape {tuple(g.shape)}, image {i} is {hw}")
+        dtype = torch.uint8 if all(g.dtype == torch.uint8 for g in gts) else torch.int64
+        off = [0]
+        for g in gts:
+            off.append(off[-1] + g.numel())
+        if all(not g.is_cuda for g in gts):                                  # one host buffer, one copy to the device per call
+            gt_flat = torch.cat([g.reshape(-1).to(dtype) for g in gts]).to(dev)
+        else:
+            gt_flat = torch.cat([g.reshape(-1).to(device=dev, dtype=dtype) for g in gts])
+        if self.slide_crop <= 0:                                             # whole-image inference has no windows to pack
+            for i in range(n):
+                metric.add(self.predict(imgs[i][None], None).reshape(-1), gt_flat[off[i]:off[i + 1]])
+            return metric.compute(), metric
+        for idx, _, _, flat in self._pipeline().label_groups(imgs, self.slide_stride, self.slide_crop, want_probs=False):
+            if idx == list(range(idx[0], idx[0] + len(idx))):                # the group's images are neighbours in the call: a slice
+                gt = gt_flat[off[idx[0]]:off[idx[-1] + 1]]
+            else:                                                            # tile-size groups interleave images: gather on the device
+                gt = torch.cat([gt_flat[off[k]:off[k + 1]] for k in idx])
+            metric.add(flat, gt)
+        return metric.compute(), metric
+
     def postprocess_result(self, seg_logits, data_samples):
         """Reference segmentor.py:475-499: class probabilities [K,H,W] + labels [1,H,W] per image."""
         pipe = self._pipeline()

@@ -438,6 +438,25 @@ int sg_extract_tiles(const sg_tile_batch* tiles, int up_h, int up_w, float* out,
  *   out = tokens - cls_hat * (cos(tokens, cls_hat) * factor), tokens [B,n,E], cls [B,E] */
 int sg_global_debias(const float* tokens, const float* cls, int B, int n, int E, float factor, float* out, sg_stream s);
 
+/* ---- evaluation: confusion counts for mmseg's IoUMetric ---------------------------------------------------------------------
+ * sg_confusion_accumulate replaces the counting behind test_evaluator = dict(type='IoUMetric', ...) (configs/base_config.py:19; the
+ * reference's eval.py runs it through runner.test() and reports the result, eval.py:94-95): mmseg's intersect_and_union, which per
+ * image copies the labels to the host, masks by ignore_index and runs torch.histc three times.  Here one device pass per call:
+ *   labels int64 [n_pixels] (what sg_postprocess / sg_postprocess_multi write; any 8-byte aligned start), gt u8 or int64 [n_pixels] (any
+ *   start), flat: one image, or the concatenated label buffer of a whole flush group.  Per pixel, in this order: g = raw truth; with
+ *   reduce_zero_label mmseg's LoadAnnotations rule (raw 0 -> 255, raw 255 stays 255, every other value -> g - 1; the 255 is literal
+ *   whatever ignore_index is); skip the pixel if g == ignore_index; p' = label if in [0,K) else K, g' likewise; table[p'][g'] += 1.
+ *   table int64 [(K+1)][(K+1)], row = prediction, column = ground truth, index K = "outside [0,K)"; counts are ADDED to it.
+ * The extra row and column reproduce torch.histc(min=0, max=K-1), which drops an out-of-range value from one histogram while the pixel
+ * still counts in the others: area_intersect[k] = table[k][k], area_pred_label[k] = sum_g' table[k][g'], area_label[k] = sum_p' table[p'][k].
+ * Counts are integers end to end (32-bit per workgroup in LDS, one 64-bit add per non-zero bin per workgroup): byte-identical across
+ * repeats and launch shapes.  HBM-bound, one pass: 9 B per pixel (int64 label + u8 truth), 16 B with int64 truth.
+ * Refused with SG_ERR_INVALID before any launch: null pointers, an unknown format, K < 1, K > 127 (the per-workgroup table of (K+1)^2
+ * 32-bit counts must fit 64 KiB of LDS; there is no slower path for larger K), n_pixels < 0 or > 2^40.  n_pixels == 0 is a valid no-op. */
+typedef enum { SG_GT_U8 = 0, SG_GT_I64 = 1 } sg_gt_format;
+int sg_confusion_accumulate(const int64_t* labels, const void* gt, int gt_format, int64_t n_pixels, int K, int ignore_index,
+                            int reduce_zero_label, int64_t* table, sg_stream s);
+
 #ifdef __cplusplus
 }
 #endif
