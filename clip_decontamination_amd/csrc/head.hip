@@ -117,6 +117,119 @@ __global__ __launch_bounds__(256) void cosine_logits_kernel(const float* __restr
   }
 }
 
+// Any Q: the text rows pass through LDS in chunks of R rows (as many as fit), inside the kernel.  A wave holds ONE round of four tokens
+// (CLW_TPB = 16 tokens per workgroup) so that their debiased features stay in registers across the chunks: read from HBM once, as above.
+// Everything per (token, q) is cosine_logits_kernel's, expression for expression: the 16-lane groups, the summation order, the
+// debias / renormalise / + lambda * cls_logits steps.  Same expressions are not same bits, though: the compiler fuses the multiply-adds
+// of the debias sums (fc, cc) in another order here than there, step by step and differently per instantiation, so with the global
+// debias a few outputs are one unit in the last place apart (11 of 2464 at E = 768; equal without it).  The entry therefore sends every
+// shape cosine_logits_kernel takes to that kernel and this one only runs with R < Q.
+// The price is the staging: Q * E floats per 16 tokens instead of per 32.
+constexpr int CLW_TPB = 16;
+template <int NV>
+__global__ __launch_bounds__(256) void cosine_logits_wide_kernel(const float* __restrict__ tokens, const float* __restrict__ cls,
+                                                                 const float* __restrict__ text, int n, int E, int Q, int R, float debias,
+                                                                 float lambda, float* __restrict__ logits) {
+  extern __shared__ float sm[];
+  float* sT = sm;                    // [R][E] the current chunk of text rows
+  float* sC = sm + (size_t)R * E;    // [E] unit-norm CLS
+  float* sCL = sC + E;               // [R] cls logits of the chunk's rows
+  const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bool use_cls = cls != nullptr;
+  if (use_cls) {
+    for (int i = tid; i < E; i += 256) sC[i] = cls[(int64_t)b * E + i];
+    __syncthreads();
+    if (wave == 0) {                                       // cls /= ||cls||  (segmentor.py:310)
+      float ss = 0.f;
+      for (int i = lane; i < E; i += 64) ss += sC[i] * sC[i];
+      const float nrm = sqrtf(wave_sum(ss));
+      for (int i = lane; i < E; i += 64) sC[i] = sC[i] / nrm;
+    }
+    __syncthreads();
+  }
+  const int sub = lane >> 4, sl = lane & 15;
+  auto group_sum = [](float v) {
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+  };
+  const bool deb = use_cls && debias != 0.f;
+  const int t = blockIdx.x * CLW_TPB + wave * 4 + sub;
+  const bool wave_live = blockIdx.x * CLW_TPB + wave * 4 < n;           // wave-uniform; a dead wave still takes part in the barriers below
+  const float* f = tokens + ((int64_t)b * n + (t < n ? t : n - 1)) * E;
+  float4 x[NV];
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const int i = 4 * sl + 64 * k;
+    x[k] = (wave_live && i < E) ? *reinterpret_cast<const float4*>(f + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  float ff = 0.f, fc = 0.f, cc = 0.f;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const int i = 4 * sl + 64 * k;
+    if (i < E) {
+      ff += (x[k].x * x[k].x + x[k].y * x[k].y) + (x[k].z * x[k].z + x[k].w * x[k].w);
+      if (use_cls) {
+        const float4 c4 = *reinterpret_cast<const float4*>(sC + i);
+        fc += (x[k].x * c4.x + x[k].y * c4.y) + (x[k].z * c4.z + x[k].w * c4.w);
+        cc += (c4.x * c4.x + c4.y * c4.y) + (c4.z * c4.z + c4.w * c4.w);
+      }
+    }
+  }
+  ff = group_sum(ff);
+  float w = 0.f;
+  if (deb) {
+    fc = group_sum(fc); cc = group_sum(cc);
+    w = (fc / (sqrtf(ff) * sqrtf(cc))) * debias;
+  }
+  float nn = 0.f;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const int i = 4 * sl + 64 * k;
+    if (i < E) {
+      if (deb) {
+        const float4 c4 = *reinterpret_cast<const float4*>(sC + i);
+        x[k].x -= c4.x * w; x[k].y -= c4.y * w; x[k].z -= c4.z * w; x[k].w -= c4.w * w;
+      }
+      nn += (x[k].x * x[k].x + x[k].y * x[k].y) + (x[k].z * x[k].z + x[k].w * x[k].w);
+    }
+  }
+  const float inv = 1.0f / sqrtf(group_sum(nn));
+  for (int q0 = 0; q0 < Q; q0 += R) {
+    const int rq = Q - q0 < R ? Q - q0 : R;
+    __syncthreads();                                       // every reader of the previous chunk is done
+    const float* src = text + (int64_t)q0 * E;
+    for (int i = tid; i < rq * E; i += 256) sT[i] = src[i];
+    __syncthreads();
+    if (use_cls) {
+      for (int q = wave; q < rq; q += 4) {                 // cls_logits = cls @ T^T  (:311)
+        float d = 0.f;
+        for (int i = lane; i < E; i += 64) d += sC[i] * sT[q * E + i];
+        d = wave_sum(d);
+        if (lane == 0) sCL[q] = d;
+      }
+      __syncthreads();
+    }
+    if (!wave_live) continue;
+    for (int q = 0; q < rq; ++q) {
+      float d = 0.f;
+#pragma unroll
+      for (int k = 0; k < NV; ++k) {
+        const int i = 4 * sl + 64 * k;
+        if (i < E) {
+          const float4 t4 = *reinterpret_cast<const float4*>(sT + q * E + i);
+          d += ((x[k].x * inv) * t4.x + (x[k].y * inv) * t4.y) + ((x[k].z * inv) * t4.z + (x[k].w * inv) * t4.w);
+        }
+      }
+      d = group_sum(d);
+      if (sl == 0 && t < n) {
+        if (use_cls && lambda != 0.f) d += sCL[q] * lambda;
+        logits[((int64_t)b * Q + q0 + q) * n + t] = d;
+      }
+    }
+  }
+}
+
 // ---- stitch -------------------------------------------------------------------------------------------------------
 // Write-once: a pixel's contributions are summed in registers in raster order of the tiles (the reference's `preds[...] += `
 // order, so the f32 sum is bit-identical), divided by the count and stored a single time.  The row test of a tile is wave-uniform
@@ -424,6 +537,170 @@ __global__ __launch_bounds__(256) void postprocess_multi_kernel(const float* __r
   labels[ooff + i] = arg;
 }
 
+// ---- fused label head: stitch -> softmax -> synonym merge -> argmax -> threshold, labels only, any Q ---------------------------
+// One 64 x 4 pixel block of one image, shared by the single-image and the multi-image kernel (so the two agree byte for byte).  The
+// stitched value of a query is stitch_kernel's: bilinear_tap taps, the covering tiles summed in raster order (the same candidate list and
+// the same fall-back beyond ST_MAXC), divided by the count.  No canvas exists: queries pass through the registers in chunks of ST_QC and
+// only a running maximum, the running sum of exp(v - max) and the best (value, class) pair survive a chunk.
+//   Online maximum and sum, not a second pass that recomputes the stitched values: the gathers are the cost of this kernel (four loads
+//   and seven multiply-adds per covering tile and query, all of it address-dependent), a second pass would double them, while the
+//   online form adds one expf per chunk of ST_QC queries (the rescale of the sum when the maximum moves).  The order of every operation
+//   is fixed by (pixel, query index), so repeats are byte-identical.
+// softmax is monotone, so the class of the largest class probability is the class of the largest scaled logit; among queries that
+// share that largest value the lowest class index wins (torch.argmax's first maximum).  Queries whose class lies outside [0,K) only
+// take part in the sum, as in postprocess_kernel.  conf = exp(v_best - v_max) / sum = 1 / sum exp(v_q - v_max).
+__device__ __forceinline__ void label_head_block(const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
+                                                 const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw,
+                                                 int up_h, int up_w, int pad_t, int pad_l, int H, int W, int bx0, int by0,
+                                                 const int32_t* __restrict__ query_idx, int K, float logit_scale, float prob_thd,
+                                                 int bg_idx, int64_t* __restrict__ labels, float* __restrict__ conf, int* s_list,
+                                                 int* s_count) {
+  const int lane = threadIdx.x & 63;
+  if ((threadIdx.x >> 6) == 0) {
+    int base = 0;
+    for (int t0 = 0; t0 < n_tiles; t0 += 64) {
+      const int t = t0 + lane;
+      bool hit = false;
+      if (t < n_tiles && (tile_image == nullptr || tile_image[t] == img)) {
+        const int y1 = win[t * 4 + 0], y2 = win[t * 4 + 1], x1 = win[t * 4 + 2], x2 = win[t * 4 + 3];
+        hit = y1 < by0 + 4 && y2 > by0 && x1 < bx0 + 64 && x2 > bx0;
+      }
+      const unsigned long long m = __ballot(hit);
+      const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+      if (hit && pos < ST_MAXC) s_list[pos] = t;
+      base += __popcll(m);
+    }
+    if (lane == 0) *s_count = base;
+  }
+  __syncthreads();
+  const int n_cand = *s_count;
+  const bool use_list = n_cand <= ST_MAXC;                         // pathological overlap (stride << crop): test every window
+  const int n_iter = use_list ? n_cand : n_tiles;
+  const int x = bx0 + lane;
+  const int y = __builtin_amdgcn_readfirstlane(by0 + (threadIdx.x >> 6));
+  if (y >= H) return;
+  const int64_t tile_sz = (int64_t)gh * gw;
+  float vmax = -INFINITY, sum = 0.f, best = -INFINITY;
+  int best_c = 0;
+  for (int q0 = 0; q0 < Q; q0 += ST_QC) {
+    float acc[ST_QC];
+#pragma unroll
+    for (int k = 0; k < ST_QC; ++k) acc[k] = 0.f;
+    float cnt = 0.f;
+    for (int it = 0; it < n_iter; ++it) {                              // raster order = the reference's add order
+      const int t = use_list ? s_list[it] : it;
+      if (!use_list && tile_image != nullptr && tile_image[t] != img) continue;
+      const int y1 = win[t * 4 + 0], y2 = win[t * 4 + 1];
+      if (y < y1 || y >= y2) continue;                                 // wave-uniform: the whole wave skips the tile
+      const int x1 = win[t * 4 + 2], x2 = win[t * 4 + 3];
+      if (x < x1 || x >= x2 || x >= W) continue;
+      int ya, yb, xa, xb; float wy0, wy1, wx0, wx1;
+      bilinear_tap(y - y1 + pad_t, gh, up_h, ya, yb, wy0, wy1);
+      bilinear_tap(x - x1 + pad_l, gw, up_w, xa, xb, wx0, wx1);
+      const float* base = tile_logits + ((int64_t)t * Q + q0) * tile_sz;
+#pragma unroll
+      for (int k = 0; k < ST_QC; ++k) {
+        if (q0 + k < Q) {
+          const float* p = base + (int64_t)k * tile_sz;
+          const float top = p[ya * gw + xa] * wx0 + p[ya * gw + xb] * wx1;
+          const float bot = p[yb * gw + xa] * wx0 + p[yb * gw + xb] * wx1;
+          acc[k] += top * wy0 + bot * wy1;
+        }
+      }
+      cnt += 1.f;
+    }
+    {
+#pragma clang fp contract(off)        // the scaled logit is rounded before the subtraction, as postprocess_kernel compiles it
+      float cm = -INFINITY;
+#pragma unroll
+      for (int k = 0; k < ST_QC; ++k)
+        if (q0 + k < Q) { acc[k] = (cnt > 0.f ? acc[k] / cnt : 0.f) * logit_scale; cm = fmaxf(cm, acc[k]); }
+      if (cm > vmax) { sum *= expf(vmax - cm); vmax = cm; }            // the first chunk: sum = 0 * exp(-inf) = 0
+#pragma unroll
+      for (int k = 0; k < ST_QC; ++k)
+        if (q0 + k < Q) {
+          sum += expf(acc[k] - vmax);
+          const int c = K == Q ? q0 + k : query_idx[q0 + k];
+          if (c >= 0 && c < K && (acc[k] > best || (acc[k] == best && c < best_c))) { best = acc[k]; best_c = c; }
+        }
+    }
+  }
+  if (x >= W) return;
+  const float cf = expf(best - vmax) / sum;
+  const int64_t o = (int64_t)y * W + x;
+  labels[o] = cf < prob_thd ? bg_idx : best_c;
+  if (conf) conf[o] = cf;
+}
+
+__global__ __launch_bounds__(256) void label_head_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows,
+                                                         int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t, int pad_l, int H,
+                                                         int W, const int32_t* __restrict__ query_idx, int K, float logit_scale,
+                                                         float prob_thd, int bg_idx, int64_t* __restrict__ labels,
+                                                         float* __restrict__ conf) {
+  __shared__ int s_list[ST_MAXC];
+  __shared__ int s_count;
+  label_head_block(tile_logits, windows, nullptr, 0, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, blockIdx.x * 64, blockIdx.y * 4,
+                   query_idx, K, logit_scale, prob_thd, bg_idx, labels, conf, s_list, &s_count);
+}
+
+// The tiles of N images (sg_stitch_multi's descriptors); labels / conf of image n at out_offset[n] pixels of the flat outputs.
+__global__ __launch_bounds__(256) void label_head_multi_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows,
+                                                               const int32_t* __restrict__ tile_image, int T, int Q, int gh, int gw,
+                                                               int up_h, int up_w, int pad_t, int pad_l,
+                                                               const int32_t* __restrict__ image_hw, const int32_t* __restrict__ image_tiles,
+                                                               const int64_t* __restrict__ out_offset, const int64_t* __restrict__ block_prefix,
+                                                               int N, int64_t out_pixels, const int32_t* __restrict__ query_idx, int K,
+                                                               float logit_scale, float prob_thd, int bg_idx, int64_t* __restrict__ labels,
+                                                               float* __restrict__ conf) {
+  __shared__ int s_list[ST_MAXC];
+  __shared__ int s_count;
+  const int n = image_of_block(block_prefix, N, blockIdx.x);
+  const int H = image_hw[2 * n], W = image_hw[2 * n + 1];
+  const int t_first = image_tiles[2 * n], n_tiles = image_tiles[2 * n + 1];
+  const int64_t off = out_offset[n];
+  // a descriptor that would read or write outside the buffers: the whole block leaves (block-uniform, before any barrier)
+  if (H <= 0 || W <= 0 || t_first < 0 || n_tiles <= 0 || t_first + n_tiles > T || off < 0 || off + (int64_t)H * W > out_pixels) return;
+  const int64_t local = blockIdx.x - block_prefix[n];
+  const int bw = (W + 63) / 64;
+  if (local >= (int64_t)bw * ((H + 3) / 4)) return;
+  label_head_block(tile_logits + (int64_t)t_first * Q * gh * gw, windows + (int64_t)t_first * 4, tile_image + t_first, n, n_tiles, Q, gh, gw,
+                   up_h, up_w, pad_t, pad_l, H, W, (int)(local % bw) * 64, (int)(local / bw) * 4, query_idx, K, logit_scale, prob_thd,
+                   bg_idx, labels + off, conf ? conf + off : nullptr, s_list, &s_count);
+}
+
+// ---- postprocess for any Q: several passes over the canvas, nothing held per query ------------------------------------------------
+// Pass 1 the maximum, pass 2 the sum (postprocess_kernel's order), pass 3 the per-class maximum, written through probs[class(q)] by the
+// pixel's own thread.  A class starts at what postprocess_kernel's `any_other` rule gives a class without queries: 0 when some query
+// belongs to another class (the zeros of probabilities * one_hot take part in the max), -inf when every query is this class's.
+// Plain and correct, not tuned: Q > PP_MAX_Q only.
+__global__ __launch_bounds__(256) void postprocess_wide_kernel(const float* __restrict__ logits, const int32_t* __restrict__ query_idx,
+                                                               int Q, int K, int64_t HW, float logit_scale, float prob_thd, int bg_idx,
+                                                               float* probs, int64_t* __restrict__ labels) {
+#pragma clang fp contract(off)          // the scaled logit is rounded before the subtraction, as postprocess_kernel compiles it
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= HW) return;
+  const bool ident = K == Q;                                            // postprocess_kernel: class(q) = q, query_idx is not read
+  bool all_same = true;
+  const int c0 = ident ? 0 : query_idx[0];
+  for (int q = 1; q < Q; ++q) all_same = all_same && (ident ? q : query_idx[q]) == c0;
+  float mx = -INFINITY;
+  for (int q = 0; q < Q; ++q) mx = fmaxf(mx, logits[q * HW + i] * logit_scale);
+  float sum = 0.f;
+  for (int q = 0; q < Q; ++q) sum += expf(logits[q * HW + i] * logit_scale - mx);
+  if (probs)
+    for (int c = 0; c < K; ++c) probs[c * HW + i] = (all_same && c == c0) ? -INFINITY : 0.f;
+  float best = -INFINITY; int arg = 0;
+  for (int q = 0; q < Q; ++q) {
+    const int c = ident ? q : query_idx[q];
+    if (c < 0 || c >= K) continue;
+    const float p = expf(logits[q * HW + i] * logit_scale - mx) / sum;
+    if (probs) { float* d = probs + c * HW + i; *d = fmaxf(*d, p); }
+    if (p > best || (p == best && c < arg)) { best = p; arg = c; }        // the first maximum over classes wins (torch argmax)
+  }
+  if (best < prob_thd) arg = bg_idx;
+  labels[i] = arg;
+}
+
 // ---- label / confidence images (segmentor.py:501-531, 580-608) ---------------------------------------------------------
 // mask  = palette[clip(label, 0, K-1)]                                (_colorize_mask)
 // heat  = (g, 0, 255 - g), g = uint8(clip(nan_to_num(max_k probs), 0, 1) * 255)   (_to_colormap, the branch without OpenCV)
@@ -669,6 +946,77 @@ extern "C" int sg_postprocess_multi(const float* canvases, const int32_t* canvas
   auto kern = Q <= 16 ? postprocess_multi_kernel<16> : postprocess_multi_kernel<PP_MAX_Q>;
   hipLaunchKernelGGL(kern, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), canvases, canvas_hw, canvas_offset, out_hw, out_offset,
                      block_prefix, N, canvas_elems, out_pixels, query_idx, Q, K, logit_scale, prob_thd, bg_idx, probs, labels);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+// sg_cosine_logits for any Q.  A text matrix that fits in LDS whole is one chunk: that is cosine_logits_kernel itself (32 tokens per
+// staging instead of 16, and the same bits as sg_cosine_logits by construction).  Beyond it the rows go through LDS in chunks inside one
+// launch of cosine_logits_wide_kernel.
+extern "C" int sg_cosine_logits_wide(const float* tokens, const float* cls, const float* text, int B, int n, int E, int Q,
+                                     float global_debias_factor, float cls_token_lambda, float* logits, sg_stream s) {
+  SG_REQUIRE(tokens && text && logits, "sg_cosine_logits_wide: null pointer");
+  SG_REQUIRE(B > 0 && n > 0 && E > 0 && Q > 0 && B < 65536, "sg_cosine_logits_wide: bad shape B=%d n=%d E=%d Q=%d", B, n, E, Q);
+  SG_REQUIRE(cls || (global_debias_factor == 0.f && cls_token_lambda == 0.f), "sg_cosine_logits_wide: cls required for debias / lambda");
+  SG_REQUIRE(E <= 64 * CL_MAXV && E % 4 == 0, "sg_cosine_logits_wide: E=%d must be a multiple of 4 and <= %d", E, 64 * CL_MAXV);
+  SG_REQUIRE((((uintptr_t)tokens) & 15) == 0, "sg_cosine_logits_wide: tokens must be 16-byte aligned");
+  SG_REQUIRE((int64_t)Q * n <= INT64_MAX / B, "sg_cosine_logits_wide: output too large");
+  if (((size_t)Q * E + E + Q) * sizeof(float) <= 160 * 1024)
+    return sg_cosine_logits(tokens, cls, text, B, n, E, Q, global_debias_factor, cls_token_lambda, logits, s);
+  const int fit = (160 * 1024 / (int)sizeof(float) - E) / (E + 1);           // rows R with (R * E + E + R) * 4 <= 160 KiB; >= 19 at E = 2048
+  const int R = Q < fit ? Q : fit;
+  const size_t lds = ((size_t)R * E + E + R) * sizeof(float);
+  const int nv = (E + 63) / 64;
+  auto kern = nv <= 8 ? cosine_logits_wide_kernel<8>
+                      : (nv <= 12 ? cosine_logits_wide_kernel<12> : (nv <= 16 ? cosine_logits_wide_kernel<16> : cosine_logits_wide_kernel<CL_MAXV>));
+  if (lds > 48 * 1024) SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds));
+  hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(n, CLW_TPB), (unsigned)B), dim3(256), lds, as_stream(s), tokens, cls, text, n, E, Q, R,
+                     global_debias_factor, cls_token_lambda, logits);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_postprocess_wide(const float* logits, const int32_t* query_idx, int Q, int K, int H, int W, float logit_scale,
+                                   float prob_thd, int bg_idx, float* probs, int64_t* labels, sg_stream s) {
+  SG_REQUIRE(logits && query_idx && labels, "sg_postprocess_wide: null pointer");
+  SG_REQUIRE(Q > 0 && K > 0 && K <= Q && H > 0 && W > 0, "sg_postprocess_wide: Q=%d K=%d H=%d W=%d unsupported", Q, K, H, W);
+  const int64_t HW = (int64_t)H * W;
+  SG_REQUIRE(cdiv(HW, 256) <= INT32_MAX, "sg_postprocess_wide: image too large for one launch");
+  hipLaunchKernelGGL(postprocess_wide_kernel, dim3((unsigned)cdiv(HW, 256)), dim3(256), 0, as_stream(s), logits, query_idx, Q, K, HW,
+                     logit_scale, prob_thd, bg_idx, probs, labels);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_label_head(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t,
+                             int pad_l, int H, int W, const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx,
+                             int64_t* labels, float* conf, sg_stream s) {
+  SG_REQUIRE(tile_logits && windows && query_idx && labels, "sg_label_head: null pointer");
+  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && H > 0 && W > 0,
+             "sg_label_head: bad shape T=%d Q=%d gh=%d gw=%d up=%dx%d H=%d W=%d", T, Q, gh, gw, up_h, up_w, H, W);
+  SG_REQUIRE(K > 0 && K <= Q, "sg_label_head: K=%d must lie in [1, Q=%d]", K, Q);
+  SG_REQUIRE(cdiv(H, 4) < 65536, "sg_label_head: canvas too tall for one launch");
+  hipLaunchKernelGGL(label_head_kernel, dim3((unsigned)cdiv(W, 64), (unsigned)cdiv(H, 4)), dim3(256), 0, as_stream(s), tile_logits, windows,
+                     T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, query_idx, K, logit_scale, prob_thd, bg_idx, labels, conf);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_label_head_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh, int gw,
+                                   int up_h, int up_w, int pad_t, int pad_l, const int32_t* image_hw, const int32_t* image_tiles,
+                                   const int64_t* out_offset, const int64_t* block_prefix, int N, int64_t total_blocks, int64_t out_pixels,
+                                   const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx, int64_t* labels,
+                                   float* conf, sg_stream s) {
+  SG_REQUIRE(tile_logits && windows && tile_image && image_hw && image_tiles && out_offset && block_prefix && query_idx && labels,
+             "sg_label_head_multi: null pointer");
+  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && N > 0 && N <= T,
+             "sg_label_head_multi: bad shape T=%d Q=%d gh=%d gw=%d N=%d", T, Q, gh, gw, N);
+  SG_REQUIRE(K > 0 && K <= Q, "sg_label_head_multi: K=%d must lie in [1, Q=%d]", K, Q);
+  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "sg_label_head_multi: total_blocks=%lld outside (0, 2^31)", (long long)total_blocks);
+  SG_REQUIRE(out_pixels > 0, "sg_label_head_multi: out_pixels=%lld holds no image", (long long)out_pixels);
+  hipLaunchKernelGGL(label_head_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q,
+                     gh, gw, up_h, up_w, pad_t, pad_l, image_hw, image_tiles, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale,
+                     prob_thd, bg_idx, labels, conf);
   SG_LAUNCH_CHECK();
   return SG_OK;
 }

@@ -241,6 +241,10 @@ def weak_token_replace(feats, attn_diag, gh: int, gw: int, top_k: int = 10):
     return feats, idx
 
 
+COSINE_LDS_BYTES = 160 * 1024      # what sg_cosine_logits stages in LDS at most: (Q*E + E + Q) floats (head.hip)
+POSTPROCESS_MAX_Q = 64             # PP_MAX_Q of sg_postprocess / sg_postprocess_multi (head.hip); beyond it: sg_postprocess_wide
+
+
 @on_tensor_device
 def cosine_logits(tokens, cls, text, global_debias_factor: float = 0.0, cls_token_lambda: float = 0.0, two_plane: bool = False):
     """tokens [B,n,E], cls [B,E] or None, text [Q,E] -> logits [B,Q,n] (segmentor.py:309-336,374-386).
@@ -255,6 +259,10 @@ def cosine_logits(tokens, cls, text, global_debias_factor: float = 0.0, cls_toke
     if two_plane and float(global_debias_factor) == 0.0:
         check(lib.sg_cosine_logits_two_plane(ptr(tokens), ptr(cls), ptr(text), B, n, E, Q, float(cls_token_lambda), ptr(out), stream_ptr()),
               "sg_cosine_logits_two_plane")
+        return out
+    if (Q * E + E + Q) * 4 > COSINE_LDS_BYTES:            # sg_cosine_logits would refuse ("exceeds LDS"): the text rows go through LDS in chunks
+        check(lib.sg_cosine_logits_wide(ptr(tokens), ptr(cls), ptr(text), B, n, E, Q, float(global_debias_factor), float(cls_token_lambda),
+                                        ptr(out), stream_ptr()), "sg_cosine_logits_wide")
         return out
     check(lib.sg_cosine_logits(ptr(tokens), ptr(cls), ptr(text), B, n, E, Q, float(global_debias_factor), float(cls_token_lambda),
                                ptr(out), stream_ptr()), "sg_cosine_logits")
@@ -299,9 +307,32 @@ def postprocess(logits, query_idx, num_classes: int, logit_scale: float, prob_th
     qi = query_idx.to(device=logits.device, dtype=torch.int32).contiguous()
     probs = torch.empty(num_classes, H, W, dtype=torch.float32, device=logits.device) if want_probs else None
     labels = torch.empty(1, H, W, dtype=torch.int64, device=logits.device)
-    check(lib.sg_postprocess(ptr(logits), ptr(qi), Q, num_classes, H, W, float(logit_scale), float(prob_thd), int(bg_idx),
-                             ptr(probs), ptr(labels), stream_ptr()), "sg_postprocess")
+    entry, name = (lib.sg_postprocess, "sg_postprocess") if Q <= POSTPROCESS_MAX_Q else (lib.sg_postprocess_wide, "sg_postprocess_wide")
+    check(entry(ptr(logits), ptr(qi), Q, num_classes, H, W, float(logit_scale), float(prob_thd), int(bg_idx),
+                ptr(probs), ptr(labels), stream_ptr()), name)
     return probs, labels
+
+
+@on_tensor_device
+def label_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, query_idx, num_classes: int, logit_scale: float, prob_thd: float,
+               bg_idx: int, want_conf: bool = False):
+    """sg_label_head: ``stitch`` + ``postprocess`` without the canvas, for any Q.  tile_logits [T,Q,gh,gw]; windows int32 [T,4]
+    -> labels int64 [1,H,W], or (labels, conf f32 [H,W] = the winning class's probability) with ``want_conf``."""
+    lib = _lib.load()
+    tile_logits = _f32(tile_logits)
+    windows = windows.to(device=tile_logits.device, dtype=torch.int32).contiguous()
+    _require_gpu(tile_logits)
+    T, Q, gh, gw = tile_logits.shape
+    H, W = canvas_hw
+    qi = query_idx.to(device=tile_logits.device, dtype=torch.int32).contiguous()
+    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T:
+        raise ValueError(f"label_head: {T} tiles of {Q} queries, but {windows.numel() // 4} windows and {qi.numel()} query indices")
+    labels = torch.empty(1, H, W, dtype=torch.int64, device=tile_logits.device)
+    conf = torch.empty(H, W, dtype=torch.float32, device=tile_logits.device) if want_conf else None
+    check(lib.sg_label_head(ptr(tile_logits), ptr(windows), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1], H, W, ptr(qi),
+                            int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx), ptr(labels), ptr(conf), stream_ptr()),
+          "sg_label_head")
+    return (labels, conf) if want_conf else labels
 
 
 def _prefix(counts):
@@ -334,6 +365,41 @@ def stitch_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, imag
           "sg_stitch_multi")
     views = [canvases[Q * pix[n]:Q * pix[n + 1]].view(Q, h, w) for n, (h, w) in enumerate(image_hw)]
     return canvases, views
+
+
+@on_tensor_device
+def label_head_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, query_idx, num_classes: int,
+                     logit_scale: float, prob_thd: float, bg_idx: int, want_conf: bool = False):
+    """sg_label_head_multi: the labels of N images in one launch, from their tile logits (arguments as ``stitch_multi`` plus the
+    post-process parameters).  -> (list of labels int64 [1,H,W], the flat int64 buffer they are views of, images back to back), plus
+    the list of conf f32 [H,W] maps as a third result with ``want_conf``.  Equals ``label_head`` per image byte for byte."""
+    lib = _lib.load()
+    tile_logits = _f32(tile_logits)
+    _require_gpu(tile_logits)
+    dev = tile_logits.device
+    T, Q, gh, gw = tile_logits.shape
+    N = len(image_hw)
+    qi = query_idx.to(device=dev, dtype=torch.int32).contiguous()
+    windows = torch.as_tensor(windows, dtype=torch.int32).to(dev).contiguous()
+    tile_image = torch.as_tensor(tile_image, dtype=torch.int32).to(dev).contiguous()
+    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T or int(tile_image.numel()) != T or len(image_tiles) != N:
+        raise ValueError("label_head_multi: tile logits, windows, tile_image, image descriptors and query indices disagree in size")
+    if any(f < 0 or c <= 0 or f + c > T for f, c in image_tiles):
+        raise ValueError(f"label_head_multi: image_tiles {list(image_tiles)} leave the {T} tiles")
+    pix = _prefix(h * w for h, w in image_hw)
+    blocks = _prefix(-(-w // 64) * -(-h // 4) for h, w in image_hw)
+    i32 = torch.tensor([list(hw) for hw in image_hw] + [list(ft) for ft in image_tiles], dtype=torch.int32).to(dev)
+    i64 = torch.tensor(pix[:-1] + blocks, dtype=torch.int64).to(dev)
+    labels = torch.empty(pix[-1], dtype=torch.int64, device=dev)
+    conf = torch.empty(pix[-1], dtype=torch.float32, device=dev) if want_conf else None
+    check(lib.sg_label_head_multi(ptr(tile_logits), ptr(windows), ptr(tile_image), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1],
+                                  ptr(i32), ptr(i32[N:]), ptr(i64), ptr(i64[N:]), N, blocks[-1], pix[-1], ptr(qi), int(num_classes),
+                                  float(logit_scale), float(prob_thd), int(bg_idx), ptr(labels), ptr(conf), stream_ptr()),
+          "sg_label_head_multi")
+    lab = [labels[pix[n]:pix[n + 1]].view(1, h, w) for n, (h, w) in enumerate(image_hw)]
+    if want_conf:
+        return lab, labels, [conf[pix[n]:pix[n + 1]].view(h, w) for n, (h, w) in enumerate(image_hw)]
+    return lab, labels
 
 
 @on_tensor_device

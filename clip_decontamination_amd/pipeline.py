@@ -307,12 +307,20 @@ def pack_scenes(scenes, device, fill=None) -> Tuple[torch.Tensor, List[Tuple[int
     return buf, shapes
 
 
+LABEL_HEADS = ("auto", "fused", "canvas")
+
+
 class SegPipeline:
     def __init__(self, net: HipCLIP, text: torch.Tensor, query_idx: torch.Tensor, model_type: str = "SegEarth",
                  ignore_residual: bool = True, cls_token_lambda: float = 0.0, global_debias_factor: float = 0.0,
                  logit_scale: float = 50.0, prob_thd: float = 0.0, bg_idx: int = 0, apply_similarity_enhancement: bool = False,
                  upsampler=None, tiles_per_launch: int = 32, cross_tile_fusion: Optional[dict] = None, apply_ctd: bool = False,
-                 tile_group=None, apply_layer_fusion: bool = False, layer_fusion_lambda: float = 0.5):
+                 tile_group=None, apply_layer_fusion: bool = False, layer_fusion_lambda: float = 0.5, label_head: str = "auto"):
+        if label_head not in LABEL_HEADS:
+            raise ValueError(f"label_head must be one of {LABEL_HEADS}, got {label_head!r}")
+        # the labels-only tail (``labels_from_tiles``): "canvas" = stitch + postprocess through the [Q,H,W] canvas, "fused" = sg_label_head
+        # (no canvas, any Q), "auto" = the canvas wherever it works (Q <= 64) and the fused head beyond
+        self.label_head = label_head
         self.apply_layer_fusion, self.layer_fusion_lambda = bool(apply_layer_fusion), float(layer_fusion_lambda)
         self.net = net
         self.visual = net.visual
@@ -339,6 +347,19 @@ class SegPipeline:
 
     def _stitch(self, tile_logits, windows, up_hw, pad_tl, canvas_hw):
         return ops.stitch(tile_logits, windows, up_hw, pad_tl, canvas_hw)
+
+    def fused_label_head(self) -> bool:
+        """Whether the labels-only tail runs the fused head (sg_label_head) instead of the canvas path."""
+        mode = getattr(self, "label_head", "auto")
+        return mode == "fused" or (mode == "auto" and self.num_queries > ops.POSTPROCESS_MAX_Q)
+
+    def labels_from_tiles(self, tile_logits, windows, up_hw, pad_tl, canvas_hw):
+        """Tile logits [T,Q,gh,gw] + windows [T,4] -> labels int64 [1,H,W]: the labels-only tail of every path that returns no
+        canvas and no probabilities.  A canvas band is a canvas with shifted windows."""
+        if self.fused_label_head():
+            return ops.label_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, self.query_idx, self.num_classes, self.logit_scale,
+                                  self.prob_thd, self.bg_idx)
+        return self.postprocess(self._stitch(tile_logits, windows, up_hw, pad_tl, canvas_hw), want_probs=False)[1]
 
     def _pre_head(self, tok, cls):
         """Global debias (+ CTD) when they cannot stay fused in the logits kernel: returns (tokens, remaining debias factor)."""
@@ -431,8 +452,16 @@ class SegPipeline:
         return canvas.unsqueeze(0)
 
     def sharded_canvas_band(self, scene, stride, crop, group):
-        """Tiles partitioned over the ranks of ``group`` -> this rank's band of the stitched canvas: (band [Q, rows, W], first row,
-        band boundaries of all ranks).  Patch-grid logits (44 kB per tile) are rebuilt everywhere with ONE all-gather (RCCL over xGMI);
+        """``sharded_band_tiles`` stitched -> (this rank's band of the canvas, its first row, the boundaries of every rank's band)."""
+        tiles, w_band, up_hw, pad_tl, hw, y0, yb = self.sharded_band_tiles(scene, stride, crop, group)
+        if hw[0] <= 0:
+            return tiles.new_zeros((self.num_queries, 0, hw[1])), y0, yb
+        return self._stitch(tiles, w_band, up_hw, pad_tl, hw), y0, yb
+
+    def sharded_band_tiles(self, scene, stride, crop, group):
+        """Tiles partitioned over the ranks of ``group`` -> this rank's band of the canvas, as what the stitch takes: (tile logits of the tiles
+        that overlap the band, their windows in band coordinates, up_hw, pad_tl, (rows, W), first row, band boundaries of all ranks);
+        rows = 0 for a rank without a band.  Patch-grid logits (44 kB per tile) are rebuilt everywhere with ONE all-gather (RCCL over xGMI);
         per-pixel logits (upsampler: 16-32 MB per tile) travel point to point, only the tiles that straddle a band edge.  Either way each
         rank stitches ONLY its own band, so the tail scales with the ranks too.  The stitch itself is identical given identical tile
         logits (write-once: the covering tiles are averaged in raster order, and all of them are present); the tile logits of a rank
@@ -459,10 +488,10 @@ class SegPipeline:
             tiles, first = exchange_halo_tiles(local, wins, world, rank, group, plan)
         y0, y1 = yb[rank], yb[rank + 1]
         if y1 <= y0:
-            return tiles.new_zeros((self.num_queries, 0, W)), y0, yb
+            return tiles, None, up_hw, pad_tl, (0, W), y0, yb
         w_band = torch.tensor(wins[first:first + tiles.shape[0]], dtype=torch.int32, device=self.device)
         w_band[:, 0:2] -= y0
-        return self._stitch(tiles, w_band, up_hw, pad_tl, (y1 - y0, W)), y0, yb
+        return tiles, w_band, up_hw, pad_tl, (y1 - y0, W), y0, yb
 
     def gather_bands(self, band: torch.Tensor, yb, H: int, group) -> torch.Tensor:
         """[C, rows_r, W] bands of every rank -> the full [C, H, W] on every rank (one all_gather_into_tensor of bands padded to
@@ -484,13 +513,15 @@ class SegPipeline:
         ``gather_labels`` is False)."""
         group = resolve_tile_group(group if group is not None else self.tile_group)
         if group is None:
-            _, labels = self.postprocess(self.forward_slide(scene, stride, crop)[0], want_probs=False)
-            return labels
-        band, y0, yb = self.sharded_canvas_band(scene, stride, crop, group)
-        if band.shape[1] > 0:
-            _, lab = self.postprocess(band, want_probs=False)
+            H, W, stride, crop, wins, tile_hw, pad_tl, up_hw, grid = self._geometry(scene, stride, crop)
+            tl = self.tile_logits(scene, wins, tile_hw, grid_of_tiles=grid)
+            win_dev = torch.tensor(wins, dtype=torch.int32, device=self.device)
+            return self.labels_from_tiles(tl, win_dev, up_hw, pad_tl, (H, W))
+        tiles, w_band, up_hw, pad_tl, hw, y0, yb = self.sharded_band_tiles(scene, stride, crop, group)
+        if hw[0] > 0:
+            lab = self.labels_from_tiles(tiles, w_band, up_hw, pad_tl, hw)
         else:
-            lab = torch.empty((1, 0, band.shape[-1]), dtype=torch.int64, device=band.device)
+            lab = torch.empty((1, 0, hw[1]), dtype=torch.int64, device=tiles.device)
         if not gather_labels:
             return lab, y0
         return self.gather_bands(lab, yb, yb[-1], group)
@@ -543,8 +574,16 @@ class SegPipeline:
     pack_fill = None            # value written into a ragged pack buffer's padding (None: left uninitialised -- it is never read)
 
     def _packed_canvases(self, scenes, stride, crop):
-        """Yields (image indices, flat canvas buffer, its [Q,H,W] views) per flush group: the packed tower over the group's chunks,
-        cross-tile fusion per image, the head, and one sg_stitch_multi launch."""
+        """Yields (image indices, flat canvas buffer, its [Q,H,W] views) per flush group: ``_packed_tiles`` and one sg_stitch_multi
+        launch."""
+        for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(scenes, stride, crop, 4 * self.num_queries):
+            canvases, views = ops.stitch_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles)
+            yield idx, canvases, views
+
+    def _packed_tiles(self, scenes, stride, crop, pixel_bytes: int):
+        """Yields, per flush group, what a multi-image stitch takes: (image indices, tile logits, windows, image of each tile, up_hw,
+        pad_tl, [(H, W)] per image, [(first tile, count)] per image) -- the packed tower over the group's chunks, cross-tile fusion per
+        image and the head.  ``pixel_bytes``: what the caller will allocate per image pixel (the planner's flush bound counts it)."""
         if self.tile_group is not None:
             raise ValueError("packed inference shards images over ranks, not tiles: with tile_group set use forward_slide / "
                              "segment_scene per image")
@@ -558,7 +597,7 @@ class SegPipeline:
             tok = gh * gw * self.visual.cfg.embed_dim * 4 if self.cross_tile_fusion is not None else 0
             return 4 * Q * oh * ow + tok
 
-        groups = plan_images(shapes, stride, crop, P, self.tiles_per_launch, tile_bytes, 4 * Q, self.flush_bytes)
+        groups = plan_images(shapes, stride, crop, P, self.tiles_per_launch, tile_bytes, pixel_bytes, self.flush_bytes)
         for g in groups:
             th, tw = g.tile_hw
             l, r, t, b = compute_padsize(th, tw, P)
@@ -566,9 +605,8 @@ class SegPipeline:
                 tl = self._packed_tile_logits(buf, g, f)
                 imgs = range(f.img_lo, f.img_hi)
                 local = [k - f.img_lo for k in imgs for _ in range(g.n_tiles[k])]
-                canvases, views = ops.stitch_multi(tl, g.windows[f.tile_lo:f.tile_hi], local, (th + t + b, tw + l + r), (t, l),
-                                            [g.shapes[k] for k in imgs], [(g.first_tile[k] - f.tile_lo, g.n_tiles[k]) for k in imgs])
-                yield [g.images[k] for k in imgs], canvases, views
+                yield ([g.images[k] for k in imgs], tl, g.windows[f.tile_lo:f.tile_hi], local, (th + t + b, tw + l + r), (t, l),
+                       [g.shapes[k] for k in imgs], [(g.first_tile[k] - f.tile_lo, g.n_tiles[k]) for k in imgs])
 
     def _packed_tile_logits(self, buf, g: TileSizeGroup, f: FlushGroup) -> torch.Tensor:
         v = self.visual
@@ -629,7 +667,31 @@ class SegPipeline:
     def label_groups(self, scenes, stride, crop, want_probs: bool = False, ori_shapes=None):
         """The whole packed path to labels, flush group by flush group: one sg_stitch_multi and one sg_postprocess_multi launch each
         (the resize to ``ori_shapes`` fused into the latter).  Yields (image indices, list of probs [K,H,W] or None, list of labels
-        [1,H,W], the flat int64 buffer those label maps are views of, in that order of images)."""
+        [1,H,W], the flat int64 buffer those label maps are views of, in that order of images).
+        Labels alone at the images' own sizes with the fused head selected (``label_head``): one sg_label_head_multi launch per flush
+        group and no canvas.  Probabilities or a resize keep the canvas; beyond 64 queries they go image by image through
+        ``ops.postprocess`` (its wide form) on the group's canvases."""
+        no_resize = ori_shapes is None or all(o is None for o in ori_shapes)
+        if not want_probs and no_resize and self.fused_label_head():
+            for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(scenes, stride, crop, 8):
+                lab, flat = ops.label_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes,
+                                                 self.logit_scale, self.prob_thd, self.bg_idx)
+                yield idx, [None] * len(idx), lab, flat
+            return
+        if self.num_queries > ops.POSTPROCESS_MAX_Q:
+            for idx, canvases, views in self._packed_canvases(scenes, stride, crop):
+                prb, lab = [], []
+                for n, k in enumerate(idx):
+                    c = views[n]
+                    if not no_resize and ori_shapes[k] is not None and tuple(ori_shapes[k]) != tuple(c.shape[1:]):
+                        c = ops.resize_bilinear(c, tuple(ori_shapes[k]))
+                    p_, l_ = self.postprocess(c, want_probs=want_probs)
+                    prb.append(p_); lab.append(l_.reshape(-1))
+                flat = torch.cat(lab)
+                pix = ops._prefix(l_.numel() for l_ in lab)
+                hw = [tuple(views[n].shape[1:]) if no_resize or ori_shapes[k] is None else tuple(ori_shapes[k]) for n, k in enumerate(idx)]
+                yield idx, prb, [flat[pix[n]:pix[n + 1]].view(1, *hw[n]) for n in range(len(lab))], flat
+            return
         for idx, canvases, views in self._packed_canvases(scenes, stride, crop):
             chw = [tuple(c.shape[1:]) for c in views]
             ohw = [chw[n] if ori_shapes is None or ori_shapes[k] is None else tuple(ori_shapes[k]) for n, k in enumerate(idx)]

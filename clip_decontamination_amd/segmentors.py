@@ -129,7 +129,14 @@ class _HipSegmentorBase(_Base):
     def _setup(self, clip_type, vit_type, model_type, name_path, device, ignore_residual, prob_thd, logit_scale, slide_stride,
                slide_crop, cls_token_lambda, bg_idx, apply_sim_feat_up, sim_feat_up_cfg, global_debias_factor=0.0,
                checkpoint=None, text_features=None, text_encoder: Optional[Callable] = None, precision="f16x2",
-               synthetic_ok=False, tiles_per_launch=None, jbu_checkpoint_ok=True, tokenizer: Optional[Callable] = None, tile_group=None):
+               synthetic_ok=False, tiles_per_launch=None, jbu_checkpoint_ok=True, tokenizer: Optional[Callable] = None, tile_group=None,
+               label_head="auto"):
+        from .pipeline import LABEL_HEADS
+        if label_head not in LABEL_HEADS:
+            raise ValueError(f"label_head must be one of {LABEL_HEADS}, got {label_head!r}")
+        # the labels-only tail: "canvas" = stitch + post-process through the [Q,H,W] canvas, "fused" = sg_label_head (no canvas, any
+        # number of queries), "auto" = the canvas wherever it works (Q <= 64) and the fused head beyond
+        self.label_head = label_head
         self.tile_group = tile_group                         # opt-in tile sharding (pipeline.resolve_tile_group); None = off
         if clip_type == "BLIP":
             raise NotImplementedError("clip_type='BLIP' is a different backbone (vendored BLIP) and is out of scope for the HIP path")
@@ -232,7 +239,7 @@ class _HipSegmentorBase(_Base):
                            upsampler=self.upsampler, tiles_per_launch=self._tiles_per_launch,
                            cross_tile_fusion=getattr(self, "cross_tile_fusion_cfg", None), apply_ctd=getattr(self, "apply_ctd", False),
                            tile_group=getattr(self, "tile_group", None), apply_layer_fusion=getattr(self, "apply_layer_fusion", False),
-                           layer_fusion_lambda=getattr(self, "layer_fusion_lambda", 0.5))
+                           layer_fusion_lambda=getattr(self, "layer_fusion_lambda", 0.5), label_head=getattr(self, "label_head", "auto"))
 
     def forward_feature(self, img, logit_size=None, tile_h_idx=None, tile_w_idx=None):
         """Reference segmentor.py:286-392.  img [B,3,H,W] -> logits [B,Q,h,w]."""
@@ -263,6 +270,10 @@ class _HipSegmentorBase(_Base):
             batch_img_metas = [dict(ori_shape=inputs.shape[2:], img_shape=inputs.shape[2:], pad_shape=inputs.shape[2:],
                                     padding_size=[0, 0, 0, 0])] * inputs.shape[0]
         inputs = inputs.float()
+        if data_samples is None and self.slide_crop > 0:
+            # labels only, at the image's own size, of the first image (what postprocess_result returns without data samples): the
+            # labels-only tail, which needs no canvas with the fused head (``label_head``)
+            return self._pipeline().segment_scene(inputs[0], self.slide_stride, self.slide_crop)
         if self.slide_crop > 0:
             seg_logits = self.forward_slide(inputs, batch_img_metas, self.slide_stride, self.slide_crop)
         else:
@@ -275,7 +286,10 @@ class _HipSegmentorBase(_Base):
         launch per flush group (SegPipeline.segment_scenes).  inputs: a list of [3,H,W] images of any sizes or a [B,3,H,W] batch.
         Fills each data sample exactly as ``predict`` does (seg_logits, pred_sem_seg, result_dir / heatmap_dir PNGs) and returns
         them; with ``data_samples=None`` returns one label map [1,H,W] per image.  In f32 the results equal ``predict`` per image bit
-        for bit; in the 2-byte modes a larger launch may take a different GEMM path and differ by 2-byte rounding."""
+        for bit; in the 2-byte modes a larger launch may take a different GEMM path and differ by 2-byte rounding.  With more than 64
+        queries the one-launch multi-canvas post-process does not apply: data samples are then filled image by image (the canvases still
+        come from the packed launches, the probabilities from sg_postprocess_wide per image); ``data_samples=None`` takes the fused
+        label head, one launch per flush group."""
         batch = torch.is_tensor(inputs)
         imgs = inputs.float() if batch else [x[0].float() if x.dim() == 4 else x.float() for x in inputs]
         n = imgs.shape[0] if batch else len(imgs)
@@ -429,7 +443,7 @@ class SegmentorEx(_HipSegmentorBase):
                  similarity_enhancement_cfg=None, result_dir=None, heatmap_dir=None,
                  # -- drop-in extras (see module docstring) --
                  checkpoint=None, text_features=None, text_encoder=None, precision="f16x2", synthetic_ok=False, tiles_per_launch=None,
-                 tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, pack_images=False):
+                 tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, pack_images=False, label_head="auto"):
         data_preprocessor = SegDataPreProcessor(mean=list(Wt.PIXEL_MEAN), std=list(Wt.PIXEL_STD), bgr_to_rgb=True)
         super().__init__(data_preprocessor=data_preprocessor)
         if model_type == "GEM":
@@ -438,7 +452,7 @@ class SegmentorEx(_HipSegmentorBase):
         visual = self._setup(clip_type, vit_type, model_type, name_path, device, ignore_residual, prob_thd, logit_scale, slide_stride,
                              slide_crop, cls_token_lambda, bg_idx, _to_bool(apply_sim_feat_up), sim_feat_up_cfg, global_debias_factor,
                              checkpoint, text_features, text_encoder, precision, synthetic_ok, tiles_per_launch, tokenizer=tokenizer,
-                             tile_group=tile_group)
+                             tile_group=tile_group, label_head=label_head)
         # opt-in extra: kwargs of the reference's CrossTileFusion (cross_tile_fusion.py:24-60), which the reference never calls (R2)
         self.cross_tile_fusion_cfg = cross_tile_fusion_cfg
         self.apply_ctd = _to_bool(apply_ctd)                                # segmentor.py:184-194, 339-365: DBSCAN + cluster debias, on the device here
@@ -473,7 +487,7 @@ class Segmentor(_HipSegmentorBase):
                  sim_feat_up_cfg=dict(model_name="jbu_one", model_path="your/model/path"),
                  checkpoint=None, text_features=None, text_encoder=None, precision="f16x2", synthetic_ok=False, tiles_per_launch=None,
                  tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, apply_outlier_suppression=False, outlier_suppression_cfg=None,
-                 pack_images=False):
+                 pack_images=False, label_head="auto"):
         data_preprocessor = SegDataPreProcessor(mean=list(Wt.PIXEL_MEAN), std=list(Wt.PIXEL_STD), bgr_to_rgb=True)
         super().__init__(data_preprocessor=data_preprocessor)
         if model_type == "GEM" and cls_token_lambda != 0:
@@ -481,7 +495,7 @@ class Segmentor(_HipSegmentorBase):
         self._setup(clip_type, vit_type, model_type, name_path, device, ignore_residual, prob_thd, logit_scale, slide_stride,
                     slide_crop, cls_token_lambda, bg_idx, apply_sim_feat_up, sim_feat_up_cfg, 0.0,
                     checkpoint, text_features, text_encoder, precision, synthetic_ok, tiles_per_launch, tokenizer=tokenizer,
-                    tile_group=tile_group)
+                    tile_group=tile_group, label_head=label_head)
         # opt-in extra: kwargs of the reference's CrossTileFusion (cross_tile_fusion.py:24-60), which the reference never calls (R2)
         self.cross_tile_fusion_cfg = cross_tile_fusion_cfg
         self.output_cls_token = cls_token_lambda != 0

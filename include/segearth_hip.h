@@ -227,6 +227,36 @@ int sg_postprocess_multi(const float* canvases, const int32_t* canvas_hw, const 
                          const int64_t* out_offset, const int64_t* block_prefix, int N, int64_t total_blocks, int64_t canvas_elems,
                          int64_t out_pixels, const int32_t* query_idx, int Q, int K, float logit_scale, float prob_thd, int bg_idx,
                          float* probs, int64_t* labels, sg_stream s);
+/* ---- large vocabularies: any Q --------------------------------------------------------------------------------------------------
+ * sg_cosine_logits_wide: the contract and output layout [B,Q,n] of sg_cosine_logits for any Q >= 1.  The text rows pass through LDS
+ * in chunks of as many rows as fit, inside one launch; a token's features are read once and stay in registers.  A shape that
+ * sg_cosine_logits takes (the whole text matrix fits in LDS) runs its kernel: the same bits.  Beyond it the expressions per (token, q)
+ * are the same, but the compiler fuses the debias sums in another order: within an ulp or two of that arithmetic.  E % 4 == 0, E <= 2048. */
+int sg_cosine_logits_wide(const float* tokens, const float* cls, const float* text, int B, int n, int E, int Q,
+                          float global_debias_factor, float cls_token_lambda, float* logits, sg_stream s);
+/* sg_postprocess_wide: the contract of sg_postprocess for any Q (sg_postprocess holds the queries in registers and stops at 64).
+ * Three passes over the canvas: maximum, sum, per-class maximum written through probs[class(q)] by the pixel's own thread.  Plain,
+ * not tuned: reads the canvas three times. */
+int sg_postprocess_wide(const float* logits, const int32_t* query_idx, int Q, int K, int H, int W, float logit_scale,
+                        float prob_thd, int bg_idx, float* probs, int64_t* labels, sg_stream s);
+/* sg_label_head: sg_stitch + sg_postprocess without the canvas, labels only, any Q >= 1 and 1 <= K <= Q.  Inputs as sg_stitch plus
+ * the post-process parameters.  Per pixel and query the stitched value is sg_stitch's (the same taps, covering tiles summed in raster
+ * order, divided by the count); the queries pass through registers in chunks with an online maximum and sum of exp.
+ *   labels int64 [H,W] = class of the largest scaled logit (lowest class index among equal ones; query_idx need not be sorted; with
+ *   K == Q class(q) = q, as in sg_postprocess), bg_idx where conf < prob_thd; conf f32 [H,W] (may be NULL) = the winning class's
+ *   probability 1 / sum_q exp(v_q - v_max).  No buffer proportional to Q*H*W, no atomics; repeats are byte-identical.
+ * Against sg_stitch + sg_postprocess the label can differ only where two class probabilities are closer than their f32 rounding. */
+int sg_label_head(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t,
+                  int pad_l, int H, int W, const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx,
+                  int64_t* labels, float* conf, sg_stream s);
+/* sg_label_head_multi: sg_label_head for the tiles of N images in one launch, descriptors as sg_stitch_multi; labels (and conf) of
+ * image n are written at out_offset[n] pixels of the flat outputs (sg_postprocess_multi's label layout), out_pixels = their size.
+ * Byte-identical to sg_label_head per image. */
+int sg_label_head_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh, int gw,
+                        int up_h, int up_w, int pad_t, int pad_l, const int32_t* image_hw, const int32_t* image_tiles,
+                        const int64_t* out_offset, const int64_t* block_prefix, int N, int64_t total_blocks, int64_t out_pixels,
+                        const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx, int64_t* labels,
+                        float* conf, sg_stream s);
 /* Label / confidence images of postprocess_result (segmentor.py:501-531): mask_rgb [H,W,3] = palette[clip(label)] (_colorize_mask,
  * :580-590); heat_rgb [H,W,3] = (g, 0, 255-g) with g = uint8(clip(max_k probs, 0, 1) * 255) (_to_colormap without OpenCV, :604-608;
  * OpenCV's JET table is not reproduced).  Either output may be NULL. */
