@@ -122,6 +122,8 @@ SIGNATURES = {
     "sg_jbu_workspace_bytes": (Z, [P, I, I, I]),
     "sg_jbu_upsample": (I, [P, P, P, I, I, I, I, I, I, P, P, Z, P]),
     "sg_jbu_logits": (I, [P, P, P, I, I, I, I, I, I, P, I, P, F, P, P, Z, P]),
+    "sg_jbu_workspace_bytes_wide": (Z, [P, I, I, I, I]),
+    "sg_jbu_logits_wide": (I, [P, P, P, I, I, I, I, I, I, P, I, P, F, P, P, Z, P]),
     "sg_jbu_set_capture": (I, [P, P]),
     "sg_jbu_last_kernels": (C.c_char_p, []),
     "sg_extract_tiles": (I, [C.POINTER(TileBatch), I, I, P, P]),

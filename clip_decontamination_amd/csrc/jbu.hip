@@ -1102,7 +1102,7 @@ constexpr int JBU_QMAX = 32;                         // queries the fused logits
 //     |out|^2     = |x|^2 + sum_c z (2 x + z)                                                       (the GEMM's row-dot epilogue)
 // so the only C x C GEMM keeps its result in registers and HBM sees x once more (f32) plus Q floats per pixel.
 __global__ __launch_bounds__(256) void jbu_geff_kernel(const float* __restrict__ text, const float* __restrict__ Wf, const float* __restrict__ bf01,
-                                                       int C, int Q, float* __restrict__ geff, float* __restrict__ g0) {
+                                                       int C, int Q, int ldq, float* __restrict__ geff, float* __restrict__ g0) {
   // block = 64 channels x 4 K-quarters (one per wave): Wf[k][c] reads are coalesced over c, 8 independent partial sums per thread
   __shared__ float part[4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1120,7 +1120,7 @@ __global__ __launch_bounds__(256) void jbu_geff_kernel(const float* __restrict__
   }
   part[wave][lane] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
   __syncthreads();
-  if (wave == 0 && c < C) geff[c * JBU_QMAX + q] = tq[c] + 0.1f * (((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane]);   // (Wf^T T^T)[c, q]
+  if (wave == 0 && c < C) geff[c * ldq + q] = tq[c] + 0.1f * (((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane]);   // (Wf^T T^T)[c, q]
   if (blockIdx.x == 0 && wave == 1) {
     float s0 = 0.f;
     for (int k = lane; k < C; k += 64) s0 += bf01[k] * tq[k];                // bf01 = 0.1 * bias (scaled at load)
@@ -1130,17 +1130,17 @@ __global__ __launch_bounds__(256) void jbu_geff_kernel(const float* __restrict__
 }
 // cls_logits[b, q] = (cls[b] / |cls[b]|) . T[q]     (segmentor.py:309-311)
 __global__ __launch_bounds__(64) void jbu_cls_logits_kernel(const float* __restrict__ cls, const float* __restrict__ text, int C, int Q,
-                                                            float* __restrict__ out) {
+                                                            int ldq, float* __restrict__ out) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const float* cr = cls + (int64_t)b * C;
   float ss = 0.f;
   for (int i = lane; i < C; i += 64) ss += cr[i] * cr[i];
   const float inv = 1.0f / sqrtf(wave_sum(ss));
-  for (int q = 0; q < Q; ++q) {
+  for (int q = blockIdx.y; q < Q; q += gridDim.y) {          // gridDim.y = 1 up to JBU_QMAX queries; the wide tail spreads them
     float d = 0.f;
     for (int i = lane; i < C; i += 64) d += cr[i] * text[(int64_t)q * C + i];
     d = wave_sum(d);
-    if (lane == 0) out[b * JBU_QMAX + q] = d * inv;
+    if (lane == 0) out[b * ldq + q] = d * inv;
   }
 }
 // One wave = 128 consecutive pixels, a lane owns pixels `lane` and `lane + 64`.  x rows are fetched coalesced (8 lanes x 16 B per pixel
@@ -1152,12 +1152,12 @@ template <int QP, typename XT>
 __global__ __launch_bounds__(256, 2) void jbu_pixel_logits_kernel(const XT* __restrict__ x, const float* __restrict__ rowdot, int slots,
                                                                   const float* __restrict__ geff, const float* __restrict__ g0,
                                                                   const float* __restrict__ clsl, float lambda, int64_t pixels, int64_t P, int C,
-                                                                  int Q, float* __restrict__ logits) {
+                                                                  int Q, int ldq, float* __restrict__ logits) {
   extern __shared__ __attribute__((aligned(16))) float pl_sm[];
   float* sG = pl_sm;                                              // [C][QP]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float* tile = pl_sm + (size_t)C * QP + wave * (64 * PL_PPL) * PL_LD;   // [128][PL_LD], private to the wave
-  for (int i = threadIdx.x; i < C * QP; i += 256) sG[i] = (i % QP) < Q ? geff[(i / QP) * JBU_QMAX + (i % QP)] : 0.f;
+  for (int i = threadIdx.x; i < C * QP; i += 256) sG[i] = (i % QP) < Q ? geff[(i / QP) * ldq + (i % QP)] : 0.f;
   __syncthreads();
   const int64_t pix0 = ((int64_t)blockIdx.x * 4 + wave) * (64 * PL_PPL);
   if (pix0 >= pixels) return;
@@ -1216,7 +1216,7 @@ __global__ __launch_bounds__(256, 2) void jbu_pixel_logits_kernel(const XT* __re
     for (int q = 0; q < QP; ++q)
       if (q < Q) {
         float vv = (acc[e][q] + g0[q]) * inv;
-        if (clsl) vv += lambda * clsl[b * JBU_QMAX + q];
+        if (clsl) vv += lambda * clsl[b * ldq + q];
         logits[(b * Q + q) * P + pp] = vv;
       }
   }
@@ -1232,7 +1232,7 @@ constexpr int PLM_ROUNDS = 4;
 __global__ __launch_bounds__(256, 2) void jbu_pixel_logits_mfma_kernel(const bf16_t* __restrict__ x, const float* __restrict__ rowdot, int slots,
                                                                        const float* __restrict__ geff, const float* __restrict__ g0,
                                                                        const float* __restrict__ clsl, float lambda, int64_t pixels, int64_t P, int C,
-                                                                       int Q, float* __restrict__ logits) {
+                                                                       int Q, int ldq, float* __restrict__ logits) {
   extern __shared__ __attribute__((aligned(16))) char plm_sm[];
   bf16_t* sGh = reinterpret_cast<bf16_t*>(plm_sm);                        // [16][C + 8]  (+8: rows 16 bytes apart in the banks)
   const int ldg = C + 8;
@@ -1241,7 +1241,7 @@ __global__ __launch_bounds__(256, 2) void jbu_pixel_logits_mfma_kernel(const bf1
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int i = tid; i < 16 * C; i += 256) {
     const int q = i / C, c = i % C;
-    const float v = q < Q ? geff[c * JBU_QMAX + q] : 0.f;
+    const float v = q < Q ? geff[c * ldq + q] : 0.f;
     const bf16_t hi = f2bf(v);
     sGh[q * ldg + c] = hi;
     sGl[q * ldg + c] = f2bf(v - bf2f(hi));
@@ -1311,14 +1311,138 @@ __global__ __launch_bounds__(256, 2) void jbu_pixel_logits_mfma_kernel(const bf1
         const float4 inv = *reinterpret_cast<const float4*>(myN + t * 16 + 4 * g);
         const int64_t b = pix / P, pp = pix % P;
         float4 o = make_float4((acc[t][0] + g0q) * inv.x, (acc[t][1] + g0q) * inv.y, (acc[t][2] + g0q) * inv.z, (acc[t][3] + g0q) * inv.w);
-        if (clsl) { const float cv = lambda * clsl[b * JBU_QMAX + r]; o.x += cv; o.y += cv; o.z += cv; o.w += cv; }
+        if (clsl) { const float cv = lambda * clsl[b * ldq + r]; o.x += cv; o.y += cv; o.z += cv; o.w += cv; }
         float* dst = logits + (b * Q + r) * P + pp;
         if (pp + 3 < P && pix + 3 < pixels && (P & 3) == 0) *reinterpret_cast<float4*>(dst) = o;   // P % 4 == 0: the four pixels share the image and the store is aligned
         else {
           const float ov[4] = {o.x, o.y, o.z, o.w};
           for (int e = 0; e < 4; ++e) {
             const int64_t pe = pix + e;
-            if (pe < pixels) logits[((pe / P) * Q + r) * P + pe % P] = ov[e] + ((clsl && pe / P != b) ? lambda * (clsl[(pe / P) * JBU_QMAX + r] - clsl[b * JBU_QMAX + r]) : 0.f);
+            if (pe < pixels) logits[((pe / P) * Q + r) * P + pe % P] = ov[e] + ((clsl && pe / P != b) ? lambda * (clsl[(pe / P) * ldq + r] - clsl[b * ldq + r]) : 0.f);
+          }
+        }
+      }
+    }
+    __builtin_amdgcn_wave_barrier();                                      // myN is rewritten in the next round
+  }
+}
+
+// The matrix-pipe form for Q > 32 (sg_jbu_logits_wide): the same product, fragments and epilogue with the queries in groups of 16.  NG
+// groups' hi + lo planes are resident in LDS ([NG * 16 q][C + 8] each, 2 * 16 * (C + 8) * 2 bytes per group: 33 / 41 / 50 / 66 KB at
+// C = 512 / 640 / 768 / 1024 of the 160 KB a workgroup may hold) and blockIdx.y walks the passes over the groups, so x is read once per
+// pass and a wave keeps 4 * NG accumulator quads.  A column's arithmetic (hi then lo per k-step, k ascending) depends neither on its
+// group nor on its neighbours; padded columns (q >= Q) are zero in LDS and never stored.  8 waves per workgroup: with the LDS of three
+// groups one workgroup fits a CU, and two waves per SIMD cover each other's fragment loads.
+constexpr int PLW_ROUNDS = 4, PLW_WAVES = 8, PLW_NG_MAX = 4;
+template <int NG>
+__global__ __launch_bounds__(64 * PLW_WAVES) void jbu_pixel_logits_wide_kernel(const bf16_t* __restrict__ x, const float* __restrict__ rowdot, int slots,
+                                                                               const float* __restrict__ geff, const float* __restrict__ g0,
+                                                                               const float* __restrict__ clsl, float lambda, int64_t pixels, int64_t P,
+                                                                               int C, int Q, int ldq, float* __restrict__ logits) {
+  extern __shared__ __attribute__((aligned(16))) char plw_sm[];
+  const int ldg = C + 8;                                                  // rows 16 bytes apart in the banks
+  bf16_t* sGh = reinterpret_cast<bf16_t*>(plw_sm);                        // [NG * 16][ldg]
+  bf16_t* sGl = sGh + NG * 16 * ldg;
+  float* sN = reinterpret_cast<float*>(sGl + NG * 16 * ldg);              // [PLW_WAVES][64] 1 / |out| of the wave's pixels
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int q_base = blockIdx.y * (NG * 16);                              // ldq = 16 ceil(Q / 16): the groups of this pass
+  const int ng = (ldq - q_base) / 16 < NG ? (ldq - q_base) / 16 : NG;
+  for (int i = tid; i < NG * 16 * C; i += 64 * PLW_WAVES) {               // query fastest: the f32 rows of Geff are read in runs
+    const int ql = i % (NG * 16), c = i / (NG * 16), q = q_base + ql;
+    const float v = q < Q ? geff[c * ldq + q] : 0.f;
+    const bf16_t hi = f2bf(v);
+    sGh[ql * ldg + c] = hi;
+    sGl[ql * ldg + c] = f2bf(v - bf2f(hi));
+  }
+  __syncthreads();
+  const int r = lane & 15, g = lane >> 4;
+  float* myN = sN + wave * 64;
+  for (int round = 0; round < PLW_ROUNDS; ++round) {
+    const int64_t pix0 = (((int64_t)blockIdx.x * PLW_ROUNDS + round) * PLW_WAVES + wave) * 64;
+    if (pix0 >= pixels) return;                                           // wave-uniform; no barrier below
+    const bf16_t* xr[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      int64_t pr = pix0 + t * 16 + r;
+      pr = pr < pixels ? pr : pixels - 1;
+      xr[t] = x + pr * C + 8 * g;
+    }
+    f32x4 acc[NG][4];
+#pragma unroll
+    for (int gi = 0; gi < NG; ++gi)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) acc[gi][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float nx[4] = {0.f, 0.f, 0.f, 0.f};
+    bf16x8 a_cur[4], a_nxt[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) a_cur[t] = *reinterpret_cast<const bf16x8*>(xr[t]);
+    const int nk = C / 32;
+    for (int ks = 0; ks < nk; ++ks) {
+      const int kn = ks + 1 < nk ? ks + 1 : ks;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) a_nxt[t] = *reinterpret_cast<const bf16x8*>(xr[t] + 32 * kn);
+#pragma unroll
+      for (int gi = 0; gi < NG; ++gi) {
+        if (gi < ng) {                                                     // block-uniform: the last pass may hold fewer groups
+          const bf16x8 bh = *reinterpret_cast<const bf16x8*>(sGh + (gi * 16 + r) * ldg + 32 * ks + 8 * g);
+          const bf16x8 bl = *reinterpret_cast<const bf16x8*>(sGl + (gi * 16 + r) * ldg + 32 * ks + 8 * g);
+#pragma unroll
+          for (int t = 0; t < 4; ++t) acc[gi][t] = mfma_16x16x32<false>(a_cur[t], bh, acc[gi][t]);   // D[pixel i][query j]: lane = j + 16 (i / 4)
+#pragma unroll
+          for (int t = 0; t < 4; ++t) acc[gi][t] = mfma_16x16x32<false>(a_cur[t], bl, acc[gi][t]);
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const uint4 raw = __builtin_bit_cast(uint4, a_cur[t]);
+        const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float lo = __uint_as_float(w[e] << 16), hi = __uint_as_float(w[e] & 0xffff0000u);
+          nx[t] = __builtin_fmaf(lo, lo, nx[t]); nx[t] = __builtin_fmaf(hi, hi, nx[t]);
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < 4; ++t) a_cur[t] = a_nxt[t];
+    }
+    // |x|^2 of pixel (t, r): the four 8-channel slices of every k-step sit in lanes r, r + 16, r + 32, r + 48
+#pragma unroll
+    for (int t = 0; t < 4; ++t) { nx[t] += __shfl_xor(nx[t], 16, 64); nx[t] += __shfl_xor(nx[t], 32, 64); }
+    if (g == 0) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        int64_t pix = pix0 + t * 16 + r;
+        pix = pix < pixels ? pix : pixels - 1;
+        float n2 = nx[t];
+        for (int sidx = 0; sidx < slots; ++sidx) n2 += rowdot[pix * slots + sidx];      // fixed order: deterministic
+        myN[t * 16 + r] = 1.0f / sqrtf(n2);
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    // lane holds pixels pix0 + 16 t + 4 g .. + 3 of query q_base + 16 gi + r
+#pragma unroll
+    for (int gi = 0; gi < NG; ++gi) {
+      const int q = q_base + gi * 16 + r;
+      if (gi < ng && q < Q) {
+        const float g0q = g0[q];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const int64_t pix = pix0 + t * 16 + 4 * g;
+          if (pix >= pixels) continue;
+          const float4 inv = *reinterpret_cast<const float4*>(myN + t * 16 + 4 * g);
+          const int64_t b = pix / P, pp = pix % P;
+          float4 o = make_float4((acc[gi][t][0] + g0q) * inv.x, (acc[gi][t][1] + g0q) * inv.y, (acc[gi][t][2] + g0q) * inv.z,
+                                 (acc[gi][t][3] + g0q) * inv.w);
+          if (clsl) { const float cv = lambda * clsl[b * ldq + q]; o.x += cv; o.y += cv; o.z += cv; o.w += cv; }
+          float* dst = logits + (b * Q + q) * P + pp;
+          if (pp + 3 < P && pix + 3 < pixels && (P & 3) == 0) *reinterpret_cast<float4*>(dst) = o;   // as jbu_pixel_logits_mfma_kernel
+          else {
+            const float ov[4] = {o.x, o.y, o.z, o.w};
+            for (int e = 0; e < 4; ++e) {
+              const int64_t pe = pix + e;
+              if (pe < pixels) logits[((pe / P) * Q + q) * P + pe % P] = ov[e] + ((clsl && pe / P != b) ? lambda * (clsl[(pe / P) * ldq + q] - clsl[b * ldq + q]) : 0.f);
+            }
           }
         }
       }
@@ -1392,11 +1516,12 @@ __device__ __forceinline__ void bilinear_cell(int dst, int in, int out, int& i0,
   i1c = i0 + 1 < in ? i0 + 1 : i0;
 }
 
-// out[b, q, Y*GW + X] = (sum_k w_k y_kq) / sqrt(sum_kl w_k w_l G_kl) + lambda * clsl[b, q].  64 x 4 pixels per block, one pixel per lane:
-// the stores of a query are 256 contiguous bytes per wave; the y rows are read as float4 (the Q loop runs in groups of 4).
+// out[b, q_off + q, Y*GW + X] = (sum_k w_k y_kq) / sqrt(sum_kl w_k w_l G_kl) + lambda * clsl[b, q].  64 x 4 pixels per block, one pixel per
+// lane: the stores of a query are 256 contiguous bytes per wave; the y rows are read as float4 (the Q loop runs in groups of 4).  Q <= 32
+// queries per launch; out holds q_rows query planes per image (sg_jbu_logits_wide: one launch per 32-query chunk, straight into place).
 __global__ __launch_bounds__(256) void bilinear_pixel_logits_kernel(const float* __restrict__ y, const float* __restrict__ gram,
                                                                     const float* __restrict__ clsl, float lambda, int gh, int gw, int GH,
-                                                                    int GW, int Q, float* __restrict__ out) {
+                                                                    int GW, int Q, int q_off, int q_rows, float* __restrict__ out) {
   const int X = blockIdx.x * 64 + (threadIdx.x & 63);
   const int Y = blockIdx.y * 4 + (threadIdx.x >> 6);
   const int b = blockIdx.z;
@@ -1416,7 +1541,7 @@ __global__ __launch_bounds__(256) void bilinear_pixel_logits_kernel(const float*
   d2 += 2.f * (w00 * (w01 * ga.y + w10 * ga.z + w11 * ga.w) + w01 * (w10 * g4 + w11 * r01) + w10 * w11 * b10);
   const float inv = 1.0f / sqrtf(d2);
   const int64_t plane = (int64_t)GH * GW;
-  float* o = out + (int64_t)b * Q * plane + (int64_t)Y * GW + X;
+  float* o = out + ((int64_t)b * q_rows + q_off) * plane + (int64_t)Y * GW + X;
   const float* cl = clsl ? clsl + b * JBU_QMAX : nullptr;
   for (int q = 0; q < Q; q += 4) {
     const float4 a = *reinterpret_cast<const float4*>(y + t00 * JBU_QMAX + q);
@@ -1542,7 +1667,7 @@ static int64_t stage_numel(int slot, int r) {
 }
 
 struct JbuPlan { float *gs, *proj, *X, *H1, *Kf, *hr, *bufA, *bufB; void* x16; bf16_t *X16, *H116; float *rowdot, *geff, *g0, *clsl; };
-static size_t jbu_plan(const sg_jbu* j, int B, int gh, int gw, void* ws, bool dry, JbuPlan& p) {
+static size_t jbu_plan(const sg_jbu* j, int B, int gh, int gw, void* ws, bool dry, JbuPlan& p, int ldq = JBU_QMAX) {   // ldq: query stride of geff / g0 / clsl
   const int r = j->st[0].r, d2 = (2 * r + 1) * (2 * r + 1);
   const int64_t pixels = (int64_t)B * 16 * gh * 16 * gw;              // final resolution
   Bump b(ws, 0, dry);
@@ -1559,9 +1684,9 @@ static size_t jbu_plan(const sg_jbu* j, int B, int gh, int gw, void* ws, bool dr
   p.bufB = (float*)b.take((size_t)pixels * j->C * 4);                    // stage-2 / stage-4 output: pong
   p.x16 = b.take((size_t)pixels * j->C * 2);
   p.rowdot = (float*)b.take((size_t)pixels * (j->C / 64 + 1) * 4);       // fused tail: per-pixel partial |out|^2 - |x|^2, one slot per 64 columns
-  p.geff = (float*)b.take((size_t)j->C * JBU_QMAX * 4);
-  p.g0 = (float*)b.take((size_t)JBU_QMAX * 4);
-  p.clsl = (float*)b.take((size_t)B * JBU_QMAX * 4);
+  p.geff = (float*)b.take((size_t)j->C * ldq * 4);
+  p.g0 = (float*)b.take((size_t)ldq * 4);
+  p.clsl = (float*)b.take((size_t)B * ldq * 4);
   return align_up(b.off, 256);
 }
 // kind 2 (bilinear): the per-token prologue's outputs -- y = tokens . T^T [B*n, JBU_QMAX] and the Gram terms [B*n, BL_G] -- and the CLS logits
@@ -1896,28 +2021,34 @@ static int bilinear_upsample(sg_jbu* j, const float* source, int B, int gh, int 
   return SG_OK;
 }
 
-static int bilinear_logits(sg_jbu* j, const float* source, int B, int gh, int gw, int GH, int GW, const float* text, int Q,
+static int bilinear_logits(const char* who, sg_jbu* j, const float* source, int B, int gh, int gw, int GH, int GW, const float* text, int Q,
                            const float* cls, float cls_token_lambda, float* logits, void* ws, size_t ws_bytes, hipStream_t s) {
   BilinearPlan p;
   const size_t need = bilinear_plan(B, gh, gw, ws, false, p);
-  if (need > ws_bytes) return fail(SG_ERR_STATE, "sg_jbu_logits: workspace %zu < required %zu", ws_bytes, need);
+  if (need > ws_bytes) return fail(SG_ERR_STATE, "%s: workspace %zu < required %zu", who, ws_bytes, need);
   const int64_t tokens = (int64_t)B * gh * gw;
-  SG_REQUIRE(cdiv(tokens, 4) < (1ll << 31) && cdiv(GH, 4) < 65536 && B < 65536, "sg_jbu_logits: shape too large for one launch");
+  SG_REQUIRE(cdiv(tokens, 4) < (1ll << 31) && cdiv(GH, 4) < 65536 && B < 65536, "%s: shape too large for one launch", who);
   jbu_rec_start();
   jbu_cap_reset(j);
-  hipLaunchKernelGGL(bilinear_prologue_kernel, dim3((unsigned)cdiv(tokens, 4)), dim3(256), 0, s, source, text, B, gh, gw, j->C, Q, p.y, p.gram);
-  SG_LAUNCH_CHECK();
-  g_jbu_rec.geff = "bilinear_prologue_kernel";
   const bool use_cls = cls != nullptr && cls_token_lambda != 0.f;
-  if (use_cls) {
-    hipLaunchKernelGGL(jbu_cls_logits_kernel, dim3(B), dim3(64), 0, s, cls, text, j->C, Q, p.clsl);
+  // the kernels hold JBU_QMAX queries in registers: Q > JBU_QMAX (sg_jbu_logits_wide) runs them per chunk of text rows on the same
+  // scratch (stream order), each chunk's pixel kernel writing its query planes of [B, Q, GH*GW] in place
+  for (int q0 = 0; q0 < Q; q0 += JBU_QMAX) {
+    const int qn = Q - q0 < JBU_QMAX ? Q - q0 : JBU_QMAX;
+    const float* tq = text + (int64_t)q0 * j->C;
+    hipLaunchKernelGGL(bilinear_prologue_kernel, dim3((unsigned)cdiv(tokens, 4)), dim3(256), 0, s, source, tq, B, gh, gw, j->C, qn, p.y, p.gram);
     SG_LAUNCH_CHECK();
-    g_jbu_rec.cls = "jbu_cls_logits_kernel";
+    g_jbu_rec.geff = "bilinear_prologue_kernel";
+    if (use_cls) {
+      hipLaunchKernelGGL(jbu_cls_logits_kernel, dim3(B), dim3(64), 0, s, cls, tq, j->C, qn, JBU_QMAX, p.clsl);
+      SG_LAUNCH_CHECK();
+      g_jbu_rec.cls = "jbu_cls_logits_kernel";
+    }
+    hipLaunchKernelGGL(bilinear_pixel_logits_kernel, dim3((unsigned)cdiv(GW, 64), (unsigned)cdiv(GH, 4), (unsigned)B), dim3(256), 0, s, p.y,
+                       p.gram, use_cls ? p.clsl : nullptr, cls_token_lambda, gh, gw, GH, GW, qn, q0, Q, logits);
+    SG_LAUNCH_CHECK();
+    g_jbu_rec.pix = "bilinear_pixel_logits_kernel";
   }
-  hipLaunchKernelGGL(bilinear_pixel_logits_kernel, dim3((unsigned)cdiv(GW, 64), (unsigned)cdiv(GH, 4), (unsigned)B), dim3(256), 0, s, p.y,
-                     p.gram, use_cls ? p.clsl : nullptr, cls_token_lambda, gh, gw, GH, GW, Q, logits);
-  SG_LAUNCH_CHECK();
-  g_jbu_rec.pix = "bilinear_pixel_logits_kernel";
   return SG_OK;
 }
 
@@ -2130,6 +2261,15 @@ extern "C" size_t sg_jbu_workspace_bytes(const sg_jbu* j, int B, int gh, int gw)
   return jbu_plan(j, B, gh, gw, nullptr, true, p);
 }
 
+// the workspace of sg_jbu_logits_wide: geff / g0 / clsl at query stride 16 ceil(Q / 16) once Q > JBU_QMAX (the other kinds and Q <= JBU_QMAX:
+// sg_jbu_workspace_bytes)
+extern "C" size_t sg_jbu_workspace_bytes_wide(const sg_jbu* j, int B, int gh, int gw, int Q) {
+  if (!j || B <= 0 || gh <= 0 || gw <= 0 || Q < 1) return 0;
+  if (Q <= JBU_QMAX || j->kind == SG_JBU_BILINEAR || j->kind == SG_JBU_RESIZE_CONV) return sg_jbu_workspace_bytes(j, B, gh, gw);
+  JbuPlan p;
+  return jbu_plan(j, B, gh, gw, nullptr, true, p, (Q + 15) / 16 * 16);
+}
+
 // source [B, gh*gw, C] (patch tokens), guidance [B,3,GH,GW] (the normalised, padded tile) -> out [B, (16gh*16gw), C]
 extern "C" int sg_jbu_upsample(sg_jbu* j, const float* source, const float* guidance, int B, int gh, int gw, int GH, int GW, int precision,
                                float* out, void* ws, size_t ws_bytes, sg_stream st) {
@@ -2176,44 +2316,58 @@ extern "C" int sg_jbu_upsample(sg_jbu* j, const float* source, const float* guid
 
 // sg_jbu_logits replaces, for a batch of tiles,  feats = upsampler(tokens, img) -> feats /= |feats| -> feats @ T^T (+ lambda * cls_logits)
 // (segmentor.py:368-379) without materialising the [S^2, C] feature map (throughput mode).
-extern "C" int sg_jbu_logits(sg_jbu* j, const float* source, const float* guidance, int B, int gh, int gw, int GH, int GW, int precision,
-                             const float* text, int Q, const float* cls, float cls_token_lambda, float* logits, void* ws, size_t ws_bytes,
-                             sg_stream st) {
-  SG_REQUIRE(j && source && guidance && text && logits && ws, "sg_jbu_logits: null argument");
-  SG_REQUIRE(Q >= 1 && Q <= JBU_QMAX, "sg_jbu_logits: 1 <= Q <= %d", JBU_QMAX);
+// One body for sg_jbu_logits (Q <= JBU_QMAX, query stride JBU_QMAX) and the Q > JBU_QMAX range of sg_jbu_logits_wide (query stride
+// Qp = 16 ceil(Q / 16), jbu_pixel_logits_wide_kernel); `who` names the entry in the refusals.
+static int jbu_logits_run(const char* who, sg_jbu* j, const float* source, const float* guidance, int B, int gh, int gw, int GH, int GW,
+                          int precision, const float* text, int Q, const float* cls, float cls_token_lambda, float* logits, void* ws,
+                          size_t ws_bytes, sg_stream st) {
+  const bool wide = Q > JBU_QMAX;
   if (j->kind == SG_JBU_BILINEAR) {                       // every precision: the bilinear logits are f32 arithmetic throughout
-    SG_REQUIRE(B > 0 && gh > 0 && gw > 0 && GH > 0 && GW > 0, "sg_jbu_logits: bad shape");
+    SG_REQUIRE(B > 0 && gh > 0 && gw > 0 && GH > 0 && GW > 0, "%s: bad shape", who);
     DeviceGuard dg(j->device);
-    return bilinear_logits(j, source, B, gh, gw, GH, GW, text, Q, cls, cls_token_lambda, logits, ws, ws_bytes, as_stream(st));
+    return bilinear_logits(who, j, source, B, gh, gw, GH, GW, text, Q, cls, cls_token_lambda, logits, ws, ws_bytes, as_stream(st));
   }
   if (j->kind == SG_JBU_RESIZE_CONV)
-    return fail(SG_ERR_INVALID, "sg_jbu_logits: resize_conv has no fused logits tail; use sg_jbu_upsample + sg_cosine_logits");
-  SG_REQUIRE(precision == SG_PREC_BF16 && j->C % 64 == 0 && j->C >= 512, "sg_jbu_logits: the fused tail is the bf16 throughput path (C %% 64 == 0, C >= 512); use sg_jbu_upsample + sg_cosine_logits otherwise");
-  for (size_t i = 0; i < j->have.size(); ++i) if (!j->have[i]) return fail(SG_ERR_STATE, "sg_jbu_logits: upsampler weights incomplete");
+    return fail(SG_ERR_INVALID, "%s: resize_conv has no fused logits tail; use sg_jbu_upsample + sg_cosine_logits", who);
+  SG_REQUIRE(precision == SG_PREC_BF16 && j->C % 64 == 0 && j->C >= 512, "%s: the fused tail is the bf16 throughput path (C %% 64 == 0, C >= 512); use sg_jbu_upsample + sg_cosine_logits otherwise", who);
+  for (size_t i = 0; i < j->have.size(); ++i) if (!j->have[i]) return fail(SG_ERR_STATE, "%s: upsampler weights incomplete", who);
+  const int C = j->C;
+  const int ldq = wide ? (Q + 15) / 16 * 16 : JBU_QMAX;
+  // wide: as many 16-query groups resident in LDS as fit (PLW_NG_MAX at most), the groups spread evenly over the passes
+  const int groups = ldq / 16;
+  const size_t group_lds = (size_t)2 * 16 * (C + 8) * sizeof(bf16_t), norm_lds = PLW_WAVES * 64 * sizeof(float);
+  int ng = 0, passes = 0;
+  if (wide) {
+    SG_REQUIRE(Q < 65536, "%s: Q < 65536", who);
+    const int fit = (int)((160 * 1024 - norm_lds) / group_lds);      // C <= 1216: below two resident groups x would be re-read once per group
+    SG_REQUIRE(fit >= 2, "%s: two 16-query groups of C = %d do not fit the 160 KB of LDS; use sg_jbu_upsample + sg_cosine_logits_wide", who, C);
+    const int ng_max = fit < PLW_NG_MAX ? fit : PLW_NG_MAX;
+    passes = (groups + ng_max - 1) / ng_max;
+    ng = (groups + passes - 1) / passes;
+  }
   DeviceGuard dg(j->device);
   hipStream_t s = as_stream(st);
   JbuPlan p;
-  const size_t need = jbu_plan(j, B, gh, gw, ws, false, p);
-  if (need > ws_bytes) return fail(SG_ERR_STATE, "sg_jbu_logits: workspace %zu < required %zu", ws_bytes, need);
-  const int C = j->C;
+  const size_t need = jbu_plan(j, B, gh, gw, ws, false, p, ldq);
+  if (need > ws_bytes) return fail(SG_ERR_STATE, "%s: workspace %zu < required %zu", who, ws_bytes, need);
   const int64_t P = (int64_t)16 * gh * 16 * gw, pixels = (int64_t)B * P;
-  SG_REQUIRE(pixels >= 1024 && pixels < (1ll << 31), "sg_jbu_logits: pixel count out of range");
+  SG_REQUIRE(pixels >= 1024 && pixels < (1ll << 31), "%s: pixel count out of range", who);
   const float* x = nullptr;
   jbu_rec_start();
   jbu_cap_reset(j);
   SG_TRY(jbu_stages(j, source, guidance, B, gh, gw, GH, GW, precision, p, &x, s, /*want_f32_x=*/false));
   const bf16_t* x16 = (const bf16_t*)p.x16;                 // the 16x features exist in bf16 only: the conv's 4 B/element f32 store and its two re-reads are gone
-  hipLaunchKernelGGL(jbu_geff_kernel, dim3((unsigned)cdiv(C, 64), (unsigned)Q), dim3(256), 0, s, text, j->fin_w, j->fin_b, C, Q, p.geff, p.g0);
+  hipLaunchKernelGGL(jbu_geff_kernel, dim3((unsigned)cdiv(C, 64), (unsigned)Q), dim3(256), 0, s, text, j->fin_w, j->fin_b, C, Q, ldq, p.geff, p.g0);
   SG_LAUNCH_CHECK();
   g_jbu_rec.geff = "jbu_geff_kernel";
-  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_GEFF, p.geff, (size_t)C * JBU_QMAX * 4, s));
-  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_G0, p.g0, (size_t)JBU_QMAX * 4, s));
+  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_GEFF, p.geff, (size_t)C * ldq * 4, s));
+  SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_G0, p.g0, (size_t)ldq * 4, s));
   const bool use_cls = cls != nullptr && cls_token_lambda != 0.f;
   if (use_cls) {
-    hipLaunchKernelGGL(jbu_cls_logits_kernel, dim3(B), dim3(64), 0, s, cls, text, C, Q, p.clsl);
+    hipLaunchKernelGGL(jbu_cls_logits_kernel, dim3(B, wide ? 16 : 1), dim3(64), 0, s, cls, text, C, Q, ldq, p.clsl);
     SG_LAUNCH_CHECK();
     g_jbu_rec.cls = "jbu_cls_logits_kernel";
-    SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_CLSL, p.clsl, (size_t)B * JBU_QMAX * 4, s));
+    SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_CLSL, p.clsl, (size_t)B * ldq * 4, s));
   }
   SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_FIN_A, x16, (size_t)pixels * C * 2, s));
   // the final 1x1 with the row-dot epilogue: residual = the bf16 x itself, nothing stored but the per-slot |out|^2 - |x|^2
@@ -2222,21 +2376,56 @@ extern "C" int sg_jbu_logits(sg_jbu* j, const float* source, const float* guidan
   const int slots = C / 64;
   g_jbu_rec.fin_a = "bf16";
   SG_TRY(jbu_cap(j, -1, SG_JBU_CAP_ROWDOT, p.rowdot, (size_t)pixels * slots * 4, s));
-  if (Q <= 16) {                                             // matrix-pipe form (its C % 32 == 0 is implied by the fused tail's C % 64 == 0)
+  if (wide) {                                                // matrix-pipe form, `ng` query groups per pass
+    const size_t lds = ng * group_lds + norm_lds;
+    const dim3 grid((unsigned)cdiv(pixels, 64 * PLW_WAVES * PLW_ROUNDS), (unsigned)passes);
+    auto launch = [&](auto kernel) -> int {
+      if (lds > 48 * 1024) SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds));
+      hipLaunchKernelGGL(kernel, grid, dim3(64 * PLW_WAVES), lds, s, x16, p.rowdot, slots, p.geff, p.g0, use_cls ? p.clsl : nullptr, cls_token_lambda,
+                         pixels, P, C, Q, ldq, logits);
+      return SG_OK;
+    };
+    switch (ng) {
+      case 2: SG_TRY(launch(jbu_pixel_logits_wide_kernel<2>)); break;
+      case 3: SG_TRY(launch(jbu_pixel_logits_wide_kernel<3>)); break;
+      default: SG_TRY(launch(jbu_pixel_logits_wide_kernel<4>)); break;
+    }
+    g_jbu_rec.pix = "jbu_pixel_logits_wide_kernel";
+  } else if (Q <= 16) {                                      // matrix-pipe form (its C % 32 == 0 is implied by the fused tail's C % 64 == 0)
     const size_t lds = (size_t)2 * 16 * (C + 8) * sizeof(bf16_t) + 4 * 64 * sizeof(float);
     SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_pixel_logits_mfma_kernel), lds));
     hipLaunchKernelGGL(jbu_pixel_logits_mfma_kernel, dim3((unsigned)cdiv(pixels, 4 * 64 * PLM_ROUNDS)), dim3(256), lds, s, x16, p.rowdot, slots, p.geff, p.g0,
-                       use_cls ? p.clsl : nullptr, cls_token_lambda, pixels, P, C, Q, logits);
+                       use_cls ? p.clsl : nullptr, cls_token_lambda, pixels, P, C, Q, ldq, logits);
     g_jbu_rec.pix = "jbu_pixel_logits_mfma_kernel";
   } else {                                                   // 17 <= Q <= 32: the VALU form with all JBU_QMAX queries in registers
     const size_t lds = ((size_t)C * 32 + 4 * 64 * PL_PPL * PL_LD) * sizeof(float);
     if (lds > 48 * 1024) SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(jbu_pixel_logits_kernel<32, bf16_t>), lds));
     hipLaunchKernelGGL((jbu_pixel_logits_kernel<32, bf16_t>), dim3((unsigned)cdiv(pixels, 4 * 64 * PL_PPL)), dim3(256), lds, s, x16, p.rowdot, slots, p.geff,
-                       p.g0, use_cls ? p.clsl : nullptr, cls_token_lambda, pixels, P, C, Q, logits);
+                       p.g0, use_cls ? p.clsl : nullptr, cls_token_lambda, pixels, P, C, Q, ldq, logits);
     g_jbu_rec.pix = "jbu_pixel_logits_kernel<32>";
   }
   SG_LAUNCH_CHECK();
   return SG_OK;
+}
+
+extern "C" int sg_jbu_logits(sg_jbu* j, const float* source, const float* guidance, int B, int gh, int gw, int GH, int GW, int precision,
+                             const float* text, int Q, const float* cls, float cls_token_lambda, float* logits, void* ws, size_t ws_bytes,
+                             sg_stream st) {
+  SG_REQUIRE(j && source && guidance && text && logits && ws, "sg_jbu_logits: null argument");
+  SG_REQUIRE(Q >= 1 && Q <= JBU_QMAX, "sg_jbu_logits: 1 <= Q <= %d", JBU_QMAX);
+  return jbu_logits_run("sg_jbu_logits", j, source, guidance, B, gh, gw, GH, GW, precision, text, Q, cls, cls_token_lambda, logits, ws, ws_bytes, st);
+}
+
+// sg_jbu_logits for any Q >= 1: up to JBU_QMAX queries it IS sg_jbu_logits (the same kernels, strides and bits); beyond, the tail runs
+// jbu_pixel_logits_wide_kernel on buffers of query stride 16 ceil(Q / 16) (sg_jbu_workspace_bytes_wide), and the bilinear kind its
+// kernels per 32-query chunk.
+extern "C" int sg_jbu_logits_wide(sg_jbu* j, const float* source, const float* guidance, int B, int gh, int gw, int GH, int GW, int precision,
+                                  const float* text, int Q, const float* cls, float cls_token_lambda, float* logits, void* ws,
+                                  size_t ws_bytes, sg_stream st) {
+  SG_REQUIRE(j && source && guidance && text && logits && ws, "sg_jbu_logits_wide: null argument");
+  SG_REQUIRE(Q >= 1, "sg_jbu_logits_wide: Q >= 1");
+  if (Q <= JBU_QMAX) return sg_jbu_logits(j, source, guidance, B, gh, gw, GH, GW, precision, text, Q, cls, cls_token_lambda, logits, ws, ws_bytes, st);
+  return jbu_logits_run("sg_jbu_logits_wide", j, source, guidance, B, gh, gw, GH, GW, precision, text, Q, cls, cls_token_lambda, logits, ws, ws_bytes, st);
 }
 
 extern "C" int sg_extract_tiles(const sg_tile_batch* t, int up_h, int up_w, float* out, sg_stream s) {

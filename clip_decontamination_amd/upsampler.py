@@ -50,7 +50,9 @@ class HipJBU:
         self._ctx = C.c_void_p()
         self._ws = {}
         self.tiles_per_launch = 8            # tiles per JBU launch (workspace ~2.2 GB per 512-pixel tile)
-        self.fused_tail = True               # bf16 mode: sg_jbu_logits (no [S^2, C] feature map); False = upsample + cosine_logits
+        self.fused_tail = True               # bf16 mode: sg_jbu_logits[_wide] (no [S^2, C] feature map); False = upsample + cosine_logits
+        # more than 32 queries: True = the fused wide tail (sg_jbu_logits_wide, C <= 1216), False = upsample + cosine_logits there
+        self.wide_tail = False
         with torch.cuda.device(self.device):
             check(self.lib.sg_jbu_create(C.byref(self._ctx), self.device.index or 0, KINDS[model_name], feat_dim), "sg_jbu_create")
 
@@ -156,6 +158,7 @@ class HipJBU:
         fmt = _lib.IMG_U8_NHWC if scene.dtype == torch.uint8 else _lib.IMG_F32_NCHW
         scene = scene.contiguous()
         H, W = (scene.shape[-3], scene.shape[-2]) if fmt == _lib.IMG_U8_NHWC else (scene.shape[-2], scene.shape[-1])
+        text = text.contiguous()
         Q = text.shape[0]
         with torch.cuda.device(self.device):
             if cls is not None and global_debias_factor != 0:
@@ -181,29 +184,24 @@ class HipJBU:
                 lam = float(cls_token_lambda) if cls is not None else 0.0
                 if self.is_bilinear:
                     # every precision: the per-pixel logits come from per-token products and Gram terms, no [GH*GW, C] map (f32 arithmetic)
-                    # (queries in groups of 32, the kernel's bound)
+                    # (any Q in one call: the library walks the queries in chunks of 32, the kernels' bound, and writes them in place)
                     lg = torch.empty(c, Q, ph * pw, dtype=torch.float32, device=self.device)
                     tk = tokens[i:i + c].contiguous().float()
                     ci = None if (cls is None or lam == 0.0) else cls[i:i + c].contiguous().float()
-                    need = self.lib.sg_jbu_workspace_bytes(self._ctx, c, gh, gw)
+                    need = self.lib.sg_jbu_workspace_bytes_wide(self._ctx, c, gh, gw, Q)
                     wp, wn = self._workspace(need)
-                    for q0 in range(0, Q, 32):
-                        qn = min(32, Q - q0)
-                        part = lg if qn == Q else torch.empty(c, qn, ph * pw, dtype=torch.float32, device=self.device)
-                        tq = text if qn == Q else text[q0:q0 + qn].contiguous()
-                        check(self.lib.sg_jbu_logits(self._ctx, ptr(tk), ptr(guid), c, gh, gw, ph, pw, self.precision, ptr(tq), qn, ptr(ci),
-                                                     lam, ptr(part), wp, wn, stream_ptr(self.device)), "sg_jbu_logits")
-                        if part is not lg:
-                            lg[:, q0:q0 + qn] = part
-                elif self.fused_tail and not self.is_resize_conv and self.precision == _lib.PREC_BF16 and self.feat_dim % 64 == 0 and self.feat_dim >= 512 and Q <= 32:
-                    # throughput mode: JBU + L2-norm + x T^T in one call; the [S^2, C] feature map never reaches HBM
+                    check(self.lib.sg_jbu_logits_wide(self._ctx, ptr(tk), ptr(guid), c, gh, gw, ph, pw, self.precision, ptr(text), Q,
+                                                      ptr(ci), lam, ptr(lg), wp, wn, stream_ptr(self.device)), "sg_jbu_logits_wide")
+                elif self.fused_tail and not self.is_resize_conv and self.precision == _lib.PREC_BF16 and self.feat_dim % 64 == 0 and self.feat_dim >= 512 and (Q <= 32 or (self.wide_tail and self.feat_dim <= 1216)):
+                    # throughput mode: JBU + L2-norm + x T^T in one call; the [S^2, C] feature map never reaches HBM (more than 32 queries:
+                    # the wide matrix-pipe tail, whose two resident query groups need C <= 1216; up to 32 the wide entry is sg_jbu_logits itself)
                     lg = torch.empty(c, Q, 256 * gh * gw, dtype=torch.float32, device=self.device)
                     tk = tokens[i:i + c].contiguous().float()
                     ci = None if (cls is None or lam == 0.0) else cls[i:i + c].contiguous().float()
-                    need = self.lib.sg_jbu_workspace_bytes(self._ctx, c, gh, gw)
+                    need = self.lib.sg_jbu_workspace_bytes_wide(self._ctx, c, gh, gw, Q)
                     wp, wn = self._workspace(need)
-                    check(self.lib.sg_jbu_logits(self._ctx, ptr(tk), ptr(guid), c, gh, gw, ph, pw, self.precision, ptr(text), Q, ptr(ci), lam,
-                                                 ptr(lg), wp, wn, stream_ptr(self.device)), "sg_jbu_logits")
+                    check(self.lib.sg_jbu_logits_wide(self._ctx, ptr(tk), ptr(guid), c, gh, gw, ph, pw, self.precision, ptr(text), Q, ptr(ci), lam,
+                                                      ptr(lg), wp, wn, stream_ptr(self.device)), "sg_jbu_logits_wide")
                 else:
                     feats = self.upsample_tokens(tokens[i:i + c], guid, gh, gw)                      # [c, 256 n, C]
                     lg = ops.cosine_logits(feats, None if cls is None else cls[i:i + c], text, 0.0, lam, two_plane=self.precision == _lib.PREC_F16X2)

@@ -434,6 +434,19 @@ int  sg_jbu_upsample(sg_jbu* j, const float* source, const float* guidance, int 
 int  sg_jbu_logits(sg_jbu* j, const float* source, const float* guidance, int B, int gh, int gw, int GH, int GW, int precision,
                    const float* text, int Q, const float* cls, float cls_token_lambda, float* logits, void* workspace, size_t workspace_bytes,
                    sg_stream s);
+/* sg_jbu_logits_wide: the contract and output layout [B, Q, 16gh*16gw] of sg_jbu_logits for any Q >= 1, i.e. segmentor.py:368-379 with a class
+ * file whose synonyms give more than 32 text rows (segmentor.py:262-276 builds one row per name).  Up to 32 queries it calls sg_jbu_logits: the
+ * same kernels, buffer strides and bits.  Beyond, the tail's product x . Geff runs on the matrix pipe with the queries in groups of 16
+ * (jbu_pixel_logits_wide_kernel: Geff as two bf16 planes in LDS, as many groups resident as fit, x re-read once per pass over the groups);
+ * geff / g0 / clsl then have the query stride Qp = 16 ceil(Q / 16), which is also what the GEFF [C,Qp], G0 [Qp] and CLSL [B,Qp] captures copy.
+ * Same conditions as sg_jbu_logits (SG_PREC_BF16, C % 64 == 0, C >= 512, 1024 <= pixels < 2^31, complete weights; resize_conv refused), each
+ * refused with its reason; beyond 32 queries also C <= 1216 (two groups' planes must fit the 160 KB of LDS) and Q < 65536.  Kind 2 ('bilinear', upsamplers.py:343-350): one call for any Q, the per-token prologue and the pixel
+ * kernel run per 32-query chunk and write their query planes in place -- per (pixel, query) the arithmetic of sg_jbu_logits on that chunk.
+ * sg_jbu_workspace_bytes_wide: the workspace of sg_jbu_logits_wide for Q queries (sg_jbu_workspace_bytes up to 32 queries and for kind 2). */
+size_t sg_jbu_workspace_bytes_wide(const sg_jbu* j, int B, int gh, int gw, int Q);
+int  sg_jbu_logits_wide(sg_jbu* j, const float* source, const float* guidance, int B, int gh, int gw, int GH, int GW, int precision,
+                        const float* text, int Q, const float* cls, float cls_token_lambda, float* logits, void* workspace,
+                        size_t workspace_bytes, sg_stream s);
 
 /* Test instrumentation of the upsampler (tests/test_gpu_jbu_reference.py).  sg_jbu_set_capture(j, cap) with a non-NULL cap makes every later
  * sg_jbu_upsample / sg_jbu_logits on j copy, on the call's stream, what each kernel of the unchanged kernel sequence read and wrote, in its
@@ -444,7 +457,8 @@ int  sg_jbu_logits(sg_jbu* j, const float* source, const float* guidance, int B,
  *   two-plane) | H1 GELU rows (f32 [px,d2], or [px,NP] 2-byte / two-plane) | KF kernel rows (f32 [px,d2] or [px,NP], f16 [px,NP]) |
  *   SRC the convolution's source as stored, taken just before it (f32, bf16 or two-plane, [B,h,w,C]) | HR the bicubic output (f32 / bf16) |
  *   OUT the stage's f32 output | OUT16 its bf16 / two-plane copy.
- * Tail: FIN_A the final 1x1 GEMM's A operand | FIN_RES its f32 residual | GEFF [C,32] | G0 [32] | CLSL [B,32] | ROWDOT [px, C/64].
+ * Tail: FIN_A the final 1x1 GEMM's A operand | FIN_RES its f32 residual | GEFF [C,32] | G0 [32] | CLSL [B,32] | ROWDOT [px, C/64]
+ *   (sg_jbu_logits_wide beyond 32 queries: query stride 16 ceil(Q / 16) in place of 32).
  * sg_jbu_last_kernels(): the calling thread's last sg_jbu_upsample / sg_jbu_logits as space-separated key=value tokens: per stage k
  * "sk.range= sk.x16= sk.fixup0= sk.fixup1= sk.kf= sk.src= sk.bicubic= sk.hr= sk.conv= sk.grid= sk.out16=", then "final=" (GEMM family) and
  * "tail=" (comma-separated kernels); "none" before the first call on the thread (a call refused by its argument checks leaves the
