@@ -235,326 +235,19 @@ __global__ __launch_bounds__(256) void cosine_logits_wide_kernel(const float* __
 // order, so the f32 sum is bit-identical), divided by the count and stored a single time.  The row test of a tile is wave-uniform
 // (one canvas row per wave) and runs on the scalar unit; queries go through the registers in chunks of ST_QC.
 constexpr int ST_QC = 8, ST_MAXC = 64;
-__global__ __launch_bounds__(256) void stitch_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows,
-                                                     int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t, int pad_l,
-                                                     int H, int W, float* __restrict__ canvas) {
-  // candidate tiles of this 64 x 4 pixel block, compacted IN RASTER ORDER by wave 0 (ballot + prefix popcount): the per-pixel
-  // loop then visits the handful of overlapping tiles instead of testing all T windows
+// One 64 x 4 pixel block of one image, the only copy of the gather: every stitch and label-head kernel, single-image or multi-image,
+// gets its stitched values here, so they agree bit for bit by construction.  tile_logits / win / tile_image point at the image's first
+// tile (tile_image == nullptr: every tile is this image's).  A thread whose row y lies in the image hands each finished chunk to
+// sink(x, y, q0, acc, cnt): acc[k] = the sum over the cnt tiles that cover (x, y) for query q0 + k (k < ST_QC, q0 + k < Q), not yet
+// divided; x may lie beyond W (cnt = 0 then).
+template <class Sink>
+__device__ __forceinline__ void stitch_block(const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
+                                             const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw, int up_h,
+                                             int up_w, int pad_t, int pad_l, int H, int W, int bx0, int by0, Sink&& sink) {
   __shared__ int s_list[ST_MAXC];
   __shared__ int s_count;
-  const int lane = threadIdx.x & 63;
-  const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * 4;
-  if ((threadIdx.x >> 6) == 0) {
-    int base = 0;
-    for (int t0 = 0; t0 < T; t0 += 64) {
-      const int t = t0 + lane;
-      bool hit = false;
-      if (t < T) {
-        const int y1 = windows[t * 4 + 0], y2 = windows[t * 4 + 1], x1 = windows[t * 4 + 2], x2 = windows[t * 4 + 3];
-        hit = y1 < by0 + 4 && y2 > by0 && x1 < bx0 + 64 && x2 > bx0;
-      }
-      const unsigned long long m = __ballot(hit);
-      const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-      if (hit && pos < ST_MAXC) s_list[pos] = t;
-      base += __popcll(m);
-    }
-    if (lane == 0) s_count = base;
-  }
-  __syncthreads();
-  const int n_cand = s_count;
-  const bool use_list = n_cand <= ST_MAXC;                         // pathological overlap (stride << crop): test every window
-  const int n_iter = use_list ? n_cand : T;
-  const int x = bx0 + lane;
-  const int y = __builtin_amdgcn_readfirstlane(by0 + (threadIdx.x >> 6));
-  if (y >= H) return;
-  const int64_t plane = (int64_t)H * W;
-  const int64_t tile_sz = (int64_t)gh * gw;
-  for (int q0 = 0; q0 < Q; q0 += ST_QC) {
-    float acc[ST_QC];
-#pragma unroll
-    for (int k = 0; k < ST_QC; ++k) acc[k] = 0.f;
-    float cnt = 0.f;
-    for (int it = 0; it < n_iter; ++it) {                              // raster order = the reference's add order
-      const int t = use_list ? s_list[it] : it;
-      const int y1 = windows[t * 4 + 0], y2 = windows[t * 4 + 1];
-      if (y < y1 || y >= y2) continue;                                 // wave-uniform: the whole wave skips the tile
-      const int x1 = windows[t * 4 + 2], x2 = windows[t * 4 + 3];
-      if (x < x1 || x >= x2 || x >= W) continue;
-      int ya, yb, xa, xb; float wy0, wy1, wx0, wx1;
-      bilinear_tap(y - y1 + pad_t, gh, up_h, ya, yb, wy0, wy1);
-      bilinear_tap(x - x1 + pad_l, gw, up_w, xa, xb, wx0, wx1);
-      const float* base = tile_logits + ((int64_t)t * Q + q0) * tile_sz;
-#pragma unroll
-      for (int k = 0; k < ST_QC; ++k) {
-        if (q0 + k < Q) {
-          const float* p = base + (int64_t)k * tile_sz;
-          const float top = p[ya * gw + xa] * wx0 + p[ya * gw + xb] * wx1;
-          const float bot = p[yb * gw + xa] * wx0 + p[yb * gw + xb] * wx1;
-          acc[k] += top * wy0 + bot * wy1;
-        }
-      }
-      cnt += 1.f;
-    }
-    if (x < W) {
-#pragma unroll
-      for (int k = 0; k < ST_QC; ++k)
-        if (q0 + k < Q) canvas[(q0 + k) * plane + (int64_t)y * W + x] = cnt > 0.f ? acc[k] / cnt : 0.f;
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __restrict__ src, int C, int h, int w,
-                                                              float* __restrict__ dst, int H, int W) {
-  const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (x >= W || y >= H) return;
-  int ya, yb, xa, xb; float wy0, wy1, wx0, wx1;
-  bilinear_tap(y, h, H, ya, yb, wy0, wy1);
-  bilinear_tap(x, w, W, xa, xb, wx0, wx1);
-  for (int c = 0; c < C; ++c) {
-    const float* p = src + (int64_t)c * h * w;
-    const float top = p[ya * w + xa] * wx0 + p[ya * w + xb] * wx1;
-    const float bot = p[yb * w + xa] * wx0 + p[yb * w + xb] * wx1;
-    dst[((int64_t)c * H + y) * W + x] = top * wy0 + bot * wy1;
-  }
-}
-
-// ---- postprocess ----------------------------------------------------------------------------------------------------
-constexpr int PP_MAX_Q = 64;
-// QMAX is a compile-time bound on Q so that v[] lives in registers (a runtime-sized v[64] goes to scratch memory)
-template <int QMAX>
-__global__ __launch_bounds__(256) void postprocess_kernel(const float* __restrict__ logits, const int32_t* __restrict__ query_idx,
-                                                          int Q, int K, int64_t HW, float logit_scale, float prob_thd, int bg_idx,
-                                                          float* __restrict__ probs, int64_t* __restrict__ labels) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= HW) return;
-  float v[QMAX];
-  float mx = -INFINITY;
-#pragma unroll
-  for (int q = 0; q < QMAX; ++q)
-    if (q < Q) { v[q] = logits[q * HW + i] * logit_scale; mx = fmaxf(mx, v[q]); }
-  float sum = 0.f;
-#pragma unroll
-  for (int q = 0; q < QMAX; ++q)
-    if (q < Q) { v[q] = expf(v[q] - mx); sum += v[q]; }
-  float best = -INFINITY; int arg = 0;
-  for (int c = 0; c < K; ++c) {
-    float pc;
-    if (K == Q) {
-      pc = 0.f;
-#pragma unroll
-      for (int q = 0; q < QMAX; ++q) if (q == c) pc = v[q] / sum;       // static indexing keeps v[] in registers
-    } else {
-      // (probabilities * one_hot).max over queries (segmentor.py:484-486): zeros take part in the max
-      bool any_other = false;
-      float m = -INFINITY;
-#pragma unroll
-      for (int q = 0; q < QMAX; ++q)
-        if (q < Q) { if (query_idx[q] == c) m = fmaxf(m, v[q] / sum); else any_other = true; }
-      pc = any_other ? fmaxf(m, 0.f) : m;
-    }
-    if (probs) probs[c * HW + i] = pc;
-    if (pc > best) { best = pc; arg = c; }                                // first maximum wins (torch argmax)
-  }
-  if (best < prob_thd) arg = bg_idx;
-  labels[i] = arg;
-}
-
-// ---- multi-canvas head: the canvases of N images in one launch ---------------------------------------------------------
-// The grid is flattened over (image, block): block_prefix[n] is the first block of image n (an exclusive prefix sum, N + 1
-// entries).  The image of a block is found by a wave-uniform binary search; no host loop over images.
-__device__ __forceinline__ int image_of_block(const int64_t* __restrict__ block_prefix, int N, int64_t blk) {
-  int lo = 0, hi = N;                                              // largest n with block_prefix[n] <= blk (skips empty images)
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (block_prefix[mid] <= blk) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-// stitch_kernel for the tiles of many images: tiles [first, first + count) of image n, windows in that image's coordinates,
-// its canvas [Q,H,W] at canvas_offset[n].  The per-pixel arithmetic, the raster-order candidate list and the averaging order are
-// those of stitch_kernel, so every canvas is bit-identical to sg_stitch on that image alone.
-__global__ __launch_bounds__(256) void stitch_multi_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows,
-                                                           const int32_t* __restrict__ tile_image, int T, int Q, int gh, int gw,
-                                                           int up_h, int up_w, int pad_t, int pad_l, const int32_t* __restrict__ image_hw,
-                                                           const int32_t* __restrict__ image_tiles, const int64_t* __restrict__ canvas_offset,
-                                                           const int64_t* __restrict__ block_prefix, int N, int64_t canvas_elems,
-                                                           float* __restrict__ canvases) {
-  __shared__ int s_list[ST_MAXC];
-  __shared__ int s_count;
-  const int n = image_of_block(block_prefix, N, blockIdx.x);
-  const int H = image_hw[2 * n], W = image_hw[2 * n + 1];
-  const int t_first = image_tiles[2 * n], n_tiles = image_tiles[2 * n + 1];
-  const int64_t plane = (int64_t)H * W;
-  const int64_t off = canvas_offset[n];
-  // a descriptor that would read or write outside the buffers: the whole block leaves (block-uniform, before any barrier)
-  if (t_first < 0 || n_tiles <= 0 || t_first + n_tiles > T || off < 0 || off + Q * plane > canvas_elems) return;
-  const int64_t local = blockIdx.x - block_prefix[n];
-  const int bw = (W + 63) / 64;
-  const int bx0 = (int)(local % bw) * 64, by0 = (int)(local / bw) * 4;
-  const int lane = threadIdx.x & 63;
-  const int32_t* win = windows + (int64_t)t_first * 4;
-  if ((threadIdx.x >> 6) == 0) {
-    int base = 0;
-    for (int t0 = 0; t0 < n_tiles; t0 += 64) {
-      const int t = t0 + lane;
-      bool hit = false;
-      if (t < n_tiles && tile_image[t_first + t] == n) {
-        const int y1 = win[t * 4 + 0], y2 = win[t * 4 + 1], x1 = win[t * 4 + 2], x2 = win[t * 4 + 3];
-        hit = y1 < by0 + 4 && y2 > by0 && x1 < bx0 + 64 && x2 > bx0;
-      }
-      const unsigned long long m = __ballot(hit);
-      const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-      if (hit && pos < ST_MAXC) s_list[pos] = t;
-      base += __popcll(m);
-    }
-    if (lane == 0) s_count = base;
-  }
-  __syncthreads();
-  const int n_cand = s_count;
-  const bool use_list = n_cand <= ST_MAXC;
-  const int n_iter = use_list ? n_cand : n_tiles;
-  const int x = bx0 + lane;
-  const int y = __builtin_amdgcn_readfirstlane(by0 + (threadIdx.x >> 6));
-  if (y >= H) return;
-  const int64_t tile_sz = (int64_t)gh * gw;
-  float* canvas = canvases + off;
-  for (int q0 = 0; q0 < Q; q0 += ST_QC) {
-    float acc[ST_QC];
-#pragma unroll
-    for (int k = 0; k < ST_QC; ++k) acc[k] = 0.f;
-    float cnt = 0.f;
-    for (int it = 0; it < n_iter; ++it) {
-      const int t = use_list ? s_list[it] : it;
-      if (!use_list && tile_image[t_first + t] != n) continue;
-      const int y1 = win[t * 4 + 0], y2 = win[t * 4 + 1];
-      if (y < y1 || y >= y2) continue;
-      const int x1 = win[t * 4 + 2], x2 = win[t * 4 + 3];
-      if (x < x1 || x >= x2 || x >= W) continue;
-      int ya, yb, xa, xb; float wy0, wy1, wx0, wx1;
-      bilinear_tap(y - y1 + pad_t, gh, up_h, ya, yb, wy0, wy1);
-      bilinear_tap(x - x1 + pad_l, gw, up_w, xa, xb, wx0, wx1);
-      const float* base = tile_logits + ((int64_t)(t_first + t) * Q + q0) * tile_sz;
-#pragma unroll
-      for (int k = 0; k < ST_QC; ++k) {
-        if (q0 + k < Q) {
-          const float* p = base + (int64_t)k * tile_sz;
-          const float top = p[ya * gw + xa] * wx0 + p[ya * gw + xb] * wx1;
-          const float bot = p[yb * gw + xa] * wx0 + p[yb * gw + xb] * wx1;
-          acc[k] += top * wy0 + bot * wy1;
-        }
-      }
-      cnt += 1.f;
-    }
-    if (x < W) {
-#pragma unroll
-      for (int k = 0; k < ST_QC; ++k)
-        if (q0 + k < Q) canvas[(q0 + k) * plane + (int64_t)y * W + x] = cnt > 0.f ? acc[k] / cnt : 0.f;
-    }
-  }
-}
-
-// postprocess_kernel for N canvases, 256 output pixels per block: canvas n [Q,h,w] at canvas_offset[n]; its outputs are
-// labels [H,W] at out_offset[n] and probs [K,H,W] at K * out_offset[n].  When (H,W) != (h,w) the align_corners=False bilinear
-// resize of resize_bilinear_kernel is evaluated per output pixel (no resized canvas is written).  The arithmetic after the load is
-// postprocess_kernel's, so the outputs are bit-identical to sg_resize_bilinear + sg_postprocess per image.
-template <int QMAX>
-__global__ __launch_bounds__(256) void postprocess_multi_kernel(const float* __restrict__ canvases, const int32_t* __restrict__ canvas_hw,
-                                                                const int64_t* __restrict__ canvas_offset, const int32_t* __restrict__ out_hw,
-                                                                const int64_t* __restrict__ out_offset, const int64_t* __restrict__ block_prefix,
-                                                                int N, int64_t canvas_elems, int64_t out_pixels,
-                                                                const int32_t* __restrict__ query_idx, int Q, int K, float logit_scale,
-                                                                float prob_thd, int bg_idx, float* __restrict__ probs,
-                                                                int64_t* __restrict__ labels) {
-  const int n = image_of_block(block_prefix, N, blockIdx.x);
-  const int h = canvas_hw[2 * n], w = canvas_hw[2 * n + 1], H = out_hw[2 * n], W = out_hw[2 * n + 1];
-  const int64_t coff = canvas_offset[n], ooff = out_offset[n];
-  const int64_t hw = (int64_t)h * w, HW = (int64_t)H * W;
-  if (coff < 0 || coff + Q * hw > canvas_elems || ooff < 0 || ooff + HW > out_pixels) return;
-  const int64_t i = (blockIdx.x - block_prefix[n]) * 256 + threadIdx.x;
-  if (i >= HW) return;
-  const float* logits = canvases + coff;
-  const bool resize = h != H || w != W;
-  int ya = 0, yb = 0, xa = 0, xb = 0; float wy0 = 0.f, wy1 = 0.f, wx0 = 0.f, wx1 = 0.f;
-  if (resize) {
-    bilinear_tap((int)(i / W), h, H, ya, yb, wy0, wy1);
-    bilinear_tap((int)(i % W), w, W, xa, xb, wx0, wx1);
-  }
-  float v[QMAX];
-  float mx = -INFINITY;
-#pragma unroll
-  for (int q = 0; q < QMAX; ++q)
-    if (q < Q) {
-      float l;
-      if (resize) {
-        // resize_bilinear_kernel's arithmetic exactly as it is compiled there, spelled out so that this kernel cannot contract it any
-        // other way.  Its channel loop is vectorised two channels at a time (v_pk_fma_f32: first product of each sum fused); an odd
-        // last channel runs through the loop's scalar remainder, which fuses the other product of `top` and rounds both products of
-        // the final blend.  Mirroring both keeps this bit-identical to sg_resize_bilinear for every Q (pinned by tests/test_gpu_batch.py
-        // for even and odd Q; a compiler that vectorised that loop differently would show up there).
-#pragma clang fp contract(off)
-        const float* p = logits + (int64_t)q * h * w;
-        if ((Q & 1) && q == Q - 1) {
-          const float top = __builtin_fmaf(p[ya * w + xb], wx1, p[ya * w + xa] * wx0);
-          const float bot = __builtin_fmaf(p[yb * w + xa], wx0, p[yb * w + xb] * wx1);
-          l = top * wy0 + bot * wy1;
-        } else {
-          const float top = __builtin_fmaf(p[ya * w + xa], wx0, p[ya * w + xb] * wx1);
-          const float bot = __builtin_fmaf(p[yb * w + xa], wx0, p[yb * w + xb] * wx1);
-          l = __builtin_fmaf(top, wy0, bot * wy1);
-        }
-        asm volatile("" : "+v"(l));     // opaque from here on, like a loaded value: the softmax below compiles as postprocess_kernel's
-      } else {
-        l = logits[q * hw + i];
-      }
-      v[q] = l * logit_scale; mx = fmaxf(mx, v[q]);
-    }
-  float sum = 0.f;
-#pragma unroll
-  for (int q = 0; q < QMAX; ++q)
-    if (q < Q) { v[q] = expf(v[q] - mx); sum += v[q]; }
-  float best = -INFINITY; int arg = 0;
-  float* pr = probs ? probs + K * ooff : nullptr;
-  for (int c = 0; c < K; ++c) {
-    float pc;
-    if (K == Q) {
-      pc = 0.f;
-#pragma unroll
-      for (int q = 0; q < QMAX; ++q) if (q == c) pc = v[q] / sum;
-    } else {
-      bool any_other = false;
-      float m = -INFINITY;
-#pragma unroll
-      for (int q = 0; q < QMAX; ++q)
-        if (q < Q) { if (query_idx[q] == c) m = fmaxf(m, v[q] / sum); else any_other = true; }
-      pc = any_other ? fmaxf(m, 0.f) : m;
-    }
-    if (pr) pr[c * HW + i] = pc;
-    if (pc > best) { best = pc; arg = c; }
-  }
-  if (best < prob_thd) arg = bg_idx;
-  labels[ooff + i] = arg;
-}
-
-// ---- fused label head: stitch -> softmax -> synonym merge -> argmax -> threshold, labels only, any Q ---------------------------
-// One 64 x 4 pixel block of one image, shared by the single-image and the multi-image kernel (so the two agree byte for byte).  The
-// stitched value of a query is stitch_kernel's: bilinear_tap taps, the covering tiles summed in raster order (the same candidate list and
-// the same fall-back beyond ST_MAXC), divided by the count.  No canvas exists: queries pass through the registers in chunks of ST_QC and
-// only a running maximum, the running sum of exp(v - max) and the best (value, class) pair survive a chunk.
-//   Online maximum and sum, not a second pass that recomputes the stitched values: the gathers are the cost of this kernel (four loads
-//   and seven multiply-adds per covering tile and query, all of it address-dependent), a second pass would double them, while the
-//   online form adds one expf per chunk of ST_QC queries (the rescale of the sum when the maximum moves).  The order of every operation
-//   is fixed by (pixel, query index), so repeats are byte-identical.
-// softmax is monotone, so the class of the largest class probability is the class of the largest scaled logit; among queries that
-// share that largest value the lowest class index wins (torch.argmax's first maximum).  Queries whose class lies outside [0,K) only
-// take part in the sum, as in postprocess_kernel.  conf = exp(v_best - v_max) / sum = 1 / sum exp(v_q - v_max).
-__device__ __forceinline__ void label_head_block(const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
-                                                 const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw,
-                                                 int up_h, int up_w, int pad_t, int pad_l, int H, int W, int bx0, int by0,
-                                                 const int32_t* __restrict__ query_idx, int K, float logit_scale, float prob_thd,
-                                                 int bg_idx, int64_t* __restrict__ labels, float* __restrict__ conf, int* s_list,
-                                                 int* s_count) {
+  // candidate tiles of this block, compacted IN RASTER ORDER by wave 0 (ballot + prefix popcount): the per-pixel loop then visits the
+  // handful of overlapping tiles instead of testing all n_tiles windows
   const int lane = threadIdx.x & 63;
   if ((threadIdx.x >> 6) == 0) {
     int base = 0;
@@ -570,18 +263,16 @@ __device__ __forceinline__ void label_head_block(const float* __restrict__ tile_
       if (hit && pos < ST_MAXC) s_list[pos] = t;
       base += __popcll(m);
     }
-    if (lane == 0) *s_count = base;
+    if (lane == 0) s_count = base;
   }
   __syncthreads();
-  const int n_cand = *s_count;
+  const int n_cand = s_count;
   const bool use_list = n_cand <= ST_MAXC;                         // pathological overlap (stride << crop): test every window
   const int n_iter = use_list ? n_cand : n_tiles;
   const int x = bx0 + lane;
   const int y = __builtin_amdgcn_readfirstlane(by0 + (threadIdx.x >> 6));
   if (y >= H) return;
   const int64_t tile_sz = (int64_t)gh * gw;
-  float vmax = -INFINITY, sum = 0.f, best = -INFINITY;
-  int best_c = 0;
   for (int q0 = 0; q0 < Q; q0 += ST_QC) {
     float acc[ST_QC];
 #pragma unroll
@@ -609,23 +300,241 @@ __device__ __forceinline__ void label_head_block(const float* __restrict__ tile_
       }
       cnt += 1.f;
     }
-    {
-#pragma clang fp contract(off)        // the scaled logit is rounded before the subtraction, as postprocess_kernel compiles it
-      float cm = -INFINITY;
-#pragma unroll
-      for (int k = 0; k < ST_QC; ++k)
-        if (q0 + k < Q) { acc[k] = (cnt > 0.f ? acc[k] / cnt : 0.f) * logit_scale; cm = fmaxf(cm, acc[k]); }
-      if (cm > vmax) { sum *= expf(vmax - cm); vmax = cm; }            // the first chunk: sum = 0 * exp(-inf) = 0
-#pragma unroll
-      for (int k = 0; k < ST_QC; ++k)
-        if (q0 + k < Q) {
-          sum += expf(acc[k] - vmax);
-          const int c = K == Q ? q0 + k : query_idx[q0 + k];
-          if (c >= 0 && c < K && (acc[k] > best || (acc[k] == best && c < best_c))) { best = acc[k]; best_c = c; }
-        }
-    }
+    sink(x, y, q0, acc, cnt);
   }
-  if (x >= W) return;
+}
+
+// The block's stitched values, count-normalised, into the image's canvas [Q,H,W].
+__device__ __forceinline__ void stitch_canvas_block(const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
+                                                    const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw,
+                                                    int up_h, int up_w, int pad_t, int pad_l, int H, int W, int bx0, int by0,
+                                                    float* __restrict__ canvas) {
+  const int64_t plane = (int64_t)H * W;
+  stitch_block(tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, bx0, by0,
+               [&](int x, int y, int q0, const float (&acc)[ST_QC], float cnt) {
+                 if (x >= W) return;
+#pragma unroll
+                 for (int k = 0; k < ST_QC; ++k)
+                   if (q0 + k < Q) canvas[(q0 + k) * plane + (int64_t)y * W + x] = cnt > 0.f ? acc[k] / cnt : 0.f;
+               });
+}
+
+__global__ __launch_bounds__(256) void stitch_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows,
+                                                     int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t, int pad_l,
+                                                     int H, int W, float* __restrict__ canvas) {
+  stitch_canvas_block(tile_logits, windows, nullptr, 0, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, blockIdx.x * 64, blockIdx.y * 4, canvas);
+}
+
+__global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __restrict__ src, int C, int h, int w,
+                                                              float* __restrict__ dst, int H, int W) {
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (x >= W || y >= H) return;
+  int ya, yb, xa, xb; float wy0, wy1, wx0, wx1;
+  bilinear_tap(y, h, H, ya, yb, wy0, wy1);
+  bilinear_tap(x, w, W, xa, xb, wx0, wx1);
+  for (int c = 0; c < C; ++c) {
+    const float* p = src + (int64_t)c * h * w;
+    const float top = p[ya * w + xa] * wx0 + p[ya * w + xb] * wx1;
+    const float bot = p[yb * w + xa] * wx0 + p[yb * w + xb] * wx1;
+    dst[((int64_t)c * H + y) * W + x] = top * wy0 + bot * wy1;
+  }
+}
+
+// ---- postprocess ----------------------------------------------------------------------------------------------------
+constexpr int PP_MAX_Q = 64;
+// Pixel i of an image from its logits to its outputs, the only copy of the tail: sg_postprocess and sg_postprocess_multi differ in how
+// logit q is loaded and where the image's outputs start, so they agree bit for bit by construction.  load(q) = logit q of the pixel; the
+// image's labels [HW] start at pixel ooff of the flat outputs, its probs [K,HW] (when wanted) at K * ooff.  QMAX is a compile-time
+// bound on Q so that v[] lives in registers (a runtime-sized v[64] goes to scratch memory).  The outputs are addressed in here, after
+// the exponentials: with the offsets folded into pointers by the caller, postprocess_multi_kernel<64> took 144 VGPRs instead of 85
+// (3 waves per SIMD instead of 5).
+template <int QMAX, class Load>
+__device__ __forceinline__ void class_tail(Load&& load, const int32_t* __restrict__ query_idx, int Q, int K, float logit_scale,
+                                           float prob_thd, int bg_idx, float* __restrict__ probs, int64_t* __restrict__ labels,
+                                           int64_t ooff, int64_t HW, int64_t i) {
+  float v[QMAX];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int q = 0; q < QMAX; ++q)
+    if (q < Q) { v[q] = load(q) * logit_scale; mx = fmaxf(mx, v[q]); }
+  float sum = 0.f;
+#pragma unroll
+  for (int q = 0; q < QMAX; ++q)
+    if (q < Q) { v[q] = expf(v[q] - mx); sum += v[q]; }
+  float best = -INFINITY; int arg = 0;
+  float* pr = probs ? probs + K * ooff : nullptr;
+  for (int c = 0; c < K; ++c) {
+    float pc;
+    if (K == Q) {
+      pc = 0.f;
+#pragma unroll
+      for (int q = 0; q < QMAX; ++q) if (q == c) pc = v[q] / sum;       // static indexing keeps v[] in registers
+    } else {
+      // (probabilities * one_hot).max over queries (segmentor.py:484-486): zeros take part in the max
+      bool any_other = false;
+      float m = -INFINITY;
+#pragma unroll
+      for (int q = 0; q < QMAX; ++q)
+        if (q < Q) { if (query_idx[q] == c) m = fmaxf(m, v[q] / sum); else any_other = true; }
+      pc = any_other ? fmaxf(m, 0.f) : m;
+    }
+    if (pr) pr[c * HW + i] = pc;
+    if (pc > best) { best = pc; arg = c; }                                // first maximum wins (torch argmax)
+  }
+  if (best < prob_thd) arg = bg_idx;
+  labels[ooff + i] = arg;
+}
+
+template <int QMAX>
+__global__ __launch_bounds__(256) void postprocess_kernel(const float* __restrict__ logits, const int32_t* __restrict__ query_idx,
+                                                          int Q, int K, int64_t HW, float logit_scale, float prob_thd, int bg_idx,
+                                                          float* __restrict__ probs, int64_t* __restrict__ labels) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= HW) return;
+  class_tail<QMAX>([&](int q) { return logits[q * HW + i]; }, query_idx, Q, K, logit_scale, prob_thd, bg_idx, probs, labels, 0, HW, i);
+}
+
+// ---- multi-canvas head: the canvases of N images in one launch ---------------------------------------------------------
+// The grid is flattened over (image, block): block_prefix[n] is the first block of image n (an exclusive prefix sum, N + 1
+// entries).  The image of a block is found by a wave-uniform binary search; no host loop over images.
+__device__ __forceinline__ int image_of_block(const int64_t* __restrict__ block_prefix, int N, int64_t blk) {
+  int lo = 0, hi = N;                                              // largest n with block_prefix[n] <= blk (skips empty images)
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (block_prefix[mid] <= blk) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// The descriptors sg_stitch_multi and sg_label_head_multi share, decoded for this block: image n is (H, W) = image_hw[n], its tiles are
+// [t_first, t_first + n_tiles) = image_tiles[n], it owns per_pixel * H * W elements at out_offset[n] of an output of out_elems, and its
+// blocks of 64 x 4 pixels follow block_prefix[n] in raster order.
+struct ImageBlock { int n, H, W, t_first, n_tiles, bx0, by0; int64_t off; };
+// false: a descriptor that would read or write outside the buffers, or a block past the image's last.  The whole block leaves then
+// (block-uniform; callers return before any barrier).
+__device__ __forceinline__ bool image_block(const int32_t* __restrict__ image_hw, const int32_t* __restrict__ image_tiles,
+                                            const int64_t* __restrict__ out_offset, const int64_t* __restrict__ block_prefix, int N, int T,
+                                            int64_t per_pixel, int64_t out_elems, ImageBlock& ib) {
+  const int n = image_of_block(block_prefix, N, blockIdx.x);
+  ib.n = n;
+  ib.H = image_hw[2 * n]; ib.W = image_hw[2 * n + 1];
+  ib.t_first = image_tiles[2 * n]; ib.n_tiles = image_tiles[2 * n + 1];
+  ib.off = out_offset[n];
+  if (ib.H <= 0 || ib.W <= 0 || ib.t_first < 0 || ib.n_tiles <= 0 || ib.t_first + ib.n_tiles > T || ib.off < 0 ||
+      ib.off + per_pixel * ((int64_t)ib.H * ib.W) > out_elems)
+    return false;
+  const int64_t local = blockIdx.x - block_prefix[n];
+  const int bw = (ib.W + 63) / 64;
+  ib.bx0 = (int)(local % bw) * 64; ib.by0 = (int)(local / bw) * 4;
+  return local < (int64_t)bw * ((ib.H + 3) / 4);
+}
+
+// stitch_kernel for the tiles of many images: tiles [first, first + count) of image n, windows in that image's coordinates,
+// its canvas [Q,H,W] at canvas_offset[n].  Both run stitch_canvas_block, so every canvas is bit-identical to sg_stitch on that image
+// alone.
+__global__ __launch_bounds__(256) void stitch_multi_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows,
+                                                           const int32_t* __restrict__ tile_image, int T, int Q, int gh, int gw,
+                                                           int up_h, int up_w, int pad_t, int pad_l, const int32_t* __restrict__ image_hw,
+                                                           const int32_t* __restrict__ image_tiles, const int64_t* __restrict__ canvas_offset,
+                                                           const int64_t* __restrict__ block_prefix, int N, int64_t canvas_elems,
+                                                           float* __restrict__ canvases) {
+  ImageBlock ib;
+  if (!image_block(image_hw, image_tiles, canvas_offset, block_prefix, N, T, Q, canvas_elems, ib)) return;
+  stitch_canvas_block(tile_logits + (int64_t)ib.t_first * Q * gh * gw, windows + (int64_t)ib.t_first * 4, tile_image + ib.t_first, ib.n,
+                      ib.n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, ib.H, ib.W, ib.bx0, ib.by0, canvases + ib.off);
+}
+
+// postprocess_kernel for N canvases, 256 output pixels per block: canvas n [Q,h,w] at canvas_offset[n]; its outputs are
+// labels [H,W] at out_offset[n] and probs [K,H,W] at K * out_offset[n].  When (H,W) != (h,w) the align_corners=False bilinear
+// resize of resize_bilinear_kernel is evaluated per output pixel (no resized canvas is written).  Everything after the load is class_tail,
+// shared with postprocess_kernel, so the outputs are bit-identical to sg_resize_bilinear + sg_postprocess per image.
+template <int QMAX>
+__global__ __launch_bounds__(256) void postprocess_multi_kernel(const float* __restrict__ canvases, const int32_t* __restrict__ canvas_hw,
+                                                                const int64_t* __restrict__ canvas_offset, const int32_t* __restrict__ out_hw,
+                                                                const int64_t* __restrict__ out_offset, const int64_t* __restrict__ block_prefix,
+                                                                int N, int64_t canvas_elems, int64_t out_pixels,
+                                                                const int32_t* __restrict__ query_idx, int Q, int K, float logit_scale,
+                                                                float prob_thd, int bg_idx, float* __restrict__ probs,
+                                                                int64_t* __restrict__ labels) {
+  const int n = image_of_block(block_prefix, N, blockIdx.x);
+  const int h = canvas_hw[2 * n], w = canvas_hw[2 * n + 1], H = out_hw[2 * n], W = out_hw[2 * n + 1];
+  const int64_t coff = canvas_offset[n], ooff = out_offset[n];
+  const int64_t hw = (int64_t)h * w, HW = (int64_t)H * W;
+  if (coff < 0 || coff + Q * hw > canvas_elems || ooff < 0 || ooff + HW > out_pixels) return;
+  const int64_t i = (blockIdx.x - block_prefix[n]) * 256 + threadIdx.x;
+  if (i >= HW) return;
+  const float* logits = canvases + coff;
+  const bool resize = h != H || w != W;
+  int ya = 0, yb = 0, xa = 0, xb = 0; float wy0 = 0.f, wy1 = 0.f, wx0 = 0.f, wx1 = 0.f;
+  if (resize) {
+    bilinear_tap((int)(i / W), h, H, ya, yb, wy0, wy1);
+    bilinear_tap((int)(i % W), w, W, xa, xb, wx0, wx1);
+  }
+  class_tail<QMAX>([&](int q) {
+    float l;
+    if (resize) {
+      // resize_bilinear_kernel's arithmetic exactly as it is compiled there, spelled out so that this kernel cannot contract it any
+      // other way.  Its channel loop is vectorised two channels at a time (v_pk_fma_f32: first product of each sum fused); an odd
+      // last channel runs through the loop's scalar remainder, which fuses the other product of `top` and rounds both products of
+      // the final blend.  Mirroring both keeps this bit-identical to sg_resize_bilinear for every Q (pinned by tests/test_gpu_batch.py
+      // for even and odd Q; a compiler that vectorised that loop differently would show up there).
+#pragma clang fp contract(off)
+      const float* p = logits + (int64_t)q * h * w;
+      if ((Q & 1) && q == Q - 1) {
+        const float top = __builtin_fmaf(p[ya * w + xb], wx1, p[ya * w + xa] * wx0);
+        const float bot = __builtin_fmaf(p[yb * w + xa], wx0, p[yb * w + xb] * wx1);
+        l = top * wy0 + bot * wy1;
+      } else {
+        const float top = __builtin_fmaf(p[ya * w + xa], wx0, p[ya * w + xb] * wx1);
+        const float bot = __builtin_fmaf(p[yb * w + xa], wx0, p[yb * w + xb] * wx1);
+        l = __builtin_fmaf(top, wy0, bot * wy1);
+      }
+      asm volatile("" : "+v"(l));     // opaque from here on, like a loaded value: the tail compiles as postprocess_kernel's
+    } else {
+      l = logits[q * hw + i];
+    }
+    return l;
+  }, query_idx, Q, K, logit_scale, prob_thd, bg_idx, probs, labels, ooff, HW, i);
+}
+
+// ---- fused label head: stitch -> softmax -> synonym merge -> argmax -> threshold, labels only, any Q ---------------------------
+// One 64 x 4 pixel block of one image, shared by the single-image and the multi-image kernel (so the two agree byte for byte).  The
+// stitched value of a query is stitch_kernel's because both get it from stitch_block, then divide by the count.  No canvas exists:
+// queries pass through the registers in chunks of ST_QC and only a running maximum, the running sum of exp(v - max) and the best (value, class) pair survive a chunk.
+//   Online maximum and sum, not a second pass that recomputes the stitched values: the gathers are the cost of this kernel (four loads
+//   and seven multiply-adds per covering tile and query, all of it address-dependent), a second pass would double them, while the
+//   online form adds one expf per chunk of ST_QC queries (the rescale of the sum when the maximum moves).  The order of every operation
+//   is fixed by (pixel, query index), so repeats are byte-identical.
+// softmax is monotone, so the class of the largest class probability is the class of the largest scaled logit; among queries that
+// share that largest value the lowest class index wins (torch.argmax's first maximum).  Queries whose class lies outside [0,K) only
+// take part in the sum, as in postprocess_kernel.  conf = exp(v_best - v_max) / sum = 1 / sum exp(v_q - v_max).
+__device__ __forceinline__ void label_head_block(const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
+                                                 const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw,
+                                                 int up_h, int up_w, int pad_t, int pad_l, int H, int W, int bx0, int by0,
+                                                 const int32_t* __restrict__ query_idx, int K, float logit_scale, float prob_thd,
+                                                 int bg_idx, int64_t* __restrict__ labels, float* __restrict__ conf) {
+  float vmax = -INFINITY, sum = 0.f, best = -INFINITY;
+  int best_c = 0;
+  stitch_block(tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, bx0, by0,
+               [&](int, int, int q0, float (&acc)[ST_QC], float cnt) {
+#pragma clang fp contract(off)        // the scaled logit is rounded before the subtraction, as postprocess_kernel compiles it
+                 float cm = -INFINITY;
+#pragma unroll
+                 for (int k = 0; k < ST_QC; ++k)
+                   if (q0 + k < Q) { acc[k] = (cnt > 0.f ? acc[k] / cnt : 0.f) * logit_scale; cm = fmaxf(cm, acc[k]); }
+                 if (cm > vmax) { sum *= expf(vmax - cm); vmax = cm; }            // the first chunk: sum = 0 * exp(-inf) = 0
+#pragma unroll
+                 for (int k = 0; k < ST_QC; ++k)
+                   if (q0 + k < Q) {
+                     sum += expf(acc[k] - vmax);
+                     const int c = K == Q ? q0 + k : query_idx[q0 + k];
+                     if (c >= 0 && c < K && (acc[k] > best || (acc[k] == best && c < best_c))) { best = acc[k]; best_c = c; }
+                   }
+               });
+  const int x = bx0 + (threadIdx.x & 63);
+  const int y = __builtin_amdgcn_readfirstlane(by0 + (threadIdx.x >> 6));
+  if (y >= H || x >= W) return;
   const float cf = expf(best - vmax) / sum;
   const int64_t o = (int64_t)y * W + x;
   labels[o] = cf < prob_thd ? bg_idx : best_c;
@@ -637,10 +546,8 @@ __global__ __launch_bounds__(256) void label_head_kernel(const float* __restrict
                                                          int W, const int32_t* __restrict__ query_idx, int K, float logit_scale,
                                                          float prob_thd, int bg_idx, int64_t* __restrict__ labels,
                                                          float* __restrict__ conf) {
-  __shared__ int s_list[ST_MAXC];
-  __shared__ int s_count;
   label_head_block(tile_logits, windows, nullptr, 0, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, blockIdx.x * 64, blockIdx.y * 4,
-                   query_idx, K, logit_scale, prob_thd, bg_idx, labels, conf, s_list, &s_count);
+                   query_idx, K, logit_scale, prob_thd, bg_idx, labels, conf);
 }
 
 // The tiles of N images (sg_stitch_multi's descriptors); labels / conf of image n at out_offset[n] pixels of the flat outputs.
@@ -652,20 +559,11 @@ __global__ __launch_bounds__(256) void label_head_multi_kernel(const float* __re
                                                                int N, int64_t out_pixels, const int32_t* __restrict__ query_idx, int K,
                                                                float logit_scale, float prob_thd, int bg_idx, int64_t* __restrict__ labels,
                                                                float* __restrict__ conf) {
-  __shared__ int s_list[ST_MAXC];
-  __shared__ int s_count;
-  const int n = image_of_block(block_prefix, N, blockIdx.x);
-  const int H = image_hw[2 * n], W = image_hw[2 * n + 1];
-  const int t_first = image_tiles[2 * n], n_tiles = image_tiles[2 * n + 1];
-  const int64_t off = out_offset[n];
-  // a descriptor that would read or write outside the buffers: the whole block leaves (block-uniform, before any barrier)
-  if (H <= 0 || W <= 0 || t_first < 0 || n_tiles <= 0 || t_first + n_tiles > T || off < 0 || off + (int64_t)H * W > out_pixels) return;
-  const int64_t local = blockIdx.x - block_prefix[n];
-  const int bw = (W + 63) / 64;
-  if (local >= (int64_t)bw * ((H + 3) / 4)) return;
-  label_head_block(tile_logits + (int64_t)t_first * Q * gh * gw, windows + (int64_t)t_first * 4, tile_image + t_first, n, n_tiles, Q, gh, gw,
-                   up_h, up_w, pad_t, pad_l, H, W, (int)(local % bw) * 64, (int)(local / bw) * 4, query_idx, K, logit_scale, prob_thd,
-                   bg_idx, labels + off, conf ? conf + off : nullptr, s_list, &s_count);
+  ImageBlock ib;
+  if (!image_block(image_hw, image_tiles, out_offset, block_prefix, N, T, 1, out_pixels, ib)) return;
+  label_head_block(tile_logits + (int64_t)ib.t_first * Q * gh * gw, windows + (int64_t)ib.t_first * 4, tile_image + ib.t_first, ib.n,
+                   ib.n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, ib.H, ib.W, ib.bx0, ib.by0, query_idx, K, logit_scale, prob_thd, bg_idx,
+                   labels + ib.off, conf ? conf + ib.off : nullptr);
 }
 
 // ---- postprocess for any Q: several passes over the canvas, nothing held per query ------------------------------------------------

@@ -38,7 +38,7 @@ def scenes(kind, shapes=SHAPES, seed=0):
 
 
 # ---- 1. sg_stitch_multi == sg_stitch per image ------------------------------------------------------------------------------------
-@pytest.mark.parametrize("Q", [1, 16])
+@pytest.mark.parametrize("Q", [1, 11, 16])                 # 11: a ragged last chunk of queries
 @pytest.mark.parametrize("per_pixel", [False, True])
 def test_stitch_multi_equals_stitch_per_image(Q, per_pixel):
     shapes = [(100, 90), (36, 36), (77, 120), (50, 41), (36, 200)]
@@ -60,14 +60,47 @@ def test_stitch_multi_equals_stitch_per_image(Q, per_pixel):
         assert torch.equal(views[n], ref), f"image {n}"
 
 
+def test_multi_heads_equal_single_when_every_window_is_tested():
+    """Stride 2 under crop 32 puts more than 64 windows over one 64 x 4 block: the candidate list overflows and the per-pixel loop
+    tests every window of the image, the one path that reads tile_image per pixel.  Canvases, labels and conf against the per-image
+    entry points."""
+    shapes, P, crop, stride, Q = [(52, 56), (40, 70)], 8, (32, 32), (2, 2), 3
+    l, r, t, b = compute_padsize(32, 32, P)
+    up = (32 + t + b, 32 + l + r)
+    wins, tile_image, image_tiles = [], [], []
+    for n, (H, W) in enumerate(shapes):
+        w = tile_windows(H, W, stride, crop)
+        assert max(sum(y1 < by + 4 and y2 > by and x1 < bx + 64 and x2 > bx for (y1, y2, x1, x2) in w)
+                   for by in range(0, H, 4) for bx in range(0, W, 64)) > 64
+        image_tiles.append((len(wins), len(w)))
+        wins += w
+        tile_image += [n] * len(w)
+    tl = rand((len(wins), Q, up[0] // P, up[1] // P), 19).to(DEV)
+    qi, K = torch.tensor([0, 1, 1]), 2
+    _, views = ops.stitch_multi(tl, wins, tile_image, up, (t, l), shapes, image_tiles)
+    lab, _, conf = ops.label_head_multi(tl, wins, tile_image, up, (t, l), shapes, image_tiles, qi, K, 50.0, 0.3, 0, want_conf=True)
+    for n, (H, W) in enumerate(shapes):
+        a, c = image_tiles[n]
+        win = torch.tensor(wins[a:a + c], dtype=torch.int32)
+        assert torch.equal(views[n], ops.stitch(tl[a:a + c], win, up, (t, l), (H, W))), f"canvas of image {n}"
+        rl, rc = ops.label_head(tl[a:a + c], win, up, (t, l), (H, W), qi, K, 50.0, 0.3, 0, want_conf=True)
+        assert torch.equal(lab[n], rl), f"labels of image {n}"
+        assert torch.equal(conf[n], rc), f"conf of image {n}"
+
+
 # ---- 2. sg_postprocess_multi == sg_resize_bilinear + sg_postprocess per image --------------------------------------------------
-@pytest.mark.parametrize("qidx", [QIDX, [0, 1, 2, 3, 4]], ids=["synonyms", "one_per_class"])
+# Q = 17 and 40 run the kernels' 64-query instantiation (odd and even Q, one class per query and about Q / 2 classes)
+@pytest.mark.parametrize("qidx", [QIDX, [0, 1, 2, 3, 4], list(range(17)), [q // 2 for q in range(17)], list(range(40)),
+                                  [q // 2 for q in range(40)]],
+                         ids=["synonyms", "one_per_class", "q17_one_per_class", "q17_synonyms", "q40_one_per_class", "q40_synonyms"])
 @pytest.mark.parametrize("prob_thd", [0.0, 0.3])
 @pytest.mark.parametrize("want_probs", [True, False])
 def test_postprocess_multi_equals_resize_and_postprocess(qidx, prob_thd, want_probs):
     canvas_hw = [(60, 76), (36, 36), (50, 90), (30, 28), (80, 52)]
     out_hw = [(60, 76), (45, 31), (50, 90), (67, 70), (33, 52)]        # same size (no resize) for two, resized for three
     Q, K = len(qidx), max(qidx) + 1
+    if Q > 16:                                                          # small canvases: one image resized, one not
+        canvas_hw, out_hw = [(40, 50), (23, 31)], [(40, 50), (37, 29)]
     qi = torch.tensor(qidx)
     canv = [rand((Q, h, w), 50 + n, 0.05).to(DEV) for n, (h, w) in enumerate(canvas_hw)]
     flat = torch.cat([c.reshape(-1) for c in canv])
@@ -82,7 +115,7 @@ def test_postprocess_multi_equals_resize_and_postprocess(qidx, prob_thd, want_pr
         else:
             assert prb[n] is None
         n_bg += int((rl == (5 if K > 5 else 0)).sum())
-    assert n_bg > 0
+    assert 0 < n_bg < sum(h * w for h, w in out_hw)
 
 
 # ---- 3 / 4. the packed pipeline == forward_slide per image (f32) ----------------------------------------------------------------
