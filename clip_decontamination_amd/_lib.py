@@ -85,6 +85,8 @@ SIGNATURES = {
     "sg_postprocess_wide": (I, [P, P, I, I, I, I, F, F, I, P, P, P]),
     "sg_label_head": (I, [P, P, I, I, I, I, I, I, I, I, I, I, P, I, F, F, I, P, P, P]),
     "sg_label_head_multi": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, I, L, L, P, I, F, F, I, P, P, P]),
+    "sg_prob_head": (I, [P, P, I, I, I, I, I, I, I, I, I, I, P, I, F, F, I, P, P, P]),
+    "sg_prob_head_multi": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, I, L, L, P, I, F, F, I, P, P, P]),
     "sg_outlier_scratch_bytes": (Z, [I, I, I]),
     "sg_outlier_suppress": (I, [P, P, P, I, I, I, I, I, F, P, P, P]),
     "sg_cross_tile_scratch_bytes": (Z, [I, I, I, I, I]),

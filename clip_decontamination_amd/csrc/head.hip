@@ -240,10 +240,12 @@ constexpr int ST_QC = 8, ST_MAXC = 64;
 // tile (tile_image == nullptr: every tile is this image's).  A thread whose row y lies in the image hands each finished chunk to
 // sink(x, y, q0, acc, cnt): acc[k] = the sum over the cnt tiles that cover (x, y) for query q0 + k (k < ST_QC, q0 + k < Q), not yet
 // divided; x may lie beyond W (cnt = 0 then).
-template <class Sink>
-__device__ __forceinline__ void stitch_block(const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
-                                             const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw, int up_h,
-                                             int up_w, int pad_t, int pad_l, int H, int W, int bx0, int by0, Sink&& sink) {
+// The gather is in two steps so that a kernel can run the second one several times over one candidate list (the three passes of the
+// probability head beyond PP_MAX_Q queries); stitch_block is the two in a row.
+struct StitchList { const int* list; int n_cand; };      // more than ST_MAXC candidates: the list is not used, every window is tested
+// Step 1, all 256 threads (one barrier): the candidate tiles of the block.
+__device__ __forceinline__ StitchList stitch_candidates(const int32_t* __restrict__ win, const int32_t* __restrict__ tile_image, int img,
+                                                        int n_tiles, int bx0, int by0) {
   __shared__ int s_list[ST_MAXC];
   __shared__ int s_count;
   // candidate tiles of this block, compacted IN RASTER ORDER by wave 0 (ballot + prefix popcount): the per-pixel loop then visits the
@@ -266,14 +268,30 @@ __device__ __forceinline__ void stitch_block(const float* __restrict__ tile_logi
     if (lane == 0) s_count = base;
   }
   __syncthreads();
-  const int n_cand = s_count;
+  return {s_list, s_count};
+}
+
+// Step 2: the stitched sums of this thread's pixel, chunk by chunk, handed to the sink.  NCHUNK = 0 walks the chunks of the Q queries in
+// a run-time loop (every stitch and label-head kernel: their machine code is what it was before the split); NCHUNK > 0 unrolls NCHUNK
+// chunks (Q <= NCHUNK * ST_QC) so that q0 is a constant in every call of the sink and a caller can file the values in statically
+// indexed registers.
+template <int NCHUNK = 0, class Sink>
+__device__ __forceinline__ void stitch_gather(const StitchList& sl, const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
+                                              const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw, int up_h,
+                                              int up_w, int pad_t, int pad_l, int H, int W, int bx0, int by0, Sink&& sink) {
+  const int* s_list = sl.list;
+  const int n_cand = sl.n_cand;
   const bool use_list = n_cand <= ST_MAXC;                         // pathological overlap (stride << crop): test every window
   const int n_iter = use_list ? n_cand : n_tiles;
+  const int lane = threadIdx.x & 63;
   const int x = bx0 + lane;
   const int y = __builtin_amdgcn_readfirstlane(by0 + (threadIdx.x >> 6));
   if (y >= H) return;
   const int64_t tile_sz = (int64_t)gh * gw;
-  for (int q0 = 0; q0 < Q; q0 += ST_QC) {
+  constexpr int UNROLL = NCHUNK > 0 ? NCHUNK : 1;                  // 1 = the run-time loop as it always was
+#pragma unroll UNROLL
+  for (int q0 = 0; NCHUNK > 0 ? q0 < NCHUNK * ST_QC : q0 < Q; q0 += ST_QC) {
+    if (NCHUNK > 0 && q0 >= Q) break;
     float acc[ST_QC];
 #pragma unroll
     for (int k = 0; k < ST_QC; ++k) acc[k] = 0.f;
@@ -302,6 +320,14 @@ __device__ __forceinline__ void stitch_block(const float* __restrict__ tile_logi
     }
     sink(x, y, q0, acc, cnt);
   }
+}
+
+template <class Sink>
+__device__ __forceinline__ void stitch_block(const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
+                                             const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw, int up_h,
+                                             int up_w, int pad_t, int pad_l, int H, int W, int bx0, int by0, Sink&& sink) {
+  const StitchList sl = stitch_candidates(win, tile_image, img, n_tiles, bx0, by0);
+  stitch_gather(sl, tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, bx0, by0, sink);
 }
 
 // The block's stitched values, count-normalised, into the image's canvas [Q,H,W].
@@ -597,6 +623,120 @@ __global__ __launch_bounds__(256) void postprocess_wide_kernel(const float* __re
   }
   if (best < prob_thd) arg = bg_idx;
   labels[i] = arg;
+}
+
+// ---- fused probability head: stitch -> class probabilities + labels, no canvas, any Q -------------------------------------------------
+// One 64 x 4 pixel block of one image, shared by the single-image and the multi-image kernel.  stitch_gather supplies the stitched
+// values (sg_stitch's by construction) and the tail is the canvas route's own, so probs and labels carry the bytes of sg_stitch +
+// sg_postprocess (QMAX = 16 / PP_MAX_Q, the instantiations sg_postprocess dispatches on) or + sg_postprocess_wide (QMAX = 0, Q > PP_MAX_Q).
+// The image's labels [H,W] start at pixel ooff of the flat outputs and its probs [K,H,W] at K * ooff.
+//   QMAX > 0: one gather.  The chunk loop is unrolled, so the Q stitched values of the pixel sit in statically indexed registers, and
+//   class_tail<QMAX> runs on them with load(q) = the register (made opaque like a loaded value, as in postprocess_multi_kernel).
+//   QMAX = 0: postprocess_wide_kernel's three passes with logits[q * HW + i] replaced by the stitched value, i.e. three gathers over
+//   one candidate list and nothing held per query.  The tile logits are L2 / MALL resident at these sizes; the gathers are the cost
+//   (label_head_block's comment), and this form pays them three times to keep that kernel's summation order: the byte identity.
+// No atomics, no buffer proportional to Q * H * W, no LDS beyond the candidate list; every output element is written by its pixel's
+// own thread in an order fixed by (pixel, query index), so repeats are byte-identical.
+template <int QMAX>
+__device__ __forceinline__ void prob_head_block(const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
+                                                const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw,
+                                                int up_h, int up_w, int pad_t, int pad_l, int H, int W, int bx0, int by0,
+                                                const int32_t* __restrict__ query_idx, int K, float logit_scale, float prob_thd,
+                                                int bg_idx, float* probs, int64_t* __restrict__ labels, int64_t ooff) {
+  const StitchList sl = stitch_candidates(win, tile_image, img, n_tiles, bx0, by0);
+  const int x = bx0 + (threadIdx.x & 63);
+  const int y = __builtin_amdgcn_readfirstlane(by0 + (threadIdx.x >> 6));
+  const bool live = y < H && x < W;
+  const int64_t HW = (int64_t)H * W, i = (int64_t)y * W + x;
+  if constexpr (QMAX > 0) {
+    float v[QMAX];
+#pragma unroll
+    for (int q = 0; q < QMAX; ++q) v[q] = 0.f;
+    stitch_gather<QMAX / ST_QC>(sl, tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, bx0, by0,
+                                [&](int, int, int q0, const float (&acc)[ST_QC], float cnt) __attribute__((always_inline)) {
+#pragma unroll
+                                  for (int k = 0; k < ST_QC; ++k)
+                                    if (q0 + k < Q) v[q0 + k] = cnt > 0.f ? acc[k] / cnt : 0.f;      // q0 is a constant here
+                                });
+    if (!live) return;
+    class_tail<QMAX>([&](int q) { float l = v[q]; asm volatile("" : "+v"(l)); return l; }, query_idx, Q, K, logit_scale, prob_thd, bg_idx,
+                     probs, labels, ooff, HW, i);
+  } else {
+    const bool ident = K == Q;                                            // postprocess_wide_kernel: class(q) = q, query_idx is not read
+    bool all_same = true;
+    const int c0 = ident ? 0 : query_idx[0];
+    for (int q = 1; q < Q; ++q) all_same = all_same && (ident ? q : query_idx[q]) == c0;
+    float mx = -INFINITY;
+    stitch_gather(sl, tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, bx0, by0,
+                  [&](int, int, int q0, const float (&acc)[ST_QC], float cnt) {
+#pragma clang fp contract(off)        // the scaled logit is rounded before the subtraction, as postprocess_wide_kernel has it
+#pragma unroll
+                    for (int k = 0; k < ST_QC; ++k)
+                      if (q0 + k < Q) mx = fmaxf(mx, (cnt > 0.f ? acc[k] / cnt : 0.f) * logit_scale);
+                  });
+    float sum = 0.f;
+    stitch_gather(sl, tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, bx0, by0,
+                  [&](int, int, int q0, const float (&acc)[ST_QC], float cnt) {
+#pragma clang fp contract(off)
+#pragma unroll
+                    for (int k = 0; k < ST_QC; ++k)                       // q ascending
+                      if (q0 + k < Q) sum += expf((cnt > 0.f ? acc[k] / cnt : 0.f) * logit_scale - mx);
+                  });
+    float* pr = probs + K * ooff;
+    if (live)
+      for (int c = 0; c < K; ++c) pr[c * HW + i] = (all_same && c == c0) ? -INFINITY : 0.f;
+    float best = -INFINITY; int arg = 0;
+    stitch_gather(sl, tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, bx0, by0,
+                  [&](int, int, int q0, const float (&acc)[ST_QC], float cnt) {
+#pragma clang fp contract(off)
+                    if (!live) return;
+#pragma unroll
+                    for (int k = 0; k < ST_QC; ++k) {
+                      if (q0 + k >= Q) continue;
+                      const int c = ident ? q0 + k : query_idx[q0 + k];
+                      if (c < 0 || c >= K) continue;
+                      const float p = expf((cnt > 0.f ? acc[k] / cnt : 0.f) * logit_scale - mx) / sum;
+                      float* d = pr + c * HW + i;
+                      *d = fmaxf(*d, p);
+                      if (p > best || (p == best && c < arg)) { best = p; arg = c; }   // the first maximum over classes wins (torch argmax)
+                    }
+                  });
+    if (!live) return;
+    if (best < prob_thd) arg = bg_idx;
+    labels[ooff + i] = arg;
+  }
+}
+
+// QMAX = PP_MAX_Q is held to at least four waves per SIMD (128 registers): the gathers want waves to hide behind.  With the output
+// offset a literal 0 the single-image kernel folded it into the pointers and took 191 registers (class_tail's comment: the same effect),
+// and spilled under the bound; with the offset opaque both kernels take 93 and no scratch.
+template <int QMAX>
+__global__ __launch_bounds__(256, QMAX > 16 ? 4 : 1) void prob_head_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows, int T,
+                                                        int Q, int gh, int gw, int up_h, int up_w, int pad_t, int pad_l, int H, int W,
+                                                        const int32_t* __restrict__ query_idx, int K, float logit_scale, float prob_thd,
+                                                        int bg_idx, float* probs, int64_t* __restrict__ labels) {
+  int64_t ooff = 0;
+  asm volatile("" : "+s"(ooff));      // not a constant to the compiler: it then addresses the outputs as the multi-image kernel does
+  prob_head_block<QMAX>(tile_logits, windows, nullptr, 0, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, blockIdx.x * 64, blockIdx.y * 4,
+                        query_idx, K, logit_scale, prob_thd, bg_idx, probs, labels, ooff);
+}
+
+// The tiles of N images (sg_stitch_multi's descriptors); labels of image n at out_offset[n] pixels of the flat outputs, its probs at
+// K * out_offset[n] (sg_postprocess_multi's layout).
+template <int QMAX>
+__global__ __launch_bounds__(256, QMAX > 16 ? 4 : 1) void prob_head_multi_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows,
+                                                              const int32_t* __restrict__ tile_image, int T, int Q, int gh, int gw,
+                                                              int up_h, int up_w, int pad_t, int pad_l,
+                                                              const int32_t* __restrict__ image_hw, const int32_t* __restrict__ image_tiles,
+                                                              const int64_t* __restrict__ out_offset, const int64_t* __restrict__ block_prefix,
+                                                              int N, int64_t out_pixels, const int32_t* __restrict__ query_idx, int K,
+                                                              float logit_scale, float prob_thd, int bg_idx, float* probs,
+                                                              int64_t* __restrict__ labels) {
+  ImageBlock ib;
+  if (!image_block(image_hw, image_tiles, out_offset, block_prefix, N, T, 1, out_pixels, ib)) return;   // K * (off + H * W) <= K * out_pixels
+  prob_head_block<QMAX>(tile_logits + (int64_t)ib.t_first * Q * gh * gw, windows + (int64_t)ib.t_first * 4, tile_image + ib.t_first, ib.n,
+                        ib.n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, ib.H, ib.W, ib.bx0, ib.by0, query_idx, K, logit_scale, prob_thd,
+                        bg_idx, probs, labels, ib.off);
 }
 
 // ---- label / confidence images (segmentor.py:501-531, 580-608) ---------------------------------------------------------
@@ -915,6 +1055,46 @@ extern "C" int sg_label_head_multi(const float* tile_logits, const int32_t* wind
   hipLaunchKernelGGL(label_head_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q,
                      gh, gw, up_h, up_w, pad_t, pad_l, image_hw, image_tiles, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale,
                      prob_thd, bg_idx, labels, conf);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+// QMAX of the probability head: sg_postprocess's two instantiations up to PP_MAX_Q, the three-pass form (0) beyond.
+#define SG_PROB_HEAD_DISPATCH(kernel, Q) ((Q) <= 16 ? kernel<16> : ((Q) <= PP_MAX_Q ? kernel<PP_MAX_Q> : kernel<0>))
+
+extern "C" int sg_prob_head(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t,
+                            int pad_l, int H, int W, const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx,
+                            float* probs, int64_t* labels, sg_stream s) {
+  SG_REQUIRE(tile_logits && windows && query_idx && labels, "sg_prob_head: null pointer");
+  SG_REQUIRE(probs, "sg_prob_head: probs is NULL (labels alone: sg_label_head)");
+  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && H > 0 && W > 0,
+             "sg_prob_head: bad shape T=%d Q=%d gh=%d gw=%d up=%dx%d H=%d W=%d", T, Q, gh, gw, up_h, up_w, H, W);
+  SG_REQUIRE(K > 0 && K <= Q, "sg_prob_head: K=%d must lie in [1, Q=%d]", K, Q);
+  SG_REQUIRE(cdiv(H, 4) < 65536, "sg_prob_head: canvas too tall for one launch");
+  auto kern = SG_PROB_HEAD_DISPATCH(prob_head_kernel, Q);
+  hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(W, 64), (unsigned)cdiv(H, 4)), dim3(256), 0, as_stream(s), tile_logits, windows, T, Q, gh, gw,
+                     up_h, up_w, pad_t, pad_l, H, W, query_idx, K, logit_scale, prob_thd, bg_idx, probs, labels);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_prob_head_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh, int gw,
+                                  int up_h, int up_w, int pad_t, int pad_l, const int32_t* image_hw, const int32_t* image_tiles,
+                                  const int64_t* out_offset, const int64_t* block_prefix, int N, int64_t total_blocks, int64_t out_pixels,
+                                  const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx, float* probs,
+                                  int64_t* labels, sg_stream s) {
+  SG_REQUIRE(tile_logits && windows && tile_image && image_hw && image_tiles && out_offset && block_prefix && query_idx && labels,
+             "sg_prob_head_multi: null pointer");
+  SG_REQUIRE(probs, "sg_prob_head_multi: probs is NULL (labels alone: sg_label_head_multi)");
+  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && N > 0 && N <= T,
+             "sg_prob_head_multi: bad shape T=%d Q=%d gh=%d gw=%d N=%d", T, Q, gh, gw, N);
+  SG_REQUIRE(K > 0 && K <= Q, "sg_prob_head_multi: K=%d must lie in [1, Q=%d]", K, Q);
+  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "sg_prob_head_multi: total_blocks=%lld outside (0, 2^31)", (long long)total_blocks);
+  SG_REQUIRE(out_pixels > 0, "sg_prob_head_multi: out_pixels=%lld holds no image", (long long)out_pixels);
+  auto kern = SG_PROB_HEAD_DISPATCH(prob_head_multi_kernel, Q);
+  hipLaunchKernelGGL(kern, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q, gh, gw, up_h, up_w,
+                     pad_t, pad_l, image_hw, image_tiles, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale, prob_thd, bg_idx,
+                     probs, labels);
   SG_LAUNCH_CHECK();
   return SG_OK;
 }

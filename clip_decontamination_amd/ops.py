@@ -403,6 +403,61 @@ def label_head_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, 
 
 
 @on_tensor_device
+def prob_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, query_idx, num_classes: int, logit_scale: float, prob_thd: float, bg_idx: int):
+    """sg_prob_head: ``stitch`` + ``postprocess`` without the canvas, for any Q.  Arguments as ``label_head``
+    -> (probs f32 [K,H,W], labels int64 [1,H,W]), byte for byte what ``postprocess(stitch(...))`` returns."""
+    lib = _lib.load()
+    tile_logits = _f32(tile_logits)
+    windows = windows.to(device=tile_logits.device, dtype=torch.int32).contiguous()
+    _require_gpu(tile_logits)
+    T, Q, gh, gw = tile_logits.shape
+    H, W = canvas_hw
+    qi = query_idx.to(device=tile_logits.device, dtype=torch.int32).contiguous()
+    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T:
+        raise ValueError(f"prob_head: {T} tiles of {Q} queries, but {windows.numel() // 4} windows and {qi.numel()} query indices")
+    probs = torch.empty(int(num_classes), H, W, dtype=torch.float32, device=tile_logits.device)
+    labels = torch.empty(1, H, W, dtype=torch.int64, device=tile_logits.device)
+    check(lib.sg_prob_head(ptr(tile_logits), ptr(windows), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1], H, W, ptr(qi),
+                           int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx), ptr(probs), ptr(labels), stream_ptr()),
+          "sg_prob_head")
+    return probs, labels
+
+
+@on_tensor_device
+def prob_head_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, query_idx, num_classes: int,
+                    logit_scale: float, prob_thd: float, bg_idx: int):
+    """sg_prob_head_multi: the class probabilities and labels of N images in one launch, from their tile logits (arguments as
+    ``label_head_multi``).  -> (list of probs f32 [K,H,W], list of labels int64 [1,H,W], the flat int64 buffer the label maps are views
+    of, images back to back): what ``postprocess_multi(..., want_probs=True, flat_labels=True)`` returns, and ``prob_head`` per image
+    byte for byte.  The probs of image n are a view at K * (its first pixel) of one flat f32 buffer."""
+    lib = _lib.load()
+    tile_logits = _f32(tile_logits)
+    _require_gpu(tile_logits)
+    dev = tile_logits.device
+    T, Q, gh, gw = tile_logits.shape
+    N, K = len(image_hw), int(num_classes)
+    qi = query_idx.to(device=dev, dtype=torch.int32).contiguous()
+    windows = torch.as_tensor(windows, dtype=torch.int32).to(dev).contiguous()
+    tile_image = torch.as_tensor(tile_image, dtype=torch.int32).to(dev).contiguous()
+    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T or int(tile_image.numel()) != T or len(image_tiles) != N:
+        raise ValueError("prob_head_multi: tile logits, windows, tile_image, image descriptors and query indices disagree in size")
+    if any(f < 0 or c <= 0 or f + c > T for f, c in image_tiles):
+        raise ValueError(f"prob_head_multi: image_tiles {list(image_tiles)} leave the {T} tiles")
+    pix = _prefix(h * w for h, w in image_hw)
+    blocks = _prefix(-(-w // 64) * -(-h // 4) for h, w in image_hw)
+    i32 = torch.tensor([list(hw) for hw in image_hw] + [list(ft) for ft in image_tiles], dtype=torch.int32).to(dev)
+    i64 = torch.tensor(pix[:-1] + blocks, dtype=torch.int64).to(dev)
+    labels = torch.empty(pix[-1], dtype=torch.int64, device=dev)
+    probs = torch.empty(max(K, 0) * pix[-1], dtype=torch.float32, device=dev)
+    check(lib.sg_prob_head_multi(ptr(tile_logits), ptr(windows), ptr(tile_image), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1],
+                                 ptr(i32), ptr(i32[N:]), ptr(i64), ptr(i64[N:]), N, blocks[-1], pix[-1], ptr(qi), K, float(logit_scale),
+                                 float(prob_thd), int(bg_idx), ptr(probs), ptr(labels), stream_ptr()), "sg_prob_head_multi")
+    lab = [labels[pix[n]:pix[n + 1]].view(1, h, w) for n, (h, w) in enumerate(image_hw)]
+    prb = [probs[K * pix[n]:K * pix[n + 1]].view(K, h, w) for n, (h, w) in enumerate(image_hw)]
+    return prb, lab, labels
+
+
+@on_tensor_device
 def postprocess_multi(canvases, canvas_hw, query_idx, num_classes: int, logit_scale: float, prob_thd: float, bg_idx: int,
                       out_hw=None, want_probs: bool = True, canvas_offsets=None, flat_labels: bool = False):
     """sg_postprocess_multi: N canvases [Q,h,w] in one flat buffer (packed back to back, or at ``canvas_offsets`` elements) ->

@@ -307,7 +307,17 @@ def pack_scenes(scenes, device, fill=None) -> Tuple[torch.Tensor, List[Tuple[int
     return buf, shapes
 
 
+def _scene_hw(s: torch.Tensor) -> Tuple[int, int]:
+    """(H, W) of one packed image: u8 [H,W,3] or f32 [3,H,W] (``pack_scenes``)."""
+    return (int(s.shape[0]), int(s.shape[1])) if s.dtype == torch.uint8 else (int(s.shape[-2]), int(s.shape[-1]))
+
+
 LABEL_HEADS = ("auto", "fused", "canvas")
+PROB_HEADS = LABEL_HEADS
+# What prob_head="auto" does beyond ops.POSTPROCESS_MAX_Q queries (up to there it is the canvas route): the fused head only where it was
+# measured no slower than the canvas route at both Q = 130 and Q = 256.  It was slower at both (13.9 against 10.5 ms and 28.8 against
+# 20.3 ms, profiles/r08_bench_prob_head.jsonl, DESIGN.md section 5 'Probability head'), so "auto" is the canvas route everywhere.
+PROB_HEAD_AUTO_FUSED_BEYOND_MAX_Q = False
 
 
 class SegPipeline:
@@ -315,9 +325,15 @@ class SegPipeline:
                  ignore_residual: bool = True, cls_token_lambda: float = 0.0, global_debias_factor: float = 0.0,
                  logit_scale: float = 50.0, prob_thd: float = 0.0, bg_idx: int = 0, apply_similarity_enhancement: bool = False,
                  upsampler=None, tiles_per_launch: int = 32, cross_tile_fusion: Optional[dict] = None, apply_ctd: bool = False,
-                 tile_group=None, apply_layer_fusion: bool = False, layer_fusion_lambda: float = 0.5, label_head: str = "auto"):
+                 tile_group=None, apply_layer_fusion: bool = False, layer_fusion_lambda: float = 0.5, label_head: str = "auto",
+                 prob_head: str = "auto"):
         if label_head not in LABEL_HEADS:
             raise ValueError(f"label_head must be one of {LABEL_HEADS}, got {label_head!r}")
+        if prob_head not in PROB_HEADS:
+            raise ValueError(f"prob_head must be one of {PROB_HEADS}, got {prob_head!r}")
+        # the tail that returns class probabilities too (``probs_from_tiles``): "canvas" = stitch + postprocess, "fused" = sg_prob_head
+        # (no canvas, any Q, the same bytes), "auto" = see ``fused_prob_head``
+        self.prob_head = prob_head
         # the labels-only tail (``labels_from_tiles``): "canvas" = stitch + postprocess through the [Q,H,W] canvas, "fused" = sg_label_head
         # (no canvas, any Q), "auto" = the canvas wherever it works (Q <= 64) and the fused head beyond
         self.label_head = label_head
@@ -360,6 +376,20 @@ class SegPipeline:
             return ops.label_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, self.query_idx, self.num_classes, self.logit_scale,
                                   self.prob_thd, self.bg_idx)
         return self.postprocess(self._stitch(tile_logits, windows, up_hw, pad_tl, canvas_hw), want_probs=False)[1]
+
+    def fused_prob_head(self) -> bool:
+        """Whether the tail that returns probabilities and labels runs the fused head (sg_prob_head) instead of the canvas path.  "auto"
+        is the canvas up to 64 queries and follows the measurement beyond (PROB_HEAD_AUTO_FUSED_BEYOND_MAX_Q)."""
+        mode = getattr(self, "prob_head", "auto")
+        return mode == "fused" or (mode == "auto" and PROB_HEAD_AUTO_FUSED_BEYOND_MAX_Q and self.num_queries > ops.POSTPROCESS_MAX_Q)
+
+    def probs_from_tiles(self, tile_logits, windows, up_hw, pad_tl, canvas_hw):
+        """Tile logits [T,Q,gh,gw] + windows [T,4] -> (probs f32 [K,H,W], labels int64 [1,H,W]): the tail of every path that returns
+        class probabilities at the scene's own size.  Both routes return the same bytes."""
+        if self.fused_prob_head():
+            return ops.prob_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, self.query_idx, self.num_classes, self.logit_scale,
+                                 self.prob_thd, self.bg_idx)
+        return self.postprocess(self._stitch(tile_logits, windows, up_hw, pad_tl, canvas_hw), want_probs=True)
 
     def _pre_head(self, tok, cls):
         """Global debias (+ CTD) when they cannot stay fused in the logits kernel: returns (tokens, remaining debias factor)."""
@@ -507,15 +537,20 @@ class SegPipeline:
             return buf[0, :, :H]
         return torch.cat([buf[r, :, :yb[r + 1] - yb[r]] for r in range(world)], 1)
 
-    def segment_scene(self, scene: torch.Tensor, stride, crop, group=None, gather_labels: bool = True):
+    def segment_scene(self, scene: torch.Tensor, stride, crop, group=None, gather_labels: bool = True, want_probs: bool = False):
         """The whole path to labels for one scene.  Sharded: every rank computes its tiles, stitches + labels ITS band; only the
         int64 label band (8 B per pixel instead of 4Q) is gathered.  -> labels [1,H,W] (or (band labels, first row) when
-        ``gather_labels`` is False)."""
+        ``gather_labels`` is False).  ``want_probs``: (probs [K,H,W], labels [1,H,W]) through ``probs_from_tiles``; not with tile
+        sharding."""
         group = resolve_tile_group(group if group is not None else self.tile_group)
+        if want_probs and group is not None:
+            raise ValueError("segment_scene: class probabilities under tile_group sharding are not built; use forward_slide + postprocess")
         if group is None:
             H, W, stride, crop, wins, tile_hw, pad_tl, up_hw, grid = self._geometry(scene, stride, crop)
             tl = self.tile_logits(scene, wins, tile_hw, grid_of_tiles=grid)
             win_dev = torch.tensor(wins, dtype=torch.int32, device=self.device)
+            if want_probs:
+                return self.probs_from_tiles(tl, win_dev, up_hw, pad_tl, (H, W))
             return self.labels_from_tiles(tl, win_dev, up_hw, pad_tl, (H, W))
         tiles, w_band, up_hw, pad_tl, hw, y0, yb = self.sharded_band_tiles(scene, stride, crop, group)
         if hw[0] > 0:
@@ -669,9 +704,19 @@ class SegPipeline:
         (the resize to ``ori_shapes`` fused into the latter).  Yields (image indices, list of probs [K,H,W] or None, list of labels
         [1,H,W], the flat int64 buffer those label maps are views of, in that order of images).
         Labels alone at the images' own sizes with the fused head selected (``label_head``): one sg_label_head_multi launch per flush
-        group and no canvas.  Probabilities or a resize keep the canvas; beyond 64 queries they go image by image through
-        ``ops.postprocess`` (its wide form) on the group's canvases."""
+        group and no canvas.  Probabilities at the images' own sizes with the fused probability head selected (``prob_head``): one
+        sg_prob_head_multi launch per flush group, no canvas, any number of queries (the planner counts 4K + 8 bytes per pixel then).
+        Otherwise probabilities or a resize keep the canvas; beyond 64 queries they then go image by image through ``ops.postprocess``
+        (its wide form) on the group's canvases."""
         no_resize = ori_shapes is None or all(o is None for o in ori_shapes)
+        if want_probs and self.fused_prob_head() and (no_resize or all(
+                o is None or tuple(o) == _scene_hw(s)
+                for o, s in zip(ori_shapes, [scenes] if torch.is_tensor(scenes) and scenes.dim() == 3 else scenes))):
+            for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(scenes, stride, crop, 4 * self.num_classes + 8):
+                prb, lab, flat = ops.prob_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes,
+                                                     self.logit_scale, self.prob_thd, self.bg_idx)
+                yield idx, prb, lab, flat
+            return
         if not want_probs and no_resize and self.fused_label_head():
             for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(scenes, stride, crop, 8):
                 lab, flat = ops.label_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes,

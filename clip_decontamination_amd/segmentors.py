@@ -130,10 +130,15 @@ class _HipSegmentorBase(_Base):
                slide_crop, cls_token_lambda, bg_idx, apply_sim_feat_up, sim_feat_up_cfg, global_debias_factor=0.0,
                checkpoint=None, text_features=None, text_encoder: Optional[Callable] = None, precision="f16x2",
                synthetic_ok=False, tiles_per_launch=None, jbu_checkpoint_ok=True, tokenizer: Optional[Callable] = None, tile_group=None,
-               label_head="auto"):
-        from .pipeline import LABEL_HEADS
+               label_head="auto", prob_head="auto"):
+        from .pipeline import LABEL_HEADS, PROB_HEADS
         if label_head not in LABEL_HEADS:
             raise ValueError(f"label_head must be one of {LABEL_HEADS}, got {label_head!r}")
+        if prob_head not in PROB_HEADS:
+            raise ValueError(f"prob_head must be one of {PROB_HEADS}, got {prob_head!r}")
+        # the tail of ``predict`` / ``predict_many`` with data samples (class probabilities + labels): "canvas" = stitch + post-process,
+        # "fused" = sg_prob_head (no canvas, the same bytes), "auto" = SegPipeline.fused_prob_head
+        self.prob_head = prob_head
         # the labels-only tail: "canvas" = stitch + post-process through the [Q,H,W] canvas, "fused" = sg_label_head (no canvas, any
         # number of queries), "auto" = the canvas wherever it works (Q <= 64) and the fused head beyond
         self.label_head = label_head
@@ -239,7 +244,8 @@ class _HipSegmentorBase(_Base):
                            upsampler=self.upsampler, tiles_per_launch=self._tiles_per_launch,
                            cross_tile_fusion=getattr(self, "cross_tile_fusion_cfg", None), apply_ctd=getattr(self, "apply_ctd", False),
                            tile_group=getattr(self, "tile_group", None), apply_layer_fusion=getattr(self, "apply_layer_fusion", False),
-                           layer_fusion_lambda=getattr(self, "layer_fusion_lambda", 0.5), label_head=getattr(self, "label_head", "auto"))
+                           layer_fusion_lambda=getattr(self, "layer_fusion_lambda", 0.5), label_head=getattr(self, "label_head", "auto"),
+                           prob_head=getattr(self, "prob_head", "auto"))
 
     def forward_feature(self, img, logit_size=None, tile_h_idx=None, tile_w_idx=None):
         """Reference segmentor.py:286-392.  img [B,3,H,W] -> logits [B,Q,h,w]."""
@@ -274,6 +280,20 @@ class _HipSegmentorBase(_Base):
             # labels only, at the image's own size, of the first image (what postprocess_result returns without data samples): the
             # labels-only tail, which needs no canvas with the fused head (``label_head``)
             return self._pipeline().segment_scene(inputs[0], self.slide_stride, self.slide_crop)
+        if self.slide_crop > 0 and getattr(self, "tile_group", None) is None and \
+                all(tuple(m["ori_shape"][:2]) == tuple(inputs.shape[2:]) for m in batch_img_metas):
+            pipe = self._pipeline()
+            if pipe.fused_prob_head():
+                # tile logits -> probabilities + labels with no canvas (sg_prob_head): the bytes of the canvas route below.  A resize to
+                # another ori_shape, tile sharding and whole-image inference keep the canvas.
+                if getattr(self, "pack_images", False) and inputs.shape[0] > 1:
+                    probs, labels = pipe.segment_scenes(inputs, self.slide_stride, self.slide_crop, want_probs=True)
+                else:
+                    pl = [pipe.segment_scene(inputs[b], self.slide_stride, self.slide_crop, want_probs=True) for b in range(inputs.shape[0])]
+                    probs, labels = [p for p, _ in pl], [l for _, l in pl]
+                for i, ds in enumerate(data_samples):
+                    self._fill_sample(ds, probs[i], labels[i], i)
+                return data_samples
         if self.slide_crop > 0:
             seg_logits = self.forward_slide(inputs, batch_img_metas, self.slide_stride, self.slide_crop)
         else:
@@ -286,10 +306,12 @@ class _HipSegmentorBase(_Base):
         launch per flush group (SegPipeline.segment_scenes).  inputs: a list of [3,H,W] images of any sizes or a [B,3,H,W] batch.
         Fills each data sample exactly as ``predict`` does (seg_logits, pred_sem_seg, result_dir / heatmap_dir PNGs) and returns
         them; with ``data_samples=None`` returns one label map [1,H,W] per image.  In f32 the results equal ``predict`` per image bit
-        for bit; in the 2-byte modes a larger launch may take a different GEMM path and differ by 2-byte rounding.  With more than 64
-        queries the one-launch multi-canvas post-process does not apply: data samples are then filled image by image (the canvases still
-        come from the packed launches, the probabilities from sg_postprocess_wide per image); ``data_samples=None`` takes the fused
-        label head, one launch per flush group."""
+        for bit; in the 2-byte modes a larger launch may take a different GEMM path and differ by 2-byte rounding.  On the canvas route with
+        more than 64 queries the one-launch multi-canvas post-process does not apply: data samples are then filled image by image (the
+        canvases still come from the packed launches, the probabilities from sg_postprocess_wide per image); ``data_samples=None`` takes the fused
+        label head, one launch per flush group.  With the fused probability head selected (``prob_head``) and every ``ori_shape`` equal
+        to its image's size, data samples are filled from one sg_prob_head_multi launch per flush group for any number of queries: no
+        canvas, and nothing image by image."""
         batch = torch.is_tensor(inputs)
         imgs = inputs.float() if batch else [x[0].float() if x.dim() == 4 else x.float() for x in inputs]
         n = imgs.shape[0] if batch else len(imgs)
@@ -307,10 +329,14 @@ class _HipSegmentorBase(_Base):
         ori = [tuple(ds.metainfo["ori_shape"][:2]) for ds in data_samples]
         probs, labels = pipe.segment_scenes(imgs, self.slide_stride, self.slide_crop, want_probs=True, ori_shapes=ori)
         for i, ds in enumerate(data_samples):
-            ds.set_data({"seg_logits": PixelData(**{"data": probs[i]}), "pred_sem_seg": PixelData(**{"data": labels[i]})})
-            if getattr(self, "result_dir", None) or getattr(self, "heatmap_dir", None):
-                self._write_maps(probs[i], labels[i], ds, i)
+            self._fill_sample(ds, probs[i], labels[i], i)
         return data_samples
+
+    def _fill_sample(self, sample, probs, seg_pred, i):
+        """What postprocess_result leaves in a data sample: seg_logits, pred_sem_seg and the result_dir / heatmap_dir images."""
+        sample.set_data({"seg_logits": PixelData(**{"data": probs}), "pred_sem_seg": PixelData(**{"data": seg_pred})})
+        if getattr(self, "result_dir", None) or getattr(self, "heatmap_dir", None):        # segmentor.py:501-531
+            self._write_maps(probs, seg_pred, sample, i)
 
     @torch.no_grad()
     def evaluate(self, inputs, gt_maps, metric=None, reduce_zero_label=False, ignore_index=255, iou_metrics=("mIoU",)):
@@ -373,9 +399,7 @@ class _HipSegmentorBase(_Base):
             probs, seg_pred = pipe.postprocess(seg_logits[i].float())
             if data_samples is None:
                 return seg_pred
-            data_samples[i].set_data({"seg_logits": PixelData(**{"data": probs}), "pred_sem_seg": PixelData(**{"data": seg_pred})})
-            if getattr(self, "result_dir", None) or getattr(self, "heatmap_dir", None):        # segmentor.py:501-531
-                self._write_maps(probs, seg_pred, data_samples[i], i)
+            self._fill_sample(data_samples[i], probs, seg_pred, i)
         return data_samples
 
     def _generate_palette(self, n):
@@ -443,7 +467,7 @@ class SegmentorEx(_HipSegmentorBase):
                  similarity_enhancement_cfg=None, result_dir=None, heatmap_dir=None,
                  # -- drop-in extras (see module docstring) --
                  checkpoint=None, text_features=None, text_encoder=None, precision="f16x2", synthetic_ok=False, tiles_per_launch=None,
-                 tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, pack_images=False, label_head="auto"):
+                 tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, pack_images=False, label_head="auto", prob_head="auto"):
         data_preprocessor = SegDataPreProcessor(mean=list(Wt.PIXEL_MEAN), std=list(Wt.PIXEL_STD), bgr_to_rgb=True)
         super().__init__(data_preprocessor=data_preprocessor)
         if model_type == "GEM":
@@ -452,7 +476,7 @@ class SegmentorEx(_HipSegmentorBase):
         visual = self._setup(clip_type, vit_type, model_type, name_path, device, ignore_residual, prob_thd, logit_scale, slide_stride,
                              slide_crop, cls_token_lambda, bg_idx, _to_bool(apply_sim_feat_up), sim_feat_up_cfg, global_debias_factor,
                              checkpoint, text_features, text_encoder, precision, synthetic_ok, tiles_per_launch, tokenizer=tokenizer,
-                             tile_group=tile_group, label_head=label_head)
+                             tile_group=tile_group, label_head=label_head, prob_head=prob_head)
         # opt-in extra: kwargs of the reference's CrossTileFusion (cross_tile_fusion.py:24-60), which the reference never calls (R2)
         self.cross_tile_fusion_cfg = cross_tile_fusion_cfg
         self.apply_ctd = _to_bool(apply_ctd)                                # segmentor.py:184-194, 339-365: DBSCAN + cluster debias, on the device here
@@ -487,7 +511,7 @@ class Segmentor(_HipSegmentorBase):
                  sim_feat_up_cfg=dict(model_name="jbu_one", model_path="your/model/path"),
                  checkpoint=None, text_features=None, text_encoder=None, precision="f16x2", synthetic_ok=False, tiles_per_launch=None,
                  tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, apply_outlier_suppression=False, outlier_suppression_cfg=None,
-                 pack_images=False, label_head="auto"):
+                 pack_images=False, label_head="auto", prob_head="auto"):
         data_preprocessor = SegDataPreProcessor(mean=list(Wt.PIXEL_MEAN), std=list(Wt.PIXEL_STD), bgr_to_rgb=True)
         super().__init__(data_preprocessor=data_preprocessor)
         if model_type == "GEM" and cls_token_lambda != 0:
@@ -495,7 +519,7 @@ class Segmentor(_HipSegmentorBase):
         self._setup(clip_type, vit_type, model_type, name_path, device, ignore_residual, prob_thd, logit_scale, slide_stride,
                     slide_crop, cls_token_lambda, bg_idx, apply_sim_feat_up, sim_feat_up_cfg, 0.0,
                     checkpoint, text_features, text_encoder, precision, synthetic_ok, tiles_per_launch, tokenizer=tokenizer,
-                    tile_group=tile_group, label_head=label_head)
+                    tile_group=tile_group, label_head=label_head, prob_head=prob_head)
         # opt-in extra: kwargs of the reference's CrossTileFusion (cross_tile_fusion.py:24-60), which the reference never calls (R2)
         self.cross_tile_fusion_cfg = cross_tile_fusion_cfg
         self.output_cls_token = cls_token_lambda != 0

@@ -257,6 +257,25 @@ int sg_label_head_multi(const float* tile_logits, const int32_t* windows, const 
                         const int64_t* out_offset, const int64_t* block_prefix, int N, int64_t total_blocks, int64_t out_pixels,
                         const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx, int64_t* labels,
                         float* conf, sg_stream s);
+/* sg_prob_head: sg_stitch + sg_postprocess without the canvas, class probabilities AND labels, any Q >= 1 and 1 <= K <= Q.  Inputs as
+ * sg_label_head; probs f32 [K,H,W] must not be NULL (labels alone: sg_label_head), labels int64 [H,W].  Contract: probs and labels are
+ * byte-identical to sg_stitch followed by sg_postprocess for Q <= 64 and by sg_postprocess_wide beyond -- the stitched value of a
+ * (pixel, query) is sg_stitch's (same taps, covering tiles summed in raster order, divided by the count, 0 where no tile covers) and
+ * the tail is that entry's own code -- and repeats are byte-identical.  Q <= 64: one gather, the pixel's Q values stay in registers.
+ * Q > 64: three gathers (maximum, sum, per-class maximum), nothing held per query.  No buffer proportional to Q*H*W, no atomics. */
+int sg_prob_head(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t,
+                 int pad_l, int H, int W, const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx,
+                 float* probs, int64_t* labels, sg_stream s);
+/* sg_prob_head_multi: sg_prob_head for the tiles of N images in one launch, descriptors as sg_label_head_multi.  The labels of image n
+ * are written at out_offset[n] pixels of `labels` and its probs [K,H,W] at K * out_offset[n] elements of `probs` (sg_postprocess_multi's
+ * layout); out_pixels = the size of `labels`, `probs` holds K * out_pixels.  Contract: per image byte-identical to sg_prob_head on that
+ * image alone, hence to sg_stitch_multi + sg_postprocess_multi (Q <= 64) or + sg_postprocess_wide per image (beyond); repeats are
+ * byte-identical. */
+int sg_prob_head_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh, int gw,
+                       int up_h, int up_w, int pad_t, int pad_l, const int32_t* image_hw, const int32_t* image_tiles,
+                       const int64_t* out_offset, const int64_t* block_prefix, int N, int64_t total_blocks, int64_t out_pixels,
+                       const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx, float* probs,
+                       int64_t* labels, sg_stream s);
 /* Label / confidence images of postprocess_result (segmentor.py:501-531): mask_rgb [H,W,3] = palette[clip(label)] (_colorize_mask,
  * :580-590); heat_rgb [H,W,3] = (g, 0, 255-g) with g = uint8(clip(max_k probs, 0, 1) * 255) (_to_colormap without OpenCV, :604-608;
  * OpenCV's JET table is not reproduced).  Either output may be NULL. */
