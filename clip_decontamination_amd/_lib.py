@@ -107,6 +107,22 @@ SIGNATURES = {
     "sg_op_layernorm": (I, [P, P, P, P, I, I, F, P]),
     "sg_attention_raw": (I, [I, P, P, P, P, P, P, L, L, P, L, L, I, I, I, I, I, I, I, F, P, P, F, L, P, P, I, P, P, P, L, L, F, P]),
     "sg_attention_stats_raw": (I, [I, P, L, L, P, I, I, I, I, F, P, P, P]),
+    "sg_layernorm_raw": (I, [P, L, P, P, P, L, I, L, I, F, P]),
+    "sg_layernorm_fp8_raw": (I, [P, L, P, P, P, L, P, L, I, F, P]),
+    "sg_quantize_rows_raw": (I, [P, I, L, P, L, P, L, I, P]),
+    "sg_embed_assemble_raw": (I, [P, L, P, P, P, P, P, I, I, I, F, P]),
+    "sg_posembed_resize_raw": (I, [P, I, I, I, I, I, P, P]),
+    "sg_pack_rows_raw": (I, [P, L, I, L, P, I, I, P]),
+    "sg_transpose_pack_raw": (I, [P, I, I, P, I, P]),
+    "sg_ln_stats_finalize_raw": (I, [P, L, I, F, P, P]),
+    "sg_fold_ln_weight_raw": (I, [P, I, I, P, P, P, I, P, P, P, P]),
+    "sg_l2norm_rows_raw": (I, [P, I, L, L, I, P, I, L, L, L, I, F, P]),
+    "sg_softmax_rows_raw": (I, [P, L, L, I, I, P, F, P, F, L, P, P, I, I, I, P, P, P]),
+    "sg_gaussian_bias_raw": (I, [I, I, F, P, P]),
+    "sg_head_norms_raw": (I, [P, I, L, L, I, I, I, I, P, P]),
+    "sg_axpby_raw": (I, [P, P, F, F, L, P]),
+    "sg_gem_inv_temp_raw": (I, [P, I, I, I, F, P, P]),
+    "sg_patchify_raw": (I, [C.POINTER(TileBatch), I, I, P, I, P]),
     "sg_op_attention_scratch_bytes": (Z, [I, I, I, I, I]),
     "sg_op_attention": (I, [P, I, I, I, I, I, P, F, P, P, P, I, P, Z, P]),
     "sg_adaptive_conv": (I, [P, P, I, I, I, I, I, P, P]),

@@ -564,6 +564,100 @@ extern "C" int sg_attention_stats_raw(int precision, const void* qk, int64_t sb,
   SG_REQUIRE(B > 0 && B < 65536 && N > 0 && H > 0 && dh > 0, "sg_attention_stats_raw: bad shape");
   return attention_stats(qk, hk_of_precision(precision), sb, st, lse, B, N, H, dh, scale, attn_cls, attn_diag, as_stream(st_));
 }
+// ---- raw test entries of the row kernels (rowops.hip) and patchify: one host function each, arguments passed one to one ---------------
+// `kind` arguments are sg_precision values naming a storage: SG_PREC_F32, SG_PREC_BF16, SG_PREC_F16, SG_PREC_F16X2 (two-plane groups).
+static int raw_kind(const char* api, int p, int* hk) {
+  SG_REQUIRE(p == SG_PREC_F32 || p == SG_PREC_BF16 || p == SG_PREC_F16 || p == SG_PREC_F16X2, "%s: bad kind %d", api, p);
+  *hk = hk_of_precision(p);
+  return SG_OK;
+}
+extern "C" int sg_layernorm_raw(const float* x, int64_t ldx, const float* gamma, const float* beta, void* y, int64_t ldy, int out_kind,
+                                int64_t rows, int D, float eps, sg_stream st) {
+  SG_REQUIRE(x && gamma && beta && y, "sg_layernorm_raw: null pointer");
+  int hk; SG_TRY(raw_kind("sg_layernorm_raw", out_kind, &hk));
+  return layernorm(x, ldx, gamma, beta, y, ldy, hk, rows, D, eps, as_stream(st));
+}
+extern "C" int sg_layernorm_fp8_raw(const float* x, int64_t ldx, const float* gamma, const float* beta, void* y, int64_t ldy, float* scale,
+                                    int64_t rows, int D, float eps, sg_stream st) {
+  SG_REQUIRE(x && gamma && beta && y && scale, "sg_layernorm_fp8_raw: null pointer");
+  return layernorm_fp8(x, ldx, gamma, beta, (uint8_t*)y, ldy, scale, rows, D, eps, as_stream(st));
+}
+extern "C" int sg_quantize_rows_raw(const void* x, int in_kind, int64_t ldx, void* y, int64_t ldy, float* scale, int64_t rows, int D,
+                                    sg_stream st) {
+  SG_REQUIRE(x && y && scale, "sg_quantize_rows_raw: null pointer");
+  SG_REQUIRE(in_kind == SG_PREC_F32 || in_kind == SG_PREC_BF16 || in_kind == SG_PREC_F16, "sg_quantize_rows_raw: bad kind %d", in_kind);
+  return quantize_rows_fp8(x, hk_of_precision(in_kind), ldx, (uint8_t*)y, ldy, scale, rows, D, as_stream(st));
+}
+extern "C" int sg_embed_assemble_raw(const float* patches, int64_t ldp, const float* cls_emb, const float* pos, const float* gamma,
+                                     const float* beta, float* x, int B, int N, int D, float eps, sg_stream st) {
+  SG_REQUIRE(patches && cls_emb && pos && gamma && beta && x, "sg_embed_assemble_raw: null pointer");
+  return embed_assemble(patches, ldp, cls_emb, pos, gamma, beta, x, B, N, D, eps, as_stream(st));
+}
+extern "C" int sg_posembed_resize_raw(const float* pos, int g0, int D, int gh, int gw, int antialias, float* out, sg_stream st) {
+  SG_REQUIRE(pos && out, "sg_posembed_resize_raw: null pointer");
+  return posembed_resize(pos, g0, D, gh, gw, antialias, out, as_stream(st));
+}
+extern "C" int sg_pack_rows_raw(const float* src, int64_t rows, int cols, int64_t ld_src, void* dst, int cols_pad, int kind, sg_stream st) {
+  SG_REQUIRE(src && dst, "sg_pack_rows_raw: null pointer");
+  int hk; SG_TRY(raw_kind("sg_pack_rows_raw", kind, &hk));
+  return pack_rows(src, rows, cols, ld_src, dst, cols_pad, hk, as_stream(st));
+}
+extern "C" int sg_transpose_pack_raw(const float* src, int rows, int cols, void* dst, int kind, sg_stream st) {
+  SG_REQUIRE(src && dst, "sg_transpose_pack_raw: null pointer");
+  int hk; SG_TRY(raw_kind("sg_transpose_pack_raw", kind, &hk));
+  return transpose_pack(src, rows, cols, dst, hk, as_stream(st));
+}
+extern "C" int sg_ln_stats_finalize_raw(const float* slice_stats, int64_t rows, int D, float eps, float* mean_rstd, sg_stream st) {
+  SG_REQUIRE(slice_stats && mean_rstd, "sg_ln_stats_finalize_raw: null pointer");
+  return ln_stats_finalize(slice_stats, rows, D, eps, mean_rstd, as_stream(st));
+}
+extern "C" int sg_fold_ln_weight_raw(const float* W, int N, int K, const float* gamma, const float* beta, const float* bias, int precision,
+                                     void* Wp, float* c, float* bias_f, sg_stream st) {
+  SG_REQUIRE(W && gamma && beta && Wp && c && bias_f, "sg_fold_ln_weight_raw: null pointer");
+  int hk; SG_TRY(raw_kind("sg_fold_ln_weight_raw", precision, &hk));
+  return fold_ln_weight(W, N, K, gamma, beta, bias, hk, Wp, c, bias_f, as_stream(st));
+}
+extern "C" int sg_l2norm_rows_raw(const void* x, int in_kind, int64_t so, int64_t si, int inner, void* y, int out_kind, int64_t yo, int64_t yi,
+                                  int64_t rows, int D, float eps, sg_stream st) {
+  SG_REQUIRE(x && y, "sg_l2norm_rows_raw: null pointer");
+  SG_REQUIRE(inner >= 1, "sg_l2norm_rows_raw: inner=%d", inner);
+  int hx, hy; SG_TRY(raw_kind("sg_l2norm_rows_raw", in_kind, &hx)); SG_TRY(raw_kind("sg_l2norm_rows_raw", out_kind, &hy));
+  return l2norm_rows(x, hx, so, si, inner, y, hy, yo, yi, rows, D, eps, as_stream(st));
+}
+extern "C" int sg_softmax_rows_raw(const float* scores, int64_t ld, int64_t rows, int N, int H, const float* scale_per_image, float scale,
+                                   const float* bias, float bias_w, int64_t bias_bstride, const float* bias_rn, const float* bias_cn, int mode,
+                                   int accumulate, int causal, float* out, float* lse, sg_stream st) {
+  SG_REQUIRE(scores && out, "sg_softmax_rows_raw: null pointer");
+  SG_REQUIRE(N >= 1 && H >= 1 && (mode == 0 || mode == 1), "sg_softmax_rows_raw: bad N=%d H=%d mode=%d", N, H, mode);
+  return softmax_rows(scores, ld, rows, N, H, scale_per_image, scale, bias, bias_w, bias_bstride, bias_rn, bias_cn, mode, accumulate, out, lse,
+                      as_stream(st), causal);
+}
+extern "C" int sg_gaussian_bias_raw(int gh, int gw, float std, float* omega, sg_stream st) {
+  SG_REQUIRE(omega, "sg_gaussian_bias_raw: null pointer");
+  SG_REQUIRE(gh >= 1 && gw >= 1, "sg_gaussian_bias_raw: bad grid %d x %d", gh, gw);
+  return gaussian_bias(gh, gw, std, omega, as_stream(st));
+}
+extern "C" int sg_head_norms_raw(const void* x, int kind, int64_t sb, int64_t st, int B, int N, int H, int dh, float* out, sg_stream st_) {
+  SG_REQUIRE(x && out, "sg_head_norms_raw: null pointer");
+  SG_REQUIRE(B > 0 && B < 65536 && N > 0 && H > 0 && dh > 0, "sg_head_norms_raw: bad shape");
+  int hk; SG_TRY(raw_kind("sg_head_norms_raw", kind, &hk));
+  return head_norms(x, hk, sb, st, B, N, H, dh, out, as_stream(st_));
+}
+extern "C" int sg_axpby_raw(float* y, const float* x, float a, float b, int64_t n, sg_stream st) {
+  SG_REQUIRE(y && x, "sg_axpby_raw: null pointer");
+  return axpby(y, x, a, b, n, as_stream(st));
+}
+extern "C" int sg_gem_inv_temp_raw(const float* x, int B, int N, int D, float scale, float* out, sg_stream st) {
+  SG_REQUIRE(x && out, "sg_gem_inv_temp_raw: null pointer");
+  SG_REQUIRE(B > 0 && N > 0 && D > 0, "sg_gem_inv_temp_raw: bad shape");
+  return gem_inv_temp(x, B, N, D, scale, out, as_stream(st));
+}
+extern "C" int sg_patchify_raw(const sg_tile_batch* tiles, int P, int Kpad, void* out, int out_kind, sg_stream st) {
+  SG_REQUIRE(tiles && out && tiles->scene && tiles->windows, "sg_patchify_raw: null pointer");
+  SG_REQUIRE(P > 0, "sg_patchify_raw: P=%d", P);
+  int hk; SG_TRY(raw_kind("sg_patchify_raw", out_kind, &hk));
+  return patchify(*tiles, P, out, Kpad, hk, as_stream(st));
+}
 // "<kernel> ..." of the calling thread's last launch through the fused attention or its statistics (thread-local text).
 extern "C" const char* sg_attention_last_kernel(void) { return attention_last_kernel(); }
 // which body that launch ran: "dma" / "staged" (the fused attention), "stats", or "none"

@@ -34,7 +34,14 @@ __global__ __launch_bounds__(256) void patchify_kernel(sg_tile_batch t, int P_rt
           v = reinterpret_cast<const float*>(t.scene)[img_off + ((int64_t)c * t.scene_h + sy) * t.scene_w + sx];
         } else {
           const uint8_t u = reinterpret_cast<const uint8_t*>(t.scene)[img_off + ((int64_t)sy * t.scene_w + sx) * 3 + c];
-          v = ((float)u - c_mean[c]) / c_std[c];
+          // (u - mean) / std to the nearest f32.  The subtraction is exact below |u - mean| = 128; above it (channel 2 from u = 233) it
+          // rounds, and with the division's own rounding the quotient was up to 1.37 ulp off.  There the subtraction's residual e (exact:
+          // |u| >= |mean|) and the division's remainder correct the quotient; every other pixel keeps the plain quotient's bits.
+          const float fu = (float)u, m = c_mean[c], sd = c_std[c];
+          const float d = fu - m;
+          const float e = (fu - d) - m;
+          v = d / sd;
+          if (e != 0.f) v += (__builtin_fmaf(-v, sd, d) + e) / sd;
         }
       }
     }

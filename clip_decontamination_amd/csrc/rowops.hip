@@ -95,7 +95,10 @@ int layernorm(const float* x, int64_t ldx, const float* gamma, const float* beta
 // ---- fp8 (OCP e4m3) row quantisation ------------------------------------------------------------------------------------------
 // q[r,:] = e4m3(v[r,:] / scale[r]),  scale[r] = max|v[r,:]| / 448  (per-token dynamic scale; per-output-channel for weights).
 // v_cvt_pk_fp8_f32 rounds to nearest even; |v| / scale <= 448 by construction, so nothing saturates.
+// A row with amax below 448 * 2^-126 keeps the smallest normal f32 as its scale: amax / 448 would be subnormal (or flushed to 0) and its
+// reciprocal +inf, which turned the whole row into inf / NaN codes.  Rows with amax >= 2^-117 are unaffected.
 constexpr float FP8_MAX = 448.0f;
+constexpr float FP8_MIN_SCALE = 1.17549435e-38f;
 __device__ __forceinline__ uint32_t pack_fp8x4(float a, float b, float c, float d) {
   int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
   w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
@@ -141,7 +144,7 @@ __global__ __launch_bounds__(256) void layernorm_fp8_kernel(const float* __restr
     }
   }
   amax = wave_max_dpp(amax);
-  const float sc = amax > 0.f ? amax / FP8_MAX : 1.0f;
+  const float sc = amax > 0.f ? fmaxf(amax / FP8_MAX, FP8_MIN_SCALE) : 1.0f;
   const float inv = 1.0f / sc;
 #pragma unroll
   for (int i = 0; i < LN_MAX_VEC; ++i) {
@@ -175,7 +178,7 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(const T* __restr
     for (int e = 0; e < 4; ++e) amax = fmaxf(amax, fabsf(to_f32<T>(xr[c + e])));
   }
   amax = wave_max_dpp(amax);
-  const float sc = amax > 0.f ? amax / FP8_MAX : 1.0f;
+  const float sc = amax > 0.f ? fmaxf(amax / FP8_MAX, FP8_MIN_SCALE) : 1.0f;
   const float inv = 1.0f / sc;
   for (int c = lane * 4; c < D; c += 256)
     *reinterpret_cast<uint32_t*>(y + row * ldy + c) =
@@ -508,6 +511,7 @@ int l2norm_rows(const void* x, int x_bf16, int64_t so, int64_t si, int inner, vo
 // scores [rows, N] (row stride ld) hold RAW dot products.  Per row r (token i = r % N of image b = r / (H*N)):
 //   mode 0: p = softmax(scale * s + w * bias)            (bias row from sim[b, i-1, :] shifted by the CLS column)
 //   mode 1: p = softmax( softmax(scale * s) + w * bias ) (the 'Experimental' double softmax, transformer.py:896-902)
+// causal: keys after the query take no part and get probability 0 in both modes (written as 0 unless accumulating).
 // out (+)= p.  lse (optional) receives log-sum-exp of (scale*s [+ w*bias]) for mode 0.
 __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restrict__ scores, int64_t ld, int64_t rows, int N, int H,
                                                            const float* __restrict__ scale_per_image, float scale,
@@ -575,6 +579,7 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
     const float q = expf(p - mx2) * inv2;
     orow[j] = accumulate ? orow[j] + q : q;
   }
+  if (!accumulate) for (int j = Nk + lane; j < N; j += 64) orow[j] = 0.f;
 }
 
 int softmax_rows(const float* scores, int64_t ld, int64_t rows, int N, int H, const float* scale_per_image, float scale,

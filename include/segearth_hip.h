@@ -373,6 +373,63 @@ int sg_attention_raw(int precision, const void* q0, const void* q1, const void* 
  * q_j.k_j - lse[b,h,j]).  SG_PREC_BF16 / F16 / F16X2 storage. */
 int sg_attention_stats_raw(int precision, const void* qk, int64_t sb, int64_t st, const float* lse, int B, int N, int H, int dh,
                            float scale, float* attn_cls, float* attn_diag, sg_stream s);
+/* ---- raw test entries of the row kernels and patchify -----------------------------------------------------------------------------
+ * Each passes its arguments one to one to ONE host function of the library (csrc/rowops.h), so a test can hold that kernel alone to a
+ * reference at any shape, stride and storage the host function accepts; a refused call (non-zero, sg_last_error) launches nothing.
+ * `kind` arguments name a storage by its sg_precision value: SG_PREC_F32 f32, SG_PREC_BF16 bf16, SG_PREC_F16 IEEE f16, SG_PREC_F16X2
+ * two-plane groups of 8 elements as [8 hi f16][8 lo f16] (rows then start on multiples of 8 elements).  Strides are in elements. */
+/* y[r, :D] = LayerNorm(x[r, :D]) * gamma + beta (biased variance, eps inside the square root), rows of x / y ldx / ldy elements apart,
+ * y in the storage `out_kind`.  D % 4 == 0, D <= 2048, strides multiples of 4 (two-plane: D and ldy multiples of 8). */
+int sg_layernorm_raw(const float* x, int64_t ldx, const float* gamma, const float* beta, void* y, int64_t ldy, int out_kind, int64_t rows,
+                     int D, float eps, sg_stream s);
+/* The same LayerNorm quantised per row to OCP e4m3: scale[r] = max|v[r, :]| / 448 (1 for an all-zero row, never below the smallest normal
+ * f32), y[r, :D] = e4m3(v / scale[r]) bytes, rows ldy bytes apart. */
+int sg_layernorm_fp8_raw(const float* x, int64_t ldx, const float* gamma, const float* beta, void* y, int64_t ldy, float* scale, int64_t rows,
+                         int D, float eps, sg_stream s);
+/* Rows of f32 / bf16 / f16 (`in_kind`, ldx elements apart) -> e4m3 bytes (ldy apart) + per-row scale as above.  D % 4 == 0, ldy % 4 == 0. */
+int sg_quantize_rows_raw(const void* x, int in_kind, int64_t ldx, void* y, int64_t ldy, float* scale, int64_t rows, int D, sg_stream s);
+/* x[b, t, :] = LayerNorm((t == 0 ? cls_emb : patches[b (N-1) + t - 1, :]) + pos[t, :]); patches rows ldp apart, x [B, N, D] dense. */
+int sg_embed_assemble_raw(const float* patches, int64_t ldp, const float* cls_emb, const float* pos, const float* gamma, const float* beta,
+                          float* x, int B, int N, int D, float eps, sg_stream s);
+/* pos [1 + g0 g0, D] -> out [1 + gh gw, D]: row 0 copied; antialias 0: bicubic (A = -0.75) at scale_factor (g + 0.1) / g0, 1: the
+ * antialiased bicubic (A = -0.5) to size (gh, gw); a downscale whose window exceeds 24 taps is refused. */
+int sg_posembed_resize_raw(const float* pos, int g0, int D, int gh, int gw, int antialias, float* out, sg_stream s);
+/* dst [rows, cols_pad] in the storage `kind` = src [rows, :cols] (rows ld_src apart) rounded once, columns >= cols zero.  Two-plane:
+ * cols_pad % 8 == 0. */
+int sg_pack_rows_raw(const float* src, int64_t rows, int cols, int64_t ld_src, void* dst, int cols_pad, int kind, sg_stream s);
+/* dst [cols, rows] in the storage `kind` = src [rows, cols]^T rounded once.  Two-plane: rows % 8 == 0. */
+int sg_transpose_pack_raw(const float* src, int rows, int cols, void* dst, int kind, sg_stream s);
+/* slice_stats [D/64][rows][2] = (sum, centred sum of squares) of each 64-wide slice of a row -> mean_rstd [rows][2] by Chan's combination.
+ * D % 64 == 0, rows > 0. */
+int sg_ln_stats_finalize_raw(const float* slice_stats, int64_t rows, int D, float eps, float* mean_rstd, sg_stream s);
+/* LayerNorm folded into a weight W [N, K]: Wp = round(gamma o W) in the storage of `precision` (bf16 / f16 / two-plane, K % 8 == 0 for the
+ * last), c[n] = sum_k Wp[n, k] of the rounded values, bias_f[n] = (bias ? bias[n] : 0) + sum_k beta[k] W[n, k]. */
+int sg_fold_ln_weight_raw(const float* W, int N, int K, const float* gamma, const float* beta, const float* bias, int precision, void* Wp,
+                          float* c, float* bias_f, sg_stream s);
+/* y_row = x_row / max(||x_row||, eps) over D contiguous elements; row r of x at (r / inner) so + (r % inner) si, of y at (r / inner) yo +
+ * (r % inner) yi; storages `in_kind` / `out_kind` (two-plane rows start on multiples of 8); x == y allowed when the kinds agree. */
+int sg_l2norm_rows_raw(const void* x, int in_kind, int64_t so, int64_t si, int inner, void* y, int out_kind, int64_t yo, int64_t yi,
+                       int64_t rows, int D, float eps, sg_stream s);
+/* The materialised softmax over rows of scores [rows, N] (stride ld; row = (b H + h) N + i), out with the same layout:
+ * mode 0 p = softmax(sc s + w bias), mode 1 p = softmax(softmax(sc s) + w bias); sc = scale_per_image ? scale_per_image[b] : scale;
+ * the bias term of (i, j) is bias[b bias_bstride + (i-1)(N-1) + j-1] (none at i == 0 or j == 0), w = bias_w (x bias_rn[b,h,i])
+ * (x bias_cn[b,h,j]); causal: keys j > i get probability 0; out += p with accumulate; lse [rows] (optional) = log-sum-exp of the first
+ * softmax's arguments. */
+int sg_softmax_rows_raw(const float* scores, int64_t ld, int64_t rows, int N, int H, const float* scale_per_image, float scale,
+                        const float* bias, float bias_w, int64_t bias_bstride, const float* bias_rn, const float* bias_cn, int mode,
+                        int accumulate, int causal, float* out, float* lse, sg_stream s);
+/* omega [gh gw, gh gw]: exp(-((y - y')^2 + (x - x')^2) / (2 std^2)) over the cells of a gh x gw grid (row-major cell index). */
+int sg_gaussian_bias_raw(int gh, int gw, float std, float* omega, sg_stream s);
+/* out[b, h, t] = || x[b sb + t st + h dh : + dh] || for x in the storage `kind` (strides in elements). */
+int sg_head_norms_raw(const void* x, int kind, int64_t sb, int64_t st, int B, int N, int H, int dh, float* out, sg_stream s);
+/* y[i] = a x[i] + b y[i], i < n. */
+int sg_axpby_raw(float* y, const float* x, float a, float b, int64_t n, sg_stream s);
+/* out[b] = scale * mean_t || x[b, t, :] || for x [B, N, D]. */
+int sg_gem_inv_temp_raw(const float* x, int B, int N, int D, float scale, float* out, sg_stream s);
+/* The patch matrix [n_tiles grid_h grid_w, Kpad] in the storage `out_kind` of a tile batch: column k = c P P + py P + px holds the
+ * (normalised, for u8 scenes) pixel of the window padded by pad_t rows on top and pad_l columns on the left, zero in the padding and in
+ * columns >= 3 P P.  Kpad >= 3 P P (two-plane: Kpad % 8 == 0), the grid must cover the padded tile. */
+int sg_patchify_raw(const sg_tile_batch* tiles, int P, int Kpad, void* out, int out_kind, sg_stream s);
 size_t sg_op_attention_scratch_bytes(int B, int N, int D, int H, int precision);
 int sg_op_attention(const float* qkv, int B, int N, int D, int H, int variant, const float* sim, float sim_weight,
                     float* ctx, float* attn_cls, float* attn_diag, int precision, void* scratch, size_t scratch_bytes,

@@ -11,26 +11,13 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import refine_reference as R                                            # noqa: E402
 from refine_reference import check_within                               # noqa: E402
+from rowops_reference import lane_sum                                   # noqa: E402  (the kernels' 64-lane strided sum + butterfly)
 from oracle import refine as OR, ctd as OC                              # noqa: E402
 
 TEMPS = (0.1, 5.0)
 
 
 # ---- refiners --------------------------------------------------------------------------------------------------------------------
-def lane_sum(v):
-    """Sum over the last axis as the kernels do: lane l adds elements l, l + 64, ... in order, then the xor butterfly 32, 16, .., 1."""
-    pad = (-v.shape[-1]) % 64
-    v = torch.nn.functional.pad(v, (0, pad)).view(*v.shape[:-1], -1, 64)
-    acc = v[..., 0, :]
-    for r in range(1, v.shape[-2]):
-        acc = acc + v[..., r, :]
-    w = 64
-    while w > 1:
-        w //= 2
-        acc = acc[..., :w] + acc[..., w:2 * w]
-    return acc[..., 0]
-
-
 def emulate_refine(feats, idx, gh, gw, temp, decontaminate, dtype=torch.float32, lane=True, mut=None):
     """refine_compute_kernel + refine_scatter_kernel in `dtype`, with the mutations of the module docstring."""
     B, n, D = feats.shape
