@@ -185,7 +185,13 @@ int sg_cosine_logits(const float* tokens, const float* cls, const float* text, i
 /* The per-pixel logits behind the upsampler (segmentor.py:374-379, no global debias: it ran before the upsampler) for the exact tower mode
  * SG_PREC_F16X2: the [n, E] x [E, Q] product on the f16 matrix pipe with both operands as two f16 planes (f32-grade results, three MFMAs per
  * product; magnitudes beyond +-131 008 saturate, as everywhere in that mode).  Same layouts as sg_cosine_logits; shapes it does not take
- * (Q > 16, E % 32 != 0, n < 4096) are forwarded to sg_cosine_logits. */
+ * (Q > 16, E % 32 != 0, n < 4096) are forwarded to sg_cosine_logits.
+ * Precision: every feature and text element is held as hi + lo with a representation error of max(2^-22 |x|, 2^-25) -- an ABSOLUTE floor
+ * of 2^-25 per element, so the kernel is not scale-invariant although the cosine it computes is.  f32-grade for per-element magnitudes of
+ * 1e-2 and above; below that the error grows as 1 / scale.  CPU emulation of the split (E = 768, Q = 16, max |err| against float64) by
+ * token scale: 1e2 6e-8, 1 7e-8, 1e-2 2.6e-7, 1e-3 2.5e-6, 1e-4 2.5e-5, 1e-5 2.3e-4.  Measured on an MI355X
+ * (tests/test_gpu_head_reference.py): 7.5e-7 over row scales 2^-6 .. 2^6 (E = 32 / 96), 7.1e-5 with every row at 2^-13 (E = 96, Q = 13;
+ * the per-element bound there is 2.9e-4).  Rescale the rows before the call if they can be smaller than that. */
 int sg_cosine_logits_two_plane(const float* tokens, const float* cls, const float* text, int B, int n, int E, int Q,
                                float cls_token_lambda, float* logits, sg_stream s);
 
