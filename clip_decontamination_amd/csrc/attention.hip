@@ -140,11 +140,25 @@ __device__ __forceinline__ void dma_tile(const bf16_t* row0, uint32_t rows_left,
 // with different bodies (AH2 is a file-level constant), so it must not share their symbols.
 // DMA: the lean dh-64 body stages K / V by LDS-DMA into the swizzled image above and keeps -m_run resident (launch_attn); false = the
 // register-staged body (every other instantiation, and under TUNE_ATTN_STAGED as the same-process baseline).
+// DMA with GK == 2 (dh 64, one stream): the 'Experimental' last block on the same staging, with its own arithmetic unchanged -- the scores
+// start at 0 and are scaled, re-soft-maxed and biased in f32 exactly as in the register-staged body (TUNE_EXPER_STAGED keeps that one
+// reachable; the two agree bit for bit).  What differs is what the result does not need: the similarity-map fetch of a STEADY tile (not
+// the first, not the last key tile, a query block without token 0) is 32 plain dword loads off one per-tile scalar base, and the key < N
+// select runs in the last key tile only.
+// VM-counter order of that body (LDS-DMA pieces and bias loads retire in issue order on ONE counter), per key tile t:
+//     [K / V fragment reads of tile t] -> pieces of tile t+1 -> [scores use the bias of tile t] -> bias loads of tile t+1 -> [exp2, P V]
+//     -> s_waitcnt vmcnt(0) -> barrier.
+// The bias of tile t was retired by the vmcnt(0) in front of the PREVIOUS barrier (the first one by a wait of its own before the loop), so
+// nothing waits between the issue of the pieces and the end of the tile: they drain where the lean body drains them.  These waits are the
+// s_waitcnt builtin, not inline assembly, so that the compiler's own counter bookkeeping knows the bias registers are ready and puts no
+// vmcnt(0) of its own in front of their first use -- which comes after the pieces' issue and would drain them at once.
 template <int DH, int TS, int GK, bool MULTI, bool F16, bool PV, bool H2 = AH2, bool DMA = false>
 // (two-plane form: twice the fragment registers -- the variants with a bias / two summed terms and every head_dim > 64 get the whole file too)
 __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 || MULTI || DH > 80)) || (AH2 && (DH > 64 || (GK != 0 && TS == 2)))) ? 1 : 2) void attn_kernel(AttnArgs a) {
   constexpr bool GENERIC = GK != 0, EXPER = GK == 2;
-  static_assert(!DMA || (GK == 0 && !AH2 && DH == 64), "attention: the LDS-DMA body is the lean dh-64 one");
+  static_assert(!DMA || ((GK == 0 || (GK == 2 && !MULTI)) && !AH2 && DH == 64), "attention: the LDS-DMA bodies are the lean and the 'Experimental' dh-64 ones");
+  constexpr bool XDMA = EXPER && DMA;                                   // the 'Experimental' LDS-DMA body
+  constexpr int VM_DRAINED = 0x0F70;                                    // s_waitcnt vmcnt(0) alone (gfx9 encoding: expcnt 7, lgkmcnt 15 = no wait)
   using C = AttnCfg<DH>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int K_LD = DMA ? DH : C::K_LD, V_LD = DMA ? DH : C::V_LD;  // LDS row strides (DMA: unpadded, swizzled)
@@ -292,9 +306,9 @@ __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 ||
     }
     __syncthreads();
     int cur = 0;
-    // DMA: the score accumulator starts from this resident -m_run block (0 while m_run is -inf); it changes only where m_run does
+    // lean DMA: the score accumulator starts from this resident -m_run block (0 while m_run is -inf); it changes only where m_run does
     f32x16 negm;
-    if constexpr (DMA) {
+    if constexpr (DMA && !GENERIC) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) negm[r] = 0.f;
     }
@@ -306,8 +320,38 @@ __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 ||
     constexpr bool BIAS_AHEAD = !(GENERIC && MULTI && DH > 64);
     float bnext[GENERIC ? 32 : 1];
     const float bias_rn = (GENERIC && a.bias_rn) ? a.bias_rn[((int64_t)b * a.H + hd) * a.N + q_ld] : 1.f;
+    // XDMA: the map of THIS image as a buffer (n n 4 bytes < 2^31, launch_attn), addressed by 32-bit byte offsets: a lane's own part -- its
+    // query column and, for the upper half-wave, four rows down (key + 4 h) -- in the VGPR offset, the key row in the scalar offset.
+    const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(XDMA ? a.bias + (int64_t)b * a.bias_bstride : nullptr), 0, XDMA ? n * n * 4 : 0, 0x00020000);
+    const int b_lane = (4 * h * n + q_ld - 1) * 4;           // steady tiles only (q_ld >= 1 there)
+    auto steady = [&](int kbase) { return kbase >= KT && kbase + KT <= a.N && qb != 0; };   // block-uniform
     auto fetch_bias = [&](int kbase) {
-      if (GENERIC && (EXPER || a.bias)) {
+      if constexpr (XDMA) {
+        if (steady(kbase)) {
+          // STEADY tile (block-uniform): every key is in [1, N) and every query of the block is >= 1, so each of the 32 addresses is
+          // element (key - 1, q_ld - 1) of this image's n x n map -- no predicate, no select, no per-lane address arithmetic: one
+          // scalar add per load.  It is THIS branch condition that keeps the loads inside the map, not the descriptor's range.
+          const int b_tile = (kbase - 1) * n * 4;
+#pragma unroll
+          for (int i = 0; i < 32; ++i) {
+            const int row = 32 * (i >> 4) + (i & 3) + 8 * ((i & 15) >> 2);    // + 4 h: in b_lane
+            bnext[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(b_rsrc, b_lane, b_tile + row * n * 4, 0));
+          }
+        } else {
+          // First key tile (key 0), last key tile (keys >= N), query block 0 (token 0): the predicate of the register-staged body picks
+          // between the map and 0 -- where the tile is USED (below, under the same block-uniform condition), so that nothing waits for
+          // a load here.  The loads themselves are unconditional from an address CLAMPED into the map (key to [1, N), query to >= 1;
+          // N >= 2 on this body, launch_attn): whatever the predicate says, no load leaves this image's map.
+          const int qcol = (q_ld >= 1 ? q_ld : 1) - 1;
+#pragma unroll
+          for (int i = 0; i < 32; ++i) {
+            const int key = kbase + 32 * (i >> 4) + (i & 3) + 8 * ((i & 15) >> 2) + 4 * h;
+            const int kc = key < 1 ? 1 : key < a.N ? key : a.N - 1;
+            bnext[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(b_rsrc, ((kc - 1) * n + qcol) * 4, 0, 0));
+          }
+        }
+      } else if (GENERIC && (EXPER || a.bias)) {
 #pragma unroll
         for (int i = 0; i < 32; ++i) {
           const int key = kbase + 32 * (i >> 4) + (i & 3) + 8 * ((i & 15) >> 2) + 4 * h;
@@ -318,6 +362,7 @@ __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 ||
       }
     };
     if (BIAS_AHEAD) fetch_bias(0);
+    if constexpr (XDMA) __builtin_amdgcn_s_waitcnt(VM_DRAINED);   // the first tile's bias (and lse_in) land here, not behind the pieces of tile 1
     for (int k0 = 0; k0 < a.N; k0 += KT) {
       const bool has_next = k0 + KT < a.N;
       if constexpr (!DMA) {
@@ -334,7 +379,7 @@ __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 ||
       f32x16 sacc[2];
       {
         const float s_init = (!GENERIC && m_run != -INFINITY) ? -m_run : 0.f;
-        if constexpr (!DMA) {
+        if constexpr (!DMA || GENERIC) {
 #pragma unroll
           for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
@@ -376,7 +421,7 @@ __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 ||
           for (int ks = 0; ks < C::KS; ++ks)
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub)              // the two key sub-blocks alternate: no MFMA waits on its predecessor
-              sacc[sub] = mfma_32x32x16<F16>(kf[sub][t][ks], qf[t][ks], (DMA && t == 0 && ks == 0) ? negm : sacc[sub]);
+              sacc[sub] = mfma_32x32x16<F16>(kf[sub][t][ks], qf[t][ks], (DMA && !GENERIC && t == 0 && ks == 0) ? negm : sacc[sub]);
         }
       }
       // (b) V^T fragments of the tile are fetched NOW (transposed LDS reads, lane 4q+p of a 16-lane group addresses row q,
@@ -410,18 +455,36 @@ __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 ||
       float mloc;
       if (GENERIC) {
         if (!BIAS_AHEAD) fetch_bias(k0);
+        if (XDMA && !steady(k0)) {                         // edge tile: token 0 and keys past the end have no map entry (see fetch_bias)
+#pragma unroll
+          for (int i = 0; i < 32; ++i) {
+            const int key = k0 + 32 * (i >> 4) + (i & 3) + 8 * ((i & 15) >> 2) + 4 * h;
+            if (!(key >= 1 && key < a.N && q_ld >= 1)) bnext[i] = 0.f;
+          }
+        }
 #pragma unroll
         for (int i = 0; i < 32; ++i) {
           const int key = k0 + 32 * (i >> 4) + (i & 3) + 8 * ((i & 15) >> 2) + 4 * h;
           const float bv = (EXPER || a.bias) ? bnext[i] * a.bias_w : 0.f;
           float v = sacc[i >> 4][i & 15] * c2;
           if (EXPER || a.resoftmax) v = (__builtin_amdgcn_exp2f(v - lse1_2) + bv) * LOG2E; else v += bv * LOG2E;
-          sc[i] = (key < a.N && !(!EXPER && a.causal && key > q_glob)) ? v : -INFINITY;   // causal: text tower (build_causal_mask)
+          sc[i] = (XDMA || (key < a.N && !(!EXPER && a.causal && key > q_glob))) ? v : -INFINITY;   // causal: text tower (build_causal_mask)
+        }
+        // XDMA: the scores are complete HERE -- left to itself the compiler sinks them below the fetch, which then needs a second set of
+        // 32 bias registers and 32 copies per tile
+        if constexpr (XDMA) {
+#pragma unroll
+          for (int i = 0; i < 32; ++i) asm volatile("" : "+v"(sc[i]));
         }
         if (BIAS_AHEAD && has_next) fetch_bias(k0 + KT);   // lands under this tile's softmax / PV and the next tile's QK^T
+        if (XDMA && k0 + KT > a.N) {                       // tail tile: mask keys past the end (block-uniform branch)
+#pragma unroll
+          for (int i = 0; i < 32; ++i)
+            if (k0 + 32 * (i >> 4) + (i & 3) + 8 * ((i & 15) >> 2) + 4 * h >= a.N) sc[i] = -INFINITY;
+        }
         mloc = sc[0];
 #pragma unroll
-        for (int i = 1; i < 32; ++i) mloc = fmaxf(mloc, sc[i]);
+        for (int i = 1; i < 32; ++i) mloc = DMA ? __builtin_elementwise_maximum(mloc, sc[i]) : fmaxf(mloc, sc[i]);
       } else {
         if (k0 + KT > a.N) {                               // tail tile: mask keys past the end (block-uniform branch)
 #pragma unroll
@@ -530,7 +593,10 @@ __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 ||
             o_acc[t] = mfma_32x32x16<F16>(*reinterpret_cast<bf16x8*>(&vfr[t][f]), pf[f], o_acc[t]);
       }
       if (NB == 1) __syncthreads();                          // single buffer: every wave is done reading the tile before it is overwritten
-      if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the next tile have landed (before the barrier)
+      if constexpr (XDMA) {                                  // the next tile's pieces AND its bias have landed (see the order at the top)
+        __builtin_amdgcn_s_waitcnt(VM_DRAINED);
+        asm volatile("" ::: "memory");
+      } else if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the next tile have landed (before the barrier)
       else if (has_next) {                                   // the other buffer was last read one iteration ago
         bf16_t* nK = sbuf + (NB == 2 ? (cur ^ 1) * BUF : 0);
 #pragma unroll
@@ -580,7 +646,7 @@ __global__ __launch_bounds__(256, ((GK != 0 && MULTI) || (DH > 64 && (GK != 0 ||
 }
 
 // The lean dh-64 kernels of the bf16 / f16 forms run the LDS-DMA body unless TUNE_ATTN_STAGED asks for the register-staged one (same-process
-// A/B and bit-identity checks against the previous body).
+// A/B and bit-identity checks against the previous body); likewise the dh-64 'Experimental' kernel and TUNE_EXPER_STAGED.
 template <int DH, int TS>
 static int launch_attn(const AttnArgs& a, hipStream_t s) {
   using C = AttnCfg<DH>;
@@ -594,8 +660,11 @@ static int launch_attn(const AttnArgs& a, hipStream_t s) {
   using Kern = void (*)(AttnArgs);
   const bool exper = generic && a.bias && a.resoftmax && !a.causal && !a.bias_cn && !a.bias_rn && !multi && a.ctx;
   constexpr bool CAN_DMA = DH == 64 && !AH2;
-  const bool dma = CAN_DMA && !generic && get_gemm_config() != TUNE_ATTN_STAGED;
-  const Kern kern = exper ? attn_kernel<DH, TS, 2, false, AF16, true>
+  // (a single token has no similarity map: the 'Experimental' LDS-DMA body, whose edge tiles load from addresses clamped INTO the map, is for N >= 2)
+  const bool dma = CAN_DMA && ((!generic && get_gemm_config() != TUNE_ATTN_STAGED) || (exper && a.N >= 2 && get_gemm_config() != TUNE_EXPER_STAGED));
+  // that body addresses the similarity map with 32-bit byte offsets inside one image
+  SG_REQUIRE(!(exper && dma) || (int64_t)(a.N - 1) * (a.N - 1) * 4 < (1ll << 31), "attention: similarity map too large for 32-bit offsets (N=%d)", a.N);
+  const Kern kern = exper ? (dma ? attn_kernel<DH, TS, 2, false, AF16, true, AH2, CAN_DMA> : attn_kernel<DH, TS, 2, false, AF16, true>)
                   : a.ctx ? (generic ? (multi ? attn_kernel<DH, TS, 1, CAN_MULTI, AF16, true> : attn_kernel<DH, TS, 1, false, AF16, true>)
                                      : dma ? (multi ? attn_kernel<DH, TS, 0, CAN_MULTI, AF16, true, AH2, CAN_DMA> : attn_kernel<DH, TS, 0, false, AF16, true, AH2, CAN_DMA>)
                                            : (multi ? attn_kernel<DH, TS, 0, CAN_MULTI, AF16, true> : attn_kernel<DH, TS, 0, false, AF16, true>))

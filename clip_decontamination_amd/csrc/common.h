@@ -302,6 +302,7 @@ enum Tuning {
   TUNE_NO_SMALL_LAUNCH = 36,   // no small-launch dispatch: a few-tile GEMM stays on the persistent kernel
   TUNE_PERSIST_K32 = 38,       // the persistent bf16 / f16 GEMM on 32-element K steps (same results as the 64-element one)
   TUNE_ATTN_STAGED = 39,       // the lean dh-64 attention with register-staged K / V instead of LDS-DMA (same results)
+  TUNE_EXPER_STAGED = 40,      // the dh-64 'Experimental' last-block attention on its register-staged body (same results)
 };
 int set_gemm_config(int c);    // tuning hook (per calling thread): -1, a Tuning code, 1000 + v or 2000 + n; anything else is refused
 

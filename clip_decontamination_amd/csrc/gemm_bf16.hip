@@ -1412,6 +1412,7 @@ int set_gemm_config(int c) {
   if (c >= 1000) { g_gemm_order = c - 1001; return SG_OK; }      // 1000 -> -1 (automatic), 1001 -> 0 (raster), 1001 + v -> N-group size v
   switch (c) {
     case -1: case TUNE_FP8_RING: case TUNE_FP8_PERSIST: case TUNE_LN_PASS: case TUNE_NO_SMALL_LAUNCH: case TUNE_PERSIST_K32: case TUNE_ATTN_STAGED:
+    case TUNE_EXPER_STAGED:
       g_gemm_config = c;
       return SG_OK;
   }

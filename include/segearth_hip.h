@@ -146,15 +146,17 @@ const char* sg_attention_last_kernel(void);   /* the calling thread's last launc
                                               * its statistics kernel: "stats_fast lph=<4|8|16> kind=<bf16|f16> grid=<blocks>" / "stats_generic lph=0
                                               * kind=<bf16|f16|h2> grid=<blocks>"; "none" when its last such call launched nothing.  Valid until the
                                               * thread's next query. */
-const char* sg_attention_last_body(void);     /* the body of that same launch: "dma" (the lean dh-64 kernel staging K / V by LDS-DMA), "staged"
-                                              * (register-staged K / V: every other fused-attention kernel, and the lean dh-64 one under tuning
-                                              * code 39), "stats" (a statistics kernel) or "none". */
+const char* sg_attention_last_body(void);     /* the body of that same launch: "dma" (the lean and the 'Experimental' dh-64 kernels staging K / V by
+                                              * LDS-DMA), "staged" (register-staged K / V: every other fused-attention kernel, the lean dh-64 one
+                                              * under tuning code 39 and the 'Experimental' dh-64 one under code 40), "stats" (a statistics kernel)
+                                              * or "none". */
 int sg_set_gemm_config(int cfg);   /* tuning hook (calling thread only), -1 = automatic; 31 = the fp8 GEMM on its ring kernels at every shape,
                                     * 32 = the fp8 GEMM's persistent kernel from K = 512 on (not only from K = 2048), 34 = LayerNorm as its own
                                     * pass (no folding), 36 = no small-launch dispatch (a few-tile GEMM stays on the persistent kernel), 38 = the
                                     * persistent kernel with 32-element K steps (same results as the default 64-element one), 39 = the fused
                                     * attention's lean dh-64 kernels with register-staged K / V instead of LDS-DMA (the previous body, bit-identical
-                                    * results); 1000 + v = tile order of the persistent kernel; 2000 + n = at most n workgroups for every persistent
+                                    * results), 40 = the dh-64 'Experimental' last-block attention on its register-staged body (likewise);
+                                    * 1000 + v = tile order of the persistent kernel; 2000 + n = at most n workgroups for every persistent
                                     * kernel (2000 = one per CU).  Any other code is refused (SG_ERR_INVALID, the setting unchanged). */
 int sg_profile_read(int category, double* total_ms, double* total_flops, int64_t* launches, int64_t* dropped);
 
