@@ -509,8 +509,8 @@ extern "C" int sg_gemm_fp8_raw(const void* A8, const float* sa, const void* W8, 
 // [K/128][M][4] bytes) describes A8; when c_mx is given the result is written as e4m3 [M,N] + block scales c_mx_scale [N/128][M][4] and C is unused.
 extern "C" int sg_gemm_fp8_mx_raw(const void* A8, const float* sa, const void* a_mx, const void* W8, const float* sw, const float* bias,
                                   const float* residual, void* C, void* c_mx, void* c_mx_scale, int M, int N, int K, int act, int c_is_bf16, sg_stream st) {
-  SG_REQUIRE(A8 && W8 && sw && ((sa != nullptr) != (a_mx != nullptr)) && (C || c_mx), "sg_gemm_fp8_mx_raw: bad pointers");
-  SG_REQUIRE(!c_mx || c_mx_scale, "sg_gemm_fp8_mx_raw: c_mx needs c_mx_scale");
+  // one of sa / a_mx and c_mx_scale with c_mx: gemm_fp8's own checks, behind the reset of the launch record (a refused call reads "none")
+  SG_REQUIRE(A8 && W8 && sw && (C || c_mx), "sg_gemm_fp8_mx_raw: null pointer");
   return linear_fp8_mx((const uint8_t*)A8, sa, (const uint8_t*)a_mx, K, (const uint8_t*)W8, sw, bias, residual, C, N, !c_is_bf16, (uint8_t*)c_mx,
                        (uint8_t*)c_mx_scale, M, N, K, act, as_stream(st));
 }

@@ -1426,6 +1426,13 @@ constexpr const char* ring_name() {
   if (FP8) return BM_ == 128 ? "fp8_ring128" : "fp8_ring256x256";
   return SPLIT ? "h2_ring128" : "ring128";
 }
+// the MXFP8 forms of the fp8 256 x 256 ring, one name per instantiation: the fc forms (MX output after QuickGELU / GELU, SPEC 2 / 3), the proj
+// form (MX operand, f32 + residual, SPEC 4), the generic MX-operand body and the generic body writing an MX output chosen at run time
+template <bool MXA, int SPEC>
+constexpr const char* mx_ring_name() {
+  if (MXA) return SPEC == 4 ? "fp8_mx_ring256x256_proj" : "fp8_mx_ring256x256_mxa";
+  return SPEC == 2 ? "fp8_mx_ring256x256_fc1" : SPEC == 3 ? "fp8_mx_ring256x256_fc2" : "fp8_mx_ring256x256_out";
+}
 template <int BM_, int BN_, int WM, int WN, int STAGES, bool FP8 = false, bool F16 = false, bool MXA = false, int SPEC = 0, bool SPLIT = false>
 static int launch_ring(const GemmBf16Args& a, int vec, hipStream_t s) {
   auto kern = gemm_bf16_ring<BM_, BN_, WM, WN, STAGES, FP8, F16, MXA, SPEC, SPLIT>;
@@ -1434,7 +1441,7 @@ static int launch_ring(const GemmBf16Args& a, int vec, hipStream_t s) {
   const int64_t tiles = cdiv(a.M, BM_) * cdiv(a.N, BN_);
   SG_REQUIRE(tiles < (1ll << 31) && a.batch < 65536, "gemm_bf16: grid too large");
   hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)a.batch), dim3(WM * WN * 64), lds, s, a, a.act, a.c_is_bf16, vec);
-  note_launch(FP8 && (a.a_mx || a.c_mx) ? "fp8_mx_ring256x256" : ring_name<BM_, BN_, FP8, SPLIT>(), tiles);
+  note_launch(FP8 && (a.a_mx || a.c_mx) ? mx_ring_name<MXA, SPEC>() : ring_name<BM_, BN_, FP8, SPLIT>(), tiles);
   return SG_OK;
 }
 
@@ -1449,6 +1456,7 @@ static int gemm_fp8(const GemmBf16Args& a, hipStream_t s) {
   SG_REQUIRE(a.lda % 16 == 0 && a.ldw % 16 == 0 && a.strideA % 16 == 0 && a.strideW % 16 == 0, "gemm_fp8: operand strides must be multiples of 16 bytes");
   SG_REQUIRE((((uintptr_t)a.A) & 15) == 0 && (((uintptr_t)a.W) & 15) == 0, "gemm_fp8: operands must be 16-byte aligned");
   SG_REQUIRE(a.col_scale && (a.row_scale || a.a_mx), "gemm_fp8: col_scale and (row_scale or MX block scales) are required");
+  SG_REQUIRE(!(a.row_scale && a.a_mx), "gemm_fp8: A takes per-row scales or MX block scales, not both");
   if (a.c_mx) SG_REQUIRE(a.c_mx_scale && a.N % 128 == 0 && a.ldc % 8 == 0 && !a.residual, "gemm_fp8: MX output needs c_mx_scale, N %% 128 == 0, no residual");
   SG_REQUIRE(a.act >= 0 && a.act <= 2, "gemm_fp8: bad act %d", a.act);
   bool vec = (a.N % 8 == 0) && (a.ldc % 8 == 0) && (a.strideC % 8 == 0) && ((((uintptr_t)a.C) & 15) == 0) && ((((uintptr_t)a.col_scale) & 15) == 0);
@@ -1456,14 +1464,14 @@ static int gemm_fp8(const GemmBf16Args& a, hipStream_t s) {
   if (a.residual) vec = vec && (a.ldr % 4 == 0) && ((((uintptr_t)a.residual) & 15) == 0);
   GemmBf16Args h = a;                                       // the same bytes seen as a bf16 matrix of half the width
   h.K = a.K / 2; h.lda = a.lda / 2; h.ldw = a.ldw / 2; h.strideA = a.strideA / 2; h.strideW = a.strideW / 2;
+  const bool mx = a.a_mx != nullptr || a.c_mx != nullptr;   // MX operands / MX output live in the ring kernel (the persistent kernel's LDS is full)
+  if (mx) SG_REQUIRE(vec && a.batch == 1 && a.M >= 1024 && a.N >= 256, "gemm_fp8: the MX forms need the large-shape vector path");   // before the timing bracket opens
   prof_begin(PROF_GEMM_FP8, 2.0 * a.M * (double)a.N * a.K * a.batch, s);
   // 256 x 256 x 128 B, two stages (1.47 / 1.32 / 1.64 PFLOP/s on the QKV / fc / proj shapes; the 256 x 128 three-stage tile 1.31 / 1.04 / 1.45)
   // large shapes: the persistent ping-pong kernel (byte strides, original K); TUNE_FP8_RING forces the two-stage ring kernel instead
   // measured (tools/bench_gemm_fp8.py, R = 175 360): proj (K 4096) 1.76 vs 1.65 PFLOP/s for the persistent kernel; QKV / fc (K 1024: 8 K steps
   // per tile, the tile switch weighs twice what it does in bf16) 1.25 / 1.23 vs 1.51 / 1.31 for the ring kernel -> persistent for long K only
-  const bool mx = a.a_mx != nullptr || a.c_mx != nullptr;
-  if (mx) {                                               // MX operands / MX output live in the ring kernel (the persistent kernel's LDS is full)
-    SG_REQUIRE(vec && a.batch == 1 && a.M >= 1024 && a.N >= 256, "gemm_fp8: the MX forms need the large-shape vector path");
+  if (mx) {
     // the tower's MLP hand-off runs on compile-time-specialised epilogues: fc -> MX output after the activation, proj <- MX operand, f32 + residual
     const bool proj_form = a.a_mx && !a.c_mx && !a.c_is_bf16 && a.residual && a.act == ACT_NONE;
     const bool fc_form = !a.a_mx && a.c_mx && (a.act == ACT_QUICK_GELU || a.act == ACT_GELU);

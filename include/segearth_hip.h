@@ -137,8 +137,10 @@ int sg_gemm_persist_last_kstep(void);   /* K step in elements of the calling thr
                                          * 32 (gemm_bf16_persist: K / 64 < 4 or tuning code 38), 0 = none yet */
 const char* sg_gemm_last_kernel(void);   /* the calling thread's last launch through the 2-byte / two-plane / fp8 GEMM: "<family> grid=<x> ngroup=<n>"
                                           * with family persist_k64, persist_k32, h2_persist, fp8_persist, pingpong, h2_pingpong, ring128,
-                                          * h2_ring128, fp8_ring128, fp8_ring256x256 or fp8_mx_ring256x256; grid = workgroups (persistent) or tiles
-                                          * along x; ngroup = the persistent kernel's N-group size (0 = raster order); "none" when its last GEMM call
+                                          * h2_ring128, fp8_ring128, fp8_ring256x256 or one of the MXFP8 forms fp8_mx_ring256x256_fc1 / _fc2 (MX
+                                          * output after QuickGELU / GELU), _proj (MX operand, f32 C + residual, no activation), _mxa (any other MX
+                                          * operand form) or _out (any other MX output form); grid = workgroups (persistent) or tiles along x;
+                                          * ngroup = the persistent kernel's N-group size (0 = raster order); "none" when its last GEMM call
                                           * launched nothing.  The text stays valid until the thread's next query. */
 const char* sg_attention_last_kernel(void);   /* the calling thread's last launch through the fused attention (sg_attention_raw, sg_op_attention,
                                               * the towers): "attn dh=<32|64|80|128> ts=<1|2> gk=<0 lean|1 generic|2 Experimental> multi=<0|1>
