@@ -147,6 +147,10 @@ SIGNATURES = {
     "sg_extract_tiles": (I, [C.POINTER(TileBatch), I, I, P, P]),
     "sg_global_debias": (I, [P, P, I, I, I, F, P, P]),
     "sg_confusion_accumulate": (I, [P, P, I, L, I, I, I, P, P]),
+    "sg_pamr_workspace_bytes": (Z, [I, I, I, I]),
+    "sg_pamr_affinity": (I, [P, I, I, C.POINTER(I), I, P, P]),
+    "sg_pamr_step": (I, [P, P, P, I, I, I, C.POINTER(I), I, P]),
+    "sg_pamr": (I, [P, P, I, I, I, C.POINTER(I), I, I, P, Z, P]),
 }
 
 _lib = None

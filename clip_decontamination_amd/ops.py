@@ -493,6 +493,102 @@ def postprocess_multi(canvases, canvas_hw, query_idx, num_classes: int, logit_sc
     return (prb, lab, labels) if flat_labels else (prb, lab)
 
 
+PAMR_MAX_DILATIONS, PAMR_MAX_DILATION, PAMR_MAX_STEPS = 8, 64, 64        # limits of sg_pamr (csrc/pamr.hip)
+
+
+def pamr_dilations(dilations):
+    """The dilations as (tuple of ints, host int array for the C ABI), checked against the limits the entries state."""
+    d = (int(dilations),) if isinstance(dilations, int) else tuple(int(x) for x in dilations)
+    if not 1 <= len(d) <= PAMR_MAX_DILATIONS or any(not 1 <= x <= PAMR_MAX_DILATION for x in d):
+        raise ValueError(f"pamr: dilations {d!r}: need 1 to {PAMR_MAX_DILATIONS} values, each in [1, {PAMR_MAX_DILATION}]")
+    return d, (C.c_int * len(d))(*d)
+
+
+@on_tensor_device
+def scene_planes(scene):
+    """u8 [H,W,3] scene -> its normalised f32 planes [3,H,W], (u - mean) / std exactly as the tower's ingest computes it (sg_extract_tiles
+    with one whole-scene window): the PAMR guidance of a u8 scene.  A float [3,H,W] scene is its own guidance and is returned as it is."""
+    if scene.dtype != torch.uint8:
+        return _f32(scene)
+    lib = _lib.load()
+    scene = scene.contiguous()
+    _require_gpu(scene)
+    if scene.dim() != 3 or scene.shape[-1] != 3:
+        raise ValueError(f"scene_planes: a u8 scene is [H,W,3], got {tuple(scene.shape)}")
+    H, W = int(scene.shape[0]), int(scene.shape[1])
+    win = torch.tensor([[0, H, 0, W]], dtype=torch.int32, device=scene.device)
+    tb = _lib.TileBatch()
+    tb.scene, tb.format, tb.scene_h, tb.scene_w, tb.windows = scene.data_ptr(), _lib.IMG_U8_NHWC, H, W, win.data_ptr()
+    tb.n_tiles, tb.tile_h, tb.tile_w = 1, H, W
+    out = torch.empty(3, H, W, dtype=torch.float32, device=scene.device)
+    check(lib.sg_extract_tiles(C.byref(tb), H, W, ptr(out), stream_ptr()), "sg_extract_tiles")
+    return out
+
+
+def _pamr_args(logits, guide):
+    _require_gpu(logits, guide)
+    if logits.dim() != 3 or guide.dim() != 3 or guide.shape[0] != 3 or tuple(guide.shape[1:]) != tuple(logits.shape[1:]):
+        raise ValueError(f"pamr: logits [Q,H,W] and guide [3,H,W] of one size, got {tuple(logits.shape)} and {tuple(guide.shape)}")
+
+
+@on_tensor_device
+def pamr_weights(guide, dilations):
+    """sg_pamr_affinity: guide f32 [3,H,W] (the normalised image) -> the PAMR weights [8D,H,W], a softmax over the 8 offsets of each of
+    the D dilations (include/segearth_hip.h states the definition)."""
+    lib = _lib.load()
+    guide = _f32(guide)
+    _require_gpu(guide)
+    if guide.dim() != 3 or guide.shape[0] != 3:
+        raise ValueError(f"pamr_weights: guide is [3,H,W], got {tuple(guide.shape)}")
+    d, arr = pamr_dilations(dilations)
+    H, W = int(guide.shape[1]), int(guide.shape[2])
+    w = torch.empty(8 * len(d), H, W, dtype=torch.float32, device=guide.device)
+    check(lib.sg_pamr_affinity(ptr(guide), H, W, arr, len(d), ptr(w), stream_ptr()), "sg_pamr_affinity")
+    return w
+
+
+@on_tensor_device
+def pamr_step(weights, logits, dilations):
+    """sg_pamr_step: one refinement step, weights [8D,H,W] + logits [Q,H,W] -> new logits [Q,H,W]."""
+    lib = _lib.load()
+    weights, logits = _f32(weights), _f32(logits)
+    _require_gpu(weights, logits)
+    d, arr = pamr_dilations(dilations)
+    Q, H, W = (int(x) for x in logits.shape)
+    if tuple(weights.shape) != (8 * len(d), H, W):
+        raise ValueError(f"pamr_step: weights {tuple(weights.shape)} do not fit {len(d)} dilations on logits {tuple(logits.shape)}")
+    out = torch.empty_like(logits)
+    check(lib.sg_pamr_step(ptr(weights), ptr(logits), ptr(out), Q, H, W, arr, len(d), stream_ptr()), "sg_pamr_step")
+    return out
+
+
+@on_tensor_device
+def pamr(logits, guide, steps: int, dilations=(8, 16), inplace: bool = False):
+    """sg_pamr: logits [Q,H,W] refined by ``steps`` PAMR steps under guide f32 [3,H,W] (the normalised image at the logits' size).
+    Returns a refined copy, or ``logits`` itself, refined where it lies, with ``inplace`` (a contiguous f32 device tensor then).
+    ``steps = 0`` returns the input values."""
+    lib = _lib.load()
+    steps = int(steps)
+    if not 0 <= steps <= PAMR_MAX_STEPS:
+        raise ValueError(f"pamr: steps={steps} outside [0, {PAMR_MAX_STEPS}]")
+    _pamr_args(logits, guide)
+    if inplace:
+        if logits.dtype != torch.float32 or not logits.is_contiguous():
+            raise ValueError("pamr: inplace needs a contiguous f32 tensor")
+        out = logits
+    else:
+        out = _f32(logits).clone()
+    guide = _f32(guide)
+    d, arr = pamr_dilations(dilations)
+    Q, H, W = (int(x) for x in out.shape)
+    if steps == 0:
+        return out
+    buf = scratch(lib.sg_pamr_workspace_bytes(Q, H, W, len(d)), out.device)
+    sp, sn = _aligned(buf)
+    check(lib.sg_pamr(ptr(guide), ptr(out), Q, H, W, arr, len(d), steps, sp, sn, stream_ptr()), "sg_pamr")
+    return out
+
+
 def _same_pixels(a, b) -> bool:
     """Equal shapes up to leading singleton dimensions ([1,H,W] labels against [H,W] truth; flat buffers against flat buffers)."""
     sa, sb = list(a.shape), list(b.shape)

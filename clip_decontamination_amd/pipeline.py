@@ -320,17 +320,33 @@ PROB_HEADS = LABEL_HEADS
 PROB_HEAD_AUTO_FUSED_BEYOND_MAX_Q = False
 
 
+PAMR_TILE_GROUP = ("PAMR under tile_group sharding is not built: a rank's canvas band would need a halo of pamr_steps * max(pamr_stride) "
+                   "rows of its neighbours' logits; run PAMR on whole images per rank")
+
+
 class SegPipeline:
+    pamr_steps, pamr_stride = 0, (8, 16)      # PAMR off unless the constructor says otherwise
+
     def __init__(self, net: HipCLIP, text: torch.Tensor, query_idx: torch.Tensor, model_type: str = "SegEarth",
                  ignore_residual: bool = True, cls_token_lambda: float = 0.0, global_debias_factor: float = 0.0,
                  logit_scale: float = 50.0, prob_thd: float = 0.0, bg_idx: int = 0, apply_similarity_enhancement: bool = False,
                  upsampler=None, tiles_per_launch: int = 32, cross_tile_fusion: Optional[dict] = None, apply_ctd: bool = False,
                  tile_group=None, apply_layer_fusion: bool = False, layer_fusion_lambda: float = 0.5, label_head: str = "auto",
-                 prob_head: str = "auto"):
+                 prob_head: str = "auto", pamr_steps: int = 0, pamr_stride=(8, 16)):
         if label_head not in LABEL_HEADS:
             raise ValueError(f"label_head must be one of {LABEL_HEADS}, got {label_head!r}")
         if prob_head not in PROB_HEADS:
             raise ValueError(f"prob_head must be one of {PROB_HEADS}, got {prob_head!r}")
+        # PAMR (pixel-adaptive mask refinement, sg_pamr): ``pamr_steps`` refinement steps over the dilations ``pamr_stride`` on the stitched
+        # logits, after the resize to ori_shape and before the post-process; 0 = off (the upstream option names).  With PAMR on, every
+        # tail that returns labels or probabilities takes the canvas route whatever label_head / prob_head say: stitch, the resize if any,
+        # PAMR, post-process.  ``forward_slide`` / ``forward_slide_many`` / ``forward_feature`` return the unrefined logits.
+        self.pamr_steps = int(pamr_steps)
+        self.pamr_stride = ops.pamr_dilations(pamr_stride)[0]
+        if not 0 <= self.pamr_steps <= ops.PAMR_MAX_STEPS:
+            raise ValueError(f"pamr_steps must lie in [0, {ops.PAMR_MAX_STEPS}], got {pamr_steps!r}")
+        if self.pamr_steps > 0 and tile_group is not None:
+            raise ValueError(PAMR_TILE_GROUP)
         # the tail that returns class probabilities too (``probs_from_tiles``): "canvas" = stitch + postprocess, "fused" = sg_prob_head
         # (no canvas, any Q, the same bytes), "auto" = see ``fused_prob_head``
         self.prob_head = prob_head
@@ -366,30 +382,57 @@ class SegPipeline:
 
     def fused_label_head(self) -> bool:
         """Whether the labels-only tail runs the fused head (sg_label_head) instead of the canvas path."""
+        if getattr(self, "pamr_steps", 0) > 0:                 # PAMR refines the canvas: there has to be one
+            return False
         mode = getattr(self, "label_head", "auto")
         return mode == "fused" or (mode == "auto" and self.num_queries > ops.POSTPROCESS_MAX_Q)
 
-    def labels_from_tiles(self, tile_logits, windows, up_hw, pad_tl, canvas_hw):
+    def refine(self, canvas: torch.Tensor, guide: torch.Tensor) -> torch.Tensor:
+        """PAMR on one image's logits [Q,H,W], in place where they are a contiguous f32 tensor.  ``guide``: the image (u8 [H,W,3] or
+        normalised f32 [3,H,W]); at another size than the logits (an ``ori_shape`` resize) its planes are resized by the same
+        ``resize_bilinear``.  Returns the refined logits; with ``pamr_steps = 0`` the logits as they came."""
+        if self.pamr_steps <= 0:
+            return canvas
+        g = ops.scene_planes(guide)
+        if tuple(g.shape[1:]) != tuple(canvas.shape[1:]):
+            g = ops.resize_bilinear(g, tuple(canvas.shape[1:]))
+        inplace = canvas.dtype == torch.float32 and canvas.is_contiguous()
+        return ops.pamr(canvas, g, self.pamr_steps, self.pamr_stride, inplace=inplace)
+
+    def _canvas_tail(self, tile_logits, windows, up_hw, pad_tl, canvas_hw, guide, want_probs: bool):
+        """stitch -> PAMR (when on; ``guide`` = the image of this canvas) -> post-process."""
+        canvas = self._stitch(tile_logits, windows, up_hw, pad_tl, canvas_hw)
+        if self.pamr_steps > 0:
+            if guide is None:
+                raise ValueError("PAMR needs the image of the canvas as guidance: pass guide= (a canvas band has none: " + PAMR_TILE_GROUP + ")")
+            canvas = self.refine(canvas, guide)
+        return self.postprocess(canvas, want_probs=want_probs)
+
+    def labels_from_tiles(self, tile_logits, windows, up_hw, pad_tl, canvas_hw, guide=None):
         """Tile logits [T,Q,gh,gw] + windows [T,4] -> labels int64 [1,H,W]: the labels-only tail of every path that returns no
-        canvas and no probabilities.  A canvas band is a canvas with shifted windows."""
+        canvas and no probabilities.  A canvas band is a canvas with shifted windows.  With PAMR on this is the canvas route, refined
+        under ``guide`` (the scene)."""
         if self.fused_label_head():
             return ops.label_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, self.query_idx, self.num_classes, self.logit_scale,
                                   self.prob_thd, self.bg_idx)
-        return self.postprocess(self._stitch(tile_logits, windows, up_hw, pad_tl, canvas_hw), want_probs=False)[1]
+        return self._canvas_tail(tile_logits, windows, up_hw, pad_tl, canvas_hw, guide, False)[1]
 
     def fused_prob_head(self) -> bool:
         """Whether the tail that returns probabilities and labels runs the fused head (sg_prob_head) instead of the canvas path.  "auto"
         is the canvas up to 64 queries and follows the measurement beyond (PROB_HEAD_AUTO_FUSED_BEYOND_MAX_Q)."""
+        if getattr(self, "pamr_steps", 0) > 0:
+            return False
         mode = getattr(self, "prob_head", "auto")
         return mode == "fused" or (mode == "auto" and PROB_HEAD_AUTO_FUSED_BEYOND_MAX_Q and self.num_queries > ops.POSTPROCESS_MAX_Q)
 
-    def probs_from_tiles(self, tile_logits, windows, up_hw, pad_tl, canvas_hw):
+    def probs_from_tiles(self, tile_logits, windows, up_hw, pad_tl, canvas_hw, guide=None):
         """Tile logits [T,Q,gh,gw] + windows [T,4] -> (probs f32 [K,H,W], labels int64 [1,H,W]): the tail of every path that returns
-        class probabilities at the scene's own size.  Both routes return the same bytes."""
+        class probabilities at the scene's own size.  Both routes return the same bytes.  With PAMR on this is the canvas route, refined
+        under ``guide`` (the scene)."""
         if self.fused_prob_head():
             return ops.prob_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, self.query_idx, self.num_classes, self.logit_scale,
                                  self.prob_thd, self.bg_idx)
-        return self.postprocess(self._stitch(tile_logits, windows, up_hw, pad_tl, canvas_hw), want_probs=True)
+        return self._canvas_tail(tile_logits, windows, up_hw, pad_tl, canvas_hw, guide, True)
 
     def _pre_head(self, tok, cls):
         """Global debias (+ CTD) when they cannot stay fused in the logits kernel: returns (tokens, remaining debias factor)."""
@@ -541,7 +584,10 @@ class SegPipeline:
         """The whole path to labels for one scene.  Sharded: every rank computes its tiles, stitches + labels ITS band; only the
         int64 label band (8 B per pixel instead of 4Q) is gathered.  -> labels [1,H,W] (or (band labels, first row) when
         ``gather_labels`` is False).  ``want_probs``: (probs [K,H,W], labels [1,H,W]) through ``probs_from_tiles``; not with tile
-        sharding."""
+        sharding.  With PAMR on (``pamr_steps``) the canvas is stitched, refined under the scene and post-processed, whatever
+        label_head / prob_head say; tile sharding is then refused (a band would need a halo of its neighbours' rows)."""
+        if self.pamr_steps > 0 and (group is not None or self.tile_group is not None):
+            raise ValueError(PAMR_TILE_GROUP)
         group = resolve_tile_group(group if group is not None else self.tile_group)
         if want_probs and group is not None:
             raise ValueError("segment_scene: class probabilities under tile_group sharding are not built; use forward_slide + postprocess")
@@ -550,8 +596,8 @@ class SegPipeline:
             tl = self.tile_logits(scene, wins, tile_hw, grid_of_tiles=grid)
             win_dev = torch.tensor(wins, dtype=torch.int32, device=self.device)
             if want_probs:
-                return self.probs_from_tiles(tl, win_dev, up_hw, pad_tl, (H, W))
-            return self.labels_from_tiles(tl, win_dev, up_hw, pad_tl, (H, W))
+                return self.probs_from_tiles(tl, win_dev, up_hw, pad_tl, (H, W), guide=scene)
+            return self.labels_from_tiles(tl, win_dev, up_hw, pad_tl, (H, W), guide=scene)
         tiles, w_band, up_hw, pad_tl, hw, y0, yb = self.sharded_band_tiles(scene, stride, crop, group)
         if hw[0] > 0:
             lab = self.labels_from_tiles(tiles, w_band, up_hw, pad_tl, hw)
@@ -707,8 +753,14 @@ class SegPipeline:
         group and no canvas.  Probabilities at the images' own sizes with the fused probability head selected (``prob_head``): one
         sg_prob_head_multi launch per flush group, no canvas, any number of queries (the planner counts 4K + 8 bytes per pixel then).
         Otherwise probabilities or a resize keep the canvas; beyond 64 queries they then go image by image through ``ops.postprocess``
-        (its wide form) on the group's canvases."""
+        (its wide form) on the group's canvases.
+        With PAMR on (``pamr_steps``) every group takes the canvas route: a flush group whose images all keep their size (and Q <= 64)
+        has each canvas view refined in place and then the one sg_postprocess_multi launch; a group holding an image with another
+        ``ori_shape`` goes image by image: resize, PAMR, post-process."""
         no_resize = ori_shapes is None or all(o is None for o in ori_shapes)
+        if self.pamr_steps > 0:
+            yield from self._label_groups_pamr(scenes, stride, crop, want_probs, ori_shapes)
+            return
         if want_probs and self.fused_prob_head() and (no_resize or all(
                 o is None or tuple(o) == _scene_hw(s)
                 for o, s in zip(ori_shapes, [scenes] if torch.is_tensor(scenes) and scenes.dim() == 3 else scenes))):
@@ -744,9 +796,32 @@ class SegPipeline:
                                                    self.bg_idx, ohw, want_probs, flat_labels=True)
             yield idx, prb, lab, flat
 
+    def _label_groups_pamr(self, scenes, stride, crop, want_probs, ori_shapes):
+        """``label_groups`` with PAMR on (see there)."""
+        single = torch.is_tensor(scenes) and scenes.dim() == 3
+        for idx, canvases, views in self._packed_canvases(scenes, stride, crop):
+            imgs = [scenes if single else scenes[k] for k in idx]
+            chw = [tuple(c.shape[1:]) for c in views]
+            ohw = [chw[n] if ori_shapes is None or ori_shapes[k] is None else tuple(ori_shapes[k]) for n, k in enumerate(idx)]
+            if ohw == chw and self.num_queries <= ops.POSTPROCESS_MAX_Q:
+                for c, im in zip(views, imgs):
+                    self.refine(c, im.to(self.device))
+                yield (idx,) + tuple(ops.postprocess_multi(canvases, chw, self.query_idx, self.num_classes, self.logit_scale, self.prob_thd,
+                                                           self.bg_idx, ohw, want_probs, flat_labels=True))
+                continue
+            prb, lab = [], []
+            for c, im, hw in zip(views, imgs, ohw):
+                if hw != tuple(c.shape[1:]):
+                    c = ops.resize_bilinear(c, hw)
+                p_, l_ = self.postprocess(self.refine(c, im.to(self.device)), want_probs=want_probs)
+                prb.append(p_); lab.append(l_.reshape(-1))
+            flat = torch.cat(lab)
+            pix = ops._prefix(l_.numel() for l_ in lab)
+            yield idx, prb, [flat[pix[n]:pix[n + 1]].view(1, *ohw[n]) for n in range(len(lab))], flat
+
     def segment_scenes(self, scenes, stride, crop, want_probs: bool = False, ori_shapes=None):
         """``label_groups`` collected per image -> list of labels [1,H,W], or (list of probs [K,H,W], list of labels) with
-        ``want_probs``."""
+        ``want_probs``.  With PAMR on every image's canvas is refined before its post-process (``label_groups``)."""
         probs: List[Optional[torch.Tensor]] = []
         labels: List[Optional[torch.Tensor]] = []
         for idx, prb, lab, _ in self.label_groups(scenes, stride, crop, want_probs, ori_shapes):

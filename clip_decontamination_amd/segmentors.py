@@ -130,8 +130,9 @@ class _HipSegmentorBase(_Base):
                slide_crop, cls_token_lambda, bg_idx, apply_sim_feat_up, sim_feat_up_cfg, global_debias_factor=0.0,
                checkpoint=None, text_features=None, text_encoder: Optional[Callable] = None, precision="f16x2",
                synthetic_ok=False, tiles_per_launch=None, jbu_checkpoint_ok=True, tokenizer: Optional[Callable] = None, tile_group=None,
-               label_head="auto", prob_head="auto"):
-        from .pipeline import LABEL_HEADS, PROB_HEADS
+               label_head="auto", prob_head="auto", pamr_steps=0, pamr_stride=(8, 16)):
+        from . import ops
+        from .pipeline import LABEL_HEADS, PAMR_TILE_GROUP, PROB_HEADS
         if label_head not in LABEL_HEADS:
             raise ValueError(f"label_head must be one of {LABEL_HEADS}, got {label_head!r}")
         if prob_head not in PROB_HEADS:
@@ -143,6 +144,14 @@ class _HipSegmentorBase(_Base):
         # number of queries), "auto" = the canvas wherever it works (Q <= 64) and the fused head beyond
         self.label_head = label_head
         self.tile_group = tile_group                         # opt-in tile sharding (pipeline.resolve_tile_group); None = off
+        # PAMR (the upstream option names): ``pamr_steps`` refinement steps over the dilations ``pamr_stride`` on the stitched logits, after
+        # the resize to ori_shape and before the post-process; 0 = off.  With PAMR on every tail that returns labels or probabilities takes
+        # the canvas route, whatever label_head / prob_head say (SegPipeline).
+        self.pamr_steps, self.pamr_stride = int(pamr_steps), ops.pamr_dilations(pamr_stride)[0]
+        if not 0 <= self.pamr_steps <= ops.PAMR_MAX_STEPS:
+            raise ValueError(f"pamr_steps must lie in [0, {ops.PAMR_MAX_STEPS}], got {pamr_steps!r}")
+        if self.pamr_steps > 0 and tile_group is not None:
+            raise ValueError(PAMR_TILE_GROUP)
         if clip_type == "BLIP":
             raise NotImplementedError("clip_type='BLIP' is a different backbone (vendored BLIP) and is out of scope for the HIP path")
         self.clip_type, self.vit_type, self.model_type = clip_type, vit_type, model_type
@@ -245,7 +254,8 @@ class _HipSegmentorBase(_Base):
                            cross_tile_fusion=getattr(self, "cross_tile_fusion_cfg", None), apply_ctd=getattr(self, "apply_ctd", False),
                            tile_group=getattr(self, "tile_group", None), apply_layer_fusion=getattr(self, "apply_layer_fusion", False),
                            layer_fusion_lambda=getattr(self, "layer_fusion_lambda", 0.5), label_head=getattr(self, "label_head", "auto"),
-                           prob_head=getattr(self, "prob_head", "auto"))
+                           prob_head=getattr(self, "prob_head", "auto"), pamr_steps=getattr(self, "pamr_steps", 0),
+                           pamr_stride=getattr(self, "pamr_stride", (8, 16)))
 
     def forward_feature(self, img, logit_size=None, tile_h_idx=None, tile_w_idx=None):
         """Reference segmentor.py:286-392.  img [B,3,H,W] -> logits [B,Q,h,w]."""
@@ -269,7 +279,9 @@ class _HipSegmentorBase(_Base):
 
     @torch.no_grad()
     def predict(self, inputs, data_samples):
-        """Reference segmentor.py:453-473."""
+        """Reference segmentor.py:453-473.  With PAMR on (``pamr_steps > 0``) the stitched logits of every image are refined under that
+        image (resized to ``ori_shape`` where the logits are) before the post-process, on the canvas route whatever label_head /
+        prob_head say; whole-image inference (``slide_crop <= 0``) likewise."""
         if data_samples is not None:
             batch_img_metas = [data_sample.metainfo for data_sample in data_samples]
         else:
@@ -298,6 +310,11 @@ class _HipSegmentorBase(_Base):
             seg_logits = self.forward_slide(inputs, batch_img_metas, self.slide_stride, self.slide_crop)
         else:
             seg_logits = self.forward_feature(inputs, batch_img_metas[0]["ori_shape"])
+        if getattr(self, "pamr_steps", 0) > 0:
+            pipe = self._pipeline()
+            seg_logits = seg_logits.float().contiguous()
+            for b in range(seg_logits.shape[0]):                             # in place: each image's logits are a contiguous f32 slice
+                pipe.refine(seg_logits[b], inputs[b])
         return self.postprocess_result(seg_logits, data_samples)
 
     @torch.no_grad()
@@ -311,7 +328,8 @@ class _HipSegmentorBase(_Base):
         canvases still come from the packed launches, the probabilities from sg_postprocess_wide per image); ``data_samples=None`` takes the fused
         label head, one launch per flush group.  With the fused probability head selected (``prob_head``) and every ``ori_shape`` equal
         to its image's size, data samples are filled from one sg_prob_head_multi launch per flush group for any number of queries: no
-        canvas, and nothing image by image."""
+        canvas, and nothing image by image.  With PAMR on (``pamr_steps > 0``) every flush group takes the canvas route and each image's
+        canvas is refined before the post-process (SegPipeline.label_groups)."""
         batch = torch.is_tensor(inputs)
         imgs = inputs.float() if batch else [x[0].float() if x.dim() == 4 else x.float() for x in inputs]
         n = imgs.shape[0] if batch else len(imgs)
@@ -348,7 +366,7 @@ class _HipSegmentorBase(_Base):
         per flush group over its flat label buffer, and only the (K+1) x (K+1) table comes back.  Whole-image inference
         (``slide_crop <= 0``) goes image by image through ``predict``.  ``tile_group`` sharding is refused here (counting each rank's
         band against the matching rows of the truth is not built yet: DESIGN.md section 8); score per rank over whole images and call
-        ``metric.reduce(group)``."""
+        ``metric.reduce(group)``.  With PAMR on (``pamr_steps > 0``) the labels come from the refined canvases (SegPipeline.label_groups)."""
         from .metrics import IoUMetric
         if getattr(self, "tile_group", None) is not None:
             raise ValueError("evaluate: tile_group sharding is not supported (each rank would have to count its own band against the "
@@ -467,7 +485,8 @@ class SegmentorEx(_HipSegmentorBase):
                  similarity_enhancement_cfg=None, result_dir=None, heatmap_dir=None,
                  # -- drop-in extras (see module docstring) --
                  checkpoint=None, text_features=None, text_encoder=None, precision="f16x2", synthetic_ok=False, tiles_per_launch=None,
-                 tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, pack_images=False, label_head="auto", prob_head="auto"):
+                 tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, pack_images=False, label_head="auto", prob_head="auto",
+                 pamr_steps=0, pamr_stride=(8, 16)):
         data_preprocessor = SegDataPreProcessor(mean=list(Wt.PIXEL_MEAN), std=list(Wt.PIXEL_STD), bgr_to_rgb=True)
         super().__init__(data_preprocessor=data_preprocessor)
         if model_type == "GEM":
@@ -476,7 +495,7 @@ class SegmentorEx(_HipSegmentorBase):
         visual = self._setup(clip_type, vit_type, model_type, name_path, device, ignore_residual, prob_thd, logit_scale, slide_stride,
                              slide_crop, cls_token_lambda, bg_idx, _to_bool(apply_sim_feat_up), sim_feat_up_cfg, global_debias_factor,
                              checkpoint, text_features, text_encoder, precision, synthetic_ok, tiles_per_launch, tokenizer=tokenizer,
-                             tile_group=tile_group, label_head=label_head, prob_head=prob_head)
+                             tile_group=tile_group, label_head=label_head, prob_head=prob_head, pamr_steps=pamr_steps, pamr_stride=pamr_stride)
         # opt-in extra: kwargs of the reference's CrossTileFusion (cross_tile_fusion.py:24-60), which the reference never calls (R2)
         self.cross_tile_fusion_cfg = cross_tile_fusion_cfg
         self.apply_ctd = _to_bool(apply_ctd)                                # segmentor.py:184-194, 339-365: DBSCAN + cluster debias, on the device here
@@ -511,7 +530,7 @@ class Segmentor(_HipSegmentorBase):
                  sim_feat_up_cfg=dict(model_name="jbu_one", model_path="your/model/path"),
                  checkpoint=None, text_features=None, text_encoder=None, precision="f16x2", synthetic_ok=False, tiles_per_launch=None,
                  tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, apply_outlier_suppression=False, outlier_suppression_cfg=None,
-                 pack_images=False, label_head="auto", prob_head="auto"):
+                 pack_images=False, label_head="auto", prob_head="auto", pamr_steps=0, pamr_stride=(8, 16)):
         data_preprocessor = SegDataPreProcessor(mean=list(Wt.PIXEL_MEAN), std=list(Wt.PIXEL_STD), bgr_to_rgb=True)
         super().__init__(data_preprocessor=data_preprocessor)
         if model_type == "GEM" and cls_token_lambda != 0:
@@ -519,7 +538,7 @@ class Segmentor(_HipSegmentorBase):
         self._setup(clip_type, vit_type, model_type, name_path, device, ignore_residual, prob_thd, logit_scale, slide_stride,
                     slide_crop, cls_token_lambda, bg_idx, apply_sim_feat_up, sim_feat_up_cfg, 0.0,
                     checkpoint, text_features, text_encoder, precision, synthetic_ok, tiles_per_launch, tokenizer=tokenizer,
-                    tile_group=tile_group, label_head=label_head, prob_head=prob_head)
+                    tile_group=tile_group, label_head=label_head, prob_head=prob_head, pamr_steps=pamr_steps, pamr_stride=pamr_stride)
         # opt-in extra: kwargs of the reference's CrossTileFusion (cross_tile_fusion.py:24-60), which the reference never calls (R2)
         self.cross_tile_fusion_cfg = cross_tile_fusion_cfg
         self.output_cls_token = cls_token_lambda != 0

@@ -587,6 +587,41 @@ typedef enum { SG_GT_U8 = 0, SG_GT_I64 = 1 } sg_gt_format;
 int sg_confusion_accumulate(const int64_t* labels, const void* gt, int gt_format, int64_t n_pixels, int K, int ignore_index,
                             int reduce_zero_label, int64_t* table, sg_stream s);
 
+/* ---- PAMR: Pixel-Adaptive Mask Refinement of the stitched logits (Araslanov & Roth 2020) ----------------------------------------
+ * The optional last stage of the training-free open-vocabulary segmenters (their pamr_steps / pamr_stride options): the [Q,H,W] logits
+ * are averaged `steps` times over image-adaptive neighbourhoods, which snaps the patch-grid logits to image edges.  It comes after the
+ * resize to ori_shape (the guidance resized to the same size with the same bilinear resize) and before the logit scale and the softmax
+ * of the post-process.  The definition:
+ *   guide g [3,H,W] f32 (the normalised image: what predict() receives; for a u8 scene (u - mean) / std as the ingest computes it),
+ *   logits m_0 [Q,H,W] f32, dilations d_1..d_D, steps.
+ *   Offsets o_1..o_8 = (-1,-1) (-1,0) (-1,1) (0,-1) (0,1) (1,-1) (1,0) (1,1) as (dy,dx).  Neighbour k = (i-1)*8 + j of pixel p = (y,x)
+ *   is n_k(p) = (clamp(y + d_i dy_j, 0, H-1), clamp(x + d_i dx_j, 0, W-1)): replicate padding; a dilation may exceed H or W.
+ *   Weights, once per image:
+ *     sigma_c(p) = the unbiased standard deviation (divisor 9D - 1) of the 9D samples g_c(p + d_i (dy,dx)), i = 1..D, dy, dx in {-1,0,1},
+ *                  clamped coordinates; the centre is among them D times.  Two passes (the mean, then the deviations), taken on the
+ *                  differences to the centre value, so that a flat window gives exactly 0.
+ *     a_k(p)     = (1/3) sum_c -|g_c(p) - g_c(n_k(p))| / (1e-8 + 0.1 sigma_c(p))
+ *     w_k(p)     = softmax over k = 1..8D of a_k(p), the maximum subtracted.
+ *   Steps, `steps` times: m_{t+1}[q,p] = sum_k w_k(p) m_t[q, n_k(p)], k in ascending order.  steps = 0 is the identity.
+ * Conditioning: where a float image's local spread is at the rounding level of its own values without being exactly flat, w is
+ * ill-conditioned in any f32 evaluation (the differences g(p) - g(n_k) and sigma are then a few units of the inputs' last place, and one
+ * such unit moves a_k by O(1)); on normalised u8 images a window is either exactly flat or spread by at least one grey level.
+ *   sg_pamr_workspace_bytes : the weights [8D,H,W] f32 (rounded up to 256 bytes) plus one ping-pong canvas [Q,H,W] f32; 0 for sizes
+ *                             the entries refuse
+ *   sg_pamr_affinity        : guide -> weights [8D,H,W] f32
+ *   sg_pamr_step            : one step, weights + in [Q,H,W] -> out [Q,H,W]; in == out is refused
+ *   sg_pamr                 : affinity + `steps` steps; the result is in logits_inout for odd and even `steps` alike (workspace 256-byte
+ *                             aligned; not read when steps == 0)
+ * `dilations` is a HOST array of n_dil ints, passed to the kernels by value.  Limits: 1 <= n_dil <= 8, 1 <= d <= 64, 0 <= steps <= 64,
+ * Q, H, W >= 1 (any Q; at most 2^38 pixels).  Every refusal (a null pointer, a limit, in == out, a workspace too small: SG_ERR_STATE)
+ * happens before any device work.  No atomics; a pixel's result depends on that pixel's lane alone: repeats are byte-identical.
+ * Bound by HBM and L2: a step moves (2Q + 8D) * 4 bytes per pixel from and to HBM, neighbour re-reads are served by the caches. */
+size_t sg_pamr_workspace_bytes(int Q, int H, int W, int n_dil);
+int sg_pamr_affinity(const float* guide, int H, int W, const int* dilations, int n_dil, float* weights, sg_stream s);
+int sg_pamr_step(const float* weights, const float* in, float* out, int Q, int H, int W, const int* dilations, int n_dil, sg_stream s);
+int sg_pamr(const float* guide, float* logits_inout, int Q, int H, int W, const int* dilations, int n_dil, int steps, void* workspace,
+            size_t workspace_bytes, sg_stream s);
+
 #ifdef __cplusplus
 }
 #endif
