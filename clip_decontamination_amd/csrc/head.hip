@@ -592,6 +592,105 @@ __global__ __launch_bounds__(256) void label_head_multi_kernel(const float* __re
                    labels + ib.off, conf ? conf + ib.off : nullptr);
 }
 
+// ---- fused top-k head: stitch -> softmax -> synonym merge -> the k best classes with their probabilities, any Q ------------------------
+// label_head_block with a sorted list of KTOP (value, class) pairs in place of the single best pair; the per-chunk statements (scaled
+// logit, chunk maximum, rescale of the sum, sum of exp) are that function's, copied, so that slot 0 carries sg_label_head's label and
+// conf byte for byte.  label_head_block itself is not shared with this one: its machine code stays what it is.
+//   The list: larger value first, among equal values the lower class first; an empty slot is (-inf, INT_MAX) and therefore sorts last.
+//   Every slot is addressed with a compile-time index in fully unrolled loops (a run-time index would send the arrays to scratch, as
+//   class_tail's comment has it).  A query (v, c) with K != Q first looks for a slot that already holds class c and raises it to
+//   max(v_slot, v): a class's value is the maximum over its queries, which is the synonym max of the class probabilities because softmax
+//   is monotone.  Otherwise it replaces the last slot if it precedes it.  Either way at most one slot is out of place afterwards and it
+//   can only have moved up, so one bottom-up pass of KTOP - 1 compare-exchanges restores the order.  With K == Q every class has one
+//   query and the search is skipped (block-uniform).
+// Outputs are planes [k,H,W] of the image: classes int32 (-1 for a slot no class filled) and probs = expf(v_j - vmax) / sum, the
+// expression of label_head_block's conf (0 for an unfilled slot).  No atomics, no LDS beyond the candidate list, nothing proportional
+// to Q * H * W; every element is written by its pixel's own thread in an order fixed by (pixel, query index).
+constexpr int TOPK_MAX = 8;
+template <int KTOP>
+__device__ __forceinline__ void topk_head_block(const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
+                                                const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw,
+                                                int up_h, int up_w, int pad_t, int pad_l, int H, int W, int bx0, int by0,
+                                                const int32_t* __restrict__ query_idx, int K, float logit_scale, int k,
+                                                int32_t* __restrict__ classes, float* __restrict__ probs) {
+  float vmax = -INFINITY, sum = 0.f;
+  float tv[KTOP];
+  int tc[KTOP];
+#pragma unroll
+  for (int j = 0; j < KTOP; ++j) { tv[j] = -INFINITY; tc[j] = INT_MAX; }
+  const bool merge = K != Q;
+  stitch_block(tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, bx0, by0,
+               [&](int, int, int q0, float (&acc)[ST_QC], float cnt) {
+#pragma clang fp contract(off)        // the scaled logit is rounded before the subtraction, as postprocess_kernel compiles it
+                 float cm = -INFINITY;
+#pragma unroll
+                 for (int k = 0; k < ST_QC; ++k)
+                   if (q0 + k < Q) { acc[k] = (cnt > 0.f ? acc[k] / cnt : 0.f) * logit_scale; cm = fmaxf(cm, acc[k]); }
+                 if (cm > vmax) { sum *= expf(vmax - cm); vmax = cm; }            // the first chunk: sum = 0 * exp(-inf) = 0
+#pragma unroll
+                 for (int k = 0; k < ST_QC; ++k)
+                   if (q0 + k < Q) {
+                     sum += expf(acc[k] - vmax);
+                     const float v = acc[k];
+                     const int c = merge ? query_idx[q0 + k] : q0 + k;
+                     if (c < 0 || c >= K) continue;
+                     bool held = false;
+                     if (merge) {
+#pragma unroll
+                       for (int j = 0; j < KTOP; ++j)
+                         if (tc[j] == c) { held = true; tv[j] = fmaxf(tv[j], v); }
+                     }
+                     if (!held && (v > tv[KTOP - 1] || (v == tv[KTOP - 1] && c < tc[KTOP - 1]))) { tv[KTOP - 1] = v; tc[KTOP - 1] = c; }
+#pragma unroll
+                     for (int j = KTOP - 1; j > 0; --j) {
+                       const bool up = tv[j] > tv[j - 1] || (tv[j] == tv[j - 1] && tc[j] < tc[j - 1]);
+                       const float fv = tv[j]; const int fc = tc[j];
+                       tv[j] = up ? tv[j - 1] : fv; tc[j] = up ? tc[j - 1] : fc;
+                       tv[j - 1] = up ? fv : tv[j - 1]; tc[j - 1] = up ? fc : tc[j - 1];
+                     }
+                   }
+               });
+  const int x = bx0 + (threadIdx.x & 63);
+  const int y = __builtin_amdgcn_readfirstlane(by0 + (threadIdx.x >> 6));
+  if (y >= H || x >= W) return;
+  const int64_t HW = (int64_t)H * W, o = (int64_t)y * W + x;
+#pragma unroll
+  for (int j = 0; j < KTOP; ++j)
+    if (j < k) {
+      const bool filled = tc[j] != INT_MAX;
+      const float p = expf(tv[j] - vmax) / sum;
+      classes[j * HW + o] = filled ? tc[j] : -1;
+      probs[j * HW + o] = filled ? p : 0.f;
+    }
+}
+
+template <int KTOP>
+__global__ __launch_bounds__(256) void topk_head_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows, int T,
+                                                        int Q, int gh, int gw, int up_h, int up_w, int pad_t, int pad_l, int H, int W,
+                                                        const int32_t* __restrict__ query_idx, int K, float logit_scale, int k,
+                                                        int32_t* __restrict__ classes, float* __restrict__ probs) {
+  topk_head_block<KTOP>(tile_logits, windows, nullptr, 0, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, blockIdx.x * 64, blockIdx.y * 4,
+                        query_idx, K, logit_scale, k, classes, probs);
+}
+
+// The tiles of N images (sg_stitch_multi's descriptors); the planes [k,H,W] of image n at k * out_offset[n] elements of the flat outputs
+// (sg_prob_head_multi's layout with k in place of K).
+template <int KTOP>
+__global__ __launch_bounds__(256) void topk_head_multi_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows,
+                                                              const int32_t* __restrict__ tile_image, int T, int Q, int gh, int gw,
+                                                              int up_h, int up_w, int pad_t, int pad_l,
+                                                              const int32_t* __restrict__ image_hw, const int32_t* __restrict__ image_tiles,
+                                                              const int64_t* __restrict__ out_offset, const int64_t* __restrict__ block_prefix,
+                                                              int N, int64_t out_pixels, const int32_t* __restrict__ query_idx, int K,
+                                                              float logit_scale, int k, int32_t* __restrict__ classes,
+                                                              float* __restrict__ probs) {
+  ImageBlock ib;
+  if (!image_block(image_hw, image_tiles, out_offset, block_prefix, N, T, 1, out_pixels, ib)) return;   // k * (off + H * W) <= k * out_pixels
+  topk_head_block<KTOP>(tile_logits + (int64_t)ib.t_first * Q * gh * gw, windows + (int64_t)ib.t_first * 4, tile_image + ib.t_first, ib.n,
+                        ib.n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, ib.H, ib.W, ib.bx0, ib.by0, query_idx, K, logit_scale, k,
+                        classes + k * ib.off, probs + k * ib.off);
+}
+
 // ---- postprocess for any Q: several passes over the canvas, nothing held per query ------------------------------------------------
 // Pass 1 the maximum, pass 2 the sum (postprocess_kernel's order), pass 3 the per-class maximum, written through probs[class(q)] by the
 // pixel's own thread.  A class starts at what postprocess_kernel's `any_other` rule gives a class without queries: 0 when some query
@@ -1095,6 +1194,45 @@ extern "C" int sg_prob_head_multi(const float* tile_logits, const int32_t* windo
   hipLaunchKernelGGL(kern, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q, gh, gw, up_h, up_w,
                      pad_t, pad_l, image_hw, image_tiles, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale, prob_thd, bg_idx,
                      probs, labels);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+// KTOP of the top-k head: the next power of two of k; the kernel writes the first k slots.
+#define SG_TOPK_HEAD_DISPATCH(kernel, k) ((k) <= 1 ? kernel<1> : ((k) <= 2 ? kernel<2> : ((k) <= 4 ? kernel<4> : kernel<TOPK_MAX>)))
+static_assert(TOPK_MAX == SG_TOPK_MAX, "the header's SG_TOPK_MAX is the largest instantiated list");
+
+extern "C" int sg_topk_head(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t,
+                            int pad_l, int H, int W, const int32_t* query_idx, int K, float logit_scale, int k, int32_t* classes,
+                            float* probs, sg_stream s) {
+  SG_REQUIRE(tile_logits && windows && query_idx && classes && probs, "sg_topk_head: null pointer");
+  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && H > 0 && W > 0,
+             "sg_topk_head: bad shape T=%d Q=%d gh=%d gw=%d up=%dx%d H=%d W=%d", T, Q, gh, gw, up_h, up_w, H, W);
+  SG_REQUIRE(K > 0 && K <= Q, "sg_topk_head: K=%d must lie in [1, Q=%d]", K, Q);
+  SG_REQUIRE(k >= 1 && k <= SG_TOPK_MAX && k <= K, "sg_topk_head: k=%d must lie in [1, min(%d, K=%d)]", k, SG_TOPK_MAX, K);
+  SG_REQUIRE(cdiv(H, 4) < 65536, "sg_topk_head: canvas too tall for one launch");
+  auto kern = SG_TOPK_HEAD_DISPATCH(topk_head_kernel, k);
+  hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(W, 64), (unsigned)cdiv(H, 4)), dim3(256), 0, as_stream(s), tile_logits, windows, T, Q, gh, gw,
+                     up_h, up_w, pad_t, pad_l, H, W, query_idx, K, logit_scale, k, classes, probs);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_topk_head_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh, int gw,
+                                  int up_h, int up_w, int pad_t, int pad_l, const int32_t* image_hw, const int32_t* image_tiles,
+                                  const int64_t* out_offset, const int64_t* block_prefix, int N, int64_t total_blocks, int64_t out_pixels,
+                                  const int32_t* query_idx, int K, float logit_scale, int k, int32_t* classes, float* probs, sg_stream s) {
+  SG_REQUIRE(tile_logits && windows && tile_image && image_hw && image_tiles && out_offset && block_prefix && query_idx && classes && probs,
+             "sg_topk_head_multi: null pointer");
+  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && N > 0 && N <= T,
+             "sg_topk_head_multi: bad shape T=%d Q=%d gh=%d gw=%d N=%d", T, Q, gh, gw, N);
+  SG_REQUIRE(K > 0 && K <= Q, "sg_topk_head_multi: K=%d must lie in [1, Q=%d]", K, Q);
+  SG_REQUIRE(k >= 1 && k <= SG_TOPK_MAX && k <= K, "sg_topk_head_multi: k=%d must lie in [1, min(%d, K=%d)]", k, SG_TOPK_MAX, K);
+  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "sg_topk_head_multi: total_blocks=%lld outside (0, 2^31)", (long long)total_blocks);
+  SG_REQUIRE(out_pixels > 0, "sg_topk_head_multi: out_pixels=%lld holds no image", (long long)out_pixels);
+  auto kern = SG_TOPK_HEAD_DISPATCH(topk_head_multi_kernel, k);
+  hipLaunchKernelGGL(kern, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q, gh, gw, up_h, up_w,
+                     pad_t, pad_l, image_hw, image_tiles, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale, k, classes, probs);
   SG_LAUNCH_CHECK();
   return SG_OK;
 }

@@ -1,7 +1,9 @@
 """Thin torch-tensor wrappers over the C ABI (one Python function per exported op).
 
 PyTorch is plumbing here: it owns device memory and the stream; every computation happens in
-libsegearth_hip.so.  Nothing in this module falls back to torch arithmetic.
+libsegearth_hip.so.  Nothing in this module falls back to torch arithmetic.  (``topk_from_probs`` is a torch
+sort by design: it turns the [K,H,W] probabilities of the canvas route into the top-k head's outputs on the routes
+where the fused head cannot run; it replaces no kernel.)
 """
 from __future__ import annotations
 
@@ -459,6 +461,84 @@ def prob_head_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, i
     lab = [labels[pix[n]:pix[n + 1]].view(1, h, w) for n, (h, w) in enumerate(image_hw)]
     prb = [probs[K * pix[n]:K * pix[n + 1]].view(K, h, w) for n, (h, w) in enumerate(image_hw)]
     return prb, lab, labels
+
+
+TOPK_MAX = 8                                                             # SG_TOPK_MAX (include/segearth_hip.h)
+
+
+@on_tensor_device
+def topk_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, query_idx, num_classes: int, logit_scale: float, k: int):
+    """sg_topk_head: the k best classes per pixel with their probabilities, from the tile logits, without a canvas or [K,H,W] planes,
+    for any Q.  Arguments as ``label_head`` with ``k`` (1 .. min(8, K)) for the threshold -> (classes int32 [k,H,W], probs f32
+    [k,H,W]), slots in descending probability, equal values by ascending class; -1 / 0 in a slot no class filled (classes that own no
+    query never appear).  Plane 0 is ``label_head``'s label before the threshold and its conf, byte for byte."""
+    lib = _lib.load()
+    tile_logits = _f32(tile_logits)
+    windows = windows.to(device=tile_logits.device, dtype=torch.int32).contiguous()
+    _require_gpu(tile_logits)
+    T, Q, gh, gw = tile_logits.shape
+    H, W = canvas_hw
+    qi = query_idx.to(device=tile_logits.device, dtype=torch.int32).contiguous()
+    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T:
+        raise ValueError(f"topk_head: {T} tiles of {Q} queries, but {windows.numel() // 4} windows and {qi.numel()} query indices")
+    kk = max(int(k), 0)
+    classes = torch.empty(kk, H, W, dtype=torch.int32, device=tile_logits.device)
+    probs = torch.empty(kk, H, W, dtype=torch.float32, device=tile_logits.device)
+    check(lib.sg_topk_head(ptr(tile_logits), ptr(windows), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1], H, W, ptr(qi),
+                           int(num_classes), float(logit_scale), int(k), ptr(classes), ptr(probs), stream_ptr()), "sg_topk_head")
+    return classes, probs
+
+
+@on_tensor_device
+def topk_head_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, query_idx, num_classes: int,
+                    logit_scale: float, k: int):
+    """sg_topk_head_multi: ``topk_head`` for N images in one launch (arguments as ``label_head_multi`` with ``k`` for the threshold).
+    -> (list of classes int32 [k,H,W], list of probs f32 [k,H,W]): views at k * (the image's first pixel) of two flat buffers.  Equals
+    ``topk_head`` per image byte for byte."""
+    lib = _lib.load()
+    tile_logits = _f32(tile_logits)
+    _require_gpu(tile_logits)
+    dev = tile_logits.device
+    T, Q, gh, gw = tile_logits.shape
+    N, kk = len(image_hw), max(int(k), 0)
+    qi = query_idx.to(device=dev, dtype=torch.int32).contiguous()
+    windows = torch.as_tensor(windows, dtype=torch.int32).to(dev).contiguous()
+    tile_image = torch.as_tensor(tile_image, dtype=torch.int32).to(dev).contiguous()
+    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T or int(tile_image.numel()) != T or len(image_tiles) != N:
+        raise ValueError("topk_head_multi: tile logits, windows, tile_image, image descriptors and query indices disagree in size")
+    if any(f < 0 or c <= 0 or f + c > T for f, c in image_tiles):
+        raise ValueError(f"topk_head_multi: image_tiles {list(image_tiles)} leave the {T} tiles")
+    pix = _prefix(h * w for h, w in image_hw)
+    blocks = _prefix(-(-w // 64) * -(-h // 4) for h, w in image_hw)
+    i32 = torch.tensor([list(hw) for hw in image_hw] + [list(ft) for ft in image_tiles], dtype=torch.int32).to(dev)
+    i64 = torch.tensor(pix[:-1] + blocks, dtype=torch.int64).to(dev)
+    classes = torch.empty(kk * pix[-1], dtype=torch.int32, device=dev)
+    probs = torch.empty(kk * pix[-1], dtype=torch.float32, device=dev)
+    check(lib.sg_topk_head_multi(ptr(tile_logits), ptr(windows), ptr(tile_image), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1],
+                                 ptr(i32), ptr(i32[N:]), ptr(i64), ptr(i64[N:]), N, blocks[-1], pix[-1], ptr(qi), int(num_classes),
+                                 float(logit_scale), int(k), ptr(classes), ptr(probs), stream_ptr()), "sg_topk_head_multi")
+    cls = [classes[kk * pix[n]:kk * pix[n + 1]].view(kk, h, w) for n, (h, w) in enumerate(image_hw)]
+    prb = [probs[kk * pix[n]:kk * pix[n + 1]].view(kk, h, w) for n, (h, w) in enumerate(image_hw)]
+    return cls, prb
+
+
+def topk_from_probs(probs, query_idx, k: int):
+    """The canvas-route equivalent of ``topk_head`` in torch (host or device tensors): class probabilities [K,H,W] (what ``postprocess``
+    returns) -> (classes int32 [k,H,W], probs f32 [k,H,W]) by a stable descending sort over the classes, so equal values keep ascending
+    class order; a class that owns no query is left out, and the slots it leaves are -1 / 0.  Not a hot path: it serves the routes on
+    which the fused head cannot run (PAMR, a resize, whole-image inference), which have the [K,H,W] planes anyway."""
+    K = int(probs.shape[0])
+    k = int(k)
+    if not 1 <= k <= min(TOPK_MAX, K):
+        raise ValueError(f"topk_from_probs: k={k} must lie in [1, min({TOPK_MAX}, K={K})]")
+    qi = torch.as_tensor(query_idx).reshape(-1).to(device=probs.device, dtype=torch.int64)
+    owned = torch.zeros(K, dtype=torch.bool, device=probs.device)
+    owned[qi[(qi >= 0) & (qi < K)]] = True
+    p = probs.float().masked_fill(~owned.view(K, 1, 1), -1.0)         # below every probability: the unowned classes sort last
+    vals, idx = torch.sort(p, dim=0, descending=True, stable=True)
+    vals, idx = vals[:k], idx[:k]
+    empty = ~owned[idx]
+    return idx.to(torch.int32).masked_fill(empty, -1), vals.masked_fill(empty, 0.0).contiguous()
 
 
 @on_tensor_device

@@ -324,6 +324,10 @@ PAMR_TILE_GROUP = ("PAMR under tile_group sharding is not built: a rank's canvas
                    "rows of its neighbours' logits; run PAMR on whole images per rank")
 
 
+TOPK_TILE_GROUP = ("top-k under tile_group sharding is not built: each rank would run the head on its own canvas band and the [k,rows,W] "
+                   "planes would be gathered (gather_bands); run top-k on whole images per rank")
+
+
 class SegPipeline:
     pamr_steps, pamr_stride = 0, (8, 16)      # PAMR off unless the constructor says otherwise
 
@@ -433,6 +437,31 @@ class SegPipeline:
             return ops.prob_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, self.query_idx, self.num_classes, self.logit_scale,
                                  self.prob_thd, self.bg_idx)
         return self._canvas_tail(tile_logits, windows, up_hw, pad_tl, canvas_hw, guide, True)
+
+    def topk_k(self, topk) -> int:
+        """``topk`` checked against what sg_topk_head takes: 1 .. min(ops.TOPK_MAX, the number of classes)."""
+        k = int(topk)
+        if not 1 <= k <= min(ops.TOPK_MAX, self.num_classes):
+            raise ValueError(f"topk must lie in [1, min({ops.TOPK_MAX}, {self.num_classes} classes)], got {topk!r}")
+        return k
+
+    def topk_from_tiles(self, tile_logits, windows, up_hw, pad_tl, canvas_hw, k: int, guide=None):
+        """Tile logits [T,Q,gh,gw] + windows [T,4] -> (classes int32 [k,H,W], probs f32 [k,H,W]): the k best classes of every pixel in
+        descending probability (sg_topk_head: no canvas, no [K,H,W] planes, any Q).  With PAMR on there has to be a canvas: stitch,
+        refine under ``guide`` (the scene), post-process, ``ops.topk_from_probs``."""
+        k = self.topk_k(k)
+        if getattr(self, "pamr_steps", 0) > 0:
+            probs, _ = self._canvas_tail(tile_logits, windows, up_hw, pad_tl, canvas_hw, guide, True)
+            return ops.topk_from_probs(probs, self.query_idx, k)
+        return ops.topk_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, self.query_idx, self.num_classes, self.logit_scale, k)
+
+    def topk_from_logits(self, seg_logits, k: int, guide=None):
+        """The canvas route to the k best classes, for logits [Q,H,W] that already exist (a resize to another ``ori_shape``, whole-image
+        inference): PAMR when on, post-process, ``ops.topk_from_probs``."""
+        k = self.topk_k(k)
+        if getattr(self, "pamr_steps", 0) > 0:
+            seg_logits = self.refine(seg_logits.float().contiguous(), guide)
+        return ops.topk_from_probs(self.postprocess(seg_logits, want_probs=True)[0], self.query_idx, k)
 
     def _pre_head(self, tok, cls):
         """Global debias (+ CTD) when they cannot stay fused in the logits kernel: returns (tokens, remaining debias factor)."""
@@ -580,12 +609,25 @@ class SegPipeline:
             return buf[0, :, :H]
         return torch.cat([buf[r, :, :yb[r + 1] - yb[r]] for r in range(world)], 1)
 
-    def segment_scene(self, scene: torch.Tensor, stride, crop, group=None, gather_labels: bool = True, want_probs: bool = False):
+    def segment_scene(self, scene: torch.Tensor, stride, crop, group=None, gather_labels: bool = True, want_probs: bool = False,
+                      topk: int = 0):
         """The whole path to labels for one scene.  Sharded: every rank computes its tiles, stitches + labels ITS band; only the
         int64 label band (8 B per pixel instead of 4Q) is gathered.  -> labels [1,H,W] (or (band labels, first row) when
         ``gather_labels`` is False).  ``want_probs``: (probs [K,H,W], labels [1,H,W]) through ``probs_from_tiles``; not with tile
         sharding.  With PAMR on (``pamr_steps``) the canvas is stitched, refined under the scene and post-processed, whatever
-        label_head / prob_head say; tile sharding is then refused (a band would need a halo of its neighbours' rows)."""
+        label_head / prob_head say; tile sharding is then refused (a band would need a halo of its neighbours' rows).
+        ``topk`` > 0: (classes int32 [topk,H,W], probs f32 [topk,H,W]) through ``topk_from_tiles`` instead of labels; not together with
+        ``want_probs`` and not with tile sharding."""
+        if topk:
+            if want_probs:
+                raise ValueError("segment_scene: topk and want_probs exclude each other (topk returns the k best class probabilities)")
+            if group is not None or self.tile_group is not None:
+                raise ValueError(TOPK_TILE_GROUP)
+            k = self.topk_k(topk)
+            H, W, stride, crop, wins, tile_hw, pad_tl, up_hw, grid = self._geometry(scene, stride, crop)
+            tl = self.tile_logits(scene, wins, tile_hw, grid_of_tiles=grid)
+            win_dev = torch.tensor(wins, dtype=torch.int32, device=self.device)
+            return self.topk_from_tiles(tl, win_dev, up_hw, pad_tl, (H, W), k, guide=scene)
         if self.pamr_steps > 0 and (group is not None or self.tile_group is not None):
             raise ValueError(PAMR_TILE_GROUP)
         group = resolve_tile_group(group if group is not None else self.tile_group)
@@ -745,7 +787,7 @@ class SegPipeline:
                 out[k] = (ops.resize_bilinear(c, ori) if ori is not None and ori != tuple(c.shape[1:]) else c).unsqueeze(0)
         return out
 
-    def label_groups(self, scenes, stride, crop, want_probs: bool = False, ori_shapes=None):
+    def label_groups(self, scenes, stride, crop, want_probs: bool = False, ori_shapes=None, topk: int = 0):
         """The whole packed path to labels, flush group by flush group: one sg_stitch_multi and one sg_postprocess_multi launch each
         (the resize to ``ori_shapes`` fused into the latter).  Yields (image indices, list of probs [K,H,W] or None, list of labels
         [1,H,W], the flat int64 buffer those label maps are views of, in that order of images).
@@ -756,8 +798,30 @@ class SegPipeline:
         (its wide form) on the group's canvases.
         With PAMR on (``pamr_steps``) every group takes the canvas route: a flush group whose images all keep their size (and Q <= 64)
         has each canvas view refined in place and then the one sg_postprocess_multi launch; a group holding an image with another
-        ``ori_shape`` goes image by image: resize, PAMR, post-process."""
+        ``ori_shape`` goes image by image: resize, PAMR, post-process.
+        ``topk`` > 0 (not with ``want_probs``): yields (image indices, list of probs f32 [topk,H,W], list of classes int32 [topk,H,W],
+        None) -- the k best classes of every pixel.  At the images' own sizes and without PAMR that is one sg_topk_head_multi launch
+        per flush group with no canvas (the planner counts 8 * topk bytes per pixel); otherwise the probabilities come as above and go
+        through ``ops.topk_from_probs`` image by image."""
         no_resize = ori_shapes is None or all(o is None for o in ori_shapes)
+        if topk:
+            if want_probs:
+                raise ValueError("label_groups: topk and want_probs exclude each other (topk returns the k best class probabilities)")
+            if self.tile_group is not None:
+                raise ValueError(TOPK_TILE_GROUP)
+            k = self.topk_k(topk)
+            same_size = no_resize or all(o is None or tuple(o) == _scene_hw(s) for o, s in zip(
+                ori_shapes, [scenes] if torch.is_tensor(scenes) and scenes.dim() == 3 else scenes))
+            if self.pamr_steps == 0 and same_size:
+                for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(scenes, stride, crop, 8 * k):
+                    cls, prb = ops.topk_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes,
+                                                   self.logit_scale, k)
+                    yield idx, prb, cls, None
+                return
+            for idx, prb, _, _ in self.label_groups(scenes, stride, crop, True, ori_shapes):
+                pairs = [ops.topk_from_probs(p, self.query_idx, k) for p in prb]
+                yield idx, [p for _, p in pairs], [c for c, _ in pairs], None
+            return
         if self.pamr_steps > 0:
             yield from self._label_groups_pamr(scenes, stride, crop, want_probs, ori_shapes)
             return
@@ -819,11 +883,18 @@ class SegPipeline:
             pix = ops._prefix(l_.numel() for l_ in lab)
             yield idx, prb, [flat[pix[n]:pix[n + 1]].view(1, *ohw[n]) for n in range(len(lab))], flat
 
-    def segment_scenes(self, scenes, stride, crop, want_probs: bool = False, ori_shapes=None):
+    def segment_scenes(self, scenes, stride, crop, want_probs: bool = False, ori_shapes=None, topk: int = 0):
         """``label_groups`` collected per image -> list of labels [1,H,W], or (list of probs [K,H,W], list of labels) with
-        ``want_probs``.  With PAMR on every image's canvas is refined before its post-process (``label_groups``)."""
+        ``want_probs``.  With PAMR on every image's canvas is refined before its post-process (``label_groups``).
+        ``topk`` > 0: a list of (classes int32 [topk,H,W], probs f32 [topk,H,W]) per image."""
         probs: List[Optional[torch.Tensor]] = []
         labels: List[Optional[torch.Tensor]] = []
+        if topk:
+            for idx, prb, cls, _ in self.label_groups(scenes, stride, crop, want_probs, ori_shapes, topk=topk):
+                probs.extend([None] * (max(idx) + 1 - len(probs)))
+                for n, i in enumerate(idx):
+                    probs[i] = (cls[n], prb[n])
+            return probs
         for idx, prb, lab, _ in self.label_groups(scenes, stride, crop, want_probs, ori_shapes):
             for lst, vals in ((probs, prb), (labels, lab)):
                 lst.extend([None] * (max(idx) + 1 - len(lst)))

@@ -350,6 +350,42 @@ class _HipSegmentorBase(_Base):
             self._fill_sample(ds, probs[i], labels[i], i)
         return data_samples
 
+    @torch.no_grad()
+    def predict_topk(self, inputs, k, data_samples=None):
+        """The ``k`` best classes of every pixel with their probabilities (1 <= k <= min(8, classes)).  inputs: as ``predict_many``.
+        Returns one (classes int32 [k,H,W], probs f32 [k,H,W]) per image, slots in descending class probability (equal values by
+        ascending class); with data samples each receives ``seg_topk_classes``, ``seg_topk_probs`` and ``pred_sem_seg`` (plane 0 with
+        ``prob_thd`` -> ``bg_idx`` applied, int64 [1,H,W]) and no ``seg_logits``, and the samples are returned.
+        Sliding-window inference at the images' own sizes without PAMR runs the fused head (sg_topk_head_multi, one launch per flush
+        group): neither the [Q,H,W] canvas nor the [K,H,W] probabilities exist, and a class that owns no query is never listed.  With
+        PAMR on, an ``ori_shape`` of another size, or whole-image inference (``slide_crop <= 0``) the canvas route of ``predict`` runs
+        (stitch, resize, PAMR, post-process) and ``ops.topk_from_probs`` sorts its probabilities.  ``tile_group`` sharding is refused."""
+        from .pipeline import TOPK_TILE_GROUP
+        if getattr(self, "tile_group", None) is not None:
+            raise ValueError(TOPK_TILE_GROUP)
+        batch = torch.is_tensor(inputs)
+        imgs = inputs.float() if batch else [x[0].float() if x.dim() == 4 else x.float() for x in inputs]
+        n = imgs.shape[0] if batch else len(imgs)
+        if data_samples is not None and len(data_samples) != n:
+            raise ValueError(f"predict_topk: {n} images but {len(data_samples)} data samples")
+        pipe = self._pipeline()
+        k = pipe.topk_k(k)
+        ori = None if data_samples is None else [tuple(ds.metainfo["ori_shape"][:2]) for ds in data_samples]
+        if self.slide_crop <= 0:                             # whole-image inference: the logits exist at the output size anyway
+            out = []
+            for i in range(n):
+                size = tuple(imgs[i].shape[-2:]) if ori is None else ori[i]
+                out.append(pipe.topk_from_logits(pipe.forward_feature(imgs[i][None], size)[0], k, guide=imgs[i]))
+        else:
+            out = pipe.segment_scenes(imgs, self.slide_stride, self.slide_crop, ori_shapes=ori, topk=k)
+        if data_samples is None:
+            return out
+        for ds, (cls, prb) in zip(data_samples, out):
+            seg_pred = torch.where(prb[0] < self.prob_thd, torch.full_like(cls[0], int(self.bg_idx)), cls[0]).to(torch.int64).unsqueeze(0)
+            ds.set_data({"seg_topk_classes": PixelData(**{"data": cls}), "seg_topk_probs": PixelData(**{"data": prb}),
+                         "pred_sem_seg": PixelData(**{"data": seg_pred})})
+        return data_samples
+
     def _fill_sample(self, sample, probs, seg_pred, i):
         """What postprocess_result leaves in a data sample: seg_logits, pred_sem_seg and the result_dir / heatmap_dir images."""
         sample.set_data({"seg_logits": PixelData(**{"data": probs}), "pred_sem_seg": PixelData(**{"data": seg_pred})})

@@ -286,6 +286,31 @@ int sg_prob_head_multi(const float* tile_logits, const int32_t* windows, const i
                        const int64_t* out_offset, const int64_t* block_prefix, int N, int64_t total_blocks, int64_t out_pixels,
                        const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx, float* probs,
                        int64_t* labels, sg_stream s);
+/* sg_topk_head: the k best classes of every pixel with their probabilities, straight from the tile logits: no [Q,H,W] canvas and no
+ * [K,H,W] probability planes.  Inputs as sg_label_head, any Q >= 1, 1 <= K <= Q, 1 <= k <= min(SG_TOPK_MAX, K).  Outputs are planes:
+ * classes int32 [k,H,W] and probs f32 [k,H,W]; the 8k bytes per pixel they hold are the call's only writes.  Contract:
+ *   - the probability of a class is the one sg_postprocess defines: the softmax over all Q scaled logits, the maximum over the class's
+ *     queries (query_idx need not be sorted; with K == Q class(q) = q; a query whose class lies outside [0,K) takes part in the sum only);
+ *   - slots are in descending order of that probability, equal values by ascending class; plane 0 is sg_label_head's label before any
+ *     threshold and its probability is sg_label_head's conf, byte for byte (thresholding it is the caller's: there is no prob_thd here);
+ *   - a class that owns no query never appears -- a deliberate difference from the canvas route, where such a class has probability 0
+ *     and would be listed after the others; the slots left unfilled hold class -1 and probability 0;
+ *   - a pixel no tile covers has every stitched value 0: classes in ascending index, equal probabilities;
+ *   - repeats are byte-identical (no atomics, every element written by its pixel's own thread in an order fixed by pixel and query);
+ *   - against sg_stitch + sg_postprocess + a stable descending sort, the order can differ only where two class probabilities are closer
+ *     than their f32 rounding.
+ * The queries pass through registers in chunks as in sg_label_head; a sorted list of k (value, class) pairs is kept per pixel. */
+#define SG_TOPK_MAX 8
+int sg_topk_head(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t,
+                 int pad_l, int H, int W, const int32_t* query_idx, int K, float logit_scale, int k, int32_t* classes, float* probs,
+                 sg_stream s);
+/* sg_topk_head_multi: sg_topk_head for the tiles of N images in one launch, descriptors as sg_label_head_multi.  The planes [k,H,W] of
+ * image n start at k * out_offset[n] elements of `classes` and of `probs` (sg_prob_head_multi's layout with k for K); out_pixels = the
+ * sum of H * W, both outputs hold k * out_pixels.  Byte-identical to sg_topk_head per image. */
+int sg_topk_head_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh, int gw,
+                       int up_h, int up_w, int pad_t, int pad_l, const int32_t* image_hw, const int32_t* image_tiles,
+                       const int64_t* out_offset, const int64_t* block_prefix, int N, int64_t total_blocks, int64_t out_pixels,
+                       const int32_t* query_idx, int K, float logit_scale, int k, int32_t* classes, float* probs, sg_stream s);
 /* Label / confidence images of postprocess_result (segmentor.py:501-531): mask_rgb [H,W,3] = palette[clip(label)] (_colorize_mask,
  * :580-590); heat_rgb [H,W,3] = (g, 0, 255-g) with g = uint8(clip(max_k probs, 0, 1) * 255) (_to_colormap without OpenCV, :604-608;
  * OpenCV's JET table is not reproduced).  Either output may be NULL. */
