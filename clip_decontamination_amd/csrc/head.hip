@@ -691,6 +691,346 @@ __global__ __launch_bounds__(256) void topk_head_multi_kernel(const float* __res
                         classes + k * ib.off, probs + k * ib.off);
 }
 
+// ---- the label and top-k heads at another ori_shape: stitch -> bilinear resize -> the same tails, no canvas --------------------------------
+// segmentor.py:447-449: preds / count, then F.interpolate(bilinear, align_corners=False) to ori_shape, then the post-process.  An output
+// pixel (Y, X) of [OH, OW] over the [h, w] canvas takes the taps of rs_tap(Y, h, OH) and rs_tap(X, w, OW), the STITCHED value of each of
+// its four canvas pixels (covering tiles summed in raster order and divided by THAT pixel's count, 0 where no tile covers: neighbouring
+// taps can have different counts, so the division comes before the blend), and blends them top row, bottom row, then the two.  The
+// blended value goes to the per-chunk statements of label_head_block / topk_head_block with cnt = 1.
+//   Two forms get the four values, both from stitched_pixel, and all of it (taps, gather, division, blend) is compiled with fp
+//   contraction off, so a value does not depend on the form that asked for it: the two forms agree byte for byte.
+//   direct: every thread gathers its own (up to) four canvas pixels; equal taps are gathered once.  Any scale.
+//   staged: the block's 64 x 4 output pixels read a canvas footprint of at most rs_span(4, h, OH) x rs_span(64, w, OW) pixels (120 for
+//   448 -> 1024 instead of 1024 gathers); the block computes each footprint pixel's chunk of ST_QC queries once into LDS, barrier, every
+//   thread blends from LDS, barrier, next chunk.  It runs when the footprint holds at most RS_STAGE_PIX pixels: ST_QC planes of
+//   RS_STAGE_PIX floats are the 16 KiB of s_stage.
+//   Barriers: in the staged form no thread leaves before the last chunk's second barrier; a thread outside the image only skips its
+//   blend and its stores.  The form is chosen per block from block-uniform values, and the multi-image kernels return on a bad
+//   descriptor before the first barrier, the whole block at once.
+constexpr int RS_STAGE_PIX = 512;
+constexpr int RS_AUTO = SG_RESIZED_AUTO, RS_DIRECT = SG_RESIZED_DIRECT, RS_STAGED = SG_RESIZED_STAGED;
+// rows (columns) of the canvas that n consecutive output rows (columns) can touch: their source coordinates span (n - 1) in / out, the
+// floor and the second tap add one each
+__host__ __device__ inline int64_t rs_span(int n, int in, int out) { return ((int64_t)n * in + out - 1) / out + 2; }
+__host__ __device__ inline bool rs_fits(int h, int w, int OH, int OW) { return rs_span(4, h, OH) * rs_span(64, w, OW) <= RS_STAGE_PIX; }
+// SG_RESIZED_AUTO: the staged form where it fits and the output is larger than the canvas along both axes -- measured 2.1 to 2.8 times
+// the direct form's speed at 448 -> 1024 and at 1.5x (a thread of the direct form gathers up to four canvas pixels, the stage holds at
+// most two per output pixel).  At the canvas's own size the direct form gathers one pixel per thread and was 5 to 10 % faster
+// (0.476 against 0.525 ms), so identity runs direct; so does a mixed up / down scale, which was not measured (profiles/head_resized.jsonl).
+__host__ __device__ inline bool rs_want_staged(int flags, int h, int w, int OH, int OW) {
+  if (flags == RS_DIRECT || !rs_fits(h, w, OH, OW)) return false;
+  return flags == RS_STAGED || (OH > h && OW > w);
+}
+
+// bilinear_tap (rowops.h) with every product rounded: the taps of both forms and of the footprint are the same numbers by construction
+__device__ __forceinline__ void rs_tap(int dst, int in, int out, int& i0, int& i1, float& l0, float& l1) {
+#pragma clang fp contract(off)
+  if (in == out) { i0 = i1 = dst; l0 = 1.f; l1 = 0.f; return; }
+  const float scale = (float)in / (float)out;
+  float src = scale * ((float)dst + 0.5f) - 0.5f;
+  src = src < 0.f ? 0.f : src;
+  i0 = (int)src; i0 = i0 > in - 1 ? in - 1 : i0;
+  i1 = i0 + (i0 < in - 1 ? 1 : 0);
+  l1 = src - (float)i0; l0 = 1.f - l1;
+}
+
+__device__ __forceinline__ float rs_blend(float v00, float v01, float v10, float v11, float wx0, float wx1, float wy0, float wy1) {
+#pragma clang fp contract(off)
+  const float top = v00 * wx0 + v01 * wx1;
+  const float bot = v10 * wx0 + v11 * wx1;
+  return top * wy0 + bot * wy1;
+}
+
+// The candidate tiles of a canvas rectangle [cx0, cx1] x [cy0, cy1] (stitch_candidates for a footprint that is not 64 x 4), all 256
+// threads, one barrier.
+__device__ __forceinline__ StitchList rs_candidates(const int32_t* __restrict__ win, const int32_t* __restrict__ tile_image, int img,
+                                                    int n_tiles, int cx0, int cy0, int cx1, int cy1) {
+  __shared__ int s_list[ST_MAXC];
+  __shared__ int s_count;
+  const int lane = threadIdx.x & 63;
+  if ((threadIdx.x >> 6) == 0) {
+    int base = 0;
+    for (int t0 = 0; t0 < n_tiles; t0 += 64) {
+      const int t = t0 + lane;
+      bool hit = false;
+      if (t < n_tiles && (tile_image == nullptr || tile_image[t] == img)) {
+        const int y1 = win[t * 4 + 0], y2 = win[t * 4 + 1], x1 = win[t * 4 + 2], x2 = win[t * 4 + 3];
+        hit = y1 <= cy1 && y2 > cy0 && x1 <= cx1 && x2 > cx0;
+      }
+      const unsigned long long m = __ballot(hit);
+      const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+      if (hit && pos < ST_MAXC) s_list[pos] = t;
+      base += __popcll(m);
+    }
+    if (lane == 0) s_count = base;
+  }
+  __syncthreads();
+  return {s_list, s_count};
+}
+
+// Canvas pixel (cx, cy), 0 <= cx < w, 0 <= cy < h: out[k] = the stitched value of query q0 + k as stitch_gather defines it -- the tiles
+// that cover the pixel in raster order, each tile's bilinear upsample, the sum divided by the count, 0 without a tile.  The only copy.
+__device__ __forceinline__ void stitched_pixel(const StitchList& sl, const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
+                                               const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw, int up_h,
+                                               int up_w, int pad_t, int pad_l, int cx, int cy, int q0, float (&out)[ST_QC]) {
+#pragma clang fp contract(off)
+  const bool use_list = sl.n_cand <= ST_MAXC;                      // beyond ST_MAXC candidates: test every window
+  const int n_iter = use_list ? sl.n_cand : n_tiles;
+  const int64_t tile_sz = (int64_t)gh * gw;
+  float acc[ST_QC];
+#pragma unroll
+  for (int k = 0; k < ST_QC; ++k) acc[k] = 0.f;
+  float cnt = 0.f;
+  for (int it = 0; it < n_iter; ++it) {                              // raster order = the reference's add order
+    const int t = use_list ? sl.list[it] : it;
+    if (!use_list && tile_image != nullptr && tile_image[t] != img) continue;
+    const int y1 = win[t * 4 + 0], y2 = win[t * 4 + 1];
+    if (cy < y1 || cy >= y2) continue;
+    const int x1 = win[t * 4 + 2], x2 = win[t * 4 + 3];
+    if (cx < x1 || cx >= x2) continue;
+    int ya, yb, xa, xb; float wy0, wy1, wx0, wx1;
+    rs_tap(cy - y1 + pad_t, gh, up_h, ya, yb, wy0, wy1);
+    rs_tap(cx - x1 + pad_l, gw, up_w, xa, xb, wx0, wx1);
+    const float* base = tile_logits + ((int64_t)t * Q + q0) * tile_sz;
+#pragma unroll
+    for (int k = 0; k < ST_QC; ++k) {
+      if (q0 + k < Q) {
+        const float* p = base + (int64_t)k * tile_sz;
+        acc[k] += rs_blend(p[ya * gw + xa], p[ya * gw + xb], p[yb * gw + xa], p[yb * gw + xb], wx0, wx1, wy0, wy1);
+      }
+    }
+    cnt += 1.f;
+  }
+#pragma unroll
+  for (int k = 0; k < ST_QC; ++k) out[k] = cnt > 0.f ? acc[k] / cnt : 0.f;
+}
+
+// One 64 x 4 block of OUTPUT pixels of one image: a thread whose pixel (X, Y) lies in the output hands each chunk's resized stitched
+// values to sink(q0, acc), acc[k] for query q0 + k.  Returns whether this thread's pixel is in the output.  All 256 threads call it.
+template <class Sink>
+__device__ __forceinline__ bool resized_gather(const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
+                                               const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw, int up_h,
+                                               int up_w, int pad_t, int pad_l, int h, int w, int OH, int OW, int bx0, int by0, int flags,
+                                               Sink&& sink) {
+  __shared__ float s_stage[ST_QC * RS_STAGE_PIX];
+  const int X = bx0 + (threadIdx.x & 63);
+  const int Y = __builtin_amdgcn_readfirstlane(by0 + (threadIdx.x >> 6));
+  const bool live = Y < OH && X < OW;
+  // the block's canvas footprint [fx0, fx1] x [fy0, fy1]: the first tap of its first row / column to the second tap of its last one
+  // (taps do not decrease with the output coordinate).  Block-uniform.
+  int fy0, fy1, fx0, fx1, unused; float u0, u1;
+  rs_tap(by0, h, OH, fy0, unused, u0, u1);
+  rs_tap(by0 + 3 < OH ? by0 + 3 : OH - 1, h, OH, unused, fy1, u0, u1);
+  rs_tap(bx0, w, OW, fx0, unused, u0, u1);
+  rs_tap(bx0 + 63 < OW ? bx0 + 63 : OW - 1, w, OW, unused, fx1, u0, u1);
+  const int fw = fx1 - fx0 + 1, npix = (fy1 - fy0 + 1) * fw;
+  const StitchList sl = rs_candidates(win, tile_image, img, n_tiles, fx0, fy0, fx1, fy1);
+  const bool staged = rs_want_staged(flags, h, w, OH, OW) && npix <= RS_STAGE_PIX;   // block-uniform; npix <= the rs_span product
+  int ya = 0, yb = 0, xa = 0, xb = 0; float wy0 = 0.f, wy1 = 0.f, wx0 = 0.f, wx1 = 0.f;
+  if (live) {
+    rs_tap(Y, h, OH, ya, yb, wy0, wy1);
+    rs_tap(X, w, OW, xa, xb, wx0, wx1);
+  }
+  if (!staged) {
+    if (!live) return false;                                         // no barrier below on this path
+    for (int q0 = 0; q0 < Q; q0 += ST_QC) {
+      float v00[ST_QC], v01[ST_QC], v10[ST_QC], v11[ST_QC], acc[ST_QC];
+      stitched_pixel(sl, tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, xa, ya, q0, v00);
+      if (xb != xa) stitched_pixel(sl, tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, xb, ya, q0, v01);
+      else {
+#pragma unroll
+        for (int k = 0; k < ST_QC; ++k) v01[k] = v00[k];
+      }
+      if (yb != ya) {
+        stitched_pixel(sl, tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, xa, yb, q0, v10);
+        if (xb != xa) stitched_pixel(sl, tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, xb, yb, q0, v11);
+        else {
+#pragma unroll
+          for (int k = 0; k < ST_QC; ++k) v11[k] = v10[k];
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < ST_QC; ++k) { v10[k] = v00[k]; v11[k] = v01[k]; }
+      }
+#pragma unroll
+      for (int k = 0; k < ST_QC; ++k) acc[k] = rs_blend(v00[k], v01[k], v10[k], v11[k], wx0, wx1, wy0, wy1);
+      sink(q0, acc);
+    }
+    return true;
+  }
+  const int i00 = (ya - fy0) * fw + (xa - fx0), i01 = (ya - fy0) * fw + (xb - fx0);
+  const int i10 = (yb - fy0) * fw + (xa - fx0), i11 = (yb - fy0) * fw + (xb - fx0);
+  for (int q0 = 0; q0 < Q; q0 += ST_QC) {                              // Q is uniform: every thread runs every barrier
+    for (int p = threadIdx.x; p < npix; p += 256) {
+      float o[ST_QC];
+      stitched_pixel(sl, tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, fx0 + p % fw, fy0 + p / fw, q0, o);
+#pragma unroll
+      for (int k = 0; k < ST_QC; ++k) s_stage[k * RS_STAGE_PIX + p] = o[k];
+    }
+    __syncthreads();
+    if (live) {
+      float acc[ST_QC];
+#pragma unroll
+      for (int k = 0; k < ST_QC; ++k) {
+        const float* sp = s_stage + k * RS_STAGE_PIX;
+        acc[k] = rs_blend(sp[i00], sp[i01], sp[i10], sp[i11], wx0, wx1, wy0, wy1);
+      }
+      sink(q0, acc);
+    }
+    __syncthreads();                                                   // the stage is free for the next chunk
+  }
+  return live;
+}
+
+// label_head_block over resized_gather: the per-chunk statements are that function's, copied (its machine code stays what it is); the
+// resized value is already count-normalised, so the division by the count is gone.
+__device__ __forceinline__ void label_head_resized_block(const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
+                                                         const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw,
+                                                         int up_h, int up_w, int pad_t, int pad_l, int h, int w, int OH, int OW, int bx0,
+                                                         int by0, int flags, const int32_t* __restrict__ query_idx, int K, float logit_scale,
+                                                         float prob_thd, int bg_idx, int64_t* __restrict__ labels, float* __restrict__ conf) {
+  float vmax = -INFINITY, sum = 0.f, best = -INFINITY;
+  int best_c = 0;
+  const bool live = resized_gather(tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, h, w, OH, OW, bx0, by0,
+                                   flags, [&](int q0, float (&acc)[ST_QC]) {
+#pragma clang fp contract(off)        // the scaled logit is rounded before the subtraction, as postprocess_kernel compiles it
+                 float cm = -INFINITY;
+#pragma unroll
+                 for (int k = 0; k < ST_QC; ++k)
+                   if (q0 + k < Q) { acc[k] = acc[k] * logit_scale; cm = fmaxf(cm, acc[k]); }
+                 if (cm > vmax) { sum *= expf(vmax - cm); vmax = cm; }            // the first chunk: sum = 0 * exp(-inf) = 0
+#pragma unroll
+                 for (int k = 0; k < ST_QC; ++k)
+                   if (q0 + k < Q) {
+                     sum += expf(acc[k] - vmax);
+                     const int c = K == Q ? q0 + k : query_idx[q0 + k];
+                     if (c >= 0 && c < K && (acc[k] > best || (acc[k] == best && c < best_c))) { best = acc[k]; best_c = c; }
+                   }
+               });
+  if (!live) return;
+  const int X = bx0 + (threadIdx.x & 63);
+  const int Y = __builtin_amdgcn_readfirstlane(by0 + (threadIdx.x >> 6));
+  const float cf = expf(best - vmax) / sum;
+  const int64_t o = (int64_t)Y * OW + X;
+  labels[o] = cf < prob_thd ? bg_idx : best_c;
+  if (conf) conf[o] = cf;
+}
+
+__global__ __launch_bounds__(256) void label_head_resized_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows,
+                                                                 int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t, int pad_l,
+                                                                 int h, int w, int OH, int OW, const int32_t* __restrict__ query_idx, int K,
+                                                                 float logit_scale, float prob_thd, int bg_idx,
+                                                                 int64_t* __restrict__ labels, float* __restrict__ conf, int flags) {
+  label_head_resized_block(tile_logits, windows, nullptr, 0, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, h, w, OH, OW, blockIdx.x * 64,
+                           blockIdx.y * 4, flags, query_idx, K, logit_scale, prob_thd, bg_idx, labels, conf);
+}
+
+// The descriptors of the resized multi-image kernels: image_block over the OUTPUT sizes (out_hw, out_offset in output pixels,
+// block_prefix over output blocks: every check of image_block holds against the output extents), plus the image's canvas size.
+__device__ __forceinline__ bool image_block_resized(const int32_t* __restrict__ image_hw, const int32_t* __restrict__ image_tiles,
+                                                    const int32_t* __restrict__ out_hw, const int64_t* __restrict__ out_offset,
+                                                    const int64_t* __restrict__ block_prefix, int N, int T, int64_t out_pixels,
+                                                    ImageBlock& ib, int& h, int& w) {
+  if (!image_block(out_hw, image_tiles, out_offset, block_prefix, N, T, 1, out_pixels, ib)) return false;
+  h = image_hw[2 * ib.n]; w = image_hw[2 * ib.n + 1];
+  return h > 0 && w > 0;
+}
+
+__global__ __launch_bounds__(256) void label_head_resized_multi_kernel(
+    const float* __restrict__ tile_logits, const int32_t* __restrict__ windows, const int32_t* __restrict__ tile_image, int T, int Q, int gh,
+    int gw, int up_h, int up_w, int pad_t, int pad_l, const int32_t* __restrict__ image_hw, const int32_t* __restrict__ image_tiles,
+    const int32_t* __restrict__ out_hw, const int64_t* __restrict__ out_offset, const int64_t* __restrict__ block_prefix, int N,
+    int64_t out_pixels, const int32_t* __restrict__ query_idx, int K, float logit_scale, float prob_thd, int bg_idx,
+    int64_t* __restrict__ labels, float* __restrict__ conf, int flags) {
+  ImageBlock ib; int h, w;
+  if (!image_block_resized(image_hw, image_tiles, out_hw, out_offset, block_prefix, N, T, out_pixels, ib, h, w)) return;
+  label_head_resized_block(tile_logits + (int64_t)ib.t_first * Q * gh * gw, windows + (int64_t)ib.t_first * 4, tile_image + ib.t_first, ib.n,
+                           ib.n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, h, w, ib.H, ib.W, ib.bx0, ib.by0, flags, query_idx, K,
+                           logit_scale, prob_thd, bg_idx, labels + ib.off, conf ? conf + ib.off : nullptr);
+}
+
+// topk_head_block over resized_gather, the per-chunk statements copied likewise: plane 0 carries sg_label_head_resized's label and conf.
+template <int KTOP>
+__device__ __forceinline__ void topk_head_resized_block(const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
+                                                        const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw,
+                                                        int up_h, int up_w, int pad_t, int pad_l, int h, int w, int OH, int OW, int bx0,
+                                                        int by0, int flags, const int32_t* __restrict__ query_idx, int K, float logit_scale,
+                                                        int k, int32_t* __restrict__ classes, float* __restrict__ probs) {
+  float vmax = -INFINITY, sum = 0.f;
+  float tv[KTOP];
+  int tc[KTOP];
+#pragma unroll
+  for (int j = 0; j < KTOP; ++j) { tv[j] = -INFINITY; tc[j] = INT_MAX; }
+  const bool merge = K != Q;
+  const bool live = resized_gather(tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, h, w, OH, OW, bx0, by0,
+                                   flags, [&](int q0, float (&acc)[ST_QC]) {
+#pragma clang fp contract(off)        // the scaled logit is rounded before the subtraction, as postprocess_kernel compiles it
+                 float cm = -INFINITY;
+#pragma unroll
+                 for (int k = 0; k < ST_QC; ++k)
+                   if (q0 + k < Q) { acc[k] = acc[k] * logit_scale; cm = fmaxf(cm, acc[k]); }
+                 if (cm > vmax) { sum *= expf(vmax - cm); vmax = cm; }            // the first chunk: sum = 0 * exp(-inf) = 0
+#pragma unroll
+                 for (int k = 0; k < ST_QC; ++k)
+                   if (q0 + k < Q) {
+                     sum += expf(acc[k] - vmax);
+                     const float v = acc[k];
+                     const int c = merge ? query_idx[q0 + k] : q0 + k;
+                     if (c < 0 || c >= K) continue;
+                     bool held = false;
+                     if (merge) {
+#pragma unroll
+                       for (int j = 0; j < KTOP; ++j)
+                         if (tc[j] == c) { held = true; tv[j] = fmaxf(tv[j], v); }
+                     }
+                     if (!held && (v > tv[KTOP - 1] || (v == tv[KTOP - 1] && c < tc[KTOP - 1]))) { tv[KTOP - 1] = v; tc[KTOP - 1] = c; }
+#pragma unroll
+                     for (int j = KTOP - 1; j > 0; --j) {
+                       const bool up = tv[j] > tv[j - 1] || (tv[j] == tv[j - 1] && tc[j] < tc[j - 1]);
+                       const float fv = tv[j]; const int fc = tc[j];
+                       tv[j] = up ? tv[j - 1] : fv; tc[j] = up ? tc[j - 1] : fc;
+                       tv[j - 1] = up ? fv : tv[j - 1]; tc[j - 1] = up ? fc : tc[j - 1];
+                     }
+                   }
+               });
+  if (!live) return;
+  const int X = bx0 + (threadIdx.x & 63);
+  const int Y = __builtin_amdgcn_readfirstlane(by0 + (threadIdx.x >> 6));
+  const int64_t HW = (int64_t)OH * OW, o = (int64_t)Y * OW + X;
+#pragma unroll
+  for (int j = 0; j < KTOP; ++j)
+    if (j < k) {
+      const bool filled = tc[j] != INT_MAX;
+      const float p = expf(tv[j] - vmax) / sum;
+      classes[j * HW + o] = filled ? tc[j] : -1;
+      probs[j * HW + o] = filled ? p : 0.f;
+    }
+}
+
+template <int KTOP>
+__global__ __launch_bounds__(256) void topk_head_resized_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows,
+                                                                int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t, int pad_l,
+                                                                int h, int w, int OH, int OW, const int32_t* __restrict__ query_idx, int K,
+                                                                float logit_scale, int k, int32_t* __restrict__ classes,
+                                                                float* __restrict__ probs, int flags) {
+  topk_head_resized_block<KTOP>(tile_logits, windows, nullptr, 0, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, h, w, OH, OW, blockIdx.x * 64,
+                                blockIdx.y * 4, flags, query_idx, K, logit_scale, k, classes, probs);
+}
+
+template <int KTOP>
+__global__ __launch_bounds__(256) void topk_head_resized_multi_kernel(
+    const float* __restrict__ tile_logits, const int32_t* __restrict__ windows, const int32_t* __restrict__ tile_image, int T, int Q, int gh,
+    int gw, int up_h, int up_w, int pad_t, int pad_l, const int32_t* __restrict__ image_hw, const int32_t* __restrict__ image_tiles,
+    const int32_t* __restrict__ out_hw, const int64_t* __restrict__ out_offset, const int64_t* __restrict__ block_prefix, int N,
+    int64_t out_pixels, const int32_t* __restrict__ query_idx, int K, float logit_scale, int k, int32_t* __restrict__ classes,
+    float* __restrict__ probs, int flags) {
+  ImageBlock ib; int h, w;
+  if (!image_block_resized(image_hw, image_tiles, out_hw, out_offset, block_prefix, N, T, out_pixels, ib, h, w)) return;   // k * (off + OH * OW) <= k * out_pixels
+  topk_head_resized_block<KTOP>(tile_logits + (int64_t)ib.t_first * Q * gh * gw, windows + (int64_t)ib.t_first * 4, tile_image + ib.t_first,
+                                ib.n, ib.n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, h, w, ib.H, ib.W, ib.bx0, ib.by0, flags, query_idx, K,
+                                logit_scale, k, classes + k * ib.off, probs + k * ib.off);
+}
+
 // ---- postprocess for any Q: several passes over the canvas, nothing held per query ------------------------------------------------
 // Pass 1 the maximum, pass 2 the sum (postprocess_kernel's order), pass 3 the per-class maximum, written through probs[class(q)] by the
 // pixel's own thread.  A class starts at what postprocess_kernel's `any_other` rule gives a class without queries: 0 when some query
@@ -1233,6 +1573,95 @@ extern "C" int sg_topk_head_multi(const float* tile_logits, const int32_t* windo
   auto kern = SG_TOPK_HEAD_DISPATCH(topk_head_multi_kernel, k);
   hipLaunchKernelGGL(kern, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q, gh, gw, up_h, up_w,
                      pad_t, pad_l, image_hw, image_tiles, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale, k, classes, probs);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+// ---- the label and top-k heads at another ori_shape (segmentor.py:447-449 fused into the heads) ------------------------------------------
+// SG_RESIZED_STAGED is refused where the footprint of a block does not fit the stage; the multi-image entries cannot see the sizes (they
+// are device arrays), so there a block whose image does not fit runs the direct form and the caller checks beforehand (ops.py does).
+#define SG_RESIZED_REQUIRE_FLAGS(name, flags) \
+  SG_REQUIRE((flags) == SG_RESIZED_AUTO || (flags) == SG_RESIZED_DIRECT || (flags) == SG_RESIZED_STAGED, name ": flags=%d is no SG_RESIZED_* value", flags)
+
+extern "C" int sg_label_head_resized(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w,
+                                     int pad_t, int pad_l, int H, int W, int out_h, int out_w, const int32_t* query_idx, int K,
+                                     float logit_scale, float prob_thd, int bg_idx, int64_t* labels, float* conf, int flags, sg_stream s) {
+  SG_REQUIRE(tile_logits && windows && query_idx && labels, "sg_label_head_resized: null pointer");
+  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && H > 0 && W > 0 && out_h > 0 && out_w > 0,
+             "sg_label_head_resized: bad shape T=%d Q=%d gh=%d gw=%d up=%dx%d H=%d W=%d out=%dx%d", T, Q, gh, gw, up_h, up_w, H, W, out_h, out_w);
+  SG_REQUIRE(K > 0 && K <= Q, "sg_label_head_resized: K=%d must lie in [1, Q=%d]", K, Q);
+  SG_REQUIRE(cdiv(out_h, 4) < 65536, "sg_label_head_resized: output too tall for one launch");
+  SG_RESIZED_REQUIRE_FLAGS("sg_label_head_resized", flags);
+  SG_REQUIRE(flags != SG_RESIZED_STAGED || rs_fits(H, W, out_h, out_w),
+             "sg_label_head_resized: the staged form does not fit: a block's footprint of %lld x %lld canvas pixels exceeds the stage of %d",
+             (long long)rs_span(4, H, out_h), (long long)rs_span(64, W, out_w), RS_STAGE_PIX);
+  hipLaunchKernelGGL(label_head_resized_kernel, dim3((unsigned)cdiv(out_w, 64), (unsigned)cdiv(out_h, 4)), dim3(256), 0, as_stream(s),
+                     tile_logits, windows, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, out_h, out_w, query_idx, K, logit_scale, prob_thd,
+                     bg_idx, labels, conf, flags);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_label_head_resized_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh,
+                                           int gw, int up_h, int up_w, int pad_t, int pad_l, const int32_t* image_hw,
+                                           const int32_t* image_tiles, const int32_t* out_hw, const int64_t* out_offset,
+                                           const int64_t* block_prefix, int N, int64_t total_blocks, int64_t out_pixels,
+                                           const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx, int64_t* labels,
+                                           float* conf, int flags, sg_stream s) {
+  SG_REQUIRE(tile_logits && windows && tile_image && image_hw && image_tiles && out_hw && out_offset && block_prefix && query_idx && labels,
+             "sg_label_head_resized_multi: null pointer");
+  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && N > 0 && N <= T,
+             "sg_label_head_resized_multi: bad shape T=%d Q=%d gh=%d gw=%d N=%d", T, Q, gh, gw, N);
+  SG_REQUIRE(K > 0 && K <= Q, "sg_label_head_resized_multi: K=%d must lie in [1, Q=%d]", K, Q);
+  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "sg_label_head_resized_multi: total_blocks=%lld outside (0, 2^31)", (long long)total_blocks);
+  SG_REQUIRE(out_pixels > 0, "sg_label_head_resized_multi: out_pixels=%lld holds no image", (long long)out_pixels);
+  SG_RESIZED_REQUIRE_FLAGS("sg_label_head_resized_multi", flags);
+  hipLaunchKernelGGL(label_head_resized_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows,
+                     tile_image, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, image_hw, image_tiles, out_hw, out_offset, block_prefix, N, out_pixels,
+                     query_idx, K, logit_scale, prob_thd, bg_idx, labels, conf, flags);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_topk_head_resized(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w,
+                                    int pad_t, int pad_l, int H, int W, int out_h, int out_w, const int32_t* query_idx, int K,
+                                    float logit_scale, int k, int32_t* classes, float* probs, int flags, sg_stream s) {
+  SG_REQUIRE(tile_logits && windows && query_idx && classes && probs, "sg_topk_head_resized: null pointer");
+  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && H > 0 && W > 0 && out_h > 0 && out_w > 0,
+             "sg_topk_head_resized: bad shape T=%d Q=%d gh=%d gw=%d up=%dx%d H=%d W=%d out=%dx%d", T, Q, gh, gw, up_h, up_w, H, W, out_h, out_w);
+  SG_REQUIRE(K > 0 && K <= Q, "sg_topk_head_resized: K=%d must lie in [1, Q=%d]", K, Q);
+  SG_REQUIRE(k >= 1 && k <= SG_TOPK_MAX && k <= K, "sg_topk_head_resized: k=%d must lie in [1, min(%d, K=%d)]", k, SG_TOPK_MAX, K);
+  SG_REQUIRE(cdiv(out_h, 4) < 65536, "sg_topk_head_resized: output too tall for one launch");
+  SG_RESIZED_REQUIRE_FLAGS("sg_topk_head_resized", flags);
+  SG_REQUIRE(flags != SG_RESIZED_STAGED || rs_fits(H, W, out_h, out_w),
+             "sg_topk_head_resized: the staged form does not fit: a block's footprint of %lld x %lld canvas pixels exceeds the stage of %d",
+             (long long)rs_span(4, H, out_h), (long long)rs_span(64, W, out_w), RS_STAGE_PIX);
+  auto kern = SG_TOPK_HEAD_DISPATCH(topk_head_resized_kernel, k);
+  hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(out_w, 64), (unsigned)cdiv(out_h, 4)), dim3(256), 0, as_stream(s), tile_logits, windows, T, Q,
+                     gh, gw, up_h, up_w, pad_t, pad_l, H, W, out_h, out_w, query_idx, K, logit_scale, k, classes, probs, flags);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_topk_head_resized_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh,
+                                          int gw, int up_h, int up_w, int pad_t, int pad_l, const int32_t* image_hw,
+                                          const int32_t* image_tiles, const int32_t* out_hw, const int64_t* out_offset,
+                                          const int64_t* block_prefix, int N, int64_t total_blocks, int64_t out_pixels,
+                                          const int32_t* query_idx, int K, float logit_scale, int k, int32_t* classes, float* probs, int flags,
+                                          sg_stream s) {
+  SG_REQUIRE(tile_logits && windows && tile_image && image_hw && image_tiles && out_hw && out_offset && block_prefix && query_idx && classes &&
+                 probs, "sg_topk_head_resized_multi: null pointer");
+  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && N > 0 && N <= T,
+             "sg_topk_head_resized_multi: bad shape T=%d Q=%d gh=%d gw=%d N=%d", T, Q, gh, gw, N);
+  SG_REQUIRE(K > 0 && K <= Q, "sg_topk_head_resized_multi: K=%d must lie in [1, Q=%d]", K, Q);
+  SG_REQUIRE(k >= 1 && k <= SG_TOPK_MAX && k <= K, "sg_topk_head_resized_multi: k=%d must lie in [1, min(%d, K=%d)]", k, SG_TOPK_MAX, K);
+  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "sg_topk_head_resized_multi: total_blocks=%lld outside (0, 2^31)", (long long)total_blocks);
+  SG_REQUIRE(out_pixels > 0, "sg_topk_head_resized_multi: out_pixels=%lld holds no image", (long long)out_pixels);
+  SG_RESIZED_REQUIRE_FLAGS("sg_topk_head_resized_multi", flags);
+  auto kern = SG_TOPK_HEAD_DISPATCH(topk_head_resized_multi_kernel, k);
+  hipLaunchKernelGGL(kern, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q, gh, gw, up_h, up_w,
+                     pad_t, pad_l, image_hw, image_tiles, out_hw, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale, k, classes,
+                     probs, flags);
   SG_LAUNCH_CHECK();
   return SG_OK;
 }

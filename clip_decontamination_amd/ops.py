@@ -522,6 +522,151 @@ def topk_head_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, i
     return cls, prb
 
 
+RESIZED_FORMS = {"auto": 0, "direct": 1, "staged": 2}                    # SG_RESIZED_* (include/segearth_hip.h)
+RESIZED_STAGE_PIX = 512                                                  # RS_STAGE_PIX (csrc/head.hip): 16 KiB per chunk of 8 queries
+
+
+def resized_footprint(canvas_hw, out_hw):
+    """(rows, columns) of the canvas that a block of 64 x 4 output pixels can touch: csrc/head.hip's rs_span."""
+    (h, w), (H, W) = canvas_hw, out_hw
+    return -(-4 * h // H) + 2, -(-64 * w // W) + 2
+
+
+def _resized_form(form: str, what: str, pairs) -> int:
+    if form not in RESIZED_FORMS:
+        raise ValueError(f"{what}: form={form!r} is none of {sorted(RESIZED_FORMS)}")
+    if form == "staged":
+        for chw, ohw in pairs:
+            r, c = resized_footprint(chw, ohw)
+            if r * c > RESIZED_STAGE_PIX:
+                raise ValueError(f"{what}: the staged form does not fit {tuple(chw)} -> {tuple(ohw)}: a block's footprint of {r} x {c} "
+                                 f"canvas pixels exceeds the stage of {RESIZED_STAGE_PIX}")
+    return RESIZED_FORMS[form]
+
+
+@on_tensor_device
+def label_head_resized(tile_logits, windows, up_hw, pad_tl, canvas_hw, out_hw, query_idx, num_classes: int, logit_scale: float,
+                       prob_thd: float, bg_idx: int, want_conf: bool = False, form: str = "auto"):
+    """sg_label_head_resized: ``label_head`` at another ``ori_shape`` -- stitch, count division, bilinear resize of the [h,w] canvas to
+    ``out_hw``, post-process -- with neither canvas.  -> labels int64 [1,H,W] (and conf f32 [H,W] with ``want_conf``), (H, W) = out_hw.
+    ``form``: "direct", "staged" (refused where a block's footprint does not fit the stage) or "auto"; the bytes do not depend on it."""
+    flags = _resized_form(form, "label_head_resized", [(canvas_hw, out_hw)])
+    lib = _lib.load()
+    tile_logits = _f32(tile_logits)
+    windows = windows.to(device=tile_logits.device, dtype=torch.int32).contiguous()
+    _require_gpu(tile_logits)
+    T, Q, gh, gw = tile_logits.shape
+    (h, w), (H, W) = canvas_hw, out_hw
+    qi = query_idx.to(device=tile_logits.device, dtype=torch.int32).contiguous()
+    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T:
+        raise ValueError(f"label_head_resized: {T} tiles of {Q} queries, but {windows.numel() // 4} windows and {qi.numel()} query indices")
+    labels = torch.empty(1, H, W, dtype=torch.int64, device=tile_logits.device)
+    conf = torch.empty(H, W, dtype=torch.float32, device=tile_logits.device) if want_conf else None
+    check(lib.sg_label_head_resized(ptr(tile_logits), ptr(windows), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1], h, w, H, W,
+                                    ptr(qi), int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx), ptr(labels), ptr(conf),
+                                    flags, stream_ptr()), "sg_label_head_resized")
+    return (labels, conf) if want_conf else labels
+
+
+def _resized_multi_args(what, tile_logits, windows, tile_image, image_hw, image_tiles, out_hw, query_idx):
+    """The descriptors the two resized multi-image entries share: (qi, windows, tile_image, i32 [canvas hw | tiles | out hw], i64
+    [out offsets | block prefix], pix, blocks) with the offsets and blocks counted in OUTPUT pixels."""
+    dev = tile_logits.device
+    T, Q = tile_logits.shape[:2]
+    N = len(image_hw)
+    qi = query_idx.to(device=dev, dtype=torch.int32).contiguous()
+    windows = torch.as_tensor(windows, dtype=torch.int32).to(dev).contiguous()
+    tile_image = torch.as_tensor(tile_image, dtype=torch.int32).to(dev).contiguous()
+    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T or int(tile_image.numel()) != T or len(image_tiles) != N or len(out_hw) != N:
+        raise ValueError(f"{what}: tile logits, windows, tile_image, image descriptors and query indices disagree in size")
+    if any(f < 0 or c <= 0 or f + c > T for f, c in image_tiles):
+        raise ValueError(f"{what}: image_tiles {list(image_tiles)} leave the {T} tiles")
+    pix = _prefix(h * w for h, w in out_hw)
+    blocks = _prefix(-(-w // 64) * -(-h // 4) for h, w in out_hw)
+    i32 = torch.tensor([list(hw) for hw in image_hw] + [list(ft) for ft in image_tiles] + [list(hw) for hw in out_hw],
+                       dtype=torch.int32).to(dev)
+    i64 = torch.tensor(pix[:-1] + blocks, dtype=torch.int64).to(dev)
+    return qi, windows, tile_image, i32, i64, pix, blocks
+
+
+@on_tensor_device
+def label_head_resized_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, out_hw, query_idx, num_classes: int,
+                             logit_scale: float, prob_thd: float, bg_idx: int, want_conf: bool = False, form: str = "auto"):
+    """sg_label_head_resized_multi: ``label_head_resized`` for N images in one launch (arguments as ``label_head_multi`` plus
+    ``out_hw`` [(H, W)] * N, each image's ori_shape; an image whose out_hw is its canvas size runs with identity taps).  -> (list of
+    labels int64 [1,H,W], the flat int64 buffer they are views of), plus the list of conf maps with ``want_conf``.  Equals
+    ``label_head_resized`` per image byte for byte."""
+    out_hw = [tuple(int(v) for v in s) for s in out_hw]
+    flags = _resized_form(form, "label_head_resized_multi", zip(image_hw, out_hw))
+    lib = _lib.load()
+    tile_logits = _f32(tile_logits)
+    _require_gpu(tile_logits)
+    T, Q, gh, gw = tile_logits.shape
+    N = len(image_hw)
+    qi, windows, tile_image, i32, i64, pix, blocks = _resized_multi_args("label_head_resized_multi", tile_logits, windows, tile_image,
+                                                                         image_hw, image_tiles, out_hw, query_idx)
+    labels = torch.empty(pix[-1], dtype=torch.int64, device=tile_logits.device)
+    conf = torch.empty(pix[-1], dtype=torch.float32, device=tile_logits.device) if want_conf else None
+    check(lib.sg_label_head_resized_multi(ptr(tile_logits), ptr(windows), ptr(tile_image), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0],
+                                          pad_tl[1], ptr(i32), ptr(i32[N:]), ptr(i32[2 * N:]), ptr(i64), ptr(i64[N:]), N, blocks[-1], pix[-1],
+                                          ptr(qi), int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx), ptr(labels),
+                                          ptr(conf), flags, stream_ptr()), "sg_label_head_resized_multi")
+    lab = [labels[pix[n]:pix[n + 1]].view(1, h, w) for n, (h, w) in enumerate(out_hw)]
+    if want_conf:
+        return lab, labels, [conf[pix[n]:pix[n + 1]].view(h, w) for n, (h, w) in enumerate(out_hw)]
+    return lab, labels
+
+
+@on_tensor_device
+def topk_head_resized(tile_logits, windows, up_hw, pad_tl, canvas_hw, out_hw, query_idx, num_classes: int, logit_scale: float, k: int,
+                      form: str = "auto"):
+    """sg_topk_head_resized: ``topk_head`` at another ``ori_shape`` (see ``label_head_resized``) -> (classes int32 [k,H,W], probs f32
+    [k,H,W]), (H, W) = out_hw.  Plane 0 is ``label_head_resized``'s label before the threshold and its conf, byte for byte."""
+    flags = _resized_form(form, "topk_head_resized", [(canvas_hw, out_hw)])
+    lib = _lib.load()
+    tile_logits = _f32(tile_logits)
+    windows = windows.to(device=tile_logits.device, dtype=torch.int32).contiguous()
+    _require_gpu(tile_logits)
+    T, Q, gh, gw = tile_logits.shape
+    (h, w), (H, W) = canvas_hw, out_hw
+    qi = query_idx.to(device=tile_logits.device, dtype=torch.int32).contiguous()
+    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T:
+        raise ValueError(f"topk_head_resized: {T} tiles of {Q} queries, but {windows.numel() // 4} windows and {qi.numel()} query indices")
+    kk = max(int(k), 0)
+    classes = torch.empty(kk, H, W, dtype=torch.int32, device=tile_logits.device)
+    probs = torch.empty(kk, H, W, dtype=torch.float32, device=tile_logits.device)
+    check(lib.sg_topk_head_resized(ptr(tile_logits), ptr(windows), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1], h, w, H, W,
+                                   ptr(qi), int(num_classes), float(logit_scale), int(k), ptr(classes), ptr(probs), flags, stream_ptr()),
+          "sg_topk_head_resized")
+    return classes, probs
+
+
+@on_tensor_device
+def topk_head_resized_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, out_hw, query_idx, num_classes: int,
+                            logit_scale: float, k: int, form: str = "auto"):
+    """sg_topk_head_resized_multi: ``topk_head_resized`` for N images in one launch (arguments as ``label_head_resized_multi`` with
+    ``k`` for the threshold) -> (list of classes int32 [k,H,W], list of probs f32 [k,H,W]): views at k * (the image's first output
+    pixel) of two flat buffers.  Equals ``topk_head_resized`` per image byte for byte."""
+    out_hw = [tuple(int(v) for v in s) for s in out_hw]
+    flags = _resized_form(form, "topk_head_resized_multi", zip(image_hw, out_hw))
+    lib = _lib.load()
+    tile_logits = _f32(tile_logits)
+    _require_gpu(tile_logits)
+    T, Q, gh, gw = tile_logits.shape
+    N, kk = len(image_hw), max(int(k), 0)
+    qi, windows, tile_image, i32, i64, pix, blocks = _resized_multi_args("topk_head_resized_multi", tile_logits, windows, tile_image,
+                                                                         image_hw, image_tiles, out_hw, query_idx)
+    classes = torch.empty(kk * pix[-1], dtype=torch.int32, device=tile_logits.device)
+    probs = torch.empty(kk * pix[-1], dtype=torch.float32, device=tile_logits.device)
+    check(lib.sg_topk_head_resized_multi(ptr(tile_logits), ptr(windows), ptr(tile_image), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0],
+                                         pad_tl[1], ptr(i32), ptr(i32[N:]), ptr(i32[2 * N:]), ptr(i64), ptr(i64[N:]), N, blocks[-1], pix[-1],
+                                         ptr(qi), int(num_classes), float(logit_scale), int(k), ptr(classes), ptr(probs), flags,
+                                         stream_ptr()), "sg_topk_head_resized_multi")
+    cls = [classes[kk * pix[n]:kk * pix[n + 1]].view(kk, h, w) for n, (h, w) in enumerate(out_hw)]
+    prb = [probs[kk * pix[n]:kk * pix[n + 1]].view(kk, h, w) for n, (h, w) in enumerate(out_hw)]
+    return cls, prb
+
+
 def topk_from_probs(probs, query_idx, k: int):
     """The canvas-route equivalent of ``topk_head`` in torch (host or device tensors): class probabilities [K,H,W] (what ``postprocess``
     returns) -> (classes int32 [k,H,W], probs f32 [k,H,W]) by a stable descending sort over the classes, so equal values keep ascending

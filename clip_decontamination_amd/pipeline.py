@@ -220,14 +220,15 @@ class TileSizeGroup:
 
 
 def plan_images(shapes: Sequence[Tuple[int, int]], stride, crop, patch: int, tiles_per_launch: int,
-                tile_bytes: Union[int, Callable[[Tuple[int, int]], int]] = 0, pixel_bytes: int = 0,
+                tile_bytes: Union[int, Callable[[Tuple[int, int]], int]] = 0, pixel_bytes: Union[int, Callable[[int], int]] = 0,
                 flush_bytes: Optional[int] = None) -> List[TileSizeGroup]:
     """Packs the sliding windows of images of any sizes into equal tower launches (pure host logic, no device).
 
     Images are grouped by window size (a launch shares one tile shape; images smaller than the crop form their own groups), groups
     in order of first appearance.  Within a group the windows of all its images are concatenated and cut by ``launch_chunks``,
     freely across image boundaries.  The group is further cut into flush groups: runs of whole images whose tile logits
-    (``tile_bytes`` per tile, or a function of the tile size) plus canvases (``pixel_bytes`` per pixel) stay within ``flush_bytes``;
+    (``tile_bytes`` per tile, or a function of the tile size) plus canvases (``pixel_bytes`` per pixel, or a function of the image's index
+    that returns the bytes of that image's outputs: they may have another size than the image) stay within ``flush_bytes``;
     an image that alone exceeds the bound is a flush group of its own.  ``patch`` is checked, the windows do not depend on it."""
     stride = (stride, stride) if isinstance(stride, int) else tuple(stride)
     crop = (crop, crop) if isinstance(crop, int) else tuple(crop)
@@ -258,7 +259,7 @@ def plan_images(shapes: Sequence[Tuple[int, int]], stride, crop, patch: int, til
         a, used = 0, 0
         for k in range(len(g.images)):
             H, W = g.shapes[k]
-            need = tb * g.n_tiles[k] + int(pixel_bytes) * H * W
+            need = tb * g.n_tiles[k] + (int(pixel_bytes(g.images[k])) if callable(pixel_bytes) else int(pixel_bytes) * H * W)
             if k > a and flush_bytes is not None and used + need > flush_bytes:
                 g.flush.append(_flush_group(g, a, k, tiles_per_launch))
                 a, used = k, 0
@@ -312,8 +313,20 @@ def _scene_hw(s: torch.Tensor) -> Tuple[int, int]:
     return (int(s.shape[0]), int(s.shape[1])) if s.dtype == torch.uint8 else (int(s.shape[-2]), int(s.shape[-1]))
 
 
+def _out_pixels(ori_shapes, i: int, scenes) -> int:
+    """Pixels of image i's outputs: its ori_shape, or its own size."""
+    o = ori_shapes[i] if ori_shapes is not None else None
+    h, w = (int(o[0]), int(o[1])) if o is not None else _scene_hw(scenes if torch.is_tensor(scenes) and scenes.dim() == 3 else scenes[i])
+    return h * w
+
+
 LABEL_HEADS = ("auto", "fused", "canvas")
 PROB_HEADS = LABEL_HEADS
+# How labels and the k best classes reach another ``ori_shape`` than the image's: "canvas" = stitch, resize the [Q,h,w] canvas to
+# [Q,H,W], post-process; "fused" = sg_label_head_resized / sg_topk_head_resized, the resize inside the head and neither canvas.  The
+# default stays "canvas" until the fused route has been measured to beat it by more than the run-to-run spread on the dataset shape
+# (DESIGN.md section 5 'Heads at another ori_shape').
+RESIZE_HEADS = ("canvas", "fused")
 # What prob_head="auto" does beyond ops.POSTPROCESS_MAX_Q queries (up to there it is the canvas route): the fused head only where it was
 # measured no slower than the canvas route at both Q = 130 and Q = 256.  It was slower at both (13.9 against 10.5 ms and 28.8 against
 # 20.3 ms, profiles/r08_bench_prob_head.jsonl, DESIGN.md section 5 'Probability head'), so "auto" is the canvas route everywhere.
@@ -336,7 +349,11 @@ class SegPipeline:
                  logit_scale: float = 50.0, prob_thd: float = 0.0, bg_idx: int = 0, apply_similarity_enhancement: bool = False,
                  upsampler=None, tiles_per_launch: int = 32, cross_tile_fusion: Optional[dict] = None, apply_ctd: bool = False,
                  tile_group=None, apply_layer_fusion: bool = False, layer_fusion_lambda: float = 0.5, label_head: str = "auto",
-                 prob_head: str = "auto", pamr_steps: int = 0, pamr_stride=(8, 16)):
+                 prob_head: str = "auto", pamr_steps: int = 0, pamr_stride=(8, 16), resize_head: str = "canvas"):
+        if resize_head not in RESIZE_HEADS:
+            raise ValueError(f"resize_head must be one of {RESIZE_HEADS}, got {resize_head!r}")
+        # labels / top-k at another ori_shape than the image's (RESIZE_HEADS); PAMR and whole-image inference keep the canvas route
+        self.resize_head = resize_head
         if label_head not in LABEL_HEADS:
             raise ValueError(f"label_head must be one of {LABEL_HEADS}, got {label_head!r}")
         if prob_head not in PROB_HEADS:
@@ -390,6 +407,10 @@ class SegPipeline:
             return False
         mode = getattr(self, "label_head", "auto")
         return mode == "fused" or (mode == "auto" and self.num_queries > ops.POSTPROCESS_MAX_Q)
+
+    def fused_resize_head(self) -> bool:
+        """Whether labels / top-k at another ``ori_shape`` run the resized heads (no canvas) instead of stitch + resize + post-process."""
+        return getattr(self, "resize_head", "canvas") == "fused" and getattr(self, "pamr_steps", 0) == 0
 
     def refine(self, canvas: torch.Tensor, guide: torch.Tensor) -> torch.Tensor:
         """PAMR on one image's logits [Q,H,W], in place where they are a contiguous f32 tensor.  ``guide``: the image (u8 [H,W,3] or
@@ -610,24 +631,47 @@ class SegPipeline:
         return torch.cat([buf[r, :, :yb[r + 1] - yb[r]] for r in range(world)], 1)
 
     def segment_scene(self, scene: torch.Tensor, stride, crop, group=None, gather_labels: bool = True, want_probs: bool = False,
-                      topk: int = 0):
+                      topk: int = 0, ori_shape=None):
         """The whole path to labels for one scene.  Sharded: every rank computes its tiles, stitches + labels ITS band; only the
         int64 label band (8 B per pixel instead of 4Q) is gathered.  -> labels [1,H,W] (or (band labels, first row) when
         ``gather_labels`` is False).  ``want_probs``: (probs [K,H,W], labels [1,H,W]) through ``probs_from_tiles``; not with tile
         sharding.  With PAMR on (``pamr_steps``) the canvas is stitched, refined under the scene and post-processed, whatever
         label_head / prob_head say; tile sharding is then refused (a band would need a halo of its neighbours' rows).
         ``topk`` > 0: (classes int32 [topk,H,W], probs f32 [topk,H,W]) through ``topk_from_tiles`` instead of labels; not together with
-        ``want_probs`` and not with tile sharding."""
+        ``want_probs`` and not with tile sharding.
+        ``ori_shape`` of another size than the scene: labels (or the ``topk`` planes) at that size; not with ``want_probs`` (use
+        ``segment_scenes``) and not with tile sharding.  ``resize_head="fused"`` without PAMR: sg_label_head_resized /
+        sg_topk_head_resized on the tile logits, no canvas; otherwise stitch, resize, PAMR when on, post-process."""
+        resize = ori_shape is not None and tuple(ori_shape) != _scene_hw(scene)
         if topk:
             if want_probs:
                 raise ValueError("segment_scene: topk and want_probs exclude each other (topk returns the k best class probabilities)")
             if group is not None or self.tile_group is not None:
                 raise ValueError(TOPK_TILE_GROUP)
             k = self.topk_k(topk)
+        if resize:
+            if want_probs:
+                raise ValueError("segment_scene: class probabilities at another ori_shape are not built here; use segment_scenes")
+            if group is not None or self.tile_group is not None:
+                raise ValueError("segment_scene: another ori_shape under tile_group sharding is not built (a canvas band does not map to "
+                                 "whole output rows); use forward_slide + postprocess")
+        if topk or resize:
             H, W, stride, crop, wins, tile_hw, pad_tl, up_hw, grid = self._geometry(scene, stride, crop)
             tl = self.tile_logits(scene, wins, tile_hw, grid_of_tiles=grid)
             win_dev = torch.tensor(wins, dtype=torch.int32, device=self.device)
-            return self.topk_from_tiles(tl, win_dev, up_hw, pad_tl, (H, W), k, guide=scene)
+            if not resize:
+                return self.topk_from_tiles(tl, win_dev, up_hw, pad_tl, (H, W), k, guide=scene)
+            out = tuple(int(v) for v in ori_shape)
+            if self.fused_resize_head():
+                if topk:
+                    return ops.topk_head_resized(tl, win_dev, up_hw, pad_tl, (H, W), out, self.query_idx, self.num_classes,
+                                                 self.logit_scale, k)
+                return ops.label_head_resized(tl, win_dev, up_hw, pad_tl, (H, W), out, self.query_idx, self.num_classes, self.logit_scale,
+                                              self.prob_thd, self.bg_idx)
+            canvas = ops.resize_bilinear(self._stitch(tl, win_dev, up_hw, pad_tl, (H, W)), out)
+            if topk:
+                return self.topk_from_logits(canvas, k, guide=scene)
+            return self.postprocess(self.refine(canvas, scene), want_probs=False)[1]
         if self.pamr_steps > 0 and (group is not None or self.tile_group is not None):
             raise ValueError(PAMR_TILE_GROUP)
         group = resolve_tile_group(group if group is not None else self.tile_group)
@@ -703,10 +747,11 @@ class SegPipeline:
             canvases, views = ops.stitch_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles)
             yield idx, canvases, views
 
-    def _packed_tiles(self, scenes, stride, crop, pixel_bytes: int):
+    def _packed_tiles(self, scenes, stride, crop, pixel_bytes):
         """Yields, per flush group, what a multi-image stitch takes: (image indices, tile logits, windows, image of each tile, up_hw,
         pad_tl, [(H, W)] per image, [(first tile, count)] per image) -- the packed tower over the group's chunks, cross-tile fusion per
-        image and the head.  ``pixel_bytes``: what the caller will allocate per image pixel (the planner's flush bound counts it)."""
+        image and the head.  ``pixel_bytes``: what the caller will allocate per image pixel, or for image i as a function of i (the
+        planner's flush bound counts it)."""
         if self.tile_group is not None:
             raise ValueError("packed inference shards images over ranks, not tiles: with tile_group set use forward_slide / "
                              "segment_scene per image")
@@ -802,7 +847,11 @@ class SegPipeline:
         ``topk`` > 0 (not with ``want_probs``): yields (image indices, list of probs f32 [topk,H,W], list of classes int32 [topk,H,W],
         None) -- the k best classes of every pixel.  At the images' own sizes and without PAMR that is one sg_topk_head_multi launch
         per flush group with no canvas (the planner counts 8 * topk bytes per pixel); otherwise the probabilities come as above and go
-        through ``ops.topk_from_probs`` image by image."""
+        through ``ops.topk_from_probs`` image by image.
+        ``resize_head="fused"`` without PAMR, when some image's ``ori_shape`` differs from its size: labels alone take one
+        sg_label_head_resized_multi launch, and ``topk`` one sg_topk_head_resized_multi launch, per flush group that holds such an image
+        (the resize runs inside the head, no canvas; the planner counts 8 or 8 * topk bytes per OUTPUT pixel); a flush group in which no
+        image differs runs what it runs without the option."""
         no_resize = ori_shapes is None or all(o is None for o in ori_shapes)
         if topk:
             if want_probs:
@@ -816,6 +865,21 @@ class SegPipeline:
                 for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(scenes, stride, crop, 8 * k):
                     cls, prb = ops.topk_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes,
                                                    self.logit_scale, k)
+                    yield idx, prb, cls, None
+                return
+            if self.fused_resize_head():
+                # some ori_shape differs: one sg_topk_head_resized_multi launch per flush group that holds such an image, today's kernel
+                # for a group that holds none; no canvas either way
+                for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(
+                        scenes, stride, crop, lambda i: 8 * k * _out_pixels(ori_shapes, i, scenes)):
+                    shapes = [tuple(hw) for hw in shapes]
+                    ohw = [shapes[n] if ori_shapes[i] is None else tuple(int(v) for v in ori_shapes[i]) for n, i in enumerate(idx)]
+                    if ohw == shapes:
+                        cls, prb = ops.topk_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes,
+                                                       self.logit_scale, k)
+                    else:
+                        cls, prb = ops.topk_head_resized_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, ohw, self.query_idx,
+                                                               self.num_classes, self.logit_scale, k)
                     yield idx, prb, cls, None
                 return
             for idx, prb, _, _ in self.label_groups(scenes, stride, crop, True, ori_shapes):
@@ -832,6 +896,32 @@ class SegPipeline:
                 prb, lab, flat = ops.prob_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes,
                                                      self.logit_scale, self.prob_thd, self.bg_idx)
                 yield idx, prb, lab, flat
+            return
+        if not want_probs and self.fused_resize_head() and not no_resize and any(
+                o is not None and tuple(o) != _scene_hw(s)
+                for o, s in zip(ori_shapes, [scenes] if torch.is_tensor(scenes) and scenes.dim() == 3 else scenes)):
+            # labels at another ori_shape with no canvas: one sg_label_head_resized_multi launch per flush group that holds such an image;
+            # a group that holds none runs today's kernels
+            for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(
+                    scenes, stride, crop, lambda i: 8 * _out_pixels(ori_shapes, i, scenes)):
+                shapes = [tuple(hw) for hw in shapes]
+                ohw = [shapes[n] if ori_shapes[i] is None else tuple(int(v) for v in ori_shapes[i]) for n, i in enumerate(idx)]
+                if ohw != shapes:
+                    lab, flat = ops.label_head_resized_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, ohw, self.query_idx,
+                                                             self.num_classes, self.logit_scale, self.prob_thd, self.bg_idx)
+                elif self.fused_label_head():
+                    lab, flat = ops.label_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes,
+                                                     self.logit_scale, self.prob_thd, self.bg_idx)
+                else:
+                    canvases, views = ops.stitch_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles)
+                    if self.num_queries <= ops.POSTPROCESS_MAX_Q:
+                        _, lab, flat = ops.postprocess_multi(canvases, shapes, self.query_idx, self.num_classes, self.logit_scale,
+                                                             self.prob_thd, self.bg_idx, shapes, False, flat_labels=True)
+                    else:                                                 # label_head="canvas" beyond 64 queries: image by image
+                        flat = torch.cat([self.postprocess(c, want_probs=False)[1].reshape(-1) for c in views])
+                        pix = ops._prefix(h * w for h, w in shapes)
+                        lab = [flat[pix[n]:pix[n + 1]].view(1, *shapes[n]) for n in range(len(shapes))]
+                yield idx, [None] * len(idx), lab, flat
             return
         if not want_probs and no_resize and self.fused_label_head():
             for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(scenes, stride, crop, 8):

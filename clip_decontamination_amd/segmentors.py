@@ -130,9 +130,14 @@ class _HipSegmentorBase(_Base):
                slide_crop, cls_token_lambda, bg_idx, apply_sim_feat_up, sim_feat_up_cfg, global_debias_factor=0.0,
                checkpoint=None, text_features=None, text_encoder: Optional[Callable] = None, precision="f16x2",
                synthetic_ok=False, tiles_per_launch=None, jbu_checkpoint_ok=True, tokenizer: Optional[Callable] = None, tile_group=None,
-               label_head="auto", prob_head="auto", pamr_steps=0, pamr_stride=(8, 16)):
+               label_head="auto", prob_head="auto", pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas"):
         from . import ops
-        from .pipeline import LABEL_HEADS, PAMR_TILE_GROUP, PROB_HEADS
+        from .pipeline import LABEL_HEADS, PAMR_TILE_GROUP, PROB_HEADS, RESIZE_HEADS
+        if resize_head not in RESIZE_HEADS:
+            raise ValueError(f"resize_head must be one of {RESIZE_HEADS}, got {resize_head!r}")
+        # labels and the k best classes at another ori_shape than the image's: "canvas" = stitch, resize the canvas, post-process; "fused" =
+        # sg_label_head_resized / sg_topk_head_resized, the resize inside the head and no canvas (not with PAMR or whole-image inference)
+        self.resize_head = resize_head
         if label_head not in LABEL_HEADS:
             raise ValueError(f"label_head must be one of {LABEL_HEADS}, got {label_head!r}")
         if prob_head not in PROB_HEADS:
@@ -255,7 +260,7 @@ class _HipSegmentorBase(_Base):
                            tile_group=getattr(self, "tile_group", None), apply_layer_fusion=getattr(self, "apply_layer_fusion", False),
                            layer_fusion_lambda=getattr(self, "layer_fusion_lambda", 0.5), label_head=getattr(self, "label_head", "auto"),
                            prob_head=getattr(self, "prob_head", "auto"), pamr_steps=getattr(self, "pamr_steps", 0),
-                           pamr_stride=getattr(self, "pamr_stride", (8, 16)))
+                           pamr_stride=getattr(self, "pamr_stride", (8, 16)), resize_head=getattr(self, "resize_head", "canvas"))
 
     def forward_feature(self, img, logit_size=None, tile_h_idx=None, tile_w_idx=None):
         """Reference segmentor.py:286-392.  img [B,3,H,W] -> logits [B,Q,h,w]."""
@@ -318,7 +323,7 @@ class _HipSegmentorBase(_Base):
         return self.postprocess_result(seg_logits, data_samples)
 
     @torch.no_grad()
-    def predict_many(self, inputs, data_samples=None):
+    def predict_many(self, inputs, data_samples=None, ori_shapes=None):
         """``predict`` for many images with their sliding windows packed into shared tower launches and one stitch + one post-process
         launch per flush group (SegPipeline.segment_scenes).  inputs: a list of [3,H,W] images of any sizes or a [B,3,H,W] batch.
         Fills each data sample exactly as ``predict`` does (seg_logits, pred_sem_seg, result_dir / heatmap_dir PNGs) and returns
@@ -329,13 +334,28 @@ class _HipSegmentorBase(_Base):
         label head, one launch per flush group.  With the fused probability head selected (``prob_head``) and every ``ori_shape`` equal
         to its image's size, data samples are filled from one sg_prob_head_multi launch per flush group for any number of queries: no
         canvas, and nothing image by image.  With PAMR on (``pamr_steps > 0``) every flush group takes the canvas route and each image's
-        canvas is refined before the post-process (SegPipeline.label_groups)."""
+        canvas is refined before the post-process (SegPipeline.label_groups).
+        ``ori_shapes`` (only with ``data_samples=None``; data samples carry their own): one (H, W) or None per image, the size of that
+        image's label map.  With ``resize_head="fused"`` the resize runs inside the label head (sg_label_head_resized_multi, one launch
+        per flush group, no canvas); otherwise the canvas is stitched, resized and post-processed."""
+        if ori_shapes is not None and data_samples is not None:
+            raise ValueError("predict_many: ori_shapes goes with data_samples=None; data samples carry their own ori_shape")
         batch = torch.is_tensor(inputs)
         imgs = inputs.float() if batch else [x[0].float() if x.dim() == 4 else x.float() for x in inputs]
         n = imgs.shape[0] if batch else len(imgs)
         if data_samples is not None and len(data_samples) != n:
             raise ValueError(f"predict_many: {n} images but {len(data_samples)} data samples")
+        if ori_shapes is not None and len(ori_shapes) != n:
+            raise ValueError(f"predict_many: {n} images but {len(ori_shapes)} ori_shapes")
         if self.slide_crop <= 0:                             # whole-image inference (forward_feature) has no windows to pack
+            if data_samples is None and ori_shapes is not None:
+                pipe = self._pipeline()
+                out = []
+                for i in range(n):
+                    size = tuple(imgs[i].shape[-2:]) if ori_shapes[i] is None else tuple(ori_shapes[i])
+                    lg = pipe.refine(pipe.forward_feature(imgs[i][None], size)[0].float().contiguous(), imgs[i])
+                    out.append(pipe.postprocess(lg, want_probs=False)[1])
+                return out
             if data_samples is None:
                 return [self.predict(imgs[i][None], None) for i in range(n)]
             for i in range(n):
@@ -343,7 +363,7 @@ class _HipSegmentorBase(_Base):
             return data_samples
         pipe = self._pipeline()
         if data_samples is None:
-            return pipe.segment_scenes(imgs, self.slide_stride, self.slide_crop, want_probs=False)
+            return pipe.segment_scenes(imgs, self.slide_stride, self.slide_crop, want_probs=False, ori_shapes=ori_shapes)
         ori = [tuple(ds.metainfo["ori_shape"][:2]) for ds in data_samples]
         probs, labels = pipe.segment_scenes(imgs, self.slide_stride, self.slide_crop, want_probs=True, ori_shapes=ori)
         for i, ds in enumerate(data_samples):
@@ -359,7 +379,9 @@ class _HipSegmentorBase(_Base):
         Sliding-window inference at the images' own sizes without PAMR runs the fused head (sg_topk_head_multi, one launch per flush
         group): neither the [Q,H,W] canvas nor the [K,H,W] probabilities exist, and a class that owns no query is never listed.  With
         PAMR on, an ``ori_shape`` of another size, or whole-image inference (``slide_crop <= 0``) the canvas route of ``predict`` runs
-        (stitch, resize, PAMR, post-process) and ``ops.topk_from_probs`` sorts its probabilities.  ``tile_group`` sharding is refused."""
+        (stitch, resize, PAMR, post-process) and ``ops.topk_from_probs`` sorts its probabilities -- except that with
+        ``resize_head="fused"`` and no PAMR another ``ori_shape`` runs sg_topk_head_resized_multi, one launch per flush group and no
+        canvas.  ``tile_group`` sharding is refused."""
         from .pipeline import TOPK_TILE_GROUP
         if getattr(self, "tile_group", None) is not None:
             raise ValueError(TOPK_TILE_GROUP)
@@ -393,7 +415,7 @@ class _HipSegmentorBase(_Base):
             self._write_maps(probs, seg_pred, sample, i)
 
     @torch.no_grad()
-    def evaluate(self, inputs, gt_maps, metric=None, reduce_zero_label=False, ignore_index=255, iou_metrics=("mIoU",)):
+    def evaluate(self, inputs, gt_maps, metric=None, reduce_zero_label=False, ignore_index=255, iou_metrics=("mIoU",), at_gt_size=False):
         """Labels to score without leaving the device: what the reference's ``test_evaluator = dict(type='IoUMetric', ...)`` reports.
         inputs: as ``predict_many``; gt_maps: one [H,W] / [1,H,W] uint8 or int64 tensor or numpy array per image, of the image's size.
         Returns ``(metric.compute(), metric)``; pass ``metric`` back in to accumulate over the calls of a dataset loop (its own
@@ -402,7 +424,10 @@ class _HipSegmentorBase(_Base):
         per flush group over its flat label buffer, and only the (K+1) x (K+1) table comes back.  Whole-image inference
         (``slide_crop <= 0``) goes image by image through ``predict``.  ``tile_group`` sharding is refused here (counting each rank's
         band against the matching rows of the truth is not built yet: DESIGN.md section 8); score per rank over whole images and call
-        ``metric.reduce(group)``.  With PAMR on (``pamr_steps > 0``) the labels come from the refined canvases (SegPipeline.label_groups)."""
+        ``metric.reduce(group)``.  With PAMR on (``pamr_steps > 0``) the labels come from the refined canvases (SegPipeline.label_groups).
+        ``at_gt_size``: a truth map of any size is accepted; its shape becomes that image's ``ori_shape`` and the labels are produced at
+        that size and counted (the configs that resize the image before inference and score at the original size).  The route follows
+        ``resize_head``: sg_label_head_resized_multi with "fused", stitch + resize + post-process with "canvas"."""
         from .metrics import IoUMetric
         if getattr(self, "tile_group", None) is not None:
             raise ValueError("evaluate: tile_group sharding is not supported (each rank would have to count its own band against the "
@@ -421,9 +446,16 @@ class _HipSegmentorBase(_Base):
             raise ValueError(f"evaluate: {n} images but {len(gt_maps)} ground-truth maps")
         dev = self.query_features.device
         gts = [torch.as_tensor(g) for g in gt_maps]
+        ori = None
+        if at_gt_size:
+            if any(g.dim() not in (2, 3) or (g.dim() == 3 and g.shape[0] != 1) or g.numel() == 0 for g in gts):
+                raise ValueError("evaluate: a ground-truth map must be a non-empty [H,W] or [1,H,W]")
+            ori = [tuple(int(v) for v in g.shape[-2:]) for g in gts]
+            if all(o == tuple(imgs[i].shape[-2:]) for i, o in enumerate(ori)):
+                ori = None                                                   # nothing to resize: today's routes
         for i, g in enumerate(gts):
             hw = tuple(imgs[i].shape[-2:])
-            if tuple(g.shape) not in (hw, (1,) + hw):
+            if not at_gt_size and tuple(g.shape) not in (hw, (1,) + hw):
                 raise ValueError(f"evaluate: ground truth {i} has shape {tuple(g.shape)}, image {i} is {hw}")
         dtype = torch.uint8 if all(g.dtype == torch.uint8 for g in gts) else torch.int64
         off = [0]
@@ -434,10 +466,11 @@ class _HipSegmentorBase(_Base):
         else:
             gt_flat = torch.cat([g.reshape(-1).to(device=dev, dtype=dtype) for g in gts])
         if self.slide_crop <= 0:                                             # whole-image inference has no windows to pack
+            labs = self.predict_many(imgs, None, ori_shapes=ori) if at_gt_size else [self.predict(imgs[i][None], None) for i in range(n)]
             for i in range(n):
-                metric.add(self.predict(imgs[i][None], None).reshape(-1), gt_flat[off[i]:off[i + 1]])
+                metric.add(labs[i].reshape(-1), gt_flat[off[i]:off[i + 1]])
             return metric.compute(), metric
-        for idx, _, _, flat in self._pipeline().label_groups(imgs, self.slide_stride, self.slide_crop, want_probs=False):
+        for idx, _, _, flat in self._pipeline().label_groups(imgs, self.slide_stride, self.slide_crop, want_probs=False, ori_shapes=ori):
             if idx == list(range(idx[0], idx[0] + len(idx))):                # the group's images are neighbours in the call: a slice
                 gt = gt_flat[off[idx[0]]:off[idx[-1] + 1]]
             else:                                                            # tile-size groups interleave images: gather on the device
@@ -522,7 +555,7 @@ class SegmentorEx(_HipSegmentorBase):
                  # -- drop-in extras (see module docstring) --
                  checkpoint=None, text_features=None, text_encoder=None, precision="f16x2", synthetic_ok=False, tiles_per_launch=None,
                  tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, pack_images=False, label_head="auto", prob_head="auto",
-                 pamr_steps=0, pamr_stride=(8, 16)):
+                 pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas"):
         data_preprocessor = SegDataPreProcessor(mean=list(Wt.PIXEL_MEAN), std=list(Wt.PIXEL_STD), bgr_to_rgb=True)
         super().__init__(data_preprocessor=data_preprocessor)
         if model_type == "GEM":
@@ -531,7 +564,8 @@ class SegmentorEx(_HipSegmentorBase):
         visual = self._setup(clip_type, vit_type, model_type, name_path, device, ignore_residual, prob_thd, logit_scale, slide_stride,
                              slide_crop, cls_token_lambda, bg_idx, _to_bool(apply_sim_feat_up), sim_feat_up_cfg, global_debias_factor,
                              checkpoint, text_features, text_encoder, precision, synthetic_ok, tiles_per_launch, tokenizer=tokenizer,
-                             tile_group=tile_group, label_head=label_head, prob_head=prob_head, pamr_steps=pamr_steps, pamr_stride=pamr_stride)
+                             tile_group=tile_group, label_head=label_head, prob_head=prob_head, pamr_steps=pamr_steps, pamr_stride=pamr_stride,
+                             resize_head=resize_head)
         # opt-in extra: kwargs of the reference's CrossTileFusion (cross_tile_fusion.py:24-60), which the reference never calls (R2)
         self.cross_tile_fusion_cfg = cross_tile_fusion_cfg
         self.apply_ctd = _to_bool(apply_ctd)                                # segmentor.py:184-194, 339-365: DBSCAN + cluster debias, on the device here
@@ -566,7 +600,7 @@ class Segmentor(_HipSegmentorBase):
                  sim_feat_up_cfg=dict(model_name="jbu_one", model_path="your/model/path"),
                  checkpoint=None, text_features=None, text_encoder=None, precision="f16x2", synthetic_ok=False, tiles_per_launch=None,
                  tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, apply_outlier_suppression=False, outlier_suppression_cfg=None,
-                 pack_images=False, label_head="auto", prob_head="auto", pamr_steps=0, pamr_stride=(8, 16)):
+                 pack_images=False, label_head="auto", prob_head="auto", pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas"):
         data_preprocessor = SegDataPreProcessor(mean=list(Wt.PIXEL_MEAN), std=list(Wt.PIXEL_STD), bgr_to_rgb=True)
         super().__init__(data_preprocessor=data_preprocessor)
         if model_type == "GEM" and cls_token_lambda != 0:
@@ -574,7 +608,8 @@ class Segmentor(_HipSegmentorBase):
         self._setup(clip_type, vit_type, model_type, name_path, device, ignore_residual, prob_thd, logit_scale, slide_stride,
                     slide_crop, cls_token_lambda, bg_idx, apply_sim_feat_up, sim_feat_up_cfg, 0.0,
                     checkpoint, text_features, text_encoder, precision, synthetic_ok, tiles_per_launch, tokenizer=tokenizer,
-                    tile_group=tile_group, label_head=label_head, prob_head=prob_head, pamr_steps=pamr_steps, pamr_stride=pamr_stride)
+                    tile_group=tile_group, label_head=label_head, prob_head=prob_head, pamr_steps=pamr_steps, pamr_stride=pamr_stride,
+                             resize_head=resize_head)
         # opt-in extra: kwargs of the reference's CrossTileFusion (cross_tile_fusion.py:24-60), which the reference never calls (R2)
         self.cross_tile_fusion_cfg = cross_tile_fusion_cfg
         self.output_cls_token = cls_token_lambda != 0

@@ -311,6 +311,54 @@ int sg_topk_head_multi(const float* tile_logits, const int32_t* windows, const i
                        int up_h, int up_w, int pad_t, int pad_l, const int32_t* image_hw, const int32_t* image_tiles,
                        const int64_t* out_offset, const int64_t* block_prefix, int N, int64_t total_blocks, int64_t out_pixels,
                        const int32_t* query_idx, int K, float logit_scale, int k, int32_t* classes, float* probs, sg_stream s);
+/* ---- the label and top-k heads at another ori_shape ----------------------------------------------------------------------------------
+ * segmentor.py:447-449 (preds / count, then the bilinear resize to ori_shape) fused into sg_label_head / sg_topk_head: the outputs are
+ * [out_h, out_w] maps over the [H, W] canvas, and neither the canvas nor the resized canvas exists.  Output pixel (Y, X) takes the
+ * align_corners=False taps of sg_resize_bilinear along each axis, the stitched value of each of its four canvas pixels as sg_stitch
+ * defines it (covering tiles in raster order, divided by that pixel's own count, 0 where no tile covers -- the division comes BEFORE the
+ * blend, neighbouring taps can have different counts), blends them top row, bottom row, then the two, and hands the result to the
+ * per-query statements of the unresized head.  Taps, gather and blend are compiled with every product rounded (no fused multiply-add),
+ * so against sg_stitch + sg_resize_bilinear + sg_postprocess a value is within a few f32 roundings, not byte-identical; with
+ * out = (H, W) the taps are the identity and the same kernel runs (it does not dispatch to the unresized entry).
+ * flags picks how a block of 64 x 4 output pixels gets its canvas values; both forms call one device function per canvas pixel and give
+ * the same bytes:
+ *   SG_RESIZED_DIRECT  every thread gathers its own four canvas pixels; any scale;
+ *   SG_RESIZED_STAGED  the block stitches its canvas footprint, (ceil(4 H / out_h) + 2) x (ceil(64 W / out_w) + 2) pixels at most, once
+ *                      per chunk of 8 queries into 16 KiB of LDS and every thread blends from there; refused when that product exceeds
+ *                      512 pixels;
+ *   SG_RESIZED_AUTO    staged where it fits and the output is larger than the canvas along both axes (measured 2.1 to 2.8 times the
+ *                      direct form's speed at 448 -> 1024 and at 1.5x), direct otherwise (at the canvas's own size direct was 5 to 10 %
+ *                      faster; a mixed up / down scale was not measured). */
+#define SG_RESIZED_AUTO 0
+#define SG_RESIZED_DIRECT 1
+#define SG_RESIZED_STAGED 2
+/* sg_label_head_resized: sg_label_head's arguments, outputs and contract with labels int64 [out_h,out_w] and conf f32 [out_h,out_w]. */
+int sg_label_head_resized(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t,
+                          int pad_l, int H, int W, int out_h, int out_w, const int32_t* query_idx, int K, float logit_scale,
+                          float prob_thd, int bg_idx, int64_t* labels, float* conf, int flags, sg_stream s);
+/* sg_label_head_resized_multi: the tiles of N images in one launch.  image_hw[n] is the canvas size and image_tiles[n] the tiles as in
+ * sg_stitch_multi; out_hw[n] is the image's ori_shape, out_offset[n] its first pixel in the flat outputs, block_prefix [N+1] the
+ * exclusive prefix sum of ceil(out_w / 64) * ceil(out_h / 4), out_pixels the size of `labels` (sg_postprocess_multi's layout: canvas
+ * size, output size, offsets in output pixels).  A descriptor that would leave the buffers makes its blocks return without writing.
+ * Byte-identical to sg_label_head_resized per image.  An image whose footprint does not fit the stage runs the direct form whatever
+ * flags says (the sizes are device arrays; a caller that wants the refusal checks them itself). */
+int sg_label_head_resized_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh, int gw,
+                                int up_h, int up_w, int pad_t, int pad_l, const int32_t* image_hw, const int32_t* image_tiles,
+                                const int32_t* out_hw, const int64_t* out_offset, const int64_t* block_prefix, int N, int64_t total_blocks,
+                                int64_t out_pixels, const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx,
+                                int64_t* labels, float* conf, int flags, sg_stream s);
+/* sg_topk_head_resized: sg_topk_head's arguments, outputs and contract with planes [k,out_h,out_w]; plane 0 is
+ * sg_label_head_resized's label before the threshold and its conf, byte for byte. */
+int sg_topk_head_resized(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t,
+                         int pad_l, int H, int W, int out_h, int out_w, const int32_t* query_idx, int K, float logit_scale, int k,
+                         int32_t* classes, float* probs, int flags, sg_stream s);
+/* sg_topk_head_resized_multi: descriptors as sg_label_head_resized_multi; the planes [k,out_h,out_w] of image n start at
+ * k * out_offset[n] elements of `classes` and `probs`, which hold k * out_pixels.  Byte-identical to sg_topk_head_resized per image. */
+int sg_topk_head_resized_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh, int gw,
+                               int up_h, int up_w, int pad_t, int pad_l, const int32_t* image_hw, const int32_t* image_tiles,
+                               const int32_t* out_hw, const int64_t* out_offset, const int64_t* block_prefix, int N, int64_t total_blocks,
+                               int64_t out_pixels, const int32_t* query_idx, int K, float logit_scale, int k, int32_t* classes,
+                               float* probs, int flags, sg_stream s);
 /* Label / confidence images of postprocess_result (segmentor.py:501-531): mask_rgb [H,W,3] = palette[clip(label)] (_colorize_mask,
  * :580-590); heat_rgb [H,W,3] = (g, 0, 255-g) with g = uint8(clip(max_k probs, 0, 1) * 255) (_to_colormap without OpenCV, :604-608;
  * OpenCV's JET table is not reproduced).  Either output may be NULL. */
