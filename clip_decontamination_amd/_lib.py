@@ -157,6 +157,13 @@ SIGNATURES = {
     "sg_pamr_affinity": (I, [P, I, I, C.POINTER(I), I, P, P]),
     "sg_pamr_step": (I, [P, P, P, I, I, I, C.POINTER(I), I, P]),
     "sg_pamr": (I, [P, P, I, I, I, C.POINTER(I), I, I, P, Z, P]),
+    "sg_class_area": (I, [P, L, I, P, P]),
+    "sg_class_area_multi": (I, [P, P, P, P, I, L, L, I, P, P]),
+    "sg_area_keep": (I, [P, I, I, I, C.c_double, P, P]),
+    "sg_area_filter_probs": (I, [P, P, P, I, I, I, F, I, P, P]),
+    "sg_area_filter_probs_multi": (I, [P, P, P, P, P, P, I, L, L, I, F, I, P, P]),
+    "sg_area_relabel": (I, [P, P, I, I, I, I, I, I, I, I, I, I, P, I, F, F, I, P, P, P, P]),
+    "sg_area_relabel_multi": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, I, L, L, P, I, F, F, I, P, P, P, P]),
 }
 
 _lib = None

@@ -1178,6 +1178,85 @@ __global__ __launch_bounds__(256, QMAX > 16 ? 4 : 1) void prob_head_multi_kernel
                         bg_idx, probs, labels, ib.off);
 }
 
+// ---- area_thd on the labels-only route: the second decision after sg_label_head, no canvas and no probability planes -----------------
+// labels [H,W] hold the first-pass labels l0 (sg_label_head with prob_thd = 0), conf its conf, keep [K] the classes that survive
+// (sg_area_keep).  A 64 x 4 block in which every first label is kept gathers nothing: l0 is still the best kept class and conf its
+// probability, so the block writes conf < prob_thd ? bg_idx : l0.  A block that holds a dropped label repeats label_head_block for all
+// its pixels with the best pair restricted to kept classes: the per-chunk statements (scaled logit, chunk maximum, rescale of the sum,
+// sum of exp) are that function's, copied -- label_head_block itself is not touched, its machine code stays what it is -- so the block's
+// output is sg_label_head's on a query_idx whose dropped queries are -1.  Dropped classes still take part in the softmax sum.
+// The vote is one __syncthreads_or per block; which path a block takes depends on its own pixels alone: repeats are byte-identical.
+__device__ __forceinline__ void area_relabel_block(const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
+                                                   const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw,
+                                                   int up_h, int up_w, int pad_t, int pad_l, int H, int W, int bx0, int by0,
+                                                   const int32_t* __restrict__ query_idx, int K, float logit_scale, float prob_thd,
+                                                   int bg_idx, const int32_t* __restrict__ keep, const float* __restrict__ conf,
+                                                   int64_t* __restrict__ labels) {
+  const int x = bx0 + (threadIdx.x & 63);
+  const int y = __builtin_amdgcn_readfirstlane(by0 + (threadIdx.x >> 6));
+  const bool inside = y < H && x < W;
+  const int64_t o = (int64_t)y * W + x;
+  int64_t l0 = 0;
+  float cf0 = 0.f;
+  bool dropped = false;
+  if (inside) {
+    l0 = labels[o];
+    cf0 = conf[o];
+    dropped = !((uint64_t)l0 < (uint64_t)K && keep[l0] != 0);
+  }
+  if (!__syncthreads_or(dropped)) {                                        // block-uniform
+    if (inside) labels[o] = cf0 < prob_thd ? bg_idx : l0;
+    return;
+  }
+  float vmax = -INFINITY, sum = 0.f, best = -INFINITY;
+  int best_c = 0;
+  stitch_block(tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, bx0, by0,
+               [&](int, int, int q0, float (&acc)[ST_QC], float cnt) {
+#pragma clang fp contract(off)        // the scaled logit is rounded before the subtraction, as postprocess_kernel compiles it
+                 float cm = -INFINITY;
+#pragma unroll
+                 for (int k = 0; k < ST_QC; ++k)
+                   if (q0 + k < Q) { acc[k] = (cnt > 0.f ? acc[k] / cnt : 0.f) * logit_scale; cm = fmaxf(cm, acc[k]); }
+                 if (cm > vmax) { sum *= expf(vmax - cm); vmax = cm; }            // the first chunk: sum = 0 * exp(-inf) = 0
+#pragma unroll
+                 for (int k = 0; k < ST_QC; ++k)
+                   if (q0 + k < Q) {
+                     sum += expf(acc[k] - vmax);
+                     const int c = K == Q ? q0 + k : query_idx[q0 + k];
+                     if (c >= 0 && c < K && keep[c] != 0 && (acc[k] > best || (acc[k] == best && c < best_c))) { best = acc[k]; best_c = c; }
+                   }
+               });
+  if (!inside) return;
+  const float cf = expf(best - vmax) / sum;
+  labels[o] = cf < prob_thd ? bg_idx : best_c;
+}
+
+__global__ __launch_bounds__(256) void area_relabel_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows,
+                                                           int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t, int pad_l, int H,
+                                                           int W, const int32_t* __restrict__ query_idx, int K, float logit_scale,
+                                                           float prob_thd, int bg_idx, const int32_t* __restrict__ keep,
+                                                           const float* __restrict__ conf, int64_t* __restrict__ labels) {
+  area_relabel_block(tile_logits, windows, nullptr, 0, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, blockIdx.x * 64, blockIdx.y * 4,
+                     query_idx, K, logit_scale, prob_thd, bg_idx, keep, conf, labels);
+}
+
+// The tiles of N images (sg_label_head_multi's descriptors); keep [N,K], conf and labels of image n at out_offset[n] pixels.
+__global__ __launch_bounds__(256) void area_relabel_multi_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows,
+                                                                 const int32_t* __restrict__ tile_image, int T, int Q, int gh, int gw,
+                                                                 int up_h, int up_w, int pad_t, int pad_l,
+                                                                 const int32_t* __restrict__ image_hw, const int32_t* __restrict__ image_tiles,
+                                                                 const int64_t* __restrict__ out_offset, const int64_t* __restrict__ block_prefix,
+                                                                 int N, int64_t out_pixels, const int32_t* __restrict__ query_idx, int K,
+                                                                 float logit_scale, float prob_thd, int bg_idx,
+                                                                 const int32_t* __restrict__ keep, const float* __restrict__ conf,
+                                                                 int64_t* __restrict__ labels) {
+  ImageBlock ib;
+  if (!image_block(image_hw, image_tiles, out_offset, block_prefix, N, T, 1, out_pixels, ib)) return;
+  area_relabel_block(tile_logits + (int64_t)ib.t_first * Q * gh * gw, windows + (int64_t)ib.t_first * 4, tile_image + ib.t_first, ib.n,
+                     ib.n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, ib.H, ib.W, ib.bx0, ib.by0, query_idx, K, logit_scale, prob_thd, bg_idx,
+                     keep + (int64_t)ib.n * K, conf + ib.off, labels + ib.off);
+}
+
 // ---- label / confidence images (segmentor.py:501-531, 580-608) ---------------------------------------------------------
 // mask  = palette[clip(label, 0, K-1)]                                (_colorize_mask)
 // heat  = (g, 0, 255 - g), g = uint8(clip(nan_to_num(max_k probs), 0, 1) * 255)   (_to_colormap, the branch without OpenCV)
@@ -1662,6 +1741,43 @@ extern "C" int sg_topk_head_resized_multi(const float* tile_logits, const int32_
   hipLaunchKernelGGL(kern, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q, gh, gw, up_h, up_w,
                      pad_t, pad_l, image_hw, image_tiles, out_hw, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale, k, classes,
                      probs, flags);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_area_relabel(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t,
+                               int pad_l, int H, int W, const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx,
+                               const int32_t* keep, const float* conf, int64_t* labels, sg_stream s) {
+  SG_REQUIRE(tile_logits && windows && query_idx && keep && conf && labels, "sg_area_relabel: null pointer");
+  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && H > 0 && W > 0,
+             "sg_area_relabel: bad shape T=%d Q=%d gh=%d gw=%d up=%dx%d H=%d W=%d", T, Q, gh, gw, up_h, up_w, H, W);
+  SG_REQUIRE(K > 0 && K <= Q, "sg_area_relabel: K=%d must lie in [1, Q=%d]", K, Q);
+  SG_REQUIRE(K <= SG_AREA_MAX_K, "sg_area_relabel: K=%d exceeds %d (SG_AREA_MAX_K, the limit of sg_class_area)", K, SG_AREA_MAX_K);
+  SG_REQUIRE(bg_idx >= 0 && bg_idx < K, "sg_area_relabel: bg_idx=%d outside [0, K=%d)", bg_idx, K);
+  SG_REQUIRE(cdiv(H, 4) < 65536, "sg_area_relabel: canvas too tall for one launch");
+  hipLaunchKernelGGL(area_relabel_kernel, dim3((unsigned)cdiv(W, 64), (unsigned)cdiv(H, 4)), dim3(256), 0, as_stream(s), tile_logits, windows,
+                     T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, query_idx, K, logit_scale, prob_thd, bg_idx, keep, conf, labels);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_area_relabel_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh, int gw,
+                                     int up_h, int up_w, int pad_t, int pad_l, const int32_t* image_hw, const int32_t* image_tiles,
+                                     const int64_t* out_offset, const int64_t* block_prefix, int N, int64_t total_blocks, int64_t out_pixels,
+                                     const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx, const int32_t* keep,
+                                     const float* conf, int64_t* labels, sg_stream s) {
+  SG_REQUIRE(tile_logits && windows && tile_image && image_hw && image_tiles && out_offset && block_prefix && query_idx && keep && conf && labels,
+             "sg_area_relabel_multi: null pointer");
+  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && N > 0 && N <= T,
+             "sg_area_relabel_multi: bad shape T=%d Q=%d gh=%d gw=%d N=%d", T, Q, gh, gw, N);
+  SG_REQUIRE(K > 0 && K <= Q, "sg_area_relabel_multi: K=%d must lie in [1, Q=%d]", K, Q);
+  SG_REQUIRE(K <= SG_AREA_MAX_K, "sg_area_relabel_multi: K=%d exceeds %d (SG_AREA_MAX_K, the limit of sg_class_area)", K, SG_AREA_MAX_K);
+  SG_REQUIRE(bg_idx >= 0 && bg_idx < K, "sg_area_relabel_multi: bg_idx=%d outside [0, K=%d)", bg_idx, K);
+  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "sg_area_relabel_multi: total_blocks=%lld outside (0, 2^31)", (long long)total_blocks);
+  SG_REQUIRE(out_pixels > 0, "sg_area_relabel_multi: out_pixels=%lld holds no image", (long long)out_pixels);
+  hipLaunchKernelGGL(area_relabel_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q,
+                     gh, gw, up_h, up_w, pad_t, pad_l, image_hw, image_tiles, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale,
+                     prob_thd, bg_idx, keep, conf, labels);
   SG_LAUNCH_CHECK();
   return SG_OK;
 }

@@ -375,10 +375,11 @@ def stitch_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, imag
 
 @on_tensor_device
 def label_head_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, query_idx, num_classes: int,
-                     logit_scale: float, prob_thd: float, bg_idx: int, want_conf: bool = False):
+                     logit_scale: float, prob_thd: float, bg_idx: int, want_conf: bool = False, flat_conf: bool = False):
     """sg_label_head_multi: the labels of N images in one launch, from their tile logits (arguments as ``stitch_multi`` plus the
     post-process parameters).  -> (list of labels int64 [1,H,W], the flat int64 buffer they are views of, images back to back), plus
-    the list of conf f32 [H,W] maps as a third result with ``want_conf``.  Equals ``label_head`` per image byte for byte."""
+    the list of conf f32 [H,W] maps as a third result with ``want_conf`` (``flat_conf``: the one flat f32 buffer those maps are views
+    of instead of the list).  Equals ``label_head`` per image byte for byte."""
     lib = _lib.load()
     tile_logits = _f32(tile_logits)
     _require_gpu(tile_logits)
@@ -404,7 +405,7 @@ def label_head_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, 
           "sg_label_head_multi")
     lab = [labels[pix[n]:pix[n + 1]].view(1, h, w) for n, (h, w) in enumerate(image_hw)]
     if want_conf:
-        return lab, labels, [conf[pix[n]:pix[n + 1]].view(h, w) for n, (h, w) in enumerate(image_hw)]
+        return lab, labels, (conf if flat_conf else [conf[pix[n]:pix[n + 1]].view(h, w) for n, (h, w) in enumerate(image_hw)])
     return lab, labels
 
 
@@ -431,11 +432,11 @@ def prob_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, query_idx, num_cla
 
 @on_tensor_device
 def prob_head_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, query_idx, num_classes: int,
-                    logit_scale: float, prob_thd: float, bg_idx: int):
+                    logit_scale: float, prob_thd: float, bg_idx: int, flat_probs: bool = False):
     """sg_prob_head_multi: the class probabilities and labels of N images in one launch, from their tile logits (arguments as
     ``label_head_multi``).  -> (list of probs f32 [K,H,W], list of labels int64 [1,H,W], the flat int64 buffer the label maps are views
     of, images back to back): what ``postprocess_multi(..., want_probs=True, flat_labels=True)`` returns, and ``prob_head`` per image
-    byte for byte.  The probs of image n are a view at K * (its first pixel) of one flat f32 buffer."""
+    byte for byte.  The probs of image n are a view at K * (its first pixel) of one flat f32 buffer (a fourth result with ``flat_probs``)."""
     lib = _lib.load()
     tile_logits = _f32(tile_logits)
     _require_gpu(tile_logits)
@@ -460,7 +461,7 @@ def prob_head_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, i
                                  float(prob_thd), int(bg_idx), ptr(probs), ptr(labels), stream_ptr()), "sg_prob_head_multi")
     lab = [labels[pix[n]:pix[n + 1]].view(1, h, w) for n, (h, w) in enumerate(image_hw)]
     prb = [probs[K * pix[n]:K * pix[n + 1]].view(K, h, w) for n, (h, w) in enumerate(image_hw)]
-    return prb, lab, labels
+    return (prb, lab, labels, probs) if flat_probs else (prb, lab, labels)
 
 
 TOPK_MAX = 8                                                             # SG_TOPK_MAX (include/segearth_hip.h)
@@ -688,11 +689,12 @@ def topk_from_probs(probs, query_idx, k: int):
 
 @on_tensor_device
 def postprocess_multi(canvases, canvas_hw, query_idx, num_classes: int, logit_scale: float, prob_thd: float, bg_idx: int,
-                      out_hw=None, want_probs: bool = True, canvas_offsets=None, flat_labels: bool = False):
+                      out_hw=None, want_probs: bool = True, canvas_offsets=None, flat_labels: bool = False, flat_probs: bool = False):
     """sg_postprocess_multi: N canvases [Q,h,w] in one flat buffer (packed back to back, or at ``canvas_offsets`` elements) ->
     (list of probs [K,H,W] or None, list of labels int64 [1,H,W]); (H, W) = out_hw[n] (default: the canvas size) -- a different size
     is the bilinear resize of sg_resize_bilinear, fused.  ``flat_labels`` adds a third result: the one int64 buffer the label maps
-    are views of, images back to back (what sg_confusion_accumulate takes for a whole flush group)."""
+    are views of, images back to back (what sg_confusion_accumulate takes for a whole flush group); ``flat_probs`` (with it and
+    ``want_probs``) a fourth: the one f32 buffer the probs are views of, image n at K * (its first pixel)."""
     lib = _lib.load()
     _require_gpu(canvases)
     if canvases.dtype != torch.float32 or not canvases.is_contiguous():
@@ -715,6 +717,8 @@ def postprocess_multi(canvases, canvas_hw, query_idx, num_classes: int, logit_sc
                                    ptr(labels), stream_ptr()), "sg_postprocess_multi")
     lab = [labels[pix[n]:pix[n + 1]].view(1, h, w) for n, (h, w) in enumerate(out_hw)]
     prb = [probs[K * pix[n]:K * pix[n + 1]].view(K, h, w) if want_probs else None for n, (h, w) in enumerate(out_hw)]
+    if flat_labels and flat_probs:
+        return prb, lab, labels, probs
     return (prb, lab, labels) if flat_labels else (prb, lab)
 
 
@@ -849,6 +853,208 @@ def confusion_accumulate(labels, gt, table, K: int, ignore_index: int = 255, red
     check(lib.sg_confusion_accumulate(ptr(labels), ptr(gt), fmt, labels.numel(), K, int(ignore_index), int(bool(reduce_zero_label)),
                                       ptr(table), stream_ptr()), "sg_confusion_accumulate")
     return table
+
+
+AREA_MAX_K = 4096                                                        # SG_AREA_MAX_K (include/segearth_hip.h)
+AREA_SPAN = 4096                                                         # pixels per block of sg_class_area_multi
+
+
+def area_args(what: str, K: int, bg_idx: int, area_thd=None):
+    """The checks every area_thd entry point shares: 0 <= bg_idx < K and, when given, a threshold that is a number >= 0."""
+    K, bg_idx = int(K), int(bg_idx)
+    if not 0 <= bg_idx < K:
+        raise ValueError(f"{what}: area_thd needs 0 <= bg_idx < K (the background class is always kept), got bg_idx={bg_idx}, K={K}")
+    if area_thd is not None and not float(area_thd) >= 0.0:
+        raise ValueError(f"{what}: area_thd must be a number >= 0 (a share of the non-background pixels), got {area_thd!r}")
+    return K, bg_idx
+
+
+def _i64_labels(what, labels):
+    _require_gpu(labels)
+    if labels.dtype != torch.int64 or not labels.is_contiguous():
+        raise TypeError(f"{what}: labels must be a contiguous int64 tensor, got {labels.dtype}")
+    return labels
+
+
+@on_tensor_device
+def class_area(labels, K: int, counts=None):
+    """sg_class_area: adds the number of pixels of every class in ``labels`` (int64, any shape; values outside [0,K) are not counted) to
+    ``counts`` int64 [K] (default: a zeroed one) and returns it.  Integer counts: byte-identical across repeats."""
+    lib = _lib.load()
+    labels = _i64_labels("class_area", labels)
+    K = int(K)
+    if counts is None:
+        counts = torch.zeros(max(K, 1), dtype=torch.int64, device=labels.device)
+    elif counts.dtype != torch.int64 or not counts.is_contiguous() or counts.numel() != K or counts.device != labels.device:
+        raise ValueError(f"class_area: counts must be contiguous int64 [{K}] on the labels' device")
+    if labels.numel() == 0 and 1 <= K <= AREA_MAX_K:                     # an empty tensor has no storage (a null pointer, which the entry refuses)
+        return counts
+    check(lib.sg_class_area(ptr(labels), labels.numel(), K, ptr(counts), stream_ptr()), "sg_class_area")
+    return counts
+
+
+@on_tensor_device
+def class_area_multi(labels, image_pixels, K: int):
+    """sg_class_area_multi: ``labels`` = the flat int64 label buffer of N images back to back (what ``label_head_multi`` /
+    ``postprocess_multi(flat_labels=True)`` return), ``image_pixels`` = their pixel counts -> counts int64 [N,K], one launch."""
+    lib = _lib.load()
+    labels = _i64_labels("class_area_multi", labels)
+    K, N = int(K), len(image_pixels)
+    pix = _prefix(image_pixels)
+    if N == 0 or any(int(p) <= 0 for p in image_pixels) or pix[-1] != labels.numel():
+        raise ValueError(f"class_area_multi: {N} images of {list(image_pixels)} pixels against {labels.numel()} labels")
+    blocks = _prefix(-(-int(p) // AREA_SPAN) for p in image_pixels)
+    counts = torch.zeros(N, max(K, 1), dtype=torch.int64, device=labels.device)
+    i64 = torch.tensor([int(p) for p in image_pixels] + pix[:-1] + blocks, dtype=torch.int64).to(labels.device)
+    check(lib.sg_class_area_multi(ptr(labels), ptr(i64), ptr(i64[N:]), ptr(i64[2 * N:]), N, blocks[-1], pix[-1], K, ptr(counts), stream_ptr()),
+          "sg_class_area_multi")
+    return counts
+
+
+@on_tensor_device
+def area_keep(counts, bg_idx: int, area_thd: float):
+    """sg_area_keep: counts int64 [K] or [N,K] -> keep int32 of the same shape: keep[c] = c == bg_idx or area[c] > area_thd * (the sum
+    of the non-background areas), compared in double on the device.  Nothing comes to the host."""
+    lib = _lib.load()
+    _require_gpu(counts)
+    if counts.dtype != torch.int64 or not counts.is_contiguous() or counts.dim() not in (1, 2):
+        raise ValueError("area_keep: counts must be contiguous int64 [K] or [N,K]")
+    K, bg_idx = area_args("area_keep", counts.shape[-1], bg_idx, area_thd)
+    keep = torch.empty(counts.shape, dtype=torch.int32, device=counts.device)
+    check(lib.sg_area_keep(ptr(counts), counts.numel() // K, K, bg_idx, float(area_thd), ptr(keep), stream_ptr()), "sg_area_keep")
+    return keep
+
+
+def _keep_arg(what, keep, shape, device):
+    if keep.dtype != torch.int32 or not keep.is_contiguous() or tuple(keep.shape) != tuple(shape) or keep.device != device:
+        raise ValueError(f"{what}: keep must be contiguous int32 {list(shape)} on the device of the other arguments")
+    return keep
+
+
+@on_tensor_device
+def area_filter_probs(probs, labels, keep, prob_thd: float, bg_idx: int):
+    """sg_area_filter_probs, IN PLACE: probs f32 [K,H,W] get the planes of dropped classes zeroed; labels int64 [1,H,W] or [H,W] hold
+    the first-pass labels (the arg-max before prob_thd) on entry and the final labels on return: the kept class of the largest
+    probability, ``bg_idx`` below ``prob_thd``.  keep int32 [K] (``area_keep``).  Returns ``labels``."""
+    lib = _lib.load()
+    _require_gpu(probs)
+    if probs.dtype != torch.float32 or not probs.is_contiguous() or probs.dim() != 3:
+        raise ValueError("area_filter_probs: probs must be a contiguous f32 [K,H,W] tensor")
+    K, H, W = probs.shape
+    K, bg_idx = area_args("area_filter_probs", K, bg_idx)
+    labels = _i64_labels("area_filter_probs", labels)
+    if labels.numel() != H * W or labels.device != probs.device:
+        raise ValueError(f"area_filter_probs: labels {tuple(labels.shape)} against probs {tuple(probs.shape)}")
+    _keep_arg("area_filter_probs", keep, (K,), probs.device)
+    check(lib.sg_area_filter_probs(ptr(probs), ptr(labels), ptr(keep), K, H, W, float(prob_thd), bg_idx, ptr(labels), stream_ptr()),
+          "sg_area_filter_probs")
+    return labels
+
+
+@on_tensor_device
+def area_filter_probs_multi(probs, labels, keep, out_hw, prob_thd: float, bg_idx: int):
+    """sg_area_filter_probs_multi, IN PLACE, on the flat outputs of ``postprocess_multi`` / ``prob_head_multi``: ``labels`` the flat int64
+    buffer of N images back to back, ``probs`` the flat f32 buffer with image n's [K,H,W] at K * (its first pixel), keep int32 [N,K],
+    out_hw [(H, W)] * N.  One launch.  Returns ``labels``."""
+    lib = _lib.load()
+    _require_gpu(probs)
+    N = len(out_hw)
+    labels = _i64_labels("area_filter_probs_multi", labels)
+    if N == 0 or keep.dim() != 2:
+        raise ValueError("area_filter_probs_multi: keep must be [N,K] for N >= 1 images")
+    K, bg_idx = area_args("area_filter_probs_multi", keep.shape[1], bg_idx)
+    pix = _prefix(h * w for h, w in out_hw)
+    if probs.dtype != torch.float32 or not probs.is_contiguous() or probs.numel() != K * pix[-1] or labels.numel() != pix[-1] or \
+            labels.device != probs.device or any(h <= 0 or w <= 0 for h, w in out_hw):
+        raise ValueError(f"area_filter_probs_multi: {pix[-1]} pixels of K={K} against {probs.numel()} probabilities and {labels.numel()} labels")
+    _keep_arg("area_filter_probs_multi", keep, (N, K), probs.device)
+    blocks = _prefix(-(-(h * w) // 256) for h, w in out_hw)
+    i32 = torch.tensor([list(hw) for hw in out_hw], dtype=torch.int32).to(probs.device)
+    i64 = torch.tensor(pix[:-1] + blocks, dtype=torch.int64).to(probs.device)
+    check(lib.sg_area_filter_probs_multi(ptr(probs), ptr(labels), ptr(keep), ptr(i32), ptr(i64), ptr(i64[N:]), N, blocks[-1], pix[-1], K,
+                                         float(prob_thd), bg_idx, ptr(labels), stream_ptr()), "sg_area_filter_probs_multi")
+    return labels
+
+
+@on_tensor_device
+def area_filter(probs, area_thd: float, prob_thd: float, bg_idx: int):
+    """area_thd for a caller who holds class probabilities f32 [K,H,W] of one image: a class that wins less than (or exactly) the share
+    ``area_thd`` of the non-background pixels is removed from the image and its pixels go to the best remaining class (the definition:
+    include/segearth_hip.h).  -> (probs' [K,H,W] with the dropped planes zeroed, labels int64 [1,H,W], keep int32 [K]); ``probs`` is left
+    as it was.  The arg-max of the first pass is taken by the filter kernel itself (every class kept, every pixel undecided), then
+    ``class_area`` -> ``area_keep`` -> ``area_filter_probs``; nothing synchronises with the host."""
+    _require_gpu(probs)
+    if probs.dim() != 3:
+        raise ValueError("area_filter: probs must be [K,H,W]")
+    K, bg_idx = area_args("area_filter", probs.shape[0], bg_idx, area_thd)
+    out = probs.float().contiguous().clone()
+    labels = torch.full((1,) + tuple(out.shape[1:]), -1, dtype=torch.int64, device=out.device)
+    area_filter_probs(out, labels, torch.ones(K, dtype=torch.int32, device=out.device), float("-inf"), bg_idx)
+    keep = area_keep(class_area(labels, K), bg_idx, area_thd)
+    area_filter_probs(out, labels, keep, prob_thd, bg_idx)
+    return out, labels, keep
+
+
+@on_tensor_device
+def area_relabel(tile_logits, windows, up_hw, pad_tl, canvas_hw, query_idx, num_classes: int, logit_scale: float, prob_thd: float,
+                 bg_idx: int, keep, conf, labels):
+    """sg_area_relabel: the second decision of area_thd on the labels-only route, no canvas and no probability planes.  Arguments as
+    ``label_head`` plus keep int32 [K] and the first pass's outputs (``label_head(..., prob_thd=0, want_conf=True)``): conf f32 [H,W] and
+    labels int64 [1,H,W], which are rewritten IN PLACE and returned.  Equals ``label_head`` on a ``query_idx`` whose dropped queries are -1."""
+    lib = _lib.load()
+    tile_logits = _f32(tile_logits)
+    windows = windows.to(device=tile_logits.device, dtype=torch.int32).contiguous()
+    _require_gpu(tile_logits)
+    T, Q, gh, gw = tile_logits.shape
+    H, W = canvas_hw
+    qi = query_idx.to(device=tile_logits.device, dtype=torch.int32).contiguous()
+    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T:
+        raise ValueError(f"area_relabel: {T} tiles of {Q} queries, but {windows.numel() // 4} windows and {qi.numel()} query indices")
+    K, bg_idx = area_args("area_relabel", num_classes, bg_idx)
+    labels = _i64_labels("area_relabel", labels)
+    if labels.numel() != H * W or conf.dtype != torch.float32 or not conf.is_contiguous() or conf.numel() != H * W or \
+            conf.device != tile_logits.device or labels.device != tile_logits.device:
+        raise ValueError(f"area_relabel: labels {tuple(labels.shape)} / conf {tuple(conf.shape)} are not the first pass of a {H} x {W} image")
+    _keep_arg("area_relabel", keep, (K,), tile_logits.device)
+    check(lib.sg_area_relabel(ptr(tile_logits), ptr(windows), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1], H, W, ptr(qi), K,
+                              float(logit_scale), float(prob_thd), bg_idx, ptr(keep), ptr(conf), ptr(labels), stream_ptr()),
+          "sg_area_relabel")
+    return labels
+
+
+@on_tensor_device
+def area_relabel_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, query_idx, num_classes: int,
+                       logit_scale: float, prob_thd: float, bg_idx: int, keep, conf, labels):
+    """sg_area_relabel_multi: ``area_relabel`` for the tiles of N images in one launch (arguments as ``label_head_multi``): keep int32
+    [N,K]; conf f32 and labels int64 are the flat first-pass buffers of ``label_head_multi(..., prob_thd=0, want_conf=True)``, images
+    back to back; labels are rewritten IN PLACE and returned.  Equals ``area_relabel`` per image byte for byte."""
+    lib = _lib.load()
+    tile_logits = _f32(tile_logits)
+    _require_gpu(tile_logits)
+    dev = tile_logits.device
+    T, Q, gh, gw = tile_logits.shape
+    N = len(image_hw)
+    qi = query_idx.to(device=dev, dtype=torch.int32).contiguous()
+    windows = torch.as_tensor(windows, dtype=torch.int32).to(dev).contiguous()
+    tile_image = torch.as_tensor(tile_image, dtype=torch.int32).to(dev).contiguous()
+    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T or int(tile_image.numel()) != T or len(image_tiles) != N:
+        raise ValueError("area_relabel_multi: tile logits, windows, tile_image, image descriptors and query indices disagree in size")
+    if any(f < 0 or c <= 0 or f + c > T for f, c in image_tiles):
+        raise ValueError(f"area_relabel_multi: image_tiles {list(image_tiles)} leave the {T} tiles")
+    K, bg_idx = area_args("area_relabel_multi", num_classes, bg_idx)
+    pix = _prefix(h * w for h, w in image_hw)
+    labels = _i64_labels("area_relabel_multi", labels)
+    if labels.numel() != pix[-1] or conf.dtype != torch.float32 or not conf.is_contiguous() or conf.numel() != pix[-1] or \
+            conf.device != dev or labels.device != dev:
+        raise ValueError(f"area_relabel_multi: labels / conf are not the flat first pass of {pix[-1]} pixels")
+    _keep_arg("area_relabel_multi", keep, (N, K), dev)
+    blocks = _prefix(-(-w // 64) * -(-h // 4) for h, w in image_hw)
+    i32 = torch.tensor([list(hw) for hw in image_hw] + [list(ft) for ft in image_tiles], dtype=torch.int32).to(dev)
+    i64 = torch.tensor(pix[:-1] + blocks, dtype=torch.int64).to(dev)
+    check(lib.sg_area_relabel_multi(ptr(tile_logits), ptr(windows), ptr(tile_image), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1],
+                                    ptr(i32), ptr(i32[N:]), ptr(i64), ptr(i64[N:]), N, blocks[-1], pix[-1], ptr(qi), K, float(logit_scale),
+                                    float(prob_thd), bg_idx, ptr(keep), ptr(conf), ptr(labels), stream_ptr()), "sg_area_relabel_multi")
+    return labels
 
 
 @on_tensor_device

@@ -341,15 +341,24 @@ TOPK_TILE_GROUP = ("top-k under tile_group sharding is not built: each rank woul
                    "planes would be gathered (gather_bands); run top-k on whole images per rank")
 
 
+AREA_TILE_GROUP = ("area_thd under tile_group sharding is not built: the class areas are a statistic of the whole image, so the counts of "
+                   "the ranks' canvas bands would need an all-reduce before any band can be relabelled; run area_thd on whole images per rank")
+
+
+AREA_TOPK = ("top-k together with area_thd is not built: the k best classes would have to skip the classes that area_thd drops, which the "
+             "top-k head decides before the areas are known; run predict_topk / topk= on an instance without area_thd")
+
+
 class SegPipeline:
     pamr_steps, pamr_stride = 0, (8, 16)      # PAMR off unless the constructor says otherwise
+    area_thd = None                           # area_thd off likewise
 
     def __init__(self, net: HipCLIP, text: torch.Tensor, query_idx: torch.Tensor, model_type: str = "SegEarth",
                  ignore_residual: bool = True, cls_token_lambda: float = 0.0, global_debias_factor: float = 0.0,
                  logit_scale: float = 50.0, prob_thd: float = 0.0, bg_idx: int = 0, apply_similarity_enhancement: bool = False,
                  upsampler=None, tiles_per_launch: int = 32, cross_tile_fusion: Optional[dict] = None, apply_ctd: bool = False,
                  tile_group=None, apply_layer_fusion: bool = False, layer_fusion_lambda: float = 0.5, label_head: str = "auto",
-                 prob_head: str = "auto", pamr_steps: int = 0, pamr_stride=(8, 16), resize_head: str = "canvas"):
+                 prob_head: str = "auto", pamr_steps: int = 0, pamr_stride=(8, 16), resize_head: str = "canvas", area_thd=None):
         if resize_head not in RESIZE_HEADS:
             raise ValueError(f"resize_head must be one of {RESIZE_HEADS}, got {resize_head!r}")
         # labels / top-k at another ori_shape than the image's (RESIZE_HEADS); PAMR and whole-image inference keep the canvas route
@@ -397,6 +406,21 @@ class SegPipeline:
         # all hold the SAME scene).  It is never inferred from torch.distributed being initialised: under the reference's own
         # multi-GPU launch every rank holds a different image.
         self.tile_group = tile_group
+        # area_thd (the upstream option name; None = off, and then no call changes route, launches or bytes): per image, a class whose
+        # arg-max area is at most area_thd times the non-background area is removed and its pixels go to the best remaining class (the
+        # definition: include/segearth_hip.h).  Every tail that returns labels or probabilities then decides twice: the first pass is
+        # today's kernel with prob_thd = 0 (its labels are the plain arg-max), then sg_class_area -> sg_area_keep on the device, then
+        #   probabilities exist (or the canvas route runs): sg_area_filter_probs -- dropped planes zeroed, labels from the kept planes.
+        #     Labels alone on the canvas route (label_head="canvas", PAMR, a resized canvas, whole-image inference, and
+        #     resize_head="fused", which takes the canvas route while area_thd is set) write the probabilities into a scratch [K,H,W]
+        #     for this and return only labels; the fused label head is the memory-lean way;
+        #   labels alone on the fused label head: sg_label_head with conf, then sg_area_relabel -- no canvas, no probability planes,
+        #     12 bytes per pixel instead of 8.
+        self.area_thd = None if area_thd is None else float(area_thd)
+        if self.area_thd is not None:
+            ops.area_args("area_thd", self.num_classes, self.bg_idx, self.area_thd)
+            if tile_group is not None:
+                raise ValueError(AREA_TILE_GROUP)
 
     def _stitch(self, tile_logits, windows, up_hw, pad_tl, canvas_hw):
         return ops.stitch(tile_logits, windows, up_hw, pad_tl, canvas_hw)
@@ -410,7 +434,7 @@ class SegPipeline:
 
     def fused_resize_head(self) -> bool:
         """Whether labels / top-k at another ``ori_shape`` run the resized heads (no canvas) instead of stitch + resize + post-process."""
-        return getattr(self, "resize_head", "canvas") == "fused" and getattr(self, "pamr_steps", 0) == 0
+        return getattr(self, "resize_head", "canvas") == "fused" and getattr(self, "pamr_steps", 0) == 0 and self.area_thd is None
 
     def refine(self, canvas: torch.Tensor, guide: torch.Tensor) -> torch.Tensor:
         """PAMR on one image's logits [Q,H,W], in place where they are a contiguous f32 tensor.  ``guide``: the image (u8 [H,W,3] or
@@ -438,9 +462,38 @@ class SegPipeline:
         canvas and no probabilities.  A canvas band is a canvas with shifted windows.  With PAMR on this is the canvas route, refined
         under ``guide`` (the scene)."""
         if self.fused_label_head():
+            if self.area_thd is not None:
+                labels, conf = ops.label_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, self.query_idx, self.num_classes,
+                                              self.logit_scale, 0.0, self.bg_idx, want_conf=True)
+                keep = ops.area_keep(ops.class_area(labels, self.num_classes), self.bg_idx, self.area_thd)
+                return ops.area_relabel(tile_logits, windows, up_hw, pad_tl, canvas_hw, self.query_idx, self.num_classes, self.logit_scale,
+                                        self.prob_thd, self.bg_idx, keep, conf, labels)
             return ops.label_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, self.query_idx, self.num_classes, self.logit_scale,
                                   self.prob_thd, self.bg_idx)
         return self._canvas_tail(tile_logits, windows, up_hw, pad_tl, canvas_hw, guide, False)[1]
+
+    def area_filter_first_pass(self, probs, labels):
+        """The second decision of area_thd for one image whose first pass (``prob_thd = 0``) left probs f32 [K,H,W] and labels int64
+        [1,H,W]: count, keep, filter -- both tensors IN PLACE, three launches, nothing comes to the host."""
+        keep = ops.area_keep(ops.class_area(labels, self.num_classes), self.bg_idx, self.area_thd)
+        ops.area_filter_probs(probs, labels, keep, self.prob_thd, self.bg_idx)
+        return probs, labels
+
+    def area_filter_first_pass_multi(self, probs, flat, out_hw):
+        """``area_filter_first_pass`` for a flush group: the flat outputs of sg_postprocess_multi / sg_prob_head_multi, one launch each."""
+        keep = ops.area_keep(ops.class_area_multi(flat, [h * w for h, w in out_hw], self.num_classes), self.bg_idx, self.area_thd)
+        ops.area_filter_probs_multi(probs, flat, keep, out_hw, self.prob_thd, self.bg_idx)
+
+    def _postprocess_multi(self, canvases, chw, ohw, want_probs):
+        """ops.postprocess_multi for a flush group -> (probs or Nones, labels, flat labels); with area_thd the first pass writes the
+        probabilities whether wanted or not (a scratch then), and the group is counted, decided and filtered with one launch each."""
+        if self.area_thd is None:
+            return ops.postprocess_multi(canvases, chw, self.query_idx, self.num_classes, self.logit_scale, self.prob_thd, self.bg_idx, ohw,
+                                         want_probs, flat_labels=True)
+        prb, lab, flat, probs = ops.postprocess_multi(canvases, chw, self.query_idx, self.num_classes, self.logit_scale, 0.0, self.bg_idx, ohw,
+                                                      True, flat_labels=True, flat_probs=True)
+        self.area_filter_first_pass_multi(probs, flat, ohw)
+        return (prb if want_probs else [None] * len(lab)), lab, flat
 
     def fused_prob_head(self) -> bool:
         """Whether the tail that returns probabilities and labels runs the fused head (sg_prob_head) instead of the canvas path.  "auto"
@@ -455,12 +508,17 @@ class SegPipeline:
         class probabilities at the scene's own size.  Both routes return the same bytes.  With PAMR on this is the canvas route, refined
         under ``guide`` (the scene)."""
         if self.fused_prob_head():
+            if self.area_thd is not None:
+                return self.area_filter_first_pass(*ops.prob_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, self.query_idx,
+                                                                  self.num_classes, self.logit_scale, 0.0, self.bg_idx))
             return ops.prob_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, self.query_idx, self.num_classes, self.logit_scale,
                                  self.prob_thd, self.bg_idx)
         return self._canvas_tail(tile_logits, windows, up_hw, pad_tl, canvas_hw, guide, True)
 
     def topk_k(self, topk) -> int:
         """``topk`` checked against what sg_topk_head takes: 1 .. min(ops.TOPK_MAX, the number of classes)."""
+        if self.area_thd is not None:
+            raise ValueError(AREA_TOPK)
         k = int(topk)
         if not 1 <= k <= min(ops.TOPK_MAX, self.num_classes):
             raise ValueError(f"topk must lie in [1, min({ops.TOPK_MAX}, {self.num_classes} classes)], got {topk!r}")
@@ -641,7 +699,12 @@ class SegPipeline:
         ``want_probs`` and not with tile sharding.
         ``ori_shape`` of another size than the scene: labels (or the ``topk`` planes) at that size; not with ``want_probs`` (use
         ``segment_scenes``) and not with tile sharding.  ``resize_head="fused"`` without PAMR: sg_label_head_resized /
-        sg_topk_head_resized on the tile logits, no canvas; otherwise stitch, resize, PAMR when on, post-process."""
+        sg_topk_head_resized on the tile logits, no canvas; otherwise stitch, resize, PAMR when on, post-process.
+        With ``area_thd`` set every route above decides twice (the constructor's comment): the fused label head through
+        sg_area_relabel, everything else through the probabilities and sg_area_filter_probs -- labels alone on the canvas route then
+        pay a scratch [K,H,W], and ``resize_head="fused"`` takes the canvas route.  ``topk`` and tile sharding are refused."""
+        if self.area_thd is not None and group is not None:
+            raise ValueError(AREA_TILE_GROUP)
         resize = ori_shape is not None and tuple(ori_shape) != _scene_hw(scene)
         if topk:
             if want_probs:
@@ -743,7 +806,8 @@ class SegPipeline:
     def _packed_canvases(self, scenes, stride, crop):
         """Yields (image indices, flat canvas buffer, its [Q,H,W] views) per flush group: ``_packed_tiles`` and one sg_stitch_multi
         launch."""
-        for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(scenes, stride, crop, 4 * self.num_queries):
+        extra = 0 if self.area_thd is None else 4 * self.num_classes + 8           # area_thd: the probability planes always exist
+        for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(scenes, stride, crop, 4 * self.num_queries + extra):
             canvases, views = ops.stitch_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles)
             yield idx, canvases, views
 
@@ -851,7 +915,12 @@ class SegPipeline:
         ``resize_head="fused"`` without PAMR, when some image's ``ori_shape`` differs from its size: labels alone take one
         sg_label_head_resized_multi launch, and ``topk`` one sg_topk_head_resized_multi launch, per flush group that holds such an image
         (the resize runs inside the head, no canvas; the planner counts 8 or 8 * topk bytes per OUTPUT pixel); a flush group in which no
-        image differs runs what it runs without the option."""
+        image differs runs what it runs without the option.
+        With ``area_thd`` set each group decides twice, with one launch per step wherever the group has one post-process or head launch
+        today: first pass (``prob_thd = 0``), sg_class_area_multi, sg_area_keep, then sg_area_filter_probs_multi on the group's
+        probabilities (written into a scratch when only labels are wanted) or, for labels alone on the fused label head,
+        sg_area_relabel_multi (no canvas, no probabilities; the planner counts 12 bytes per pixel instead of 8).  Groups that go image by
+        image stay image by image (``postprocess``).  ``resize_head="fused"`` takes the canvas route; ``topk`` is refused."""
         no_resize = ori_shapes is None or all(o is None for o in ori_shapes)
         if topk:
             if want_probs:
@@ -893,8 +962,13 @@ class SegPipeline:
                 o is None or tuple(o) == _scene_hw(s)
                 for o, s in zip(ori_shapes, [scenes] if torch.is_tensor(scenes) and scenes.dim() == 3 else scenes))):
             for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(scenes, stride, crop, 4 * self.num_classes + 8):
-                prb, lab, flat = ops.prob_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes,
-                                                     self.logit_scale, self.prob_thd, self.bg_idx)
+                if self.area_thd is not None:
+                    prb, lab, flat, probs = ops.prob_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx,
+                                                                self.num_classes, self.logit_scale, 0.0, self.bg_idx, flat_probs=True)
+                    self.area_filter_first_pass_multi(probs, flat, [tuple(hw) for hw in shapes])
+                else:
+                    prb, lab, flat = ops.prob_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes,
+                                                         self.logit_scale, self.prob_thd, self.bg_idx)
                 yield idx, prb, lab, flat
             return
         if not want_probs and self.fused_resize_head() and not no_resize and any(
@@ -924,6 +998,16 @@ class SegPipeline:
                 yield idx, [None] * len(idx), lab, flat
             return
         if not want_probs and no_resize and self.fused_label_head():
+            if self.area_thd is not None:
+                # first pass with conf (12 bytes per pixel), the areas of every image of the group, then the relabel: one launch each
+                for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(scenes, stride, crop, 12):
+                    lab, flat, conf = ops.label_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes,
+                                                           self.logit_scale, 0.0, self.bg_idx, want_conf=True, flat_conf=True)
+                    keep = ops.area_keep(ops.class_area_multi(flat, [h * w for h, w in shapes], self.num_classes), self.bg_idx, self.area_thd)
+                    ops.area_relabel_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes, self.logit_scale,
+                                           self.prob_thd, self.bg_idx, keep, conf, flat)
+                    yield idx, [None] * len(idx), lab, flat
+                return
             for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(scenes, stride, crop, 8):
                 lab, flat = ops.label_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes,
                                                  self.logit_scale, self.prob_thd, self.bg_idx)
@@ -946,8 +1030,7 @@ class SegPipeline:
         for idx, canvases, views in self._packed_canvases(scenes, stride, crop):
             chw = [tuple(c.shape[1:]) for c in views]
             ohw = [chw[n] if ori_shapes is None or ori_shapes[k] is None else tuple(ori_shapes[k]) for n, k in enumerate(idx)]
-            prb, lab, flat = ops.postprocess_multi(canvases, chw, self.query_idx, self.num_classes, self.logit_scale, self.prob_thd,
-                                                   self.bg_idx, ohw, want_probs, flat_labels=True)
+            prb, lab, flat = self._postprocess_multi(canvases, chw, ohw, want_probs)
             yield idx, prb, lab, flat
 
     def _label_groups_pamr(self, scenes, stride, crop, want_probs, ori_shapes):
@@ -960,8 +1043,7 @@ class SegPipeline:
             if ohw == chw and self.num_queries <= ops.POSTPROCESS_MAX_Q:
                 for c, im in zip(views, imgs):
                     self.refine(c, im.to(self.device))
-                yield (idx,) + tuple(ops.postprocess_multi(canvases, chw, self.query_idx, self.num_classes, self.logit_scale, self.prob_thd,
-                                                           self.bg_idx, ohw, want_probs, flat_labels=True))
+                yield (idx,) + tuple(self._postprocess_multi(canvases, chw, ohw, want_probs))
                 continue
             prb, lab = [], []
             for c, im, hw in zip(views, imgs, ohw):
@@ -1007,5 +1089,10 @@ class SegPipeline:
 
     # -- reference postprocess_result --------------------------------------------------------------------------
     def postprocess(self, seg_logits: torch.Tensor, want_probs: bool = True):
-        """seg_logits [Q,H,W] -> (probs [K,H,W], labels int64 [1,H,W])."""
+        """seg_logits [Q,H,W] -> (probs [K,H,W], labels int64 [1,H,W]).  With ``area_thd`` the first pass runs with ``prob_thd = 0`` and
+        always writes the probabilities (a scratch [K,H,W] when they are not wanted), then ``area_filter_first_pass``."""
+        if self.area_thd is not None:
+            probs, labels = self.area_filter_first_pass(*ops.postprocess(seg_logits, self.query_idx, self.num_classes, self.logit_scale, 0.0,
+                                                                         self.bg_idx, True))
+            return (probs if want_probs else None), labels
         return ops.postprocess(seg_logits, self.query_idx, self.num_classes, self.logit_scale, self.prob_thd, self.bg_idx, want_probs)

@@ -130,9 +130,18 @@ class _HipSegmentorBase(_Base):
                slide_crop, cls_token_lambda, bg_idx, apply_sim_feat_up, sim_feat_up_cfg, global_debias_factor=0.0,
                checkpoint=None, text_features=None, text_encoder: Optional[Callable] = None, precision="f16x2",
                synthetic_ok=False, tiles_per_launch=None, jbu_checkpoint_ok=True, tokenizer: Optional[Callable] = None, tile_group=None,
-               label_head="auto", prob_head="auto", pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas"):
+               label_head="auto", prob_head="auto", pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas", area_thd=None):
         from . import ops
-        from .pipeline import LABEL_HEADS, PAMR_TILE_GROUP, PROB_HEADS, RESIZE_HEADS
+        from .pipeline import AREA_TILE_GROUP, LABEL_HEADS, PAMR_TILE_GROUP, PROB_HEADS, RESIZE_HEADS
+        # area_thd (the upstream option name; None = off): per image, a class that wins at most this share of the non-background pixels is
+        # removed and its pixels go to the best remaining class (SegPipeline; the definition: include/segearth_hip.h).  The background
+        # class is always kept, so 0 <= bg_idx < the number of classes is required (checked below, once the class file is read).
+        if area_thd is not None:
+            if not float(area_thd) >= 0.0:
+                raise ValueError(f"area_thd must be None or a number >= 0 (a share of the non-background pixels), got {area_thd!r}")
+            if tile_group is not None:
+                raise ValueError(AREA_TILE_GROUP)
+        self.area_thd = None if area_thd is None else float(area_thd)
         if resize_head not in RESIZE_HEADS:
             raise ValueError(f"resize_head must be one of {RESIZE_HEADS}, got {resize_head!r}")
         # labels and the k best classes at another ori_shape than the image's: "canvas" = stitch, resize the canvas, post-process; "fused" =
@@ -189,6 +198,8 @@ class _HipSegmentorBase(_Base):
         query_words, query_idx = get_cls_idx(name_path)
         self.num_queries = len(query_words)
         self.num_classes = max(query_idx) + 1
+        if self.area_thd is not None:
+            ops.area_args("area_thd", self.num_classes, bg_idx)
         self.query_idx = torch.tensor(query_idx, dtype=torch.int64, device=dev)
         E = cfg.embed_dim
         if text_features is not None:
@@ -260,7 +271,8 @@ class _HipSegmentorBase(_Base):
                            tile_group=getattr(self, "tile_group", None), apply_layer_fusion=getattr(self, "apply_layer_fusion", False),
                            layer_fusion_lambda=getattr(self, "layer_fusion_lambda", 0.5), label_head=getattr(self, "label_head", "auto"),
                            prob_head=getattr(self, "prob_head", "auto"), pamr_steps=getattr(self, "pamr_steps", 0),
-                           pamr_stride=getattr(self, "pamr_stride", (8, 16)), resize_head=getattr(self, "resize_head", "canvas"))
+                           pamr_stride=getattr(self, "pamr_stride", (8, 16)), resize_head=getattr(self, "resize_head", "canvas"),
+                           area_thd=getattr(self, "area_thd", None))
 
     def forward_feature(self, img, logit_size=None, tile_h_idx=None, tile_w_idx=None):
         """Reference segmentor.py:286-392.  img [B,3,H,W] -> logits [B,Q,h,w]."""
@@ -286,7 +298,12 @@ class _HipSegmentorBase(_Base):
     def predict(self, inputs, data_samples):
         """Reference segmentor.py:453-473.  With PAMR on (``pamr_steps > 0``) the stitched logits of every image are refined under that
         image (resized to ``ori_shape`` where the logits are) before the post-process, on the canvas route whatever label_head /
-        prob_head say; whole-image inference (``slide_crop <= 0``) likewise."""
+        prob_head say; whole-image inference (``slide_crop <= 0``) likewise.
+        With ``area_thd`` set the tail runs twice over the decision: the first pass with ``prob_thd = 0`` gives the plain arg-max, its
+        per-image class areas decide which classes stay (sg_class_area, sg_area_keep: on the device, no host synchronisation), and
+        ``seg_logits`` hold the probabilities with the dropped planes zeroed, ``pred_sem_seg`` the best kept class (sg_area_filter_probs).
+        Labels alone on the fused label head need no probability planes for it (sg_area_relabel); labels alone on the canvas route
+        write the probabilities into a scratch [K,H,W] first -- the fused head is the memory-lean way."""
         if data_samples is not None:
             batch_img_metas = [data_sample.metainfo for data_sample in data_samples]
         else:
@@ -337,7 +354,10 @@ class _HipSegmentorBase(_Base):
         canvas is refined before the post-process (SegPipeline.label_groups).
         ``ori_shapes`` (only with ``data_samples=None``; data samples carry their own): one (H, W) or None per image, the size of that
         image's label map.  With ``resize_head="fused"`` the resize runs inside the label head (sg_label_head_resized_multi, one launch
-        per flush group, no canvas); otherwise the canvas is stitched, resized and post-processed."""
+        per flush group, no canvas); otherwise the canvas is stitched, resized and post-processed.
+        With ``area_thd`` set every flush group decides twice (``predict``; SegPipeline.label_groups): one launch per step and group,
+        labels alone on the fused label head through sg_area_relabel_multi with no probability planes, ``resize_head="fused"`` on the
+        canvas route."""
         if ori_shapes is not None and data_samples is not None:
             raise ValueError("predict_many: ori_shapes goes with data_samples=None; data samples carry their own ori_shape")
         batch = torch.is_tensor(inputs)
@@ -382,9 +402,11 @@ class _HipSegmentorBase(_Base):
         (stitch, resize, PAMR, post-process) and ``ops.topk_from_probs`` sorts its probabilities -- except that with
         ``resize_head="fused"`` and no PAMR another ``ori_shape`` runs sg_topk_head_resized_multi, one launch per flush group and no
         canvas.  ``tile_group`` sharding is refused."""
-        from .pipeline import TOPK_TILE_GROUP
+        from .pipeline import AREA_TOPK, TOPK_TILE_GROUP
         if getattr(self, "tile_group", None) is not None:
             raise ValueError(TOPK_TILE_GROUP)
+        if getattr(self, "area_thd", None) is not None:
+            raise ValueError(AREA_TOPK)
         batch = torch.is_tensor(inputs)
         imgs = inputs.float() if batch else [x[0].float() if x.dim() == 4 else x.float() for x in inputs]
         n = imgs.shape[0] if batch else len(imgs)
@@ -427,7 +449,8 @@ class _HipSegmentorBase(_Base):
         ``metric.reduce(group)``.  With PAMR on (``pamr_steps > 0``) the labels come from the refined canvases (SegPipeline.label_groups).
         ``at_gt_size``: a truth map of any size is accepted; its shape becomes that image's ``ori_shape`` and the labels are produced at
         that size and counted (the configs that resize the image before inference and score at the original size).  The route follows
-        ``resize_head``: sg_label_head_resized_multi with "fused", stitch + resize + post-process with "canvas"."""
+        ``resize_head``: sg_label_head_resized_multi with "fused", stitch + resize + post-process with "canvas".
+        With ``area_thd`` set the labels that are counted are the filtered ones (SegPipeline.label_groups)."""
         from .metrics import IoUMetric
         if getattr(self, "tile_group", None) is not None:
             raise ValueError("evaluate: tile_group sharding is not supported (each rank would have to count its own band against the "
@@ -555,7 +578,7 @@ class SegmentorEx(_HipSegmentorBase):
                  # -- drop-in extras (see module docstring) --
                  checkpoint=None, text_features=None, text_encoder=None, precision="f16x2", synthetic_ok=False, tiles_per_launch=None,
                  tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, pack_images=False, label_head="auto", prob_head="auto",
-                 pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas"):
+                 pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas", area_thd=None):
         data_preprocessor = SegDataPreProcessor(mean=list(Wt.PIXEL_MEAN), std=list(Wt.PIXEL_STD), bgr_to_rgb=True)
         super().__init__(data_preprocessor=data_preprocessor)
         if model_type == "GEM":
@@ -565,7 +588,7 @@ class SegmentorEx(_HipSegmentorBase):
                              slide_crop, cls_token_lambda, bg_idx, _to_bool(apply_sim_feat_up), sim_feat_up_cfg, global_debias_factor,
                              checkpoint, text_features, text_encoder, precision, synthetic_ok, tiles_per_launch, tokenizer=tokenizer,
                              tile_group=tile_group, label_head=label_head, prob_head=prob_head, pamr_steps=pamr_steps, pamr_stride=pamr_stride,
-                             resize_head=resize_head)
+                             resize_head=resize_head, area_thd=area_thd)
         # opt-in extra: kwargs of the reference's CrossTileFusion (cross_tile_fusion.py:24-60), which the reference never calls (R2)
         self.cross_tile_fusion_cfg = cross_tile_fusion_cfg
         self.apply_ctd = _to_bool(apply_ctd)                                # segmentor.py:184-194, 339-365: DBSCAN + cluster debias, on the device here
@@ -600,7 +623,8 @@ class Segmentor(_HipSegmentorBase):
                  sim_feat_up_cfg=dict(model_name="jbu_one", model_path="your/model/path"),
                  checkpoint=None, text_features=None, text_encoder=None, precision="f16x2", synthetic_ok=False, tiles_per_launch=None,
                  tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, apply_outlier_suppression=False, outlier_suppression_cfg=None,
-                 pack_images=False, label_head="auto", prob_head="auto", pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas"):
+                 pack_images=False, label_head="auto", prob_head="auto", pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas",
+                 area_thd=None):
         data_preprocessor = SegDataPreProcessor(mean=list(Wt.PIXEL_MEAN), std=list(Wt.PIXEL_STD), bgr_to_rgb=True)
         super().__init__(data_preprocessor=data_preprocessor)
         if model_type == "GEM" and cls_token_lambda != 0:
@@ -609,7 +633,7 @@ class Segmentor(_HipSegmentorBase):
                     slide_crop, cls_token_lambda, bg_idx, apply_sim_feat_up, sim_feat_up_cfg, 0.0,
                     checkpoint, text_features, text_encoder, precision, synthetic_ok, tiles_per_launch, tokenizer=tokenizer,
                     tile_group=tile_group, label_head=label_head, prob_head=prob_head, pamr_steps=pamr_steps, pamr_stride=pamr_stride,
-                             resize_head=resize_head)
+                             resize_head=resize_head, area_thd=area_thd)
         # opt-in extra: kwargs of the reference's CrossTileFusion (cross_tile_fusion.py:24-60), which the reference never calls (R2)
         self.cross_tile_fusion_cfg = cross_tile_fusion_cfg
         self.output_cls_token = cls_token_lambda != 0

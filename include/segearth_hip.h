@@ -695,6 +695,61 @@ int sg_pamr_step(const float* weights, const float* in, float* out, int Q, int H
 int sg_pamr(const float* guide, float* logits_inout, int Q, int H, int W, const int* dilations, int n_dil, int steps, void* workspace,
             size_t workspace_bytes, sg_stream s);
 
+/* ---- area_thd: per-image suppression of small-area classes ---------------------------------------------------------------------
+ * The `area_thd` option of the training-free open-vocabulary segmenters: a class that wins only a small share of an image's
+ * non-background pixels is removed from that image and its pixels go to the best remaining class.  The definition, for one image:
+ *   p [K,H,W] f32 = the class probabilities exactly as the tail produces them (after stitch, the resize to ori_shape, PAMR, logit scale,
+ *   softmax and the synonym maximum); area_thd a double >= 0 (the option's range is [0, 1]; above 1 every non-background class goes).
+ *   1. l0(x)    = the class of the first maximum of p[:,x] (lowest class index on ties), BEFORE prob_thd.
+ *   2. area[c]  = the number of pixels with l0 = c, int64; total = sum over c != bg_idx of area[c].
+ *   3. keep[c]  = (c == bg_idx) or (double)area[c] > area_thd * (double)total.  The comparison is strict and is evaluated in double on
+ *                 the device (upstream compares in the logits' dtype; counts above 2^24 are not exact in f32).  The background class
+ *                 is always kept; total = 0 keeps only the background.
+ *   4. p'[c]    = keep[c] ? p[c] : 0: what the probabilities hold afterwards.
+ *   5. label(x) = the kept class with the largest p[c,x] (lowest index on ties), or bg_idx if that maximum is < prob_thd.
+ * Dropped classes are EXCLUDED from the arg-max of step 5 rather than compared as zeros.  The two readings differ only at a pixel where
+ * every kept probability is exactly 0 (the zeros of the dropped planes then tie with them and a dropped class of lower index would win);
+ * they never differ for bg_idx = 0, because the background is kept and has the lowest index.
+ * The first pass is the existing tail run with prob_thd = 0, whose labels are l0.  No entry synchronises with the host.
+ *   sg_class_area[_multi]        labels int64 -> counts int64 [K] / [N,K], ADDED to `counts` (the caller zeroes it).  A label outside [0,K)
+ *                                is not counted.  32-bit counts per workgroup in LDS, one 64-bit add per non-zero bin per workgroup:
+ *                                integers end to end, byte-identical across repeats and launch shapes.  Multi: image n holds
+ *                                image_pixels[n] labels at out_offset[n] of the flat buffer of out_pixels labels; block_prefix [N+1] =
+ *                                exclusive prefix sum of ceil(image_pixels[n] / 4096); a block never straddles two images.
+ *   sg_area_keep                 counts [N,K], bg_idx, area_thd -> keep int32 [N,K] (1 / 0), step 3, one launch of N workgroups.
+ *   sg_area_filter_probs[_multi] steps 4 and 5: probs in place, first-pass labels in, final labels out (labels_in == labels_out is
+ *                                allowed).  A pixel whose l0 is kept reads p[l0] only; one whose l0 is dropped (or outside [0,K)) takes
+ *                                the first maximum over the kept planes.  Comparisons and stores, no arithmetic: byte-equal to the
+ *                                definition on the same inputs.  Multi: sg_postprocess_multi's output layout (labels of image n at
+ *                                out_offset[n], probs [K,H,W] at K * out_offset[n], block_prefix of ceil(H*W/256)), keep [N,K].
+ *   sg_area_relabel[_multi]      the labels-only route, no canvas and no probability planes: sg_label_head[_multi]'s arguments plus keep,
+ *                                the first-pass conf, and labels in/out (the first pass: sg_label_head with prob_thd = 0 and conf).  A
+ *                                64 x 4 pixel block in which every first label is kept gathers nothing and writes
+ *                                conf < prob_thd ? bg_idx : l0.  A block that holds a dropped label repeats sg_label_head's statements
+ *                                with the best (value, class) pair restricted to kept classes.  Contract: every pixel equals
+ *                                sg_label_head called with a query_idx in which the queries of dropped classes are -1.
+ * Limits: 1 <= K <= SG_AREA_MAX_K (the per-workgroup table of K 32-bit counts: 16 KiB, so far more than two workgroups share a CU's
+ * LDS; there is no slower path beyond it), 0 <= bg_idx < K, n_pixels <= 2^40.  Every refusal (a null pointer, a limit, K, a bg_idx out of
+ * range) is SG_ERR_INVALID before any device work. */
+#define SG_AREA_MAX_K 4096
+int sg_class_area(const int64_t* labels, int64_t n_pixels, int K, int64_t* counts, sg_stream s);
+int sg_class_area_multi(const int64_t* labels, const int64_t* image_pixels, const int64_t* out_offset, const int64_t* block_prefix, int N,
+                        int64_t total_blocks, int64_t out_pixels, int K, int64_t* counts, sg_stream s);
+int sg_area_keep(const int64_t* counts, int N, int K, int bg_idx, double area_thd, int32_t* keep, sg_stream s);
+int sg_area_filter_probs(float* probs, const int64_t* labels_in, const int32_t* keep, int K, int H, int W, float prob_thd, int bg_idx,
+                         int64_t* labels_out, sg_stream s);
+int sg_area_filter_probs_multi(float* probs, const int64_t* labels_in, const int32_t* keep, const int32_t* out_hw, const int64_t* out_offset,
+                               const int64_t* block_prefix, int N, int64_t total_blocks, int64_t out_pixels, int K, float prob_thd,
+                               int bg_idx, int64_t* labels_out, sg_stream s);
+int sg_area_relabel(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t,
+                    int pad_l, int H, int W, const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx,
+                    const int32_t* keep, const float* conf, int64_t* labels, sg_stream s);
+int sg_area_relabel_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh, int gw,
+                          int up_h, int up_w, int pad_t, int pad_l, const int32_t* image_hw, const int32_t* image_tiles,
+                          const int64_t* out_offset, const int64_t* block_prefix, int N, int64_t total_blocks, int64_t out_pixels,
+                          const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx, const int32_t* keep,
+                          const float* conf, int64_t* labels, sg_stream s);
+
 #ifdef __cplusplus
 }
 #endif
