@@ -319,28 +319,6 @@ def postprocess(logits, query_idx, num_classes: int, logit_scale: float, prob_th
     return probs, labels
 
 
-@on_tensor_device
-def label_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, query_idx, num_classes: int, logit_scale: float, prob_thd: float,
-               bg_idx: int, want_conf: bool = False):
-    """sg_label_head: ``stitch`` + ``postprocess`` without the canvas, for any Q.  tile_logits [T,Q,gh,gw]; windows int32 [T,4]
-    -> labels int64 [1,H,W], or (labels, conf f32 [H,W] = the winning class's probability) with ``want_conf``."""
-    lib = _lib.load()
-    tile_logits = _f32(tile_logits)
-    windows = windows.to(device=tile_logits.device, dtype=torch.int32).contiguous()
-    _require_gpu(tile_logits)
-    T, Q, gh, gw = tile_logits.shape
-    H, W = canvas_hw
-    qi = query_idx.to(device=tile_logits.device, dtype=torch.int32).contiguous()
-    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T:
-        raise ValueError(f"label_head: {T} tiles of {Q} queries, but {windows.numel() // 4} windows and {qi.numel()} query indices")
-    labels = torch.empty(1, H, W, dtype=torch.int64, device=tile_logits.device)
-    conf = torch.empty(H, W, dtype=torch.float32, device=tile_logits.device) if want_conf else None
-    check(lib.sg_label_head(ptr(tile_logits), ptr(windows), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1], H, W, ptr(qi),
-                            int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx), ptr(labels), ptr(conf), stream_ptr()),
-          "sg_label_head")
-    return (labels, conf) if want_conf else labels
-
-
 def _prefix(counts):
     out = [0]
     for c in counts:
@@ -348,29 +326,82 @@ def _prefix(counts):
     return out
 
 
-@on_tensor_device
-def stitch_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles):
-    """The canvases of N images in one launch (sg_stitch_multi).  tile_logits [T,Q,gh,gw]; windows [T,4] in each image's own
-    coordinates; tile_image [T] = image of each tile (0..N-1); image_hw [(H, W)] * N; image_tiles [(first, count)] * N.
-    -> (canvases: one flat f32 buffer, list of N views [Q,H,W] into it)."""
-    lib = _lib.load()
+def flat_views(flat, planes: int, image_hw):
+    """The views [planes,H,W] of one flat buffer that holds N images back to back with ``planes`` values per pixel."""
+    pix = _prefix(h * w for h, w in image_hw)
+    return [flat[planes * pix[n]:planes * pix[n + 1]].view(planes, h, w) for n, (h, w) in enumerate(image_hw)]
+
+
+def _tile_args(what, tile_logits, windows, up_hw, pad_tl, query_idx):
+    """What every single-image head takes: tile_logits [T,Q,gh,gw], windows int32 [T,4] (y1,y2,x1,x2) and the query indices, checked
+    against each other -> (device, the entry's leading arguments through pad_tl, query indices int32, the tensors those arguments point
+    into: hold them until the launch)."""
+    tile_logits = _f32(tile_logits)
+    windows = windows.to(device=tile_logits.device, dtype=torch.int32).contiguous()
+    _require_gpu(tile_logits)
+    T, Q, gh, gw = tile_logits.shape
+    qi = query_idx.to(device=tile_logits.device, dtype=torch.int32).contiguous()
+    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T:
+        raise ValueError(f"{what}: {T} tiles of {Q} queries, but {windows.numel() // 4} windows and {qi.numel()} query indices")
+    return tile_logits.device, (ptr(tile_logits), ptr(windows), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1]), qi, (tile_logits, windows)
+
+
+def _multi_args(what, tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, query_idx=None, out_hw=None, planes: int = 1):
+    """What every multi-image launch takes.  tile_logits [T,Q,gh,gw]; windows [T,4] in each image's own coordinates; tile_image [T] =
+    image of each tile (0..N-1); image_hw [(H, W)] * N; image_tiles [(first, count)] * N; out_hw [(H, W)] * N for the resized heads, whose
+    outputs, offsets and blocks are counted in OUTPUT pixels.  Checks the sizes against each other and builds the two descriptor tensors:
+    i32 [image hw | image tiles | out hw] and i64 [planes * first output pixel | prefix of the 64 x 4 blocks].
+    -> (device, the entry's leading arguments through the block count, query indices int32 or None, the prefix of the output pixels, the
+    tensors those arguments point into: hold them until the launch)."""
     tile_logits = _f32(tile_logits)
     _require_gpu(tile_logits)
     dev = tile_logits.device
     T, Q, gh, gw = tile_logits.shape
     N = len(image_hw)
-    pix = _prefix(h * w for h, w in image_hw)
-    blocks = _prefix(-(-w // 64) * -(-h // 4) for h, w in image_hw)
-    canvases = torch.empty(Q * pix[-1], dtype=torch.float32, device=dev)
-    i32 = torch.tensor([list(hw) for hw in image_hw] + [list(ft) for ft in image_tiles], dtype=torch.int32).to(dev)
-    i64 = torch.tensor([Q * p for p in pix[:-1]] + blocks, dtype=torch.int64).to(dev)
+    qi = None if query_idx is None else query_idx.to(device=dev, dtype=torch.int32).contiguous()
     windows = torch.as_tensor(windows, dtype=torch.int32).to(dev).contiguous()
     tile_image = torch.as_tensor(tile_image, dtype=torch.int32).to(dev).contiguous()
-    check(lib.sg_stitch_multi(ptr(tile_logits), ptr(windows), ptr(tile_image), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1],
-                              ptr(i32), ptr(i32[N:]), ptr(i64), ptr(i64[N:]), N, blocks[-1], canvases.numel(), ptr(canvases), stream_ptr()),
-          "sg_stitch_multi")
-    views = [canvases[Q * pix[n]:Q * pix[n + 1]].view(Q, h, w) for n, (h, w) in enumerate(image_hw)]
-    return canvases, views
+    if (qi is not None and int(qi.numel()) != Q) or int(windows.numel()) != 4 * T or int(tile_image.numel()) != T or len(image_tiles) != N or \
+            (out_hw is not None and len(out_hw) != N):
+        raise ValueError(f"{what}: tile logits, windows, tile_image, image descriptors and query indices disagree in size")
+    if any(f < 0 or c <= 0 or f + c > T for f, c in image_tiles):
+        raise ValueError(f"{what}: image_tiles {list(image_tiles)} leave the {T} tiles")
+    sizes = image_hw if out_hw is None else out_hw
+    pix = _prefix(h * w for h, w in sizes)
+    blocks = _prefix(-(-w // 64) * -(-h // 4) for h, w in sizes)
+    i32 = torch.tensor([list(hw) for hw in image_hw] + [list(ft) for ft in image_tiles] + [list(hw) for hw in out_hw or ()],
+                       dtype=torch.int32).to(dev)
+    i64 = torch.tensor([planes * p for p in pix[:-1]] + blocks, dtype=torch.int64).to(dev)
+    desc = (ptr(i32), ptr(i32[N:])) + ((ptr(i32[2 * N:]),) if out_hw is not None else ()) + (ptr(i64), ptr(i64[N:]), N, blocks[-1])
+    lead = (ptr(tile_logits), ptr(windows), ptr(tile_image), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1]) + desc
+    return dev, lead, qi, pix, (tile_logits, windows, tile_image, i32, i64)
+
+
+@on_tensor_device
+def label_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, query_idx, num_classes: int, logit_scale: float, prob_thd: float,
+               bg_idx: int, want_conf: bool = False):
+    """sg_label_head: ``stitch`` + ``postprocess`` without the canvas, for any Q.  tile_logits [T,Q,gh,gw]; windows int32 [T,4]
+    -> labels int64 [1,H,W], or (labels, conf f32 [H,W] = the winning class's probability) with ``want_conf``."""
+    lib = _lib.load()
+    dev, lead, qi, hold = _tile_args("label_head", tile_logits, windows, up_hw, pad_tl, query_idx)
+    H, W = canvas_hw
+    labels = torch.empty(1, H, W, dtype=torch.int64, device=dev)
+    conf = torch.empty(H, W, dtype=torch.float32, device=dev) if want_conf else None
+    check(lib.sg_label_head(*lead, H, W, ptr(qi), int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx), ptr(labels), ptr(conf),
+                            stream_ptr()), "sg_label_head")
+    return (labels, conf) if want_conf else labels
+
+
+@on_tensor_device
+def stitch_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles):
+    """The canvases of N images in one launch (sg_stitch_multi); the arguments: ``_multi_args``.
+    -> (canvases: one flat f32 buffer, list of N views [Q,H,W] into it)."""
+    lib = _lib.load()
+    Q = tile_logits.shape[1]
+    dev, lead, _, pix, hold = _multi_args("stitch_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, planes=Q)
+    canvases = torch.empty(Q * pix[-1], dtype=torch.float32, device=dev)
+    check(lib.sg_stitch_multi(*lead, canvases.numel(), ptr(canvases), stream_ptr()), "sg_stitch_multi")
+    return canvases, flat_views(canvases, Q, image_hw)
 
 
 @on_tensor_device
@@ -381,31 +412,14 @@ def label_head_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, 
     the list of conf f32 [H,W] maps as a third result with ``want_conf`` (``flat_conf``: the one flat f32 buffer those maps are views
     of instead of the list).  Equals ``label_head`` per image byte for byte."""
     lib = _lib.load()
-    tile_logits = _f32(tile_logits)
-    _require_gpu(tile_logits)
-    dev = tile_logits.device
-    T, Q, gh, gw = tile_logits.shape
-    N = len(image_hw)
-    qi = query_idx.to(device=dev, dtype=torch.int32).contiguous()
-    windows = torch.as_tensor(windows, dtype=torch.int32).to(dev).contiguous()
-    tile_image = torch.as_tensor(tile_image, dtype=torch.int32).to(dev).contiguous()
-    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T or int(tile_image.numel()) != T or len(image_tiles) != N:
-        raise ValueError("label_head_multi: tile logits, windows, tile_image, image descriptors and query indices disagree in size")
-    if any(f < 0 or c <= 0 or f + c > T for f, c in image_tiles):
-        raise ValueError(f"label_head_multi: image_tiles {list(image_tiles)} leave the {T} tiles")
-    pix = _prefix(h * w for h, w in image_hw)
-    blocks = _prefix(-(-w // 64) * -(-h // 4) for h, w in image_hw)
-    i32 = torch.tensor([list(hw) for hw in image_hw] + [list(ft) for ft in image_tiles], dtype=torch.int32).to(dev)
-    i64 = torch.tensor(pix[:-1] + blocks, dtype=torch.int64).to(dev)
+    dev, lead, qi, pix, hold = _multi_args("label_head_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, query_idx)
     labels = torch.empty(pix[-1], dtype=torch.int64, device=dev)
     conf = torch.empty(pix[-1], dtype=torch.float32, device=dev) if want_conf else None
-    check(lib.sg_label_head_multi(ptr(tile_logits), ptr(windows), ptr(tile_image), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1],
-                                  ptr(i32), ptr(i32[N:]), ptr(i64), ptr(i64[N:]), N, blocks[-1], pix[-1], ptr(qi), int(num_classes),
-                                  float(logit_scale), float(prob_thd), int(bg_idx), ptr(labels), ptr(conf), stream_ptr()),
-          "sg_label_head_multi")
-    lab = [labels[pix[n]:pix[n + 1]].view(1, h, w) for n, (h, w) in enumerate(image_hw)]
+    check(lib.sg_label_head_multi(*lead, pix[-1], ptr(qi), int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx), ptr(labels),
+                                  ptr(conf), stream_ptr()), "sg_label_head_multi")
+    lab = flat_views(labels, 1, image_hw)
     if want_conf:
-        return lab, labels, (conf if flat_conf else [conf[pix[n]:pix[n + 1]].view(h, w) for n, (h, w) in enumerate(image_hw)])
+        return lab, labels, (conf if flat_conf else [c[0] for c in flat_views(conf, 1, image_hw)])
     return lab, labels
 
 
@@ -414,19 +428,12 @@ def prob_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, query_idx, num_cla
     """sg_prob_head: ``stitch`` + ``postprocess`` without the canvas, for any Q.  Arguments as ``label_head``
     -> (probs f32 [K,H,W], labels int64 [1,H,W]), byte for byte what ``postprocess(stitch(...))`` returns."""
     lib = _lib.load()
-    tile_logits = _f32(tile_logits)
-    windows = windows.to(device=tile_logits.device, dtype=torch.int32).contiguous()
-    _require_gpu(tile_logits)
-    T, Q, gh, gw = tile_logits.shape
+    dev, lead, qi, hold = _tile_args("prob_head", tile_logits, windows, up_hw, pad_tl, query_idx)
     H, W = canvas_hw
-    qi = query_idx.to(device=tile_logits.device, dtype=torch.int32).contiguous()
-    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T:
-        raise ValueError(f"prob_head: {T} tiles of {Q} queries, but {windows.numel() // 4} windows and {qi.numel()} query indices")
-    probs = torch.empty(int(num_classes), H, W, dtype=torch.float32, device=tile_logits.device)
-    labels = torch.empty(1, H, W, dtype=torch.int64, device=tile_logits.device)
-    check(lib.sg_prob_head(ptr(tile_logits), ptr(windows), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1], H, W, ptr(qi),
-                           int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx), ptr(probs), ptr(labels), stream_ptr()),
-          "sg_prob_head")
+    probs = torch.empty(int(num_classes), H, W, dtype=torch.float32, device=dev)
+    labels = torch.empty(1, H, W, dtype=torch.int64, device=dev)
+    check(lib.sg_prob_head(*lead, H, W, ptr(qi), int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx), ptr(probs), ptr(labels),
+                           stream_ptr()), "sg_prob_head")
     return probs, labels
 
 
@@ -438,29 +445,13 @@ def prob_head_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, i
     of, images back to back): what ``postprocess_multi(..., want_probs=True, flat_labels=True)`` returns, and ``prob_head`` per image
     byte for byte.  The probs of image n are a view at K * (its first pixel) of one flat f32 buffer (a fourth result with ``flat_probs``)."""
     lib = _lib.load()
-    tile_logits = _f32(tile_logits)
-    _require_gpu(tile_logits)
-    dev = tile_logits.device
-    T, Q, gh, gw = tile_logits.shape
-    N, K = len(image_hw), int(num_classes)
-    qi = query_idx.to(device=dev, dtype=torch.int32).contiguous()
-    windows = torch.as_tensor(windows, dtype=torch.int32).to(dev).contiguous()
-    tile_image = torch.as_tensor(tile_image, dtype=torch.int32).to(dev).contiguous()
-    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T or int(tile_image.numel()) != T or len(image_tiles) != N:
-        raise ValueError("prob_head_multi: tile logits, windows, tile_image, image descriptors and query indices disagree in size")
-    if any(f < 0 or c <= 0 or f + c > T for f, c in image_tiles):
-        raise ValueError(f"prob_head_multi: image_tiles {list(image_tiles)} leave the {T} tiles")
-    pix = _prefix(h * w for h, w in image_hw)
-    blocks = _prefix(-(-w // 64) * -(-h // 4) for h, w in image_hw)
-    i32 = torch.tensor([list(hw) for hw in image_hw] + [list(ft) for ft in image_tiles], dtype=torch.int32).to(dev)
-    i64 = torch.tensor(pix[:-1] + blocks, dtype=torch.int64).to(dev)
+    dev, lead, qi, pix, hold = _multi_args("prob_head_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, query_idx)
+    K = int(num_classes)
     labels = torch.empty(pix[-1], dtype=torch.int64, device=dev)
     probs = torch.empty(max(K, 0) * pix[-1], dtype=torch.float32, device=dev)
-    check(lib.sg_prob_head_multi(ptr(tile_logits), ptr(windows), ptr(tile_image), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1],
-                                 ptr(i32), ptr(i32[N:]), ptr(i64), ptr(i64[N:]), N, blocks[-1], pix[-1], ptr(qi), K, float(logit_scale),
-                                 float(prob_thd), int(bg_idx), ptr(probs), ptr(labels), stream_ptr()), "sg_prob_head_multi")
-    lab = [labels[pix[n]:pix[n + 1]].view(1, h, w) for n, (h, w) in enumerate(image_hw)]
-    prb = [probs[K * pix[n]:K * pix[n + 1]].view(K, h, w) for n, (h, w) in enumerate(image_hw)]
+    check(lib.sg_prob_head_multi(*lead, pix[-1], ptr(qi), K, float(logit_scale), float(prob_thd), int(bg_idx), ptr(probs), ptr(labels),
+                                 stream_ptr()), "sg_prob_head_multi")
+    prb, lab = flat_views(probs, K, image_hw), flat_views(labels, 1, image_hw)
     return (prb, lab, labels, probs) if flat_probs else (prb, lab, labels)
 
 
@@ -474,19 +465,13 @@ def topk_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, query_idx, num_cla
     [k,H,W]), slots in descending probability, equal values by ascending class; -1 / 0 in a slot no class filled (classes that own no
     query never appear).  Plane 0 is ``label_head``'s label before the threshold and its conf, byte for byte."""
     lib = _lib.load()
-    tile_logits = _f32(tile_logits)
-    windows = windows.to(device=tile_logits.device, dtype=torch.int32).contiguous()
-    _require_gpu(tile_logits)
-    T, Q, gh, gw = tile_logits.shape
+    dev, lead, qi, hold = _tile_args("topk_head", tile_logits, windows, up_hw, pad_tl, query_idx)
     H, W = canvas_hw
-    qi = query_idx.to(device=tile_logits.device, dtype=torch.int32).contiguous()
-    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T:
-        raise ValueError(f"topk_head: {T} tiles of {Q} queries, but {windows.numel() // 4} windows and {qi.numel()} query indices")
     kk = max(int(k), 0)
-    classes = torch.empty(kk, H, W, dtype=torch.int32, device=tile_logits.device)
-    probs = torch.empty(kk, H, W, dtype=torch.float32, device=tile_logits.device)
-    check(lib.sg_topk_head(ptr(tile_logits), ptr(windows), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1], H, W, ptr(qi),
-                           int(num_classes), float(logit_scale), int(k), ptr(classes), ptr(probs), stream_ptr()), "sg_topk_head")
+    classes = torch.empty(kk, H, W, dtype=torch.int32, device=dev)
+    probs = torch.empty(kk, H, W, dtype=torch.float32, device=dev)
+    check(lib.sg_topk_head(*lead, H, W, ptr(qi), int(num_classes), float(logit_scale), int(k), ptr(classes), ptr(probs), stream_ptr()),
+          "sg_topk_head")
     return classes, probs
 
 
@@ -497,30 +482,13 @@ def topk_head_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, i
     -> (list of classes int32 [k,H,W], list of probs f32 [k,H,W]): views at k * (the image's first pixel) of two flat buffers.  Equals
     ``topk_head`` per image byte for byte."""
     lib = _lib.load()
-    tile_logits = _f32(tile_logits)
-    _require_gpu(tile_logits)
-    dev = tile_logits.device
-    T, Q, gh, gw = tile_logits.shape
-    N, kk = len(image_hw), max(int(k), 0)
-    qi = query_idx.to(device=dev, dtype=torch.int32).contiguous()
-    windows = torch.as_tensor(windows, dtype=torch.int32).to(dev).contiguous()
-    tile_image = torch.as_tensor(tile_image, dtype=torch.int32).to(dev).contiguous()
-    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T or int(tile_image.numel()) != T or len(image_tiles) != N:
-        raise ValueError("topk_head_multi: tile logits, windows, tile_image, image descriptors and query indices disagree in size")
-    if any(f < 0 or c <= 0 or f + c > T for f, c in image_tiles):
-        raise ValueError(f"topk_head_multi: image_tiles {list(image_tiles)} leave the {T} tiles")
-    pix = _prefix(h * w for h, w in image_hw)
-    blocks = _prefix(-(-w // 64) * -(-h // 4) for h, w in image_hw)
-    i32 = torch.tensor([list(hw) for hw in image_hw] + [list(ft) for ft in image_tiles], dtype=torch.int32).to(dev)
-    i64 = torch.tensor(pix[:-1] + blocks, dtype=torch.int64).to(dev)
+    dev, lead, qi, pix, hold = _multi_args("topk_head_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, query_idx)
+    kk = max(int(k), 0)
     classes = torch.empty(kk * pix[-1], dtype=torch.int32, device=dev)
     probs = torch.empty(kk * pix[-1], dtype=torch.float32, device=dev)
-    check(lib.sg_topk_head_multi(ptr(tile_logits), ptr(windows), ptr(tile_image), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1],
-                                 ptr(i32), ptr(i32[N:]), ptr(i64), ptr(i64[N:]), N, blocks[-1], pix[-1], ptr(qi), int(num_classes),
-                                 float(logit_scale), int(k), ptr(classes), ptr(probs), stream_ptr()), "sg_topk_head_multi")
-    cls = [classes[kk * pix[n]:kk * pix[n + 1]].view(kk, h, w) for n, (h, w) in enumerate(image_hw)]
-    prb = [probs[kk * pix[n]:kk * pix[n + 1]].view(kk, h, w) for n, (h, w) in enumerate(image_hw)]
-    return cls, prb
+    check(lib.sg_topk_head_multi(*lead, pix[-1], ptr(qi), int(num_classes), float(logit_scale), int(k), ptr(classes), ptr(probs), stream_ptr()),
+          "sg_topk_head_multi")
+    return flat_views(classes, kk, image_hw), flat_views(probs, kk, image_hw)
 
 
 RESIZED_FORMS = {"auto": 0, "direct": 1, "staged": 2}                    # SG_RESIZED_* (include/segearth_hip.h)
@@ -553,41 +521,13 @@ def label_head_resized(tile_logits, windows, up_hw, pad_tl, canvas_hw, out_hw, q
     ``form``: "direct", "staged" (refused where a block's footprint does not fit the stage) or "auto"; the bytes do not depend on it."""
     flags = _resized_form(form, "label_head_resized", [(canvas_hw, out_hw)])
     lib = _lib.load()
-    tile_logits = _f32(tile_logits)
-    windows = windows.to(device=tile_logits.device, dtype=torch.int32).contiguous()
-    _require_gpu(tile_logits)
-    T, Q, gh, gw = tile_logits.shape
+    dev, lead, qi, hold = _tile_args("label_head_resized", tile_logits, windows, up_hw, pad_tl, query_idx)
     (h, w), (H, W) = canvas_hw, out_hw
-    qi = query_idx.to(device=tile_logits.device, dtype=torch.int32).contiguous()
-    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T:
-        raise ValueError(f"label_head_resized: {T} tiles of {Q} queries, but {windows.numel() // 4} windows and {qi.numel()} query indices")
-    labels = torch.empty(1, H, W, dtype=torch.int64, device=tile_logits.device)
-    conf = torch.empty(H, W, dtype=torch.float32, device=tile_logits.device) if want_conf else None
-    check(lib.sg_label_head_resized(ptr(tile_logits), ptr(windows), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1], h, w, H, W,
-                                    ptr(qi), int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx), ptr(labels), ptr(conf),
-                                    flags, stream_ptr()), "sg_label_head_resized")
+    labels = torch.empty(1, H, W, dtype=torch.int64, device=dev)
+    conf = torch.empty(H, W, dtype=torch.float32, device=dev) if want_conf else None
+    check(lib.sg_label_head_resized(*lead, h, w, H, W, ptr(qi), int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx),
+                                    ptr(labels), ptr(conf), flags, stream_ptr()), "sg_label_head_resized")
     return (labels, conf) if want_conf else labels
-
-
-def _resized_multi_args(what, tile_logits, windows, tile_image, image_hw, image_tiles, out_hw, query_idx):
-    """The descriptors the two resized multi-image entries share: (qi, windows, tile_image, i32 [canvas hw | tiles | out hw], i64
-    [out offsets | block prefix], pix, blocks) with the offsets and blocks counted in OUTPUT pixels."""
-    dev = tile_logits.device
-    T, Q = tile_logits.shape[:2]
-    N = len(image_hw)
-    qi = query_idx.to(device=dev, dtype=torch.int32).contiguous()
-    windows = torch.as_tensor(windows, dtype=torch.int32).to(dev).contiguous()
-    tile_image = torch.as_tensor(tile_image, dtype=torch.int32).to(dev).contiguous()
-    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T or int(tile_image.numel()) != T or len(image_tiles) != N or len(out_hw) != N:
-        raise ValueError(f"{what}: tile logits, windows, tile_image, image descriptors and query indices disagree in size")
-    if any(f < 0 or c <= 0 or f + c > T for f, c in image_tiles):
-        raise ValueError(f"{what}: image_tiles {list(image_tiles)} leave the {T} tiles")
-    pix = _prefix(h * w for h, w in out_hw)
-    blocks = _prefix(-(-w // 64) * -(-h // 4) for h, w in out_hw)
-    i32 = torch.tensor([list(hw) for hw in image_hw] + [list(ft) for ft in image_tiles] + [list(hw) for hw in out_hw],
-                       dtype=torch.int32).to(dev)
-    i64 = torch.tensor(pix[:-1] + blocks, dtype=torch.int64).to(dev)
-    return qi, windows, tile_image, i32, i64, pix, blocks
 
 
 @on_tensor_device
@@ -600,22 +540,14 @@ def label_head_resized_multi(tile_logits, windows, tile_image, up_hw, pad_tl, im
     out_hw = [tuple(int(v) for v in s) for s in out_hw]
     flags = _resized_form(form, "label_head_resized_multi", zip(image_hw, out_hw))
     lib = _lib.load()
-    tile_logits = _f32(tile_logits)
-    _require_gpu(tile_logits)
-    T, Q, gh, gw = tile_logits.shape
-    N = len(image_hw)
-    qi, windows, tile_image, i32, i64, pix, blocks = _resized_multi_args("label_head_resized_multi", tile_logits, windows, tile_image,
-                                                                         image_hw, image_tiles, out_hw, query_idx)
-    labels = torch.empty(pix[-1], dtype=torch.int64, device=tile_logits.device)
-    conf = torch.empty(pix[-1], dtype=torch.float32, device=tile_logits.device) if want_conf else None
-    check(lib.sg_label_head_resized_multi(ptr(tile_logits), ptr(windows), ptr(tile_image), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0],
-                                          pad_tl[1], ptr(i32), ptr(i32[N:]), ptr(i32[2 * N:]), ptr(i64), ptr(i64[N:]), N, blocks[-1], pix[-1],
-                                          ptr(qi), int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx), ptr(labels),
-                                          ptr(conf), flags, stream_ptr()), "sg_label_head_resized_multi")
-    lab = [labels[pix[n]:pix[n + 1]].view(1, h, w) for n, (h, w) in enumerate(out_hw)]
-    if want_conf:
-        return lab, labels, [conf[pix[n]:pix[n + 1]].view(h, w) for n, (h, w) in enumerate(out_hw)]
-    return lab, labels
+    dev, lead, qi, pix, hold = _multi_args("label_head_resized_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles,
+                                           query_idx, out_hw)
+    labels = torch.empty(pix[-1], dtype=torch.int64, device=dev)
+    conf = torch.empty(pix[-1], dtype=torch.float32, device=dev) if want_conf else None
+    check(lib.sg_label_head_resized_multi(*lead, pix[-1], ptr(qi), int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx),
+                                          ptr(labels), ptr(conf), flags, stream_ptr()), "sg_label_head_resized_multi")
+    lab = flat_views(labels, 1, out_hw)
+    return (lab, labels, [c[0] for c in flat_views(conf, 1, out_hw)]) if want_conf else (lab, labels)
 
 
 @on_tensor_device
@@ -625,20 +557,13 @@ def topk_head_resized(tile_logits, windows, up_hw, pad_tl, canvas_hw, out_hw, qu
     [k,H,W]), (H, W) = out_hw.  Plane 0 is ``label_head_resized``'s label before the threshold and its conf, byte for byte."""
     flags = _resized_form(form, "topk_head_resized", [(canvas_hw, out_hw)])
     lib = _lib.load()
-    tile_logits = _f32(tile_logits)
-    windows = windows.to(device=tile_logits.device, dtype=torch.int32).contiguous()
-    _require_gpu(tile_logits)
-    T, Q, gh, gw = tile_logits.shape
+    dev, lead, qi, hold = _tile_args("topk_head_resized", tile_logits, windows, up_hw, pad_tl, query_idx)
     (h, w), (H, W) = canvas_hw, out_hw
-    qi = query_idx.to(device=tile_logits.device, dtype=torch.int32).contiguous()
-    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T:
-        raise ValueError(f"topk_head_resized: {T} tiles of {Q} queries, but {windows.numel() // 4} windows and {qi.numel()} query indices")
     kk = max(int(k), 0)
-    classes = torch.empty(kk, H, W, dtype=torch.int32, device=tile_logits.device)
-    probs = torch.empty(kk, H, W, dtype=torch.float32, device=tile_logits.device)
-    check(lib.sg_topk_head_resized(ptr(tile_logits), ptr(windows), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1], h, w, H, W,
-                                   ptr(qi), int(num_classes), float(logit_scale), int(k), ptr(classes), ptr(probs), flags, stream_ptr()),
-          "sg_topk_head_resized")
+    classes = torch.empty(kk, H, W, dtype=torch.int32, device=dev)
+    probs = torch.empty(kk, H, W, dtype=torch.float32, device=dev)
+    check(lib.sg_topk_head_resized(*lead, h, w, H, W, ptr(qi), int(num_classes), float(logit_scale), int(k), ptr(classes), ptr(probs), flags,
+                                   stream_ptr()), "sg_topk_head_resized")
     return classes, probs
 
 
@@ -651,21 +576,14 @@ def topk_head_resized_multi(tile_logits, windows, tile_image, up_hw, pad_tl, ima
     out_hw = [tuple(int(v) for v in s) for s in out_hw]
     flags = _resized_form(form, "topk_head_resized_multi", zip(image_hw, out_hw))
     lib = _lib.load()
-    tile_logits = _f32(tile_logits)
-    _require_gpu(tile_logits)
-    T, Q, gh, gw = tile_logits.shape
-    N, kk = len(image_hw), max(int(k), 0)
-    qi, windows, tile_image, i32, i64, pix, blocks = _resized_multi_args("topk_head_resized_multi", tile_logits, windows, tile_image,
-                                                                         image_hw, image_tiles, out_hw, query_idx)
-    classes = torch.empty(kk * pix[-1], dtype=torch.int32, device=tile_logits.device)
-    probs = torch.empty(kk * pix[-1], dtype=torch.float32, device=tile_logits.device)
-    check(lib.sg_topk_head_resized_multi(ptr(tile_logits), ptr(windows), ptr(tile_image), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0],
-                                         pad_tl[1], ptr(i32), ptr(i32[N:]), ptr(i32[2 * N:]), ptr(i64), ptr(i64[N:]), N, blocks[-1], pix[-1],
-                                         ptr(qi), int(num_classes), float(logit_scale), int(k), ptr(classes), ptr(probs), flags,
+    dev, lead, qi, pix, hold = _multi_args("topk_head_resized_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles,
+                                           query_idx, out_hw)
+    kk = max(int(k), 0)
+    classes = torch.empty(kk * pix[-1], dtype=torch.int32, device=dev)
+    probs = torch.empty(kk * pix[-1], dtype=torch.float32, device=dev)
+    check(lib.sg_topk_head_resized_multi(*lead, pix[-1], ptr(qi), int(num_classes), float(logit_scale), int(k), ptr(classes), ptr(probs), flags,
                                          stream_ptr()), "sg_topk_head_resized_multi")
-    cls = [classes[kk * pix[n]:kk * pix[n + 1]].view(kk, h, w) for n, (h, w) in enumerate(out_hw)]
-    prb = [probs[kk * pix[n]:kk * pix[n + 1]].view(kk, h, w) for n, (h, w) in enumerate(out_hw)]
-    return cls, prb
+    return flat_views(classes, kk, out_hw), flat_views(probs, kk, out_hw)
 
 
 def topk_from_probs(probs, query_idx, k: int):
@@ -715,8 +633,8 @@ def postprocess_multi(canvases, canvas_hw, query_idx, num_classes: int, logit_sc
     check(lib.sg_postprocess_multi(ptr(canvases), ptr(i32), ptr(i64), ptr(i32[N:]), ptr(i64[N:]), ptr(i64[2 * N:]), N, blocks[-1],
                                    canvases.numel(), pix[-1], ptr(qi), Q, K, float(logit_scale), float(prob_thd), int(bg_idx), ptr(probs),
                                    ptr(labels), stream_ptr()), "sg_postprocess_multi")
-    lab = [labels[pix[n]:pix[n + 1]].view(1, h, w) for n, (h, w) in enumerate(out_hw)]
-    prb = [probs[K * pix[n]:K * pix[n + 1]].view(K, h, w) if want_probs else None for n, (h, w) in enumerate(out_hw)]
+    lab = flat_views(labels, 1, out_hw)
+    prb = flat_views(probs, K, out_hw) if want_probs else [None] * N
     if flat_labels and flat_probs:
         return prb, lab, labels, probs
     return (prb, lab, labels) if flat_labels else (prb, lab)
@@ -1002,23 +920,16 @@ def area_relabel(tile_logits, windows, up_hw, pad_tl, canvas_hw, query_idx, num_
     ``label_head`` plus keep int32 [K] and the first pass's outputs (``label_head(..., prob_thd=0, want_conf=True)``): conf f32 [H,W] and
     labels int64 [1,H,W], which are rewritten IN PLACE and returned.  Equals ``label_head`` on a ``query_idx`` whose dropped queries are -1."""
     lib = _lib.load()
-    tile_logits = _f32(tile_logits)
-    windows = windows.to(device=tile_logits.device, dtype=torch.int32).contiguous()
-    _require_gpu(tile_logits)
-    T, Q, gh, gw = tile_logits.shape
+    dev, lead, qi, hold = _tile_args("area_relabel", tile_logits, windows, up_hw, pad_tl, query_idx)
     H, W = canvas_hw
-    qi = query_idx.to(device=tile_logits.device, dtype=torch.int32).contiguous()
-    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T:
-        raise ValueError(f"area_relabel: {T} tiles of {Q} queries, but {windows.numel() // 4} windows and {qi.numel()} query indices")
     K, bg_idx = area_args("area_relabel", num_classes, bg_idx)
     labels = _i64_labels("area_relabel", labels)
     if labels.numel() != H * W or conf.dtype != torch.float32 or not conf.is_contiguous() or conf.numel() != H * W or \
-            conf.device != tile_logits.device or labels.device != tile_logits.device:
+            conf.device != dev or labels.device != dev:
         raise ValueError(f"area_relabel: labels {tuple(labels.shape)} / conf {tuple(conf.shape)} are not the first pass of a {H} x {W} image")
-    _keep_arg("area_relabel", keep, (K,), tile_logits.device)
-    check(lib.sg_area_relabel(ptr(tile_logits), ptr(windows), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1], H, W, ptr(qi), K,
-                              float(logit_scale), float(prob_thd), bg_idx, ptr(keep), ptr(conf), ptr(labels), stream_ptr()),
-          "sg_area_relabel")
+    _keep_arg("area_relabel", keep, (K,), dev)
+    check(lib.sg_area_relabel(*lead, H, W, ptr(qi), K, float(logit_scale), float(prob_thd), bg_idx, ptr(keep), ptr(conf), ptr(labels),
+                              stream_ptr()), "sg_area_relabel")
     return labels
 
 
@@ -1029,31 +940,15 @@ def area_relabel_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw
     [N,K]; conf f32 and labels int64 are the flat first-pass buffers of ``label_head_multi(..., prob_thd=0, want_conf=True)``, images
     back to back; labels are rewritten IN PLACE and returned.  Equals ``area_relabel`` per image byte for byte."""
     lib = _lib.load()
-    tile_logits = _f32(tile_logits)
-    _require_gpu(tile_logits)
-    dev = tile_logits.device
-    T, Q, gh, gw = tile_logits.shape
-    N = len(image_hw)
-    qi = query_idx.to(device=dev, dtype=torch.int32).contiguous()
-    windows = torch.as_tensor(windows, dtype=torch.int32).to(dev).contiguous()
-    tile_image = torch.as_tensor(tile_image, dtype=torch.int32).to(dev).contiguous()
-    if int(qi.numel()) != Q or int(windows.numel()) != 4 * T or int(tile_image.numel()) != T or len(image_tiles) != N:
-        raise ValueError("area_relabel_multi: tile logits, windows, tile_image, image descriptors and query indices disagree in size")
-    if any(f < 0 or c <= 0 or f + c > T for f, c in image_tiles):
-        raise ValueError(f"area_relabel_multi: image_tiles {list(image_tiles)} leave the {T} tiles")
+    dev, lead, qi, pix, hold = _multi_args("area_relabel_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, query_idx)
     K, bg_idx = area_args("area_relabel_multi", num_classes, bg_idx)
-    pix = _prefix(h * w for h, w in image_hw)
     labels = _i64_labels("area_relabel_multi", labels)
     if labels.numel() != pix[-1] or conf.dtype != torch.float32 or not conf.is_contiguous() or conf.numel() != pix[-1] or \
             conf.device != dev or labels.device != dev:
         raise ValueError(f"area_relabel_multi: labels / conf are not the flat first pass of {pix[-1]} pixels")
-    _keep_arg("area_relabel_multi", keep, (N, K), dev)
-    blocks = _prefix(-(-w // 64) * -(-h // 4) for h, w in image_hw)
-    i32 = torch.tensor([list(hw) for hw in image_hw] + [list(ft) for ft in image_tiles], dtype=torch.int32).to(dev)
-    i64 = torch.tensor(pix[:-1] + blocks, dtype=torch.int64).to(dev)
-    check(lib.sg_area_relabel_multi(ptr(tile_logits), ptr(windows), ptr(tile_image), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1],
-                                    ptr(i32), ptr(i32[N:]), ptr(i64), ptr(i64[N:]), N, blocks[-1], pix[-1], ptr(qi), K, float(logit_scale),
-                                    float(prob_thd), bg_idx, ptr(keep), ptr(conf), ptr(labels), stream_ptr()), "sg_area_relabel_multi")
+    _keep_arg("area_relabel_multi", keep, (len(image_hw), K), dev)
+    check(lib.sg_area_relabel_multi(*lead, pix[-1], ptr(qi), K, float(logit_scale), float(prob_thd), bg_idx, ptr(keep), ptr(conf), ptr(labels),
+                                    stream_ptr()), "sg_area_relabel_multi")
     return labels
 
 

@@ -313,11 +313,55 @@ def _scene_hw(s: torch.Tensor) -> Tuple[int, int]:
     return (int(s.shape[0]), int(s.shape[1])) if s.dtype == torch.uint8 else (int(s.shape[-2]), int(s.shape[-1]))
 
 
+def _images(scenes):
+    """What ``pack_scenes`` takes, as a sequence of images: a single [3,H,W] / [H,W,3] tensor is one image."""
+    return [scenes] if torch.is_tensor(scenes) and scenes.dim() == 3 else scenes
+
+
 def _out_pixels(ori_shapes, i: int, scenes) -> int:
     """Pixels of image i's outputs: its ori_shape, or its own size."""
     o = ori_shapes[i] if ori_shapes is not None else None
-    h, w = (int(o[0]), int(o[1])) if o is not None else _scene_hw(scenes if torch.is_tensor(scenes) and scenes.dim() == 3 else scenes[i])
+    h, w = (int(o[0]), int(o[1])) if o is not None else _scene_hw(_images(scenes)[i])
     return h * w
+
+
+def _ori_differs(ori_shapes, scenes) -> bool:
+    """Whether some image's ``ori_shape`` is another size than the image."""
+    return ori_shapes is not None and any(o is not None and tuple(o) != _scene_hw(s) for o, s in zip(ori_shapes, _images(scenes)))
+
+
+def _out_sizes(ori_shapes, idx, shapes) -> List[Tuple[int, int]]:
+    """The output size of every image of a flush group (images ``idx``, sizes ``shapes``): its ori_shape, or its own size."""
+    return [tuple(shapes[n]) if ori_shapes is None or ori_shapes[i] is None else tuple(int(v) for v in ori_shapes[i])
+            for n, i in enumerate(idx)]
+
+
+@dataclass(frozen=True)
+class TileGeometry:
+    """What the patch grid makes of a tile of ``tile_hw``: the pad to whole patches, the patch grid, the padded size that a tile's
+    logits are upsampled to, and the padded tile's offset of the window's top-left corner."""
+    pad: Tuple[int, int, int, int]       # (l, r, t, b), engine.compute_padsize
+    grid: Tuple[int, int]                # (gh, gw)
+    up_hw: Tuple[int, int]
+    pad_tl: Tuple[int, int]              # (t, l)
+
+
+def tile_geometry(tile_hw: Tuple[int, int], patch: int) -> TileGeometry:
+    th, tw = tile_hw
+    l, r, t, b = compute_padsize(th, tw, patch)
+    up_hw = (th + t + b, tw + l + r)
+    return TileGeometry((l, r, t, b), (up_hw[0] // patch, up_hw[1] // patch), up_hw, (t, l))
+
+
+# The routes of a tail (DESIGN.md section 5 'Route table'): a head on the tile logits (no canvas), a resized head on the tile logits (no
+# canvas, another ori_shape), or the stitched canvas with one multi-image post-process per flush group / image by image.
+HEAD, RESIZED_HEAD, CANVAS_MULTI, CANVAS_EACH = "head", "resized_head", "canvas_multi", "canvas_each"
+
+
+@dataclass(frozen=True)
+class TailRoute:
+    route: str
+    pixel_bytes: int                     # what the planner counts per image pixel; per OUTPUT pixel on RESIZED_HEAD
 
 
 LABEL_HEADS = ("auto", "fused", "canvas")
@@ -350,8 +394,12 @@ AREA_TOPK = ("top-k together with area_thd is not built: the k best classes woul
 
 
 class SegPipeline:
+    # Every constructor option has its default here too, so an instance built without the constructor (the CPU tests' stubs) reads them.
     pamr_steps, pamr_stride = 0, (8, 16)      # PAMR off unless the constructor says otherwise
     area_thd = None                           # area_thd off likewise
+    label_head, prob_head, resize_head = "auto", "auto", "canvas"
+    apply_ctd, apply_layer_fusion, layer_fusion_lambda = False, False, 0.5
+    cross_tile_fusion = tile_group = upsampler = None
 
     def __init__(self, net: HipCLIP, text: torch.Tensor, query_idx: torch.Tensor, model_type: str = "SegEarth",
                  ignore_residual: bool = True, cls_token_lambda: float = 0.0, global_debias_factor: float = 0.0,
@@ -375,8 +423,7 @@ class SegPipeline:
         self.pamr_stride = ops.pamr_dilations(pamr_stride)[0]
         if not 0 <= self.pamr_steps <= ops.PAMR_MAX_STEPS:
             raise ValueError(f"pamr_steps must lie in [0, {ops.PAMR_MAX_STEPS}], got {pamr_steps!r}")
-        if self.pamr_steps > 0 and tile_group is not None:
-            raise ValueError(PAMR_TILE_GROUP)
+        self._check_sharding(tile_group is not None)            # PAMR is refused before anything of the net is touched; area_thd below
         # the tail that returns class probabilities too (``probs_from_tiles``): "canvas" = stitch + postprocess, "fused" = sg_prob_head
         # (no canvas, any Q, the same bytes), "auto" = see ``fused_prob_head``
         self.prob_head = prob_head
@@ -409,33 +456,79 @@ class SegPipeline:
         # area_thd (the upstream option name; None = off, and then no call changes route, launches or bytes): per image, a class whose
         # arg-max area is at most area_thd times the non-background area is removed and its pixels go to the best remaining class (the
         # definition: include/segearth_hip.h).  Every tail that returns labels or probabilities then decides twice: the first pass is
-        # today's kernel with prob_thd = 0 (its labels are the plain arg-max), then sg_class_area -> sg_area_keep on the device, then
-        #   probabilities exist (or the canvas route runs): sg_area_filter_probs -- dropped planes zeroed, labels from the kept planes.
-        #     Labels alone on the canvas route (label_head="canvas", PAMR, a resized canvas, whole-image inference, and
-        #     resize_head="fused", which takes the canvas route while area_thd is set) write the probabilities into a scratch [K,H,W]
-        #     for this and return only labels; the fused label head is the memory-lean way;
-        #   labels alone on the fused label head: sg_label_head with conf, then sg_area_relabel -- no canvas, no probability planes,
-        #     12 bytes per pixel instead of 8.
+        # the route's own kernel with prob_thd = 0 (its labels are the plain arg-max), then sg_class_area -> sg_area_keep on the device,
+        # then sg_area_filter_probs on the probabilities (a scratch [K,H,W] where only labels are wanted) or, on the fused label head,
+        # sg_area_relabel: no canvas, no probability planes, 12 bytes per pixel instead of 8 (DESIGN.md section 5 'Route table').
         self.area_thd = None if area_thd is None else float(area_thd)
         if self.area_thd is not None:
             ops.area_args("area_thd", self.num_classes, self.bg_idx, self.area_thd)
-            if tile_group is not None:
-                raise ValueError(AREA_TILE_GROUP)
+        self._check_sharding(tile_group is not None)
 
     def _stitch(self, tile_logits, windows, up_hw, pad_tl, canvas_hw):
         return ops.stitch(tile_logits, windows, up_hw, pad_tl, canvas_hw)
 
+    # -- which tail runs: one decision (DESIGN.md section 5 'Route table') ----------------------------------------------
     def fused_label_head(self) -> bool:
-        """Whether the labels-only tail runs the fused head (sg_label_head) instead of the canvas path."""
-        if getattr(self, "pamr_steps", 0) > 0:                 # PAMR refines the canvas: there has to be one
-            return False
-        mode = getattr(self, "label_head", "auto")
-        return mode == "fused" or (mode == "auto" and self.num_queries > ops.POSTPROCESS_MAX_Q)
+        """Whether the labels-only tail runs the fused head (sg_label_head) instead of the canvas path: "auto" = the canvas wherever it
+        works (Q <= 64) and the fused head beyond.  PAMR refines the canvas, so there has to be one."""
+        return self.pamr_steps == 0 and (self.label_head == "fused" or (
+            self.label_head == "auto" and self.num_queries > ops.POSTPROCESS_MAX_Q))
+
+    def fused_prob_head(self) -> bool:
+        """Whether the tail that returns probabilities and labels runs the fused head (sg_prob_head) instead of the canvas path.  "auto"
+        is the canvas up to 64 queries and follows the measurement beyond (PROB_HEAD_AUTO_FUSED_BEYOND_MAX_Q)."""
+        return self.pamr_steps == 0 and (self.prob_head == "fused" or (
+            self.prob_head == "auto" and PROB_HEAD_AUTO_FUSED_BEYOND_MAX_Q and self.num_queries > ops.POSTPROCESS_MAX_Q))
 
     def fused_resize_head(self) -> bool:
         """Whether labels / top-k at another ``ori_shape`` run the resized heads (no canvas) instead of stitch + resize + post-process."""
-        return getattr(self, "resize_head", "canvas") == "fused" and getattr(self, "pamr_steps", 0) == 0 and self.area_thd is None
+        return self.resize_head == "fused" and self.pamr_steps == 0 and self.area_thd is None
 
+    def topk_k(self, topk) -> int:
+        """``topk`` checked against what sg_topk_head takes: 1 .. min(ops.TOPK_MAX, the number of classes)."""
+        if self.area_thd is not None:
+            raise ValueError(AREA_TOPK)
+        k = int(topk)
+        if not 1 <= k <= min(ops.TOPK_MAX, self.num_classes):
+            raise ValueError(f"topk must lie in [1, min({ops.TOPK_MAX}, {self.num_classes} classes)], got {topk!r}")
+        return k
+
+    def _wanted(self, where: str, want_probs: bool, topk: int, sharded: bool) -> Tuple[str, int]:
+        """What a tail is asked for: ("labels" | "probs" | "topk", k)."""
+        if not topk:
+            return ("probs" if want_probs else "labels"), 0
+        if want_probs:
+            raise ValueError(f"{where}: topk and want_probs exclude each other (topk returns the k best class probabilities)")
+        if sharded:
+            raise ValueError(TOPK_TILE_GROUP)
+        return "topk", self.topk_k(topk)
+
+    def _check_sharding(self, sharded: bool) -> None:
+        if sharded and self.pamr_steps > 0:
+            raise ValueError(PAMR_TILE_GROUP)
+        if sharded and self.area_thd is not None:
+            raise ValueError(AREA_TILE_GROUP)
+
+    def _canvas_bytes(self) -> int:
+        """Per pixel of a canvas route: the [Q,H,W] canvas, and with area_thd the probability planes and labels, which then always exist."""
+        return 4 * self.num_queries + (0 if self.area_thd is None else 4 * self.num_classes + 8)
+
+    def tail_route(self, want: str, k: int = 0, given: bool = False, differs: bool = False) -> TailRoute:
+        """THE route decision.  ``want``: "labels", "probs" or "topk" (then ``k``); ``differs``: some ``ori_shape`` is another size than
+        its image; ``given``: some ``ori_shape`` is given at all -- the packed labels-only tail takes the fused head only when none is,
+        an ``ori_shape`` equal to the image's size keeps the canvas there."""
+        if self.pamr_steps == 0:
+            if want == "topk" and not differs:
+                return TailRoute(HEAD, 8 * k)
+            if want == "probs" and not differs and self.fused_prob_head():
+                return TailRoute(HEAD, 4 * self.num_classes + 8)
+            if want == "labels" and not given and not differs and self.fused_label_head():
+                return TailRoute(HEAD, 8 if self.area_thd is None else 12)
+            if want != "probs" and differs and self.fused_resize_head():
+                return TailRoute(RESIZED_HEAD, 8 * k if want == "topk" else 8)
+        return TailRoute(CANVAS_MULTI if self.num_queries <= ops.POSTPROCESS_MAX_Q else CANVAS_EACH, self._canvas_bytes())
+
+    # -- the tails ------------------------------------------------------------------------------------------------------
     def refine(self, canvas: torch.Tensor, guide: torch.Tensor) -> torch.Tensor:
         """PAMR on one image's logits [Q,H,W], in place where they are a contiguous f32 tensor.  ``guide``: the image (u8 [H,W,3] or
         normalised f32 [3,H,W]); at another size than the logits (an ``ori_shape`` resize) its planes are resized by the same
@@ -448,41 +541,75 @@ class SegPipeline:
         inplace = canvas.dtype == torch.float32 and canvas.is_contiguous()
         return ops.pamr(canvas, g, self.pamr_steps, self.pamr_stride, inplace=inplace)
 
-    def _canvas_tail(self, tile_logits, windows, up_hw, pad_tl, canvas_hw, guide, want_probs: bool):
-        """stitch -> PAMR (when on; ``guide`` = the image of this canvas) -> post-process."""
-        canvas = self._stitch(tile_logits, windows, up_hw, pad_tl, canvas_hw)
-        if self.pamr_steps > 0:
-            if guide is None:
-                raise ValueError("PAMR needs the image of the canvas as guidance: pass guide= (a canvas band has none: " + PAMR_TILE_GROUP + ")")
-            canvas = self.refine(canvas, guide)
-        return self.postprocess(canvas, want_probs=want_probs)
-
-    def labels_from_tiles(self, tile_logits, windows, up_hw, pad_tl, canvas_hw, guide=None):
-        """Tile logits [T,Q,gh,gw] + windows [T,4] -> labels int64 [1,H,W]: the labels-only tail of every path that returns no
-        canvas and no probabilities.  A canvas band is a canvas with shifted windows.  With PAMR on this is the canvas route, refined
-        under ``guide`` (the scene)."""
-        if self.fused_label_head():
-            if self.area_thd is not None:
-                labels, conf = ops.label_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, self.query_idx, self.num_classes,
-                                              self.logit_scale, 0.0, self.bg_idx, want_conf=True)
-                keep = ops.area_keep(ops.class_area(labels, self.num_classes), self.bg_idx, self.area_thd)
-                return ops.area_relabel(tile_logits, windows, up_hw, pad_tl, canvas_hw, self.query_idx, self.num_classes, self.logit_scale,
-                                        self.prob_thd, self.bg_idx, keep, conf, labels)
-            return ops.label_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, self.query_idx, self.num_classes, self.logit_scale,
-                                  self.prob_thd, self.bg_idx)
-        return self._canvas_tail(tile_logits, windows, up_hw, pad_tl, canvas_hw, guide, False)[1]
+    def _area_keep(self, labels, image_pixels=None):
+        """area_thd, between the passes: the class areas of the first pass's labels (one image, or the flat labels of a flush group with
+        ``image_pixels``) -> keep; two launches, nothing comes to the host."""
+        counts = ops.class_area(labels, self.num_classes) if image_pixels is None else ops.class_area_multi(labels, image_pixels, self.num_classes)
+        return ops.area_keep(counts, self.bg_idx, self.area_thd)
 
     def area_filter_first_pass(self, probs, labels):
         """The second decision of area_thd for one image whose first pass (``prob_thd = 0``) left probs f32 [K,H,W] and labels int64
-        [1,H,W]: count, keep, filter -- both tensors IN PLACE, three launches, nothing comes to the host."""
-        keep = ops.area_keep(ops.class_area(labels, self.num_classes), self.bg_idx, self.area_thd)
-        ops.area_filter_probs(probs, labels, keep, self.prob_thd, self.bg_idx)
+        [1,H,W]: count, keep, filter -- both tensors IN PLACE."""
+        ops.area_filter_probs(probs, labels, self._area_keep(labels), self.prob_thd, self.bg_idx)
         return probs, labels
 
     def area_filter_first_pass_multi(self, probs, flat, out_hw):
         """``area_filter_first_pass`` for a flush group: the flat outputs of sg_postprocess_multi / sg_prob_head_multi, one launch each."""
-        keep = ops.area_keep(ops.class_area_multi(flat, [h * w for h, w in out_hw], self.num_classes), self.bg_idx, self.area_thd)
+        keep = self._area_keep(flat, [h * w for h, w in out_hw])
         ops.area_filter_probs_multi(probs, flat, keep, out_hw, self.prob_thd, self.bg_idx)
+
+    def _image_tail(self, route: str, want: str, k: int, tile_logits, windows, up_hw, pad_tl, canvas_hw, out_hw, guide):
+        """One image's (or one canvas band's) tile logits [T,Q,gh,gw] + windows [T,4] -> labels int64 [1,H,W], (probs f32 [K,H,W],
+        labels) or (classes int32 [k,H,W], probs f32 [k,H,W]) on ``route``, (H, W) = ``out_hw``."""
+        args = (tile_logits, windows, up_hw, pad_tl, canvas_hw)
+        if route == RESIZED_HEAD:
+            post = (out_hw, self.query_idx, self.num_classes, self.logit_scale)
+            return ops.topk_head_resized(*args, *post, k) if want == "topk" else ops.label_head_resized(*args, *post, self.prob_thd, self.bg_idx)
+        if route == HEAD:
+            post = (self.query_idx, self.num_classes, self.logit_scale)
+            if want == "topk":
+                return ops.topk_head(*args, *post, k)
+            area = self.area_thd is not None
+            thd = 0.0 if area else self.prob_thd                  # area_thd: the first pass is the plain arg-max
+            if want == "probs":
+                probs, labels = ops.prob_head(*args, *post, thd, self.bg_idx)
+                return self.area_filter_first_pass(probs, labels) if area else (probs, labels)
+            if not area:
+                return ops.label_head(*args, *post, thd, self.bg_idx)
+            labels, conf = ops.label_head(*args, *post, thd, self.bg_idx, want_conf=True)
+            return ops.area_relabel(*args, *post, self.prob_thd, self.bg_idx, self._area_keep(labels), conf, labels)
+        canvas = self._stitch(*args)                              # stitch -> resize -> PAMR -> post-process
+        if tuple(out_hw) != tuple(canvas_hw):
+            canvas = ops.resize_bilinear(canvas, out_hw)
+        if self.pamr_steps > 0:
+            if guide is None:
+                raise ValueError("PAMR needs the image of the canvas as guidance: pass guide= (a canvas band has none: " + PAMR_TILE_GROUP + ")")
+            canvas = self.refine(canvas, guide)
+        probs, labels = self.postprocess(canvas, want_probs=want != "labels")
+        if want == "topk":
+            return ops.topk_from_probs(probs, self.query_idx, k)
+        return (probs, labels) if want == "probs" else labels
+
+    def labels_from_tiles(self, tile_logits, windows, up_hw, pad_tl, canvas_hw, guide=None):
+        """The labels-only tail of one image or canvas band (a canvas with shifted windows) -> labels int64 [1,H,W]."""
+        return self._image_tail(self.tail_route("labels").route, "labels", 0, tile_logits, windows, up_hw, pad_tl, canvas_hw, canvas_hw, guide)
+
+    def probs_from_tiles(self, tile_logits, windows, up_hw, pad_tl, canvas_hw, guide=None):
+        """-> (probs f32 [K,H,W], labels int64 [1,H,W]) at the scene's own size; every route returns the same bytes."""
+        return self._image_tail(self.tail_route("probs").route, "probs", 0, tile_logits, windows, up_hw, pad_tl, canvas_hw, canvas_hw, guide)
+
+    def topk_from_tiles(self, tile_logits, windows, up_hw, pad_tl, canvas_hw, k: int, guide=None):
+        """-> (classes int32 [k,H,W], probs f32 [k,H,W]): the k best classes of every pixel in descending probability."""
+        k = self.topk_k(k)
+        return self._image_tail(self.tail_route("topk", k).route, "topk", k, tile_logits, windows, up_hw, pad_tl, canvas_hw, canvas_hw, guide)
+
+    def topk_from_logits(self, seg_logits, k: int, guide=None):
+        """The canvas route to the k best classes, for logits [Q,H,W] that already exist (whole-image inference): PAMR when on,
+        post-process, ``ops.topk_from_probs``."""
+        k = self.topk_k(k)
+        if self.pamr_steps > 0:
+            seg_logits = self.refine(seg_logits.float().contiguous(), guide)
+        return ops.topk_from_probs(self.postprocess(seg_logits, want_probs=True)[0], self.query_idx, k)
 
     def _postprocess_multi(self, canvases, chw, ohw, want_probs):
         """ops.postprocess_multi for a flush group -> (probs or Nones, labels, flat labels); with area_thd the first pass writes the
@@ -495,57 +622,65 @@ class SegPipeline:
         self.area_filter_first_pass_multi(probs, flat, ohw)
         return (prb if want_probs else [None] * len(lab)), lab, flat
 
-    def fused_prob_head(self) -> bool:
-        """Whether the tail that returns probabilities and labels runs the fused head (sg_prob_head) instead of the canvas path.  "auto"
-        is the canvas up to 64 queries and follows the measurement beyond (PROB_HEAD_AUTO_FUSED_BEYOND_MAX_Q)."""
-        if getattr(self, "pamr_steps", 0) > 0:
-            return False
-        mode = getattr(self, "prob_head", "auto")
-        return mode == "fused" or (mode == "auto" and PROB_HEAD_AUTO_FUSED_BEYOND_MAX_Q and self.num_queries > ops.POSTPROCESS_MAX_Q)
+    def _postprocess_each(self, views, ohw, imgs, want_probs):
+        """The canvases of a flush group image by image -- resize, PAMR when on, ``postprocess`` -> (probs or Nones, labels, flat labels):
+        the label maps are copied into one flat buffer and returned as views of it."""
+        prb, lab = [], []
+        for c, hw, im in zip(views, ohw, imgs):
+            if hw != tuple(c.shape[1:]):
+                c = ops.resize_bilinear(c, hw)
+            if self.pamr_steps > 0:
+                c = self.refine(c, im.to(self.device))
+            p_, l_ = self.postprocess(c, want_probs=want_probs)
+            prb.append(p_); lab.append(l_.reshape(-1))
+        flat = torch.cat(lab)
+        return prb, ops.flat_views(flat, 1, ohw), flat
 
-    def probs_from_tiles(self, tile_logits, windows, up_hw, pad_tl, canvas_hw, guide=None):
-        """Tile logits [T,Q,gh,gw] + windows [T,4] -> (probs f32 [K,H,W], labels int64 [1,H,W]): the tail of every path that returns
-        class probabilities at the scene's own size.  Both routes return the same bytes.  With PAMR on this is the canvas route, refined
-        under ``guide`` (the scene)."""
-        if self.fused_prob_head():
-            if self.area_thd is not None:
-                return self.area_filter_first_pass(*ops.prob_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, self.query_idx,
-                                                                  self.num_classes, self.logit_scale, 0.0, self.bg_idx))
-            return ops.prob_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, self.query_idx, self.num_classes, self.logit_scale,
-                                 self.prob_thd, self.bg_idx)
-        return self._canvas_tail(tile_logits, windows, up_hw, pad_tl, canvas_hw, guide, True)
-
-    def topk_k(self, topk) -> int:
-        """``topk`` checked against what sg_topk_head takes: 1 .. min(ops.TOPK_MAX, the number of classes)."""
-        if self.area_thd is not None:
-            raise ValueError(AREA_TOPK)
-        k = int(topk)
-        if not 1 <= k <= min(ops.TOPK_MAX, self.num_classes):
-            raise ValueError(f"topk must lie in [1, min({ops.TOPK_MAX}, {self.num_classes} classes)], got {topk!r}")
-        return k
-
-    def topk_from_tiles(self, tile_logits, windows, up_hw, pad_tl, canvas_hw, k: int, guide=None):
-        """Tile logits [T,Q,gh,gw] + windows [T,4] -> (classes int32 [k,H,W], probs f32 [k,H,W]): the k best classes of every pixel in
-        descending probability (sg_topk_head: no canvas, no [K,H,W] planes, any Q).  With PAMR on there has to be a canvas: stitch,
-        refine under ``guide`` (the scene), post-process, ``ops.topk_from_probs``."""
-        k = self.topk_k(k)
-        if getattr(self, "pamr_steps", 0) > 0:
-            probs, _ = self._canvas_tail(tile_logits, windows, up_hw, pad_tl, canvas_hw, guide, True)
-            return ops.topk_from_probs(probs, self.query_idx, k)
-        return ops.topk_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, self.query_idx, self.num_classes, self.logit_scale, k)
-
-    def topk_from_logits(self, seg_logits, k: int, guide=None):
-        """The canvas route to the k best classes, for logits [Q,H,W] that already exist (a resize to another ``ori_shape``, whole-image
-        inference): PAMR when on, post-process, ``ops.topk_from_probs``."""
-        k = self.topk_k(k)
-        if getattr(self, "pamr_steps", 0) > 0:
-            seg_logits = self.refine(seg_logits.float().contiguous(), guide)
-        return ops.topk_from_probs(self.postprocess(seg_logits, want_probs=True)[0], self.query_idx, k)
+    def _group_tail(self, route: str, want: str, k: int, group, ohw, imgs):
+        """One flush group of ``_packed_tiles`` on ``route`` -> (list of probs or Nones, list of labels, flat labels), or for top-k
+        (list of probs [k,H,W], list of classes [k,H,W], None).  ``ohw``: the output size per image; ``imgs``: the images (PAMR's guides)."""
+        idx, shapes = group[0], group[6]
+        args, post = group[1:], (self.query_idx, self.num_classes, self.logit_scale)
+        if route == RESIZED_HEAD and ohw == shapes:               # no image of this group differs: what runs without the option
+            route = self.tail_route(want, k).route
+        if route == RESIZED_HEAD:
+            if want == "topk":
+                cls, prb = ops.topk_head_resized_multi(*args, ohw, *post, k)
+                return prb, cls, None
+            lab, flat = ops.label_head_resized_multi(*args, ohw, *post, self.prob_thd, self.bg_idx)
+            return [None] * len(idx), lab, flat
+        if route == HEAD:
+            if want == "topk":
+                cls, prb = ops.topk_head_multi(*args, *post, k)
+                return prb, cls, None
+            area = self.area_thd is not None
+            thd = 0.0 if area else self.prob_thd                  # area_thd: the first pass is the plain arg-max
+            if want == "probs":
+                prb, lab, flat, *probs = ops.prob_head_multi(*args, *post, thd, self.bg_idx, flat_probs=area)
+                if area:
+                    self.area_filter_first_pass_multi(probs[0], flat, shapes)
+                return prb, lab, flat
+            lab, flat, *conf = ops.label_head_multi(*args, *post, thd, self.bg_idx, want_conf=area, flat_conf=area)
+            if area:                                              # 12 bytes per pixel: labels and conf, no canvas, no probability planes
+                ops.area_relabel_multi(*args, *post, self.prob_thd, self.bg_idx, self._area_keep(flat, [h * w for h, w in shapes]), conf[0], flat)
+            return [None] * len(idx), lab, flat
+        canvases, views = ops.stitch_multi(*args)
+        if route == CANVAS_MULTI and (self.pamr_steps == 0 or ohw == shapes):
+            if self.pamr_steps > 0:                               # PAMR comes after the resize: a group that holds one goes image by image
+                for c, im in zip(views, imgs):
+                    self.refine(c, im.to(self.device))
+            prb, lab, flat = self._postprocess_multi(canvases, shapes, ohw, want != "labels")
+        else:
+            prb, lab, flat = self._postprocess_each(views, ohw, imgs, want != "labels")
+        if want == "topk":
+            pairs = [ops.topk_from_probs(p, self.query_idx, k) for p in prb]
+            return [p for _, p in pairs], [c for c, _ in pairs], None
+        return prb, lab, flat
 
     def _pre_head(self, tok, cls):
         """Global debias (+ CTD) when they cannot stay fused in the logits kernel: returns (tokens, remaining debias factor)."""
         f = self.global_debias_factor if cls is not None else 0.0
-        if not getattr(self, "apply_ctd", False) or cls is None:
+        if not self.apply_ctd or cls is None:
             return tok, f
         if f != 0:                                            # reference order: global debias, then cluster on the debiased features
             tok = ops.global_debias(tok, cls, f)
@@ -553,68 +688,71 @@ class SegPipeline:
         return tok, 0.0
 
     # -- per-tile logits -----------------------------------------------------------------------------------
+    def _tile_geometry(self, tile_hw) -> TileGeometry:
+        return tile_geometry(tile_hw, self.visual.cfg.patch)
+
+    def _forward_opts(self):
+        return self.visual.forward_opts(self.model_type, self.ignore_residual, self.apply_similarity_enhancement, self.apply_layer_fusion,
+                                        self.layer_fusion_lambda)
+
+    def _fusion_args(self) -> Tuple[int, str, float]:
+        """(boundary width, mode, strength) of cross-tile fusion: the constructor kwargs of the reference's CrossTileFusion."""
+        cf = self.cross_tile_fusion
+        return cf.get("cache_boundary_width", 2), cf.get("fusion_mode", "weighted"), cf.get("fusion_strength", 0.3)
+
+    def _tower(self, scene, win, tile_hw, chunks, scene_index=None):
+        """The tower over the launch ``chunks`` [a, z) of the windows ``win`` -> (cls or None, tok) of all of them, concatenated."""
+        opts = self._forward_opts()
+        cls_all, tok_all = [], []
+        for a, z in chunks:
+            c_, t_ = self.visual.forward_tiles(scene, win[a:z], tile_hw, opts, None if scene_index is None else scene_index[a:z])
+            cls_all.append(c_); tok_all.append(t_)
+        return (None if cls_all[0] is None else torch.cat(cls_all, 0)), torch.cat(tok_all, 0)
+
+    def _head_logits(self, tok, cls, scene, win, tile_hw, scene_index=None):
+        """Tokens -> logits [T,Q,gh,gw] (per-pixel [T,Q,H',W'] with an upsampler): global debias and CTD, then the upsampler's logits tail
+        (segmentor.py:368-372: tokens -> fusion -> JBU -> logits) or the cosine logits on the patch grid."""
+        geo = self._tile_geometry(tile_hw)
+        tok, f = self._pre_head(tok, cls)
+        if self.upsampler is not None:
+            return self.upsampler.logits(tok, cls, scene, win, tile_hw, (geo.pad[0], geo.pad[2]), geo.grid, self.text, f, self.cls_token_lambda,
+                                         scene_index, padded_hw=geo.up_hw)
+        lg = ops.cosine_logits(tok, cls, self.text, f, self.cls_token_lambda if cls is not None else 0.0)
+        return lg.reshape(win.shape[0], self.num_queries, *geo.grid)
+
+    def _logits_by_chunk(self, scene, win, tile_hw, chunks, scene_index=None):
+        """Tower and head launch chunk by launch chunk: the tiles are independent (no cross-tile fusion)."""
+        opts = self._forward_opts()
+        outs = []
+        for a, z in chunks:
+            si = None if scene_index is None else scene_index[a:z]
+            cls, tok = self.visual.forward_tiles(scene, win[a:z], tile_hw, opts, si)
+            outs.append(self._head_logits(tok, cls, scene, win[a:z], tile_hw, si))
+        return torch.cat(outs, 0) if len(outs) > 1 else outs[0]
+
     def tile_logits(self, scene: torch.Tensor, windows: Sequence[Tuple[int, int, int, int]], tile_hw: Tuple[int, int],
                     scene_index: Optional[torch.Tensor] = None, grid_of_tiles: Optional[Tuple[int, int]] = None) -> torch.Tensor:
         """-> [T, Q, gh, gw] patch-grid logits (or [T, Q, H', W'] per-pixel logits with the JBU upsampler)."""
-        v = self.visual
-        P = v.cfg.patch
-        th, tw = tile_hw
-        l, r, t, b = compute_padsize(th, tw, P)
-        gh, gw = (th + t + b) // P, (tw + l + r) // P
-        opts = v.forward_opts(self.model_type, self.ignore_residual, self.apply_similarity_enhancement,
-                              getattr(self, "apply_layer_fusion", False), getattr(self, "layer_fusion_lambda", 0.5))
         win = torch.tensor(list(windows), dtype=torch.int32, device=self.device).reshape(-1, 4)
-        outs = []
-        fuse = self.cross_tile_fusion is not None and grid_of_tiles is not None and grid_of_tiles[0] * grid_of_tiles[1] > 1
-        if fuse:
-            # boundary fusion couples neighbouring tiles: run the tower over the whole scene first, fuse, then the head
-            cls_all, tok_all = [], []
-            for i, j in launch_chunks(win.shape[0], self.tiles_per_launch):
-                si = None if scene_index is None else scene_index[i:j]
-                c_, t_ = v.forward_tiles(scene, win[i:j], tile_hw, opts, si)
-                cls_all.append(c_); tok_all.append(t_)
-            tok = ops.cross_tile_fusion(torch.cat(tok_all, 0), grid_of_tiles[0], grid_of_tiles[1], gh, gw,
-                                        self.cross_tile_fusion.get("cache_boundary_width", 2),
-                                        self.cross_tile_fusion.get("fusion_mode", "weighted"),
-                                        self.cross_tile_fusion.get("fusion_strength", 0.3))
-            cls = None if cls_all[0] is None else torch.cat(cls_all, 0)
-            tok, f = self._pre_head(tok, cls)
-            if self.upsampler is not None:
-                # segmentor.py:368-372 after cross_tile_fusion.py:238-320: the FUSED tokens go through the upsampler (tokens -> fusion -> JBU -> logits)
-                return self.upsampler.logits(tok, cls, scene, win, tile_hw, (l, t), (gh, gw), self.text, f, self.cls_token_lambda, scene_index,
-                                             padded_hw=(th + t + b, tw + l + r))
-            lg = ops.cosine_logits(tok, cls, self.text, f, self.cls_token_lambda if cls is not None else 0.0)
-            return lg.reshape(win.shape[0], self.num_queries, gh, gw)
-        for i, j in launch_chunks(win.shape[0], self.tiles_per_launch):
-            w = win[i:j]
-            si = None if scene_index is None else scene_index[i:j]
-            cls, tok = v.forward_tiles(scene, w, tile_hw, opts, si)
-            tok, f = self._pre_head(tok, cls)
-            if self.upsampler is not None:
-                outs.append(self.upsampler.logits(tok, cls, scene, w, tile_hw, (l, t), (gh, gw), self.text,
-                                                  f, self.cls_token_lambda, si,
-                                                  padded_hw=(th + t + b, tw + l + r)))
-            else:
-                lg = ops.cosine_logits(tok, cls, self.text, f, self.cls_token_lambda if cls is not None else 0.0)
-                outs.append(lg.reshape(w.shape[0], self.num_queries, gh, gw))
-        return torch.cat(outs, 0) if len(outs) > 1 else outs[0]
+        chunks = launch_chunks(win.shape[0], self.tiles_per_launch)
+        if self.cross_tile_fusion is None or grid_of_tiles is None or grid_of_tiles[0] * grid_of_tiles[1] <= 1:
+            return self._logits_by_chunk(scene, win, tile_hw, chunks, scene_index)
+        # boundary fusion couples neighbouring tiles: run the tower over the whole scene first, fuse, then the head
+        cls, tok = self._tower(scene, win, tile_hw, chunks, scene_index)
+        tok = ops.cross_tile_fusion(tok, grid_of_tiles[0], grid_of_tiles[1], *self._tile_geometry(tile_hw).grid, *self._fusion_args())
+        return self._head_logits(tok, cls, scene, win, tile_hw, scene_index)
 
     # -- reference forward_slide -----------------------------------------------------------------------------
     def _geometry(self, scene, stride, crop):
-        if scene.dtype == torch.uint8:
-            H, W = int(scene.shape[0]), int(scene.shape[1])
-        else:
-            H, W = int(scene.shape[-2]), int(scene.shape[-1])
+        H, W = _scene_hw(scene)
         stride = (stride, stride) if isinstance(stride, int) else tuple(stride)
         crop = (crop, crop) if isinstance(crop, int) else tuple(crop)
         wins = tile_windows(H, W, stride, crop)
         tile_hw = (wins[0][1] - wins[0][0], wins[0][3] - wins[0][2])
-        P = self.visual.cfg.patch
-        l, r, t, b = compute_padsize(tile_hw[0], tile_hw[1], P)
-        up_hw = (tile_hw[0] + t + b, tile_hw[1] + l + r)
+        geo = self._tile_geometry(tile_hw)
         hg = max(H - crop[0] + stride[0] - 1, 0) // stride[0] + 1
         wg = max(W - crop[1] + stride[1] - 1, 0) // stride[1] + 1
-        return H, W, stride, crop, wins, tile_hw, (t, l), up_hw, (hg, wg)
+        return H, W, stride, crop, wins, tile_hw, geo.pad_tl, geo.up_hw, (hg, wg)
 
     def forward_slide(self, scene: torch.Tensor, stride, crop, ori_shape=None, group=None) -> torch.Tensor:
         """scene: f32 [3,H,W] normalised planes or u8 [H,W,3].  Returns logits [1,Q,H_ori,W_ori] (on every rank of the tile
@@ -690,53 +828,22 @@ class SegPipeline:
 
     def segment_scene(self, scene: torch.Tensor, stride, crop, group=None, gather_labels: bool = True, want_probs: bool = False,
                       topk: int = 0, ori_shape=None):
-        """The whole path to labels for one scene.  Sharded: every rank computes its tiles, stitches + labels ITS band; only the
-        int64 label band (8 B per pixel instead of 4Q) is gathered.  -> labels [1,H,W] (or (band labels, first row) when
-        ``gather_labels`` is False).  ``want_probs``: (probs [K,H,W], labels [1,H,W]) through ``probs_from_tiles``; not with tile
-        sharding.  With PAMR on (``pamr_steps``) the canvas is stitched, refined under the scene and post-processed, whatever
-        label_head / prob_head say; tile sharding is then refused (a band would need a halo of its neighbours' rows).
-        ``topk`` > 0: (classes int32 [topk,H,W], probs f32 [topk,H,W]) through ``topk_from_tiles`` instead of labels; not together with
-        ``want_probs`` and not with tile sharding.
-        ``ori_shape`` of another size than the scene: labels (or the ``topk`` planes) at that size; not with ``want_probs`` (use
-        ``segment_scenes``) and not with tile sharding.  ``resize_head="fused"`` without PAMR: sg_label_head_resized /
-        sg_topk_head_resized on the tile logits, no canvas; otherwise stitch, resize, PAMR when on, post-process.
-        With ``area_thd`` set every route above decides twice (the constructor's comment): the fused label head through
-        sg_area_relabel, everything else through the probabilities and sg_area_filter_probs -- labels alone on the canvas route then
-        pay a scratch [K,H,W], and ``resize_head="fused"`` takes the canvas route.  ``topk`` and tile sharding are refused."""
-        if self.area_thd is not None and group is not None:
-            raise ValueError(AREA_TILE_GROUP)
+        """The whole path for one scene -> labels int64 [1,H,W]; with ``want_probs`` (probs f32 [K,H,W], labels); with ``topk`` > 0
+        (classes int32 [topk,H,W], probs f32 [topk,H,W]) instead.  ``ori_shape`` of another size than the scene: labels or the top-k
+        planes at that size.  Which kernels run is ``tail_route`` for this one image (DESIGN.md section 5 'Route table').
+        Sharded (``group``, or ``tile_group``): every rank computes its tiles, stitches + labels ITS band, and only the int64 label band
+        (8 B per pixel instead of 4Q) is gathered; (band labels, first row) when ``gather_labels`` is False.  Labels only: sharding
+        refuses probabilities, top-k, another ``ori_shape``, PAMR and area_thd; probabilities at another ``ori_shape`` and top-k
+        together with ``want_probs`` or area_thd are refused everywhere."""
+        sharded = group is not None or self.tile_group is not None
+        self._check_sharding(sharded)
+        want, k = self._wanted("segment_scene", want_probs, topk, sharded)
         resize = ori_shape is not None and tuple(ori_shape) != _scene_hw(scene)
-        if topk:
-            if want_probs:
-                raise ValueError("segment_scene: topk and want_probs exclude each other (topk returns the k best class probabilities)")
-            if group is not None or self.tile_group is not None:
-                raise ValueError(TOPK_TILE_GROUP)
-            k = self.topk_k(topk)
-        if resize:
-            if want_probs:
-                raise ValueError("segment_scene: class probabilities at another ori_shape are not built here; use segment_scenes")
-            if group is not None or self.tile_group is not None:
-                raise ValueError("segment_scene: another ori_shape under tile_group sharding is not built (a canvas band does not map to "
-                                 "whole output rows); use forward_slide + postprocess")
-        if topk or resize:
-            H, W, stride, crop, wins, tile_hw, pad_tl, up_hw, grid = self._geometry(scene, stride, crop)
-            tl = self.tile_logits(scene, wins, tile_hw, grid_of_tiles=grid)
-            win_dev = torch.tensor(wins, dtype=torch.int32, device=self.device)
-            if not resize:
-                return self.topk_from_tiles(tl, win_dev, up_hw, pad_tl, (H, W), k, guide=scene)
-            out = tuple(int(v) for v in ori_shape)
-            if self.fused_resize_head():
-                if topk:
-                    return ops.topk_head_resized(tl, win_dev, up_hw, pad_tl, (H, W), out, self.query_idx, self.num_classes,
-                                                 self.logit_scale, k)
-                return ops.label_head_resized(tl, win_dev, up_hw, pad_tl, (H, W), out, self.query_idx, self.num_classes, self.logit_scale,
-                                              self.prob_thd, self.bg_idx)
-            canvas = ops.resize_bilinear(self._stitch(tl, win_dev, up_hw, pad_tl, (H, W)), out)
-            if topk:
-                return self.topk_from_logits(canvas, k, guide=scene)
-            return self.postprocess(self.refine(canvas, scene), want_probs=False)[1]
-        if self.pamr_steps > 0 and (group is not None or self.tile_group is not None):
-            raise ValueError(PAMR_TILE_GROUP)
+        if resize and want_probs:
+            raise ValueError("segment_scene: class probabilities at another ori_shape are not built here; use segment_scenes")
+        if resize and sharded:
+            raise ValueError("segment_scene: another ori_shape under tile_group sharding is not built (a canvas band does not map to "
+                             "whole output rows); use forward_slide + postprocess")
         group = resolve_tile_group(group if group is not None else self.tile_group)
         if want_probs and group is not None:
             raise ValueError("segment_scene: class probabilities under tile_group sharding are not built; use forward_slide + postprocess")
@@ -744,9 +851,8 @@ class SegPipeline:
             H, W, stride, crop, wins, tile_hw, pad_tl, up_hw, grid = self._geometry(scene, stride, crop)
             tl = self.tile_logits(scene, wins, tile_hw, grid_of_tiles=grid)
             win_dev = torch.tensor(wins, dtype=torch.int32, device=self.device)
-            if want_probs:
-                return self.probs_from_tiles(tl, win_dev, up_hw, pad_tl, (H, W), guide=scene)
-            return self.labels_from_tiles(tl, win_dev, up_hw, pad_tl, (H, W), guide=scene)
+            out_hw = tuple(int(v) for v in ori_shape) if resize else (H, W)
+            return self._image_tail(self.tail_route(want, k, differs=resize).route, want, k, tl, win_dev, up_hw, pad_tl, (H, W), out_hw, scene)
         tiles, w_band, up_hw, pad_tl, hw, y0, yb = self.sharded_band_tiles(scene, stride, crop, group)
         if hw[0] > 0:
             lab = self.labels_from_tiles(tiles, w_band, up_hw, pad_tl, hw)
@@ -763,7 +869,7 @@ class SegPipeline:
         T = len(wins)
         lo, hi = partition(T, world, rank)
         mine = list(wins[lo:hi])
-        fuse = getattr(self, "cross_tile_fusion", None) is not None and grid_of_tiles is not None and T > 1
+        fuse = self.cross_tile_fusion is not None and grid_of_tiles is not None and T > 1
         if fuse:
             local = self._fused_tile_logits(scene, mine if mine else [wins[0]], tile_hw, grid_of_tiles, T, world, rank, group,
                                             n_real=hi - lo)
@@ -772,32 +878,18 @@ class SegPipeline:
         return gather_blocks(local, T, world, rank, group)
 
     def _fused_tile_logits(self, scene, mine, tile_hw, grid_of_tiles, T, world, rank, group, n_real):
-        v = self.visual
-        P = v.cfg.patch
-        l, r, t, b = compute_padsize(tile_hw[0], tile_hw[1], P)
-        gh, gw = (tile_hw[0] + t + b) // P, (tile_hw[1] + l + r) // P
-        opts = v.forward_opts(self.model_type, self.ignore_residual, self.apply_similarity_enhancement,
-                              getattr(self, "apply_layer_fusion", False), getattr(self, "layer_fusion_lambda", 0.5))
+        """The logits of this rank's tiles ``mine`` (``n_real`` of them; a dummy tile keeps a rank without tiles in the collectives) with
+        cross-tile fusion across the ranks: tower, ``sharded_cross_tile_fusion``, head."""
+        geo = self._tile_geometry(tile_hw)
         win = torch.tensor(list(mine), dtype=torch.int32, device=self.device).reshape(-1, 4)
-        cls_all, tok_all = [], []
-        for i, j in launch_chunks(win.shape[0], self.tiles_per_launch):
-            c_, t_ = v.forward_tiles(scene, win[i:j], tile_hw, opts, None)
-            cls_all.append(c_); tok_all.append(t_)
-        tok = torch.cat(tok_all, 0)[:n_real].contiguous()
-        cls = None if cls_all[0] is None else torch.cat(cls_all, 0)[:n_real].contiguous()
-        cf = self.cross_tile_fusion
-        steps = ops.CrossTileSteps(gh, gw, tok.shape[-1], cf.get("cache_boundary_width", 2), cf.get("fusion_mode", "weighted"),
-                                   cf.get("fusion_strength", 0.3), grid_of_tiles[1])
+        cls, tok = self._tower(scene, win, tile_hw, launch_chunks(win.shape[0], self.tiles_per_launch))
+        tok = tok[:n_real].contiguous()
+        cls = None if cls is None else cls[:n_real].contiguous()
+        steps = ops.CrossTileSteps(*geo.grid, tok.shape[-1], *self._fusion_args(), grid_of_tiles[1])
         tok = sharded_cross_tile_fusion(tok, steps, T, world, rank, group)
         if n_real == 0:
-            up_hw = (tile_hw[0] + t + b, tile_hw[1] + l + r)
-            return tok.new_zeros((0, self.num_queries) + (self.upsampler.output_hw((gh, gw), up_hw) if self.upsampler is not None else (gh, gw)))
-        tok, f = self._pre_head(tok, cls)
-        if self.upsampler is not None:                   # fused tokens -> JBU -> per-pixel logits of this rank's tiles (they travel as halo tiles)
-            return self.upsampler.logits(tok, cls, scene, win[:n_real], tile_hw, (l, t), (gh, gw), self.text, f, self.cls_token_lambda, None,
-                                         padded_hw=(tile_hw[0] + t + b, tile_hw[1] + l + r))
-        lg = ops.cosine_logits(tok, cls, self.text, f, self.cls_token_lambda if cls is not None else 0.0)
-        return lg.reshape(n_real, self.num_queries, gh, gw)
+            return tok.new_zeros((0, self.num_queries) + (self.upsampler.output_hw(geo.grid, geo.up_hw) if self.upsampler is not None else geo.grid))
+        return self._head_logits(tok, cls, scene, win[:n_real], tile_hw)
 
     # -- packed slide inference: the windows of many images in shared launches ----------------------------------------
     flush_bytes = 4 << 30       # bound on the tile logits + canvases of one flush group (plan_images)
@@ -806,10 +898,9 @@ class SegPipeline:
     def _packed_canvases(self, scenes, stride, crop):
         """Yields (image indices, flat canvas buffer, its [Q,H,W] views) per flush group: ``_packed_tiles`` and one sg_stitch_multi
         launch."""
-        extra = 0 if self.area_thd is None else 4 * self.num_classes + 8           # area_thd: the probability planes always exist
-        for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(scenes, stride, crop, 4 * self.num_queries + extra):
-            canvases, views = ops.stitch_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles)
-            yield idx, canvases, views
+        for group in self._packed_tiles(scenes, stride, crop, self._canvas_bytes()):
+            canvases, views = ops.stitch_multi(*group[1:])
+            yield group[0], canvases, views
 
     def _packed_tiles(self, scenes, stride, crop, pixel_bytes):
         """Yields, per flush group, what a multi-image stitch takes: (image indices, tile logits, windows, image of each tile, up_hw,
@@ -820,68 +911,38 @@ class SegPipeline:
             raise ValueError("packed inference shards images over ranks, not tiles: with tile_group set use forward_slide / "
                              "segment_scene per image")
         buf, shapes = pack_scenes(scenes, self.device, self.pack_fill)
-        P, Q = self.visual.cfg.patch, self.num_queries
 
         def tile_bytes(thw):
-            l, r, t, b = compute_padsize(thw[0], thw[1], P)
-            gh, gw = (thw[0] + t + b) // P, (thw[1] + l + r) // P
-            oh, ow = self.upsampler.output_hw((gh, gw), (thw[0] + t + b, thw[1] + l + r)) if self.upsampler is not None else (gh, gw)
-            tok = gh * gw * self.visual.cfg.embed_dim * 4 if self.cross_tile_fusion is not None else 0
-            return 4 * Q * oh * ow + tok
+            geo = self._tile_geometry(thw)
+            oh, ow = self.upsampler.output_hw(geo.grid, geo.up_hw) if self.upsampler is not None else geo.grid
+            tok = geo.grid[0] * geo.grid[1] * self.visual.cfg.embed_dim * 4 if self.cross_tile_fusion is not None else 0
+            return 4 * self.num_queries * oh * ow + tok
 
-        groups = plan_images(shapes, stride, crop, P, self.tiles_per_launch, tile_bytes, pixel_bytes, self.flush_bytes)
+        groups = plan_images(shapes, stride, crop, self.visual.cfg.patch, self.tiles_per_launch, tile_bytes, pixel_bytes, self.flush_bytes)
         for g in groups:
-            th, tw = g.tile_hw
-            l, r, t, b = compute_padsize(th, tw, P)
+            geo = self._tile_geometry(g.tile_hw)
             for f in g.flush:
                 tl = self._packed_tile_logits(buf, g, f)
                 imgs = range(f.img_lo, f.img_hi)
                 local = [k - f.img_lo for k in imgs for _ in range(g.n_tiles[k])]
-                yield ([g.images[k] for k in imgs], tl, g.windows[f.tile_lo:f.tile_hi], local, (th + t + b, tw + l + r), (t, l),
+                yield ([g.images[k] for k in imgs], tl, g.windows[f.tile_lo:f.tile_hi], local, geo.up_hw, geo.pad_tl,
                        [g.shapes[k] for k in imgs], [(g.first_tile[k] - f.tile_lo, g.n_tiles[k]) for k in imgs])
 
     def _packed_tile_logits(self, buf, g: TileSizeGroup, f: FlushGroup) -> torch.Tensor:
-        v = self.visual
-        P = v.cfg.patch
-        th, tw = g.tile_hw
-        l, r, t, b = compute_padsize(th, tw, P)
-        gh, gw = (th + t + b) // P, (tw + l + r) // P
-        opts = v.forward_opts(self.model_type, self.ignore_residual, self.apply_similarity_enhancement, self.apply_layer_fusion,
-                              self.layer_fusion_lambda)
         win = torch.tensor(g.windows[f.tile_lo:f.tile_hi], dtype=torch.int32, device=self.device).reshape(-1, 4)
         sidx = torch.tensor(g.tile_image[f.tile_lo:f.tile_hi], dtype=torch.int32, device=self.device)
-
-        def head(tok, cls, w, si):
-            tok, fct = self._pre_head(tok, cls)
-            if self.upsampler is not None:
-                return self.upsampler.logits(tok, cls, buf, w, (th, tw), (l, t), (gh, gw), self.text, fct, self.cls_token_lambda, si,
-                                             padded_hw=(th + t + b, tw + l + r))
-            lg = ops.cosine_logits(tok, cls, self.text, fct, self.cls_token_lambda if cls is not None else 0.0)
-            return lg.reshape(w.shape[0], self.num_queries, gh, gw)
-
+        chunks = [(i - f.tile_lo, j - f.tile_lo) for i, j in f.chunks]
         fused = [k for k in range(f.img_lo, f.img_hi) if g.grids[k][0] * g.grids[k][1] > 1]
         if self.cross_tile_fusion is None or not fused:
-            outs = []
-            for i, j in f.chunks:
-                a, z = i - f.tile_lo, j - f.tile_lo
-                cls, tok = v.forward_tiles(buf, win[a:z], (th, tw), opts, sidx[a:z])
-                outs.append(head(tok, cls, win[a:z], sidx[a:z]))
-            return torch.cat(outs, 0) if len(outs) > 1 else outs[0]
+            return self._logits_by_chunk(buf, win, g.tile_hw, chunks, sidx)
         # boundary fusion couples the tiles of one image's grid: the packed tower first, then the fusion on each image's contiguous
         # token slice, then the head over the whole flush group
-        cls_all, tok_all = [], []
-        for i, j in f.chunks:
-            c_, t_ = v.forward_tiles(buf, win[i - f.tile_lo:j - f.tile_lo], (th, tw), opts, sidx[i - f.tile_lo:j - f.tile_lo])
-            cls_all.append(c_); tok_all.append(t_)
-        tok = torch.cat(tok_all, 0)
-        cf = self.cross_tile_fusion
+        cls, tok = self._tower(buf, win, g.tile_hw, chunks, sidx)
+        gh, gw = self._tile_geometry(g.tile_hw).grid
         for k in fused:
-            a = g.first_tile[k] - f.tile_lo
-            n = g.n_tiles[k]
-            tok[a:a + n] = ops.cross_tile_fusion(tok[a:a + n], g.grids[k][0], g.grids[k][1], gh, gw, cf.get("cache_boundary_width", 2),
-                                                 cf.get("fusion_mode", "weighted"), cf.get("fusion_strength", 0.3))
-        cls = None if cls_all[0] is None else torch.cat(cls_all, 0)
-        return head(tok, cls, win, sidx)
+            a, n = g.first_tile[k] - f.tile_lo, g.n_tiles[k]
+            tok[a:a + n] = ops.cross_tile_fusion(tok[a:a + n], g.grids[k][0], g.grids[k][1], gh, gw, *self._fusion_args())
+        return self._head_logits(tok, cls, buf, win, g.tile_hw, sidx)
 
     def forward_slide_many(self, scenes, stride, crop, ori_shapes=None) -> List[torch.Tensor]:
         """``forward_slide`` for many images with their windows packed into shared tower launches (``plan_images``).  scenes: a list
@@ -897,163 +958,22 @@ class SegPipeline:
         return out
 
     def label_groups(self, scenes, stride, crop, want_probs: bool = False, ori_shapes=None, topk: int = 0):
-        """The whole packed path to labels, flush group by flush group: one sg_stitch_multi and one sg_postprocess_multi launch each
-        (the resize to ``ori_shapes`` fused into the latter).  Yields (image indices, list of probs [K,H,W] or None, list of labels
-        [1,H,W], the flat int64 buffer those label maps are views of, in that order of images).
-        Labels alone at the images' own sizes with the fused head selected (``label_head``): one sg_label_head_multi launch per flush
-        group and no canvas.  Probabilities at the images' own sizes with the fused probability head selected (``prob_head``): one
-        sg_prob_head_multi launch per flush group, no canvas, any number of queries (the planner counts 4K + 8 bytes per pixel then).
-        Otherwise probabilities or a resize keep the canvas; beyond 64 queries they then go image by image through ``ops.postprocess``
-        (its wide form) on the group's canvases.
-        With PAMR on (``pamr_steps``) every group takes the canvas route: a flush group whose images all keep their size (and Q <= 64)
-        has each canvas view refined in place and then the one sg_postprocess_multi launch; a group holding an image with another
-        ``ori_shape`` goes image by image: resize, PAMR, post-process.
-        ``topk`` > 0 (not with ``want_probs``): yields (image indices, list of probs f32 [topk,H,W], list of classes int32 [topk,H,W],
-        None) -- the k best classes of every pixel.  At the images' own sizes and without PAMR that is one sg_topk_head_multi launch
-        per flush group with no canvas (the planner counts 8 * topk bytes per pixel); otherwise the probabilities come as above and go
-        through ``ops.topk_from_probs`` image by image.
-        ``resize_head="fused"`` without PAMR, when some image's ``ori_shape`` differs from its size: labels alone take one
-        sg_label_head_resized_multi launch, and ``topk`` one sg_topk_head_resized_multi launch, per flush group that holds such an image
-        (the resize runs inside the head, no canvas; the planner counts 8 or 8 * topk bytes per OUTPUT pixel); a flush group in which no
-        image differs runs what it runs without the option.
-        With ``area_thd`` set each group decides twice, with one launch per step wherever the group has one post-process or head launch
-        today: first pass (``prob_thd = 0``), sg_class_area_multi, sg_area_keep, then sg_area_filter_probs_multi on the group's
-        probabilities (written into a scratch when only labels are wanted) or, for labels alone on the fused label head,
-        sg_area_relabel_multi (no canvas, no probabilities; the planner counts 12 bytes per pixel instead of 8).  Groups that go image by
-        image stay image by image (``postprocess``).  ``resize_head="fused"`` takes the canvas route; ``topk`` is refused."""
-        no_resize = ori_shapes is None or all(o is None for o in ori_shapes)
-        if topk:
-            if want_probs:
-                raise ValueError("label_groups: topk and want_probs exclude each other (topk returns the k best class probabilities)")
-            if self.tile_group is not None:
-                raise ValueError(TOPK_TILE_GROUP)
-            k = self.topk_k(topk)
-            same_size = no_resize or all(o is None or tuple(o) == _scene_hw(s) for o, s in zip(
-                ori_shapes, [scenes] if torch.is_tensor(scenes) and scenes.dim() == 3 else scenes))
-            if self.pamr_steps == 0 and same_size:
-                for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(scenes, stride, crop, 8 * k):
-                    cls, prb = ops.topk_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes,
-                                                   self.logit_scale, k)
-                    yield idx, prb, cls, None
-                return
-            if self.fused_resize_head():
-                # some ori_shape differs: one sg_topk_head_resized_multi launch per flush group that holds such an image, today's kernel
-                # for a group that holds none; no canvas either way
-                for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(
-                        scenes, stride, crop, lambda i: 8 * k * _out_pixels(ori_shapes, i, scenes)):
-                    shapes = [tuple(hw) for hw in shapes]
-                    ohw = [shapes[n] if ori_shapes[i] is None else tuple(int(v) for v in ori_shapes[i]) for n, i in enumerate(idx)]
-                    if ohw == shapes:
-                        cls, prb = ops.topk_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes,
-                                                       self.logit_scale, k)
-                    else:
-                        cls, prb = ops.topk_head_resized_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, ohw, self.query_idx,
-                                                               self.num_classes, self.logit_scale, k)
-                    yield idx, prb, cls, None
-                return
-            for idx, prb, _, _ in self.label_groups(scenes, stride, crop, True, ori_shapes):
-                pairs = [ops.topk_from_probs(p, self.query_idx, k) for p in prb]
-                yield idx, [p for _, p in pairs], [c for c, _ in pairs], None
-            return
-        if self.pamr_steps > 0:
-            yield from self._label_groups_pamr(scenes, stride, crop, want_probs, ori_shapes)
-            return
-        if want_probs and self.fused_prob_head() and (no_resize or all(
-                o is None or tuple(o) == _scene_hw(s)
-                for o, s in zip(ori_shapes, [scenes] if torch.is_tensor(scenes) and scenes.dim() == 3 else scenes))):
-            for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(scenes, stride, crop, 4 * self.num_classes + 8):
-                if self.area_thd is not None:
-                    prb, lab, flat, probs = ops.prob_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx,
-                                                                self.num_classes, self.logit_scale, 0.0, self.bg_idx, flat_probs=True)
-                    self.area_filter_first_pass_multi(probs, flat, [tuple(hw) for hw in shapes])
-                else:
-                    prb, lab, flat = ops.prob_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes,
-                                                         self.logit_scale, self.prob_thd, self.bg_idx)
-                yield idx, prb, lab, flat
-            return
-        if not want_probs and self.fused_resize_head() and not no_resize and any(
-                o is not None and tuple(o) != _scene_hw(s)
-                for o, s in zip(ori_shapes, [scenes] if torch.is_tensor(scenes) and scenes.dim() == 3 else scenes)):
-            # labels at another ori_shape with no canvas: one sg_label_head_resized_multi launch per flush group that holds such an image;
-            # a group that holds none runs today's kernels
-            for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(
-                    scenes, stride, crop, lambda i: 8 * _out_pixels(ori_shapes, i, scenes)):
-                shapes = [tuple(hw) for hw in shapes]
-                ohw = [shapes[n] if ori_shapes[i] is None else tuple(int(v) for v in ori_shapes[i]) for n, i in enumerate(idx)]
-                if ohw != shapes:
-                    lab, flat = ops.label_head_resized_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, ohw, self.query_idx,
-                                                             self.num_classes, self.logit_scale, self.prob_thd, self.bg_idx)
-                elif self.fused_label_head():
-                    lab, flat = ops.label_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes,
-                                                     self.logit_scale, self.prob_thd, self.bg_idx)
-                else:
-                    canvases, views = ops.stitch_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles)
-                    if self.num_queries <= ops.POSTPROCESS_MAX_Q:
-                        _, lab, flat = ops.postprocess_multi(canvases, shapes, self.query_idx, self.num_classes, self.logit_scale,
-                                                             self.prob_thd, self.bg_idx, shapes, False, flat_labels=True)
-                    else:                                                 # label_head="canvas" beyond 64 queries: image by image
-                        flat = torch.cat([self.postprocess(c, want_probs=False)[1].reshape(-1) for c in views])
-                        pix = ops._prefix(h * w for h, w in shapes)
-                        lab = [flat[pix[n]:pix[n + 1]].view(1, *shapes[n]) for n in range(len(shapes))]
-                yield idx, [None] * len(idx), lab, flat
-            return
-        if not want_probs and no_resize and self.fused_label_head():
-            if self.area_thd is not None:
-                # first pass with conf (12 bytes per pixel), the areas of every image of the group, then the relabel: one launch each
-                for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(scenes, stride, crop, 12):
-                    lab, flat, conf = ops.label_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes,
-                                                           self.logit_scale, 0.0, self.bg_idx, want_conf=True, flat_conf=True)
-                    keep = ops.area_keep(ops.class_area_multi(flat, [h * w for h, w in shapes], self.num_classes), self.bg_idx, self.area_thd)
-                    ops.area_relabel_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes, self.logit_scale,
-                                           self.prob_thd, self.bg_idx, keep, conf, flat)
-                    yield idx, [None] * len(idx), lab, flat
-                return
-            for idx, tl, wins, local, up_hw, pad_tl, shapes, tiles in self._packed_tiles(scenes, stride, crop, 8):
-                lab, flat = ops.label_head_multi(tl, wins, local, up_hw, pad_tl, shapes, tiles, self.query_idx, self.num_classes,
-                                                 self.logit_scale, self.prob_thd, self.bg_idx)
-                yield idx, [None] * len(idx), lab, flat
-            return
-        if self.num_queries > ops.POSTPROCESS_MAX_Q:
-            for idx, canvases, views in self._packed_canvases(scenes, stride, crop):
-                prb, lab = [], []
-                for n, k in enumerate(idx):
-                    c = views[n]
-                    if not no_resize and ori_shapes[k] is not None and tuple(ori_shapes[k]) != tuple(c.shape[1:]):
-                        c = ops.resize_bilinear(c, tuple(ori_shapes[k]))
-                    p_, l_ = self.postprocess(c, want_probs=want_probs)
-                    prb.append(p_); lab.append(l_.reshape(-1))
-                flat = torch.cat(lab)
-                pix = ops._prefix(l_.numel() for l_ in lab)
-                hw = [tuple(views[n].shape[1:]) if no_resize or ori_shapes[k] is None else tuple(ori_shapes[k]) for n, k in enumerate(idx)]
-                yield idx, prb, [flat[pix[n]:pix[n + 1]].view(1, *hw[n]) for n in range(len(lab))], flat
-            return
-        for idx, canvases, views in self._packed_canvases(scenes, stride, crop):
-            chw = [tuple(c.shape[1:]) for c in views]
-            ohw = [chw[n] if ori_shapes is None or ori_shapes[k] is None else tuple(ori_shapes[k]) for n, k in enumerate(idx)]
-            prb, lab, flat = self._postprocess_multi(canvases, chw, ohw, want_probs)
-            yield idx, prb, lab, flat
-
-    def _label_groups_pamr(self, scenes, stride, crop, want_probs, ori_shapes):
-        """``label_groups`` with PAMR on (see there)."""
-        single = torch.is_tensor(scenes) and scenes.dim() == 3
-        for idx, canvases, views in self._packed_canvases(scenes, stride, crop):
-            imgs = [scenes if single else scenes[k] for k in idx]
-            chw = [tuple(c.shape[1:]) for c in views]
-            ohw = [chw[n] if ori_shapes is None or ori_shapes[k] is None else tuple(ori_shapes[k]) for n, k in enumerate(idx)]
-            if ohw == chw and self.num_queries <= ops.POSTPROCESS_MAX_Q:
-                for c, im in zip(views, imgs):
-                    self.refine(c, im.to(self.device))
-                yield (idx,) + tuple(self._postprocess_multi(canvases, chw, ohw, want_probs))
-                continue
-            prb, lab = [], []
-            for c, im, hw in zip(views, imgs, ohw):
-                if hw != tuple(c.shape[1:]):
-                    c = ops.resize_bilinear(c, hw)
-                p_, l_ = self.postprocess(self.refine(c, im.to(self.device)), want_probs=want_probs)
-                prb.append(p_); lab.append(l_.reshape(-1))
-            flat = torch.cat(lab)
-            pix = ops._prefix(l_.numel() for l_ in lab)
-            yield idx, prb, [flat[pix[n]:pix[n + 1]].view(1, *ohw[n]) for n in range(len(lab))], flat
+        """The whole packed path, flush group by flush group.  Yields (image indices, list of probs f32 [K,H,W] or None, list of labels
+        int64 [1,H,W], the flat int64 buffer those label maps are views of, in that order of images); (H, W) = ``ori_shapes[i]`` or the
+        image's size.  ``topk`` > 0 (not with ``want_probs``, not with area_thd): yields (image indices, list of probs f32 [topk,H,W],
+        list of classes int32 [topk,H,W], None) -- the k best classes of every pixel.
+        Which kernels run is decided once for the call by ``tail_route`` and applied per flush group by ``_group_tail``; every route
+        returns the same bytes (DESIGN.md section 5 'Route table')."""
+        want, k = self._wanted("label_groups", want_probs, topk, self.tile_group is not None)
+        given = ori_shapes is not None and any(o is not None for o in ori_shapes)
+        route = self.tail_route(want, k, given, _ori_differs(ori_shapes, scenes))
+        pixel_bytes = route.pixel_bytes
+        if route.route == RESIZED_HEAD:
+            pixel_bytes = lambda i: route.pixel_bytes * _out_pixels(ori_shapes, i, scenes)
+        for group in self._packed_tiles(scenes, stride, crop, pixel_bytes):
+            idx = group[0]
+            imgs = [_images(scenes)[i] for i in idx] if self.pamr_steps > 0 else [None] * len(idx)
+            yield (idx,) + self._group_tail(route.route, want, k, group, _out_sizes(ori_shapes, idx, group[6]), imgs)
 
     def segment_scenes(self, scenes, stride, crop, want_probs: bool = False, ori_shapes=None, topk: int = 0):
         """``label_groups`` collected per image -> list of labels [1,H,W], or (list of probs [K,H,W], list of labels) with

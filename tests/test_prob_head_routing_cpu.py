@@ -4,7 +4,6 @@ above the canvas route's at both Q = 130 and Q = 256 -- otherwise the canvas eve
 rule gives on the recorded numbers."""
 import json
 import os
-import types
 
 import pytest
 
@@ -12,9 +11,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROFILE = os.path.join(ROOT, "profiles", "r08_bench_prob_head.jsonl")
 
 
+def stub(**attrs):
+    """A SegPipeline without its constructor, with only these attributes set: every option not given reads its class-level default."""
+    from clip_decontamination_amd.pipeline import SegPipeline
+    pipe = SegPipeline.__new__(SegPipeline)
+    for name, value in attrs.items():
+        setattr(pipe, name, value)
+    return pipe
+
+
 def fused(mode, Q):
     from clip_decontamination_amd.pipeline import SegPipeline
-    return SegPipeline.fused_prob_head(types.SimpleNamespace(prob_head=mode, num_queries=Q))
+    return SegPipeline.fused_prob_head(stub(prob_head=mode, num_queries=Q))
 
 
 def recorded_rule():
@@ -47,7 +55,7 @@ def test_auto_beyond_64_queries_follows_the_recorded_measurement(Q):
 
 def test_a_pipeline_without_the_attribute_is_auto():
     from clip_decontamination_amd.pipeline import SegPipeline
-    assert SegPipeline.fused_prob_head(types.SimpleNamespace(num_queries=9)) is False
+    assert SegPipeline.fused_prob_head(stub(num_queries=9)) is False
 
 
 def test_unknown_mode_is_refused_by_the_pipeline():
