@@ -164,6 +164,8 @@ SIGNATURES = {
     "sg_area_filter_probs_multi": (I, [P, P, P, P, P, P, I, L, L, I, F, I, P, P]),
     "sg_area_relabel": (I, [P, P, I, I, I, I, I, I, I, I, I, I, P, I, F, F, I, P, P, P, P]),
     "sg_area_relabel_multi": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, I, L, L, P, I, F, F, I, P, P, P, P]),
+    "sg_sieve_workspace_bytes": (Z, [L, I]),
+    "sg_sieve": (I, [P, P, P, P, I, L, I, I, L, P, Z, P]),
 }
 
 _lib = None

@@ -1063,3 +1063,80 @@ class CrossTileSteps:
         check(self.lib.sg_cross_tile_apply(ptr(tokens), ptr(left_result), ptr(top_result), tokens.shape[0], tile0, self.wg, self.gh, self.gw,
                                            self.C, self.bw, stream_ptr()), "sg_cross_tile_apply")
         return tokens
+
+
+SIEVE_FILLS = {"bg": 0, "neighbour": 1}                                  # SG_SIEVE_FILL_* (include/segearth_hip.h)
+SIEVE_MAX_PIXELS = (1 << 31) - 1                                         # per image: region roots are 32-bit raster indices
+
+
+def sieve_args(min_region, connectivity=4, fill="neighbour"):
+    """The checks of the min_region options, shared by ``sieve`` and the constructors: min_region an integer >= 1, connectivity 4 or
+    8, fill "bg" or "neighbour" -> (min_region, connectivity, fill)."""
+    if isinstance(min_region, bool) or not isinstance(min_region, int) or min_region < 1:
+        raise ValueError(f"min_region must be an integer >= 1 (a region is small when its area is below it), got {min_region!r}")
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError(f"region connectivity must be 4 or 8, got {connectivity!r}")
+    if fill not in SIEVE_FILLS:
+        raise ValueError(f"region fill must be one of {tuple(SIEVE_FILLS)}, got {fill!r}")
+    return int(min_region), int(connectivity), fill
+
+
+@on_tensor_device
+def sieve_flat(labels, image_hw, min_region, connectivity=4, fill="neighbour", bg_idx=0, out=None):
+    """sg_sieve on a flat int64 buffer that holds N label maps back to back (what the multi-image heads return), sizes ``image_hw``:
+    one call, one launch sequence per 64 images.  In place unless ``out`` (a flat int64 buffer of the same size) is given; returns the
+    buffer that was written.  Nothing synchronises with the host."""
+    lib = _lib.load()
+    min_region, connectivity, fill = sieve_args(min_region, connectivity, fill)
+    labels = _i64_labels("sieve", labels)
+    image_hw = [(int(h), int(w)) for h, w in image_hw]
+    pix = _prefix(h * w for h, w in image_hw)
+    if not image_hw or any(h <= 0 or w <= 0 for h, w in image_hw) or pix[-1] != labels.numel():
+        raise ValueError(f"sieve: {len(image_hw)} images of sizes {image_hw} against {labels.numel()} labels")
+    if any(h * w > SIEVE_MAX_PIXELS for h, w in image_hw):
+        raise ValueError(f"sieve: an image of 2^31 or more pixels is not supported (region roots are 32-bit raster indices), got {image_hw}")
+    if out is None:
+        out = labels
+    elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != labels.numel() or out.device != labels.device:
+        raise ValueError("sieve: out must be a contiguous int64 tensor of the labels' size on the labels' device")
+    N = len(image_hw)
+    hw = (C.c_int32 * (2 * N))(*[v for s in image_hw for v in s])
+    off = (C.c_int64 * N)(*pix[:-1])
+    nbytes = int(lib.sg_sieve_workspace_bytes(pix[-1], SIEVE_FILLS[fill]))
+    buf = scratch(nbytes, labels.device)
+    wp, wn = _aligned(buf)
+    check(lib.sg_sieve(ptr(labels), ptr(out), hw, off, N, min_region, connectivity, SIEVE_FILLS[fill], int(bg_idx), wp, wn, stream_ptr()),
+          "sg_sieve")
+    return out
+
+
+def sieve(labels, min_region, connectivity=4, fill="neighbour", bg_idx=0, out=None):
+    """Sieve the connected regions of fewer than ``min_region`` pixels out of a label map (the definition: sg_sieve in
+    include/segearth_hip.h).  ``labels``: int64 [H,W] or [1,H,W] on the device, or a list of such maps of any sizes -- a list is packed
+    into one flat buffer and served by one sg_sieve call.  ``fill="bg"``: a small region that is not background becomes ``bg_idx``
+    (remove_small_objects); ``fill="neighbour"``: every small region takes the label of its largest adjacent kept region, ties to the
+    smaller root, ``bg_idx`` when there is none (one pass, not iterated to a fixed point).  Returns new tensors of the same shapes, or
+    writes ``out`` (same shapes; ``out=labels`` sieves in place) and returns it."""
+    many = isinstance(labels, (list, tuple))
+    maps = list(labels) if many else [labels]
+    outs = None if out is None else (list(out) if many else [out])
+    if not maps or (outs is not None and len(outs) != len(maps)):
+        raise ValueError("sieve: needs at least one label map, and one out per map")
+    for m in maps:
+        if not torch.is_tensor(m) or m.dim() not in (2, 3) or (m.dim() == 3 and m.shape[0] != 1) or m.numel() == 0:
+            raise ValueError("sieve: a label map must be a non-empty int64 [H,W] or [1,H,W] tensor")
+        _i64_labels("sieve", m)
+    hw = [tuple(m.shape[-2:]) for m in maps]
+    if len(maps) == 1:
+        dst = outs[0] if outs is not None else torch.empty_like(maps[0])
+        if tuple(dst.shape) != tuple(maps[0].shape):
+            raise ValueError(f"sieve: out {tuple(dst.shape)} against labels {tuple(maps[0].shape)}")
+        sieve_flat(maps[0].reshape(-1), hw, min_region, connectivity, fill, bg_idx, out=dst.reshape(-1) if dst.is_contiguous() else dst)
+        return [dst] if many else dst
+    flat = sieve_flat(torch.cat([m.reshape(-1) for m in maps]), hw, min_region, connectivity, fill, bg_idx)
+    res = [v.view(m.shape) for v, m in zip(flat_views(flat, 1, hw), maps)]
+    if outs is None:
+        return res
+    for o, r in zip(outs, res):
+        o.copy_(r)
+    return outs

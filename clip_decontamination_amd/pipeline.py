@@ -393,10 +393,19 @@ AREA_TOPK = ("top-k together with area_thd is not built: the k best classes woul
              "top-k head decides before the areas are known; run predict_topk / topk= on an instance without area_thd")
 
 
+SIEVE_TILE_GROUP = ("min_region under tile_group sharding is not built: a region crosses the ranks' canvas bands, so each band would need a "
+                    "halo and the roots on the band borders a union across the ranks; sieve whole images per rank")
+
+
+SIEVE_TOPK = ("top-k together with min_region is not built: sieving plane 0 would leave the other planes describing pixels whose label has "
+              "changed; run predict_topk / topk= on an instance without min_region")
+
+
 class SegPipeline:
     # Every constructor option has its default here too, so an instance built without the constructor (the CPU tests' stubs) reads them.
     pamr_steps, pamr_stride = 0, (8, 16)      # PAMR off unless the constructor says otherwise
     area_thd = None                           # area_thd off likewise
+    min_region, region_connectivity, region_fill = None, 4, "neighbour"      # the sieve off likewise
     label_head, prob_head, resize_head = "auto", "auto", "canvas"
     apply_ctd, apply_layer_fusion, layer_fusion_lambda = False, False, 0.5
     cross_tile_fusion = tile_group = upsampler = None
@@ -406,7 +415,15 @@ class SegPipeline:
                  logit_scale: float = 50.0, prob_thd: float = 0.0, bg_idx: int = 0, apply_similarity_enhancement: bool = False,
                  upsampler=None, tiles_per_launch: int = 32, cross_tile_fusion: Optional[dict] = None, apply_ctd: bool = False,
                  tile_group=None, apply_layer_fusion: bool = False, layer_fusion_lambda: float = 0.5, label_head: str = "auto",
-                 prob_head: str = "auto", pamr_steps: int = 0, pamr_stride=(8, 16), resize_head: str = "canvas", area_thd=None):
+                 prob_head: str = "auto", pamr_steps: int = 0, pamr_stride=(8, 16), resize_head: str = "canvas", area_thd=None,
+                 min_region=None, region_connectivity: int = 4, region_fill: str = "neighbour"):
+        # min_region (None = off, and then no call changes route, launches or bytes): the connected regions of the FINAL labels -- after
+        # prob_thd and area_thd, at ori_shape, whatever route the tail took -- that have fewer than min_region pixels are sieved out
+        # (sg_sieve; the definition: include/segearth_hip.h): region_fill "neighbour" gives them the label of their largest adjacent kept
+        # region, "bg" turns the non-background ones into bg_idx; region_connectivity 4 or 8.  One sg_sieve call per image or per flush
+        # group.  Probabilities that are returned beside the labels are left as they are.
+        _, self.region_connectivity, self.region_fill = ops.sieve_args(1 if min_region is None else min_region, region_connectivity, region_fill)
+        self.min_region = min_region
         if resize_head not in RESIZE_HEADS:
             raise ValueError(f"resize_head must be one of {RESIZE_HEADS}, got {resize_head!r}")
         # labels / top-k at another ori_shape than the image's (RESIZE_HEADS); PAMR and whole-image inference keep the canvas route
@@ -488,6 +505,8 @@ class SegPipeline:
         """``topk`` checked against what sg_topk_head takes: 1 .. min(ops.TOPK_MAX, the number of classes)."""
         if self.area_thd is not None:
             raise ValueError(AREA_TOPK)
+        if self.min_region is not None:
+            raise ValueError(SIEVE_TOPK)
         k = int(topk)
         if not 1 <= k <= min(ops.TOPK_MAX, self.num_classes):
             raise ValueError(f"topk must lie in [1, min({ops.TOPK_MAX}, {self.num_classes} classes)], got {topk!r}")
@@ -508,6 +527,8 @@ class SegPipeline:
             raise ValueError(PAMR_TILE_GROUP)
         if sharded and self.area_thd is not None:
             raise ValueError(AREA_TILE_GROUP)
+        if sharded and self.min_region is not None:
+            raise ValueError(SIEVE_TILE_GROUP)
 
     def _canvas_bytes(self) -> int:
         """Per pixel of a canvas route: the [Q,H,W] canvas, and with area_thd the probability planes and labels, which then always exist."""
@@ -558,7 +579,22 @@ class SegPipeline:
         keep = self._area_keep(flat, [h * w for h, w in out_hw])
         ops.area_filter_probs_multi(probs, flat, keep, out_hw, self.prob_thd, self.bg_idx)
 
+    def sieve(self, labels: torch.Tensor, image_hw=None) -> torch.Tensor:
+        """min_region, the last step on final labels, IN PLACE: one label map int64 [1,H,W] / [H,W], or with ``image_hw`` the flat buffer
+        of a flush group's maps (one sg_sieve call for the group).  With ``min_region = None`` the labels as they came."""
+        if self.min_region is not None:
+            hw = [tuple(labels.shape[-2:])] if image_hw is None else image_hw
+            ops.sieve_flat(labels.view(-1), hw, self.min_region, self.region_connectivity, self.region_fill, self.bg_idx)
+        return labels
+
     def _image_tail(self, route: str, want: str, k: int, tile_logits, windows, up_hw, pad_tl, canvas_hw, out_hw, guide):
+        """``_image_tail_unsieved`` and then, with min_region set, the sieve on its labels (top-k is refused with min_region)."""
+        out = self._image_tail_unsieved(route, want, k, tile_logits, windows, up_hw, pad_tl, canvas_hw, out_hw, guide)
+        if self.min_region is not None and want != "topk":
+            self.sieve(out[1] if want == "probs" else out)
+        return out
+
+    def _image_tail_unsieved(self, route: str, want: str, k: int, tile_logits, windows, up_hw, pad_tl, canvas_hw, out_hw, guide):
         """One image's (or one canvas band's) tile logits [T,Q,gh,gw] + windows [T,4] -> labels int64 [1,H,W], (probs f32 [K,H,W],
         labels) or (classes int32 [k,H,W], probs f32 [k,H,W]) on ``route``, (H, W) = ``out_hw``."""
         args = (tile_logits, windows, up_hw, pad_tl, canvas_hw)
@@ -637,6 +673,14 @@ class SegPipeline:
         return prb, ops.flat_views(flat, 1, ohw), flat
 
     def _group_tail(self, route: str, want: str, k: int, group, ohw, imgs):
+        """``_group_tail_unsieved`` and then, with min_region set, ONE sg_sieve call over the group's flat labels (the label maps are
+        views of that buffer)."""
+        prb, lab, flat = self._group_tail_unsieved(route, want, k, group, ohw, imgs)
+        if self.min_region is not None and want != "topk":
+            self.sieve(flat, ohw)
+        return prb, lab, flat
+
+    def _group_tail_unsieved(self, route: str, want: str, k: int, group, ohw, imgs):
         """One flush group of ``_packed_tiles`` on ``route`` -> (list of probs or Nones, list of labels, flat labels), or for top-k
         (list of probs [k,H,W], list of classes [k,H,W], None).  ``ohw``: the output size per image; ``imgs``: the images (PAMR's guides)."""
         idx, shapes = group[0], group[6]
@@ -1010,7 +1054,9 @@ class SegPipeline:
     # -- reference postprocess_result --------------------------------------------------------------------------
     def postprocess(self, seg_logits: torch.Tensor, want_probs: bool = True):
         """seg_logits [Q,H,W] -> (probs [K,H,W], labels int64 [1,H,W]).  With ``area_thd`` the first pass runs with ``prob_thd = 0`` and
-        always writes the probabilities (a scratch [K,H,W] when they are not wanted), then ``area_filter_first_pass``."""
+        always writes the probabilities (a scratch [K,H,W] when they are not wanted), then ``area_filter_first_pass``.  ``min_region``
+        is not applied here (the tails call this and sieve their whole group): a caller who post-processes logits itself follows with
+        ``sieve(labels)``, as the drop-in classes do."""
         if self.area_thd is not None:
             probs, labels = self.area_filter_first_pass(*ops.postprocess(seg_logits, self.query_idx, self.num_classes, self.logit_scale, 0.0,
                                                                          self.bg_idx, True))

@@ -130,9 +130,16 @@ class _HipSegmentorBase(_Base):
                slide_crop, cls_token_lambda, bg_idx, apply_sim_feat_up, sim_feat_up_cfg, global_debias_factor=0.0,
                checkpoint=None, text_features=None, text_encoder: Optional[Callable] = None, precision="f16x2",
                synthetic_ok=False, tiles_per_launch=None, jbu_checkpoint_ok=True, tokenizer: Optional[Callable] = None, tile_group=None,
-               label_head="auto", prob_head="auto", pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas", area_thd=None):
+               label_head="auto", prob_head="auto", pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas", area_thd=None,
+               min_region=None, region_connectivity=4, region_fill="neighbour"):
         from . import ops
-        from .pipeline import AREA_TILE_GROUP, LABEL_HEADS, PAMR_TILE_GROUP, PROB_HEADS, RESIZE_HEADS
+        from .pipeline import AREA_TILE_GROUP, LABEL_HEADS, PAMR_TILE_GROUP, PROB_HEADS, RESIZE_HEADS, SIEVE_TILE_GROUP
+        # min_region (None = off): the last step on the final labels of predict / predict_many / evaluate -- connected regions of fewer
+        # than min_region pixels are sieved out on the device (SegPipeline; the definition: include/segearth_hip.h)
+        _, self.region_connectivity, self.region_fill = ops.sieve_args(1 if min_region is None else min_region, region_connectivity, region_fill)
+        self.min_region = min_region
+        if min_region is not None and tile_group is not None:
+            raise ValueError(SIEVE_TILE_GROUP)
         # area_thd (the upstream option name; None = off): per image, a class that wins at most this share of the non-background pixels is
         # removed and its pixels go to the best remaining class (SegPipeline; the definition: include/segearth_hip.h).  The background
         # class is always kept, so 0 <= bg_idx < the number of classes is required (checked below, once the class file is read).
@@ -272,7 +279,8 @@ class _HipSegmentorBase(_Base):
                            layer_fusion_lambda=getattr(self, "layer_fusion_lambda", 0.5), label_head=getattr(self, "label_head", "auto"),
                            prob_head=getattr(self, "prob_head", "auto"), pamr_steps=getattr(self, "pamr_steps", 0),
                            pamr_stride=getattr(self, "pamr_stride", (8, 16)), resize_head=getattr(self, "resize_head", "canvas"),
-                           area_thd=getattr(self, "area_thd", None))
+                           area_thd=getattr(self, "area_thd", None), min_region=getattr(self, "min_region", None),
+                           region_connectivity=getattr(self, "region_connectivity", 4), region_fill=getattr(self, "region_fill", "neighbour"))
 
     def forward_feature(self, img, logit_size=None, tile_h_idx=None, tile_w_idx=None):
         """Reference segmentor.py:286-392.  img [B,3,H,W] -> logits [B,Q,h,w]."""
@@ -303,7 +311,10 @@ class _HipSegmentorBase(_Base):
         per-image class areas decide which classes stay (sg_class_area, sg_area_keep: on the device, no host synchronisation), and
         ``seg_logits`` hold the probabilities with the dropped planes zeroed, ``pred_sem_seg`` the best kept class (sg_area_filter_probs).
         Labels alone on the fused label head need no probability planes for it (sg_area_relabel); labels alone on the canvas route
-        write the probabilities into a scratch [K,H,W] first -- the fused head is the memory-lean way."""
+        write the probabilities into a scratch [K,H,W] first -- the fused head is the memory-lean way.
+        With ``min_region`` set the connected regions of fewer than ``min_region`` pixels are sieved out of the final labels (sg_sieve,
+        after prob_thd and area_thd, at ``ori_shape``, whatever route the tail took): ``pred_sem_seg`` holds the sieved labels,
+        ``seg_logits`` are left as they are."""
         if data_samples is not None:
             batch_img_metas = [data_sample.metainfo for data_sample in data_samples]
         else:
@@ -357,7 +368,7 @@ class _HipSegmentorBase(_Base):
         per flush group, no canvas); otherwise the canvas is stitched, resized and post-processed.
         With ``area_thd`` set every flush group decides twice (``predict``; SegPipeline.label_groups): one launch per step and group,
         labels alone on the fused label head through sg_area_relabel_multi with no probability planes, ``resize_head="fused"`` on the
-        canvas route."""
+        canvas route.  With ``min_region`` set the labels of every flush group are sieved by one sg_sieve call (``predict``)."""
         if ori_shapes is not None and data_samples is not None:
             raise ValueError("predict_many: ori_shapes goes with data_samples=None; data samples carry their own ori_shape")
         batch = torch.is_tensor(inputs)
@@ -374,7 +385,7 @@ class _HipSegmentorBase(_Base):
                 for i in range(n):
                     size = tuple(imgs[i].shape[-2:]) if ori_shapes[i] is None else tuple(ori_shapes[i])
                     lg = pipe.refine(pipe.forward_feature(imgs[i][None], size)[0].float().contiguous(), imgs[i])
-                    out.append(pipe.postprocess(lg, want_probs=False)[1])
+                    out.append(pipe.sieve(pipe.postprocess(lg, want_probs=False)[1]))
                 return out
             if data_samples is None:
                 return [self.predict(imgs[i][None], None) for i in range(n)]
@@ -402,11 +413,13 @@ class _HipSegmentorBase(_Base):
         (stitch, resize, PAMR, post-process) and ``ops.topk_from_probs`` sorts its probabilities -- except that with
         ``resize_head="fused"`` and no PAMR another ``ori_shape`` runs sg_topk_head_resized_multi, one launch per flush group and no
         canvas.  ``tile_group`` sharding is refused."""
-        from .pipeline import AREA_TOPK, TOPK_TILE_GROUP
+        from .pipeline import AREA_TOPK, SIEVE_TOPK, TOPK_TILE_GROUP
         if getattr(self, "tile_group", None) is not None:
             raise ValueError(TOPK_TILE_GROUP)
         if getattr(self, "area_thd", None) is not None:
             raise ValueError(AREA_TOPK)
+        if getattr(self, "min_region", None) is not None:
+            raise ValueError(SIEVE_TOPK)
         batch = torch.is_tensor(inputs)
         imgs = inputs.float() if batch else [x[0].float() if x.dim() == 4 else x.float() for x in inputs]
         n = imgs.shape[0] if batch else len(imgs)
@@ -450,7 +463,8 @@ class _HipSegmentorBase(_Base):
         ``at_gt_size``: a truth map of any size is accepted; its shape becomes that image's ``ori_shape`` and the labels are produced at
         that size and counted (the configs that resize the image before inference and score at the original size).  The route follows
         ``resize_head``: sg_label_head_resized_multi with "fused", stitch + resize + post-process with "canvas".
-        With ``area_thd`` set the labels that are counted are the filtered ones (SegPipeline.label_groups)."""
+        With ``area_thd`` set the labels that are counted are the filtered ones (SegPipeline.label_groups); with ``min_region`` set,
+        the sieved ones."""
         from .metrics import IoUMetric
         if getattr(self, "tile_group", None) is not None:
             raise ValueError("evaluate: tile_group sharding is not supported (each rank would have to count its own band against the "
@@ -507,6 +521,7 @@ class _HipSegmentorBase(_Base):
         batch_size = seg_logits.shape[0]
         for i in range(batch_size):
             probs, seg_pred = pipe.postprocess(seg_logits[i].float())
+            seg_pred = pipe.sieve(seg_pred)                                  # min_region: the last step on the labels; seg_logits stay
             if data_samples is None:
                 return seg_pred
             self._fill_sample(data_samples[i], probs, seg_pred, i)
@@ -578,7 +593,8 @@ class SegmentorEx(_HipSegmentorBase):
                  # -- drop-in extras (see module docstring) --
                  checkpoint=None, text_features=None, text_encoder=None, precision="f16x2", synthetic_ok=False, tiles_per_launch=None,
                  tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, pack_images=False, label_head="auto", prob_head="auto",
-                 pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas", area_thd=None):
+                 pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas", area_thd=None, min_region=None, region_connectivity=4,
+                 region_fill="neighbour"):
         data_preprocessor = SegDataPreProcessor(mean=list(Wt.PIXEL_MEAN), std=list(Wt.PIXEL_STD), bgr_to_rgb=True)
         super().__init__(data_preprocessor=data_preprocessor)
         if model_type == "GEM":
@@ -588,7 +604,8 @@ class SegmentorEx(_HipSegmentorBase):
                              slide_crop, cls_token_lambda, bg_idx, _to_bool(apply_sim_feat_up), sim_feat_up_cfg, global_debias_factor,
                              checkpoint, text_features, text_encoder, precision, synthetic_ok, tiles_per_launch, tokenizer=tokenizer,
                              tile_group=tile_group, label_head=label_head, prob_head=prob_head, pamr_steps=pamr_steps, pamr_stride=pamr_stride,
-                             resize_head=resize_head, area_thd=area_thd)
+                             resize_head=resize_head, area_thd=area_thd, min_region=min_region, region_connectivity=region_connectivity,
+                             region_fill=region_fill)
         # opt-in extra: kwargs of the reference's CrossTileFusion (cross_tile_fusion.py:24-60), which the reference never calls (R2)
         self.cross_tile_fusion_cfg = cross_tile_fusion_cfg
         self.apply_ctd = _to_bool(apply_ctd)                                # segmentor.py:184-194, 339-365: DBSCAN + cluster debias, on the device here
@@ -624,7 +641,7 @@ class Segmentor(_HipSegmentorBase):
                  checkpoint=None, text_features=None, text_encoder=None, precision="f16x2", synthetic_ok=False, tiles_per_launch=None,
                  tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, apply_outlier_suppression=False, outlier_suppression_cfg=None,
                  pack_images=False, label_head="auto", prob_head="auto", pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas",
-                 area_thd=None):
+                 area_thd=None, min_region=None, region_connectivity=4, region_fill="neighbour"):
         data_preprocessor = SegDataPreProcessor(mean=list(Wt.PIXEL_MEAN), std=list(Wt.PIXEL_STD), bgr_to_rgb=True)
         super().__init__(data_preprocessor=data_preprocessor)
         if model_type == "GEM" and cls_token_lambda != 0:
@@ -633,7 +650,8 @@ class Segmentor(_HipSegmentorBase):
                     slide_crop, cls_token_lambda, bg_idx, apply_sim_feat_up, sim_feat_up_cfg, 0.0,
                     checkpoint, text_features, text_encoder, precision, synthetic_ok, tiles_per_launch, tokenizer=tokenizer,
                     tile_group=tile_group, label_head=label_head, prob_head=prob_head, pamr_steps=pamr_steps, pamr_stride=pamr_stride,
-                             resize_head=resize_head, area_thd=area_thd)
+                             resize_head=resize_head, area_thd=area_thd, min_region=min_region, region_connectivity=region_connectivity,
+                             region_fill=region_fill)
         # opt-in extra: kwargs of the reference's CrossTileFusion (cross_tile_fusion.py:24-60), which the reference never calls (R2)
         self.cross_tile_fusion_cfg = cross_tile_fusion_cfg
         self.output_cls_token = cls_token_lambda != 0

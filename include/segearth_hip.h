@@ -750,6 +750,42 @@ int sg_area_relabel_multi(const float* tile_logits, const int32_t* windows, cons
                           const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx, const int32_t* keep,
                           const float* conf, int64_t* labels, sg_stream s);
 
+/* ---- min_region: sieve small connected regions out of a label map ---------------------------------------------------------------
+ * The spatial clean-up that follows prob_thd and area_thd: skimage's remove_small_objects (fill "bg") and GDAL's sieve (fill
+ * "neighbour"), on the final labels.
+ * Input.  labels int64 [H,W]; any int64 value is a label.  Two pixels belong to the same *region* when they hold the same label and are
+ *   linked by a chain of such pixels under the chosen connectivity: 4 (edge neighbours) or 8 (edge and corner neighbours).  A region's
+ *   *area* is its pixel count, its *root* the smallest raster index y*W + x among its pixels.  min_region is an integer >= 1; a region is
+ *   *small* when area < min_region and *kept* otherwise.  min_region = 1 changes nothing: the output holds the input bytes.
+ * SG_SIEVE_FILL_BG (remove small objects).  Every small region whose label is not bg_idx becomes bg_idx.  Regions labelled bg_idx are
+ *   never changed.
+ * SG_SIEVE_FILL_NEIGHBOUR (sieve).  Every small region is sieved, background ones included: it takes the label of the kept region
+ *   adjacent to it (same connectivity as the regions) that has the largest area; ties on area go to the smaller root.  A small region
+ *   with no adjacent kept region becomes bg_idx.  There is ONE pass over the regions of the input and no iteration: a sieved region may
+ *   take the label of a kept region next to another kept region of that label, or several small neighbours may fall to bg_idx together,
+ *   so the result is not necessarily a fixed point -- sieving it again can change it.
+ * The output is int64 [H,W] and may alias the input.  The images of a multi-image call never connect to each other.
+ *   sg_sieve_workspace_bytes  scratch for n_pixels_total pixels (the sum over the images): parent int32 + area int32 per pixel, and best
+ *                             u64 per pixel for SG_SIEVE_FILL_NEIGHBOUR -- 8 or 16 bytes per pixel.  0 for a negative count or an
+ *                             unknown fill.
+ *   sg_sieve                  N >= 1 images in one flat int64 buffer (what the multi-image heads write): image n is image_hw[2n] x
+ *                             image_hw[2n+1] labels at labels + out_offset[n] and is written to labels_out + out_offset[n].  image_hw
+ *                             (int32 [N,2]) and out_offset (int64 [N]) are HOST arrays: they are checked before anything is launched
+ *                             and travel to the kernels as launch arguments, SG_SIEVE_GROUP images per launch sequence (local
+ *                             labelling, border merge, flatten + areas, neighbour choice, apply), so a group of up to SG_SIEVE_GROUP
+ *                             images is served by one sequence, a larger one by one per SG_SIEVE_GROUP, and nothing is copied or
+ *                             synchronised.  workspace: 8-byte aligned device memory.
+ * Integers and integer atomics only: byte-identical across repeats and launch shapes.  Nothing visits the host.
+ * Refused with SG_ERR_INVALID before any device work: a null pointer, min_region < 1, a connectivity other than 4 or 8, an unknown fill,
+ * N < 1, an image of non-positive size or of 2^31 or more pixels, a negative out_offset, a misaligned buffer, a workspace that is too
+ * small. */
+#define SG_SIEVE_FILL_BG 0
+#define SG_SIEVE_FILL_NEIGHBOUR 1
+#define SG_SIEVE_GROUP 64
+size_t sg_sieve_workspace_bytes(int64_t n_pixels_total, int fill);
+int sg_sieve(const int64_t* labels, int64_t* labels_out, const int32_t* image_hw, const int64_t* out_offset, int N, int64_t min_region,
+             int connectivity, int fill, int64_t bg_idx, void* workspace, size_t workspace_bytes, sg_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
