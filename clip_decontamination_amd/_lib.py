@@ -85,6 +85,10 @@ SIGNATURES = {
     "sg_postprocess_wide": (I, [P, P, I, I, I, I, F, F, I, P, P, P]),
     "sg_label_head": (I, [P, P, I, I, I, I, I, I, I, I, I, I, P, I, F, F, I, P, P, P]),
     "sg_label_head_multi": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, I, L, L, P, I, F, F, I, P, P, P]),
+    "sg_stitch_blend": (I, [P, P, I, I, I, I, I, I, I, I, I, I, P, P, I, P]),
+    "sg_stitch_blend_multi": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, I, L, L, P, P, I, P]),
+    "sg_label_head_blend": (I, [P, P, I, I, I, I, I, I, I, I, I, I, P, I, F, F, I, P, P, P, I, P]),
+    "sg_label_head_blend_multi": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, I, L, L, P, I, F, F, I, P, P, P, I, P]),
     "sg_prob_head": (I, [P, P, I, I, I, I, I, I, I, I, I, I, P, I, F, F, I, P, P, P]),
     "sg_prob_head_multi": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, I, L, L, P, I, F, F, I, P, P, P]),
     "sg_topk_head": (I, [P, P, I, I, I, I, I, I, I, I, I, I, P, I, F, I, P, P, P]),

@@ -275,10 +275,20 @@ __device__ __forceinline__ StitchList stitch_candidates(const int32_t* __restric
 // a run-time loop (every stitch and label-head kernel: their machine code is what it was before the split); NCHUNK > 0 unrolls NCHUNK
 // chunks (Q <= NCHUNK * ST_QC) so that q0 is a constant in every call of the sink and a caller can file the values in statically
 // indexed registers.
-template <int NCHUNK = 0, class Sink>
+//
+// BLEND (sg_stitch_blend, include/segearth_hip.h): every covering tile enters with the weight w = ramp[min(dy, L-1)] * ramp[min(dx, L-1)]
+// of the pixel's distance to the tile's own window edges, acc = fma(w, u, acc) with u the unweighted form's value, and the sink gets the
+// sum of the weights where the unweighted form hands it the count.  The row weight is wave-uniform (y is, and so is the tile) and is
+// read with a scalar index; the column weight is one load per lane.  The table is read through the cache, not staged in LDS: a block
+// of 64 x 4 pixels touches at most 68 of its entries per tile, they are shared by every block of the launch (1 KiB at the default
+// R = 256, 8 KiB at most), and staging would cost every block a barrier and up to SG_BLEND_MAX_RAMP loads for those few reads.
+// With BLEND = false nothing of this is compiled: the unweighted instantiations are what they were.
+struct StitchRamp { const float* r = nullptr; int last = 0; };   // the table and L - 1
+template <int NCHUNK = 0, bool BLEND = false, class Sink>
 __device__ __forceinline__ void stitch_gather(const StitchList& sl, const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
                                               const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw, int up_h,
-                                              int up_w, int pad_t, int pad_l, int H, int W, int bx0, int by0, Sink&& sink) {
+                                              int up_w, int pad_t, int pad_l, int H, int W, int bx0, int by0, Sink&& sink,
+                                              StitchRamp ramp = {}) {
   const int* s_list = sl.list;
   const int n_cand = sl.n_cand;
   const bool use_list = n_cand <= ST_MAXC;                         // pathological overlap (stride << crop): test every window
@@ -302,10 +312,14 @@ __device__ __forceinline__ void stitch_gather(const StitchList& sl, const float*
       const int y1 = win[t * 4 + 0], y2 = win[t * 4 + 1];
       if (y < y1 || y >= y2) continue;                                 // wave-uniform: the whole wave skips the tile
       const int x1 = win[t * 4 + 2], x2 = win[t * 4 + 3];
+      int dy = 0;
+      if constexpr (BLEND) dy = __builtin_amdgcn_readfirstlane(min(min(y - y1, y2 - 1 - y), ramp.last));   // 0 <= y - y1 < y2 - y1
       if (x < x1 || x >= x2 || x >= W) continue;
       int ya, yb, xa, xb; float wy0, wy1, wx0, wx1;
       bilinear_tap(y - y1 + pad_t, gh, up_h, ya, yb, wy0, wy1);
       bilinear_tap(x - x1 + pad_l, gw, up_w, xa, xb, wx0, wx1);
+      float w = 1.f;
+      if constexpr (BLEND) w = ramp.r[dy] * ramp.r[min(min(x - x1, x2 - 1 - x), ramp.last)];                // 0 <= x - x1 < x2 - x1
       const float* base = tile_logits + ((int64_t)t * Q + q0) * tile_sz;
 #pragma unroll
       for (int k = 0; k < ST_QC; ++k) {
@@ -313,42 +327,54 @@ __device__ __forceinline__ void stitch_gather(const StitchList& sl, const float*
           const float* p = base + (int64_t)k * tile_sz;
           const float top = p[ya * gw + xa] * wx0 + p[ya * gw + xb] * wx1;
           const float bot = p[yb * gw + xa] * wx0 + p[yb * gw + xb] * wx1;
-          acc[k] += top * wy0 + bot * wy1;
+          if constexpr (BLEND) acc[k] = __builtin_fmaf(w, top * wy0 + bot * wy1, acc[k]);
+          else acc[k] += top * wy0 + bot * wy1;
         }
       }
-      cnt += 1.f;
+      cnt += BLEND ? w : 1.f;                                          // the sum of the weights where the unweighted form counts
     }
     sink(x, y, q0, acc, cnt);
   }
 }
 
-template <class Sink>
+template <bool BLEND = false, class Sink>
 __device__ __forceinline__ void stitch_block(const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
                                              const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw, int up_h,
-                                             int up_w, int pad_t, int pad_l, int H, int W, int bx0, int by0, Sink&& sink) {
+                                             int up_w, int pad_t, int pad_l, int H, int W, int bx0, int by0, Sink&& sink,
+                                             StitchRamp ramp = {}) {
   const StitchList sl = stitch_candidates(win, tile_image, img, n_tiles, bx0, by0);
-  stitch_gather(sl, tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, bx0, by0, sink);
+  stitch_gather<0, BLEND>(sl, tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, bx0, by0, sink, ramp);
 }
 
-// The block's stitched values, count-normalised, into the image's canvas [Q,H,W].
+// The block's stitched values, count-normalised (BLEND: divided by the sum of the weights), into the image's canvas [Q,H,W].
+template <bool BLEND = false>
 __device__ __forceinline__ void stitch_canvas_block(const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
                                                     const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw,
                                                     int up_h, int up_w, int pad_t, int pad_l, int H, int W, int bx0, int by0,
-                                                    float* __restrict__ canvas) {
+                                                    float* __restrict__ canvas, StitchRamp ramp = {}) {
   const int64_t plane = (int64_t)H * W;
-  stitch_block(tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, bx0, by0,
+  stitch_block<BLEND>(tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, bx0, by0,
                [&](int x, int y, int q0, const float (&acc)[ST_QC], float cnt) {
                  if (x >= W) return;
 #pragma unroll
                  for (int k = 0; k < ST_QC; ++k)
                    if (q0 + k < Q) canvas[(q0 + k) * plane + (int64_t)y * W + x] = cnt > 0.f ? acc[k] / cnt : 0.f;
-               });
+               }, ramp);
 }
 
 __global__ __launch_bounds__(256) void stitch_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows,
                                                      int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t, int pad_l,
                                                      int H, int W, float* __restrict__ canvas) {
   stitch_canvas_block(tile_logits, windows, nullptr, 0, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, blockIdx.x * 64, blockIdx.y * 4, canvas);
+}
+
+// stitch_kernel with every tile weighted by the ramp of the distance to its own window edges (stitch_gather's BLEND form).
+__global__ __launch_bounds__(256) void stitch_blend_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows,
+                                                           int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t, int pad_l,
+                                                           int H, int W, float* __restrict__ canvas, const float* __restrict__ ramp,
+                                                           int ramp_len) {
+  stitch_canvas_block<true>(tile_logits, windows, nullptr, 0, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, blockIdx.x * 64, blockIdx.y * 4,
+                            canvas, {ramp, ramp_len - 1});
 }
 
 __global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __restrict__ src, int C, int h, int w,
@@ -471,6 +497,22 @@ __global__ __launch_bounds__(256) void stitch_multi_kernel(const float* __restri
                       ib.n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, ib.H, ib.W, ib.bx0, ib.by0, canvases + ib.off);
 }
 
+// stitch_blend_kernel for the tiles of many images (stitch_multi_kernel's descriptors): every canvas is bit-identical to sg_stitch_blend
+// on that image alone.
+__global__ __launch_bounds__(256) void stitch_blend_multi_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows,
+                                                                 const int32_t* __restrict__ tile_image, int T, int Q, int gh, int gw,
+                                                                 int up_h, int up_w, int pad_t, int pad_l,
+                                                                 const int32_t* __restrict__ image_hw, const int32_t* __restrict__ image_tiles,
+                                                                 const int64_t* __restrict__ canvas_offset,
+                                                                 const int64_t* __restrict__ block_prefix, int N, int64_t canvas_elems,
+                                                                 float* __restrict__ canvases, const float* __restrict__ ramp, int ramp_len) {
+  ImageBlock ib;
+  if (!image_block(image_hw, image_tiles, canvas_offset, block_prefix, N, T, Q, canvas_elems, ib)) return;
+  stitch_canvas_block<true>(tile_logits + (int64_t)ib.t_first * Q * gh * gw, windows + (int64_t)ib.t_first * 4, tile_image + ib.t_first,
+                            ib.n, ib.n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, ib.H, ib.W, ib.bx0, ib.by0, canvases + ib.off,
+                            {ramp, ramp_len - 1});
+}
+
 // postprocess_kernel for N canvases, 256 output pixels per block: canvas n [Q,h,w] at canvas_offset[n]; its outputs are
 // labels [H,W] at out_offset[n] and probs [K,H,W] at K * out_offset[n].  When (H,W) != (h,w) the align_corners=False bilinear
 // resize of resize_bilinear_kernel is evaluated per output pixel (no resized canvas is written).  Everything after the load is class_tail,
@@ -535,14 +577,17 @@ __global__ __launch_bounds__(256) void postprocess_multi_kernel(const float* __r
 // softmax is monotone, so the class of the largest class probability is the class of the largest scaled logit; among queries that
 // share that largest value the lowest class index wins (torch.argmax's first maximum).  Queries whose class lies outside [0,K) only
 // take part in the sum, as in postprocess_kernel.  conf = exp(v_best - v_max) / sum = 1 / sum exp(v_q - v_max).
+// BLEND (sg_label_head_blend): the stitched value is stitch_blend_kernel's, acc / the sum of the weights, which the sink receives as cnt;
+// every statement after it is the same.
+template <bool BLEND = false>
 __device__ __forceinline__ void label_head_block(const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
                                                  const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw,
                                                  int up_h, int up_w, int pad_t, int pad_l, int H, int W, int bx0, int by0,
                                                  const int32_t* __restrict__ query_idx, int K, float logit_scale, float prob_thd,
-                                                 int bg_idx, int64_t* __restrict__ labels, float* __restrict__ conf) {
+                                                 int bg_idx, int64_t* __restrict__ labels, float* __restrict__ conf, StitchRamp ramp = {}) {
   float vmax = -INFINITY, sum = 0.f, best = -INFINITY;
   int best_c = 0;
-  stitch_block(tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, bx0, by0,
+  stitch_block<BLEND>(tile_logits, win, tile_image, img, n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, bx0, by0,
                [&](int, int, int q0, float (&acc)[ST_QC], float cnt) {
 #pragma clang fp contract(off)        // the scaled logit is rounded before the subtraction, as postprocess_kernel compiles it
                  float cm = -INFINITY;
@@ -557,7 +602,7 @@ __device__ __forceinline__ void label_head_block(const float* __restrict__ tile_
                      const int c = K == Q ? q0 + k : query_idx[q0 + k];
                      if (c >= 0 && c < K && (acc[k] > best || (acc[k] == best && c < best_c))) { best = acc[k]; best_c = c; }
                    }
-               });
+               }, ramp);
   const int x = bx0 + (threadIdx.x & 63);
   const int y = __builtin_amdgcn_readfirstlane(by0 + (threadIdx.x >> 6));
   if (y >= H || x >= W) return;
@@ -590,6 +635,33 @@ __global__ __launch_bounds__(256) void label_head_multi_kernel(const float* __re
   label_head_block(tile_logits + (int64_t)ib.t_first * Q * gh * gw, windows + (int64_t)ib.t_first * 4, tile_image + ib.t_first, ib.n,
                    ib.n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, ib.H, ib.W, ib.bx0, ib.by0, query_idx, K, logit_scale, prob_thd, bg_idx,
                    labels + ib.off, conf ? conf + ib.off : nullptr);
+}
+
+// label_head_kernel / label_head_multi_kernel over the blended stitch (label_head_block<true>).
+__global__ __launch_bounds__(256) void label_head_blend_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows,
+                                                               int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t, int pad_l,
+                                                               int H, int W, const int32_t* __restrict__ query_idx, int K,
+                                                               float logit_scale, float prob_thd, int bg_idx, int64_t* __restrict__ labels,
+                                                               float* __restrict__ conf, const float* __restrict__ ramp, int ramp_len) {
+  label_head_block<true>(tile_logits, windows, nullptr, 0, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, blockIdx.x * 64, blockIdx.y * 4,
+                         query_idx, K, logit_scale, prob_thd, bg_idx, labels, conf, {ramp, ramp_len - 1});
+}
+
+__global__ __launch_bounds__(256) void label_head_blend_multi_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows,
+                                                                     const int32_t* __restrict__ tile_image, int T, int Q, int gh, int gw,
+                                                                     int up_h, int up_w, int pad_t, int pad_l,
+                                                                     const int32_t* __restrict__ image_hw,
+                                                                     const int32_t* __restrict__ image_tiles,
+                                                                     const int64_t* __restrict__ out_offset,
+                                                                     const int64_t* __restrict__ block_prefix, int N, int64_t out_pixels,
+                                                                     const int32_t* __restrict__ query_idx, int K, float logit_scale,
+                                                                     float prob_thd, int bg_idx, int64_t* __restrict__ labels,
+                                                                     float* __restrict__ conf, const float* __restrict__ ramp, int ramp_len) {
+  ImageBlock ib;
+  if (!image_block(image_hw, image_tiles, out_offset, block_prefix, N, T, 1, out_pixels, ib)) return;
+  label_head_block<true>(tile_logits + (int64_t)ib.t_first * Q * gh * gw, windows + (int64_t)ib.t_first * 4, tile_image + ib.t_first, ib.n,
+                         ib.n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, ib.H, ib.W, ib.bx0, ib.by0, query_idx, K, logit_scale, prob_thd,
+                         bg_idx, labels + ib.off, conf ? conf + ib.off : nullptr, {ramp, ramp_len - 1});
 }
 
 // ---- fused top-k head: stitch -> softmax -> synonym merge -> the k best classes with their probabilities, any Q ------------------------
@@ -1573,6 +1645,84 @@ extern "C" int sg_label_head_multi(const float* tile_logits, const int32_t* wind
   hipLaunchKernelGGL(label_head_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q,
                      gh, gw, up_h, up_w, pad_t, pad_l, image_hw, image_tiles, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale,
                      prob_thd, bg_idx, labels, conf);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+// ---- weighted window blending: the four entries above with a ramp table (include/segearth_hip.h) ------------------------------------------
+// Each repeats its counterpart's checks under its own name, then the table's; the kernels index the table with min(d, ramp_len - 1) and
+// d >= 0, so a table of ramp_len entries is all they read.
+#define SG_REQUIRE_RAMP(name)                                                                                                         \
+  do {                                                                                                                                \
+    SG_REQUIRE(ramp, name ": null ramp");                                                                                             \
+    SG_REQUIRE(ramp_len >= 1 && ramp_len <= SG_BLEND_MAX_RAMP, name ": ramp_len=%d outside [1, %d]", ramp_len, SG_BLEND_MAX_RAMP);   \
+  } while (0)
+
+extern "C" int sg_stitch_blend(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w,
+                               int pad_t, int pad_l, int H, int W, float* canvas, const float* ramp, int ramp_len, sg_stream s) {
+  SG_REQUIRE(tile_logits && windows && canvas, "sg_stitch_blend: null pointer");
+  SG_REQUIRE_RAMP("sg_stitch_blend");
+  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && H > 0 && W > 0, "sg_stitch_blend: bad shape");
+  SG_REQUIRE(cdiv(H, 4) < 65536, "sg_stitch_blend: canvas too tall for one launch");
+  hipLaunchKernelGGL(stitch_blend_kernel, dim3((unsigned)cdiv(W, 64), (unsigned)cdiv(H, 4)), dim3(256), 0, as_stream(s), tile_logits,
+                     windows, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, canvas, ramp, ramp_len);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_stitch_blend_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh,
+                                     int gw, int up_h, int up_w, int pad_t, int pad_l, const int32_t* image_hw, const int32_t* image_tiles,
+                                     const int64_t* canvas_offset, const int64_t* block_prefix, int N, int64_t total_blocks,
+                                     int64_t canvas_elems, float* canvases, const float* ramp, int ramp_len, sg_stream s) {
+  SG_REQUIRE(tile_logits && windows && tile_image && image_hw && image_tiles && canvas_offset && block_prefix && canvases,
+             "sg_stitch_blend_multi: null pointer");
+  SG_REQUIRE_RAMP("sg_stitch_blend_multi");
+  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && N > 0 && N <= T,
+             "sg_stitch_blend_multi: bad shape T=%d Q=%d gh=%d gw=%d N=%d", T, Q, gh, gw, N);
+  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "sg_stitch_blend_multi: total_blocks=%lld outside (0, 2^31)",
+             (long long)total_blocks);
+  SG_REQUIRE(canvas_elems >= Q, "sg_stitch_blend_multi: canvas_elems=%lld holds no canvas", (long long)canvas_elems);
+  hipLaunchKernelGGL(stitch_blend_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q,
+                     gh, gw, up_h, up_w, pad_t, pad_l, image_hw, image_tiles, canvas_offset, block_prefix, N, canvas_elems, canvases, ramp,
+                     ramp_len);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_label_head_blend(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w,
+                                   int pad_t, int pad_l, int H, int W, const int32_t* query_idx, int K, float logit_scale, float prob_thd,
+                                   int bg_idx, int64_t* labels, float* conf, const float* ramp, int ramp_len, sg_stream s) {
+  SG_REQUIRE(tile_logits && windows && query_idx && labels, "sg_label_head_blend: null pointer");
+  SG_REQUIRE_RAMP("sg_label_head_blend");
+  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && H > 0 && W > 0,
+             "sg_label_head_blend: bad shape T=%d Q=%d gh=%d gw=%d up=%dx%d H=%d W=%d", T, Q, gh, gw, up_h, up_w, H, W);
+  SG_REQUIRE(K > 0 && K <= Q, "sg_label_head_blend: K=%d must lie in [1, Q=%d]", K, Q);
+  SG_REQUIRE(cdiv(H, 4) < 65536, "sg_label_head_blend: canvas too tall for one launch");
+  hipLaunchKernelGGL(label_head_blend_kernel, dim3((unsigned)cdiv(W, 64), (unsigned)cdiv(H, 4)), dim3(256), 0, as_stream(s), tile_logits,
+                     windows, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, query_idx, K, logit_scale, prob_thd, bg_idx, labels, conf, ramp,
+                     ramp_len);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_label_head_blend_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh,
+                                         int gw, int up_h, int up_w, int pad_t, int pad_l, const int32_t* image_hw,
+                                         const int32_t* image_tiles, const int64_t* out_offset, const int64_t* block_prefix, int N,
+                                         int64_t total_blocks, int64_t out_pixels, const int32_t* query_idx, int K, float logit_scale,
+                                         float prob_thd, int bg_idx, int64_t* labels, float* conf, const float* ramp, int ramp_len,
+                                         sg_stream s) {
+  SG_REQUIRE(tile_logits && windows && tile_image && image_hw && image_tiles && out_offset && block_prefix && query_idx && labels,
+             "sg_label_head_blend_multi: null pointer");
+  SG_REQUIRE_RAMP("sg_label_head_blend_multi");
+  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && N > 0 && N <= T,
+             "sg_label_head_blend_multi: bad shape T=%d Q=%d gh=%d gw=%d N=%d", T, Q, gh, gw, N);
+  SG_REQUIRE(K > 0 && K <= Q, "sg_label_head_blend_multi: K=%d must lie in [1, Q=%d]", K, Q);
+  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "sg_label_head_blend_multi: total_blocks=%lld outside (0, 2^31)",
+             (long long)total_blocks);
+  SG_REQUIRE(out_pixels > 0, "sg_label_head_blend_multi: out_pixels=%lld holds no image", (long long)out_pixels);
+  hipLaunchKernelGGL(label_head_blend_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image,
+                     T, Q, gh, gw, up_h, up_w, pad_t, pad_l, image_hw, image_tiles, out_offset, block_prefix, N, out_pixels, query_idx, K,
+                     logit_scale, prob_thd, bg_idx, labels, conf, ramp, ramp_len);
   SG_LAUNCH_CHECK();
   return SG_OK;
 }

@@ -423,6 +423,116 @@ def label_head_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, 
     return lab, labels
 
 
+BLEND_KINDS = ("uniform", "linear", "hann")
+BLEND_MAX_RAMP = 2048                                                    # SG_BLEND_MAX_RAMP (include/segearth_hip.h)
+_BLEND_TABLES: dict = {}                                                 # (kind, R, device) -> the device table
+
+
+def blend_args(blend, blend_ramp=None):
+    """The ``blend`` / ``blend_ramp`` options checked -> (blend, blend_ramp): ``blend`` one of BLEND_KINDS, ``blend_ramp`` None (the
+    full window: half the tile's smaller side, resolved where the tile size is known) or an integer in [1, BLEND_MAX_RAMP - 1]."""
+    if blend not in BLEND_KINDS:
+        raise ValueError(f"blend must be one of {BLEND_KINDS}, got {blend!r}")
+    if blend_ramp is None:
+        return blend, None
+    import numbers
+    if isinstance(blend_ramp, bool) or not isinstance(blend_ramp, numbers.Integral) or not 1 <= blend_ramp <= BLEND_MAX_RAMP - 1:
+        raise ValueError(f"blend_ramp must be None or an integer in [1, {BLEND_MAX_RAMP - 1}], got {blend_ramp!r}")
+    return blend, int(blend_ramp)
+
+
+def blend_ramp(kind: str, R: int) -> torch.Tensor:
+    """The ramp table of sg_stitch_blend on the host, f32 [R + 1]: r[d] = (d + 0.5) / R ("linear") or sin^2(pi/2 (d + 0.5) / R) ("hann")
+    for d < R and r[R] = 1 exactly, computed in float64 and rounded once.  "uniform": the one entry 1.0, the plain mean."""
+    import math
+    kind, R = blend_args(kind, R)
+    if kind == "uniform":
+        return torch.ones(1, dtype=torch.float32)
+    ramp = [(d + 0.5) / R for d in range(R)]
+    if kind == "hann":
+        ramp = [math.sin(0.5 * math.pi * v) ** 2 for v in ramp]
+    return torch.tensor(ramp + [1.0], dtype=torch.float64).to(torch.float32)
+
+
+def blend_table(kind: str, R: int, device) -> torch.Tensor:
+    """``blend_ramp(kind, R)`` on ``device``, built once per (kind, R, device)."""
+    key = (kind, int(R), str(torch.device(device)))
+    if key not in _BLEND_TABLES:
+        _BLEND_TABLES[key] = blend_ramp(kind, R).to(device)
+    return _BLEND_TABLES[key]
+
+
+def _ramp_arg(what, ramp, device):
+    """A caller's ramp tensor as the entry takes it -> (f32 table on ``device``, its length)."""
+    ramp = _f32(ramp).to(device).reshape(-1)
+    if not 1 <= int(ramp.numel()) <= BLEND_MAX_RAMP:
+        raise ValueError(f"{what}: a ramp of {ramp.numel()} entries, must be 1 .. {BLEND_MAX_RAMP}")
+    return ramp, int(ramp.numel())
+
+
+@on_tensor_device
+def stitch_blend(tile_logits, windows, up_hw, pad_tl, canvas_hw, ramp):
+    """sg_stitch_blend: ``stitch`` with every tile weighted by ``ramp`` (f32 [L], ``blend_ramp``) of the pixel's distance to the tile's
+    own window edges and divided by the sum of the weights -> canvas [Q,H,W]."""
+    lib = _lib.load()
+    tile_logits = _f32(tile_logits)
+    windows = windows.to(device=tile_logits.device, dtype=torch.int32).contiguous()
+    _require_gpu(tile_logits)
+    T, Q, gh, gw = tile_logits.shape
+    H, W = canvas_hw
+    ramp, L = _ramp_arg("stitch_blend", ramp, tile_logits.device)
+    canvas = torch.empty(Q, H, W, dtype=torch.float32, device=tile_logits.device)
+    check(lib.sg_stitch_blend(ptr(tile_logits), ptr(windows), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1], H, W, ptr(canvas),
+                              ptr(ramp), L, stream_ptr()), "sg_stitch_blend")
+    return canvas
+
+
+@on_tensor_device
+def stitch_blend_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, ramp):
+    """sg_stitch_blend_multi: ``stitch_multi`` with the weights of ``stitch_blend``; the same results."""
+    lib = _lib.load()
+    Q = tile_logits.shape[1]
+    dev, lead, _, pix, hold = _multi_args("stitch_blend_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, planes=Q)
+    ramp, L = _ramp_arg("stitch_blend_multi", ramp, dev)
+    canvases = torch.empty(Q * pix[-1], dtype=torch.float32, device=dev)
+    check(lib.sg_stitch_blend_multi(*lead, canvases.numel(), ptr(canvases), ptr(ramp), L, stream_ptr()), "sg_stitch_blend_multi")
+    return canvases, flat_views(canvases, Q, image_hw)
+
+
+@on_tensor_device
+def label_head_blend(tile_logits, windows, up_hw, pad_tl, canvas_hw, query_idx, num_classes: int, logit_scale: float, prob_thd: float,
+                     bg_idx: int, ramp, want_conf: bool = False):
+    """sg_label_head_blend: ``label_head`` on the blended stitch (``stitch_blend``'s value per pixel and query); the same results."""
+    lib = _lib.load()
+    dev, lead, qi, hold = _tile_args("label_head_blend", tile_logits, windows, up_hw, pad_tl, query_idx)
+    H, W = canvas_hw
+    ramp, L = _ramp_arg("label_head_blend", ramp, dev)
+    labels = torch.empty(1, H, W, dtype=torch.int64, device=dev)
+    conf = torch.empty(H, W, dtype=torch.float32, device=dev) if want_conf else None
+    check(lib.sg_label_head_blend(*lead, H, W, ptr(qi), int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx), ptr(labels),
+                                  ptr(conf), ptr(ramp), L, stream_ptr()), "sg_label_head_blend")
+    return (labels, conf) if want_conf else labels
+
+
+@on_tensor_device
+def label_head_blend_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, query_idx, num_classes: int,
+                           logit_scale: float, prob_thd: float, bg_idx: int, ramp, want_conf: bool = False, flat_conf: bool = False):
+    """sg_label_head_blend_multi: ``label_head_multi`` on the blended stitch; the same results, ``label_head_blend`` per image byte for
+    byte."""
+    lib = _lib.load()
+    dev, lead, qi, pix, hold = _multi_args("label_head_blend_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles,
+                                           query_idx)
+    ramp, L = _ramp_arg("label_head_blend_multi", ramp, dev)
+    labels = torch.empty(pix[-1], dtype=torch.int64, device=dev)
+    conf = torch.empty(pix[-1], dtype=torch.float32, device=dev) if want_conf else None
+    check(lib.sg_label_head_blend_multi(*lead, pix[-1], ptr(qi), int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx),
+                                        ptr(labels), ptr(conf), ptr(ramp), L, stream_ptr()), "sg_label_head_blend_multi")
+    lab = flat_views(labels, 1, image_hw)
+    if want_conf:
+        return lab, labels, (conf if flat_conf else [c[0] for c in flat_views(conf, 1, image_hw)])
+    return lab, labels
+
+
 @on_tensor_device
 def prob_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, query_idx, num_classes: int, logit_scale: float, prob_thd: float, bg_idx: int):
     """sg_prob_head: ``stitch`` + ``postprocess`` without the canvas, for any Q.  Arguments as ``label_head``

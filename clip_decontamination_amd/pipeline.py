@@ -407,6 +407,7 @@ class SegPipeline:
     area_thd = None                           # area_thd off likewise
     min_region, region_connectivity, region_fill = None, 4, "neighbour"      # the sieve off likewise
     label_head, prob_head, resize_head = "auto", "auto", "canvas"
+    blend, blend_ramp = "uniform", None       # weighted window blending off likewise
     apply_ctd, apply_layer_fusion, layer_fusion_lambda = False, False, 0.5
     cross_tile_fusion = tile_group = upsampler = None
 
@@ -416,7 +417,14 @@ class SegPipeline:
                  upsampler=None, tiles_per_launch: int = 32, cross_tile_fusion: Optional[dict] = None, apply_ctd: bool = False,
                  tile_group=None, apply_layer_fusion: bool = False, layer_fusion_lambda: float = 0.5, label_head: str = "auto",
                  prob_head: str = "auto", pamr_steps: int = 0, pamr_stride=(8, 16), resize_head: str = "canvas", area_thd=None,
-                 min_region=None, region_connectivity: int = 4, region_fill: str = "neighbour"):
+                 min_region=None, region_connectivity: int = 4, region_fill: str = "neighbour", blend: str = "uniform", blend_ramp=None):
+        # blend ("uniform" = off, and then no call changes route, launches or bytes): overlapping windows are combined by a weighted mean,
+        # each tile weighted by a ramp ("linear" or "hann", ops.blend_ramp) of the pixel's distance to the tile's own window edges
+        # (sg_stitch_blend; the definition: include/segearth_hip.h), which takes the step out of the stitched logits where a window starts
+        # or ends.  ``blend_ramp``: the ramp's length R in pixels, None = the full window, max(1, min(tile_h, tile_w) // 2), resolved per
+        # tile size (``_ramp``).  Labels only take sg_label_head_blend where the unweighted call takes sg_label_head (not with area_thd,
+        # whose second pass gathers unweighted); everything else takes the canvas route with sg_stitch_blend in place of sg_stitch.
+        self.blend, self.blend_ramp = ops.blend_args(blend, blend_ramp)
         # min_region (None = off, and then no call changes route, launches or bytes): the connected regions of the FINAL labels -- after
         # prob_thd and area_thd, at ori_shape, whatever route the tail took -- that have fewer than min_region pixels are sieved out
         # (sg_sieve; the definition: include/segearth_hip.h): region_fill "neighbour" gives them the label of their largest adjacent kept
@@ -481,8 +489,27 @@ class SegPipeline:
             ops.area_args("area_thd", self.num_classes, self.bg_idx, self.area_thd)
         self._check_sharding(tile_group is not None)
 
-    def _stitch(self, tile_logits, windows, up_hw, pad_tl, canvas_hw):
+    def _stitch(self, tile_logits, windows, up_hw, pad_tl, canvas_hw, ramp=None):
+        if ramp is not None:
+            return ops.stitch_blend(tile_logits, windows, up_hw, pad_tl, canvas_hw, ramp)
         return ops.stitch(tile_logits, windows, up_hw, pad_tl, canvas_hw)
+
+    def _stitched(self, tile_hw, *args):
+        """``_stitch`` of windows of ``tile_hw``, blended when ``blend`` is on (the weights depend on the position inside a tile's own
+        window, so a band's shifted windows give the whole canvas's rows)."""
+        ramp = self._ramp(tile_hw)
+        return self._stitch(*args) if ramp is None else self._stitch(*args, ramp)
+
+    def _ramp(self, tile_hw):
+        """The device ramp table of ``blend`` for windows of ``tile_hw`` (R = ``blend_ramp``, or half the window's smaller side); None
+        with blend = "uniform": every caller then makes the unweighted call.  A caller that only has the tile logits and windows on the
+        device passes None for ``tile_hw`` and must have set ``blend_ramp``."""
+        if self.blend == "uniform":
+            return None
+        if self.blend_ramp is None and tile_hw is None:
+            raise ValueError("blend: the window size is not known here, so blend_ramp=None cannot be resolved; pass tile_hw= or set blend_ramp")
+        R = self.blend_ramp if self.blend_ramp is not None else max(1, min(int(tile_hw[0]), int(tile_hw[1])) // 2)
+        return ops.blend_table(self.blend, R, self.device)
 
     # -- which tail runs: one decision (DESIGN.md section 5 'Route table') ----------------------------------------------
     def fused_label_head(self) -> bool:
@@ -538,14 +565,15 @@ class SegPipeline:
         """THE route decision.  ``want``: "labels", "probs" or "topk" (then ``k``); ``differs``: some ``ori_shape`` is another size than
         its image; ``given``: some ``ori_shape`` is given at all -- the packed labels-only tail takes the fused head only when none is,
         an ``ori_shape`` equal to the image's size keeps the canvas there."""
+        blended = self.blend != "uniform"      # only the label head has a blended form, and sg_area_relabel gathers unweighted
         if self.pamr_steps == 0:
-            if want == "topk" and not differs:
+            if want == "topk" and not differs and not blended:
                 return TailRoute(HEAD, 8 * k)
-            if want == "probs" and not differs and self.fused_prob_head():
+            if want == "probs" and not differs and not blended and self.fused_prob_head():
                 return TailRoute(HEAD, 4 * self.num_classes + 8)
-            if want == "labels" and not given and not differs and self.fused_label_head():
+            if want == "labels" and not given and not differs and self.fused_label_head() and not (blended and self.area_thd is not None):
                 return TailRoute(HEAD, 8 if self.area_thd is None else 12)
-            if want != "probs" and differs and self.fused_resize_head():
+            if want != "probs" and differs and not blended and self.fused_resize_head():
                 return TailRoute(RESIZED_HEAD, 8 * k if want == "topk" else 8)
         return TailRoute(CANVAS_MULTI if self.num_queries <= ops.POSTPROCESS_MAX_Q else CANVAS_EACH, self._canvas_bytes())
 
@@ -587,22 +615,27 @@ class SegPipeline:
             ops.sieve_flat(labels.view(-1), hw, self.min_region, self.region_connectivity, self.region_fill, self.bg_idx)
         return labels
 
-    def _image_tail(self, route: str, want: str, k: int, tile_logits, windows, up_hw, pad_tl, canvas_hw, out_hw, guide):
+    def _image_tail(self, route: str, want: str, k: int, tile_logits, windows, up_hw, pad_tl, canvas_hw, out_hw, guide, ramp=None):
         """``_image_tail_unsieved`` and then, with min_region set, the sieve on its labels (top-k is refused with min_region)."""
-        out = self._image_tail_unsieved(route, want, k, tile_logits, windows, up_hw, pad_tl, canvas_hw, out_hw, guide)
+        out = self._image_tail_unsieved(route, want, k, tile_logits, windows, up_hw, pad_tl, canvas_hw, out_hw, guide, ramp)
         if self.min_region is not None and want != "topk":
             self.sieve(out[1] if want == "probs" else out)
         return out
 
-    def _image_tail_unsieved(self, route: str, want: str, k: int, tile_logits, windows, up_hw, pad_tl, canvas_hw, out_hw, guide):
+    def _image_tail_unsieved(self, route: str, want: str, k: int, tile_logits, windows, up_hw, pad_tl, canvas_hw, out_hw, guide, ramp=None):
         """One image's (or one canvas band's) tile logits [T,Q,gh,gw] + windows [T,4] -> labels int64 [1,H,W], (probs f32 [K,H,W],
-        labels) or (classes int32 [k,H,W], probs f32 [k,H,W]) on ``route``, (H, W) = ``out_hw``."""
+        labels) or (classes int32 [k,H,W], probs f32 [k,H,W]) on ``route``, (H, W) = ``out_hw``.  ``ramp``: the table of ``_ramp`` for
+        these tiles (None: the unweighted stitch); ``tail_route`` sends a blended tail to HEAD for plain labels only."""
         args = (tile_logits, windows, up_hw, pad_tl, canvas_hw)
+        if ramp is not None and (route == RESIZED_HEAD or (route == HEAD and (want != "labels" or self.area_thd is not None))):
+            raise ValueError("blend: only the plain label head has a blended form; everything else takes the canvas route")
         if route == RESIZED_HEAD:
             post = (out_hw, self.query_idx, self.num_classes, self.logit_scale)
             return ops.topk_head_resized(*args, *post, k) if want == "topk" else ops.label_head_resized(*args, *post, self.prob_thd, self.bg_idx)
         if route == HEAD:
             post = (self.query_idx, self.num_classes, self.logit_scale)
+            if ramp is not None:
+                return ops.label_head_blend(*args, *post, self.prob_thd, self.bg_idx, ramp)
             if want == "topk":
                 return ops.topk_head(*args, *post, k)
             area = self.area_thd is not None
@@ -614,7 +647,7 @@ class SegPipeline:
                 return ops.label_head(*args, *post, thd, self.bg_idx)
             labels, conf = ops.label_head(*args, *post, thd, self.bg_idx, want_conf=True)
             return ops.area_relabel(*args, *post, self.prob_thd, self.bg_idx, self._area_keep(labels), conf, labels)
-        canvas = self._stitch(*args)                              # stitch -> resize -> PAMR -> post-process
+        canvas = self._stitch(*args) if ramp is None else self._stitch(*args, ramp)      # stitch -> resize -> PAMR -> post-process
         if tuple(out_hw) != tuple(canvas_hw):
             canvas = ops.resize_bilinear(canvas, out_hw)
         if self.pamr_steps > 0:
@@ -626,18 +659,22 @@ class SegPipeline:
             return ops.topk_from_probs(probs, self.query_idx, k)
         return (probs, labels) if want == "probs" else labels
 
-    def labels_from_tiles(self, tile_logits, windows, up_hw, pad_tl, canvas_hw, guide=None):
-        """The labels-only tail of one image or canvas band (a canvas with shifted windows) -> labels int64 [1,H,W]."""
-        return self._image_tail(self.tail_route("labels").route, "labels", 0, tile_logits, windows, up_hw, pad_tl, canvas_hw, canvas_hw, guide)
+    def labels_from_tiles(self, tile_logits, windows, up_hw, pad_tl, canvas_hw, guide=None, tile_hw=None):
+        """The labels-only tail of one image or canvas band (a canvas with shifted windows) -> labels int64 [1,H,W].  ``tile_hw``: the
+        window size, which ``blend`` resolves its ramp from (``_ramp``); the same in the two tails below."""
+        return self._image_tail(self.tail_route("labels").route, "labels", 0, tile_logits, windows, up_hw, pad_tl, canvas_hw, canvas_hw, guide,
+                                self._ramp(tile_hw))
 
-    def probs_from_tiles(self, tile_logits, windows, up_hw, pad_tl, canvas_hw, guide=None):
+    def probs_from_tiles(self, tile_logits, windows, up_hw, pad_tl, canvas_hw, guide=None, tile_hw=None):
         """-> (probs f32 [K,H,W], labels int64 [1,H,W]) at the scene's own size; every route returns the same bytes."""
-        return self._image_tail(self.tail_route("probs").route, "probs", 0, tile_logits, windows, up_hw, pad_tl, canvas_hw, canvas_hw, guide)
+        return self._image_tail(self.tail_route("probs").route, "probs", 0, tile_logits, windows, up_hw, pad_tl, canvas_hw, canvas_hw, guide,
+                                self._ramp(tile_hw))
 
-    def topk_from_tiles(self, tile_logits, windows, up_hw, pad_tl, canvas_hw, k: int, guide=None):
+    def topk_from_tiles(self, tile_logits, windows, up_hw, pad_tl, canvas_hw, k: int, guide=None, tile_hw=None):
         """-> (classes int32 [k,H,W], probs f32 [k,H,W]): the k best classes of every pixel in descending probability."""
         k = self.topk_k(k)
-        return self._image_tail(self.tail_route("topk", k).route, "topk", k, tile_logits, windows, up_hw, pad_tl, canvas_hw, canvas_hw, guide)
+        return self._image_tail(self.tail_route("topk", k).route, "topk", k, tile_logits, windows, up_hw, pad_tl, canvas_hw, canvas_hw, guide,
+                                self._ramp(tile_hw))
 
     def topk_from_logits(self, seg_logits, k: int, guide=None):
         """The canvas route to the k best classes, for logits [Q,H,W] that already exist (whole-image inference): PAMR when on,
@@ -672,6 +709,11 @@ class SegPipeline:
         flat = torch.cat(lab)
         return prb, ops.flat_views(flat, 1, ohw), flat
 
+    def _group_ramp(self, group):
+        """``_ramp`` for a flush group of ``_packed_tiles``: its windows (host tuples) all have the group's one tile size."""
+        y1, y2, x1, x2 = group[2][0]
+        return self._ramp((y2 - y1, x2 - x1))
+
     def _group_tail(self, route: str, want: str, k: int, group, ohw, imgs):
         """``_group_tail_unsieved`` and then, with min_region set, ONE sg_sieve call over the group's flat labels (the label maps are
         views of that buffer)."""
@@ -685,6 +727,7 @@ class SegPipeline:
         (list of probs [k,H,W], list of classes [k,H,W], None).  ``ohw``: the output size per image; ``imgs``: the images (PAMR's guides)."""
         idx, shapes = group[0], group[6]
         args, post = group[1:], (self.query_idx, self.num_classes, self.logit_scale)
+        ramp = self._group_ramp(group)                            # None unless blend is on; tail_route then gives HEAD to plain labels only
         if route == RESIZED_HEAD and ohw == shapes:               # no image of this group differs: what runs without the option
             route = self.tail_route(want, k).route
         if route == RESIZED_HEAD:
@@ -704,11 +747,14 @@ class SegPipeline:
                 if area:
                     self.area_filter_first_pass_multi(probs[0], flat, shapes)
                 return prb, lab, flat
+            if ramp is not None:
+                lab, flat = ops.label_head_blend_multi(*args, *post, thd, self.bg_idx, ramp)
+                return [None] * len(idx), lab, flat
             lab, flat, *conf = ops.label_head_multi(*args, *post, thd, self.bg_idx, want_conf=area, flat_conf=area)
             if area:                                              # 12 bytes per pixel: labels and conf, no canvas, no probability planes
                 ops.area_relabel_multi(*args, *post, self.prob_thd, self.bg_idx, self._area_keep(flat, [h * w for h, w in shapes]), conf[0], flat)
             return [None] * len(idx), lab, flat
-        canvases, views = ops.stitch_multi(*args)
+        canvases, views = ops.stitch_multi(*args) if ramp is None else ops.stitch_blend_multi(*args, ramp)
         if route == CANVAS_MULTI and (self.pamr_steps == 0 or ohw == shapes):
             if self.pamr_steps > 0:                               # PAMR comes after the resize: a group that holds one goes image by image
                 for c, im in zip(views, imgs):
@@ -806,7 +852,7 @@ class SegPipeline:
         if group is None:
             tl = self.tile_logits(scene, wins, tile_hw, grid_of_tiles=grid)
             win_dev = torch.tensor(wins, dtype=torch.int32, device=self.device)
-            canvas = self._stitch(tl, win_dev, up_hw, pad_tl, (H, W))
+            canvas = self._stitched(tile_hw, tl, win_dev, up_hw, pad_tl, (H, W))
         else:
             band, y0, yb = self.sharded_canvas_band(scene, stride, crop, group)
             canvas = self.gather_bands(band, yb, H, group)
@@ -819,7 +865,11 @@ class SegPipeline:
         tiles, w_band, up_hw, pad_tl, hw, y0, yb = self.sharded_band_tiles(scene, stride, crop, group)
         if hw[0] <= 0:
             return tiles.new_zeros((self.num_queries, 0, hw[1])), y0, yb
-        return self._stitch(tiles, w_band, up_hw, pad_tl, hw), y0, yb
+        return self._stitched(self._band_tile_hw(scene, stride, crop), tiles, w_band, up_hw, pad_tl, hw), y0, yb
+
+    def _band_tile_hw(self, scene, stride, crop):
+        """The window size of a scene whose band tiles are at hand (``sharded_band_tiles`` does not return it); only ``blend`` asks."""
+        return None if self.blend == "uniform" else self._geometry(scene, stride, crop)[5]
 
     def sharded_band_tiles(self, scene, stride, crop, group):
         """Tiles partitioned over the ranks of ``group`` -> this rank's band of the canvas, as what the stitch takes: (tile logits of the tiles
@@ -896,10 +946,11 @@ class SegPipeline:
             tl = self.tile_logits(scene, wins, tile_hw, grid_of_tiles=grid)
             win_dev = torch.tensor(wins, dtype=torch.int32, device=self.device)
             out_hw = tuple(int(v) for v in ori_shape) if resize else (H, W)
-            return self._image_tail(self.tail_route(want, k, differs=resize).route, want, k, tl, win_dev, up_hw, pad_tl, (H, W), out_hw, scene)
+            return self._image_tail(self.tail_route(want, k, differs=resize).route, want, k, tl, win_dev, up_hw, pad_tl, (H, W), out_hw, scene,
+                                    self._ramp(tile_hw))
         tiles, w_band, up_hw, pad_tl, hw, y0, yb = self.sharded_band_tiles(scene, stride, crop, group)
         if hw[0] > 0:
-            lab = self.labels_from_tiles(tiles, w_band, up_hw, pad_tl, hw)
+            lab = self.labels_from_tiles(tiles, w_band, up_hw, pad_tl, hw, tile_hw=self._band_tile_hw(scene, stride, crop))
         else:
             lab = torch.empty((1, 0, hw[1]), dtype=torch.int64, device=tiles.device)
         if not gather_labels:
@@ -943,7 +994,8 @@ class SegPipeline:
         """Yields (image indices, flat canvas buffer, its [Q,H,W] views) per flush group: ``_packed_tiles`` and one sg_stitch_multi
         launch."""
         for group in self._packed_tiles(scenes, stride, crop, self._canvas_bytes()):
-            canvases, views = ops.stitch_multi(*group[1:])
+            ramp = self._group_ramp(group)
+            canvases, views = ops.stitch_multi(*group[1:]) if ramp is None else ops.stitch_blend_multi(*group[1:], ramp)
             yield group[0], canvases, views
 
     def _packed_tiles(self, scenes, stride, crop, pixel_bytes):

@@ -131,9 +131,12 @@ class _HipSegmentorBase(_Base):
                checkpoint=None, text_features=None, text_encoder: Optional[Callable] = None, precision="f16x2",
                synthetic_ok=False, tiles_per_launch=None, jbu_checkpoint_ok=True, tokenizer: Optional[Callable] = None, tile_group=None,
                label_head="auto", prob_head="auto", pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas", area_thd=None,
-               min_region=None, region_connectivity=4, region_fill="neighbour"):
+               min_region=None, region_connectivity=4, region_fill="neighbour", blend="uniform", blend_ramp=None):
         from . import ops
         from .pipeline import AREA_TILE_GROUP, LABEL_HEADS, PAMR_TILE_GROUP, PROB_HEADS, RESIZE_HEADS, SIEVE_TILE_GROUP
+        # blend ("uniform" = off) / blend_ramp: overlapping windows combined by a ramp-weighted mean instead of the plain one (SegPipeline;
+        # the definition: include/segearth_hip.h).  Whole-image inference (slide_crop <= 0) has no windows and ignores it.
+        self.blend, self.blend_ramp = ops.blend_args(blend, blend_ramp)
         # min_region (None = off): the last step on the final labels of predict / predict_many / evaluate -- connected regions of fewer
         # than min_region pixels are sieved out on the device (SegPipeline; the definition: include/segearth_hip.h)
         _, self.region_connectivity, self.region_fill = ops.sieve_args(1 if min_region is None else min_region, region_connectivity, region_fill)
@@ -280,7 +283,8 @@ class _HipSegmentorBase(_Base):
                            prob_head=getattr(self, "prob_head", "auto"), pamr_steps=getattr(self, "pamr_steps", 0),
                            pamr_stride=getattr(self, "pamr_stride", (8, 16)), resize_head=getattr(self, "resize_head", "canvas"),
                            area_thd=getattr(self, "area_thd", None), min_region=getattr(self, "min_region", None),
-                           region_connectivity=getattr(self, "region_connectivity", 4), region_fill=getattr(self, "region_fill", "neighbour"))
+                           region_connectivity=getattr(self, "region_connectivity", 4), region_fill=getattr(self, "region_fill", "neighbour"),
+                           blend=getattr(self, "blend", "uniform"), blend_ramp=getattr(self, "blend_ramp", None))
 
     def forward_feature(self, img, logit_size=None, tile_h_idx=None, tile_w_idx=None):
         """Reference segmentor.py:286-392.  img [B,3,H,W] -> logits [B,Q,h,w]."""
@@ -594,7 +598,7 @@ class SegmentorEx(_HipSegmentorBase):
                  checkpoint=None, text_features=None, text_encoder=None, precision="f16x2", synthetic_ok=False, tiles_per_launch=None,
                  tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, pack_images=False, label_head="auto", prob_head="auto",
                  pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas", area_thd=None, min_region=None, region_connectivity=4,
-                 region_fill="neighbour"):
+                 region_fill="neighbour", blend="uniform", blend_ramp=None):
         data_preprocessor = SegDataPreProcessor(mean=list(Wt.PIXEL_MEAN), std=list(Wt.PIXEL_STD), bgr_to_rgb=True)
         super().__init__(data_preprocessor=data_preprocessor)
         if model_type == "GEM":
@@ -605,7 +609,7 @@ class SegmentorEx(_HipSegmentorBase):
                              checkpoint, text_features, text_encoder, precision, synthetic_ok, tiles_per_launch, tokenizer=tokenizer,
                              tile_group=tile_group, label_head=label_head, prob_head=prob_head, pamr_steps=pamr_steps, pamr_stride=pamr_stride,
                              resize_head=resize_head, area_thd=area_thd, min_region=min_region, region_connectivity=region_connectivity,
-                             region_fill=region_fill)
+                             region_fill=region_fill, blend=blend, blend_ramp=blend_ramp)
         # opt-in extra: kwargs of the reference's CrossTileFusion (cross_tile_fusion.py:24-60), which the reference never calls (R2)
         self.cross_tile_fusion_cfg = cross_tile_fusion_cfg
         self.apply_ctd = _to_bool(apply_ctd)                                # segmentor.py:184-194, 339-365: DBSCAN + cluster debias, on the device here
@@ -641,7 +645,7 @@ class Segmentor(_HipSegmentorBase):
                  checkpoint=None, text_features=None, text_encoder=None, precision="f16x2", synthetic_ok=False, tiles_per_launch=None,
                  tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, apply_outlier_suppression=False, outlier_suppression_cfg=None,
                  pack_images=False, label_head="auto", prob_head="auto", pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas",
-                 area_thd=None, min_region=None, region_connectivity=4, region_fill="neighbour"):
+                 area_thd=None, min_region=None, region_connectivity=4, region_fill="neighbour", blend="uniform", blend_ramp=None):
         data_preprocessor = SegDataPreProcessor(mean=list(Wt.PIXEL_MEAN), std=list(Wt.PIXEL_STD), bgr_to_rgb=True)
         super().__init__(data_preprocessor=data_preprocessor)
         if model_type == "GEM" and cls_token_lambda != 0:
@@ -651,7 +655,7 @@ class Segmentor(_HipSegmentorBase):
                     checkpoint, text_features, text_encoder, precision, synthetic_ok, tiles_per_launch, tokenizer=tokenizer,
                     tile_group=tile_group, label_head=label_head, prob_head=prob_head, pamr_steps=pamr_steps, pamr_stride=pamr_stride,
                              resize_head=resize_head, area_thd=area_thd, min_region=min_region, region_connectivity=region_connectivity,
-                             region_fill=region_fill)
+                             region_fill=region_fill, blend=blend, blend_ramp=blend_ramp)
         # opt-in extra: kwargs of the reference's CrossTileFusion (cross_tile_fusion.py:24-60), which the reference never calls (R2)
         self.cross_tile_fusion_cfg = cross_tile_fusion_cfg
         self.output_cls_token = cls_token_lambda != 0

@@ -207,6 +207,37 @@ int sg_cosine_logits_two_plane(const float* tokens, const float* cls, const floa
 int sg_stitch(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw,
               int up_h, int up_w, int pad_t, int pad_l, int H, int W, float* canvas, sg_stream s);
 
+/* ---- weighted window blending: sg_stitch with every tile feathered towards its own window edges -----------------------------------
+ * The ramp is an f32 table r[0 .. L-1] in device memory, L = ramp_len >= 1, every entry finite and > 0.  For a pixel (y, x) inside
+ * window t = (y1, y2, x1, x2):
+ *     dy = min(y - y1, y2 - 1 - y),  dx = min(x - x1, x2 - 1 - x),  w_t = fl32(r[min(dy, L-1)] * r[min(dx, L-1)]).
+ * The distances are taken in the window's own coordinates, so the shifted windows of a canvas band give the weights of the whole
+ * canvas.  With u_t the bilinear value sg_stitch takes from tile t (the same taps, the same expression):
+ *     acc = sum_t w_t u_t over the covering tiles in raster order, each step one fused multiply-add; wsum = sum_t w_t in that order;
+ *     canvas = wsum > 0 ? acc / wsum : 0.
+ * A table of the one entry 1.0f is the uniform mean: byte for byte sg_stitch.  No atomics, every pixel is written once by its own
+ * thread, repeats are byte-identical.  The host builds r[d] = (d + 0.5) / R ("linear") or sin^2(pi/2 (d + 0.5) / R) ("hann") for
+ * d < R and r[R] = 1, L = R + 1, in float64 rounded once; the kernels only read the table.  "hann" with R = crop / 2 at a stride of
+ * crop / 2 is a partition of unity away from the image border.
+ * The four entries take their counterpart's arguments with (ramp, ramp_len) before the stream and refuse, before any device work, a
+ * NULL ramp and a ramp_len outside [1, SG_BLEND_MAX_RAMP].  sg_label_head_blend[_multi]: sg_label_head[_multi] on the blended value
+ * (acc / wsum where that one has acc / count), every later statement the same; the multi entries equal the single ones per image. */
+#define SG_BLEND_MAX_RAMP 2048
+int sg_stitch_blend(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t,
+                    int pad_l, int H, int W, float* canvas, const float* ramp, int ramp_len, sg_stream s);
+int sg_stitch_blend_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh, int gw,
+                          int up_h, int up_w, int pad_t, int pad_l, const int32_t* image_hw, const int32_t* image_tiles,
+                          const int64_t* canvas_offset, const int64_t* block_prefix, int N, int64_t total_blocks, int64_t canvas_elems,
+                          float* canvases, const float* ramp, int ramp_len, sg_stream s);
+int sg_label_head_blend(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t,
+                        int pad_l, int H, int W, const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx,
+                        int64_t* labels, float* conf, const float* ramp, int ramp_len, sg_stream s);
+int sg_label_head_blend_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh, int gw,
+                              int up_h, int up_w, int pad_t, int pad_l, const int32_t* image_hw, const int32_t* image_tiles,
+                              const int64_t* out_offset, const int64_t* block_prefix, int N, int64_t total_blocks, int64_t out_pixels,
+                              const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx, int64_t* labels,
+                              float* conf, const float* ramp, int ramp_len, sg_stream s);
+
 /* F.interpolate(mode='bilinear', align_corners=False) on [C,h,w] -> [C,H,W] (segmentor.py:389,449) */
 int sg_resize_bilinear(const float* src, int C, int h, int w, float* dst, int H, int W, sg_stream s);
 
