@@ -170,6 +170,8 @@ SIGNATURES = {
     "sg_area_relabel_multi": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, I, L, L, P, I, F, F, I, P, P, P, P]),
     "sg_sieve_workspace_bytes": (Z, [L, I]),
     "sg_sieve": (I, [P, P, P, P, I, L, I, I, L, P, Z, P]),
+    "sg_regions_workspace_bytes": (Z, [L, L]),
+    "sg_regions": (I, [P, P, P, P, I, I, L, L, I, L, P, P, P, P, Z, P]),
 }
 
 _lib = None

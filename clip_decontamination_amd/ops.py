@@ -1250,3 +1250,128 @@ def sieve(labels, min_region, connectivity=4, fill="neighbour", bg_idx=0, out=No
     for o, r in zip(outs, res):
         o.copy_(r)
     return outs
+
+
+# ---- the region table (sg_regions; the definition: include/segearth_hip.h) ------------------------------------------------------------------
+REGION_COLUMNS = {"image": 0, "root": 1, "label": 2, "area": 3, "y0": 4, "x0": 5, "y1": 6, "x1": 7, "sum_y": 8, "sum_x": 9, "score_q": 10}    # SG_REGION_*
+REGION_FIELDS = 12                                                       # SG_REGION_FIELDS
+REGION_SCORE_ONE = 1 << 24                                               # q(1.0)
+REGIONS_BLOCK_PIXELS = 2048                                              # SG_REGIONS_BLOCK_PIXELS
+REGIONS_SCAN_BLOCKS = 1024                                               # SG_REGIONS_SCAN_BLOCKS
+REGIONS_FIRST_ROWS = 1 << 18                                             # max_regions=None: the rows of the first call
+REGIONS_MAX_PIXELS = (1 << 31) - 1                                       # per call: row indices are 32-bit
+
+
+def regions_args(connectivity=4, min_area=1, skip_label=None, max_regions=None):
+    """The checks of the region-table options: connectivity 4 or 8, min_area an integer >= 1, skip_label None or an integer, max_regions
+    None or an integer >= 1 -> the four as given."""
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError(f"regions: connectivity must be 4 or 8, got {connectivity!r}")
+    if isinstance(min_area, bool) or not isinstance(min_area, int) or min_area < 1:
+        raise ValueError(f"regions: min_area must be an integer >= 1 (a region is listed when its area is at least it), got {min_area!r}")
+    if skip_label is not None and (isinstance(skip_label, bool) or not isinstance(skip_label, int)):
+        raise ValueError(f"regions: skip_label must be None or an integer label, got {skip_label!r}")
+    if max_regions is not None and (isinstance(max_regions, bool) or not isinstance(max_regions, int) or max_regions < 1):
+        raise ValueError(f"regions: max_regions must be None or an integer >= 1, got {max_regions!r}")
+    return int(connectivity), int(min_area), skip_label, max_regions
+
+
+@on_tensor_device
+def regions_table(labels, image_hw, conf, connectivity, min_area, skip_label, max_regions, table, region_of=None):
+    """One sg_regions call, raw: ``labels`` flat int64, ``conf`` flat f32 or None, ``table`` int64 [>= max_regions, 12] written in place
+    (rows beyond the listed regions keep their bytes), ``region_of`` flat int32 or None -> counts int64 [N+1] on the device.  Nothing
+    synchronises with the host."""
+    lib = _lib.load()
+    N = len(image_hw)
+    pix = _prefix(h * w for h, w in image_hw)
+    hw = (C.c_int32 * (2 * N))(*[v for s in image_hw for v in s])
+    off = (C.c_int64 * N)(*pix[:-1])
+    counts = torch.empty(N + 1, dtype=torch.int64, device=labels.device)
+    buf = scratch(int(lib.sg_regions_workspace_bytes(pix[-1], max_regions)), labels.device)
+    wp, wn = _aligned(buf)
+    check(lib.sg_regions(ptr(labels), ptr(conf), hw, off, N, connectivity, min_area, 0 if skip_label is None else int(skip_label),
+                         int(skip_label is not None), max_regions, ptr(table), ptr(region_of), ptr(counts), wp, wn, stream_ptr()), "sg_regions")
+    return counts
+
+
+def regions_flat(labels, image_hw, conf=None, connectivity=4, min_area=1, skip_label=None, max_regions=None, want_map=False):
+    """The region table of N label maps that lie back to back in one flat int64 buffer (what the multi-image heads return), sizes
+    ``image_hw``; ``conf``: None or an f32 buffer of the same layout.  See ``regions`` for the options and the result; ``region_of`` is
+    one int32 [H,W] view per image."""
+    connectivity, min_area, skip_label, max_regions = regions_args(connectivity, min_area, skip_label, max_regions)
+    labels = _i64_labels("regions", labels)
+    image_hw = [(int(h), int(w)) for h, w in image_hw]
+    total_pix = sum(h * w for h, w in image_hw)
+    if not image_hw or any(h <= 0 or w <= 0 for h, w in image_hw) or total_pix != labels.numel():
+        raise ValueError(f"regions: {len(image_hw)} images of sizes {image_hw} against {labels.numel()} labels")
+    if total_pix > REGIONS_MAX_PIXELS:
+        raise ValueError(f"regions: 2^31 or more pixels in one call are not supported (row indices are 32-bit), got {total_pix}")
+    if conf is not None:
+        _require_gpu(conf)
+        if conf.dtype != torch.float32 or not conf.is_contiguous() or conf.numel() != labels.numel() or conf.device != labels.device:
+            raise ValueError("regions: conf must be a contiguous f32 tensor of the labels' size on the labels' device")
+    N = len(image_hw)
+    rows = min(total_pix, REGIONS_FIRST_ROWS) if max_regions is None else max_regions
+    region_of = torch.empty(total_pix, dtype=torch.int32, device=labels.device) if want_map else None
+    table = torch.empty(rows, REGION_FIELDS, dtype=torch.int64, device=labels.device)
+    counts = regions_table(labels.view(-1), image_hw, conf, connectivity, min_area, skip_label, rows, table, region_of).cpu()   # THE host read
+    total = int(counts[N])
+    if total > rows and max_regions is None:                                 # too few rows on the first call: once more with the exact number
+        rows = total
+        table = torch.empty(rows, REGION_FIELDS, dtype=torch.int64, device=labels.device)
+        regions_table(labels.view(-1), image_hw, conf, connectivity, min_area, skip_label, rows, table, region_of)
+    t = table[:min(total, rows)]
+    col = REGION_COLUMNS
+    area = t[:, col["area"]]
+    out = {k: t[:, col[k]] for k in ("image", "root", "label", "area")}
+    out["bbox"] = t[:, col["y0"]:col["x1"] + 1]
+    out["centroid"] = t[:, col["sum_y"]:col["sum_x"] + 1].double() / area.double()[:, None]
+    out["score"] = None if conf is None else t[:, col["score_q"]].double() / float(REGION_SCORE_ONE) / area.double()
+    out["score_q"] = None if conf is None else t[:, col["score_q"]]
+    out["counts"] = counts[:N].to(labels.device)
+    out["counts_host"] = counts[:N]                                          # what was read: a caller that splits the rows needs no second read
+    if total > rows:
+        out["truncated"] = True
+    if want_map:
+        out["region_of"] = [v[0] for v in flat_views(region_of, 1, image_hw)]
+    return out
+
+
+def label_confidence(probs, labels):
+    """probs f32 [K,H,W], labels int64 [1,H,W] -> f32 [1,H,W]: the probability of each pixel's label; 0 where the label is no class plane
+    (outside [0, K)).  Plain torch: what ``predict_regions(with_score=True)`` hands to sg_regions as ``conf``."""
+    K = probs.shape[0]
+    inside = (labels >= 0) & (labels < K)
+    return torch.where(inside, probs.gather(0, labels.clamp(0, K - 1)), torch.zeros((), device=probs.device, dtype=probs.dtype)).float()
+
+
+def regions(labels, conf=None, connectivity=4, min_area=1, skip_label=None, max_regions=None, want_map=False):
+    """List the connected regions of a label map (the definition: sg_regions in include/segearth_hip.h; regions, roots and connectivity
+    are those of ``sieve``).  ``labels``: int64 [H,W] or [1,H,W] on the device, or a list of such maps of any sizes -- a list is packed
+    into one flat buffer and served by one sg_regions call; ``conf``: None, or f32 of the labels' shape(s), a per-pixel confidence.
+    A region is listed when it has at least ``min_area`` pixels and its label is not ``skip_label``; the rows are ordered by (image,
+    root).  Returns a dict of device tensors over the R listed regions: ``image``, ``root``, ``label``, ``area`` int64 [R]; ``bbox``
+    int64 [R,4] (y0, x0, y1, x1), half-open; ``centroid`` float64 [R,2] (y, x); ``score`` float64 [R], the region's mean clamp(conf, 0,
+    1) from the exact integer sum ``score_q`` of conf in steps of 2^-24 (both None without ``conf``); ``counts`` int64 [N], the regions
+    per image (``counts_host``: the same on the host, as it was read); with ``want_map`` ``region_of``, per map an int32 [H,W] of each pixel's row (-1: not listed).
+    ``max_regions=None`` starts with min(pixels, 2^18) rows and calls once more with the exact total if those were too few; an explicit
+    ``max_regions`` truncates the table to its first rows (``counts`` and ``region_of`` stay uncapped) and adds ``truncated=True``.
+    The one host read is ``counts`` after the call, to slice the table."""
+    many = isinstance(labels, (list, tuple))
+    maps = list(labels) if many else [labels]
+    confs = None if conf is None else (list(conf) if many else [conf])
+    if not maps or (confs is not None and len(confs) != len(maps)):
+        raise ValueError("regions: needs at least one label map, and one conf per map")
+    for m in maps:
+        if not torch.is_tensor(m) or m.dim() not in (2, 3) or (m.dim() == 3 and m.shape[0] != 1) or m.numel() == 0:
+            raise ValueError("regions: a label map must be a non-empty int64 [H,W] or [1,H,W] tensor")
+        _i64_labels("regions", m)
+    if confs is not None and any(not torch.is_tensor(c) or c.numel() != m.numel() or c.dtype != torch.float32 for c, m in zip(confs, maps)):
+        raise ValueError("regions: conf must be f32 of the labels' shape")
+    hw = [tuple(m.shape[-2:]) for m in maps]
+    flat = maps[0].reshape(-1) if len(maps) == 1 else torch.cat([m.reshape(-1) for m in maps])
+    cflat = None if confs is None else (confs[0].contiguous().reshape(-1) if len(maps) == 1 else torch.cat([c.reshape(-1) for c in confs]))
+    out = regions_flat(flat, hw, cflat, connectivity, min_area, skip_label, max_regions, want_map)
+    if want_map and not many:
+        out["region_of"] = out["region_of"][0]
+    return out

@@ -401,6 +401,10 @@ SIEVE_TOPK = ("top-k together with min_region is not built: sieving plane 0 woul
               "changed; run predict_topk / topk= on an instance without min_region")
 
 
+REGIONS_TILE_GROUP = ("the region table under tile_group sharding is not built: a region crosses the ranks' canvas bands, so the roots on "
+                      "the band borders would need a union across the ranks and the rows a merge; list the regions of whole images per rank")
+
+
 class SegPipeline:
     # Every constructor option has its default here too, so an instance built without the constructor (the CPU tests' stubs) reads them.
     pamr_steps, pamr_stride = 0, (8, 16)      # PAMR off unless the constructor says otherwise
@@ -614,6 +618,22 @@ class SegPipeline:
             hw = [tuple(labels.shape[-2:])] if image_hw is None else image_hw
             ops.sieve_flat(labels.view(-1), hw, self.min_region, self.region_connectivity, self.region_fill, self.bg_idx)
         return labels
+
+    def regions(self, labels, image_hw=None, conf=None, min_area: int = 1, include_bg: bool = False, connectivity=None, skip_label=None,
+                max_regions=None, want_map: bool = False) -> dict:
+        """The region table of final labels (sg_regions; ``ops.regions`` describes the result): one label map int64 [1,H,W] / [H,W], a
+        list of maps, or with ``image_hw`` the flat buffer of a flush group's maps -- one sg_regions call each.  ``conf``: None or f32
+        of the same layout.  ``connectivity`` defaults to ``region_connectivity``, ``skip_label`` to ``bg_idx`` unless ``include_bg``.
+        The labels are only read.  ``tile_group`` sharding is refused."""
+        if self.tile_group is not None:
+            raise ValueError(REGIONS_TILE_GROUP)
+        connectivity = self.region_connectivity if connectivity is None else connectivity
+        if skip_label is None and not include_bg:
+            skip_label = int(self.bg_idx)
+        if image_hw is not None:
+            return ops.regions_flat(labels.view(-1), image_hw, None if conf is None else conf.view(-1), connectivity, min_area, skip_label,
+                                    max_regions, want_map)
+        return ops.regions(labels, conf, connectivity, min_area, skip_label, max_regions, want_map)
 
     def _image_tail(self, route: str, want: str, k: int, tile_logits, windows, up_hw, pad_tl, canvas_hw, out_hw, guide, ramp=None):
         """``_image_tail_unsieved`` and then, with min_region set, the sieve on its labels (top-k is refused with min_region)."""

@@ -61,6 +61,16 @@ except Exception:  # stand-alone use (tests, bench, serving)
     MODELS = _Registry()
 
 
+class _RegionSample:
+    """The least of a data sample that ``predict`` fills: predict_regions(with_score=True) without data samples, whole-image inference."""
+
+    def __init__(self, metainfo):
+        self.metainfo = metainfo
+
+    def set_data(self, data):
+        self.__dict__.update(data)
+
+
 def get_cls_idx(path):
     """One class per line, commas separate synonym queries (reference segmentor.py:611-622)."""
     with open(path, "r") as f:
@@ -404,6 +414,77 @@ class _HipSegmentorBase(_Base):
         for i, ds in enumerate(data_samples):
             self._fill_sample(ds, probs[i], labels[i], i)
         return data_samples
+
+    @torch.no_grad()
+    def predict_regions(self, images, data_samples=None, min_area=1, include_bg=False, with_score=False, want_map=False):
+        """The label maps of ``predict_many`` and the table of their connected regions (SegPipeline.regions, sg_regions: the definition
+        is in include/segearth_hip.h).  images: as ``predict_many``.  The labels come from the calls ``predict_many`` itself makes, every
+        option as configured (``area_thd``, ``min_region``, ``blend``, the data samples' ``ori_shape``), so they equal its labels byte
+        for byte; the regions are then listed on those final labels by ONE sg_regions call per flush group, on the group's flat label
+        buffer (whole-image inference, ``slide_crop <= 0``, has no flush groups: one call per image).  A region is listed when it has
+        at least ``min_area`` pixels and, unless ``include_bg``, its label is not ``bg_idx``; connectivity is ``region_connectivity``.
+        Returns ``(label_maps, regions)``: one int64 [1,H,W] map and one dict per image (``root``, ``label``, ``area``, ``bbox``,
+        ``centroid``, ``score`` / ``score_q``, and ``region_of`` int32 [H,W] with ``want_map``: rows of that image, counted from 0).
+        With data samples ``pred_sem_seg`` and ``seg_logits`` are set as ``predict`` sets them -- which means the probability tail runs,
+        with or without ``with_score`` -- and the dict is attached as ``pred_regions``.
+        ``with_score``: the probability tail that ``predict_many(images, data_samples)`` takes runs instead of the labels-only one
+        (without data samples too, at the images' own sizes), and a region's score is the mean probability of its pixels' final label,
+        ``probs.gather(0, labels)``; a pixel whose final label is no class plane (a ``bg_idx`` outside [0, K)) scores 0.  This costs
+        the K probability planes of every image; the label head's own confidence plane (``conf`` of sg_label_head) is the follow-up
+        that needs none.  ``tile_group`` sharding is refused."""
+        from . import ops
+        from .pipeline import REGIONS_TILE_GROUP
+        if getattr(self, "tile_group", None) is not None:
+            raise ValueError(REGIONS_TILE_GROUP)
+        batch = torch.is_tensor(images)
+        imgs = images.float() if batch else [x[0].float() if x.dim() == 4 else x.float() for x in images]
+        n = imgs.shape[0] if batch else len(imgs)
+        if data_samples is not None and len(data_samples) != n:
+            raise ValueError(f"predict_regions: {n} images but {len(data_samples)} data samples")
+        ops.regions_args(self.region_connectivity, min_area)                 # before any tower work
+        pipe = self._pipeline()
+        want_probs = with_score or data_samples is not None
+        labels, regions = [None] * n, [None] * n
+
+        def listed(idx, prb, lab, flat):
+            """One sg_regions call over the label maps ``lab`` of the images ``idx`` (``flat``: the buffer they are views of)."""
+            conf = None
+            if with_score:                                                   # the probability of the pixel's final label; no plane: 0
+                conf = [ops.label_confidence(p, l).reshape(-1) for p, l in zip(prb, lab)]
+                conf = conf[0] if len(conf) == 1 else torch.cat(conf)
+            hw = [tuple(l.shape[-2:]) for l in lab]
+            table = pipe.regions(flat, image_hw=hw, conf=conf, min_area=min_area, include_bg=include_bg, want_map=want_map)
+            r0 = 0
+            for k, (i, c) in enumerate(zip(idx, table["counts_host"].tolist())):
+                d = {key: (None if table[key] is None else table[key][r0:r0 + c]) for key in ("root", "label", "area", "bbox", "centroid", "score", "score_q")}
+                if want_map:
+                    m = table["region_of"][k]
+                    d["region_of"] = torch.where(m >= 0, m - r0, m)
+                labels[i], regions[i] = lab[k], d
+                r0 += c
+
+        if self.slide_crop <= 0:                                             # whole-image inference has no windows to pack: image by image
+            for i in range(n):
+                if not want_probs:
+                    lab = self.predict_many(imgs[i][None], None)[0].contiguous()
+                    listed([i], [None], [lab], lab.view(-1))
+                    continue
+                hw = tuple(imgs[i].shape[-2:])
+                ds = data_samples[i] if data_samples is not None else _RegionSample(dict(ori_shape=hw, img_shape=hw, pad_shape=hw, padding_size=[0, 0, 0, 0]))
+                self.predict_many(imgs[i][None], [ds])
+                lab = ds.pred_sem_seg.data.contiguous()
+                listed([i], [ds.seg_logits.data], [lab], lab.view(-1))
+        else:
+            ori = None if data_samples is None else [tuple(ds.metainfo["ori_shape"][:2]) for ds in data_samples]
+            for idx, prb, lab, flat in pipe.label_groups(imgs, self.slide_stride, self.slide_crop, want_probs=want_probs, ori_shapes=ori):
+                listed(idx, prb, lab, flat)
+                if data_samples is not None:
+                    for k, i in enumerate(idx):
+                        self._fill_sample(data_samples[i], prb[k], lab[k], i)
+        if data_samples is not None:
+            for ds, d in zip(data_samples, regions):
+                ds.set_data({"pred_regions": d})
+        return labels, regions
 
     @torch.no_grad()
     def predict_topk(self, inputs, k, data_samples=None):

@@ -817,6 +817,60 @@ size_t sg_sieve_workspace_bytes(int64_t n_pixels_total, int fill);
 int sg_sieve(const int64_t* labels, int64_t* labels_out, const int32_t* image_hw, const int64_t* out_offset, int N, int64_t min_region,
              int connectivity, int fill, int64_t bg_idx, void* workspace, size_t workspace_bytes, sg_stream stream);
 
+/* ---- region table: list the connected regions of a label map --------------------------------------------------------------------------
+ * The last stage after prob_thd -> area_thd -> min_region, for the object datasets: how many regions, how large, where, how confident.
+ * It only reads final labels.  Regions, area, root and connectivity are exactly those of sg_sieve: a region is a set of pixels of equal
+ * int64 label, connected under connectivity 4 or 8; its root is its smallest raster index y*W + x.
+ * A region is *listed* when area >= min_area (min_area >= 1) and, if use_skip is set, its label is not skip_label.  The listed regions
+ * of a call are ordered by (image index, root), ascending; the images of a call never connect to each other.
+ * table.  Row r is one region: SG_REGION_FIELDS = 12 int64 columns, 96 bytes:
+ *   SG_REGION_IMAGE    the image index            SG_REGION_ROOT   the region's root
+ *   SG_REGION_LABEL    its label                  SG_REGION_AREA   its pixel count
+ *   SG_REGION_Y0, _X0, _Y1, _X1   the half-open bounding box: Y1 / X1 are one past the last row / column
+ *   SG_REGION_SUM_Y, _SUM_X       the integer sums of the pixels' coordinates; centroid = sum / area, in double on the caller's side
+ *   SG_REGION_SCORE_Q  the sum over the region's pixels of q(conf); 0 when conf is null
+ *   column 11          0
+ *   q(c) is round-to-nearest-even of clamp(c, 0, 1) * 2^24 as a 64-bit integer; a NaN counts 0.  The scaling by a power of two is exact
+ *   in f32, so the sum is an exact integer, independent of arrival order.  The mean score is SCORE_Q / 2^24 / AREA.
+ * counts int64 [N+1]: counts[n] is the true number of listed regions of image n, counts[N] their total; both are uncapped.  Rows
+ *   0 .. min(total, max_regions) - 1 are written; rows beyond that are not touched: the caller's bytes stay.
+ * region_of (optional) int32, laid out like labels: the row index of the pixel's region in the uncapped order (so it may be >=
+ *   max_regions), -1 where the region is not listed.
+ * conf (optional) f32 with the labels' layout and offsets.  image_hw / out_offset are HOST arrays, as in sg_sieve.
+ *   sg_regions_workspace_bytes  8 * n_pixels_total (parent int32 + area int32 per pixel; a listed root's area entry becomes its row
+ *                               index) + 4 * (ceil(n_pixels_total / SG_REGIONS_BLOCK_PIXELS) + SG_SIEVE_GROUP + 1) rounded up to 8 (the
+ *                               scan's block array: one int32 per per-pixel workgroup of a launch sequence, and the running total).
+ *                               max_regions does not enter it.  0 for a negative count or max_regions < 1.
+ *   sg_regions                  per launch sequence of up to SG_SIEVE_GROUP images: the three labelling kernels of sg_sieve, then count
+ *                               (listed roots per workgroup of SG_REGIONS_BLOCK_PIXELS pixels), scan (one workgroup, exclusive offsets,
+ *                               SG_REGIONS_SCAN_BLOCKS entries per pass; the row offset passes from one sequence to the next in
+ *                               counts[N]), scatter (the rows' IMAGE, ROOT, LABEL, AREA and start values; the whole row of a one-pixel
+ *                               region) and reduce (box, sums, score and region_of, on tiles of 64 x 128 pixels; merged per wave and
+ *                               per workgroup before they reach global memory).  All in stream order; nothing is copied or
+ *                               synchronised.
+ * Integers and integer atomics only (min, max, add): byte-identical across repeats and launch shapes.
+ * Refused with SG_ERR_INVALID before any device work: a null labels / image_hw / out_offset / table / counts / workspace, a connectivity
+ * other than 4 or 8, min_area < 1, max_regions < 1, N < 1, an image of non-positive size, a negative out_offset, 2^31 or more pixels in
+ * the call (row indices are int32), a buffer that is not 8-byte aligned (region_of / conf: 4-byte), a workspace that is too small. */
+#define SG_REGION_IMAGE 0
+#define SG_REGION_ROOT 1
+#define SG_REGION_LABEL 2
+#define SG_REGION_AREA 3
+#define SG_REGION_Y0 4
+#define SG_REGION_X0 5
+#define SG_REGION_Y1 6
+#define SG_REGION_X1 7
+#define SG_REGION_SUM_Y 8
+#define SG_REGION_SUM_X 9
+#define SG_REGION_SCORE_Q 10
+#define SG_REGION_FIELDS 12
+#define SG_REGIONS_BLOCK_PIXELS 2048
+#define SG_REGIONS_SCAN_BLOCKS 1024
+size_t sg_regions_workspace_bytes(int64_t n_pixels_total, int64_t max_regions);
+int sg_regions(const int64_t* labels, const float* conf, const int32_t* image_hw, const int64_t* out_offset, int N, int connectivity,
+               int64_t min_area, int64_t skip_label, int use_skip, int64_t max_regions, int64_t* table, int32_t* region_of, int64_t* counts,
+               void* workspace, size_t workspace_bytes, sg_stream s);
+
 #ifdef __cplusplus
 }
 #endif
