@@ -133,6 +133,10 @@ SIGNATURES = {
     "sg_axpby_raw": (I, [P, P, F, F, L, P]),
     "sg_gem_inv_temp_raw": (I, [P, I, I, I, F, P, P]),
     "sg_patchify_raw": (I, [C.POINTER(TileBatch), I, I, P, I, P]),
+    "sg_gemm_f32_raw": (I, [P, L, L, L, P, L, L, L, L, P, P, L, P, L, L, L, I, I, I, I, I, I, F, P]),
+    "sg_attn_average_raw": (I, [I, P, I, I, I, I, P, Z, P, P]),
+    "sg_attn_enhance_raw": (I, [P, L, L, P, I, I, I, F, F, P, P]),
+    "sg_layer_fusion_apply_raw": (I, [P, P, I, I, I, I, P, P, P, P, P]),
     "sg_op_attention_scratch_bytes": (Z, [I, I, I, I, I]),
     "sg_op_attention": (I, [P, I, I, I, I, I, P, F, P, P, P, I, P, Z, P]),
     "sg_adaptive_conv": (I, [P, P, I, I, I, I, I, P, P]),

@@ -855,7 +855,13 @@ static int mlp_block(const TowerCore& c, const LayerW& L, float* x, const BlockS
   return SG_OK;
 }
 
-static int averaged_attention(const TowerCore& c, const BlockScratch& sc, int B, int N, hipStream_t s);
+static int averaged_attention(int hk, size_t esz, int D, int H, const void* qkv_or_probs, float* qk32, float* scores, float* probs, float* attn_avg,
+                              int B, int N, hipStream_t s);
+// the block whose packed qkv (parity mode: whose materialised probabilities) the scratch holds -> sc.attn_avg
+static int block_averaged_attention(const TowerCore& c, const BlockScratch& sc, int B, int N, hipStream_t s) {
+  return averaged_attention(c.hk, c.esz, c.width, c.heads, c.hk == HK_F32 ? (const void*)sc.probs : sc.qkv, sc.sa_qk32, sc.sa_scores, sc.sa_probs,
+                            sc.attn_avg, B, N, s);
+}
 // One ordinary residual block (reference open_clip/transformer.py:234-254), x updated in place.
 static int std_block(const TowerCore& c, const LayerW& L, float* x, const BlockScratch& sc, int B, int N, const BlockOpts& o, LnHandoff& h,
                      hipStream_t s) {
@@ -868,7 +874,7 @@ static int std_block(const TowerCore& c, const LayerW& L, float* x, const BlockS
   if (o.stats)
     SG_TRY(attention_stats(sc.qkv, c.hk, (int64_t)N * 3 * D, 3 * D, sc.lse, B, N, H, D / H, 1.0f / sqrtf((float)(D / H)), sc.attn_cls,
                            sc.attn_diag, s));
-  if (o.want_avg) SG_TRY(averaged_attention(c, sc, B, N, s));
+  if (o.want_avg) SG_TRY(block_averaged_attention(c, sc, B, N, s));
   if (fold) SG_TRY(linear_ln_producer(c.hk, sc.ctx, D, L.w_out, L.b_out, x, x, D, sc.xn, sc.ln_slice, (int)R, D, D, s));
   else SG_TRY(linear(c.hk, sc.ctx, D, L.w_out, L.b_out, x, x, D, true, (int)R, D, D, ACT_NONE, s));
   h.x16 = fold;                                                       // the out-projection has just written x
@@ -883,23 +889,26 @@ __global__ void unpack_qk_kernel(const void* __restrict__ qkv, int N, int D, flo
   const bf16_t v = reinterpret_cast<const bf16_t*>(qkv)[(int64_t)t * 3 * D + c];
   out[i] = kind == HK_F16 ? h2f(f16_t{v}) : bf2f(v);
 }
-// head-averaged attention matrix [B,N,N] of the block whose packed qkv is in sc.qkv (the tensor the reference gets from
-// nn.MultiheadAttention(need_weights=True), transformer.py:609-610).  Only the optional mode='attention' enhancer needs it.
-static int averaged_attention(const TowerCore& c, const BlockScratch& sc, int B, int N, hipStream_t s) {
-  const int D = c.width, H = c.heads, dh = D / H;
+// head-averaged attention matrix [B,N,N] of a block (the tensor the reference gets from nn.MultiheadAttention(need_weights=True),
+// transformer.py:609-610).  Only the optional mode='attention' enhancer and layer fusion need it.  Parity mode (HK_F32): `qkv_or_probs` is the
+// materialised probabilities [B,H,N,N] and the head mean is the whole stage; otherwise it is the packed qkv [B,N,3D] in the storage `hk`
+// (esz bytes per element), rebuilt per image through qk32 [N,2D], scores and probs [H,N,N] (all f32).
+static int averaged_attention(int hk, size_t esz, int D, int H, const void* qkv_or_probs, float* qk32, float* scores, float* probs, float* attn_avg,
+                              int B, int N, hipStream_t s) {
+  const int dh = D / H;
   const float scale = 1.0f / sqrtf((float)dh);
-  if (c.hk == HK_F32) return head_mean(sc.probs, B, H, N, sc.attn_avg, s);   // parity mode: the probabilities are materialised already
+  if (hk == HK_F32) return head_mean((const float*)qkv_or_probs, B, H, N, attn_avg, s);   // parity mode: the probabilities are materialised already
   const int64_t NN = (int64_t)N * N;
   for (int b = 0; b < B; ++b) {
-    const void* qkv = (const char*)sc.qkv + (size_t)b * N * 3 * D * c.esz;
-    hipLaunchKernelGGL(unpack_qk_kernel, dim3((unsigned)cdiv((int64_t)N * 2 * D, 256)), dim3(256), 0, s, qkv, N, D, sc.sa_qk32, c.hk);
+    const void* qkv = (const char*)qkv_or_probs + (size_t)b * N * 3 * D * esz;
+    hipLaunchKernelGGL(unpack_qk_kernel, dim3((unsigned)cdiv((int64_t)N * 2 * D, 256)), dim3(256), 0, s, qkv, N, D, qk32, hk);
     SG_LAUNCH_CHECK();
     GemmF32Args g{};
-    g.A = sc.sa_qk32; g.lda = 2 * D; g.sAi = dh; g.B = sc.sa_qk32 + D; g.sbk = 1; g.sbn = 2 * D; g.sBi = dh;
-    g.C = sc.sa_scores; g.ldc = N; g.sCi = NN; g.M = N; g.N = N; g.K = dh; g.batch = H; g.inner = H; g.act = 0; g.alpha = 1.f;
+    g.A = qk32; g.lda = 2 * D; g.sAi = dh; g.B = qk32 + D; g.sbk = 1; g.sbn = 2 * D; g.sBi = dh;
+    g.C = scores; g.ldc = N; g.sCi = NN; g.M = N; g.N = N; g.K = dh; g.batch = H; g.inner = H; g.act = 0; g.alpha = 1.f;
     SG_TRY(gemm_f32(g, s));
-    SG_TRY(softmax_rows(sc.sa_scores, N, (int64_t)H * N, N, H, nullptr, scale, nullptr, 0.f, 0, nullptr, nullptr, 0, 0, sc.sa_probs, nullptr, s));
-    SG_TRY(head_mean(sc.sa_probs, 1, H, N, sc.attn_avg + (int64_t)b * NN, s));
+    SG_TRY(softmax_rows(scores, N, (int64_t)H * N, N, H, nullptr, scale, nullptr, 0.f, 0, nullptr, nullptr, 0, 0, probs, nullptr, s));
+    SG_TRY(head_mean(probs, 1, H, N, attn_avg + (int64_t)b * NN, s));
   }
   return SG_OK;
 }
@@ -992,7 +1001,7 @@ extern "C" int sg_vit_forward(sg_context* c, const sg_tile_batch* tiles, const s
         AttnBuffers av{sc.scores, sc.probs, sc.lse, sc.lse1, sc.omega, sc.qnorm, sc.knorm};
         SG_TRY(run_attention(hk, sc.qkv, B, N, D, H, SG_VANILLA, nullptr, 0.f, nullptr, sc.ctx, false, av, s));
       }
-      SG_TRY(averaged_attention(core, sc, B, N, s));
+      SG_TRY(block_averaged_attention(core, sc, B, N, s));
       if (L == 1) SG_HIP(hipMemcpyAsync(p.lf_acc, sc.attn_avg, (size_t)BNN * 4, hipMemcpyDeviceToDevice, s));
       else SG_TRY(axpby(p.lf_acc, sc.attn_avg, 1.0f - lf, lf, BNN, s));
     }
@@ -1004,17 +1013,8 @@ extern "C" int sg_vit_forward(sg_context* c, const sg_tile_batch* tiles, const s
     LnHandoff none;                                                   // p.out_last comes from a plain GEMM
     if (!o->ignore_residual) SG_TRY(mlp_block(core, LL, p.out_last, sc, R, none, s));
     // ---- attention-map layer fusion: mask the fused map's outlier columns, renormalise, re-weight every token (transformer.py:647-690) ----
-    if (fusion && o->outlier_enabled) {
-      const int k = o->outlier_top_k < n ? o->outlier_top_k : n;
-      SG_TRY(fusion_row_diag(p.lf_acc, B, N, sc.attn_cls, sc.attn_diag, s));
-      SG_TRY(select_topk(sc.attn_cls, sc.attn_diag, B, N, k, 0, p.idx_out, s));
-      SG_TRY(fusion_mask_normalize(p.lf_acc, p.idx_out, B, N, k, s));
-      GemmF32Args g{};
-      g.A = p.lf_acc; g.lda = N; g.sAo = (int64_t)N * N; g.B = p.out_last; g.sbk = D; g.sbn = 1; g.sBo = (int64_t)N * D;
-      g.C = sc.sa_tmp; g.ldc = D; g.sCo = (int64_t)N * D; g.M = N; g.N = D; g.K = N; g.batch = B; g.inner = 1; g.act = 0; g.alpha = 1.f;
-      SG_TRY(gemm_f32(g, s));
-      SG_HIP(hipMemcpyAsync(p.out_last, sc.sa_tmp, (size_t)R * D * 4, hipMemcpyDeviceToDevice, s));
-    }
+    if (fusion && o->outlier_enabled)
+      SG_TRY(layer_fusion_apply(p.lf_acc, p.out_last, B, N, D, o->outlier_top_k, sc.attn_cls, sc.attn_diag, p.idx_out, sc.sa_tmp, s));
     // ---- refinements on the last-block output (transformer.py:698-742); need block L-2's attention, which layer fusion does not capture ----
     if (!fusion && o->outlier_enabled && o->selfattn_enabled && o->selfattn_mode == 1) {
       SG_TRY(attn_mode_enhance(p.out_last, (int64_t)N * D, D, sc.attn_avg, B, N, D, o->selfattn_strength, o->selfattn_threshold, sc.sa_tmp, s));
@@ -1359,6 +1359,46 @@ extern "C" int sg_similarity_map(const float* patches, int64_t batch_stride, int
   if (hk != HK_F32) SG_REQUIRE(D % 64 == 0, "sg_similarity_map: bf16 mode needs D %% 64 == 0");
   SG_TRY(l2norm_rows(patches, 0, batch_stride, ld, n, scratch, hk, (int64_t)n * D, D, (int64_t)B * n, D, 1e-12f, s));
   return similarity_from_xhat(hk, scratch, B, n, D, temperature, add_self, sim, s);
+}
+
+// ---- raw test entries of the f32 GEMM and the attention-map stages: one host function each, arguments passed one to one -------------------
+extern "C" int sg_gemm_f32_raw(const float* A, int64_t lda, int64_t sAo, int64_t sAi, const float* B, int64_t sbk, int64_t sbn, int64_t sBo,
+                               int64_t sBi, const float* bias, const float* residual, int64_t ldr, float* C, int64_t ldc, int64_t sCo, int64_t sCi,
+                               int M, int N, int K, int batch, int inner, int act, float alpha, sg_stream st) {
+  SG_REQUIRE(A && B && C, "sg_gemm_f32_raw: null pointer");
+  GemmF32Args g{};
+  g.A = A; g.lda = lda; g.sAo = sAo; g.sAi = sAi; g.B = B; g.sbk = sbk; g.sbn = sbn; g.sBo = sBo; g.sBi = sBi;
+  g.bias = bias; g.residual = residual; g.ldr = ldr; g.C = C; g.ldc = ldc; g.sCo = sCo; g.sCi = sCi;
+  g.M = M; g.N = N; g.K = K; g.batch = batch; g.inner = inner; g.act = act; g.alpha = alpha;
+  return gemm_f32(g, as_stream(st));
+}
+extern "C" int sg_attn_average_raw(int precision, const void* qkv_or_probs, int B, int N, int D, int H, void* scratch, size_t scratch_bytes,
+                                   float* attn_avg, sg_stream st) {
+  SG_REQUIRE(qkv_or_probs && attn_avg, "sg_attn_average_raw: null pointer");
+  SG_REQUIRE(B > 0 && B < 65536 && N > 0 && D > 0 && H > 0 && D % H == 0, "sg_attn_average_raw: bad shape B=%d N=%d D=%d H=%d", B, N, D, H);
+  int hk; SG_TRY(raw_kind("sg_attn_average_raw", precision, &hk));
+  float *qk32 = nullptr, *scores = nullptr, *probs = nullptr;
+  if (hk != HK_F32) {
+    SG_REQUIRE(hk != HK_F16X2 || D % 8 == 0, "sg_attn_average_raw: two-plane rows need D %% 8 == 0");
+    SG_REQUIRE(scratch && (((uintptr_t)scratch) & 255) == 0, "sg_attn_average_raw: scratch must be 256-byte aligned");
+    Bump b(scratch, scratch_bytes, false);
+    qk32 = b.get<float>((size_t)N * 2 * D); scores = b.get<float>((size_t)H * N * N); probs = b.get<float>((size_t)H * N * N);
+    if (b.off > scratch_bytes) return fail(SG_ERR_STATE, "sg_attn_average_raw: scratch %zu < %zu", scratch_bytes, b.off);
+  }
+  return averaged_attention(hk, hk_esz(hk), D, H, qkv_or_probs, qk32, scores, probs, attn_avg, B, N, as_stream(st));
+}
+extern "C" int sg_attn_enhance_raw(float* tokens, int64_t sb, int64_t st, float* A, int B, int N, int D, float strength, float threshold, float* tmp,
+                                   sg_stream st_) {
+  SG_REQUIRE(tokens && A && tmp, "sg_attn_enhance_raw: null pointer");
+  SG_REQUIRE(B > 0 && B < 65536 && N > 1 && D > 0, "sg_attn_enhance_raw: bad shape B=%d N=%d D=%d", B, N, D);
+  SG_REQUIRE(st == D && sb >= (int64_t)N * D, "sg_attn_enhance_raw: the write-back needs dense token rows (st == D) and sb >= N D");
+  return attn_mode_enhance(tokens, sb, st, A, B, N, D, strength, threshold, tmp, as_stream(st_));
+}
+extern "C" int sg_layer_fusion_apply_raw(float* acc, float* tokens, int B, int N, int D, int top_k, float* a_cls, float* a_diag, int32_t* idx_out,
+                                         float* tmp, sg_stream st) {
+  SG_REQUIRE(acc && tokens && a_cls && a_diag && idx_out && tmp, "sg_layer_fusion_apply_raw: null pointer");
+  SG_REQUIRE(B > 0 && B < 65536 && N > 1 && D > 0 && top_k >= 1, "sg_layer_fusion_apply_raw: bad shape B=%d N=%d D=%d top_k=%d", B, N, D, top_k);
+  return layer_fusion_apply(acc, tokens, B, N, D, top_k, a_cls, a_diag, idx_out, tmp, as_stream(st));
 }
 
 extern "C" size_t sg_outlier_scratch_bytes(int B, int D, int k) { return refine_scratch_bytes(B, D, k); }

@@ -257,6 +257,24 @@ int attn_mode_enhance(float* tokens, int64_t sb, int64_t st, float* A, int B, in
   return SG_OK;
 }
 
+// ---- attention-map layer fusion: mask the fused map's outlier columns, renormalise, re-weight every token (transformer.py:647-690) ----
+// acc [B,N,N] the fused map (destroyed: masked and renormalised in place); tokens [B,N,D] dense f32, in / out; a_cls, a_diag [B,N];
+// idx_out [B,k] with k = min(top_k, N - 1); tmp [B,N,D] f32
+int layer_fusion_apply(float* acc, float* tokens, int B, int N, int D, int top_k, float* a_cls, float* a_diag, int32_t* idx_out, float* tmp,
+                       hipStream_t s) {
+  const int n = N - 1;
+  const int k = top_k < n ? top_k : n;
+  SG_TRY(fusion_row_diag(acc, B, N, a_cls, a_diag, s));
+  SG_TRY(select_topk(a_cls, a_diag, B, N, k, 0, idx_out, s));
+  SG_TRY(fusion_mask_normalize(acc, idx_out, B, N, k, s));
+  GemmF32Args g{};
+  g.A = acc; g.lda = N; g.sAo = (int64_t)N * N; g.B = tokens; g.sbk = D; g.sbn = 1; g.sBo = (int64_t)N * D;
+  g.C = tmp; g.ldc = D; g.sCo = (int64_t)N * D; g.M = N; g.N = D; g.K = N; g.batch = B; g.inner = 1; g.act = 0; g.alpha = 1.f;
+  SG_TRY(gemm_f32(g, s));
+  SG_HIP(hipMemcpyAsync(tokens, tmp, (size_t)B * N * D * 4, hipMemcpyDeviceToDevice, s));
+  return SG_OK;
+}
+
 // ---- cross-tile boundary fusion (reference cross_tile_fusion.py:24-320; unwired there) -----------------------------
 // Tiles arrive in raster order, so only the 'top' and 'left' directions ever find a cached neighbour.  The reference's
 // strip extraction aliases (row strips are views, column strips are copies), which fixes the data flow restated in

@@ -87,6 +87,8 @@ int fusion_row_diag(const float* A, int B, int N, float* a_cls, float* a_diag, h
 int fusion_mask_normalize(float* A, const int32_t* idx, int B, int N, int k, hipStream_t s);
 int attn_mode_enhance(float* tokens, int64_t sb, int64_t st, float* A, int B, int N, int D, float strength, float threshold, float* tmp,
                       hipStream_t s);
+int layer_fusion_apply(float* acc, float* tokens, int B, int N, int D, int top_k, float* a_cls, float* a_diag, int32_t* idx_out, float* tmp,
+                       hipStream_t s);
 
 // ---- bilinear helpers (align_corners=False, ATen area_pixel_compute_source_index) ------------------------------------
 __device__ __forceinline__ void bilinear_tap(int dst, int in, int out, int& i0, int& i1, float& l0, float& l1) {

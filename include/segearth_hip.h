@@ -544,6 +544,33 @@ int sg_gem_inv_temp_raw(const float* x, int B, int N, int D, float scale, float*
  * (normalised, for u8 scenes) pixel of the window padded by pad_t rows on top and pad_l columns on the left, zero in the padding and in
  * columns >= 3 P P.  Kpad >= 3 P P (two-plane: Kpad % 8 == 0), the grid must cover the padded tile. */
 int sg_patchify_raw(const sg_tile_batch* tiles, int P, int Kpad, void* out, int out_kind, sg_stream s);
+/* ---- raw test entries of the f32 GEMM and the attention-map stages --------------------------------------------------------------------
+ * Same convention: one host function each, arguments one to one, a refused call launches nothing.  Strides in f32 elements. */
+/* The parity-mode f32 GEMM in every form it has:  C[z](m, n) = act(alpha sum_k A[z](m, k) B[z](k, n) + bias[n]) + residual[z](m, n)  with
+ * A[z](m, k) at A[zo sAo + zi sAi + m lda + k], B[z](k, n) at B[zo sBo + zi sBi + k sbk + n sbn], C[z](m, n) at C[zo sCo + zi sCi + m ldc + n],
+ * zo = z / inner, zi = z % inner, z < batch.  bias [N] (nullable) is shared by the batch.  residual (nullable) is batched by C's strides
+ * (sCo / sCi) with its own leading dimension: residual[z](m, n) at residual[zo sCo + zi sCi + m ldr + n].  act: 0 none, 1 QuickGELU, 2 erf-GELU,
+ * 3 ReLU.  M, N, K, batch, inner > 0 (refused otherwise), batch < 65536.  A == B and residual == C are allowed. */
+int sg_gemm_f32_raw(const float* A, int64_t lda, int64_t sAo, int64_t sAi, const float* B, int64_t sbk, int64_t sbn, int64_t sBo, int64_t sBi,
+                    const float* bias, const float* residual, int64_t ldr, float* C, int64_t ldc, int64_t sCo, int64_t sCi, int M, int N, int K,
+                    int batch, int inner, int act, float alpha, sg_stream s);
+/* attn_avg [B,N,N] = the head-averaged attention matrix mean_h softmax_j(q_i.k_j / sqrt(D / H)) of an ordinary block.
+ * SG_PREC_F32: qkv_or_probs is the materialised probabilities [B,H,N,N] f32 and the head mean is the whole stage (scratch unused, may be NULL).
+ * SG_PREC_BF16 / F16 / F16X2: qkv_or_probs is the packed qkv [B,N,3D] in that storage; q and k are unpacked exactly to f32 and the scores,
+ * the softmax and the mean run in f32, image by image.  scratch (256-byte aligned) holds [N,2D] + 2 [H,N,N] f32, each rounded up to 256 bytes. */
+int sg_attn_average_raw(int precision, const void* qkv_or_probs, int B, int N, int D, int H, void* scratch, size_t scratch_bytes, float* attn_avg,
+                        sg_stream s);
+/* Self-attention enhancement, mode 'attention', on tokens [B,N,D] f32 (image b at tokens + b sb, dense rows: st == D, sb >= N D) with the
+ * head-averaged map A [B,N,N]:  A'[i,i] += max(threshold - A[i,i], 0) strength for the patch rows i >= 1, every row divided by (its sum +
+ * 1e-8), column 0 dropped; tokens[b, 1:, :] = (A'[b] . tokens[b])[1:, :], the CLS row untouched.  A is destroyed; tmp [B,N,D] f32. */
+int sg_attn_enhance_raw(float* tokens, int64_t sb, int64_t st, float* A, int B, int N, int D, float strength, float threshold, float* tmp,
+                        sg_stream s);
+/* Attention-map layer fusion on the fused map acc [B,N,N] (destroyed) and tokens [B,N,D] dense f32 (in / out): a_cls[b, j] = acc[b, 0, j],
+ * a_diag[b, j] = acc[b, j, j]; idx_out [B,k], k = min(top_k, N - 1): the k patch tokens with the largest a_cls / (a_diag + 1e-8), descending,
+ * ties to the lowest index; columns 1 + idx_out[b, :] of acc[b] zeroed, every row divided by (its sum + 1e-8); tokens[b] = acc[b] . tokens[b].
+ * tmp [B,N,D] f32. */
+int sg_layer_fusion_apply_raw(float* acc, float* tokens, int B, int N, int D, int top_k, float* a_cls, float* a_diag, int32_t* idx_out, float* tmp,
+                              sg_stream s);
 size_t sg_op_attention_scratch_bytes(int B, int N, int D, int H, int precision);
 int sg_op_attention(const float* qkv, int B, int N, int D, int H, int variant, const float* sim, float sim_weight,
                     float* ctx, float* attn_cls, float* attn_diag, int precision, void* scratch, size_t scratch_bytes,
