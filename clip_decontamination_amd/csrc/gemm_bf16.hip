@@ -1120,6 +1120,8 @@ __device__ __forceinline__ void epilogue_store8_fp8(f32x4 (&acc)[MI][NI], const 
 //           through a patch inside the just-consumed A slot, one barrier, group 1 re-staggers.
 // Per wave and K step: 8 LDS-DMA pieces and 24 ds_read_b128.  Look-ahead is 3 K steps: >= 4 K steps per tile keep every load within the next
 // output tile.  Operand rows of a tile are addressed from a 64-bit tile base with 32-bit byte offsets (row strides checked by the dispatch).
+// Addresses cost a steady K step 4 vector instructions: pieces take a scalar base + the lane's per-tile offset, ring positions rotate in
+// SGPRs, fragment reads add the slot to a per-lane base once per operand and K half.
 // Arithmetic (bf16 / f16): every accumulator gets its K 0-31 MFMA and then its K 32-63 one, with read_frag32's lane -> K-chunk mapping, so its
 // MFMA sequence is the one the 32-element kernel issues and the results are bit-identical to that kernel's (tuning code 38 runs it).
 // fp8: the concatenated halves are the instruction's own K order (dwords 0-3 of lane block b are K 16b..16b+15, dwords 4-7 K 64+16b..;
@@ -1166,9 +1168,7 @@ __device__ __forceinline__ void gemm_persist128(const GemmBf16Args& a, int act, 
   constexpr int EB = FP8 ? 1 : 2;                                        // bytes per unit of a.K / lda / ldw / strides
   constexpr int KB = 128;                                                // K step in bytes
   constexpr int SLOT = 256 * KB;                                         // 32 KiB
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  char* ldsA = lds;                                                      // 2 slots
-  char* ldsW = lds + 2 * SLOT;                                           // 3 slots
+  extern __shared__ __attribute__((aligned(16))) char lds[];                // A ring: slots 0-1, W ring: slots 2-4
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = wave >> 2, wi = wave & 3;
   const PersistOrder order(a, FP8 ? 0 : a.ngroup);                      // (fp8 launches never take the N-group order: a compile-time 0 keeps it at 0 B scratch)
@@ -1202,32 +1202,42 @@ __device__ __forceinline__ void gemm_persist128(const GemmBf16Args& a, int act, 
   Src nxt = make_src(my_tiles > 1 ? 1 : 0);
   int cur_end = nt;                                                      // stream index where `nxt` begins
   const int lda_i = (int)lda_b, ldw_i = (int)ldw_b;
-  auto load_a = [&](int u) {                                             // this wave's pieces of A_g(u)
+  // Ring positions as LDS byte offsets that rotate once per K step: A(s) sits at apos (two slots, toggled), W(s) / W(s+1) / W(s-1) at
+  // wpos / wnext / wprev (three slots).  Wave-uniform, so they live in SGPRs and no s & 1 / s % 3 is formed per step.
+  int apos = 0, wpos = 2 * SLOT, wnext = 3 * SLOT, wprev = 4 * SLOT;
+  // One LDS-DMA piece: 8 rows x 128 B from a wave-uniform 64-bit base plus this lane's non-negative 32-bit offset (the scalar-base form of
+  // global_load_lds_dwordx4: no vector arithmetic per piece), to LDS byte offset dst (M0).
+  auto piece = [&](const char* base, int& off, int dst) {
+    // (off passes through an empty statement in place: with its zero-extension hoisted out of the loop as a 64-bit per-lane value, the
+    // instruction selector no longer folds it into the scalar-base form -- one 64-bit vector add per piece and twice the offset registers)
+    asm volatile("" : "+v"(off));
+    __builtin_amdgcn_global_load_lds((gbl_ptr_t)(base + (uint32_t)off), (lds_ptr_t)(lds + dst), 16, 0, 0);
+  };
+  const int dst_a = (128 * g + 32 * wi) * KB, dst_w = (64 * wi + 32 * g) * KB;   // this wave's first piece inside an A / a W slot
+  auto off_a = [&](const Src& sp, int p) { return row_a(sp, p) * lda_i + ((p & 1) ? swz_o : swz_e); };   // rows past the edge re-read the last row (never stored)
+  auto off_w = [&](const Src& sp, int p) { return row_w(sp, p) * ldw_i + ((p & 1) ? swz_o : swz_e); };
+  auto load_a = [&](int u, int pos) {                                    // this wave's pieces of A_g(u), into the slot at pos
     if (u >= total) return;
     const bool nx = u >= cur_end;
     const Src& sp = nx ? nxt : cur;
-    const int kt = nx ? u - cur_end : u - (cur_end - nt);
-    char* base = ldsA + (u & 1) * SLOT + (128 * g + 32 * wi) * KB;
+    const char* base = sp.Ab + (int64_t)(nx ? u - cur_end : u - (cur_end - nt)) * KB;
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int r = row_a(sp, p);                                        // rows past the edge re-read the last row (never stored)
-      const int off = r * lda_i + ((p & 1) ? swz_o : swz_e) + kt * KB;
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(sp.Ab + off), (lds_ptr_t)(base + p * 8 * KB), 16, 0, 0);
-    }
+    for (int p = 0; p < 4; ++p) { int off = off_a(sp, p); piece(base, off, pos + dst_a + p * 8 * KB); }
   };
-  auto load_w = [&](int u) {                                             // this wave's rows of W(u)
+  auto load_w = [&](int u, int pos) {                                    // this wave's rows of W(u), into the slot at pos
     if (u >= total) return;
     const bool nx = u >= cur_end;
     const Src& sp = nx ? nxt : cur;
-    const int kt = nx ? u - cur_end : u - (cur_end - nt);
-    char* base = ldsW + (u % 3) * SLOT + (64 * wi + 32 * g) * KB;
+    const char* base = sp.Wb + (int64_t)(nx ? u - cur_end : u - (cur_end - nt)) * KB;
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int r = row_w(sp, p);
-      const int off = r * ldw_i + ((p & 1) ? swz_o : swz_e) + kt * KB;
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(sp.Wb + off), (lds_ptr_t)(base + p * 8 * KB), 16, 0, 0);
-    }
+    for (int p = 0; p < 4; ++p) { int off = off_w(sp, p); piece(base, off, pos + dst_w + p * 8 * KB); }
   };
+  // Fragment reads: chunk h * 4 + lane / 16 of row R + (lane & 15), R a multiple of 16, sits at (R + (lane & 15)) * 128 +
+  // (((h * 4 + lane / 16) ^ ((lane & 15) >> 1)) << 4): a per-lane part per K half (the halves differ in address bit 6) computed once, plus
+  // the slot (one add per operand and half in READ0), plus row-group displacements that ds_read_b128 takes as immediates.
+  const int frag0 = (lane & 15) * KB + (((lane >> 4) ^ ((lane & 15) >> 1)) << 4);
+  const int frag_w[2] = {frag0 + 64 * wi * KB, (frag0 ^ 64) + 64 * wi * KB}, frag_a[2] = {frag0 + 128 * g * KB, (frag0 ^ 64) + 128 * g * KB};
+  auto frag = [&](int off) { return *reinterpret_cast<const bf16x8*>(lds + off); };
 #define SG_P128_SYNC()                               \
   do {                                               \
     __builtin_amdgcn_sched_barrier(0);               \
@@ -1237,8 +1247,8 @@ __device__ __forceinline__ void gemm_persist128(const GemmBf16Args& a, int act, 
 
   // prologue: A(0), W(0), W(1) from everybody, W(2) from group 1 (group 0 issues its rows of W(2) in READ1(0)).  Group 1 retires its rows of
   // W(1) here as well: group 0 reads them in READ0(1), which runs while group 1 is in MFMA1(0), before group 1's first wait in the loop.
-  load_a(0); load_w(0); load_w(1);
-  if (g == 1) { load_w(2); if (2 < total) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
+  load_a(0, apos); load_w(0, wpos); load_w(1, wnext);
+  if (g == 1) { load_w(2, wprev); if (2 < total) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
   else { if (1 < total) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
   SG_P128_SYNC();
   if (g == 1) SG_P128_SYNC();
@@ -1253,48 +1263,44 @@ __device__ __forceinline__ void gemm_persist128(const GemmBf16Args& a, int act, 
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) acc[i][jj] = (f32x4){0.f, 0.f, 0.f, 0.f};
     int kt = 0;
+    int oa[4], ow[4];                                                    // steady form: this lane's piece offsets inside the tile, formed once
+#pragma unroll
+    for (int p = 0; p < 4; ++p) { oa[p] = off_a(cur, p); ow[p] = off_w(cur, p); }
     // One K step.  STEADY: every piece this step requests (A(s+1), W(s+2+g)) belongs to the current output tile -- no source select, no
     // end-of-stream test; the last three steps of a tile take the general form (measured on bf16: +1.0 % on the bench line against the
     // general form throughout, which is 2-4 % faster on the run-time epilogue form alone)
     auto kstep = [&](auto steady_tag) {
       constexpr bool STEADY = decltype(steady_tag)::value;
-      const char* tA = ldsA + (s & 1) * SLOT;
-      const char* tW = ldsW + (s % 3) * SLOT;
-      // READ0(s): W fragments (kept for both phases) + A rows 0-63 of the group's half; issue A_g(s+1)
+      // READ0(s): W fragments (kept for both phases) + A rows 0-63 of the group's half; issue A_g(s+1) into the other A slot
+      const int tW[2] = {frag_w[0] + wpos, frag_w[1] + wpos}, tA[2] = {frag_a[0] + apos, frag_a[1] + apos};
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj) fw[jj].h[h] = read_frag(tW, 64 * wi + 16 * jj + (lane & 15), h * 4 + (lane >> 4));
+        for (int jj = 0; jj < 4; ++jj) fw[jj].h[h] = frag(tW[h] + 16 * jj * KB);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) fa[i].h[h] = read_frag(tA, 128 * g + 16 * i + (lane & 15), h * 4 + (lane >> 4));
+        for (int i = 0; i < 4; ++i) fa[i].h[h] = frag(tA[h] + 16 * i * KB);
       }
       if constexpr (STEADY) {
-        char* base = ldsA + ((s + 1) & 1) * SLOT + (128 * g + 32 * wi) * KB;
+        const char* base = cur.Ab + (int64_t)(kt + 1) * KB;
 #pragma unroll
-        for (int p = 0; p < 4; ++p) {
-          const int r = row_a(cur, p);
-          __builtin_amdgcn_global_load_lds((gbl_ptr_t)(cur.Ab + (r * lda_i + ((p & 1) ? swz_o : swz_e) + (kt + 1) * KB)), (lds_ptr_t)(base + p * 8 * KB), 16, 0, 0);
-        }
-      } else load_a(s + 1);
+        for (int p = 0; p < 4; ++p) piece(base, oa[p], (apos ^ SLOT) + dst_a + p * 8 * KB);
+      } else load_a(s + 1, apos ^ SLOT);
       SG_P128_SYNC();
       // MFMA0(s)
       persist128_mfma<OP>(acc, 0, fa, fw);
       SG_P128_SYNC();
-      // READ1(s): A rows 64-127; issue this group's rows of W(s+2) / W(s+3)
+      // READ1(s): A rows 64-127; issue this group's rows of W(s+2) / W(s+3), into the slot of W(s-1) / W(s)
 #pragma unroll
       for (int h = 0; h < 2; ++h)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) fa[i].h[h] = read_frag(tA, 128 * g + 64 + 16 * i + (lane & 15), h * 4 + (lane >> 4));
-      const int uw = s + 2 + g;
+        for (int i = 0; i < 4; ++i) fa[i].h[h] = frag(tA[h] + (64 + 16 * i) * KB);
+      const int uw = s + 2 + g, wdst = g ? wpos : wprev;
       if constexpr (STEADY) {
-        char* base = ldsW + (uw % 3) * SLOT + (64 * wi + 32 * g) * KB;
+        const char* base = cur.Wb + (int64_t)(kt + 2 + g) * KB;
 #pragma unroll
-        for (int p = 0; p < 4; ++p) {
-          const int r = row_w(cur, p);
-          __builtin_amdgcn_global_load_lds((gbl_ptr_t)(cur.Wb + (r * ldw_i + ((p & 1) ? swz_o : swz_e) + (kt + 2 + g) * KB)), (lds_ptr_t)(base + p * 8 * KB), 16, 0, 0);
-        }
+        for (int p = 0; p < 4; ++p) piece(base, ow[p], wdst + dst_w + p * 8 * KB);
       } else {
-        load_w(uw);
+        load_w(uw, wdst);
         if (FP8 && kt == nt - 1) {                                        // last K step of the tile: the row scales for the epilogue
 #pragma unroll
           for (int u2 = 0; u2 < 2; ++u2) { int m = cur.m0 + 128 * g + u2 * 64 + lane; m = m < a.M ? m : a.M - 1; rs_pre[u2] = a.row_scale[m]; }
@@ -1307,6 +1313,8 @@ __device__ __forceinline__ void gemm_persist128(const GemmBf16Args& a, int act, 
       else if (STEADY || uw < total) wait_vmcnt<4>(); else wait_vmcnt<0>();   // all but the W pieces just issued
       SG_P128_SYNC();
       ++kt; ++s;
+      apos ^= SLOT;
+      { const int t = wprev; wprev = wpos; wpos = wnext; wnext = t; }
     };
     // steady split: bf16 / f16 only.  With it, fp8 spills 20 B and the two-plane run-time form <0,0> 132 B instead of 52
     if constexpr (!FP8 && !H2) { while (kt + 3 < nt) kstep(std::true_type{}); }
@@ -1314,7 +1322,7 @@ __device__ __forceinline__ void gemm_persist128(const GemmBf16Args& a, int act, 
     // ---- tile end ----
     if (g == 0) SG_P128_SYNC();                                          // align: every read of this tile's last K step has retired
     {
-      float* pbase = reinterpret_cast<float*>(ldsA + ((s - 1) & 1) * SLOT);    // the consumed A slot: 8 patches of 8 rows x 68 floats (+pad), then
+      float* pbase = reinterpret_cast<float*>(lds + (apos ^ SLOT));    // the consumed A slot: 8 patches of 8 rows x 68 floats (+pad), then
       if constexpr (FP8)                                                       // 8 x 128 row scales (fp8) / 1 KiB per wave (statistics)
         epilogue_store8_fp8<8, 4>(acc, a, act, c_bf16, cur.m0 + 128 * g, cur.n0 + 64 * wi, pbase + wave * 576, pbase + 8 * 576 + wave * 128, lane, rs_pre);
       else
