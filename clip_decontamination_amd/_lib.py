@@ -97,6 +97,9 @@ SIGNATURES = {
     "sg_label_head_resized_multi": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, P, I, L, L, P, I, F, F, I, P, P, I, P]),
     "sg_topk_head_resized": (I, [P, P, I, I, I, I, I, I, I, I, I, I, I, I, P, I, F, I, P, P, I, P]),
     "sg_topk_head_resized_multi": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P, P, P, P, I, L, L, P, I, F, I, P, P, I, P]),
+    "sg_tta_head": (I, [P, L, P, I, P, I, I, I, I, P, I, F, F, I, P, P, P, I, P]),
+    "sg_tta_accumulate": (I, [P, I, I, I, I, P, I, P]),
+    "sg_tta_finish": (I, [P, I, I, I, I, F, I, P, P, P, P]),
     "sg_outlier_scratch_bytes": (Z, [I, I, I]),
     "sg_outlier_suppress": (I, [P, P, P, I, I, I, I, I, F, P, P, P]),
     "sg_cross_tile_scratch_bytes": (Z, [I, I, I, I, I]),

@@ -879,22 +879,29 @@ __device__ __forceinline__ void stitched_pixel(const StitchList& sl, const float
 
 // One 64 x 4 block of OUTPUT pixels of one image: a thread whose pixel (X, Y) lies in the output hands each chunk's resized stitched
 // values to sink(q0, acc), acc[k] for query q0 + k.  Returns whether this thread's pixel is in the output.  All 256 threads call it.
-template <class Sink>
+// FLIP (sg_tta_head): the instantiation can read the resized canvas mirrored along the width -- with `flip` set the thread of output
+// column X takes the taps of column OW - 1 - X and the block's footprint is that of the mirrored columns; what is gathered, divided and
+// blended per canvas pixel is the same code.  With FLIP = false nothing of this is compiled and `flip` is not read.
+template <bool FLIP = false, class Sink>
 __device__ __forceinline__ bool resized_gather(const float* __restrict__ tile_logits, const int32_t* __restrict__ win,
                                                const int32_t* __restrict__ tile_image, int img, int n_tiles, int Q, int gh, int gw, int up_h,
                                                int up_w, int pad_t, int pad_l, int h, int w, int OH, int OW, int bx0, int by0, int flags,
-                                               Sink&& sink) {
+                                               Sink&& sink, bool flip = false) {
   __shared__ float s_stage[ST_QC * RS_STAGE_PIX];
-  const int X = bx0 + (threadIdx.x & 63);
+  int X = bx0 + (threadIdx.x & 63);
   const int Y = __builtin_amdgcn_readfirstlane(by0 + (threadIdx.x >> 6));
   const bool live = Y < OH && X < OW;
+  int bxa = bx0, bxb = bx0 + 63 < OW ? bx0 + 63 : OW - 1;            // the block's first and last source column
+  if constexpr (FLIP) {
+    if (flip) { X = OW - 1 - X; const int t = OW - 1 - bxb; bxb = OW - 1 - bxa; bxa = t; }   // live: 0 <= X < OW either way
+  }
   // the block's canvas footprint [fx0, fx1] x [fy0, fy1]: the first tap of its first row / column to the second tap of its last one
   // (taps do not decrease with the output coordinate).  Block-uniform.
   int fy0, fy1, fx0, fx1, unused; float u0, u1;
   rs_tap(by0, h, OH, fy0, unused, u0, u1);
   rs_tap(by0 + 3 < OH ? by0 + 3 : OH - 1, h, OH, unused, fy1, u0, u1);
-  rs_tap(bx0, w, OW, fx0, unused, u0, u1);
-  rs_tap(bx0 + 63 < OW ? bx0 + 63 : OW - 1, w, OW, unused, fx1, u0, u1);
+  rs_tap(bxa, w, OW, fx0, unused, u0, u1);
+  rs_tap(bxb, w, OW, unused, fx1, u0, u1);
   const int fw = fx1 - fx0 + 1, npix = (fy1 - fy0 + 1) * fw;
   const StitchList sl = rs_candidates(win, tile_image, img, n_tiles, fx0, fy0, fx1, fy1);
   const bool staged = rs_want_staged(flags, h, w, OH, OW) && npix <= RS_STAGE_PIX;   // block-uniform; npix <= the rs_span product
@@ -1101,6 +1108,116 @@ __global__ __launch_bounds__(256) void topk_head_resized_multi_kernel(
   topk_head_resized_block<KTOP>(tile_logits + (int64_t)ib.t_first * Q * gh * gw, windows + (int64_t)ib.t_first * 4, tile_image + ib.t_first,
                                 ib.n, ib.n_tiles, Q, gh, gw, up_h, up_w, pad_t, pad_l, h, w, ib.H, ib.W, ib.bx0, ib.by0, flags, query_idx, K,
                                 logit_scale, k, classes + k * ib.off, probs + k * ib.off);
+}
+
+// ---- test-time augmentation: the class probabilities of V views merged at the output size (sg_tta_head) ------------------------------
+// One 64 x 4 block of output pixels walks the views in ascending order.  Per view resized_gather<FLIP> hands the thread its pixel's
+// resized stitched values chunk by chunk (mirrored along the width for a flipped view) and the sink runs label_head_resized_block's
+// online softmax in its chunk order -- the running maximum and sum are that kernel's bytes -- while the largest scaled logit of every
+// class goes to s_cmax[class][thread]: the class of a query is a run-time value, so this is the one dynamically indexed array and it
+// lives in LDS ((K - 1) * 1 KiB, dynamic), each thread reading and writing only its own column (no barrier guards it).  The last class
+// is kept in a register instead: at K = 64 the array is then 63 KiB, and with the 16 KiB stage and the candidate list a workgroup stays
+// under 80 KiB, so two fit a CU (with all 64 KiB one did, and the head took 54.1 instead of 29.9 ms on the bench's three views).  At the end of the
+// view P_v[c] = expf(cmax[c] - vmax) / sum (0 for a class without a query: expf is monotone, so this is the largest probability of the
+// class's queries) is added to P[c], QMAX statically indexed registers.  Then P[c] / V, the arg-max (first maximum) and the threshold.
+//   With V = 1 and no flip, conf is expf(best - vmax) / sum / 1: sg_label_head_resized's bytes, and so is the label unless two classes'
+//   distinct best logits round to one probability (that kernel compares logits, this one the probabilities the definition names).
+//   Barriers: resized_gather's own, plus one at the end of every view -- its direct form ends without one, and the next view's candidate
+//   list and stage reuse the same LDS.  No thread leaves before the last view's barrier; V and every descriptor are block-uniform.
+//   No atomics, nothing proportional to Q * H * W or V * K * H * W; every output element is written by its pixel's thread in an order
+//   fixed by (pixel, view, query).
+constexpr int TTA_MAX_VIEWS = SG_TTA_MAX_VIEWS;
+struct TtaView { int T, t0, gh, gw, up_h, up_w, pad_t, pad_l, h, w, flip; int64_t off; };   // t0: first window; off: first tile-logit element
+struct TtaViews { TtaView v[TTA_MAX_VIEWS]; };
+
+template <int QMAX>
+__global__ __launch_bounds__(256) void tta_head_kernel(const float* __restrict__ tile_logits, const int32_t* __restrict__ windows,
+                                                       const TtaViews views, int V, int Q, int OH, int OW,
+                                                       const int32_t* __restrict__ query_idx, int K, float logit_scale, float prob_thd,
+                                                       int bg_idx, int64_t* __restrict__ labels, float* __restrict__ conf,
+                                                       float* __restrict__ probs, int flags) {
+  extern __shared__ float s_cmax[];                                    // [K - 1][256]; class K - 1 lives in a register (clast)
+  const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * 4;
+  float* cm = s_cmax + threadIdx.x;
+  float P[QMAX];
+#pragma unroll
+  for (int c = 0; c < QMAX; ++c) P[c] = 0.f;
+  bool live = false;
+  for (int v = 0; v < V; ++v) {
+    const TtaView& d = views.v[v];
+    for (int c = 0; c < K - 1; ++c) cm[c * 256] = -INFINITY;
+    float vmax = -INFINITY, sum = 0.f, clast = -INFINITY;
+    live = resized_gather<true>(tile_logits + d.off, windows + (int64_t)d.t0 * 4, nullptr, 0, d.T, Q, d.gh, d.gw, d.up_h, d.up_w, d.pad_t,
+                                d.pad_l, d.h, d.w, OH, OW, bx0, by0, flags, [&](int q0, float (&acc)[ST_QC]) {
+#pragma clang fp contract(off)        // label_head_resized_block's statements: the scaled logit is rounded before the subtraction
+                 float m = -INFINITY;
+#pragma unroll
+                 for (int k = 0; k < ST_QC; ++k)
+                   if (q0 + k < Q) { acc[k] = acc[k] * logit_scale; m = fmaxf(m, acc[k]); }
+                 if (m > vmax) { sum *= expf(vmax - m); vmax = m; }               // the first chunk: sum = 0 * exp(-inf) = 0
+#pragma unroll
+                 for (int k = 0; k < ST_QC; ++k)
+                   if (q0 + k < Q) {
+                     sum += expf(acc[k] - vmax);
+                     const int c = K == Q ? q0 + k : query_idx[q0 + k];
+                     if (c >= 0 && c < K - 1) cm[c * 256] = fmaxf(cm[c * 256], acc[k]);
+                     else if (c == K - 1) clast = fmaxf(clast, acc[k]);
+                   }
+               }, d.flip != 0);
+    if (live) {
+#pragma clang fp contract(off)
+#pragma unroll
+      for (int c = 0; c < QMAX; ++c)
+        if (c < K) {
+          const float m = c < K - 1 ? cm[c * 256] : clast;
+          P[c] += m == -INFINITY ? 0.f : expf(m - vmax) / sum;
+        }
+    }
+    __syncthreads();                                                   // the candidate list and the stage are free for the next view
+  }
+  if (!live) return;
+  const int X = bx0 + (threadIdx.x & 63);
+  const int Y = __builtin_amdgcn_readfirstlane(by0 + (threadIdx.x >> 6));
+  const int64_t plane = (int64_t)OH * OW, o = (int64_t)Y * OW + X;
+  const float fv = (float)V;
+  float best = -INFINITY; int arg = 0;
+#pragma unroll
+  for (int c = 0; c < QMAX; ++c)
+    if (c < K) {
+      const float p = P[c] / fv;
+      if (probs) probs[c * plane + o] = p;
+      if (p > best) { best = p; arg = c; }                             // first maximum wins: ties go to the lower class
+    }
+  labels[o] = best < prob_thd ? bg_idx : arg;
+  if (conf) conf[o] = best;
+}
+
+// The canvas route of the same merge (any Q, any stitch): every view's [K,OH,OW] probability planes come from the existing tail and are
+// added into one accumulator, a flipped view mirrored along the width; sg_tta_finish then divides, takes the arg-max and thresholds with
+// tta_head_kernel's statements.  Plain elementwise kernels.
+__global__ __launch_bounds__(256) void tta_accumulate_kernel(const float* __restrict__ probs_view, int64_t rows, int OW, int flip, int first,
+                                                             float* __restrict__ acc) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows * OW) return;
+  const int64_t r = i / OW;
+  const int x = (int)(i - r * OW);
+  const float p = probs_view[r * OW + (flip ? OW - 1 - x : x)];
+  acc[i] = first ? p : acc[i] + p;
+}
+
+__global__ __launch_bounds__(256) void tta_finish_kernel(const float* acc, int V, int K, int64_t HW, float prob_thd, int bg_idx,
+                                                         int64_t* __restrict__ labels, float* __restrict__ conf, float* probs) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= HW) return;
+  const float fv = (float)V;
+  float best = -INFINITY; int arg = 0;
+  for (int c = 0; c < K; ++c) {
+    const float p = acc[c * HW + i] / fv;
+    if (probs) probs[c * HW + i] = p;                                  // probs may be acc itself: the element is read before it is written
+    if (p > best) { best = p; arg = c; }
+  }
+  labels[i] = best < prob_thd ? bg_idx : arg;
+  if (conf) conf[i] = best;
 }
 
 // ---- postprocess for any Q: several passes over the canvas, nothing held per query ------------------------------------------------
@@ -1891,6 +2008,74 @@ extern "C" int sg_topk_head_resized_multi(const float* tile_logits, const int32_
   hipLaunchKernelGGL(kern, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q, gh, gw, up_h, up_w,
                      pad_t, pad_l, image_hw, image_tiles, out_hw, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale, k, classes,
                      probs, flags);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+// ---- test-time augmentation ---------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(TtaViews) <= 1024, "the view table travels as a kernel argument");
+
+extern "C" int sg_tta_head(const float* tile_logits, int64_t logit_elems, const int32_t* windows, int total_tiles, const int32_t* views, int V,
+                           int Q, int out_h, int out_w, const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx,
+                           int64_t* labels, float* conf, float* probs, int flags, sg_stream s) {
+  SG_REQUIRE(tile_logits && windows && views && query_idx && labels, "sg_tta_head: null pointer");
+  SG_REQUIRE(V >= 1 && V <= SG_TTA_MAX_VIEWS, "sg_tta_head: V=%d views, must lie in [1, %d]", V, SG_TTA_MAX_VIEWS);
+  SG_REQUIRE(Q > 0 && Q <= PP_MAX_Q, "sg_tta_head: Q=%d must lie in [1, %d] (more queries: sg_tta_accumulate / sg_tta_finish)", Q, PP_MAX_Q);
+  SG_REQUIRE(K > 0 && K <= Q, "sg_tta_head: K=%d must lie in [1, Q=%d]", K, Q);
+  SG_REQUIRE(bg_idx >= 0 && bg_idx < K, "sg_tta_head: bg_idx=%d outside [0, K=%d)", bg_idx, K);
+  SG_REQUIRE(out_h > 0 && out_w > 0, "sg_tta_head: bad output size %dx%d", out_h, out_w);
+  SG_REQUIRE(cdiv(out_h, 4) < 65536, "sg_tta_head: output too tall for one launch");
+  SG_RESIZED_REQUIRE_FLAGS("sg_tta_head", flags);
+  TtaViews tv;
+  memset(&tv, 0, sizeof(tv));
+  int64_t tiles = 0, elems = 0;
+  for (int v = 0; v < V; ++v) {
+    const int32_t* f = views + (int64_t)v * SG_TTA_VIEW_FIELDS;
+    TtaView& d = tv.v[v];
+    d.T = f[0]; d.t0 = f[1]; d.gh = f[2]; d.gw = f[3]; d.up_h = f[4]; d.up_w = f[5]; d.pad_t = f[6]; d.pad_l = f[7]; d.h = f[8]; d.w = f[9];
+    d.flip = f[10]; d.off = elems;
+    SG_REQUIRE(d.T > 0 && d.gh > 0 && d.gw > 0 && d.up_h > 0 && d.up_w > 0 && d.pad_t >= 0 && d.pad_l >= 0 && d.h > 0 && d.w > 0,
+               "sg_tta_head: view %d has a bad shape T=%d gh=%d gw=%d up=%dx%d pad=%d,%d H=%d W=%d", v, d.T, d.gh, d.gw, d.up_h, d.up_w, d.pad_t,
+               d.pad_l, d.h, d.w);
+    SG_REQUIRE(d.flip == 0 || d.flip == 1, "sg_tta_head: view %d has flip=%d, neither 0 nor 1", v, d.flip);
+    SG_REQUIRE(d.t0 == tiles, "sg_tta_head: view %d starts at tile %d, but the views before it hold %lld (the views' tiles follow each other)",
+               v, d.t0, (long long)tiles);
+    tiles += d.T;
+    elems += (int64_t)d.T * Q * d.gh * d.gw;
+  }
+  SG_REQUIRE(tiles == total_tiles && elems == logit_elems,
+             "sg_tta_head: the views hold %lld tiles and %lld logits, the buffers %d and %lld", (long long)tiles, (long long)elems, total_tiles,
+             (long long)logit_elems);
+  auto kern = Q <= 16 ? tta_head_kernel<16> : tta_head_kernel<PP_MAX_Q>;
+  const size_t lds = (size_t)(K - 1) * 256 * sizeof(float);        // 63 KiB at K = 64: with the 16 KiB stage two workgroups fit a CU's 160 KiB
+  if (lds > 32 * 1024) SG_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), (size_t)PP_MAX_Q * 256 * sizeof(float)));
+  hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(out_w, 64), (unsigned)cdiv(out_h, 4)), dim3(256), lds, as_stream(s), tile_logits, windows, tv, V, Q,
+                     out_h, out_w, query_idx, K, logit_scale, prob_thd, bg_idx, labels, conf, probs, flags);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_tta_accumulate(const float* probs_view, int K, int out_h, int out_w, int flip, float* acc, int first, sg_stream s) {
+  SG_REQUIRE(probs_view && acc && probs_view != acc, "sg_tta_accumulate: null pointer, or the view's planes are the accumulator");
+  SG_REQUIRE(K > 0 && out_h > 0 && out_w > 0, "sg_tta_accumulate: bad shape K=%d out=%dx%d", K, out_h, out_w);
+  SG_REQUIRE((flip == 0 || flip == 1) && (first == 0 || first == 1), "sg_tta_accumulate: flip=%d first=%d, each 0 or 1", flip, first);
+  const int64_t rows = (int64_t)K * out_h, n = rows * out_w;
+  SG_REQUIRE(cdiv(n, 256) <= INT32_MAX, "sg_tta_accumulate: too large for one launch");
+  hipLaunchKernelGGL(tta_accumulate_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, as_stream(s), probs_view, rows, out_w, flip, first, acc);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
+extern "C" int sg_tta_finish(const float* acc, int V, int K, int out_h, int out_w, float prob_thd, int bg_idx, int64_t* labels, float* conf,
+                             float* probs, sg_stream s) {
+  SG_REQUIRE(acc && labels, "sg_tta_finish: null pointer");
+  SG_REQUIRE(V >= 1 && V <= SG_TTA_MAX_VIEWS, "sg_tta_finish: V=%d views, must lie in [1, %d]", V, SG_TTA_MAX_VIEWS);
+  SG_REQUIRE(K > 0 && out_h > 0 && out_w > 0, "sg_tta_finish: bad shape K=%d out=%dx%d", K, out_h, out_w);
+  SG_REQUIRE(bg_idx >= 0 && bg_idx < K, "sg_tta_finish: bg_idx=%d outside [0, K=%d)", bg_idx, K);
+  const int64_t HW = (int64_t)out_h * out_w;
+  SG_REQUIRE(cdiv(HW, 256) <= INT32_MAX, "sg_tta_finish: too large for one launch");
+  hipLaunchKernelGGL(tta_finish_kernel, dim3((unsigned)cdiv(HW, 256)), dim3(256), 0, as_stream(s), acc, V, K, HW, prob_thd, bg_idx, labels, conf,
+                     probs);
   SG_LAUNCH_CHECK();
   return SG_OK;
 }

@@ -696,6 +696,105 @@ def topk_head_resized_multi(tile_logits, windows, tile_image, up_hw, pad_tl, ima
     return flat_views(classes, kk, out_hw), flat_views(probs, kk, out_hw)
 
 
+TTA_MAX_VIEWS = 8                                                        # SG_TTA_MAX_VIEWS (include/segearth_hip.h)
+TTA_VIEW_FIELDS = 11                                                     # SG_TTA_VIEW_FIELDS
+TTA_MAX_Q = POSTPROCESS_MAX_Q                                            # sg_tta_head's bound on Q; beyond: tta_accumulate / tta_finish
+
+
+def tta_views(hw, scales, flip: bool = False):
+    """The views of test-time augmentation for an image of ``hw``: ``scales`` x ({False, True} if ``flip`` else {False}), scale outer
+    -> [(scale, flipped, (h, w))] with (h, w) = (max(1, int(H * s + 0.5)), max(1, int(W * s + 0.5))).  ``scales=None`` means (1.0,).
+    A pure function (no device); more than TTA_MAX_VIEWS views, no view or a scale that is no positive finite number is refused."""
+    H, W = int(hw[0]), int(hw[1])
+    if H <= 0 or W <= 0:
+        raise ValueError(f"tta_views: bad image size {tuple(hw)}")
+    scales = (1.0,) if scales is None else tuple(float(s) for s in ([scales] if isinstance(scales, (int, float)) else scales))
+    if not scales or any(not (s > 0.0 and s != float("inf")) for s in scales):
+        raise ValueError(f"tta_scales must be a non-empty sequence of positive finite numbers, got {scales!r}")
+    views = [(s, f, (max(1, int(H * s + 0.5)), max(1, int(W * s + 0.5)))) for s in scales for f in ((False, True) if flip else (False,))]
+    if len(views) > TTA_MAX_VIEWS:
+        raise ValueError(f"test-time augmentation takes at most {TTA_MAX_VIEWS} views, got {len(views)} ({len(scales)} scales"
+                         f"{' x 2 for the flip' if flip else ''})")
+    return views
+
+
+@on_tensor_device
+def tta_head(views, out_hw, query_idx, num_classes: int, logit_scale: float, prob_thd: float, bg_idx: int, want_conf: bool = False,
+             want_probs: bool = False, form: str = "auto"):
+    """sg_tta_head: the class probabilities of V views of one image merged at ``out_hw`` in one launch, no canvas and no per-view planes
+    (the definition: include/segearth_hip.h).  ``views``: [(tile_logits [T_v,Q,gh_v,gw_v], windows int32 [T_v,4], up_hw, pad_tl,
+    canvas_hw, flipped)] in merge order.  -> labels int64 [1,H,W], then conf f32 [H,W] with ``want_conf`` and the mean planes f32
+    [K,H,W] with ``want_probs`` (a tuple when either is asked).  The views' tile logits are copied into one buffer (one view: used as
+    it is).  ``form``: as ``label_head_resized``, per view; a view that does not fit the stage runs direct."""
+    if form not in RESIZED_FORMS:
+        raise ValueError(f"tta_head: form={form!r} is none of {sorted(RESIZED_FORMS)}")
+    if not 1 <= len(views) <= TTA_MAX_VIEWS:
+        raise ValueError(f"tta_head: {len(views)} views, must lie in [1, {TTA_MAX_VIEWS}]")
+    lib = _lib.load()
+    tls, wins, table, first = [], [], [], 0
+    dev, Q = None, None
+    for v, (tl, win, up_hw, pad_tl, canvas_hw, flipped) in enumerate(views):
+        tl = _f32(tl)
+        _require_gpu(tl)
+        T, q, gh, gw = tl.shape
+        dev, Q = (tl.device, q) if dev is None else (dev, Q)
+        win = torch.as_tensor(win, dtype=torch.int32).to(dev).contiguous()
+        if q != Q or int(win.numel()) != 4 * T or tl.device != dev:
+            raise ValueError(f"tta_head: view {v} has {T} tiles of {q} queries and {win.numel() // 4} windows; the first view has {Q} queries")
+        tls.append(tl.reshape(-1)); wins.append(win.reshape(-1, 4))
+        table.append([T, first, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1], canvas_hw[0], canvas_hw[1], int(bool(flipped))])
+        first += T
+    qi = query_idx.to(device=dev, dtype=torch.int32).contiguous()
+    if int(qi.numel()) != Q:
+        raise ValueError(f"tta_head: {Q} queries but {qi.numel()} query indices")
+    logits = tls[0] if len(tls) == 1 else torch.cat(tls)
+    windows = wins[0] if len(wins) == 1 else torch.cat(wins)
+    desc = (C.c_int32 * (len(table) * TTA_VIEW_FIELDS))(*[int(x) for row in table for x in row])
+    H, W = (int(v) for v in out_hw)
+    K = int(num_classes)
+    labels = torch.empty(1, H, W, dtype=torch.int64, device=dev)
+    conf = torch.empty(H, W, dtype=torch.float32, device=dev) if want_conf else None
+    probs = torch.empty(K, H, W, dtype=torch.float32, device=dev) if want_probs else None
+    check(lib.sg_tta_head(ptr(logits), int(logits.numel()), ptr(windows), first, desc, len(table), Q, H, W, ptr(qi), K, float(logit_scale),
+                          float(prob_thd), int(bg_idx), ptr(labels), ptr(conf), ptr(probs), RESIZED_FORMS[form], stream_ptr()), "sg_tta_head")
+    out = (labels,) + ((conf,) if want_conf else ()) + ((probs,) if want_probs else ())
+    return out if len(out) > 1 else labels
+
+
+@on_tensor_device
+def tta_accumulate(probs_view, flipped: bool, acc=None):
+    """sg_tta_accumulate: ``acc`` += one view's probability planes f32 [K,H,W] (mirrored along the width when ``flipped``), IN PLACE;
+    ``acc=None`` starts a new accumulator with this view.  -> acc."""
+    lib = _lib.load()
+    p = _f32(probs_view)
+    _require_gpu(p)
+    K, H, W = p.shape
+    first = acc is None
+    if first:
+        acc = torch.empty_like(p)
+    elif tuple(acc.shape) != (K, H, W) or acc.dtype != torch.float32 or not acc.is_contiguous() or acc.device != p.device:
+        raise ValueError(f"tta_accumulate: the accumulator must be a contiguous f32 {(K, H, W)} tensor on the view's device")
+    check(lib.sg_tta_accumulate(ptr(p), K, H, W, int(bool(flipped)), ptr(acc), int(first), stream_ptr()), "sg_tta_accumulate")
+    return acc
+
+
+@on_tensor_device
+def tta_finish(acc, n_views: int, prob_thd: float, bg_idx: int, want_conf: bool = False, want_probs: bool = False):
+    """sg_tta_finish: the accumulator of ``n_views`` views -> labels int64 [1,H,W], then conf f32 [H,W] with ``want_conf`` and the mean
+    planes with ``want_probs`` -- written IN PLACE over ``acc``, which is what is returned (a tuple when either is asked)."""
+    lib = _lib.load()
+    _require_gpu(acc)
+    if acc.dtype != torch.float32 or not acc.is_contiguous() or acc.dim() != 3:
+        raise ValueError("tta_finish: the accumulator must be a contiguous f32 [K,H,W] tensor")
+    K, H, W = acc.shape
+    labels = torch.empty(1, H, W, dtype=torch.int64, device=acc.device)
+    conf = torch.empty(H, W, dtype=torch.float32, device=acc.device) if want_conf else None
+    check(lib.sg_tta_finish(ptr(acc), int(n_views), K, H, W, float(prob_thd), int(bg_idx), ptr(labels), ptr(conf),
+                            ptr(acc) if want_probs else None, stream_ptr()), "sg_tta_finish")
+    out = (labels,) + ((conf,) if want_conf else ()) + ((acc,) if want_probs else ())
+    return out if len(out) > 1 else labels
+
+
 def topk_from_probs(probs, query_idx, k: int):
     """The canvas-route equivalent of ``topk_head`` in torch (host or device tensors): class probabilities [K,H,W] (what ``postprocess``
     returns) -> (classes int32 [k,H,W], probs f32 [k,H,W]) by a stable descending sort over the classes, so equal values keep ascending

@@ -356,6 +356,9 @@ def tile_geometry(tile_hw: Tuple[int, int], patch: int) -> TileGeometry:
 # The routes of a tail (DESIGN.md section 5 'Route table'): a head on the tile logits (no canvas), a resized head on the tile logits (no
 # canvas, another ori_shape), or the stitched canvas with one multi-image post-process per flush group / image by image.
 HEAD, RESIZED_HEAD, CANVAS_MULTI, CANVAS_EACH = "head", "resized_head", "canvas_multi", "canvas_each"
+# Test-time augmentation on (tta_scales / tta_flip): the views' class probabilities merged at the output size, by sg_tta_head on the
+# views' tile logits (no canvas, no per-view planes) or view by view through the canvas and sg_tta_accumulate / sg_tta_finish.
+TTA_HEAD, TTA_CANVAS = "tta_head", "tta_canvas"
 
 
 @dataclass(frozen=True)
@@ -375,6 +378,46 @@ RESIZE_HEADS = ("canvas", "fused")
 # measured no slower than the canvas route at both Q = 130 and Q = 256.  It was slower at both (13.9 against 10.5 ms and 28.8 against
 # 20.3 ms, profiles/r08_bench_prob_head.jsonl, DESIGN.md section 5 'Probability head'), so "auto" is the canvas route everywhere.
 PROB_HEAD_AUTO_FUSED_BEYOND_MAX_Q = False
+
+
+TTA_HEADS = ("auto", "fused", "canvas")
+# What tta_head="auto" takes where the fused head can run: the fused head unless tools/bench_tta.py showed it slower than the canvas
+# route.  It did, on every case of profiles/bench_tta.jsonl (2048 x 4608, scales 0.75 / 1.0 / 1.25): 4.65 against 4.29 ms at Q = 16 and
+# 29.9 against 27.9 ms at Q = 64 with three views, 9.12 against 8.32 and 63.8 against 54.9 ms with six -- so "auto" is the canvas route,
+# and "fused" is the choice for memory: 0.1 to 0.3 GB beyond the tile logits for labels where the canvas route takes 2.2 GB (Q = 16) or
+# 8.6 GB (Q = 64) (DESIGN.md section 5 'Test-time augmentation').
+TTA_AUTO_FUSED = False
+
+
+TTA_TILE_GROUP = ("test-time augmentation under tile_group sharding is not built: every view has its own canvas bands, so a rank's band "
+                  "of the output would need all views' tiles that map into it; run the views on whole images per rank")
+
+
+TTA_PAMR = ("test-time augmentation together with PAMR is not built: the guide image would have to follow each view (resized and "
+            "mirrored) and every view's canvas be refined before its probabilities are merged; use one or the other")
+
+
+TTA_AREA = ("test-time augmentation together with area_thd is not built: the class areas would have to be counted on the merged "
+            "arg-max and the mean probabilities filtered afterwards; use one or the other")
+
+
+TTA_TOPK = ("top-k together with test-time augmentation is not built: the k best classes would have to be ranked on the merged mean "
+            "probabilities, which the top-k head never sees; run predict_topk / topk= on an instance without tta_scales / tta_flip")
+
+
+def tta_view_scene(scene: torch.Tensor, hw, flipped: bool) -> torch.Tensor:
+    """One view of test-time augmentation: ``scene`` (u8 [H,W,3] or f32 [3,H,W]) resized to ``hw`` -- torch plumbing on the scene's
+    device: f32, F.interpolate(bilinear, align_corners=False, antialias=False), a u8 scene rounded to nearest and clamped back to
+    u8 -- and then mirrored along the width when ``flipped``.  At the scene's own size without flip: the scene object itself."""
+    u8 = scene.dtype == torch.uint8
+    v = scene
+    if tuple(int(x) for x in hw) != _scene_hw(scene):
+        x = (scene.permute(2, 0, 1) if u8 else scene).float().unsqueeze(0)
+        x = torch.nn.functional.interpolate(x, size=tuple(int(v_) for v_ in hw), mode="bilinear", align_corners=False, antialias=False)[0]
+        v = x.round().clamp_(0, 255).to(torch.uint8).permute(1, 2, 0) if u8 else x
+    if flipped:
+        v = torch.flip(v, dims=[1 if u8 else 2])
+    return v if v is scene else v.contiguous()
 
 
 PAMR_TILE_GROUP = ("PAMR under tile_group sharding is not built: a rank's canvas band would need a halo of pamr_steps * max(pamr_stride) "
@@ -412,6 +455,7 @@ class SegPipeline:
     min_region, region_connectivity, region_fill = None, 4, "neighbour"      # the sieve off likewise
     label_head, prob_head, resize_head = "auto", "auto", "canvas"
     blend, blend_ramp = "uniform", None       # weighted window blending off likewise
+    tta_scales, tta_flip, tta_head = None, False, "auto"      # test-time augmentation off likewise
     apply_ctd, apply_layer_fusion, layer_fusion_lambda = False, False, 0.5
     cross_tile_fusion = tile_group = upsampler = None
 
@@ -421,7 +465,26 @@ class SegPipeline:
                  upsampler=None, tiles_per_launch: int = 32, cross_tile_fusion: Optional[dict] = None, apply_ctd: bool = False,
                  tile_group=None, apply_layer_fusion: bool = False, layer_fusion_lambda: float = 0.5, label_head: str = "auto",
                  prob_head: str = "auto", pamr_steps: int = 0, pamr_stride=(8, 16), resize_head: str = "canvas", area_thd=None,
-                 min_region=None, region_connectivity: int = 4, region_fill: str = "neighbour", blend: str = "uniform", blend_ramp=None):
+                 min_region=None, region_connectivity: int = 4, region_fill: str = "neighbour", blend: str = "uniform", blend_ramp=None,
+                 tta_scales=None, tta_flip: bool = False, tta_head: str = "auto"):
+        # Test-time augmentation (tta_scales=None and tta_flip=False = off, and then no call changes route, launches or bytes): every
+        # image is run as the views ops.tta_views lists -- resized by each scale, and mirrored too with tta_flip; tta_flip alone means
+        # scales (1.0,) -- each slid with this instance's stride / crop and tower options, and the views' class probabilities are averaged
+        # at the output size before the arg-max and prob_thd (the definition: include/segearth_hip.h).  tta_head: "fused" = sg_tta_head
+        # on the views' tile logits, "canvas" = view by view through the canvas and sg_tta_accumulate / sg_tta_finish, "auto" = what
+        # was measured faster, the canvas route (TTA_AUTO_FUSED).  "fused" where the fused head cannot run is refused
+        # (``tta_fused_reason``).  The views are refused with tile_group, PAMR, area_thd and top-k.
+        if tta_head not in TTA_HEADS:
+            raise ValueError(f"tta_head must be one of {TTA_HEADS}, got {tta_head!r}")
+        self.tta_scales = None if tta_scales is None else tuple(
+            float(s) for s in ([tta_scales] if isinstance(tta_scales, (int, float)) else tta_scales))
+        self.tta_flip, self.tta_head = bool(tta_flip), tta_head
+        if self.tta_on():
+            ops.tta_views((64, 64), self.tta_scales, self.tta_flip)         # the scales and the number of views, before anything else
+            if pamr_steps:
+                raise ValueError(TTA_PAMR)
+            if area_thd is not None:
+                raise ValueError(TTA_AREA)
         # blend ("uniform" = off, and then no call changes route, launches or bytes): overlapping windows are combined by a weighted mean,
         # each tile weighted by a ramp ("linear" or "hann", ops.blend_ramp) of the pixel's distance to the tile's own window edges
         # (sg_stitch_blend; the definition: include/segearth_hip.h), which takes the step out of the stitched logits where a window starts
@@ -492,6 +555,8 @@ class SegPipeline:
         if self.area_thd is not None:
             ops.area_args("area_thd", self.num_classes, self.bg_idx, self.area_thd)
         self._check_sharding(tile_group is not None)
+        if self.tta_on() and self.tta_head == "fused" and self.tta_fused_reason() is not None:
+            raise ValueError(f"tta_head='fused' cannot serve this instance: {self.tta_fused_reason()}; use tta_head='canvas' or 'auto'")
 
     def _stitch(self, tile_logits, windows, up_hw, pad_tl, canvas_hw, ramp=None):
         if ramp is not None:
@@ -532,12 +597,31 @@ class SegPipeline:
         """Whether labels / top-k at another ``ori_shape`` run the resized heads (no canvas) instead of stitch + resize + post-process."""
         return self.resize_head == "fused" and self.pamr_steps == 0 and self.area_thd is None
 
+    def tta_on(self) -> bool:
+        return self.tta_scales is not None or bool(self.tta_flip)
+
+    def tta_fused_reason(self):
+        """Why sg_tta_head cannot serve this instance, or None: it stitches unweighted patch-grid tile logits of at most 64 queries."""
+        if self.num_queries > ops.TTA_MAX_Q:
+            return f"{self.num_queries} queries exceed the fused head's {ops.TTA_MAX_Q}"
+        if self.blend != "uniform":
+            return f"blend={self.blend!r} needs the weighted stitch, which only the canvas route has"
+        if self.upsampler is not None:
+            return "the JBU upsampler's per-pixel tile logits take the canvas route"
+        return None
+
+    def tta_fused(self) -> bool:
+        """Whether the merge of the views runs sg_tta_head (sliding-window inference; whole-image inference has no tiles)."""
+        return self.tta_head != "canvas" and self.tta_fused_reason() is None and (self.tta_head == "fused" or TTA_AUTO_FUSED)
+
     def topk_k(self, topk) -> int:
         """``topk`` checked against what sg_topk_head takes: 1 .. min(ops.TOPK_MAX, the number of classes)."""
         if self.area_thd is not None:
             raise ValueError(AREA_TOPK)
         if self.min_region is not None:
             raise ValueError(SIEVE_TOPK)
+        if self.tta_on():
+            raise ValueError(TTA_TOPK)
         k = int(topk)
         if not 1 <= k <= min(ops.TOPK_MAX, self.num_classes):
             raise ValueError(f"topk must lie in [1, min({ops.TOPK_MAX}, {self.num_classes} classes)], got {topk!r}")
@@ -560,6 +644,8 @@ class SegPipeline:
             raise ValueError(AREA_TILE_GROUP)
         if sharded and self.min_region is not None:
             raise ValueError(SIEVE_TILE_GROUP)
+        if sharded and self.tta_on():
+            raise ValueError(TTA_TILE_GROUP)
 
     def _canvas_bytes(self) -> int:
         """Per pixel of a canvas route: the [Q,H,W] canvas, and with area_thd the probability planes and labels, which then always exist."""
@@ -569,6 +655,11 @@ class SegPipeline:
         """THE route decision.  ``want``: "labels", "probs" or "topk" (then ``k``); ``differs``: some ``ori_shape`` is another size than
         its image; ``given``: some ``ori_shape`` is given at all -- the packed labels-only tail takes the fused head only when none is,
         an ``ori_shape`` equal to the image's size keeps the canvas there."""
+        if self.tta_on():                      # per OUTPUT pixel: labels and conf, the mean planes; the canvas route also one view's
+            K = self.num_classes               # planes and its resized canvas.  The views' tile logits come on top of either.
+            if self.tta_fused():
+                return TailRoute(TTA_HEAD, 8 + (4 * K if want == "probs" else 0))
+            return TailRoute(TTA_CANVAS, 8 + 8 * K + 4 * self.num_queries)
         blended = self.blend != "uniform"      # only the label head has a blended form, and sg_area_relabel gathers unweighted
         if self.pamr_steps == 0:
             if want == "topk" and not differs and not blended:
@@ -952,6 +1043,8 @@ class SegPipeline:
         sharded = group is not None or self.tile_group is not None
         self._check_sharding(sharded)
         want, k = self._wanted("segment_scene", want_probs, topk, sharded)
+        if self.tta_on():                                       # sharding and top-k were refused above
+            return self.tta_image(scene, stride, crop, ori_shape, want_probs)
         resize = ori_shape is not None and tuple(ori_shape) != _scene_hw(scene)
         if resize and want_probs:
             raise ValueError("segment_scene: class probabilities at another ori_shape are not built here; use segment_scenes")
@@ -976,6 +1069,45 @@ class SegPipeline:
         if not gather_labels:
             return lab, y0
         return self.gather_bands(lab, yb, yb[-1], group)
+
+    def tta_image(self, scene: torch.Tensor, stride, crop, ori_shape=None, want_probs: bool = False):
+        """Test-time augmentation for one image -> labels int64 [1,H,W], or (mean probs f32 [K,H,W], labels) with ``want_probs``;
+        (H, W) = ``ori_shape`` or the image's size.  Every view of ``ops.tta_views`` is made by ``tta_view_scene`` and slid like any
+        image (``tile_logits``, so ``tiles_per_launch`` holds).  TTA_HEAD: the views' tile logits are kept and sg_tta_head merges them
+        in one launch.  TTA_CANVAS: view by view stitch -> resize to (H, W) -> the probability tail -> sg_tta_accumulate, one view's
+        planes and the accumulator alive at a time, then sg_tta_finish.  ``crop`` <= 0 (or None): whole-image inference per view
+        (``forward_feature`` at (H, W)), always view by view.  ``min_region`` follows on the final labels."""
+        scene = scene.to(self.device)
+        H, W = _scene_hw(scene)
+        out_hw = (H, W) if ori_shape is None else tuple(int(v) for v in ori_shape)
+        whole = crop is None or (isinstance(crop, int) and crop <= 0)
+        fused = not whole and self.tail_route("probs" if want_probs else "labels").route == TTA_HEAD
+        views, acc = [], None
+        post = (self.query_idx, self.num_classes, self.logit_scale)
+        listed = ops.tta_views((H, W), self.tta_scales, self.tta_flip)
+        for _, flipped, hw in listed:
+            view = tta_view_scene(scene, hw, flipped)
+            if whole:
+                planes = ops.scene_planes(view) if view.dtype == torch.uint8 else view
+                canvas = self.forward_feature(planes.float().unsqueeze(0), out_hw)[0]
+            else:
+                h, w, _, _, wins, tile_hw, pad_tl, up_hw, grid = self._geometry(view, stride, crop)
+                tl = self.tile_logits(view, wins, tile_hw, grid_of_tiles=grid)
+                win_dev = torch.tensor(wins, dtype=torch.int32, device=self.device)
+                if fused:
+                    views.append((tl, win_dev, up_hw, pad_tl, (h, w), flipped))
+                    continue
+                canvas = self._stitched(tile_hw, tl, win_dev, up_hw, pad_tl, (h, w))
+                if (h, w) != out_hw:
+                    canvas = ops.resize_bilinear(canvas, out_hw)
+            probs, _ = ops.postprocess(canvas, *post, 0.0, self.bg_idx, True)
+            acc = ops.tta_accumulate(probs, flipped, acc)
+        if fused:
+            out = ops.tta_head(views, out_hw, *post, self.prob_thd, self.bg_idx, want_probs=want_probs)
+        else:
+            out = ops.tta_finish(acc, len(listed), self.prob_thd, self.bg_idx, want_probs=want_probs)
+        labels = self.sieve(out[0] if want_probs else out)
+        return (out[1], labels) if want_probs else labels
 
     def gather_tile_logits(self, scene, wins, tile_hw, world, rank, group=None, grid_of_tiles=None) -> torch.Tensor:
         """Rank r computes a contiguous block of the raster tile list; one all-gather (RCCL over xGMI on GPUs)
@@ -1081,6 +1213,13 @@ class SegPipeline:
         Which kernels run is decided once for the call by ``tail_route`` and applied per flush group by ``_group_tail``; every route
         returns the same bytes (DESIGN.md section 5 'Route table')."""
         want, k = self._wanted("label_groups", want_probs, topk, self.tile_group is not None)
+        if self.tta_on():                                       # image by image through the single-image merge: one group per image
+            self._check_sharding(self.tile_group is not None)
+            for i, im in enumerate(_images(scenes)):
+                out = self.tta_image(im, stride, crop, None if ori_shapes is None else ori_shapes[i], want_probs)
+                lab = out[1] if want_probs else out
+                yield [i], [out[0] if want_probs else None], [lab], lab.view(-1)
+            return
         given = ori_shapes is not None and any(o is not None for o in ori_shapes)
         route = self.tail_route(want, k, given, _ori_differs(ori_shapes, scenes))
         pixel_bytes = route.pixel_bytes

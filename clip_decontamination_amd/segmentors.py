@@ -141,9 +141,24 @@ class _HipSegmentorBase(_Base):
                checkpoint=None, text_features=None, text_encoder: Optional[Callable] = None, precision="f16x2",
                synthetic_ok=False, tiles_per_launch=None, jbu_checkpoint_ok=True, tokenizer: Optional[Callable] = None, tile_group=None,
                label_head="auto", prob_head="auto", pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas", area_thd=None,
-               min_region=None, region_connectivity=4, region_fill="neighbour", blend="uniform", blend_ramp=None):
+               min_region=None, region_connectivity=4, region_fill="neighbour", blend="uniform", blend_ramp=None,
+               tta_scales=None, tta_flip=False, tta_head="auto"):
         from . import ops
-        from .pipeline import AREA_TILE_GROUP, LABEL_HEADS, PAMR_TILE_GROUP, PROB_HEADS, RESIZE_HEADS, SIEVE_TILE_GROUP
+        from .pipeline import (AREA_TILE_GROUP, LABEL_HEADS, PAMR_TILE_GROUP, PROB_HEADS, RESIZE_HEADS, SIEVE_TILE_GROUP, TTA_AREA, TTA_HEADS,
+                               TTA_PAMR, TTA_TILE_GROUP)
+        # Test-time augmentation (tta_scales=None and tta_flip=False = off): predict / predict_many / predict_regions / evaluate run every
+        # image as the views ops.tta_views lists and average the views' class probabilities at ori_shape before the arg-max (SegPipeline;
+        # the definition: include/segearth_hip.h); seg_logits are the mean planes.  forward_slide / forward_feature return the logits of
+        # the image as it is.  Refused with tile_group, PAMR, area_thd and predict_topk.
+        if tta_head not in TTA_HEADS:
+            raise ValueError(f"tta_head must be one of {TTA_HEADS}, got {tta_head!r}")
+        self.tta_scales = None if tta_scales is None else tuple(float(v) for v in ([tta_scales] if isinstance(tta_scales, (int, float)) else tta_scales))
+        self.tta_flip, self.tta_head = _to_bool(tta_flip), tta_head
+        if self.tta_scales is not None or self.tta_flip:
+            ops.tta_views((64, 64), self.tta_scales, self.tta_flip)
+            for on, why in ((tile_group is not None, TTA_TILE_GROUP), (int(pamr_steps) > 0, TTA_PAMR), (area_thd is not None, TTA_AREA)):
+                if on:
+                    raise ValueError(why)
         # blend ("uniform" = off) / blend_ramp: overlapping windows combined by a ramp-weighted mean instead of the plain one (SegPipeline;
         # the definition: include/segearth_hip.h).  Whole-image inference (slide_crop <= 0) has no windows and ignores it.
         self.blend, self.blend_ramp = ops.blend_args(blend, blend_ramp)
@@ -294,7 +309,9 @@ class _HipSegmentorBase(_Base):
                            pamr_stride=getattr(self, "pamr_stride", (8, 16)), resize_head=getattr(self, "resize_head", "canvas"),
                            area_thd=getattr(self, "area_thd", None), min_region=getattr(self, "min_region", None),
                            region_connectivity=getattr(self, "region_connectivity", 4), region_fill=getattr(self, "region_fill", "neighbour"),
-                           blend=getattr(self, "blend", "uniform"), blend_ramp=getattr(self, "blend_ramp", None))
+                           blend=getattr(self, "blend", "uniform"), blend_ramp=getattr(self, "blend_ramp", None),
+                           tta_scales=getattr(self, "tta_scales", None), tta_flip=getattr(self, "tta_flip", False),
+                           tta_head=getattr(self, "tta_head", "auto"))
 
     def forward_feature(self, img, logit_size=None, tile_h_idx=None, tile_w_idx=None):
         """Reference segmentor.py:286-392.  img [B,3,H,W] -> logits [B,Q,h,w]."""
@@ -335,6 +352,15 @@ class _HipSegmentorBase(_Base):
             batch_img_metas = [dict(ori_shape=inputs.shape[2:], img_shape=inputs.shape[2:], pad_shape=inputs.shape[2:],
                                     padding_size=[0, 0, 0, 0])] * inputs.shape[0]
         inputs = inputs.float()
+        if getattr(self, "tta_scales", None) is not None or getattr(self, "tta_flip", False):
+            # test-time augmentation: every image through SegPipeline.tta_image at its ori_shape (sliding windows or whole image)
+            pipe = self._pipeline()
+            if data_samples is None:
+                return pipe.tta_image(inputs[0], self.slide_stride, self.slide_crop)
+            for i, ds in enumerate(data_samples):
+                probs, labels = pipe.tta_image(inputs[i], self.slide_stride, self.slide_crop, tuple(batch_img_metas[i]["ori_shape"][:2]), True)
+                self._fill_sample(ds, probs, labels, i)
+            return data_samples
         if data_samples is None and self.slide_crop > 0:
             # labels only, at the image's own size, of the first image (what postprocess_result returns without data samples): the
             # labels-only tail, which needs no canvas with the fused head (``label_head``)
@@ -392,6 +418,13 @@ class _HipSegmentorBase(_Base):
             raise ValueError(f"predict_many: {n} images but {len(data_samples)} data samples")
         if ori_shapes is not None and len(ori_shapes) != n:
             raise ValueError(f"predict_many: {n} images but {len(ori_shapes)} ori_shapes")
+        if self.slide_crop <= 0 and (getattr(self, "tta_scales", None) is not None or getattr(self, "tta_flip", False)):
+            pipe = self._pipeline()                          # whole-image inference under test-time augmentation: image by image
+            if data_samples is None:
+                return [pipe.tta_image(imgs[i], None, None, None if ori_shapes is None else ori_shapes[i]) for i in range(n)]
+            for i, ds in enumerate(data_samples):
+                self._fill_sample(ds, *pipe.tta_image(imgs[i], None, None, tuple(ds.metainfo["ori_shape"][:2]), True), i)
+            return data_samples
         if self.slide_crop <= 0:                             # whole-image inference (forward_feature) has no windows to pack
             if data_samples is None and ori_shapes is not None:
                 pipe = self._pipeline()
@@ -498,9 +531,11 @@ class _HipSegmentorBase(_Base):
         (stitch, resize, PAMR, post-process) and ``ops.topk_from_probs`` sorts its probabilities -- except that with
         ``resize_head="fused"`` and no PAMR another ``ori_shape`` runs sg_topk_head_resized_multi, one launch per flush group and no
         canvas.  ``tile_group`` sharding is refused."""
-        from .pipeline import AREA_TOPK, SIEVE_TOPK, TOPK_TILE_GROUP
+        from .pipeline import AREA_TOPK, SIEVE_TOPK, TOPK_TILE_GROUP, TTA_TOPK
         if getattr(self, "tile_group", None) is not None:
             raise ValueError(TOPK_TILE_GROUP)
+        if getattr(self, "tta_scales", None) is not None or getattr(self, "tta_flip", False):
+            raise ValueError(TTA_TOPK)
         if getattr(self, "area_thd", None) is not None:
             raise ValueError(AREA_TOPK)
         if getattr(self, "min_region", None) is not None:
@@ -679,7 +714,7 @@ class SegmentorEx(_HipSegmentorBase):
                  checkpoint=None, text_features=None, text_encoder=None, precision="f16x2", synthetic_ok=False, tiles_per_launch=None,
                  tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, pack_images=False, label_head="auto", prob_head="auto",
                  pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas", area_thd=None, min_region=None, region_connectivity=4,
-                 region_fill="neighbour", blend="uniform", blend_ramp=None):
+                 region_fill="neighbour", blend="uniform", blend_ramp=None, tta_scales=None, tta_flip=False, tta_head="auto"):
         data_preprocessor = SegDataPreProcessor(mean=list(Wt.PIXEL_MEAN), std=list(Wt.PIXEL_STD), bgr_to_rgb=True)
         super().__init__(data_preprocessor=data_preprocessor)
         if model_type == "GEM":
@@ -690,7 +725,8 @@ class SegmentorEx(_HipSegmentorBase):
                              checkpoint, text_features, text_encoder, precision, synthetic_ok, tiles_per_launch, tokenizer=tokenizer,
                              tile_group=tile_group, label_head=label_head, prob_head=prob_head, pamr_steps=pamr_steps, pamr_stride=pamr_stride,
                              resize_head=resize_head, area_thd=area_thd, min_region=min_region, region_connectivity=region_connectivity,
-                             region_fill=region_fill, blend=blend, blend_ramp=blend_ramp)
+                             region_fill=region_fill, blend=blend, blend_ramp=blend_ramp, tta_scales=tta_scales, tta_flip=tta_flip,
+                             tta_head=tta_head)
         # opt-in extra: kwargs of the reference's CrossTileFusion (cross_tile_fusion.py:24-60), which the reference never calls (R2)
         self.cross_tile_fusion_cfg = cross_tile_fusion_cfg
         self.apply_ctd = _to_bool(apply_ctd)                                # segmentor.py:184-194, 339-365: DBSCAN + cluster debias, on the device here
@@ -726,7 +762,8 @@ class Segmentor(_HipSegmentorBase):
                  checkpoint=None, text_features=None, text_encoder=None, precision="f16x2", synthetic_ok=False, tiles_per_launch=None,
                  tokenizer=None, cross_tile_fusion_cfg=None, tile_group=None, apply_outlier_suppression=False, outlier_suppression_cfg=None,
                  pack_images=False, label_head="auto", prob_head="auto", pamr_steps=0, pamr_stride=(8, 16), resize_head="canvas",
-                 area_thd=None, min_region=None, region_connectivity=4, region_fill="neighbour", blend="uniform", blend_ramp=None):
+                 area_thd=None, min_region=None, region_connectivity=4, region_fill="neighbour", blend="uniform", blend_ramp=None,
+                 tta_scales=None, tta_flip=False, tta_head="auto"):
         data_preprocessor = SegDataPreProcessor(mean=list(Wt.PIXEL_MEAN), std=list(Wt.PIXEL_STD), bgr_to_rgb=True)
         super().__init__(data_preprocessor=data_preprocessor)
         if model_type == "GEM" and cls_token_lambda != 0:
@@ -736,7 +773,8 @@ class Segmentor(_HipSegmentorBase):
                     checkpoint, text_features, text_encoder, precision, synthetic_ok, tiles_per_launch, tokenizer=tokenizer,
                     tile_group=tile_group, label_head=label_head, prob_head=prob_head, pamr_steps=pamr_steps, pamr_stride=pamr_stride,
                              resize_head=resize_head, area_thd=area_thd, min_region=min_region, region_connectivity=region_connectivity,
-                             region_fill=region_fill, blend=blend, blend_ramp=blend_ramp)
+                             region_fill=region_fill, blend=blend, blend_ramp=blend_ramp, tta_scales=tta_scales, tta_flip=tta_flip,
+                             tta_head=tta_head)
         # opt-in extra: kwargs of the reference's CrossTileFusion (cross_tile_fusion.py:24-60), which the reference never calls (R2)
         self.cross_tile_fusion_cfg = cross_tile_fusion_cfg
         self.output_cls_token = cls_token_lambda != 0

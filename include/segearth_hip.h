@@ -390,6 +390,45 @@ int sg_topk_head_resized_multi(const float* tile_logits, const int32_t* windows,
                                const int32_t* out_hw, const int64_t* out_offset, const int64_t* block_prefix, int N, int64_t total_blocks,
                                int64_t out_pixels, const int32_t* query_idx, int K, float logit_scale, int k, int32_t* classes,
                                float* probs, int flags, sg_stream s);
+/* ---- test-time augmentation: V views of one image merged at the output size ----------------------------------------------------------
+ * mmseg's SegTTAModel over postprocess_result (segearth_segmentor.py:301-326): every view's seg_logits are class probabilities, the
+ * views' probabilities are summed, divided by V, and the arg-max is taken.  A view is the image resized by a scale and possibly
+ * mirrored along the width, slid like any image: it has its own tile logits [T_v,Q,gh_v,gw_v], windows, up size, pad and canvas
+ * (h_v, w_v).  For output pixel (Y, X) of the (out_h, out_w) map and view v:
+ *   X_v    = out_w - 1 - X if the view is flipped, else X;
+ *   r_v[q] = the value at (Y, X_v) of the view's stitched canvas resized to (out_h, out_w), exactly as sg_label_head_resized defines
+ *            it (every tap divided by its own count, the same taps and blend, every product rounded);
+ *   p_v    = softmax_q(logit_scale * r_v), that entry's online recurrence in its chunk order;
+ *   P_v[c] = the largest p_v[q] over the queries of class c (query_idx[q] == c; K == Q: class q), 0 for a class without a query;
+ *   P[c]   = (P_0[c] + P_1[c] + ... in ascending v) / V;  label = the first c with the largest P[c];  conf = P[label];
+ *   label  = bg_idx where conf < prob_thd.
+ * sg_tta_head does this in one launch, one block per 64 x 4 output pixels, with no canvas, no per-view planes and no atomics; every
+ * output element is written by its pixel's thread in an order fixed by (pixel, view, query), so repeats are byte-identical.  With
+ * V = 1 and flip = 0 conf carries sg_label_head_resized's bytes, and so do the labels except where two classes' distinct best logits
+ * round to the same probability (this entry compares the probabilities).
+ *   tile_logits  the views' tile logits back to back, logit_elems floats = sum of T_v * Q * gh_v * gw_v;
+ *   windows      int32 [total_tiles,4], the views' windows back to back, each in its own view's canvas coordinates;
+ *   views        HOST array int32 [V][SG_TTA_VIEW_FIELDS]: T_v, first tile (= the sum of the T before it), gh, gw, up_h, up_w, pad_t,
+ *                pad_l, h, w, flip (0 / 1).  It is read during the call and travels as a kernel argument;
+ *   labels int64 [out_h,out_w]; conf f32 [out_h,out_w] or NULL; probs f32 [K,out_h,out_w] (the mean planes P) or NULL;
+ *   flags        SG_RESIZED_*, per view: a view whose footprint does not fit the stage runs the direct form (same bytes).
+ * Refused with the outputs untouched: V outside [1, SG_TTA_MAX_VIEWS], a non-positive size, Q > 64, K outside [1, Q], bg_idx outside
+ * [0, K), a flip that is neither 0 nor 1, views whose tiles do not follow each other or do not add up to the buffers.
+ * LDS: 1 KiB per class but the last (the per-view class maxima, one column per thread) beside the 16 KiB stage. */
+#define SG_TTA_MAX_VIEWS 8
+#define SG_TTA_VIEW_FIELDS 11
+int sg_tta_head(const float* tile_logits, int64_t logit_elems, const int32_t* windows, int total_tiles, const int32_t* views, int V, int Q,
+                int out_h, int out_w, const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx, int64_t* labels,
+                float* conf, float* probs, int flags, sg_stream s);
+/* The same merge for what the fused entry does not take (Q > 64, a weighted stitch, the JBU upsampler, whole-image inference): every
+ * view goes through the existing probability tail at (out_h, out_w), then
+ *   sg_tta_accumulate  acc[c,y,x] = (first ? 0 : acc[c,y,x]) + probs_view[c,y, flip ? out_w-1-x : x]   (acc and probs_view f32
+ *                      [K,out_h,out_w], distinct buffers), views in ascending order;
+ *   sg_tta_finish      P = acc / V, label, conf and threshold as above; probs (NULL, or f32 [K,out_h,out_w], or acc itself) gets P.
+ * Plain elementwise kernels; one view's planes and the accumulator are all that is alive. */
+int sg_tta_accumulate(const float* probs_view, int K, int out_h, int out_w, int flip, float* acc, int first, sg_stream s);
+int sg_tta_finish(const float* acc, int V, int K, int out_h, int out_w, float prob_thd, int bg_idx, int64_t* labels, float* conf,
+                  float* probs, sg_stream s);
 /* Label / confidence images of postprocess_result (segmentor.py:501-531): mask_rgb [H,W,3] = palette[clip(label)] (_colorize_mask,
  * :580-590); heat_rgb [H,W,3] = (g, 0, 255-g) with g = uint8(clip(max_k probs, 0, 1) * 255) (_to_colormap without OpenCV, :604-608;
  * OpenCV's JET table is not reproduced).  Either output may be NULL. */
