@@ -862,8 +862,11 @@ def pamr_dilations(dilations):
 
 @on_tensor_device
 def scene_planes(scene):
-    """u8 [H,W,3] scene -> its normalised f32 planes [3,H,W], (u - mean) / std exactly as the tower's ingest computes it (sg_extract_tiles
-    with one whole-scene window): the PAMR guidance of a u8 scene.  A float [3,H,W] scene is its own guidance and is returned as it is."""
+    """u8 [H,W,3] scene -> its normalised f32 planes [3,H,W] (sg_extract_tiles with one whole-scene window): the PAMR guidance of a u8
+    scene.  Each value is the plain f32 quotient (float(u) - mean) / std, one rounding in the subtraction and one in the division, which is
+    what torch computes from the same bytes.  The tower's ingest (patchify_kernel) holds the same bits wherever the subtraction is exact; in
+    channel 2 from u = 233 and channel 0 from u = 251 it corrects the quotient to the nearest f32 and the two may differ in the last bit
+    (tests/test_gpu_tiles_reference.py pins both).  A float [3,H,W] scene is its own guidance and is returned as it is."""
     if scene.dtype != torch.uint8:
         return _f32(scene)
     lib = _lib.load()

@@ -481,7 +481,7 @@ def test_jbu_against_oracle_nonsquare_and_batched():
     assert (out.cpu() - ref).abs().max().item() < 2e-4 * max(1.0, ref.abs().max().item())
 
 
-def test_global_debias_and_extract_tiles(ops):
+def test_global_debias_one_shape_vs_torch(ops):
     import ctypes as C
     from clip_decontamination_amd import _lib
     lib = _lib.load()
