@@ -179,6 +179,9 @@ SIGNATURES = {
     "sg_sieve": (I, [P, P, P, P, I, L, I, I, L, P, Z, P]),
     "sg_regions_workspace_bytes": (Z, [L, L]),
     "sg_regions": (I, [P, P, P, P, I, I, L, L, I, L, P, P, P, P, Z, P]),
+    "sg_boundary_workspace_bytes": (Z, [L]),
+    "sg_boundary_band": (I, [P, I, P, P, P, I, P, P, Z, P]),
+    "sg_boundary_accumulate": (I, [P, P, I, P, P, P, I, I, I, I, P, P, Z, P]),
 }
 
 _lib = None

@@ -174,8 +174,123 @@ class IoUMetric:
         return metrics_from_confusion(self.confusion, self.metrics, self.nan_to_num, self.beta)
 
 
-try:  # with mmseg installed the class is also buildable from a config, under a name that leaves mmseg's own IoUMetric alone
+def metrics_from_boundary(areas, nan_to_num: Optional[int] = None) -> dict:
+    """Boundary IoU (Cheng et al., CVPR 2021) from the band-restricted counts ``areas`` int64 [3,K] of ``sg_boundary_accumulate`` (rows:
+    intersection of the two bands, prediction band, truth band): ``BIoU`` float64 [K] = areas[0] / (areas[1] + areas[2] - areas[0]),
+    NaN where a class has no band pixel in prediction and truth, and ``summary['mBIoU']`` = ``nanmean * 100`` rounded to 2 decimals,
+    with such a class left out of the mean (``nan_to_num`` replaces NaN first), as ``metrics_from_confusion`` treats ``IoU``."""
+    a = areas.detach().cpu().numpy() if torch.is_tensor(areas) else np.asarray(areas)
+    if a.ndim != 2 or a.shape[0] != 3 or a.shape[1] < 1:
+        raise ValueError(f"boundary areas must be [3,K] with K >= 1, got shape {a.shape}")
+    if not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"boundary areas must hold integers, got {a.dtype}")
+    inter, pred, label = (a[i].astype(np.float64) for i in range(3))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        biou = np.asarray(inter / (pred + label - inter), dtype=np.float64)
+    if nan_to_num is not None:
+        biou = np.nan_to_num(biou, nan=nan_to_num)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", category=RuntimeWarning)
+        mean = float(np.round(np.nanmean(biou) * 100, 2))
+    return {"BIoU": biou, "summary": {"mBIoU": mean}}
+
+
+class BoundaryIoUMetric(IoUMetric):
+    """``IoUMetric`` plus Boundary IoU: the confusion table as before and ``boundary_areas`` int64 [3,K], the counts restricted to the
+    bands of prediction and truth (``sg_boundary_accumulate``).  The band width is ``boundary_ratio`` of each image's diagonal
+    (``ops.boundary_width``; 0.02 as in the paper) or the fixed ``boundary_px``, which overrides the ratio.
+
+    ``add(labels, gt)`` takes one 2-D map ([H,W] or [1,H,W]) and counts both tables; ``add_flat(labels, gt, image_hw)`` the flat buffers
+    of a flush group with the sizes of its images; ``reduce(group)`` sums both tables; ``add_confusion`` is IoUMetric's and leaves the
+    boundary counts alone; ``compute()`` returns IoUMetric's dict plus ``BIoU`` and ``summary['mBIoU']``."""
+
+    def __init__(self, *args, boundary_ratio: float = 0.02, boundary_px: Optional[int] = None, **kwargs):
+        from . import ops
+        if boundary_px is not None:
+            if isinstance(boundary_px, bool) or not isinstance(boundary_px, int) or not 1 <= boundary_px <= ops.BOUNDARY_MAX_D:
+                raise ValueError(f"boundary_px must be an integer in [1, {ops.BOUNDARY_MAX_D}] or None, got {boundary_px!r}")
+        else:
+            ops.boundary_width((1, 1), boundary_ratio)                       # the ratio's own checks
+        super().__init__(*args, **kwargs)
+        if self.num_classes is not None and self.num_classes > ops.BOUNDARY_MAX_K:
+            raise ValueError(f"BoundaryIoUMetric: num_classes={self.num_classes} exceeds {ops.BOUNDARY_MAX_K}")
+        self.boundary_ratio, self.boundary_px = boundary_ratio, boundary_px
+        self._areas: Optional[torch.Tensor] = None
+
+    def width(self, hw) -> int:
+        """The band width of an image of size ``hw``."""
+        from . import ops
+        return self.boundary_px if self.boundary_px is not None else ops.boundary_width(hw, self.boundary_ratio)
+
+    def _ensure_areas(self, device) -> torch.Tensor:
+        K = self._classes()
+        if self._areas is None:
+            self._areas = torch.zeros(3, K, dtype=torch.int64, device=device)
+        elif self._areas.device != torch.device(device):
+            self._areas = self._areas.to(device)
+        return self._areas
+
+    @property
+    def boundary_areas(self) -> torch.Tensor:
+        """The [3,K] int64 band counts: intersection, prediction band, truth band."""
+        return self._ensure_areas("cpu" if self._areas is None else self._areas.device)
+
+    def reset(self) -> None:
+        super().reset()
+        self._areas = None
+
+    def add(self, labels: torch.Tensor, gt: torch.Tensor) -> None:
+        """Counts one image in both tables: labels int64 and gt uint8 / int64, [H,W] or [1,H,W] of one size.  The band needs the
+        image's shape, so a flat buffer goes through ``add_flat``."""
+        gt = torch.as_tensor(gt)
+        for name, t in (("labels", labels), ("gt", gt)):
+            if not torch.is_tensor(t) or t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[0] != 1) or t.numel() == 0:
+                raise ValueError(f"BoundaryIoUMetric.add: {name} must be a non-empty [H,W] or [1,H,W] map (a flat buffer of images goes "
+                                 "through add_flat with their sizes)")
+        if tuple(labels.shape[-2:]) != tuple(gt.shape[-2:]):
+            raise ValueError(f"BoundaryIoUMetric.add: labels {tuple(labels.shape)} and gt {tuple(gt.shape)} differ in size")
+        self.add_flat(labels.reshape(-1), gt.reshape(-1), [tuple(labels.shape[-2:])])
+
+    def add_flat(self, labels: torch.Tensor, gt: torch.Tensor, image_hw) -> None:
+        """Counts the images that lie back to back in the flat ``labels`` / ``gt`` buffers (a flush group's), sizes ``image_hw``: one
+        sg_confusion_accumulate launch and one sg_boundary_accumulate call on the current stream."""
+        from . import ops
+        image_hw = [(int(h), int(w)) for h, w in image_hw]
+        if not image_hw or any(h < 1 or w < 1 for h, w in image_hw):
+            raise ValueError(f"BoundaryIoUMetric.add_flat: needs at least one image of positive size, got {image_hw}")
+        if not torch.is_tensor(labels) or labels.numel() != sum(h * w for h, w in image_hw):
+            raise ValueError(f"BoundaryIoUMetric.add_flat: images of sizes {image_hw} against "
+                             f"{labels.numel() if torch.is_tensor(labels) else type(labels).__name__} labels")
+        ds = [self.width(hw) for hw in image_hw]
+        if not labels.is_cuda:
+            raise RuntimeError("BoundaryIoUMetric counts on the GPU (sg_boundary_accumulate): labels must be a device tensor; "
+                               "there is no CPU fallback")
+        gt = torch.as_tensor(gt)
+        if gt.dtype not in (torch.uint8, torch.int64):
+            gt = gt.to(torch.int64)
+        gt = gt.to(labels.device).reshape(-1)
+        labels = labels.reshape(-1)
+        K = self._classes()
+        ops.confusion_accumulate(labels, gt, self._ensure(labels.device), K, self.ignore_index, self.reduce_zero_label)
+        ops.boundary_accumulate(labels, gt, image_hw, ds, self._ensure_areas(labels.device), K, self.ignore_index, self.reduce_zero_label)
+
+    def reduce(self, group=None) -> None:
+        """Sums both tables over the ranks of ``group``: two all_reduces."""
+        import torch.distributed as dist
+        super().reduce(group)
+        dist.all_reduce(self.boundary_areas, op=dist.ReduceOp.SUM, group=group)
+
+    def compute(self) -> dict:
+        out = super().compute()
+        b = metrics_from_boundary(self.boundary_areas, self.nan_to_num)
+        out["BIoU"] = b["BIoU"]
+        out["summary"] = dict(out["summary"], mBIoU=b["summary"]["mBIoU"])
+        return out
+
+
+try:  # with mmseg installed the classes are also buildable from a config, under names that leave mmseg's own IoUMetric alone
     from mmseg.registry import METRICS as _METRICS
     _METRICS.register_module(name="HipIoUMetric", module=IoUMetric)
+    _METRICS.register_module(name="HipBoundaryIoUMetric", module=BoundaryIoUMetric)
 except Exception:
     pass

@@ -1477,3 +1477,122 @@ def regions(labels, conf=None, connectivity=4, min_area=1, skip_label=None, max_
     if want_map and not many:
         out["region_of"] = out["region_of"][0]
     return out
+
+
+# ---- Boundary IoU (sg_boundary_band / sg_boundary_accumulate; the definition: include/segearth_hip.h) --------------------------------------
+BOUNDARY_MAX_D = 4095                                                    # the widest band the entries take
+BOUNDARY_MAX_K = 127                                                     # the cap of sg_confusion_accumulate
+BOUNDARY_MAX_PIXELS = (1 << 31) - 1                                      # per image
+
+
+def boundary_width(hw, ratio=0.02):
+    """The band width of an image of size ``hw`` = (H, W): d = max(1, int(round(ratio * sqrt(H*H + W*W)))), host arithmetic in double
+    with Python's round, as in the official Boundary IoU code (ratio 0.02 of the diagonal: 14 px on a 512 tile, 101 px on 2048 x 4608)."""
+    import math
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not (ratio > 0) or not math.isfinite(ratio):
+        raise ValueError(f"boundary_ratio must be a finite number > 0 (a share of the image diagonal), got {ratio!r}")
+    h, w = (int(v) for v in hw)
+    if h < 1 or w < 1:
+        raise ValueError(f"boundary_width: an image of size {h} x {w}")
+    d = max(1, int(round(float(ratio) * math.sqrt(h * h + w * w))))
+    if d > BOUNDARY_MAX_D:
+        raise ValueError(f"boundary_width: ratio {ratio} of the diagonal of {h} x {w} is {d} px, above the limit of {BOUNDARY_MAX_D}")
+    return d
+
+
+def boundary_args(image_hw, d):
+    """The checks of the boundary entries, before any library call: sizes positive and below 2^31 pixels per image, every width an
+    integer in [1, 4095]; one width serves every image -> (image_hw, widths)."""
+    image_hw = [(int(h), int(w)) for h, w in image_hw]
+    if not image_hw or any(h <= 0 or w <= 0 for h, w in image_hw):
+        raise ValueError(f"boundary: needs at least one image of positive size, got {image_hw}")
+    if any(h * w > BOUNDARY_MAX_PIXELS for h, w in image_hw):
+        raise ValueError(f"boundary: an image of 2^31 or more pixels is not supported, got {image_hw}")
+    ds = list(d) if isinstance(d, (list, tuple)) else [d] * len(image_hw)
+    if len(ds) != len(image_hw):
+        raise ValueError(f"boundary: {len(ds)} widths for {len(image_hw)} images")
+    for v in ds:
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= BOUNDARY_MAX_D:
+            raise ValueError(f"boundary: the band width d must be an integer in [1, {BOUNDARY_MAX_D}], got {v!r}")
+    return image_hw, ds
+
+
+def _boundary_arrays(image_hw, ds):
+    N = len(image_hw)
+    pix = _prefix(h * w for h, w in image_hw)
+    return N, pix, (C.c_int32 * (2 * N))(*[v for s in image_hw for v in s]), (C.c_int64 * N)(*pix[:-1]), (C.c_int32 * N)(*ds)
+
+
+@on_tensor_device
+def boundary_band_flat(labels, image_hw, d):
+    """sg_boundary_band on a flat int64 or uint8 buffer that holds N label maps back to back, sizes ``image_hw``, widths ``d`` (one
+    integer, or one per image) -> the flat uint8 band buffer, 0 / 1.  One call; nothing synchronises with the host."""
+    image_hw, ds = boundary_args(image_hw, d)
+    if not torch.is_tensor(labels) or labels.dtype not in (torch.int64, torch.uint8) or not labels.is_contiguous():
+        raise TypeError("boundary_band: labels must be a contiguous int64 or uint8 tensor")
+    N, pix, hw, off, dd = _boundary_arrays(image_hw, ds)
+    if pix[-1] != labels.numel():
+        raise ValueError(f"boundary_band: {N} images of sizes {image_hw} against {labels.numel()} labels")
+    _require_gpu(labels)
+    lib = _lib.load()
+    band = torch.empty(labels.numel(), dtype=torch.uint8, device=labels.device)
+    buf = scratch(int(lib.sg_boundary_workspace_bytes(pix[-1])) // 4, labels.device)
+    wp, wn = _aligned(buf)
+    fmt = _lib.GT_U8 if labels.dtype == torch.uint8 else _lib.GT_I64
+    check(lib.sg_boundary_band(ptr(labels), fmt, hw, off, dd, N, ptr(band), wp, wn, stream_ptr()), "sg_boundary_band")
+    return band
+
+
+def boundary_band(labels, d):
+    """The boundary band of a label map (the definition: sg_boundary_band in include/segearth_hip.h): 1 where the (2d+1) x (2d+1) window
+    around a pixel leaves the image or holds another label -- for every class at once the pixels of its mask within ``d`` of its contour.
+    ``labels``: int64 or uint8 [H,W] or [1,H,W] on the device, or a list of such maps of any sizes (one dtype) -- a list is packed into
+    one flat buffer and served by one call; ``d`` one integer or one per map.  Returns uint8 maps of the same shapes."""
+    many = isinstance(labels, (list, tuple))
+    maps = list(labels) if many else [labels]
+    if not maps:
+        raise ValueError("boundary_band: needs at least one label map")
+    for m in maps:
+        if not torch.is_tensor(m) or m.dim() not in (2, 3) or (m.dim() == 3 and m.shape[0] != 1) or m.numel() == 0:
+            raise ValueError("boundary_band: a label map must be a non-empty int64 or uint8 [H,W] or [1,H,W] tensor")
+        if m.dtype != maps[0].dtype or m.dtype not in (torch.int64, torch.uint8):
+            raise TypeError(f"boundary_band: label maps must all be int64 or all uint8, got {m.dtype}")
+    hw = [tuple(m.shape[-2:]) for m in maps]
+    boundary_args(hw, d)
+    flat = maps[0].reshape(-1).contiguous() if len(maps) == 1 else torch.cat([m.reshape(-1) for m in maps])
+    band = boundary_band_flat(flat, hw, d)
+    res = [v.view(m.shape) for v, m in zip(flat_views(band, 1, hw), maps)]
+    return res if many else res[0]
+
+
+@on_tensor_device
+def boundary_accumulate(labels_flat, gt_flat, image_hw, d, areas, K: int, ignore_index: int = 255, reduce_zero_label: bool = False):
+    """sg_boundary_accumulate on the current stream: the bands of the predictions and of the (transformed) truth of N images that lie
+    back to back in ``labels_flat`` (int64) and ``gt_flat`` (uint8 or int64), sizes ``image_hw``, widths ``d`` (one integer or one per
+    image); the band-restricted counts are ADDED to ``areas`` int64 [3,K] (intersection, prediction band, truth band), which is
+    returned.  Nothing comes back to the host."""
+    image_hw, ds = boundary_args(image_hw, d)
+    K = int(K)
+    if not 1 <= K <= BOUNDARY_MAX_K:
+        raise ValueError(f"boundary_accumulate: K={K} outside [1, {BOUNDARY_MAX_K}] (the cap of sg_confusion_accumulate)")
+    if not torch.is_tensor(labels_flat) or labels_flat.dtype != torch.int64:
+        raise TypeError("boundary_accumulate: labels must be an int64 tensor")
+    if not torch.is_tensor(gt_flat) or gt_flat.dtype not in (torch.uint8, torch.int64):
+        raise TypeError("boundary_accumulate: gt must be a uint8 or int64 tensor")
+    N, pix, hw, off, dd = _boundary_arrays(image_hw, ds)
+    if labels_flat.numel() != pix[-1] or gt_flat.numel() != pix[-1]:
+        raise ValueError(f"boundary_accumulate: {N} images of sizes {image_hw} against {labels_flat.numel()} labels and "
+                         f"{gt_flat.numel()} truth pixels")
+    if not torch.is_tensor(areas) or areas.dtype != torch.int64 or not areas.is_contiguous() or areas.numel() != 3 * K:
+        raise ValueError(f"boundary_accumulate: areas must be contiguous int64 with {3 * K} elements for K={K}")
+    _require_gpu(labels_flat, gt_flat, areas)
+    if gt_flat.device != labels_flat.device or areas.device != labels_flat.device:
+        raise ValueError("boundary_accumulate: labels, gt and areas must live on one device")
+    lib = _lib.load()
+    labels_flat, gt_flat = labels_flat.contiguous().view(-1), gt_flat.contiguous().view(-1)
+    buf = scratch(int(lib.sg_boundary_workspace_bytes(pix[-1])), labels_flat.device)
+    wp, wn = _aligned(buf)
+    fmt = _lib.GT_U8 if gt_flat.dtype == torch.uint8 else _lib.GT_I64
+    check(lib.sg_boundary_accumulate(ptr(labels_flat), ptr(gt_flat), fmt, hw, off, dd, N, K, int(ignore_index), int(bool(reduce_zero_label)),
+                                     ptr(areas), wp, wn, stream_ptr()), "sg_boundary_accumulate")
+    return areas

@@ -570,7 +570,8 @@ class _HipSegmentorBase(_Base):
             self._write_maps(probs, seg_pred, sample, i)
 
     @torch.no_grad()
-    def evaluate(self, inputs, gt_maps, metric=None, reduce_zero_label=False, ignore_index=255, iou_metrics=("mIoU",), at_gt_size=False):
+    def evaluate(self, inputs, gt_maps, metric=None, reduce_zero_label=False, ignore_index=255, iou_metrics=("mIoU",), at_gt_size=False,
+                 boundary_ratio=None, boundary_px=None):
         """Labels to score without leaving the device: what the reference's ``test_evaluator = dict(type='IoUMetric', ...)`` reports.
         inputs: as ``predict_many``; gt_maps: one [H,W] / [1,H,W] uint8 or int64 tensor or numpy array per image, of the image's size.
         Returns ``(metric.compute(), metric)``; pass ``metric`` back in to accumulate over the calls of a dataset loop (its own
@@ -584,12 +585,27 @@ class _HipSegmentorBase(_Base):
         that size and counted (the configs that resize the image before inference and score at the original size).  The route follows
         ``resize_head``: sg_label_head_resized_multi with "fused", stitch + resize + post-process with "canvas".
         With ``area_thd`` set the labels that are counted are the filtered ones (SegPipeline.label_groups); with ``min_region`` set,
-        the sieved ones."""
-        from .metrics import IoUMetric
+        the sieved ones.
+        ``boundary_ratio`` / ``boundary_px``: Boundary IoU next to the plain metric.  With both None and ``metric`` None or a plain
+        ``IoUMetric``, nothing above changes.  With one of them set, or with a ``BoundaryIoUMetric`` passed in, the metric is a
+        ``BoundaryIoUMetric``: built here with the band width ``boundary_ratio`` of each image's diagonal or the fixed ``boundary_px``,
+        or the one passed in, whose own ratio / width hold.  Every flush group's flat labels then go to ``metric.add_flat`` with the
+        sizes of its images, which adds one sg_boundary_accumulate call per group, and the result carries ``BIoU`` and
+        ``summary['mBIoU']``.  It reads final labels only, so it composes with ``at_gt_size``, ``area_thd``, ``min_region``, PAMR,
+        ``blend`` and TTA."""
+        from .metrics import BoundaryIoUMetric, IoUMetric
+        boundary = boundary_ratio is not None or boundary_px is not None or isinstance(metric, BoundaryIoUMetric)
         if getattr(self, "tile_group", None) is not None:
             raise ValueError("evaluate: tile_group sharding is not supported (each rank would have to count its own band against the "
                              "matching rows of the truth); evaluate whole images per rank and call metric.reduce(group)")
-        if metric is None:
+        if boundary and metric is not None and not isinstance(metric, BoundaryIoUMetric):
+            raise TypeError("evaluate: boundary_ratio / boundary_px need a BoundaryIoUMetric (or metric=None to have one built), got "
+                            f"{type(metric).__name__}")
+        if metric is None and boundary:
+            metric = BoundaryIoUMetric(ignore_index=ignore_index, iou_metrics=list(iou_metrics), num_classes=self.num_classes,
+                                       reduce_zero_label=reduce_zero_label, boundary_px=boundary_px,
+                                       **({} if boundary_ratio is None else {"boundary_ratio": boundary_ratio}))
+        elif metric is None:
             metric = IoUMetric(ignore_index=ignore_index, iou_metrics=list(iou_metrics), num_classes=self.num_classes,
                                reduce_zero_label=reduce_zero_label)
         elif metric.num_classes is None:
@@ -625,14 +641,20 @@ class _HipSegmentorBase(_Base):
         if self.slide_crop <= 0:                                             # whole-image inference has no windows to pack
             labs = self.predict_many(imgs, None, ori_shapes=ori) if at_gt_size else [self.predict(imgs[i][None], None) for i in range(n)]
             for i in range(n):
-                metric.add(labs[i].reshape(-1), gt_flat[off[i]:off[i + 1]])
+                if boundary:
+                    metric.add_flat(labs[i].reshape(-1), gt_flat[off[i]:off[i + 1]], [tuple(labs[i].shape[-2:])])
+                else:
+                    metric.add(labs[i].reshape(-1), gt_flat[off[i]:off[i + 1]])
             return metric.compute(), metric
-        for idx, _, _, flat in self._pipeline().label_groups(imgs, self.slide_stride, self.slide_crop, want_probs=False, ori_shapes=ori):
+        for idx, _, labs, flat in self._pipeline().label_groups(imgs, self.slide_stride, self.slide_crop, want_probs=False, ori_shapes=ori):
             if idx == list(range(idx[0], idx[0] + len(idx))):                # the group's images are neighbours in the call: a slice
                 gt = gt_flat[off[idx[0]]:off[idx[-1] + 1]]
             else:                                                            # tile-size groups interleave images: gather on the device
                 gt = torch.cat([gt_flat[off[k]:off[k + 1]] for k in idx])
-            metric.add(flat, gt)
+            if boundary:
+                metric.add_flat(flat, gt, [tuple(x.shape[-2:]) for x in labs])
+            else:
+                metric.add(flat, gt)
         return metric.compute(), metric
 
     def postprocess_result(self, seg_logits, data_samples):

@@ -937,6 +937,49 @@ int sg_regions(const int64_t* labels, const float* conf, const int32_t* image_hw
                int64_t min_area, int64_t skip_label, int use_skip, int64_t max_regions, int64_t* table, int32_t* region_of, int64_t* counts,
                void* workspace, size_t workspace_bytes, sg_stream s);
 
+/* ---- Boundary IoU: boundary bands and band-restricted counts (Cheng et al., CVPR 2021) -------------------------------------------------
+ * IoU restricted to the pixels of each mask that lie within d pixels of that mask's contour: the score that moves when an outline moves,
+ * which area IoU (sg_confusion_accumulate) barely does.  It only reads final labels.
+ * Band.  For a label map L of H x W and a width d >= 1, band(y,x) = 1 iff the square window [y-d, y+d] x [x-d, x+d] either leaves the
+ *   image or holds a pixel whose label differs from L(y,x).  This is, for every class c at once, the paper's
+ *   mask_c - erode(pad0(mask_c), 3x3 ones, iterations = d) with mask_c = (L == c); every pixel has exactly one label, so one bit per pixel
+ *   carries the bands of all classes.  Labels are compared as raw 64-bit values: a value outside [0,K) is a label like any other here.
+ * Width from the ratio (host arithmetic in double, per image): d = max(1, int(round(ratio * sqrt(H*H + W*W)))), Python's round; the
+ *   paper's default ratio is 0.02.  1 <= d <= 4095.
+ * Counts.  Per image, bandP is the band of the prediction as it is; bandG the band of the truth after reduce_zero_label (the rule of
+ *   sg_confusion_accumulate: raw 0 -> 255, raw 255 stays, else g - 1).  Ignored truth pixels stay in the map, as a value that belongs to
+ *   no class: a class that borders an ignored area has a boundary there, as the per-class binary mask gives.  Then every pixel whose
+ *   transformed truth g is not ignore_index is counted, with p its prediction and areas int64 [3][K]:
+ *     areas[0][k] += (p == k && g == k && bandP && bandG)      the intersection of the two bands
+ *     areas[1][k] += (p == k && bandP)                         the prediction's band
+ *     areas[2][k] += (g == k && bandG)                         the truth's band
+ *   Values outside [0,K) add to nothing.  BIoU[k] = areas[0][k] / (areas[1][k] + areas[2][k] - areas[0][k]) in float64 on the caller's
+ *   side, NaN where the denominator is 0.  With d >= max(H, W) every pixel is in both bands and areas equals (area_intersect,
+ *   area_pred_label, area_label) of the confusion table on the same inputs.
+ * N >= 1 maps lie back to back in one flat buffer (what the multi-image heads write): image n is image_hw[2n] x image_hw[2n+1] at
+ * offset[n] (in pixels), with its own width d[n]; image_hw, offset and d are HOST arrays, checked before anything is launched.  The
+ * images lie in ascending order, do not overlap and stay inside the n_pixels_total = sum of H*W pixels of the call (so offset[n] is the
+ * sum of the sizes before image n).
+ *   sg_boundary_workspace_bytes  4 planes of n_pixels_total bytes, each rounded up to 256: row bytes and band of the prediction and of the
+ *                                truth (sg_boundary_accumulate).  sg_boundary_band uses the first plane only and accepts a workspace of
+ *                                a quarter of this.  0 for a negative count.
+ *   sg_boundary_band             labels u8 (SG_GT_U8) or int64 (SG_GT_I64) -> band u8 [n_pixels_total], 0 / 1, same offsets.  Per image a
+ *                                row pass (per row one sweep with a running start-of-run: is [x-d, x+d] inside the image and of one
+ *                                label) and a column pass (a march down the columns over the row pass's bytes, in row bands with a halo
+ *                                of 2d rows).  No loop over the window: the work per pixel does not grow with d.
+ *   sg_boundary_accumulate       the bands of labels and of the transformed truth, then the counts above ADDED to areas (the caller zeroes
+ *                                it): 3K 32-bit bins in LDS per workgroup, one 64-bit add per non-zero bin per workgroup.
+ * Integers and integer atomics only: byte-identical across repeats.  Nothing is copied or synchronised; no workgroup waits for another.
+ * Refused with SG_ERR_INVALID before any launch: a null pointer, an unknown format, N < 1, an image of non-positive size or of 2^31 or
+ * more pixels, an offset that puts an image over the one before it or outside the call's pixels, d outside [1, 4095], K < 1, K > 127 (the cap of
+ * sg_confusion_accumulate, so that one metric object can hold both tables), a misaligned int64 buffer, a workspace that is too small. */
+size_t sg_boundary_workspace_bytes(int64_t n_pixels_total);
+int sg_boundary_band(const void* labels, int fmt, const int32_t* image_hw, const int64_t* offset, const int32_t* d, int N, uint8_t* band,
+                     void* workspace, size_t workspace_bytes, sg_stream s);
+int sg_boundary_accumulate(const int64_t* labels, const void* gt, int gt_format, const int32_t* image_hw, const int64_t* offset,
+                           const int32_t* d, int N, int K, int ignore_index, int reduce_zero_label, int64_t* areas, void* workspace,
+                           size_t workspace_bytes, sg_stream s);
+
 #ifdef __cplusplus
 }
 #endif
