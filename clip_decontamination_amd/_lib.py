@@ -18,6 +18,7 @@ MODEL_TYPES = {"vanilla": 0, "MaskCLIP": 1, "ClearCLIP": 2, "SCLIP": 3, "SegEart
                "NACLIP": 7, "NOnly": 8, "GAV": 9, "GEM": 10}
 IMG_F32_NCHW, IMG_U8_NHWC = 0, 1
 GT_U8, GT_I64 = 0, 1
+TOL_REGION, TOL_CONTOUR = 0, 1
 
 
 class VitDesc(C.Structure):
@@ -182,6 +183,8 @@ SIGNATURES = {
     "sg_boundary_workspace_bytes": (Z, [L]),
     "sg_boundary_band": (I, [P, I, P, P, P, I, P, P, Z, P]),
     "sg_boundary_accumulate": (I, [P, P, I, P, P, P, I, I, I, I, P, P, Z, P]),
+    "sg_tolerant_workspace_bytes": (Z, [L, I]),
+    "sg_tolerant_accumulate": (I, [P, P, I, P, P, P, I, I, I, I, I, P, P, Z, P]),
 }
 
 _lib = None

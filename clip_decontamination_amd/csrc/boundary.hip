@@ -31,28 +31,6 @@ constexpr int BD_COL_BATCH = 16;                 // rows a lane of the column pa
 constexpr int BD_COL_WAVES_PER_CU = 16;          // the column pass splits the rows until about this many waves per CU march
 constexpr size_t BD_PLANE_ALIGN = 256;
 
-// mmseg LoadAnnotations under reduce_zero_label: 0 -> 255, 255 stays, else g - 1 (the rule of sg_confusion_accumulate)
-__device__ __forceinline__ int64_t bd_reduce_zero(int64_t g) { return (g == 0 || g == 255) ? (int64_t)255 : (int64_t)((uint64_t)g - 1u); }
-
-template <typename T> __device__ __forceinline__ int64_t bd_value(const T* p, int64_t i, int rzl) {
-  const int64_t v = (int64_t)p[i];
-  return rzl ? bd_reduce_zero(v) : v;
-}
-
-// values of BD_ROW_RUN consecutive pixels from column u0 of a row (columns >= W: any value, never used)
-template <typename T>
-__device__ __forceinline__ void bd_load_run(const T* __restrict__ row, int64_t u0, int W, int rzl, int64_t (&v)[BD_ROW_RUN]) {
-  if (u0 + BD_ROW_RUN <= W) {
-    T raw[BD_ROW_RUN];
-    __builtin_memcpy(raw, row + u0, sizeof(raw));
-#pragma unroll
-    for (int j = 0; j < BD_ROW_RUN; ++j) v[j] = rzl ? bd_reduce_zero((int64_t)raw[j]) : (int64_t)raw[j];
-  } else {
-#pragma unroll
-    for (int j = 0; j < BD_ROW_RUN; ++j) v[j] = u0 + j < W ? bd_value(row, u0 + j, rzl) : 0;
-  }
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void bd_row_kernel(const T* __restrict__ labels, int H, int W, int d, int rzl, uint8_t* __restrict__ rowb) {
   __shared__ int wave_last[2][4];
@@ -69,9 +47,9 @@ __global__ __launch_bounds__(256) void bd_row_kernel(const T* __restrict__ label
     for (int64_t c0 = 0; c0 < W; c0 += BD_ROW_CHUNK, par ^= 1) {           // block-uniform
       const int64_t u0 = c0 + (int64_t)tid * BD_ROW_RUN;
       int64_t v[BD_ROW_RUN], up[BD_ROW_RUN];
-      bd_load_run(row, u0, W, rzl, v);
-      if (above) bd_load_run(above, u0, W, rzl, up);
-      const int64_t prev = (u0 > 0 && u0 < W) ? bd_value(row, u0 - 1, rzl) : 0;
+      lm_load_run<BD_ROW_RUN>(row, u0, W, rzl, v);
+      if (above) lm_load_run<BD_ROW_RUN>(above, u0, W, rzl, up);
+      const int64_t prev = (u0 > 0 && u0 < W) ? lm_value(row, u0 - 1, rzl) : 0;
       bool brk[BD_ROW_RUN];
       int last = -1;                                                       // the lane's last break column, -1 = none
 #pragma unroll
@@ -158,40 +136,9 @@ __global__ __launch_bounds__(256) void bd_col_kernel(const uint8_t* __restrict__
   for (int64_t yy = (H - d > yb ? H - d : yb); yy < ye; ++yy) dst[yy * W] = 1;
 }
 
-// One stream of bins for BD_CNT_RUN consecutive pixels of every lane, added to the LDS table as confusion_kernel adds its bins: equal
-// neighbours merge into (bin, length) runs in registers; slot by slot the wave combines by leader match (one ballot for the lanes on the
-// leader's bin, five for the sum of their lengths, one LDS add); after two rounds, once a round matches fewer than 4 lanes, the rest
-// go to the LDS atomic unit directly.  b < 0 = nothing to add.
-__device__ __forceinline__ void bd_add_stream(const int (&b)[BD_CNT_RUN], uint32_t* bins, int lane) {
-  int len[BD_CNT_RUN];
-  len[BD_CNT_RUN - 1] = 1;
-#pragma unroll
-  for (int j = BD_CNT_RUN - 2; j >= 0; --j) len[j] = b[j] == b[j + 1] ? len[j + 1] + 1 : 1;
-#pragma unroll
-  for (int j = 0; j < BD_CNT_RUN; ++j) {
-    bool act = b[j] >= 0 && (j == 0 || b[j] != b[j - 1]);
-    unsigned long long rem = __ballot(act);
-    int rounds = 0;
-    while (rem != 0ull) {                                                // wave-uniform
-      const int src = __ffsll((long long)rem) - 1;
-      const int lb = __builtin_amdgcn_readlane(b[j], src);
-      const bool m = act && b[j] == lb;
-      const unsigned long long mm = __ballot(m);
-      int total = 0;
-#pragma unroll
-      for (int bit = 0; bit < 5; ++bit) total += __popcll(__ballot(m && ((len[j] >> bit) & 1))) << bit;
-      if (lane == src) atomicAdd(&bins[lb], (uint32_t)total);
-      act = act && !m;
-      rem &= ~mm;
-      if (++rounds >= 2 && __popcll(mm) < 4) break;
-    }
-    if (act) atomicAdd(&bins[b[j]], (uint32_t)len[j]);
-  }
-}
-
 // the three bins of one pixel (-1 = none): intersection k, prediction band K + k, truth band 2K + k
 __device__ __forceinline__ void bd_pixel_bins(int64_t p, int64_t g, int bp, int bg, int K, int ignore_index, int rzl, int& bi, int& bpd, int& bgt) {
-  if (rzl) g = bd_reduce_zero(g);
+  if (rzl) g = lm_reduce_zero(g);
   const bool counted = g != (int64_t)ignore_index;
   const bool pin = counted && bp && (uint64_t)p < (uint64_t)K;
   const bool gin = counted && bg && (uint64_t)g < (uint64_t)K;
@@ -247,9 +194,9 @@ __global__ __launch_bounds__(256) void bd_count_kernel(const int64_t* __restrict
 #pragma unroll
       for (int j = 0; j < BD_CNT_RUN; ++j) bd_pixel_bins(p[j], g[j], mp[j], mg[j], K, ignore_index, rzl, bi[j], bpd[j], bgt[j]);
     }
-    bd_add_stream(bi, bd_bins, lane);
-    bd_add_stream(bpd, bd_bins, lane);
-    bd_add_stream(bgt, bd_bins, lane);
+    lm_add_stream<BD_CNT_RUN>(bi, bd_bins, lane);
+    lm_add_stream<BD_CNT_RUN>(bpd, bd_bins, lane);
+    lm_add_stream<BD_CNT_RUN>(bgt, bd_bins, lane);
   }
   __syncthreads();
   for (int i = tid; i < nb; i += 256) {

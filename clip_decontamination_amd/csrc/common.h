@@ -318,4 +318,60 @@ struct GemmF32Args {
 };
 int gemm_f32(const GemmF32Args& a, hipStream_t s);
 
+// ---- label maps: what boundary.hip and tolerant.hip share ------------------------------------------------------------------------------
+// mmseg LoadAnnotations under reduce_zero_label: 0 -> 255, 255 stays, else g - 1 (the rule of sg_confusion_accumulate)
+__device__ __forceinline__ int64_t lm_reduce_zero(int64_t g) { return (g == 0 || g == 255) ? (int64_t)255 : (int64_t)((uint64_t)g - 1u); }
+
+template <typename T> __device__ __forceinline__ int64_t lm_value(const T* p, int64_t i, int rzl) {
+  const int64_t v = (int64_t)p[i];
+  return rzl ? lm_reduce_zero(v) : v;
+}
+
+// values of RUN consecutive pixels from column u0 of a row (columns >= W: any value, never used)
+template <int RUN, typename T>
+__device__ __forceinline__ void lm_load_run(const T* __restrict__ row, int64_t u0, int W, int rzl, int64_t (&v)[RUN]) {
+  if (u0 + RUN <= W) {
+    T raw[RUN];
+    __builtin_memcpy(raw, row + u0, sizeof(raw));
+#pragma unroll
+    for (int j = 0; j < RUN; ++j) v[j] = rzl ? lm_reduce_zero((int64_t)raw[j]) : (int64_t)raw[j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < RUN; ++j) v[j] = u0 + j < W ? lm_value(row, u0 + j, rzl) : 0;
+  }
+}
+
+// One stream of bins for RUN <= 31 consecutive pixels of every lane, added to the LDS table as confusion_kernel adds its bins: equal
+// neighbours merge into (bin, length) runs in registers; slot by slot the wave combines by leader match (one ballot for the lanes on the
+// leader's bin, five for the sum of their lengths, one LDS add); after two rounds, once a round matches fewer than 4 lanes, the rest
+// go to the LDS atomic unit directly.  b < 0 = nothing to add.  Every lane of the wave calls it.
+template <int RUN>
+__device__ __forceinline__ void lm_add_stream(const int (&b)[RUN], uint32_t* bins, int lane) {
+  static_assert(RUN >= 1 && RUN <= 31, "a run length is summed from five ballots");
+  int len[RUN];
+  len[RUN - 1] = 1;
+#pragma unroll
+  for (int j = RUN - 2; j >= 0; --j) len[j] = b[j] == b[j + 1] ? len[j + 1] + 1 : 1;
+#pragma unroll
+  for (int j = 0; j < RUN; ++j) {
+    bool act = b[j] >= 0 && (j == 0 || b[j] != b[j - 1]);
+    unsigned long long rem = __ballot(act);
+    int rounds = 0;
+    while (rem != 0ull) {                                                // wave-uniform
+      const int src = __ffsll((long long)rem) - 1;
+      const int lb = __builtin_amdgcn_readlane(b[j], src);
+      const bool m = act && b[j] == lb;
+      const unsigned long long mm = __ballot(m);
+      int total = 0;
+#pragma unroll
+      for (int bit = 0; bit < 5; ++bit) total += __popcll(__ballot(m && ((len[j] >> bit) & 1))) << bit;
+      if (lane == src) atomicAdd(&bins[lb], (uint32_t)total);
+      act = act && !m;
+      rem &= ~mm;
+      if (++rounds >= 2 && __popcll(mm) < 4) break;
+    }
+    if (act) atomicAdd(&bins[b[j]], (uint32_t)len[j]);
+  }
+}
+
 }  // namespace sg

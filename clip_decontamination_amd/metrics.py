@@ -174,6 +174,40 @@ class IoUMetric:
         return metrics_from_confusion(self.confusion, self.metrics, self.nan_to_num, self.beta)
 
 
+def _one_map(who: str, labels, gt):
+    """The checks of ``add`` on the metrics that need an image's shape: one non-empty [H,W] / [1,H,W] map each, of one size
+    -> (gt as a tensor, (H, W))."""
+    gt = torch.as_tensor(gt)
+    for name, t in (("labels", labels), ("gt", gt)):
+        if not torch.is_tensor(t) or t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[0] != 1) or t.numel() == 0:
+            raise ValueError(f"{who}.add: {name} must be a non-empty [H,W] or [1,H,W] map (a flat buffer of images goes "
+                             "through add_flat with their sizes)")
+    if tuple(labels.shape[-2:]) != tuple(gt.shape[-2:]):
+        raise ValueError(f"{who}.add: labels {tuple(labels.shape)} and gt {tuple(gt.shape)} differ in size")
+    return gt, tuple(labels.shape[-2:])
+
+
+def _flat_sizes(who: str, labels, image_hw):
+    """The checks of ``add_flat`` on the sizes of a flush group, before anything is counted -> image_hw as int pairs."""
+    image_hw = [(int(h), int(w)) for h, w in image_hw]
+    if not image_hw or any(h < 1 or w < 1 for h, w in image_hw):
+        raise ValueError(f"{who}.add_flat: needs at least one image of positive size, got {image_hw}")
+    if not torch.is_tensor(labels) or labels.numel() != sum(h * w for h, w in image_hw):
+        raise ValueError(f"{who}.add_flat: images of sizes {image_hw} against "
+                         f"{labels.numel() if torch.is_tensor(labels) else type(labels).__name__} labels")
+    return image_hw
+
+
+def _flat_on_device(who: str, entry: str, labels, gt):
+    """Flat labels and truth of one flush group on the labels' device; no CPU fallback."""
+    if not labels.is_cuda:
+        raise RuntimeError(f"{who} counts on the GPU ({entry}): labels must be a device tensor; there is no CPU fallback")
+    gt = torch.as_tensor(gt)
+    if gt.dtype not in (torch.uint8, torch.int64):
+        gt = gt.to(torch.int64)
+    return labels.reshape(-1), gt.to(labels.device).reshape(-1)
+
+
 def metrics_from_boundary(areas, nan_to_num: Optional[int] = None) -> dict:
     """Boundary IoU (Cheng et al., CVPR 2021) from the band-restricted counts ``areas`` int64 [3,K] of ``sg_boundary_accumulate`` (rows:
     intersection of the two bands, prediction band, truth band): ``BIoU`` float64 [K] = areas[0] / (areas[1] + areas[2] - areas[0]),
@@ -242,34 +276,16 @@ class BoundaryIoUMetric(IoUMetric):
     def add(self, labels: torch.Tensor, gt: torch.Tensor) -> None:
         """Counts one image in both tables: labels int64 and gt uint8 / int64, [H,W] or [1,H,W] of one size.  The band needs the
         image's shape, so a flat buffer goes through ``add_flat``."""
-        gt = torch.as_tensor(gt)
-        for name, t in (("labels", labels), ("gt", gt)):
-            if not torch.is_tensor(t) or t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[0] != 1) or t.numel() == 0:
-                raise ValueError(f"BoundaryIoUMetric.add: {name} must be a non-empty [H,W] or [1,H,W] map (a flat buffer of images goes "
-                                 "through add_flat with their sizes)")
-        if tuple(labels.shape[-2:]) != tuple(gt.shape[-2:]):
-            raise ValueError(f"BoundaryIoUMetric.add: labels {tuple(labels.shape)} and gt {tuple(gt.shape)} differ in size")
-        self.add_flat(labels.reshape(-1), gt.reshape(-1), [tuple(labels.shape[-2:])])
+        gt, hw = _one_map("BoundaryIoUMetric", labels, gt)
+        self.add_flat(labels.reshape(-1), gt.reshape(-1), [hw])
 
     def add_flat(self, labels: torch.Tensor, gt: torch.Tensor, image_hw) -> None:
         """Counts the images that lie back to back in the flat ``labels`` / ``gt`` buffers (a flush group's), sizes ``image_hw``: one
         sg_confusion_accumulate launch and one sg_boundary_accumulate call on the current stream."""
         from . import ops
-        image_hw = [(int(h), int(w)) for h, w in image_hw]
-        if not image_hw or any(h < 1 or w < 1 for h, w in image_hw):
-            raise ValueError(f"BoundaryIoUMetric.add_flat: needs at least one image of positive size, got {image_hw}")
-        if not torch.is_tensor(labels) or labels.numel() != sum(h * w for h, w in image_hw):
-            raise ValueError(f"BoundaryIoUMetric.add_flat: images of sizes {image_hw} against "
-                             f"{labels.numel() if torch.is_tensor(labels) else type(labels).__name__} labels")
+        image_hw = _flat_sizes("BoundaryIoUMetric", labels, image_hw)
         ds = [self.width(hw) for hw in image_hw]
-        if not labels.is_cuda:
-            raise RuntimeError("BoundaryIoUMetric counts on the GPU (sg_boundary_accumulate): labels must be a device tensor; "
-                               "there is no CPU fallback")
-        gt = torch.as_tensor(gt)
-        if gt.dtype not in (torch.uint8, torch.int64):
-            gt = gt.to(torch.int64)
-        gt = gt.to(labels.device).reshape(-1)
-        labels = labels.reshape(-1)
+        labels, gt = _flat_on_device("BoundaryIoUMetric", "sg_boundary_accumulate", labels, gt)
         K = self._classes()
         ops.confusion_accumulate(labels, gt, self._ensure(labels.device), K, self.ignore_index, self.reduce_zero_label)
         ops.boundary_accumulate(labels, gt, image_hw, ds, self._ensure_areas(labels.device), K, self.ignore_index, self.reduce_zero_label)
@@ -288,9 +304,123 @@ class BoundaryIoUMetric(IoUMetric):
         return out
 
 
+TOLERANT_KEYS = {"region": ("RelPrecision", "RelRecall", "RelFscore", "mRelPrecision", "mRelRecall", "mRelFscore"),
+                 "contour": ("BPrecision", "BRecall", "BFscore", "mBPrecision", "mBRecall", "mBF")}
+
+
+def metrics_from_tolerant(counts, mode: str = "region", nan_to_num: Optional[int] = None) -> dict:
+    """Relaxed precision / recall / F (``mode`` "region": Mnih & Hinton 2010) or the boundary precision / recall / F-score ("contour":
+    Martin et al. 2004, Csurka et al. 2013) from the counts int64 [4,K] of ``sg_tolerant_accumulate`` (rows: predicted, predicted and
+    right within the tolerance, true, true and found): precision = counts[1] / counts[0], recall = counts[3] / counts[2],
+    F = 2PR / (P + R), float64 [K], NaN where a denominator is 0.  Keys ``RelPrecision`` / ``RelRecall`` / ``RelFscore`` or
+    ``BPrecision`` / ``BRecall`` / ``BFscore``, and ``summary`` with ``mRelPrecision`` / ``mRelRecall`` / ``mRelFscore`` or
+    ``mBPrecision`` / ``mBRecall`` / ``mBF``: ``nanmean * 100`` rounded to 2 decimals, NaN classes left out (``nan_to_num`` replaces NaN
+    first), as ``metrics_from_boundary`` does."""
+    if mode not in TOLERANT_KEYS:
+        raise ValueError(f"metrics_from_tolerant: mode must be one of {sorted(TOLERANT_KEYS)}, got {mode!r}")
+    a = counts.detach().cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)
+    if a.ndim != 2 or a.shape[0] != 4 or a.shape[1] < 1:
+        raise ValueError(f"tolerant counts must be [4,K] with K >= 1, got shape {a.shape}")
+    if not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"tolerant counts must hold integers, got {a.dtype}")
+    pred, right, true, found = (a[i].astype(np.float64) for i in range(4))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p, r = right / pred, found / true
+        vals = [np.asarray(v, dtype=np.float64) for v in (p, r, 2 * p * r / (p + r))]
+    if nan_to_num is not None:
+        vals = [np.nan_to_num(v, nan=nan_to_num) for v in vals]
+    keys = TOLERANT_KEYS[mode]
+    out = dict(zip(keys[:3], vals))
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", category=RuntimeWarning)
+        out["summary"] = {k: float(np.round(np.nanmean(v) * 100, 2)) for k, v in zip(keys[3:], vals)}
+    return out
+
+
+class RelaxedMetric(IoUMetric):
+    """``IoUMetric`` plus the tolerant scores: the confusion table as before and ``tolerant_counts`` int64 [4,K]
+    (``sg_tolerant_accumulate``).  ``mode`` "region" gives relaxed precision / recall / F (roads), "contour" the boundary F-score.
+    The tolerance is ``tolerance_ratio`` of each image's diagonal (``ops.tolerance_sq``; 0.0075) or the fixed ``tolerance_px``
+    (an integer in [0, 254]), which overrides the ratio.
+
+    ``add(labels, gt)`` takes one 2-D map ([H,W] or [1,H,W]) and counts both tables; ``add_flat(labels, gt, image_hw)`` the flat buffers
+    of a flush group with the sizes of its images; ``reduce(group)`` sums both tables; ``add_confusion`` is IoUMetric's and leaves the
+    tolerant counts alone; ``compute()`` returns IoUMetric's dict plus the keys of ``metrics_from_tolerant``, merged into ``summary``."""
+
+    def __init__(self, *args, mode: str = "region", tolerance_px: Optional[int] = None, tolerance_ratio: float = 0.0075, **kwargs):
+        from . import ops
+        if mode not in ops.TOLERANT_MODES:
+            raise ValueError(f"RelaxedMetric: mode must be one of {sorted(ops.TOLERANT_MODES)}, got {mode!r}")
+        if tolerance_px is not None:
+            if isinstance(tolerance_px, bool) or not isinstance(tolerance_px, int) or not 0 <= tolerance_px <= 254:
+                raise ValueError(f"tolerance_px must be an integer in [0, 254] or None, got {tolerance_px!r}")
+        else:
+            ops.tolerance_sq((1, 1), tolerance_ratio)                        # the ratio's own checks
+        super().__init__(*args, **kwargs)
+        if self.num_classes is not None and self.num_classes > ops.TOLERANT_MAX_K:
+            raise ValueError(f"RelaxedMetric: num_classes={self.num_classes} exceeds {ops.TOLERANT_MAX_K}")
+        self.mode, self.tolerance_px, self.tolerance_ratio = mode, tolerance_px, tolerance_ratio
+        self._counts: Optional[torch.Tensor] = None
+
+    def tolerance_sq(self, hw) -> int:
+        """The squared tolerance of an image of size ``hw``."""
+        from . import ops
+        return self.tolerance_px * self.tolerance_px if self.tolerance_px is not None else ops.tolerance_sq(hw, self.tolerance_ratio)
+
+    def _ensure_counts(self, device) -> torch.Tensor:
+        K = self._classes()
+        if self._counts is None:
+            self._counts = torch.zeros(4, K, dtype=torch.int64, device=device)
+        elif self._counts.device != torch.device(device):
+            self._counts = self._counts.to(device)
+        return self._counts
+
+    @property
+    def tolerant_counts(self) -> torch.Tensor:
+        """The [4,K] int64 counts: predicted, predicted and right, true, true and found."""
+        return self._ensure_counts("cpu" if self._counts is None else self._counts.device)
+
+    def reset(self) -> None:
+        super().reset()
+        self._counts = None
+
+    def add(self, labels: torch.Tensor, gt: torch.Tensor) -> None:
+        """Counts one image in both tables: labels int64 and gt uint8 / int64, [H,W] or [1,H,W] of one size.  The search needs the
+        image's shape, so a flat buffer goes through ``add_flat``."""
+        gt, hw = _one_map("RelaxedMetric", labels, gt)
+        self.add_flat(labels.reshape(-1), gt.reshape(-1), [hw])
+
+    def add_flat(self, labels: torch.Tensor, gt: torch.Tensor, image_hw) -> None:
+        """Counts the images that lie back to back in the flat ``labels`` / ``gt`` buffers (a flush group's), sizes ``image_hw``: one
+        sg_confusion_accumulate launch and one sg_tolerant_accumulate call on the current stream."""
+        from . import ops
+        image_hw = _flat_sizes("RelaxedMetric", labels, image_hw)
+        ts = [self.tolerance_sq(hw) for hw in image_hw]
+        labels, gt = _flat_on_device("RelaxedMetric", "sg_tolerant_accumulate", labels, gt)
+        K = self._classes()
+        ops.confusion_accumulate(labels, gt, self._ensure(labels.device), K, self.ignore_index, self.reduce_zero_label)
+        ops.tolerant_accumulate(labels, gt, image_hw, ts, self._ensure_counts(labels.device), K, self.ignore_index, self.reduce_zero_label,
+                                self.mode)
+
+    def reduce(self, group=None) -> None:
+        """Sums both tables over the ranks of ``group``: two all_reduces."""
+        import torch.distributed as dist
+        super().reduce(group)
+        dist.all_reduce(self.tolerant_counts, op=dist.ReduceOp.SUM, group=group)
+
+    def compute(self) -> dict:
+        out = super().compute()
+        t = metrics_from_tolerant(self.tolerant_counts, self.mode, self.nan_to_num)
+        summary = dict(out["summary"], **t.pop("summary"))
+        out.update(t)
+        out["summary"] = summary
+        return out
+
+
 try:  # with mmseg installed the classes are also buildable from a config, under names that leave mmseg's own IoUMetric alone
     from mmseg.registry import METRICS as _METRICS
     _METRICS.register_module(name="HipIoUMetric", module=IoUMetric)
     _METRICS.register_module(name="HipBoundaryIoUMetric", module=BoundaryIoUMetric)
+    _METRICS.register_module(name="HipRelaxedMetric", module=RelaxedMetric)
 except Exception:
     pass

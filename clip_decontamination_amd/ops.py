@@ -1596,3 +1596,79 @@ def boundary_accumulate(labels_flat, gt_flat, image_hw, d, areas, K: int, ignore
     check(lib.sg_boundary_accumulate(ptr(labels_flat), ptr(gt_flat), fmt, hw, off, dd, N, K, int(ignore_index), int(bool(reduce_zero_label)),
                                      ptr(areas), wp, wn, stream_ptr()), "sg_boundary_accumulate")
     return areas
+
+
+# ---- Tolerant matching: relaxed precision / recall and the boundary F-score (sg_tolerant_accumulate; the definition: include/segearth_hip.h) --
+TOLERANT_MAX_SQ = 254 * 254                                              # the largest squared tolerance: a radius of 254 px
+TOLERANT_MAX_K = 127                                                     # the cap of sg_confusion_accumulate
+TOLERANT_MODES = {"region": _lib.TOL_REGION, "contour": _lib.TOL_CONTOUR}
+
+
+def tolerance_sq(hw, ratio=0.0075):
+    """The squared tolerance of an image of size ``hw`` = (H, W): r = max(1, ceil(ratio * sqrt(H*H + W*W))), tol_sq = r*r, host
+    arithmetic in double (ratio 0.0075 of the diagonal, the boundary F-measure's: 6 px on a 512 tile, 38 px on 2048 x 4608)."""
+    import math
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not (ratio > 0) or not math.isfinite(ratio):
+        raise ValueError(f"tolerance_ratio must be a finite number > 0 (a share of the image diagonal), got {ratio!r}")
+    h, w = (int(v) for v in hw)
+    if h < 1 or w < 1:
+        raise ValueError(f"tolerance_sq: an image of size {h} x {w}")
+    r = max(1, int(math.ceil(float(ratio) * math.sqrt(h * h + w * w))))
+    if r * r > TOLERANT_MAX_SQ:
+        raise ValueError(f"tolerance_sq: ratio {ratio} of the diagonal of {h} x {w} is {r} px, above the limit of 254 (distances are "
+                         "kept in one byte)")
+    return r * r
+
+
+def tolerant_args(image_hw, tol_sq, mode):
+    """The checks of sg_tolerant_accumulate, before any library call: sizes positive and below 2^31 pixels per image, every squared
+    tolerance an integer in [0, 254^2] (one serves every image), a known mode -> (image_hw, tolerances, mode code)."""
+    if mode not in TOLERANT_MODES:
+        raise ValueError(f"tolerant: mode must be one of {sorted(TOLERANT_MODES)}, got {mode!r}")
+    image_hw = [(int(h), int(w)) for h, w in image_hw]
+    if not image_hw or any(h <= 0 or w <= 0 for h, w in image_hw):
+        raise ValueError(f"tolerant: needs at least one image of positive size, got {image_hw}")
+    if any(h * w > BOUNDARY_MAX_PIXELS for h, w in image_hw):
+        raise ValueError(f"tolerant: an image of 2^31 or more pixels is not supported, got {image_hw}")
+    ts = list(tol_sq) if isinstance(tol_sq, (list, tuple)) else [tol_sq] * len(image_hw)
+    if len(ts) != len(image_hw):
+        raise ValueError(f"tolerant: {len(ts)} tolerances for {len(image_hw)} images")
+    for v in ts:
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= TOLERANT_MAX_SQ:
+            raise ValueError(f"tolerant: the squared tolerance tol_sq must be an integer in [0, {TOLERANT_MAX_SQ}], got {v!r}")
+    return image_hw, ts, TOLERANT_MODES[mode]
+
+
+@on_tensor_device
+def tolerant_accumulate(labels_flat, gt_flat, image_hw, tol_sq, counts, K: int, ignore_index: int = 255, reduce_zero_label: bool = False,
+                        mode: str = "region"):
+    """sg_tolerant_accumulate on the current stream: per class, the marked pixels (``mode`` "region": all; "contour": the class
+    outlines) of the predictions that have a marked pixel of the same class of the (transformed) truth within sqrt(``tol_sq``) pixels,
+    and the other way round, over N images that lie back to back in ``labels_flat`` (int64) and ``gt_flat`` (uint8 or int64), sizes
+    ``image_hw``, squared tolerances ``tol_sq`` (one integer or one per image).  The counts are ADDED to ``counts`` int64 [4,K]
+    (predicted, predicted and right, true, true and found), which is returned.  Nothing comes back to the host."""
+    image_hw, ts, mode_code = tolerant_args(image_hw, tol_sq, mode)
+    K = int(K)
+    if not 1 <= K <= TOLERANT_MAX_K:
+        raise ValueError(f"tolerant_accumulate: K={K} outside [1, {TOLERANT_MAX_K}] (the cap of sg_confusion_accumulate)")
+    if not torch.is_tensor(labels_flat) or labels_flat.dtype != torch.int64:
+        raise TypeError("tolerant_accumulate: labels must be an int64 tensor")
+    if not torch.is_tensor(gt_flat) or gt_flat.dtype not in (torch.uint8, torch.int64):
+        raise TypeError("tolerant_accumulate: gt must be a uint8 or int64 tensor")
+    N, pix, hw, off, tt = _boundary_arrays(image_hw, ts)
+    if labels_flat.numel() != pix[-1] or gt_flat.numel() != pix[-1]:
+        raise ValueError(f"tolerant_accumulate: {N} images of sizes {image_hw} against {labels_flat.numel()} labels and "
+                         f"{gt_flat.numel()} truth pixels")
+    if not torch.is_tensor(counts) or counts.dtype != torch.int64 or not counts.is_contiguous() or counts.numel() != 4 * K:
+        raise ValueError(f"tolerant_accumulate: counts must be contiguous int64 with {4 * K} elements for K={K}")
+    _require_gpu(labels_flat, gt_flat, counts)
+    if gt_flat.device != labels_flat.device or counts.device != labels_flat.device:
+        raise ValueError("tolerant_accumulate: labels, gt and counts must live on one device")
+    lib = _lib.load()
+    labels_flat, gt_flat = labels_flat.contiguous().view(-1), gt_flat.contiguous().view(-1)
+    buf = scratch(int(lib.sg_tolerant_workspace_bytes(pix[-1], K)), labels_flat.device)
+    wp, wn = _aligned(buf)
+    fmt = _lib.GT_U8 if gt_flat.dtype == torch.uint8 else _lib.GT_I64
+    check(lib.sg_tolerant_accumulate(ptr(labels_flat), ptr(gt_flat), fmt, hw, off, tt, N, K, mode_code, int(ignore_index),
+                                     int(bool(reduce_zero_label)), ptr(counts), wp, wn, stream_ptr()), "sg_tolerant_accumulate")
+    return counts

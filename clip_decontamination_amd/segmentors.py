@@ -571,7 +571,7 @@ class _HipSegmentorBase(_Base):
 
     @torch.no_grad()
     def evaluate(self, inputs, gt_maps, metric=None, reduce_zero_label=False, ignore_index=255, iou_metrics=("mIoU",), at_gt_size=False,
-                 boundary_ratio=None, boundary_px=None):
+                 boundary_ratio=None, boundary_px=None, relaxed_px=None, relaxed_ratio=None, relaxed_mode="region"):
         """Labels to score without leaving the device: what the reference's ``test_evaluator = dict(type='IoUMetric', ...)`` reports.
         inputs: as ``predict_many``; gt_maps: one [H,W] / [1,H,W] uint8 or int64 tensor or numpy array per image, of the image's size.
         Returns ``(metric.compute(), metric)``; pass ``metric`` back in to accumulate over the calls of a dataset loop (its own
@@ -592,12 +592,26 @@ class _HipSegmentorBase(_Base):
         or the one passed in, whose own ratio / width hold.  Every flush group's flat labels then go to ``metric.add_flat`` with the
         sizes of its images, which adds one sg_boundary_accumulate call per group, and the result carries ``BIoU`` and
         ``summary['mBIoU']``.  It reads final labels only, so it composes with ``at_gt_size``, ``area_thd``, ``min_region``, PAMR,
-        ``blend`` and TTA."""
-        from .metrics import BoundaryIoUMetric, IoUMetric
+        ``blend`` and TTA.
+        ``relaxed_px`` / ``relaxed_ratio`` / ``relaxed_mode``: relaxed precision / recall / F (``relaxed_mode`` "region", the road
+        score) or the boundary F-score ("contour") next to the plain metric (the definition: sg_tolerant_accumulate in
+        include/segearth_hip.h).  With both None and no ``RelaxedMetric`` passed in, nothing above changes.  With one of them set a
+        ``RelaxedMetric`` is built here with the fixed tolerance ``relaxed_px`` or ``relaxed_ratio`` of each image's diagonal; one that
+        is passed in keeps its own settings.  It is fed by ``add_flat`` per flush group exactly where the boundary metric is fed, which
+        adds one sg_tolerant_accumulate call per group, and composes in the same way.  ``relaxed_*`` together with ``boundary_*``,
+        or a passed metric of the other kind, is refused: one metric object with both tables is not built."""
+        from .metrics import BoundaryIoUMetric, IoUMetric, RelaxedMetric
         boundary = boundary_ratio is not None or boundary_px is not None or isinstance(metric, BoundaryIoUMetric)
+        relaxed = relaxed_px is not None or relaxed_ratio is not None or isinstance(metric, RelaxedMetric)
         if getattr(self, "tile_group", None) is not None:
             raise ValueError("evaluate: tile_group sharding is not supported (each rank would have to count its own band against the "
                              "matching rows of the truth); evaluate whole images per rank and call metric.reduce(group)")
+        if boundary and relaxed:
+            raise ValueError("evaluate: relaxed_* and boundary_* (or a metric of the other kind) in one call are not supported: one "
+                             "metric object with both tables is not built; evaluate twice")
+        if relaxed and metric is not None and not isinstance(metric, RelaxedMetric):
+            raise TypeError("evaluate: relaxed_px / relaxed_ratio need a RelaxedMetric (or metric=None to have one built), got "
+                            f"{type(metric).__name__}")
         if boundary and metric is not None and not isinstance(metric, BoundaryIoUMetric):
             raise TypeError("evaluate: boundary_ratio / boundary_px need a BoundaryIoUMetric (or metric=None to have one built), got "
                             f"{type(metric).__name__}")
@@ -605,6 +619,10 @@ class _HipSegmentorBase(_Base):
             metric = BoundaryIoUMetric(ignore_index=ignore_index, iou_metrics=list(iou_metrics), num_classes=self.num_classes,
                                        reduce_zero_label=reduce_zero_label, boundary_px=boundary_px,
                                        **({} if boundary_ratio is None else {"boundary_ratio": boundary_ratio}))
+        elif metric is None and relaxed:
+            metric = RelaxedMetric(ignore_index=ignore_index, iou_metrics=list(iou_metrics), num_classes=self.num_classes,
+                                   reduce_zero_label=reduce_zero_label, mode=relaxed_mode, tolerance_px=relaxed_px,
+                                   **({} if relaxed_ratio is None else {"tolerance_ratio": relaxed_ratio}))
         elif metric is None:
             metric = IoUMetric(ignore_index=ignore_index, iou_metrics=list(iou_metrics), num_classes=self.num_classes,
                                reduce_zero_label=reduce_zero_label)
@@ -641,7 +659,7 @@ class _HipSegmentorBase(_Base):
         if self.slide_crop <= 0:                                             # whole-image inference has no windows to pack
             labs = self.predict_many(imgs, None, ori_shapes=ori) if at_gt_size else [self.predict(imgs[i][None], None) for i in range(n)]
             for i in range(n):
-                if boundary:
+                if boundary or relaxed:
                     metric.add_flat(labs[i].reshape(-1), gt_flat[off[i]:off[i + 1]], [tuple(labs[i].shape[-2:])])
                 else:
                     metric.add(labs[i].reshape(-1), gt_flat[off[i]:off[i + 1]])
@@ -651,7 +669,7 @@ class _HipSegmentorBase(_Base):
                 gt = gt_flat[off[idx[0]]:off[idx[-1] + 1]]
             else:                                                            # tile-size groups interleave images: gather on the device
                 gt = torch.cat([gt_flat[off[k]:off[k + 1]] for k in idx])
-            if boundary:
+            if boundary or relaxed:
                 metric.add_flat(flat, gt, [tuple(x.shape[-2:]) for x in labs])
             else:
                 metric.add(flat, gt)

@@ -980,6 +980,55 @@ int sg_boundary_accumulate(const int64_t* labels, const void* gt, int gt_format,
                            const int32_t* d, int N, int K, int ignore_index, int reduce_zero_label, int64_t* areas, void* workspace,
                            size_t workspace_bytes, sg_stream s);
 
+/* ---- Tolerant matching: relaxed precision / recall (Mnih & Hinton 2010) and the boundary F-score (Martin et al. 2004; Csurka et al. 2013) --
+ * Both scores are one count: per class, the marked pixels of one label map that have a marked pixel of the same class in the other map
+ * within a Euclidean distance.  Area IoU and Boundary IoU do not give it: a two-pixel-wide road lies wholly inside its own band, so a
+ * prediction displaced by two pixels scores about zero BIoU and about one relaxed F.  It only reads final labels.
+ * Inputs.  A prediction P and a truth G of H x W, G taken after reduce_zero_label (the rule of sg_confusion_accumulate: raw 0 -> 255, raw
+ *   255 stays, else g - 1), an integer tol_sq >= 0 and a mode.
+ * Marked pixels M_L of a map L.  SG_TOL_REGION: every pixel.  SG_TOL_CONTOUR: a pixel is marked iff one of its 4-neighbours inside the
+ *   image holds another 64-bit value (of G: after the transform).  The image border is not a contour.  An ignored truth value is a value
+ *   like any other here: a class that borders an ignored area has a contour there, as in Boundary IoU.
+ * Class sets and nearness.  S_L(k) = { q in M_L : L(q) == k } for 0 <= k < K; near_L(p,k) holds iff some q in S_L(k) has
+ *   (py-qy)^2 + (px-qx)^2 <= tol_sq, in integer arithmetic: tol_sq = 10 reaches the offset (1,3), tol_sq = 9 does not.
+ * Sources and targets.  A source p is counted only where G(p) is not ignore_index; targets are never restricted by that.
+ * Counts, ADDED to counts int64 [4][K] (the caller zeroes it):
+ *     counts[0][k] += (p in S_P(k), counted)                   predicted pixels of class k
+ *     counts[1][k] += (p in S_P(k), counted, near_G(p,k))      ... that are right within the tolerance
+ *     counts[2][k] += (p in S_G(k), counted)                   true pixels of class k
+ *     counts[3][k] += (p in S_G(k), counted, near_P(p,k))      ... that are found within the tolerance
+ *   Values outside [0,K) add to nothing and match nothing.
+ * Scores, in float64 on the caller's side, NaN where the denominator is 0: precision = counts[1] / counts[0], recall = counts[3] /
+ *   counts[2], F = 2PR / (P + R).
+ * Identities.  With tol_sq = 0 in region mode rows 1 and 3 both equal area_intersect, rows 0 and 2 area_pred_label and area_label of the
+ *   confusion table on the same inputs.  With tol_sq >= (H-1)^2 + (W-1)^2 a source is matched iff its class is marked anywhere in the
+ *   other map.
+ * Limits.  0 <= tol_sq <= 254*254, so the radius r = isqrt(tol_sq) <= 254 and a one-byte capped distance suffices; 1 <= K <= 127, as
+ *   in the other two tables; an image has fewer than 2^31 pixels.
+ * Tolerance from a ratio (host arithmetic in double, per image): r = max(1, ceil(ratio * sqrt(H*H + W*W))), tol_sq = r*r; the default
+ *   ratio is 0.0075 (38 px on 2048 x 4608); a radius above 254 is refused.
+ * N >= 1 images lie back to back in flat buffers with HOST arrays image_hw, offset and tol_sq[n]; the layout rules are those of
+ * sg_boundary_accumulate (ascending, no overlap, inside the n_pixels_total = sum of H*W pixels of the call).
+ *   sg_tolerant_workspace_bytes  min(K, 8) planes of n_pixels_total bytes, each rounded up to 256: per class of a group of up to 8 classes
+ *                                the distance, capped at 255, to the nearest marked pixel of that class in the same row.  Groups and
+ *                                directions reuse the planes, so it does not grow with K beyond 8 planes.  0 for a negative count or a K
+ *                                outside [1, 127].
+ *   sg_tolerant_accumulate       per image, per class group and per direction a row pass over the target map (two scans per row, no loop
+ *                                over the tolerance) and a count over the source map (a walk over at most 2r + 1 rows of those bytes against
+ *                                w(dy) = isqrt(tol_sq - dy*dy), stopped at the first hit: linear in r), into 2K 32-bit LDS bins per
+ *                                workgroup, then one 64-bit add per non-zero bin per workgroup.
+ * Integers and integer atomics only: byte-identical across repeats.  Nothing is copied or synchronised; no workgroup waits for another; the
+ * inputs are only read.
+ * Refused with SG_ERR_INVALID before any launch, counts untouched: a null pointer, an unknown format or mode, N < 1, an image of
+ * non-positive size or of 2^31 or more pixels, an offset that puts an image over the one before it or outside the call's pixels, tol_sq
+ * outside [0, 254*254], K outside [1, 127], a misaligned int64 buffer, a workspace that is too small. */
+#define SG_TOL_REGION 0
+#define SG_TOL_CONTOUR 1
+size_t sg_tolerant_workspace_bytes(int64_t n_pixels_total, int K);
+int sg_tolerant_accumulate(const int64_t* labels, const void* gt, int gt_format, const int32_t* image_hw, const int64_t* offset,
+                           const int32_t* tol_sq, int N, int K, int mode, int ignore_index, int reduce_zero_label, int64_t* counts,
+                           void* workspace, size_t workspace_bytes, sg_stream s);
+
 #ifdef __cplusplus
 }
 #endif
