@@ -185,6 +185,8 @@ SIGNATURES = {
     "sg_boundary_accumulate": (I, [P, P, I, P, P, P, I, I, I, I, P, P, Z, P]),
     "sg_tolerant_workspace_bytes": (Z, [L, I]),
     "sg_tolerant_accumulate": (I, [P, P, I, P, P, P, I, I, I, I, I, P, P, Z, P]),
+    "sg_object_workspace_bytes": (Z, [L]),
+    "sg_object_match": (I, [P, P, I, P, P, I, I, I, L, L, I, I, I, I, I, P, P, P, Z, P]),
 }
 
 _lib = None

@@ -21,7 +21,7 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libsegearth_hip.so")
 ARCH = "gfx950"
 SOURCES = ["capi.hip", "gemm_bf16.hip", "gemm_f32.hip", "attention.hip", "attention_f16.hip", "attention_h2.hip", "rowops.hip", "patchify.hip", "refine.hip",
-           "head.hip", "jbu.hip", "ctd.hip", "metric.hip", "pamr.hip", "area.hip", "sieve.hip", "boundary.hip", "tolerant.hip"]
+           "head.hip", "jbu.hip", "ctd.hip", "metric.hip", "pamr.hip", "area.hip", "sieve.hip", "boundary.hip", "tolerant.hip", "objmatch.hip"]
 # the attention loops count vector-issue slots between MFMAs: SLP-packed v_pk_add_f32 / v_pk_mul_f32 cost several plain f32 ops there
 # (MI355X_MICROARCH.md, 'price of one filler beside MFMAs'), so the scalar f32 arithmetic of those units stays scalar.
 # jbu.hip: with the Keff arithmetic of jbu_conv_lowres_kernel SLP-packed into v_pk_fma_f32 the kernel was not reproducible from run to

@@ -417,10 +417,108 @@ class RelaxedMetric(IoUMetric):
         return out
 
 
+OBJECT_KEYS = ("ObjPrecision", "ObjRecall", "ObjF1", "SQ", "PQ")
+
+
+def metrics_from_objects(counts, nan_to_num: Optional[int] = None) -> dict:
+    """Object-level precision / recall / F1 and panoptic quality (Kirillov et al., CVPR 2019, with connected regions as the segments)
+    from the counts int64 [4,K] of ``sg_object_match`` (rows: matched pairs TP, predicted objects, true objects, the matched pairs' IoU
+    in steps of 2^-24): ``ObjPrecision`` = TP / counts[1], ``ObjRecall`` = TP / counts[2], ``ObjF1`` = RQ = 2 TP / (counts[1] +
+    counts[2]), ``SQ`` = counts[3] / 2^24 / TP, ``PQ`` = SQ * RQ, float64 [K], NaN where a denominator is 0; and ``summary`` with
+    ``mObjPrecision`` / ``mObjRecall`` / ``mObjF1`` / ``mSQ`` / ``mPQ``: ``nanmean * 100`` rounded to 2 decimals, NaN classes left out
+    (``nan_to_num`` replaces NaN first), as ``metrics_from_tolerant`` does."""
+    a = counts.detach().cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)
+    if a.ndim != 2 or a.shape[0] != 4 or a.shape[1] < 1:
+        raise ValueError(f"object counts must be [4,K] with K >= 1, got shape {a.shape}")
+    if not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"object counts must hold integers, got {a.dtype}")
+    tp, pred, true, iou_q = (a[i].astype(np.float64) for i in range(4))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rq, sq = 2 * tp / (pred + true), iou_q / float(1 << 24) / tp
+        vals = [np.asarray(v, dtype=np.float64) for v in (tp / pred, tp / true, rq, sq, sq * rq)]
+    if nan_to_num is not None:
+        vals = [np.nan_to_num(v, nan=nan_to_num) for v in vals]
+    out = dict(zip(OBJECT_KEYS, vals))
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", category=RuntimeWarning)
+        out["summary"] = {"m" + k: float(np.round(np.nanmean(v) * 100, 2)) for k, v in zip(OBJECT_KEYS, vals)}
+    return out
+
+
+class ObjectMetric(IoUMetric):
+    """``IoUMetric`` plus the object-level scores: the confusion table as before and ``object_counts`` int64 [4,K]
+    (``sg_object_match``): per class the connected regions of prediction and truth, matched where their IoU is strictly above
+    ``object_iou`` (a float or a ``(num, den)`` pair in [1/2, 1), ``ops.object_iou_fraction``).  A region is an object when it has at
+    least ``min_area`` pixels and its class is not ``skip_label`` (the background of a building or road set); ``connectivity`` 4 or 8.
+
+    ``add(labels, gt)`` takes one 2-D map ([H,W] or [1,H,W]) and counts both tables; ``add_flat(labels, gt, image_hw)`` the flat buffers
+    of a flush group with the sizes of its images; ``reduce(group)`` sums both tables; ``add_confusion`` is IoUMetric's and leaves the
+    object counts alone; ``compute()`` returns IoUMetric's dict plus the keys of ``metrics_from_objects``, merged into ``summary``."""
+
+    def __init__(self, *args, object_iou=0.5, min_area: int = 1, connectivity: int = 4, skip_label: Optional[int] = None, **kwargs):
+        from . import ops
+        self.object_iou = ops.object_args([(1, 1)], 1, object_iou, connectivity, min_area, skip_label)[2]
+        super().__init__(*args, **kwargs)
+        if self.num_classes is not None and self.num_classes > ops.OBJECT_MAX_K:
+            raise ValueError(f"ObjectMetric: num_classes={self.num_classes} exceeds {ops.OBJECT_MAX_K}")
+        self.min_area, self.connectivity, self.skip_label = int(min_area), int(connectivity), skip_label
+        self._counts: Optional[torch.Tensor] = None
+
+    def _ensure_counts(self, device) -> torch.Tensor:
+        K = self._classes()
+        if self._counts is None:
+            self._counts = torch.zeros(4, K, dtype=torch.int64, device=device)
+        elif self._counts.device != torch.device(device):
+            self._counts = self._counts.to(device)
+        return self._counts
+
+    @property
+    def object_counts(self) -> torch.Tensor:
+        """The [4,K] int64 counts: matched pairs, predicted objects, true objects, the matched pairs' IoU in steps of 2^-24."""
+        return self._ensure_counts("cpu" if self._counts is None else self._counts.device)
+
+    def reset(self) -> None:
+        super().reset()
+        self._counts = None
+
+    def add(self, labels: torch.Tensor, gt: torch.Tensor, match_map: Optional[torch.Tensor] = None) -> None:
+        """Counts one image in both tables: labels int64 and gt uint8 / int64, [H,W] or [1,H,W] of one size.  The regions need the
+        image's shape, so a flat buffer goes through ``add_flat``."""
+        gt, hw = _one_map("ObjectMetric", labels, gt)
+        self.add_flat(labels.reshape(-1), gt.reshape(-1), [hw], match_map)
+
+    def add_flat(self, labels: torch.Tensor, gt: torch.Tensor, image_hw, match_map: Optional[torch.Tensor] = None) -> None:
+        """Counts the images that lie back to back in the flat ``labels`` / ``gt`` buffers (a flush group's), sizes ``image_hw``: one
+        sg_confusion_accumulate launch and one sg_object_match call on the current stream.  ``match_map``: None, or a uint8 tensor of
+        the labels' size that receives the TP / FP / FN picture (``ops.object_match``)."""
+        from . import ops
+        image_hw = _flat_sizes("ObjectMetric", labels, image_hw)
+        labels, gt = _flat_on_device("ObjectMetric", "sg_object_match", labels, gt)
+        K = self._classes()
+        ops.confusion_accumulate(labels, gt, self._ensure(labels.device), K, self.ignore_index, self.reduce_zero_label)
+        ops.object_match(labels, gt, image_hw, self._ensure_counts(labels.device), K, self.object_iou, self.connectivity, self.min_area,
+                         self.skip_label, self.ignore_index, self.reduce_zero_label, match_map)
+
+    def reduce(self, group=None) -> None:
+        """Sums both tables over the ranks of ``group``: two all_reduces."""
+        import torch.distributed as dist
+        super().reduce(group)
+        dist.all_reduce(self.object_counts, op=dist.ReduceOp.SUM, group=group)
+
+    def compute(self) -> dict:
+        out = super().compute()
+        t = metrics_from_objects(self.object_counts, self.nan_to_num)
+        summary = dict(out["summary"], **t.pop("summary"))
+        out.update(t)
+        out["summary"] = summary
+        return out
+
+
 try:  # with mmseg installed the classes are also buildable from a config, under names that leave mmseg's own IoUMetric alone
     from mmseg.registry import METRICS as _METRICS
     _METRICS.register_module(name="HipIoUMetric", module=IoUMetric)
     _METRICS.register_module(name="HipBoundaryIoUMetric", module=BoundaryIoUMetric)
     _METRICS.register_module(name="HipRelaxedMetric", module=RelaxedMetric)
+    _METRICS.register_module(name="HipObjectMetric", module=ObjectMetric)
 except Exception:
     pass

@@ -1672,3 +1672,89 @@ def tolerant_accumulate(labels_flat, gt_flat, image_hw, tol_sq, counts, K: int, 
     check(lib.sg_tolerant_accumulate(ptr(labels_flat), ptr(gt_flat), fmt, hw, off, tt, N, K, mode_code, int(ignore_index),
                                      int(bool(reduce_zero_label)), ptr(counts), wp, wn, stream_ptr()), "sg_tolerant_accumulate")
     return counts
+
+
+# ---- Object matching: object-level precision / recall / F1 and panoptic quality (sg_object_match; the definition: include/segearth_hip.h) --
+OBJECT_MAX_K = 127                                                       # the cap of sg_confusion_accumulate
+OBJECT_MAX_DEN = 1 << 20                                                 # the largest denominator of the IoU threshold
+OBJECT_SQ_ONE = 1 << 24                                                  # row 3 of the counts: IoU in steps of 2^-24
+OBJECT_MAX_PIXELS = (1 << 31) - 1                                        # per call
+OBJECT_MATCHED_PRED, OBJECT_UNMATCHED_PRED, OBJECT_MATCHED_TRUE, OBJECT_UNMATCHED_TRUE = 1, 2, 4, 8      # the bits of match_map
+
+
+def object_iou_fraction(t):
+    """The IoU threshold of the object match as an exact fraction: ``t`` is a ``(num, den)`` pair of integers or a float, which is
+    converted by ``fractions.Fraction(str(float(t)))`` (0.5 -> (1, 2), 0.6 -> (3, 5): the decimal that was written, not the binary
+    double behind it).  The threshold must lie in [1/2, 1) -- below 1/2 the match is not unique -- with a denominator of at most 2^20
+    -> (num, den) in lowest terms."""
+    import math
+    from fractions import Fraction
+    if isinstance(t, (tuple, list)):
+        if len(t) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in t) or t[1] < 1:
+            raise ValueError(f"object_iou: a threshold pair must be (num, den) of integers with den >= 1, got {t!r}")
+        f = Fraction(int(t[0]), int(t[1]))
+    elif isinstance(t, bool) or not isinstance(t, (int, float)) or not math.isfinite(t):
+        raise ValueError(f"object_iou must be a finite number or a (num, den) pair, got {t!r}")
+    else:
+        f = Fraction(str(float(t)))
+    if not Fraction(1, 2) <= f < 1:
+        raise ValueError(f"object_iou={t!r} outside [1/2, 1): below 1/2 an object could have two partners, at 1 nothing matches")
+    if f.denominator > OBJECT_MAX_DEN:
+        raise ValueError(f"object_iou={t!r} has the denominator {f.denominator}, above the limit of 2^20")
+    return f.numerator, f.denominator
+
+
+def object_args(image_hw, K, iou=(1, 2), connectivity=4, min_area=1, skip_label=None):
+    """The checks of sg_object_match, before any library call: sizes positive and below 2^31 pixels per call, K in [1, 127], a threshold
+    in [1/2, 1), connectivity 4 or 8, min_area an integer >= 1, skip_label None or an integer -> (image_hw, K, (num, den))."""
+    image_hw = [(int(h), int(w)) for h, w in image_hw]
+    if not image_hw or any(h <= 0 or w <= 0 for h, w in image_hw):
+        raise ValueError(f"object_match: needs at least one image of positive size, got {image_hw}")
+    if sum(h * w for h, w in image_hw) > OBJECT_MAX_PIXELS:
+        raise ValueError("object_match: 2^31 or more pixels in one call are not supported (region roots are 32-bit)")
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= OBJECT_MAX_K:
+        raise ValueError(f"object_match: K={K!r} outside [1, {OBJECT_MAX_K}] (the cap of sg_confusion_accumulate)")
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError(f"object_match: connectivity must be 4 or 8, got {connectivity!r}")
+    if isinstance(min_area, bool) or not isinstance(min_area, int) or min_area < 1:
+        raise ValueError(f"object_match: min_area must be an integer >= 1 (a region is an object when its area is at least it), got {min_area!r}")
+    if skip_label is not None and (isinstance(skip_label, bool) or not isinstance(skip_label, int)):
+        raise ValueError(f"object_match: skip_label must be None or an integer label, got {skip_label!r}")
+    return image_hw, int(K), object_iou_fraction(iou)
+
+
+@on_tensor_device
+def object_match(labels, gt, image_hw, counts, K, iou=(1, 2), connectivity=4, min_area=1, skip_label=None, ignore_index=255,
+                 reduce_zero_label=False, match_map=None):
+    """sg_object_match on the current stream: per class, the connected regions of the predictions matched against those of the
+    (transformed) truth at an IoU strictly above ``iou`` (a float or a ``(num, den)`` pair in [1/2, 1)), over N images that lie back to
+    back in ``labels`` (int64) and ``gt`` (uint8 or int64), sizes ``image_hw``.  A region is an object when its value is a class in
+    [0, K) other than ``skip_label``, it has at least ``min_area`` pixels and, for the truth, it is not ``ignore_index``.  The counts
+    are ADDED to ``counts`` int64 [4,K] (matched pairs, predicted objects, true objects, the matched pairs' IoU in steps of 2^-24), which
+    is returned; ``match_map``: None or a uint8 tensor of the labels' size that receives 1 / 2 (matched / unmatched predicted object)
+    plus 4 / 8 (matched / unmatched true object) per pixel.  Nothing comes back to the host."""
+    image_hw, K, (num, den) = object_args(image_hw, K, iou, connectivity, min_area, skip_label)
+    if not torch.is_tensor(labels) or labels.dtype != torch.int64:
+        raise TypeError("object_match: labels must be an int64 tensor")
+    if not torch.is_tensor(gt) or gt.dtype not in (torch.uint8, torch.int64):
+        raise TypeError("object_match: gt must be a uint8 or int64 tensor")
+    N, pix, hw, off, _ = _boundary_arrays(image_hw, [0] * len(image_hw))
+    if labels.numel() != pix[-1] or gt.numel() != pix[-1]:
+        raise ValueError(f"object_match: {N} images of sizes {image_hw} against {labels.numel()} labels and {gt.numel()} truth pixels")
+    if not torch.is_tensor(counts) or counts.dtype != torch.int64 or not counts.is_contiguous() or counts.numel() != 4 * K:
+        raise ValueError(f"object_match: counts must be contiguous int64 with {4 * K} elements for K={K}")
+    if match_map is not None and (not torch.is_tensor(match_map) or match_map.dtype != torch.uint8 or not match_map.is_contiguous() or
+                                  match_map.numel() != pix[-1]):
+        raise ValueError(f"object_match: match_map must be a contiguous uint8 tensor of {pix[-1]} elements")
+    _require_gpu(labels, gt, counts)
+    if gt.device != labels.device or counts.device != labels.device or (match_map is not None and match_map.device != labels.device):
+        raise ValueError("object_match: labels, gt, counts and match_map must live on one device")
+    lib = _lib.load()
+    labels, gt = labels.contiguous().view(-1), gt.contiguous().view(-1)
+    buf = scratch(int(lib.sg_object_workspace_bytes(pix[-1])), labels.device)
+    wp, wn = _aligned(buf)
+    fmt = _lib.GT_U8 if gt.dtype == torch.uint8 else _lib.GT_I64
+    check(lib.sg_object_match(ptr(labels), ptr(gt), fmt, hw, off, N, K, int(connectivity), int(min_area), 0 if skip_label is None else int(skip_label),
+                              int(skip_label is not None), num, den, int(ignore_index), int(bool(reduce_zero_label)), ptr(counts), ptr(match_map),
+                              wp, wn, stream_ptr()), "sg_object_match")
+    return counts

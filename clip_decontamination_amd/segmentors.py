@@ -571,7 +571,8 @@ class _HipSegmentorBase(_Base):
 
     @torch.no_grad()
     def evaluate(self, inputs, gt_maps, metric=None, reduce_zero_label=False, ignore_index=255, iou_metrics=("mIoU",), at_gt_size=False,
-                 boundary_ratio=None, boundary_px=None, relaxed_px=None, relaxed_ratio=None, relaxed_mode="region"):
+                 boundary_ratio=None, boundary_px=None, relaxed_px=None, relaxed_ratio=None, relaxed_mode="region", object_iou=None,
+                 object_min_area=1, object_include_bg=False):
         """Labels to score without leaving the device: what the reference's ``test_evaluator = dict(type='IoUMetric', ...)`` reports.
         inputs: as ``predict_many``; gt_maps: one [H,W] / [1,H,W] uint8 or int64 tensor or numpy array per image, of the image's size.
         Returns ``(metric.compute(), metric)``; pass ``metric`` back in to accumulate over the calls of a dataset loop (its own
@@ -599,8 +600,16 @@ class _HipSegmentorBase(_Base):
         ``RelaxedMetric`` is built here with the fixed tolerance ``relaxed_px`` or ``relaxed_ratio`` of each image's diagonal; one that
         is passed in keeps its own settings.  It is fed by ``add_flat`` per flush group exactly where the boundary metric is fed, which
         adds one sg_tolerant_accumulate call per group, and composes in the same way.  ``relaxed_*`` together with ``boundary_*``,
-        or a passed metric of the other kind, is refused: one metric object with both tables is not built."""
-        from .metrics import BoundaryIoUMetric, IoUMetric, RelaxedMetric
+        or a passed metric of the other kind, is refused: one metric object with both tables is not built.
+        ``object_iou`` / ``object_min_area`` / ``object_include_bg``: object-level precision / recall / F1 and panoptic quality next to
+        the plain metric (the definition: sg_object_match in include/segearth_hip.h).  With ``object_iou`` None and no ``ObjectMetric``
+        passed in, nothing above changes.  With it set (a float or a ``(num, den)`` pair in [1/2, 1)) an ``ObjectMetric`` is built here:
+        regions connected under ``region_connectivity``, of at least ``object_min_area`` pixels and, unless ``object_include_bg``, not
+        of the class ``bg_idx``; one that is passed in keeps its own settings.  It is fed by ``add_flat`` per flush group where the other
+        two are, which adds one sg_object_match call per group; it reads final labels only and composes in the same way.  ``object_*``
+        together with ``boundary_*`` or ``relaxed_*``, or a passed metric of another kind, is refused."""
+        from .metrics import BoundaryIoUMetric, IoUMetric, ObjectMetric, RelaxedMetric
+        objects = object_iou is not None or isinstance(metric, ObjectMetric)
         boundary = boundary_ratio is not None or boundary_px is not None or isinstance(metric, BoundaryIoUMetric)
         relaxed = relaxed_px is not None or relaxed_ratio is not None or isinstance(metric, RelaxedMetric)
         if getattr(self, "tile_group", None) is not None:
@@ -609,6 +618,11 @@ class _HipSegmentorBase(_Base):
         if boundary and relaxed:
             raise ValueError("evaluate: relaxed_* and boundary_* (or a metric of the other kind) in one call are not supported: one "
                              "metric object with both tables is not built; evaluate twice")
+        if objects and (boundary or relaxed):
+            raise ValueError("evaluate: object_* together with boundary_* or relaxed_* (or a metric of another kind) in one call is not "
+                             "supported: one metric object with several tables is not built; evaluate twice")
+        if objects and metric is not None and not isinstance(metric, ObjectMetric):
+            raise TypeError(f"evaluate: object_iou needs an ObjectMetric (or metric=None to have one built), got {type(metric).__name__}")
         if relaxed and metric is not None and not isinstance(metric, RelaxedMetric):
             raise TypeError("evaluate: relaxed_px / relaxed_ratio need a RelaxedMetric (or metric=None to have one built), got "
                             f"{type(metric).__name__}")
@@ -623,6 +637,11 @@ class _HipSegmentorBase(_Base):
             metric = RelaxedMetric(ignore_index=ignore_index, iou_metrics=list(iou_metrics), num_classes=self.num_classes,
                                    reduce_zero_label=reduce_zero_label, mode=relaxed_mode, tolerance_px=relaxed_px,
                                    **({} if relaxed_ratio is None else {"tolerance_ratio": relaxed_ratio}))
+        elif metric is None and objects:
+            metric = ObjectMetric(ignore_index=ignore_index, iou_metrics=list(iou_metrics), num_classes=self.num_classes,
+                                  reduce_zero_label=reduce_zero_label, object_iou=object_iou, min_area=object_min_area,
+                                  connectivity=getattr(self, "region_connectivity", 4),
+                                  skip_label=None if object_include_bg else int(self.bg_idx))
         elif metric is None:
             metric = IoUMetric(ignore_index=ignore_index, iou_metrics=list(iou_metrics), num_classes=self.num_classes,
                                reduce_zero_label=reduce_zero_label)
@@ -659,7 +678,7 @@ class _HipSegmentorBase(_Base):
         if self.slide_crop <= 0:                                             # whole-image inference has no windows to pack
             labs = self.predict_many(imgs, None, ori_shapes=ori) if at_gt_size else [self.predict(imgs[i][None], None) for i in range(n)]
             for i in range(n):
-                if boundary or relaxed:
+                if boundary or relaxed or objects:
                     metric.add_flat(labs[i].reshape(-1), gt_flat[off[i]:off[i + 1]], [tuple(labs[i].shape[-2:])])
                 else:
                     metric.add(labs[i].reshape(-1), gt_flat[off[i]:off[i + 1]])
@@ -669,7 +688,7 @@ class _HipSegmentorBase(_Base):
                 gt = gt_flat[off[idx[0]]:off[idx[-1] + 1]]
             else:                                                            # tile-size groups interleave images: gather on the device
                 gt = torch.cat([gt_flat[off[k]:off[k + 1]] for k in idx])
-            if boundary or relaxed:
+            if boundary or relaxed or objects:
                 metric.add_flat(flat, gt, [tuple(x.shape[-2:]) for x in labs])
             else:
                 metric.add(flat, gt)

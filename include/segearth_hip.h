@@ -1029,6 +1029,60 @@ int sg_tolerant_accumulate(const int64_t* labels, const void* gt, int gt_format,
                            const int32_t* tol_sq, int N, int K, int mode, int ignore_index, int reduce_zero_label, int64_t* counts,
                            void* workspace, size_t workspace_bytes, sg_stream s);
 
+/* ---- Object matching: object-level precision / recall / F1 and panoptic quality (Kirillov et al., "Panoptic Segmentation", CVPR 2019) ----
+ * The three tables above are pixel counts: one warehouse of 40 000 pixels outvotes forty missed houses of 400 pixels each.  This one
+ * counts objects: per class, which connected region of the prediction overlaps which connected region of the truth with an IoU above a
+ * threshold.  It only reads final labels.
+ * Inputs.  A prediction P of H x W, int64, and a truth G (SG_GT_U8 or SG_GT_I64) taken after reduce_zero_label (the rule of
+ *   sg_confusion_accumulate: raw 0 -> 255, raw 255 stays, else g - 1); call it G'.
+ * Objects of a map L.  A region is what sg_sieve calls a region: pixels of equal 64-bit value, connected under connectivity 4 or 8; its
+ *   root is its smallest raster index y*W + x.  A region is an *object of class k* when its value is k with 0 <= k < K, use_skip is 0 or
+ *   k != skip_label, its area >= min_area (>= 1) and, for the truth, k != ignore_index.  Ignored truth is a value like any other: it
+ *   separates regions and is itself no object.  Predicted objects are counted WHEREVER they lie, also on ignored truth (there they find no
+ *   partner and count as false positives); dropping predicted objects that lie mostly on ignored truth is a follow-up.
+ * Match.  A predicted object p and a true object g of the same class in the same image, I = |p n g|, U = |p| + |g| - I, match iff
+ *   I * iou_den > iou_num * U, in 64-bit integers, strictly.  1 <= iou_num < iou_den <= 2^20 and 2 * iou_num >= iou_den: with a threshold
+ *   of at least 1/2 and the strict comparison every object has at most one partner (Theorem 1 of the paper), so no ordering or greedy
+ *   assignment exists.  At 1/2 a pair at exactly IoU 0.5 is NOT a match: the panoptic-quality rule.
+ * Counts, ADDED to counts int64 [4][K] (the caller zeroes it):
+ *     counts[0][k]   matched pairs of class k                       TP
+ *     counts[1][k]   predicted objects of class k                   TP + FP
+ *     counts[2][k]   true objects of class k                        TP + FN
+ *     counts[3][k]   the sum over the matched pairs of floor(I * 2^24 / U), 64-bit integer division: an exact integer, independent of
+ *                    arrival order, like SG_REGION_SCORE_Q
+ * Scores, in float64 on the caller's side, NaN where a denominator is 0: precision = counts[0] / counts[1], recall = counts[0] /
+ *   counts[2], F1 = RQ = 2 counts[0] / (counts[1] + counts[2]), SQ = counts[3] / 2^24 / counts[0], PQ = SQ * RQ (connected regions as
+ *   the segments).
+ * match_map (optional, null allowed) uint8, laid out like labels, WRITTEN for every pixel of the call: a + b with a = 1 where the pixel's
+ *   predicted region is a matched object, 2 where it is an unmatched object, else 0; b = 4 where the pixel's true region is a matched
+ *   object, 8 where it is an unmatched object, else 0.  It is the TP / FP / FN picture, and a root pixel's byte joins the matches to the
+ *   rows of sg_regions.
+ * Limits.  1 <= K <= 127, as in the other tables; fewer than 2^31 pixels per call.
+ * N >= 1 images lie back to back in flat buffers with HOST arrays image_hw and offset; the layout rules are those of
+ * sg_boundary_accumulate (ascending, no overlap, inside the n_pixels_total = sum of H*W pixels of the call).  The images never connect.
+ *   sg_object_workspace_bytes  36 * n_pixels_total + 2 * (n_pixels_total rounded up to 256): per pixel G' int64, the candidate word u64,
+ *                              parent and area int32 of both maps, the intersection counter u32, and two planes of match marks u8.
+ *                              Linear in the pixels whatever the maps hold: there is no cap on the number of objects and no overflow
+ *                              case.  0 for a negative count.
+ *   sg_object_match            one kernel writes G'; then per launch sequence of up to SG_SIEVE_GROUP images the three labelling
+ *                              kernels of sg_sieve on P and on G', and: vote (one word per predicted root, candidate true root : 32 |
+ *                              counter : 32, a Boyer-Moore majority summary merged by a 64-bit compare-and-swap loop -- a match needs
+ *                              I > |p| / 2, so the partner is the strict majority among the true objects of p's class under p's pixels,
+ *                              and the summary finds a strict majority whatever the merge order), verify (I of the candidate, exactly),
+ *                              decide (over the root pixels: the integer test, K-wide LDS bins, one 64-bit add per non-zero bin per
+ *                              workgroup) and, with match_map, one pass that writes the bytes.  Votes and intersections merge in
+ *                              registers, across the wave and in an LDS cache of the workgroup (32 768 pixels) before they reach memory.
+ * Integers and integer atomics only: byte-identical across repeats.  Nothing is copied or synchronised; no workgroup waits for another
+ * (the compare-and-swap retry is lock-free); the inputs are only read.
+ * Refused with SG_ERR_INVALID before any launch, counts and match_map untouched: a null labels / gt / image_hw / offset / counts /
+ * workspace, an unknown format, N < 1, an image of non-positive size, 2^31 or more pixels in the call, an offset that puts an image over
+ * the one before it or outside the call's pixels, K outside [1, 127], a connectivity other than 4 or 8, min_area < 1, a threshold outside
+ * the limits above, a misaligned int64 buffer or workspace, a workspace that is too small. */
+size_t sg_object_workspace_bytes(int64_t n_pixels_total);
+int sg_object_match(const int64_t* labels, const void* gt, int gt_format, const int32_t* image_hw, const int64_t* offset, int N, int K,
+                    int connectivity, int64_t min_area, int64_t skip_label, int use_skip, int iou_num, int iou_den, int ignore_index,
+                    int reduce_zero_label, int64_t* counts, uint8_t* match_map, void* workspace, size_t workspace_bytes, sg_stream s);
+
 #ifdef __cplusplus
 }
 #endif
