@@ -20,8 +20,6 @@
 namespace sg {
 
 constexpr int BD_MAX_D = 4095;
-constexpr int BD_MAX_K = 127;                    // CF_MAX_K of metric.hip: one metric object holds both tables
-constexpr int64_t BD_MAX_PIXELS = ((int64_t)1 << 31) - 1;
 constexpr int BD_ROW_RUN = 8;                    // consecutive pixels per lane per chunk of the row pass
 constexpr int BD_ROW_CHUNK = 256 * BD_ROW_RUN;
 constexpr int BD_CNT_RUN = 16;                   // consecutive pixels per lane per step of the count
@@ -29,7 +27,6 @@ constexpr int BD_WG_PER_CU = 4;
 constexpr int BD_ROW_MAX_BLOCKS = 1 << 20;          // workgroups of the row pass: rows beyond it are looped over
 constexpr int BD_COL_BATCH = 16;                 // rows a lane of the column pass loads ahead
 constexpr int BD_COL_WAVES_PER_CU = 16;          // the column pass splits the rows until about this many waves per CU march
-constexpr size_t BD_PLANE_ALIGN = 256;
 
 template <typename T>
 __global__ __launch_bounds__(256) void bd_row_kernel(const T* __restrict__ labels, int H, int W, int d, int rzl, uint8_t* __restrict__ rowb) {
@@ -226,28 +223,13 @@ static int bd_band_image(const T* labels, int H, int W, int d, int rzl, uint8_t*
   return SG_OK;
 }
 
-static inline size_t bd_plane_bytes(int64_t n) { return align_up((size_t)n, BD_PLANE_ALIGN); }
-
-// the checks both entries share; total = the pixels of the call
+// the checks both entries share: the images (fewer than 2^31 pixels each) and a band width in [1, BD_MAX_D] for every one
 static int bd_check_images(const char* who, const int32_t* image_hw, const int64_t* offset, const int32_t* d, int N, int64_t* total_out) {
-  SG_REQUIRE(N >= 1, "%s: N=%d images", who, N);
-  int64_t total = 0;
-  for (int n = 0; n < N; ++n) {
-    const int64_t h = image_hw[2 * n], w = image_hw[2 * n + 1];
-    SG_REQUIRE(h > 0 && w > 0, "%s: image %d has non-positive size %lld x %lld", who, n, (long long)h, (long long)w);
-    SG_REQUIRE(h * w <= BD_MAX_PIXELS, "%s: image %d of %lld x %lld has 2^31 or more pixels", who, n, (long long)h, (long long)w);
+  const auto width = [&](int n) -> int {
     SG_REQUIRE(d[n] >= 1 && d[n] <= BD_MAX_D, "%s: d[%d]=%d outside [1, %d]", who, n, d[n], BD_MAX_D);
-    total += h * w;
-  }
-  int64_t end = 0;                                                       // the images lie in ascending order and do not overlap
-  for (int n = 0; n < N; ++n) {
-    const int64_t px = (int64_t)image_hw[2 * n] * image_hw[2 * n + 1];
-    SG_REQUIRE(offset[n] >= end && offset[n] + px <= total, "%s: offset[%d]=%lld puts image %d over the image before it or outside the %lld pixels of the call",
-               who, n, (long long)offset[n], n, (long long)total);
-    end = offset[n] + px;
-  }
-  *total_out = total;
-  return SG_OK;
+    return SG_OK;
+  };
+  return lm_check_images(who, image_hw, offset, N, false, width, total_out);
 }
 
 }  // namespace sg
@@ -256,7 +238,7 @@ using namespace sg;
 
 extern "C" size_t sg_boundary_workspace_bytes(int64_t n_pixels_total) {
   if (n_pixels_total < 0) return 0;
-  return 4 * bd_plane_bytes(n_pixels_total);
+  return 4 * lm_plane_bytes(n_pixels_total);
 }
 
 extern "C" int sg_boundary_band(const void* labels, int fmt, const int32_t* image_hw, const int64_t* offset, const int32_t* d, int N,
@@ -265,8 +247,8 @@ extern "C" int sg_boundary_band(const void* labels, int fmt, const int32_t* imag
   SG_REQUIRE(fmt == SG_GT_U8 || fmt == SG_GT_I64, "sg_boundary_band: unknown label format %d", fmt);
   int64_t total = 0;
   SG_TRY(bd_check_images("sg_boundary_band", image_hw, offset, d, N, &total));
-  SG_REQUIRE(fmt == SG_GT_U8 || (((uintptr_t)labels) & 7) == 0, "sg_boundary_band: int64 labels must be 8-byte aligned");
-  const size_t need = bd_plane_bytes(total);
+  SG_REQUIRE(fmt == SG_GT_U8 || lm_aligned8(labels), "sg_boundary_band: int64 labels must be 8-byte aligned");
+  const size_t need = lm_plane_bytes(total);
   SG_REQUIRE(workspace_bytes >= need, "sg_boundary_band: workspace too small: %zu bytes given, %zu needed for %lld pixels", workspace_bytes,
              need, (long long)total);
   uint8_t* rowb = reinterpret_cast<uint8_t*>(workspace);
@@ -286,16 +268,16 @@ extern "C" int sg_boundary_accumulate(const int64_t* labels, const void* gt, int
   SG_REQUIRE(labels && gt && image_hw && offset && d && areas && workspace, "sg_boundary_accumulate: null pointer");
   SG_REQUIRE(gt_format == SG_GT_U8 || gt_format == SG_GT_I64, "sg_boundary_accumulate: unknown ground-truth format %d", gt_format);
   SG_REQUIRE(K >= 1, "sg_boundary_accumulate: K=%d, need at least one class", K);
-  SG_REQUIRE(K <= BD_MAX_K, "sg_boundary_accumulate: K=%d exceeds %d (the cap of sg_confusion_accumulate)", K, BD_MAX_K);
+  SG_REQUIRE(K <= LM_MAX_K, "sg_boundary_accumulate: K=%d exceeds %d (the cap of sg_confusion_accumulate)", K, LM_MAX_K);
   int64_t total = 0;
   SG_TRY(bd_check_images("sg_boundary_accumulate", image_hw, offset, d, N, &total));
-  SG_REQUIRE((((uintptr_t)labels) & 7) == 0 && (gt_format == SG_GT_U8 || (((uintptr_t)gt) & 7) == 0) && (((uintptr_t)areas) & 7) == 0,
+  SG_REQUIRE(lm_aligned8(labels) && (gt_format == SG_GT_U8 || lm_aligned8(gt)) && lm_aligned8(areas),
              "sg_boundary_accumulate: int64 buffers must be 8-byte aligned");
   const size_t need = sg_boundary_workspace_bytes(total);
   SG_REQUIRE(workspace_bytes >= need, "sg_boundary_accumulate: workspace too small: %zu bytes given, %zu needed for %lld pixels",
              workspace_bytes, need, (long long)total);
   // workspace: row bytes of the prediction, row bytes of the truth, band of the prediction, band of the truth
-  const size_t plane = bd_plane_bytes(total);
+  const size_t plane = lm_plane_bytes(total);
   uint8_t* rowb_p = reinterpret_cast<uint8_t*>(workspace);
   uint8_t* rowb_g = rowb_p + plane;
   uint8_t* band_p = rowb_g + plane;
@@ -316,7 +298,7 @@ extern "C" int sg_boundary_accumulate(const int64_t* labels, const void* gt, int
     const int64_t nchunks = px / BD_CNT_RUN;
     int64_t blocks = cdiv(nchunks, 256);
     blocks = blocks < 1 ? 1 : (blocks > cap ? cap : blocks);             // an image has < 2^31 pixels: no 32-bit count wraps
-    const void* gt_n = gt64 ? (const void*)(reinterpret_cast<const int64_t*>(gt) + o) : (const void*)(reinterpret_cast<const uint8_t*>(gt) + o);
+    const void* gt_n = lm_gt_at(gt, gt_format, o);
     auto kern = gt64 ? bd_count_kernel<true> : bd_count_kernel<false>;
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, st, labels + o, gt_n, (const uint8_t*)(band_p + o),
                        (const uint8_t*)(band_g + o), px, nchunks, K, ignore_index, rzl, reinterpret_cast<unsigned long long*>(areas));

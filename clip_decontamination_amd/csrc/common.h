@@ -374,4 +374,44 @@ __device__ __forceinline__ void lm_add_stream(const int (&b)[RUN], uint32_t* bin
   }
 }
 
+// ---- label maps, host side: what the entries that take N images back to back in flat buffers check and compute alike (boundary.hip,
+// tolerant.hip, objmatch.hip) ------------------------------------------------------------------------------------------------------------
+constexpr int LM_MAX_K = 127;                                        // CF_MAX_K of metric.hip: one metric object holds its table and the entry's
+constexpr int64_t LM_MAX_PIXELS = ((int64_t)1 << 31) - 1;            // pixel offsets and region roots are 32-bit
+
+static inline size_t lm_plane_bytes(int64_t n) { return align_up((size_t)n, 256); }      // one byte per pixel of the call, planes 256-byte aligned
+static inline bool lm_aligned8(const void* p) { return (((uintptr_t)p) & 7) == 0; }
+// pixel o of a ground-truth buffer of either format
+static inline const void* lm_gt_at(const void* gt, int gt_format, int64_t o) {
+  return gt_format == SG_GT_I64 ? (const void*)(reinterpret_cast<const int64_t*>(gt) + o) : (const void*)(reinterpret_cast<const uint8_t*>(gt) + o);
+}
+
+// The image checks of an entry `who`: at least one image, every size positive, fewer than 2^31 pixels per image or (cap_per_call) in
+// the call, then own(n) -- the entry's check of its own value of image n, an int(int) that returns SG_OK or fails -- and, after all
+// images, offsets that put them in ascending order without overlap inside the call's pixels.  total = the pixels of the call.
+template <typename Own>
+static int lm_check_images(const char* who, const int32_t* image_hw, const int64_t* offset, int N, bool cap_per_call, Own own, int64_t* total_out) {
+  SG_REQUIRE(N >= 1, "%s: N=%d images", who, N);
+  int64_t total = 0;
+  for (int n = 0; n < N; ++n) {
+    const int64_t h = image_hw[2 * n], w = image_hw[2 * n + 1];
+    SG_REQUIRE(h > 0 && w > 0, "%s: image %d has non-positive size %lld x %lld", who, n, (long long)h, (long long)w);
+    total += h * w;
+    if (cap_per_call)
+      SG_REQUIRE(total <= LM_MAX_PIXELS, "%s: the images up to %d hold 2^31 or more pixels", who, n);
+    else
+      SG_REQUIRE(h * w <= LM_MAX_PIXELS, "%s: image %d of %lld x %lld has 2^31 or more pixels", who, n, (long long)h, (long long)w);
+    SG_TRY(own(n));
+  }
+  int64_t end = 0;                                                       // the images lie in ascending order and do not overlap
+  for (int n = 0; n < N; ++n) {
+    const int64_t px = (int64_t)image_hw[2 * n] * image_hw[2 * n + 1];
+    SG_REQUIRE(offset[n] >= end && offset[n] + px <= total, "%s: offset[%d]=%lld puts image %d over the image before it or outside the %lld pixels of the call",
+               who, n, (long long)offset[n], n, (long long)total);
+    end = offset[n] + px;
+  }
+  *total_out = total;
+  return SG_OK;
+}
+
 }  // namespace sg

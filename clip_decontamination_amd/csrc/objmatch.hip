@@ -28,11 +28,10 @@
 
 namespace sg {
 
-constexpr int OM_MAX_K = 127;                                         // CF_MAX_K of metric.hip
+constexpr int OM_MAX_K = LM_MAX_K;
 constexpr int OM_RUN = SV_RUN;                                        // consecutive pixels per lane of object_vote / object_verify
 constexpr int OM_MAX_DEN = 1 << 20;
 constexpr int OM_SQ_SHIFT = 24;                                       // row 3 counts IoU in steps of 2^-24, as SG_REGION_SCORE_Q
-constexpr size_t OM_PLANE_ALIGN = 256;
 constexpr int OM_CHUNKS = 16;                                         // chunks of SV_PIX pixels a workgroup of object_vote sweeps
 constexpr int OM_SLOT_BITS = 6, OM_SLOTS = 1 << OM_SLOT_BITS;         // the workgroup's list and its cache; one lane of a wave per slot
 static_assert(OM_RUN <= 15, "a run length is summed from four ballots");
@@ -313,15 +312,13 @@ __global__ __launch_bounds__(256) void object_map_kernel(const int64_t* __restri
   }
 }
 
-static inline size_t om_plane_bytes(int64_t n) { return align_up((size_t)n, OM_PLANE_ALIGN); }
-
 }  // namespace sg
 
 using namespace sg;
 
 extern "C" size_t sg_object_workspace_bytes(int64_t n_pixels_total) {
   if (n_pixels_total < 0) return 0;
-  return (size_t)n_pixels_total * 36 + 2 * om_plane_bytes(n_pixels_total);
+  return (size_t)n_pixels_total * 36 + 2 * lm_plane_bytes(n_pixels_total);
 }
 
 extern "C" int sg_object_match(const int64_t* labels, const void* gt, int gt_format, const int32_t* image_hw, const int64_t* offset, int N, int K,
@@ -335,23 +332,9 @@ extern "C" int sg_object_match(const int64_t* labels, const void* gt, int gt_for
   SG_REQUIRE(min_area >= 1, "%s: min_area=%lld must be >= 1 (a region is an object when its area is at least it)", who, (long long)min_area);
   SG_REQUIRE(iou_num >= 1 && iou_num < iou_den && iou_den <= OM_MAX_DEN, "%s: the threshold %d / %d needs 1 <= num < den <= 2^20", who, iou_num, iou_den);
   SG_REQUIRE(2 * (int64_t)iou_num >= (int64_t)iou_den, "%s: the threshold %d / %d is below 1/2: the match would not be unique", who, iou_num, iou_den);
-  SG_REQUIRE(N >= 1, "%s: N=%d images", who, N);
-  int64_t total = 0;
-  for (int n = 0; n < N; ++n) {
-    const int64_t h = image_hw[2 * n], w = image_hw[2 * n + 1];
-    SG_REQUIRE(h > 0 && w > 0, "%s: image %d has non-positive size %lld x %lld", who, n, (long long)h, (long long)w);
-    total += h * w;
-    SG_REQUIRE(total <= SV_MAX_PIXELS, "%s: the images up to %d hold 2^31 or more pixels", who, n);
-  }
-  int64_t end = 0;                                                     // the images lie in ascending order and do not overlap
-  for (int n = 0; n < N; ++n) {
-    const int64_t px = (int64_t)image_hw[2 * n] * image_hw[2 * n + 1];
-    SG_REQUIRE(offset[n] >= end && offset[n] + px <= total, "%s: offset[%d]=%lld puts image %d over the image before it or outside the %lld pixels of the call",
-               who, n, (long long)offset[n], n, (long long)total);
-    end = offset[n] + px;
-  }
-  SG_REQUIRE((((uintptr_t)labels) & 7) == 0 && (gt_format == SG_GT_U8 || (((uintptr_t)gt) & 7) == 0) && (((uintptr_t)counts) & 7) == 0 &&
-                 (((uintptr_t)workspace) & 7) == 0,
+  int64_t total = 0;                                                   // per call: region roots index the call's pixels in 32 bits
+  SG_TRY(lm_check_images(who, image_hw, offset, N, true, [](int) -> int { return SG_OK; }, &total));
+  SG_REQUIRE(lm_aligned8(labels) && (gt_format == SG_GT_U8 || lm_aligned8(gt)) && lm_aligned8(counts) && lm_aligned8(workspace),
              "%s: int64 buffers and the workspace must be 8-byte aligned", who);
   const size_t need = sg_object_workspace_bytes(total);
   SG_REQUIRE(workspace_bytes >= need, "%s: workspace too small: %zu bytes given, %zu needed for %lld pixels", who, workspace_bytes, need,
@@ -367,7 +350,7 @@ extern "C" int sg_object_match(const int64_t* labels, const void* gt, int gt_for
   int32_t* area_g = parent_g + total;
   uint32_t* inter = reinterpret_cast<uint32_t*>(area_g + total);
   uint8_t* mark_p = reinterpret_cast<uint8_t*>(wsp + (size_t)total * 36);
-  uint8_t* mark_g = mark_p + om_plane_bytes(total);
+  uint8_t* mark_g = mark_p + lm_plane_bytes(total);
   const int conn8 = connectivity == 8;
   const ObjectRule ru = {(long long)min_area, (long long)skip_label, use_skip != 0, K, ignore_index};
   const int rzl = reduce_zero_label ? 1 : 0;
@@ -387,19 +370,9 @@ extern "C" int sg_object_match(const int64_t* labels, const void* gt, int gt_for
     SieveImages im;
     int64_t tiles = 0, blks = 0;
     n0 += sieve_group(image_hw, offset, N, n0, &wbase, &im, &tiles, &blks);
-    const dim3 gt_((unsigned)tiles), gp((unsigned)blks);
-    hipLaunchKernelGGL(sieve_local_kernel, gt_, dim3(256), 0, st, labels, im, conn8, parent_p, area_p, summary);      // zeroes the summaries
-    SG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sieve_merge_kernel, gt_, dim3(128), 0, st, labels, im, conn8, parent_p);
-    SG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sieve_flatten_kernel, gp, dim3(256), 0, st, im, parent_p, area_p);
-    SG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sieve_local_kernel, gt_, dim3(256), 0, st, (const int64_t*)gprime, im, conn8, parent_g, area_g, (unsigned long long*)nullptr);
-    SG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sieve_merge_kernel, gt_, dim3(128), 0, st, (const int64_t*)gprime, im, conn8, parent_g);
-    SG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sieve_flatten_kernel, gp, dim3(256), 0, st, im, parent_g, area_g);
-    SG_LAUNCH_CHECK();
+    const dim3 gp((unsigned)blks);
+    SG_TRY(sieve_label(labels, im, tiles, blks, conn8, parent_p, area_p, summary, st));      // zeroes the summaries
+    SG_TRY(sieve_label(gprime, im, tiles, blks, conn8, parent_g, area_g, nullptr, st));
     ObjectBlocks ob;                                                   // a sixteenth of the per-pixel workgroups, rounded up per image
     int64_t vblks = 0;
     for (int k = 0; k <= SV_GROUP; ++k) {

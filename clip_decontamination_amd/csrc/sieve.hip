@@ -411,14 +411,9 @@ extern "C" int sg_sieve(const int64_t* labels, int64_t* labels_out, const int32_
     SieveImages im;
     int64_t tiles = 0, blks = 0;
     n0 += sieve_group(image_hw, out_offset, N, n0, &wbase, &im, &tiles, &blks);
-    const dim3 gt((unsigned)tiles), gp((unsigned)blks);
+    const dim3 gp((unsigned)blks);
     if (min_region > 1) {                                              // min_region = 1: no region is small, the apply kernel copies
-      hipLaunchKernelGGL(sieve_local_kernel, gt, dim3(256), 0, s, labels, im, conn8, parent, area, best);
-      SG_LAUNCH_CHECK();
-      hipLaunchKernelGGL(sieve_merge_kernel, gt, dim3(128), 0, s, labels, im, conn8, parent);
-      SG_LAUNCH_CHECK();
-      hipLaunchKernelGGL(sieve_flatten_kernel, gp, dim3(256), 0, s, im, parent, area);
-      SG_LAUNCH_CHECK();
+      SG_TRY(sieve_label(labels, im, tiles, blks, conn8, parent, area, best, s));
       if (best) {
         hipLaunchKernelGGL(sieve_choose_kernel, gp, dim3(256), 0, s, im, conn8, min_region, parent, area, best);
         SG_LAUNCH_CHECK();
@@ -474,13 +469,8 @@ extern "C" int sg_regions(const int64_t* labels, const float* conf, const int32_
     int64_t tiles = 0, blks = 0;
     const int image0 = n0;
     n0 += sieve_group(image_hw, out_offset, N, n0, &wbase, &im, &tiles, &blks);
-    const dim3 gt((unsigned)tiles), gp((unsigned)blks);
-    hipLaunchKernelGGL(sieve_local_kernel, gt, dim3(256), 0, s, labels, im, conn8, parent, area, (unsigned long long*)nullptr);
-    SG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sieve_merge_kernel, gt, dim3(128), 0, s, labels, im, conn8, parent);
-    SG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sieve_flatten_kernel, gp, dim3(256), 0, s, im, parent, area);
-    SG_LAUNCH_CHECK();
+    const dim3 gp((unsigned)blks);
+    SG_TRY(sieve_label(labels, im, tiles, blks, conn8, parent, area, nullptr, s));
     hipLaunchKernelGGL(regions_count_kernel, gp, dim3(256), 0, s, labels, im, ru, parent, area, blk);
     SG_LAUNCH_CHECK();
     // the rows of the sequences before this one wait in counts[N]: the host never sees them

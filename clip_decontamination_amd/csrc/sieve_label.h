@@ -279,5 +279,19 @@ static int sieve_group(const int32_t* image_hw, const int64_t* out_offset, int N
   return k;
 }
 
+// The three labelling launches over the images of one launch sequence (im, tiles and blks as sieve_group left them), in stream order.
+// sieve_local also zeroes best[] of every pixel where best is not null.
+static int sieve_label(const int64_t* labels, const SieveImages& im, int64_t tiles, int64_t blks, int conn8, int32_t* parent, int32_t* area,
+                       unsigned long long* best, hipStream_t s) {
+  const dim3 gt((unsigned)tiles), gp((unsigned)blks);
+  hipLaunchKernelGGL(sieve_local_kernel, gt, dim3(256), 0, s, labels, im, conn8, parent, area, best);
+  SG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(sieve_merge_kernel, gt, dim3(128), 0, s, labels, im, conn8, parent);
+  SG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(sieve_flatten_kernel, gp, dim3(256), 0, s, im, parent, area);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
 }  // namespace
 }  // namespace sg

@@ -22,9 +22,8 @@
 namespace sg {
 
 constexpr int TL_MAX_SQ = 254 * 254;
-constexpr int TL_MAX_K = 127;                    // CF_MAX_K of metric.hip
+constexpr int TL_MAX_K = LM_MAX_K;
 constexpr int TL_GROUP = 8;                      // classes per pass: planes of the workspace
-constexpr int64_t TL_MAX_PIXELS = ((int64_t)1 << 31) - 1;
 constexpr int TL_ROW_RUN = 8;                    // consecutive pixels per lane per chunk of the row pass
 constexpr int TL_ROW_CHUNK = 256 * TL_ROW_RUN;
 constexpr int TL_ROW_MAX_BLOCKS = 1 << 16;       // workgroups of the row pass: rows beyond it are looped over
@@ -33,7 +32,6 @@ constexpr int TL_WALK = 8;                       // rows above and below a lane 
 constexpr int TL_WG_PER_CU = 8;
 constexpr int TL_NONE_LEFT = -256;               // "no marked column yet": any column minus it is capped
 constexpr int TL_NONE_RIGHT = 0x7fffffff;
-constexpr size_t TL_PLANE_ALIGN = 256;
 
 __device__ __forceinline__ int tl_isqrt(int v) {                          // floor(sqrt(v)), 0 <= v <= 254^2: the float is a first guess only
   int w = (int)sqrtf((float)v);
@@ -278,8 +276,6 @@ __global__ __launch_bounds__(256) void tl_count_kernel(const int64_t* __restrict
   }
 }
 
-static inline size_t tl_plane_bytes(int64_t n) { return align_up((size_t)n, TL_PLANE_ALIGN); }
-
 template <typename T>
 static int tl_row_pass(const T* map, int H, int W, int rzl, int mode, int c0, int G, uint8_t* hd, size_t plane, hipStream_t st) {
   hipLaunchKernelGGL(tl_row_kernel<T>, dim3((unsigned)(H < TL_ROW_MAX_BLOCKS ? H : TL_ROW_MAX_BLOCKS)), dim3(256), 0, st, map, H, W, rzl, mode, c0, G,
@@ -294,7 +290,7 @@ using namespace sg;
 
 extern "C" size_t sg_tolerant_workspace_bytes(int64_t n_pixels_total, int K) {
   if (n_pixels_total < 0 || K < 1 || K > TL_MAX_K) return 0;
-  return (size_t)(K < TL_GROUP ? K : TL_GROUP) * tl_plane_bytes(n_pixels_total);
+  return (size_t)(K < TL_GROUP ? K : TL_GROUP) * lm_plane_bytes(n_pixels_total);
 }
 
 extern "C" int sg_tolerant_accumulate(const int64_t* labels, const void* gt, int gt_format, const int32_t* image_hw, const int64_t* offset,
@@ -305,29 +301,18 @@ extern "C" int sg_tolerant_accumulate(const int64_t* labels, const void* gt, int
   SG_REQUIRE(gt_format == SG_GT_U8 || gt_format == SG_GT_I64, "%s: unknown ground-truth format %d", who, gt_format);
   SG_REQUIRE(mode == SG_TOL_REGION || mode == SG_TOL_CONTOUR, "%s: unknown mode %d", who, mode);
   SG_REQUIRE(K >= 1 && K <= TL_MAX_K, "%s: K=%d outside [1, %d] (the cap of sg_confusion_accumulate)", who, K, TL_MAX_K);
-  SG_REQUIRE(N >= 1, "%s: N=%d images", who, N);
-  int64_t total = 0;
-  for (int n = 0; n < N; ++n) {
-    const int64_t h = image_hw[2 * n], w = image_hw[2 * n + 1];
-    SG_REQUIRE(h > 0 && w > 0, "%s: image %d has non-positive size %lld x %lld", who, n, (long long)h, (long long)w);
-    SG_REQUIRE(h * w <= TL_MAX_PIXELS, "%s: image %d of %lld x %lld has 2^31 or more pixels", who, n, (long long)h, (long long)w);
+  const auto tolerance = [&](int n) -> int {
     SG_REQUIRE(tol_sq[n] >= 0 && tol_sq[n] <= TL_MAX_SQ, "%s: tol_sq[%d]=%d outside [0, %d]", who, n, tol_sq[n], TL_MAX_SQ);
-    total += h * w;
-  }
-  int64_t end = 0;                                                         // the images lie in ascending order and do not overlap
-  for (int n = 0; n < N; ++n) {
-    const int64_t px = (int64_t)image_hw[2 * n] * image_hw[2 * n + 1];
-    SG_REQUIRE(offset[n] >= end && offset[n] + px <= total, "%s: offset[%d]=%lld puts image %d over the image before it or outside the %lld pixels of the call",
-               who, n, (long long)offset[n], n, (long long)total);
-    end = offset[n] + px;
-  }
-  SG_REQUIRE((((uintptr_t)labels) & 7) == 0 && (gt_format == SG_GT_U8 || (((uintptr_t)gt) & 7) == 0) && (((uintptr_t)counts) & 7) == 0,
-             "%s: int64 buffers must be 8-byte aligned", who);
+    return SG_OK;
+  };
+  int64_t total = 0;
+  SG_TRY(lm_check_images(who, image_hw, offset, N, false, tolerance, &total));
+  SG_REQUIRE(lm_aligned8(labels) && (gt_format == SG_GT_U8 || lm_aligned8(gt)) && lm_aligned8(counts), "%s: int64 buffers must be 8-byte aligned", who);
   const size_t need = sg_tolerant_workspace_bytes(total, K);
   SG_REQUIRE(workspace_bytes >= need, "%s: workspace too small: %zu bytes given, %zu needed for %lld pixels and K=%d", who, workspace_bytes, need,
              (long long)total, K);
 
-  const size_t plane = tl_plane_bytes(total);
+  const size_t plane = lm_plane_bytes(total);
   uint8_t* hd = reinterpret_cast<uint8_t*>(workspace);
   const bool gt64 = gt_format == SG_GT_I64;
   const int rzl = reduce_zero_label ? 1 : 0;
@@ -339,7 +324,7 @@ extern "C" int sg_tolerant_accumulate(const int64_t* labels, const void* gt, int
     const int H = image_hw[2 * n], W = image_hw[2 * n + 1];
     const int64_t o = offset[n];
     const int64_t* lab_n = labels + o;
-    const void* gt_n = gt64 ? (const void*)(reinterpret_cast<const int64_t*>(gt) + o) : (const void*)(reinterpret_cast<const uint8_t*>(gt) + o);
+    const void* gt_n = lm_gt_at(gt, gt_format, o);
     int r = 0;
     while ((r + 1) * (r + 1) <= tol_sq[n]) ++r;
     const int64_t col_groups = cdiv(W, 256), ntiles = col_groups * cdiv(H, TL_RUN);

@@ -67,19 +67,52 @@ def metrics_from_confusion(table, metrics: Sequence[str] = ("mIoU",), nan_to_num
                 precision, recall = inter / pred, inter / label
                 out["Fscore"] = (1 + beta ** 2) * (precision * recall) / ((beta ** 2 * precision) + recall)
                 out["Precision"], out["Recall"] = precision, recall
-    out = {k: np.asarray(v, dtype=np.float64) for k, v in out.items()}
+    out = _with_summary(out, [k if k == "aAcc" else "m" + k for k in out], nan_to_num)
+    out["aAcc"] = float(out["aAcc"])
+    return out
+
+
+def _with_summary(vectors: dict, summary_keys, nan_to_num) -> dict:
+    """The last step of every ``metrics_from_*``: the ratios as float64 (``nan_to_num`` replaces NaN first, as in mmseg) plus
+    ``summary``, one ``nanmean * 100`` rounded to 2 decimals per ratio, under ``summary_keys`` in the ratios' order."""
+    out = {k: np.asarray(v, dtype=np.float64) for k, v in vectors.items()}
     if nan_to_num is not None:
         out = {k: np.nan_to_num(v, nan=nan_to_num) for k, v in out.items()}
     with warnings.catch_warnings():                      # nanmean of an all-NaN vector (no class seen) is NaN by design, not a warning
         warnings.simplefilter("ignore", category=RuntimeWarning)
-        summary = {(k if k == "aAcc" else "m" + k): float(np.round(np.nanmean(v) * 100, 2)) for k, v in out.items()}
-    out["aAcc"] = float(out["aAcc"])
+        summary = {s: float(np.round(np.nanmean(v) * 100, 2)) for s, v in zip(summary_keys, out.values())}
     out["summary"] = summary
     return out
 
 
+def _count_rows(counts, rows: int, what: str):
+    """The checks of the ``metrics_from_*`` of a second table: integer ``[rows, K]`` counts, K >= 1 -> its rows as float64 [K]."""
+    a = counts.detach().cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)
+    if a.ndim != 2 or a.shape[0] != rows or a.shape[1] < 1:
+        raise ValueError(f"{what} must be [{rows},K] with K >= 1, got shape {a.shape}")
+    if not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"{what} must hold integers, got {a.dtype}")
+    return (a[i].astype(np.float64) for i in range(rows))
+
+
 def _field(obj, name):
     return obj[name] if isinstance(obj, dict) else getattr(obj, name)
+
+
+def _lazy_table(table: Optional[torch.Tensor], shape, device=None) -> torch.Tensor:
+    """A count table that follows the data: zeros of ``shape`` (int64) at its first use, moved when ``device`` is another than its own.
+    ``device`` None: where it is; a table read before the first add is on the CPU."""
+    if table is None:
+        return torch.zeros(*shape, dtype=torch.int64, device="cpu" if device is None else device)
+    return table if device is None or table.device == torch.device(device) else table.to(device)
+
+
+def _gt_on(gt, device) -> torch.Tensor:
+    """Ground truth as the entries take it: uint8 or int64 (anything else is widened), on the labels' device."""
+    gt = torch.as_tensor(gt)
+    if gt.dtype not in (torch.uint8, torch.int64):
+        gt = gt.to(torch.int64)
+    return gt.to(device)
 
 
 class IoUMetric:
@@ -117,18 +150,15 @@ class IoUMetric:
             raise RuntimeError("IoUMetric: num_classes is not set (pass num_classes=, or dataset_meta with 'classes')")
         return self.num_classes
 
-    def _ensure(self, device) -> torch.Tensor:
+    def _ensure(self, device=None) -> torch.Tensor:
         K = self._classes()
-        if self._table is None:
-            self._table = torch.zeros(K + 1, K + 1, dtype=torch.int64, device=device)
-        elif self._table.device != torch.device(device):          # the table follows the data (a table read before the first add is on the CPU)
-            self._table = self._table.to(device)
+        self._table = _lazy_table(self._table, (K + 1, K + 1), device)
         return self._table
 
     @property
     def confusion(self) -> torch.Tensor:
         """The (K+1) x (K+1) int64 table, row = prediction, column = ground truth, index K = outside [0,K)."""
-        return self._ensure("cpu" if self._table is None else self._table.device)
+        return self._ensure()
 
     def reset(self) -> None:
         self._table = None
@@ -149,11 +179,8 @@ class IoUMetric:
         if not (torch.is_tensor(labels) and labels.is_cuda):
             raise RuntimeError("IoUMetric.add counts on the GPU (sg_confusion_accumulate): labels must be a device tensor; "
                                "there is no CPU fallback")
-        gt = torch.as_tensor(gt)
-        if gt.dtype not in (torch.uint8, torch.int64):
-            gt = gt.to(torch.int64)
-        gt = gt.to(labels.device)
-        ops.confusion_accumulate(labels, gt, self._ensure(labels.device), self._classes(), self.ignore_index, self.reduce_zero_label)
+        ops.confusion_accumulate(labels, _gt_on(gt, labels.device), self._ensure(labels.device), self._classes(), self.ignore_index,
+                                 self.reduce_zero_label)
 
     def process(self, data_batch, data_samples) -> None:
         """mmseg's ``process``: every sample (object or dict) carries ``pred_sem_seg`` and ``gt_sem_seg``, each with ``.data`` /
@@ -174,38 +201,109 @@ class IoUMetric:
         return metrics_from_confusion(self.confusion, self.metrics, self.nan_to_num, self.beta)
 
 
-def _one_map(who: str, labels, gt):
-    """The checks of ``add`` on the metrics that need an image's shape: one non-empty [H,W] / [1,H,W] map each, of one size
-    -> (gt as a tensor, (H, W))."""
-    gt = torch.as_tensor(gt)
-    for name, t in (("labels", labels), ("gt", gt)):
-        if not torch.is_tensor(t) or t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[0] != 1) or t.numel() == 0:
-            raise ValueError(f"{who}.add: {name} must be a non-empty [H,W] or [1,H,W] map (a flat buffer of images goes "
-                             "through add_flat with their sizes)")
-    if tuple(labels.shape[-2:]) != tuple(gt.shape[-2:]):
-        raise ValueError(f"{who}.add: labels {tuple(labels.shape)} and gt {tuple(gt.shape)} differ in size")
-    return gt, tuple(labels.shape[-2:])
+class _ImageShapeMetric(IoUMetric):
+    """What the metrics that need an image's shape share: the confusion table as before and a second int64 table ``[_ROWS, K]``,
+    counted by the subclass's entry ``_ENTRY``.  It is created at its first use and follows the data's device like the first; a
+    subclass publishes it under its own property name.
 
+    ``add(labels, gt)`` takes one 2-D map ([H,W] or [1,H,W]) and counts both tables; ``add_flat(labels, gt, image_hw)`` the flat buffers
+    of a flush group with the sizes of its images; ``reduce(group)`` sums both tables; ``add_confusion`` is IoUMetric's and leaves the
+    second table alone; ``compute()`` returns IoUMetric's dict plus the subclass's scores, merged into ``summary``.
 
-def _flat_sizes(who: str, labels, image_hw):
-    """The checks of ``add_flat`` on the sizes of a flush group, before anything is counted -> image_hw as int pairs."""
-    image_hw = [(int(h), int(w)) for h, w in image_hw]
-    if not image_hw or any(h < 1 or w < 1 for h, w in image_hw):
-        raise ValueError(f"{who}.add_flat: needs at least one image of positive size, got {image_hw}")
-    if not torch.is_tensor(labels) or labels.numel() != sum(h * w for h, w in image_hw):
-        raise ValueError(f"{who}.add_flat: images of sizes {image_hw} against "
-                         f"{labels.numel() if torch.is_tensor(labels) else type(labels).__name__} labels")
-    return image_hw
+    A subclass checks its own options before this constructor runs and supplies ``_count`` (its one ``ops`` call), ``_scores`` (its
+    ``metrics_from_*``) and, where each image has a value of its own (a band width, a tolerance), ``_per_image``."""
+    _ROWS, _ENTRY = 0, ""
 
+    def __init__(self, *args, **kwargs):
+        from . import ops
+        super().__init__(*args, **kwargs)
+        if self.num_classes is not None and self.num_classes > ops.CONFUSION_MAX_K:
+            raise ValueError(f"{type(self).__name__}: num_classes={self.num_classes} exceeds {ops.CONFUSION_MAX_K}")
+        self._second: Optional[torch.Tensor] = None
 
-def _flat_on_device(who: str, entry: str, labels, gt):
-    """Flat labels and truth of one flush group on the labels' device; no CPU fallback."""
-    if not labels.is_cuda:
-        raise RuntimeError(f"{who} counts on the GPU ({entry}): labels must be a device tensor; there is no CPU fallback")
-    gt = torch.as_tensor(gt)
-    if gt.dtype not in (torch.uint8, torch.int64):
-        gt = gt.to(torch.int64)
-    return labels.reshape(-1), gt.to(labels.device).reshape(-1)
+    def _ensure_second(self, device=None) -> torch.Tensor:
+        self._second = _lazy_table(self._second, (self._ROWS, self._classes()), device)
+        return self._second
+
+    def reset(self) -> None:
+        super().reset()
+        self._second = None
+
+    def _one_map(self, labels, gt):
+        """The checks of ``add``: one non-empty [H,W] / [1,H,W] map each, of one size -> (gt as a tensor, (H, W))."""
+        who = type(self).__name__
+        gt = torch.as_tensor(gt)
+        for name, t in (("labels", labels), ("gt", gt)):
+            if not torch.is_tensor(t) or t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[0] != 1) or t.numel() == 0:
+                raise ValueError(f"{who}.add: {name} must be a non-empty [H,W] or [1,H,W] map (a flat buffer of images goes "
+                                 "through add_flat with their sizes)")
+        if tuple(labels.shape[-2:]) != tuple(gt.shape[-2:]):
+            raise ValueError(f"{who}.add: labels {tuple(labels.shape)} and gt {tuple(gt.shape)} differ in size")
+        return gt, tuple(labels.shape[-2:])
+
+    def _flat_sizes(self, labels, image_hw):
+        """The checks of ``add_flat`` on the sizes of a flush group, before anything is counted -> image_hw as int pairs."""
+        who = type(self).__name__
+        image_hw = [(int(h), int(w)) for h, w in image_hw]
+        if not image_hw or any(h < 1 or w < 1 for h, w in image_hw):
+            raise ValueError(f"{who}.add_flat: needs at least one image of positive size, got {image_hw}")
+        if not torch.is_tensor(labels) or labels.numel() != sum(h * w for h, w in image_hw):
+            raise ValueError(f"{who}.add_flat: images of sizes {image_hw} against "
+                             f"{labels.numel() if torch.is_tensor(labels) else type(labels).__name__} labels")
+        return image_hw
+
+    def _flat_on_device(self, labels, gt):
+        """Flat labels and truth of one flush group on the labels' device; no CPU fallback."""
+        if not labels.is_cuda:
+            raise RuntimeError(f"{type(self).__name__} counts on the GPU ({self._ENTRY}): labels must be a device tensor; there is no "
+                               "CPU fallback")
+        return labels.reshape(-1), _gt_on(gt, labels.device).reshape(-1)
+
+    def _per_image(self, image_hw):
+        """The subclass's value of every image, worked out (and refused) before anything is counted; handed to ``_count``."""
+        return None
+
+    def _count(self, labels, gt, image_hw, values, table, K, match_map) -> None:
+        """The subclass's one ``ops`` call: adds the counts of the flat device buffers to ``table``.  ``match_map`` is ObjectMetric's."""
+        raise NotImplementedError
+
+    def _scores(self) -> dict:
+        """The subclass's ``metrics_from_*`` of the second table."""
+        raise NotImplementedError
+
+    def add(self, labels: torch.Tensor, gt: torch.Tensor) -> None:
+        """Counts one image in both tables: labels int64 and gt uint8 / int64, [H,W] or [1,H,W] of one size.  The second table needs
+        the image's shape, so a flat buffer goes through ``add_flat``."""
+        gt, hw = self._one_map(labels, gt)
+        self.add_flat(labels.reshape(-1), gt.reshape(-1), [hw])
+
+    def add_flat(self, labels: torch.Tensor, gt: torch.Tensor, image_hw) -> None:
+        """Counts the images that lie back to back in the flat ``labels`` / ``gt`` buffers (a flush group's), sizes ``image_hw``: one
+        sg_confusion_accumulate launch and one call of the subclass's entry on the current stream."""
+        self._add_flat(labels, gt, image_hw)
+
+    def _add_flat(self, labels, gt, image_hw, match_map=None) -> None:
+        from . import ops
+        image_hw = self._flat_sizes(labels, image_hw)
+        values = self._per_image(image_hw)
+        labels, gt = self._flat_on_device(labels, gt)
+        K = self._classes()
+        ops.confusion_accumulate(labels, gt, self._ensure(labels.device), K, self.ignore_index, self.reduce_zero_label)
+        self._count(labels, gt, image_hw, values, self._ensure_second(labels.device), K, match_map)
+
+    def reduce(self, group=None) -> None:
+        """Sums both tables over the ranks of ``group``: two all_reduces."""
+        import torch.distributed as dist
+        super().reduce(group)
+        dist.all_reduce(self._ensure_second(), op=dist.ReduceOp.SUM, group=group)
+
+    def compute(self) -> dict:
+        out = super().compute()
+        own = self._scores()
+        summary = dict(out["summary"], **own.pop("summary"))
+        out.update(own)
+        out["summary"] = summary
+        return out
 
 
 def metrics_from_boundary(areas, nan_to_num: Optional[int] = None) -> dict:
@@ -213,30 +311,20 @@ def metrics_from_boundary(areas, nan_to_num: Optional[int] = None) -> dict:
     intersection of the two bands, prediction band, truth band): ``BIoU`` float64 [K] = areas[0] / (areas[1] + areas[2] - areas[0]),
     NaN where a class has no band pixel in prediction and truth, and ``summary['mBIoU']`` = ``nanmean * 100`` rounded to 2 decimals,
     with such a class left out of the mean (``nan_to_num`` replaces NaN first), as ``metrics_from_confusion`` treats ``IoU``."""
-    a = areas.detach().cpu().numpy() if torch.is_tensor(areas) else np.asarray(areas)
-    if a.ndim != 2 or a.shape[0] != 3 or a.shape[1] < 1:
-        raise ValueError(f"boundary areas must be [3,K] with K >= 1, got shape {a.shape}")
-    if not np.issubdtype(a.dtype, np.integer):
-        raise TypeError(f"boundary areas must hold integers, got {a.dtype}")
-    inter, pred, label = (a[i].astype(np.float64) for i in range(3))
+    inter, pred, label = _count_rows(areas, 3, "boundary areas")
     with np.errstate(divide="ignore", invalid="ignore"):
-        biou = np.asarray(inter / (pred + label - inter), dtype=np.float64)
-    if nan_to_num is not None:
-        biou = np.nan_to_num(biou, nan=nan_to_num)
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", category=RuntimeWarning)
-        mean = float(np.round(np.nanmean(biou) * 100, 2))
-    return {"BIoU": biou, "summary": {"mBIoU": mean}}
+        biou = inter / (pred + label - inter)
+    return _with_summary({"BIoU": biou}, ["mBIoU"], nan_to_num)
 
 
-class BoundaryIoUMetric(IoUMetric):
+class BoundaryIoUMetric(_ImageShapeMetric):
     """``IoUMetric`` plus Boundary IoU: the confusion table as before and ``boundary_areas`` int64 [3,K], the counts restricted to the
     bands of prediction and truth (``sg_boundary_accumulate``).  The band width is ``boundary_ratio`` of each image's diagonal
     (``ops.boundary_width``; 0.02 as in the paper) or the fixed ``boundary_px``, which overrides the ratio.
 
-    ``add(labels, gt)`` takes one 2-D map ([H,W] or [1,H,W]) and counts both tables; ``add_flat(labels, gt, image_hw)`` the flat buffers
-    of a flush group with the sizes of its images; ``reduce(group)`` sums both tables; ``add_confusion`` is IoUMetric's and leaves the
-    boundary counts alone; ``compute()`` returns IoUMetric's dict plus ``BIoU`` and ``summary['mBIoU']``."""
+    ``add`` / ``add_flat`` / ``reduce`` / ``compute`` as the shared base describes them; ``compute()`` adds ``BIoU`` and
+    ``summary['mBIoU']``."""
+    _ROWS, _ENTRY = 3, "sg_boundary_accumulate"
 
     def __init__(self, *args, boundary_ratio: float = 0.02, boundary_px: Optional[int] = None, **kwargs):
         from . import ops
@@ -246,62 +334,27 @@ class BoundaryIoUMetric(IoUMetric):
         else:
             ops.boundary_width((1, 1), boundary_ratio)                       # the ratio's own checks
         super().__init__(*args, **kwargs)
-        if self.num_classes is not None and self.num_classes > ops.BOUNDARY_MAX_K:
-            raise ValueError(f"BoundaryIoUMetric: num_classes={self.num_classes} exceeds {ops.BOUNDARY_MAX_K}")
         self.boundary_ratio, self.boundary_px = boundary_ratio, boundary_px
-        self._areas: Optional[torch.Tensor] = None
 
     def width(self, hw) -> int:
         """The band width of an image of size ``hw``."""
         from . import ops
         return self.boundary_px if self.boundary_px is not None else ops.boundary_width(hw, self.boundary_ratio)
 
-    def _ensure_areas(self, device) -> torch.Tensor:
-        K = self._classes()
-        if self._areas is None:
-            self._areas = torch.zeros(3, K, dtype=torch.int64, device=device)
-        elif self._areas.device != torch.device(device):
-            self._areas = self._areas.to(device)
-        return self._areas
-
     @property
     def boundary_areas(self) -> torch.Tensor:
         """The [3,K] int64 band counts: intersection, prediction band, truth band."""
-        return self._ensure_areas("cpu" if self._areas is None else self._areas.device)
+        return self._ensure_second()
 
-    def reset(self) -> None:
-        super().reset()
-        self._areas = None
+    def _per_image(self, image_hw):
+        return [self.width(hw) for hw in image_hw]
 
-    def add(self, labels: torch.Tensor, gt: torch.Tensor) -> None:
-        """Counts one image in both tables: labels int64 and gt uint8 / int64, [H,W] or [1,H,W] of one size.  The band needs the
-        image's shape, so a flat buffer goes through ``add_flat``."""
-        gt, hw = _one_map("BoundaryIoUMetric", labels, gt)
-        self.add_flat(labels.reshape(-1), gt.reshape(-1), [hw])
-
-    def add_flat(self, labels: torch.Tensor, gt: torch.Tensor, image_hw) -> None:
-        """Counts the images that lie back to back in the flat ``labels`` / ``gt`` buffers (a flush group's), sizes ``image_hw``: one
-        sg_confusion_accumulate launch and one sg_boundary_accumulate call on the current stream."""
+    def _count(self, labels, gt, image_hw, values, table, K, match_map) -> None:
         from . import ops
-        image_hw = _flat_sizes("BoundaryIoUMetric", labels, image_hw)
-        ds = [self.width(hw) for hw in image_hw]
-        labels, gt = _flat_on_device("BoundaryIoUMetric", "sg_boundary_accumulate", labels, gt)
-        K = self._classes()
-        ops.confusion_accumulate(labels, gt, self._ensure(labels.device), K, self.ignore_index, self.reduce_zero_label)
-        ops.boundary_accumulate(labels, gt, image_hw, ds, self._ensure_areas(labels.device), K, self.ignore_index, self.reduce_zero_label)
+        ops.boundary_accumulate(labels, gt, image_hw, values, table, K, self.ignore_index, self.reduce_zero_label)
 
-    def reduce(self, group=None) -> None:
-        """Sums both tables over the ranks of ``group``: two all_reduces."""
-        import torch.distributed as dist
-        super().reduce(group)
-        dist.all_reduce(self.boundary_areas, op=dist.ReduceOp.SUM, group=group)
-
-    def compute(self) -> dict:
-        out = super().compute()
-        b = metrics_from_boundary(self.boundary_areas, self.nan_to_num)
-        out["BIoU"] = b["BIoU"]
-        out["summary"] = dict(out["summary"], mBIoU=b["summary"]["mBIoU"])
-        return out
+    def _scores(self) -> dict:
+        return metrics_from_boundary(self.boundary_areas, self.nan_to_num)
 
 
 TOLERANT_KEYS = {"region": ("RelPrecision", "RelRecall", "RelFscore", "mRelPrecision", "mRelRecall", "mRelFscore"),
@@ -318,34 +371,23 @@ def metrics_from_tolerant(counts, mode: str = "region", nan_to_num: Optional[int
     first), as ``metrics_from_boundary`` does."""
     if mode not in TOLERANT_KEYS:
         raise ValueError(f"metrics_from_tolerant: mode must be one of {sorted(TOLERANT_KEYS)}, got {mode!r}")
-    a = counts.detach().cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)
-    if a.ndim != 2 or a.shape[0] != 4 or a.shape[1] < 1:
-        raise ValueError(f"tolerant counts must be [4,K] with K >= 1, got shape {a.shape}")
-    if not np.issubdtype(a.dtype, np.integer):
-        raise TypeError(f"tolerant counts must hold integers, got {a.dtype}")
-    pred, right, true, found = (a[i].astype(np.float64) for i in range(4))
+    pred, right, true, found = _count_rows(counts, 4, "tolerant counts")
     with np.errstate(divide="ignore", invalid="ignore"):
         p, r = right / pred, found / true
-        vals = [np.asarray(v, dtype=np.float64) for v in (p, r, 2 * p * r / (p + r))]
-    if nan_to_num is not None:
-        vals = [np.nan_to_num(v, nan=nan_to_num) for v in vals]
+        f = 2 * p * r / (p + r)
     keys = TOLERANT_KEYS[mode]
-    out = dict(zip(keys[:3], vals))
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", category=RuntimeWarning)
-        out["summary"] = {k: float(np.round(np.nanmean(v) * 100, 2)) for k, v in zip(keys[3:], vals)}
-    return out
+    return _with_summary(dict(zip(keys[:3], (p, r, f))), keys[3:], nan_to_num)
 
 
-class RelaxedMetric(IoUMetric):
+class RelaxedMetric(_ImageShapeMetric):
     """``IoUMetric`` plus the tolerant scores: the confusion table as before and ``tolerant_counts`` int64 [4,K]
     (``sg_tolerant_accumulate``).  ``mode`` "region" gives relaxed precision / recall / F (roads), "contour" the boundary F-score.
     The tolerance is ``tolerance_ratio`` of each image's diagonal (``ops.tolerance_sq``; 0.0075) or the fixed ``tolerance_px``
     (an integer in [0, 254]), which overrides the ratio.
 
-    ``add(labels, gt)`` takes one 2-D map ([H,W] or [1,H,W]) and counts both tables; ``add_flat(labels, gt, image_hw)`` the flat buffers
-    of a flush group with the sizes of its images; ``reduce(group)`` sums both tables; ``add_confusion`` is IoUMetric's and leaves the
-    tolerant counts alone; ``compute()`` returns IoUMetric's dict plus the keys of ``metrics_from_tolerant``, merged into ``summary``."""
+    ``add`` / ``add_flat`` / ``reduce`` / ``compute`` as the shared base describes them; ``compute()`` adds the keys of
+    ``metrics_from_tolerant``."""
+    _ROWS, _ENTRY = 4, "sg_tolerant_accumulate"
 
     def __init__(self, *args, mode: str = "region", tolerance_px: Optional[int] = None, tolerance_ratio: float = 0.0075, **kwargs):
         from . import ops
@@ -357,64 +399,27 @@ class RelaxedMetric(IoUMetric):
         else:
             ops.tolerance_sq((1, 1), tolerance_ratio)                        # the ratio's own checks
         super().__init__(*args, **kwargs)
-        if self.num_classes is not None and self.num_classes > ops.TOLERANT_MAX_K:
-            raise ValueError(f"RelaxedMetric: num_classes={self.num_classes} exceeds {ops.TOLERANT_MAX_K}")
         self.mode, self.tolerance_px, self.tolerance_ratio = mode, tolerance_px, tolerance_ratio
-        self._counts: Optional[torch.Tensor] = None
 
     def tolerance_sq(self, hw) -> int:
         """The squared tolerance of an image of size ``hw``."""
         from . import ops
         return self.tolerance_px * self.tolerance_px if self.tolerance_px is not None else ops.tolerance_sq(hw, self.tolerance_ratio)
 
-    def _ensure_counts(self, device) -> torch.Tensor:
-        K = self._classes()
-        if self._counts is None:
-            self._counts = torch.zeros(4, K, dtype=torch.int64, device=device)
-        elif self._counts.device != torch.device(device):
-            self._counts = self._counts.to(device)
-        return self._counts
-
     @property
     def tolerant_counts(self) -> torch.Tensor:
         """The [4,K] int64 counts: predicted, predicted and right, true, true and found."""
-        return self._ensure_counts("cpu" if self._counts is None else self._counts.device)
+        return self._ensure_second()
 
-    def reset(self) -> None:
-        super().reset()
-        self._counts = None
+    def _per_image(self, image_hw):
+        return [self.tolerance_sq(hw) for hw in image_hw]
 
-    def add(self, labels: torch.Tensor, gt: torch.Tensor) -> None:
-        """Counts one image in both tables: labels int64 and gt uint8 / int64, [H,W] or [1,H,W] of one size.  The search needs the
-        image's shape, so a flat buffer goes through ``add_flat``."""
-        gt, hw = _one_map("RelaxedMetric", labels, gt)
-        self.add_flat(labels.reshape(-1), gt.reshape(-1), [hw])
-
-    def add_flat(self, labels: torch.Tensor, gt: torch.Tensor, image_hw) -> None:
-        """Counts the images that lie back to back in the flat ``labels`` / ``gt`` buffers (a flush group's), sizes ``image_hw``: one
-        sg_confusion_accumulate launch and one sg_tolerant_accumulate call on the current stream."""
+    def _count(self, labels, gt, image_hw, values, table, K, match_map) -> None:
         from . import ops
-        image_hw = _flat_sizes("RelaxedMetric", labels, image_hw)
-        ts = [self.tolerance_sq(hw) for hw in image_hw]
-        labels, gt = _flat_on_device("RelaxedMetric", "sg_tolerant_accumulate", labels, gt)
-        K = self._classes()
-        ops.confusion_accumulate(labels, gt, self._ensure(labels.device), K, self.ignore_index, self.reduce_zero_label)
-        ops.tolerant_accumulate(labels, gt, image_hw, ts, self._ensure_counts(labels.device), K, self.ignore_index, self.reduce_zero_label,
-                                self.mode)
+        ops.tolerant_accumulate(labels, gt, image_hw, values, table, K, self.ignore_index, self.reduce_zero_label, self.mode)
 
-    def reduce(self, group=None) -> None:
-        """Sums both tables over the ranks of ``group``: two all_reduces."""
-        import torch.distributed as dist
-        super().reduce(group)
-        dist.all_reduce(self.tolerant_counts, op=dist.ReduceOp.SUM, group=group)
-
-    def compute(self) -> dict:
-        out = super().compute()
-        t = metrics_from_tolerant(self.tolerant_counts, self.mode, self.nan_to_num)
-        summary = dict(out["summary"], **t.pop("summary"))
-        out.update(t)
-        out["summary"] = summary
-        return out
+    def _scores(self) -> dict:
+        return metrics_from_tolerant(self.tolerant_counts, self.mode, self.nan_to_num)
 
 
 OBJECT_KEYS = ("ObjPrecision", "ObjRecall", "ObjF1", "SQ", "PQ")
@@ -427,91 +432,51 @@ def metrics_from_objects(counts, nan_to_num: Optional[int] = None) -> dict:
     counts[2]), ``SQ`` = counts[3] / 2^24 / TP, ``PQ`` = SQ * RQ, float64 [K], NaN where a denominator is 0; and ``summary`` with
     ``mObjPrecision`` / ``mObjRecall`` / ``mObjF1`` / ``mSQ`` / ``mPQ``: ``nanmean * 100`` rounded to 2 decimals, NaN classes left out
     (``nan_to_num`` replaces NaN first), as ``metrics_from_tolerant`` does."""
-    a = counts.detach().cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)
-    if a.ndim != 2 or a.shape[0] != 4 or a.shape[1] < 1:
-        raise ValueError(f"object counts must be [4,K] with K >= 1, got shape {a.shape}")
-    if not np.issubdtype(a.dtype, np.integer):
-        raise TypeError(f"object counts must hold integers, got {a.dtype}")
-    tp, pred, true, iou_q = (a[i].astype(np.float64) for i in range(4))
+    tp, pred, true, iou_q = _count_rows(counts, 4, "object counts")
     with np.errstate(divide="ignore", invalid="ignore"):
         rq, sq = 2 * tp / (pred + true), iou_q / float(1 << 24) / tp
-        vals = [np.asarray(v, dtype=np.float64) for v in (tp / pred, tp / true, rq, sq, sq * rq)]
-    if nan_to_num is not None:
-        vals = [np.nan_to_num(v, nan=nan_to_num) for v in vals]
-    out = dict(zip(OBJECT_KEYS, vals))
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", category=RuntimeWarning)
-        out["summary"] = {"m" + k: float(np.round(np.nanmean(v) * 100, 2)) for k, v in zip(OBJECT_KEYS, vals)}
-    return out
+        vals = (tp / pred, tp / true, rq, sq, sq * rq)
+    return _with_summary(dict(zip(OBJECT_KEYS, vals)), ["m" + k for k in OBJECT_KEYS], nan_to_num)
 
 
-class ObjectMetric(IoUMetric):
+class ObjectMetric(_ImageShapeMetric):
     """``IoUMetric`` plus the object-level scores: the confusion table as before and ``object_counts`` int64 [4,K]
     (``sg_object_match``): per class the connected regions of prediction and truth, matched where their IoU is strictly above
     ``object_iou`` (a float or a ``(num, den)`` pair in [1/2, 1), ``ops.object_iou_fraction``).  A region is an object when it has at
     least ``min_area`` pixels and its class is not ``skip_label`` (the background of a building or road set); ``connectivity`` 4 or 8.
 
-    ``add(labels, gt)`` takes one 2-D map ([H,W] or [1,H,W]) and counts both tables; ``add_flat(labels, gt, image_hw)`` the flat buffers
-    of a flush group with the sizes of its images; ``reduce(group)`` sums both tables; ``add_confusion`` is IoUMetric's and leaves the
-    object counts alone; ``compute()`` returns IoUMetric's dict plus the keys of ``metrics_from_objects``, merged into ``summary``."""
+    ``add`` / ``add_flat`` / ``reduce`` / ``compute`` as the shared base describes them; ``add`` and ``add_flat`` also take
+    ``match_map``: None, or a uint8 tensor of the labels' size that receives the TP / FP / FN picture (``ops.object_match``);
+    ``compute()`` adds the keys of ``metrics_from_objects``."""
+    _ROWS, _ENTRY = 4, "sg_object_match"
 
     def __init__(self, *args, object_iou=0.5, min_area: int = 1, connectivity: int = 4, skip_label: Optional[int] = None, **kwargs):
         from . import ops
         self.object_iou = ops.object_args([(1, 1)], 1, object_iou, connectivity, min_area, skip_label)[2]
         super().__init__(*args, **kwargs)
-        if self.num_classes is not None and self.num_classes > ops.OBJECT_MAX_K:
-            raise ValueError(f"ObjectMetric: num_classes={self.num_classes} exceeds {ops.OBJECT_MAX_K}")
         self.min_area, self.connectivity, self.skip_label = int(min_area), int(connectivity), skip_label
-        self._counts: Optional[torch.Tensor] = None
-
-    def _ensure_counts(self, device) -> torch.Tensor:
-        K = self._classes()
-        if self._counts is None:
-            self._counts = torch.zeros(4, K, dtype=torch.int64, device=device)
-        elif self._counts.device != torch.device(device):
-            self._counts = self._counts.to(device)
-        return self._counts
 
     @property
     def object_counts(self) -> torch.Tensor:
         """The [4,K] int64 counts: matched pairs, predicted objects, true objects, the matched pairs' IoU in steps of 2^-24."""
-        return self._ensure_counts("cpu" if self._counts is None else self._counts.device)
-
-    def reset(self) -> None:
-        super().reset()
-        self._counts = None
+        return self._ensure_second()
 
     def add(self, labels: torch.Tensor, gt: torch.Tensor, match_map: Optional[torch.Tensor] = None) -> None:
-        """Counts one image in both tables: labels int64 and gt uint8 / int64, [H,W] or [1,H,W] of one size.  The regions need the
-        image's shape, so a flat buffer goes through ``add_flat``."""
-        gt, hw = _one_map("ObjectMetric", labels, gt)
+        """The base's ``add`` with ``match_map``, a uint8 tensor of the map's size."""
+        gt, hw = self._one_map(labels, gt)
         self.add_flat(labels.reshape(-1), gt.reshape(-1), [hw], match_map)
 
     def add_flat(self, labels: torch.Tensor, gt: torch.Tensor, image_hw, match_map: Optional[torch.Tensor] = None) -> None:
-        """Counts the images that lie back to back in the flat ``labels`` / ``gt`` buffers (a flush group's), sizes ``image_hw``: one
-        sg_confusion_accumulate launch and one sg_object_match call on the current stream.  ``match_map``: None, or a uint8 tensor of
-        the labels' size that receives the TP / FP / FN picture (``ops.object_match``)."""
+        """The base's ``add_flat`` with ``match_map``, a uint8 tensor of the labels' size."""
+        self._add_flat(labels, gt, image_hw, match_map)
+
+    def _count(self, labels, gt, image_hw, values, table, K, match_map) -> None:
         from . import ops
-        image_hw = _flat_sizes("ObjectMetric", labels, image_hw)
-        labels, gt = _flat_on_device("ObjectMetric", "sg_object_match", labels, gt)
-        K = self._classes()
-        ops.confusion_accumulate(labels, gt, self._ensure(labels.device), K, self.ignore_index, self.reduce_zero_label)
-        ops.object_match(labels, gt, image_hw, self._ensure_counts(labels.device), K, self.object_iou, self.connectivity, self.min_area,
-                         self.skip_label, self.ignore_index, self.reduce_zero_label, match_map)
+        ops.object_match(labels, gt, image_hw, table, K, self.object_iou, self.connectivity, self.min_area, self.skip_label,
+                         self.ignore_index, self.reduce_zero_label, match_map)
 
-    def reduce(self, group=None) -> None:
-        """Sums both tables over the ranks of ``group``: two all_reduces."""
-        import torch.distributed as dist
-        super().reduce(group)
-        dist.all_reduce(self.object_counts, op=dist.ReduceOp.SUM, group=group)
-
-    def compute(self) -> dict:
-        out = super().compute()
-        t = metrics_from_objects(self.object_counts, self.nan_to_num)
-        summary = dict(out["summary"], **t.pop("summary"))
-        out.update(t)
-        out["summary"] = summary
-        return out
+    def _scores(self) -> dict:
+        return metrics_from_objects(self.object_counts, self.nan_to_num)
 
 
 try:  # with mmseg installed the classes are also buildable from a config, under names that leave mmseg's own IoUMetric alone

@@ -1479,10 +1479,71 @@ def regions(labels, conf=None, connectivity=4, min_area=1, skip_label=None, max_
     return out
 
 
+# ---- What the entries that count flat buffers image by image share (boundary, tolerant, object matching) ------------------------------------
+CONFUSION_MAX_K = 127                                                    # the cap of sg_confusion_accumulate: one metric object holds its table too
+_MAX_PIXELS = (1 << 31) - 1                                              # pixel indices are 32-bit on the device
+
+
+def _image_sizes(who: str, image_hw, per_call: bool):
+    """Sizes of the images of a call as int pairs: at least one, all positive, below 2^31 pixels each or (``per_call``) together."""
+    image_hw = [(int(h), int(w)) for h, w in image_hw]
+    if not image_hw or any(h <= 0 or w <= 0 for h, w in image_hw):
+        raise ValueError(f"{who}: needs at least one image of positive size, got {image_hw}")
+    if per_call and sum(h * w for h, w in image_hw) > _MAX_PIXELS:
+        raise ValueError(f"{who}: 2^31 or more pixels in one call are not supported (region roots are 32-bit)")
+    if not per_call and any(h * w > _MAX_PIXELS for h, w in image_hw):
+        raise ValueError(f"{who}: an image of 2^31 or more pixels is not supported, got {image_hw}")
+    return image_hw
+
+
+def _per_image_ints(who: str, values, n_images: int, lo: int, hi: int, plural: str, name: str):
+    """One value for every image or one per image, integers in [lo, hi] -> the list of ``n_images`` values."""
+    vs = list(values) if isinstance(values, (list, tuple)) else [values] * n_images
+    if len(vs) != n_images:
+        raise ValueError(f"{who}: {len(vs)} {plural} for {n_images} images")
+    for v in vs:
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f"{who}: {name} must be an integer in [{lo}, {hi}], got {v!r}")
+    return vs
+
+
+def _image_arrays(image_hw):
+    """The C arrays of N images that lie back to back -> (N, prefix sums of their pixels, int32 [2N] sizes, int64 [N] pixel offsets)."""
+    N = len(image_hw)
+    pix = _prefix(h * w for h, w in image_hw)
+    return N, pix, (C.c_int32 * (2 * N))(*[v for s in image_hw for v in s]), (C.c_int64 * N)(*pix[:-1])
+
+
+def _flat_call(who: str, labels, gt, image_hw, K: int, table, table_name: str, rows: int, extra=None, extra_name: Optional[str] = None):
+    """The checks of a call on the flat int64 labels and uint8 / int64 truth of the images ``image_hw`` (already checked) that adds to
+    the int64 ``table`` [rows, K], in the order the callers refuse: K, the dtypes, the pixels against the sizes, the table, ``extra``
+    (None, or a uint8 buffer of one byte per pixel: object_match's match_map), the device.  Nothing here touches the library
+    -> (contiguous flat labels, contiguous flat truth, N, pixels of the call, sizes array, offsets array, ground-truth format code)."""
+    if not 1 <= K <= CONFUSION_MAX_K:
+        raise ValueError(f"{who}: K={K} outside [1, {CONFUSION_MAX_K}] (the cap of sg_confusion_accumulate)")
+    if not torch.is_tensor(labels) or labels.dtype != torch.int64:
+        raise TypeError(f"{who}: labels must be an int64 tensor")
+    if not torch.is_tensor(gt) or gt.dtype not in (torch.uint8, torch.int64):
+        raise TypeError(f"{who}: gt must be a uint8 or int64 tensor")
+    N, pix, hw, off = _image_arrays(image_hw)
+    if labels.numel() != pix[-1] or gt.numel() != pix[-1]:
+        raise ValueError(f"{who}: {N} images of sizes {image_hw} against {labels.numel()} labels and {gt.numel()} truth pixels")
+    if not torch.is_tensor(table) or table.dtype != torch.int64 or not table.is_contiguous() or table.numel() != rows * K:
+        raise ValueError(f"{who}: {table_name} must be contiguous int64 with {rows * K} elements for K={K}")
+    if extra is not None and (not torch.is_tensor(extra) or extra.dtype != torch.uint8 or not extra.is_contiguous() or extra.numel() != pix[-1]):
+        raise ValueError(f"{who}: {extra_name} must be a contiguous uint8 tensor of {pix[-1]} elements")
+    _require_gpu(labels, gt, table)
+    if gt.device != labels.device or table.device != labels.device or (extra is not None and extra.device != labels.device):
+        names = f"labels, gt and {table_name}" if extra_name is None else f"labels, gt, {table_name} and {extra_name}"
+        raise ValueError(f"{who}: {names} must live on one device")
+    fmt = _lib.GT_U8 if gt.dtype == torch.uint8 else _lib.GT_I64
+    return labels.contiguous().view(-1), gt.contiguous().view(-1), N, pix[-1], hw, off, fmt
+
+
 # ---- Boundary IoU (sg_boundary_band / sg_boundary_accumulate; the definition: include/segearth_hip.h) --------------------------------------
 BOUNDARY_MAX_D = 4095                                                    # the widest band the entries take
-BOUNDARY_MAX_K = 127                                                     # the cap of sg_confusion_accumulate
-BOUNDARY_MAX_PIXELS = (1 << 31) - 1                                      # per image
+BOUNDARY_MAX_K = CONFUSION_MAX_K
+BOUNDARY_MAX_PIXELS = _MAX_PIXELS                                        # per image
 
 
 def boundary_width(hw, ratio=0.02):
@@ -1503,24 +1564,8 @@ def boundary_width(hw, ratio=0.02):
 def boundary_args(image_hw, d):
     """The checks of the boundary entries, before any library call: sizes positive and below 2^31 pixels per image, every width an
     integer in [1, 4095]; one width serves every image -> (image_hw, widths)."""
-    image_hw = [(int(h), int(w)) for h, w in image_hw]
-    if not image_hw or any(h <= 0 or w <= 0 for h, w in image_hw):
-        raise ValueError(f"boundary: needs at least one image of positive size, got {image_hw}")
-    if any(h * w > BOUNDARY_MAX_PIXELS for h, w in image_hw):
-        raise ValueError(f"boundary: an image of 2^31 or more pixels is not supported, got {image_hw}")
-    ds = list(d) if isinstance(d, (list, tuple)) else [d] * len(image_hw)
-    if len(ds) != len(image_hw):
-        raise ValueError(f"boundary: {len(ds)} widths for {len(image_hw)} images")
-    for v in ds:
-        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= BOUNDARY_MAX_D:
-            raise ValueError(f"boundary: the band width d must be an integer in [1, {BOUNDARY_MAX_D}], got {v!r}")
-    return image_hw, ds
-
-
-def _boundary_arrays(image_hw, ds):
-    N = len(image_hw)
-    pix = _prefix(h * w for h, w in image_hw)
-    return N, pix, (C.c_int32 * (2 * N))(*[v for s in image_hw for v in s]), (C.c_int64 * N)(*pix[:-1]), (C.c_int32 * N)(*ds)
+    image_hw = _image_sizes("boundary", image_hw, per_call=False)
+    return image_hw, _per_image_ints("boundary", d, len(image_hw), 1, BOUNDARY_MAX_D, "widths", "the band width d")
 
 
 @on_tensor_device
@@ -1530,7 +1575,7 @@ def boundary_band_flat(labels, image_hw, d):
     image_hw, ds = boundary_args(image_hw, d)
     if not torch.is_tensor(labels) or labels.dtype not in (torch.int64, torch.uint8) or not labels.is_contiguous():
         raise TypeError("boundary_band: labels must be a contiguous int64 or uint8 tensor")
-    N, pix, hw, off, dd = _boundary_arrays(image_hw, ds)
+    N, pix, hw, off = _image_arrays(image_hw)
     if pix[-1] != labels.numel():
         raise ValueError(f"boundary_band: {N} images of sizes {image_hw} against {labels.numel()} labels")
     _require_gpu(labels)
@@ -1539,7 +1584,7 @@ def boundary_band_flat(labels, image_hw, d):
     buf = scratch(int(lib.sg_boundary_workspace_bytes(pix[-1])) // 4, labels.device)
     wp, wn = _aligned(buf)
     fmt = _lib.GT_U8 if labels.dtype == torch.uint8 else _lib.GT_I64
-    check(lib.sg_boundary_band(ptr(labels), fmt, hw, off, dd, N, ptr(band), wp, wn, stream_ptr()), "sg_boundary_band")
+    check(lib.sg_boundary_band(ptr(labels), fmt, hw, off, (C.c_int32 * N)(*ds), N, ptr(band), wp, wn, stream_ptr()), "sg_boundary_band")
     return band
 
 
@@ -1573,34 +1618,18 @@ def boundary_accumulate(labels_flat, gt_flat, image_hw, d, areas, K: int, ignore
     returned.  Nothing comes back to the host."""
     image_hw, ds = boundary_args(image_hw, d)
     K = int(K)
-    if not 1 <= K <= BOUNDARY_MAX_K:
-        raise ValueError(f"boundary_accumulate: K={K} outside [1, {BOUNDARY_MAX_K}] (the cap of sg_confusion_accumulate)")
-    if not torch.is_tensor(labels_flat) or labels_flat.dtype != torch.int64:
-        raise TypeError("boundary_accumulate: labels must be an int64 tensor")
-    if not torch.is_tensor(gt_flat) or gt_flat.dtype not in (torch.uint8, torch.int64):
-        raise TypeError("boundary_accumulate: gt must be a uint8 or int64 tensor")
-    N, pix, hw, off, dd = _boundary_arrays(image_hw, ds)
-    if labels_flat.numel() != pix[-1] or gt_flat.numel() != pix[-1]:
-        raise ValueError(f"boundary_accumulate: {N} images of sizes {image_hw} against {labels_flat.numel()} labels and "
-                         f"{gt_flat.numel()} truth pixels")
-    if not torch.is_tensor(areas) or areas.dtype != torch.int64 or not areas.is_contiguous() or areas.numel() != 3 * K:
-        raise ValueError(f"boundary_accumulate: areas must be contiguous int64 with {3 * K} elements for K={K}")
-    _require_gpu(labels_flat, gt_flat, areas)
-    if gt_flat.device != labels_flat.device or areas.device != labels_flat.device:
-        raise ValueError("boundary_accumulate: labels, gt and areas must live on one device")
+    labels_flat, gt_flat, N, total, hw, off, fmt = _flat_call("boundary_accumulate", labels_flat, gt_flat, image_hw, K, areas, "areas", 3)
     lib = _lib.load()
-    labels_flat, gt_flat = labels_flat.contiguous().view(-1), gt_flat.contiguous().view(-1)
-    buf = scratch(int(lib.sg_boundary_workspace_bytes(pix[-1])), labels_flat.device)
+    buf = scratch(int(lib.sg_boundary_workspace_bytes(total)), labels_flat.device)
     wp, wn = _aligned(buf)
-    fmt = _lib.GT_U8 if gt_flat.dtype == torch.uint8 else _lib.GT_I64
-    check(lib.sg_boundary_accumulate(ptr(labels_flat), ptr(gt_flat), fmt, hw, off, dd, N, K, int(ignore_index), int(bool(reduce_zero_label)),
-                                     ptr(areas), wp, wn, stream_ptr()), "sg_boundary_accumulate")
+    check(lib.sg_boundary_accumulate(ptr(labels_flat), ptr(gt_flat), fmt, hw, off, (C.c_int32 * N)(*ds), N, K, int(ignore_index),
+                                     int(bool(reduce_zero_label)), ptr(areas), wp, wn, stream_ptr()), "sg_boundary_accumulate")
     return areas
 
 
 # ---- Tolerant matching: relaxed precision / recall and the boundary F-score (sg_tolerant_accumulate; the definition: include/segearth_hip.h) --
 TOLERANT_MAX_SQ = 254 * 254                                              # the largest squared tolerance: a radius of 254 px
-TOLERANT_MAX_K = 127                                                     # the cap of sg_confusion_accumulate
+TOLERANT_MAX_K = CONFUSION_MAX_K
 TOLERANT_MODES = {"region": _lib.TOL_REGION, "contour": _lib.TOL_CONTOUR}
 
 
@@ -1625,17 +1654,8 @@ def tolerant_args(image_hw, tol_sq, mode):
     tolerance an integer in [0, 254^2] (one serves every image), a known mode -> (image_hw, tolerances, mode code)."""
     if mode not in TOLERANT_MODES:
         raise ValueError(f"tolerant: mode must be one of {sorted(TOLERANT_MODES)}, got {mode!r}")
-    image_hw = [(int(h), int(w)) for h, w in image_hw]
-    if not image_hw or any(h <= 0 or w <= 0 for h, w in image_hw):
-        raise ValueError(f"tolerant: needs at least one image of positive size, got {image_hw}")
-    if any(h * w > BOUNDARY_MAX_PIXELS for h, w in image_hw):
-        raise ValueError(f"tolerant: an image of 2^31 or more pixels is not supported, got {image_hw}")
-    ts = list(tol_sq) if isinstance(tol_sq, (list, tuple)) else [tol_sq] * len(image_hw)
-    if len(ts) != len(image_hw):
-        raise ValueError(f"tolerant: {len(ts)} tolerances for {len(image_hw)} images")
-    for v in ts:
-        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= TOLERANT_MAX_SQ:
-            raise ValueError(f"tolerant: the squared tolerance tol_sq must be an integer in [0, {TOLERANT_MAX_SQ}], got {v!r}")
+    image_hw = _image_sizes("tolerant", image_hw, per_call=False)
+    ts = _per_image_ints("tolerant", tol_sq, len(image_hw), 0, TOLERANT_MAX_SQ, "tolerances", "the squared tolerance tol_sq")
     return image_hw, ts, TOLERANT_MODES[mode]
 
 
@@ -1649,36 +1669,20 @@ def tolerant_accumulate(labels_flat, gt_flat, image_hw, tol_sq, counts, K: int, 
     (predicted, predicted and right, true, true and found), which is returned.  Nothing comes back to the host."""
     image_hw, ts, mode_code = tolerant_args(image_hw, tol_sq, mode)
     K = int(K)
-    if not 1 <= K <= TOLERANT_MAX_K:
-        raise ValueError(f"tolerant_accumulate: K={K} outside [1, {TOLERANT_MAX_K}] (the cap of sg_confusion_accumulate)")
-    if not torch.is_tensor(labels_flat) or labels_flat.dtype != torch.int64:
-        raise TypeError("tolerant_accumulate: labels must be an int64 tensor")
-    if not torch.is_tensor(gt_flat) or gt_flat.dtype not in (torch.uint8, torch.int64):
-        raise TypeError("tolerant_accumulate: gt must be a uint8 or int64 tensor")
-    N, pix, hw, off, tt = _boundary_arrays(image_hw, ts)
-    if labels_flat.numel() != pix[-1] or gt_flat.numel() != pix[-1]:
-        raise ValueError(f"tolerant_accumulate: {N} images of sizes {image_hw} against {labels_flat.numel()} labels and "
-                         f"{gt_flat.numel()} truth pixels")
-    if not torch.is_tensor(counts) or counts.dtype != torch.int64 or not counts.is_contiguous() or counts.numel() != 4 * K:
-        raise ValueError(f"tolerant_accumulate: counts must be contiguous int64 with {4 * K} elements for K={K}")
-    _require_gpu(labels_flat, gt_flat, counts)
-    if gt_flat.device != labels_flat.device or counts.device != labels_flat.device:
-        raise ValueError("tolerant_accumulate: labels, gt and counts must live on one device")
+    labels_flat, gt_flat, N, total, hw, off, fmt = _flat_call("tolerant_accumulate", labels_flat, gt_flat, image_hw, K, counts, "counts", 4)
     lib = _lib.load()
-    labels_flat, gt_flat = labels_flat.contiguous().view(-1), gt_flat.contiguous().view(-1)
-    buf = scratch(int(lib.sg_tolerant_workspace_bytes(pix[-1], K)), labels_flat.device)
+    buf = scratch(int(lib.sg_tolerant_workspace_bytes(total, K)), labels_flat.device)
     wp, wn = _aligned(buf)
-    fmt = _lib.GT_U8 if gt_flat.dtype == torch.uint8 else _lib.GT_I64
-    check(lib.sg_tolerant_accumulate(ptr(labels_flat), ptr(gt_flat), fmt, hw, off, tt, N, K, mode_code, int(ignore_index),
+    check(lib.sg_tolerant_accumulate(ptr(labels_flat), ptr(gt_flat), fmt, hw, off, (C.c_int32 * N)(*ts), N, K, mode_code, int(ignore_index),
                                      int(bool(reduce_zero_label)), ptr(counts), wp, wn, stream_ptr()), "sg_tolerant_accumulate")
     return counts
 
 
 # ---- Object matching: object-level precision / recall / F1 and panoptic quality (sg_object_match; the definition: include/segearth_hip.h) --
-OBJECT_MAX_K = 127                                                       # the cap of sg_confusion_accumulate
+OBJECT_MAX_K = CONFUSION_MAX_K
 OBJECT_MAX_DEN = 1 << 20                                                 # the largest denominator of the IoU threshold
 OBJECT_SQ_ONE = 1 << 24                                                  # row 3 of the counts: IoU in steps of 2^-24
-OBJECT_MAX_PIXELS = (1 << 31) - 1                                        # per call
+OBJECT_MAX_PIXELS = _MAX_PIXELS                                          # per call
 OBJECT_MATCHED_PRED, OBJECT_UNMATCHED_PRED, OBJECT_MATCHED_TRUE, OBJECT_UNMATCHED_TRUE = 1, 2, 4, 8      # the bits of match_map
 
 
@@ -1707,11 +1711,7 @@ def object_iou_fraction(t):
 def object_args(image_hw, K, iou=(1, 2), connectivity=4, min_area=1, skip_label=None):
     """The checks of sg_object_match, before any library call: sizes positive and below 2^31 pixels per call, K in [1, 127], a threshold
     in [1/2, 1), connectivity 4 or 8, min_area an integer >= 1, skip_label None or an integer -> (image_hw, K, (num, den))."""
-    image_hw = [(int(h), int(w)) for h, w in image_hw]
-    if not image_hw or any(h <= 0 or w <= 0 for h, w in image_hw):
-        raise ValueError(f"object_match: needs at least one image of positive size, got {image_hw}")
-    if sum(h * w for h, w in image_hw) > OBJECT_MAX_PIXELS:
-        raise ValueError("object_match: 2^31 or more pixels in one call are not supported (region roots are 32-bit)")
+    image_hw = _image_sizes("object_match", image_hw, per_call=True)
     if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= OBJECT_MAX_K:
         raise ValueError(f"object_match: K={K!r} outside [1, {OBJECT_MAX_K}] (the cap of sg_confusion_accumulate)")
     if isinstance(connectivity, bool) or connectivity not in (4, 8):
@@ -1734,26 +1734,10 @@ def object_match(labels, gt, image_hw, counts, K, iou=(1, 2), connectivity=4, mi
     is returned; ``match_map``: None or a uint8 tensor of the labels' size that receives 1 / 2 (matched / unmatched predicted object)
     plus 4 / 8 (matched / unmatched true object) per pixel.  Nothing comes back to the host."""
     image_hw, K, (num, den) = object_args(image_hw, K, iou, connectivity, min_area, skip_label)
-    if not torch.is_tensor(labels) or labels.dtype != torch.int64:
-        raise TypeError("object_match: labels must be an int64 tensor")
-    if not torch.is_tensor(gt) or gt.dtype not in (torch.uint8, torch.int64):
-        raise TypeError("object_match: gt must be a uint8 or int64 tensor")
-    N, pix, hw, off, _ = _boundary_arrays(image_hw, [0] * len(image_hw))
-    if labels.numel() != pix[-1] or gt.numel() != pix[-1]:
-        raise ValueError(f"object_match: {N} images of sizes {image_hw} against {labels.numel()} labels and {gt.numel()} truth pixels")
-    if not torch.is_tensor(counts) or counts.dtype != torch.int64 or not counts.is_contiguous() or counts.numel() != 4 * K:
-        raise ValueError(f"object_match: counts must be contiguous int64 with {4 * K} elements for K={K}")
-    if match_map is not None and (not torch.is_tensor(match_map) or match_map.dtype != torch.uint8 or not match_map.is_contiguous() or
-                                  match_map.numel() != pix[-1]):
-        raise ValueError(f"object_match: match_map must be a contiguous uint8 tensor of {pix[-1]} elements")
-    _require_gpu(labels, gt, counts)
-    if gt.device != labels.device or counts.device != labels.device or (match_map is not None and match_map.device != labels.device):
-        raise ValueError("object_match: labels, gt, counts and match_map must live on one device")
+    labels, gt, N, total, hw, off, fmt = _flat_call("object_match", labels, gt, image_hw, K, counts, "counts", 4, match_map, "match_map")
     lib = _lib.load()
-    labels, gt = labels.contiguous().view(-1), gt.contiguous().view(-1)
-    buf = scratch(int(lib.sg_object_workspace_bytes(pix[-1])), labels.device)
+    buf = scratch(int(lib.sg_object_workspace_bytes(total)), labels.device)
     wp, wn = _aligned(buf)
-    fmt = _lib.GT_U8 if gt.dtype == torch.uint8 else _lib.GT_I64
     check(lib.sg_object_match(ptr(labels), ptr(gt), fmt, hw, off, N, K, int(connectivity), int(min_area), 0 if skip_label is None else int(skip_label),
                               int(skip_label is not None), num, den, int(ignore_index), int(bool(reduce_zero_label)), ptr(counts), ptr(match_map),
                               wp, wn, stream_ptr()), "sg_object_match")

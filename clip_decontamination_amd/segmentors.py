@@ -608,43 +608,29 @@ class _HipSegmentorBase(_Base):
         of the class ``bg_idx``; one that is passed in keeps its own settings.  It is fed by ``add_flat`` per flush group where the other
         two are, which adds one sg_object_match call per group; it reads final labels only and composes in the same way.  ``object_*``
         together with ``boundary_*`` or ``relaxed_*``, or a passed metric of another kind, is refused."""
-        from .metrics import BoundaryIoUMetric, IoUMetric, ObjectMetric, RelaxedMetric
-        objects = object_iou is not None or isinstance(metric, ObjectMetric)
-        boundary = boundary_ratio is not None or boundary_px is not None or isinstance(metric, BoundaryIoUMetric)
-        relaxed = relaxed_px is not None or relaxed_ratio is not None or isinstance(metric, RelaxedMetric)
+        from .metrics import BoundaryIoUMetric, IoUMetric, ObjectMetric, RelaxedMetric, _ImageShapeMetric
+        # the kinds of metric with a second table: the class, whether its keyword arguments were given, their words in the refusals,
+        # and what the class is built with next to IoUMetric's arguments.  A kind is wanted by its arguments or by a metric of its class.
+        kinds = ((ObjectMetric, object_iou is not None, "object_*", "object_iou needs an",
+                  dict(object_iou=object_iou, min_area=object_min_area, connectivity=getattr(self, "region_connectivity", 4),
+                       skip_label=None if object_include_bg else int(self.bg_idx))),
+                 (RelaxedMetric, relaxed_px is not None or relaxed_ratio is not None, "relaxed_*", "relaxed_px / relaxed_ratio need a",
+                  dict(mode=relaxed_mode, tolerance_px=relaxed_px, **({} if relaxed_ratio is None else {"tolerance_ratio": relaxed_ratio}))),
+                 (BoundaryIoUMetric, boundary_ratio is not None or boundary_px is not None, "boundary_*", "boundary_ratio / boundary_px need a",
+                  dict(boundary_px=boundary_px, **({} if boundary_ratio is None else {"boundary_ratio": boundary_ratio}))))
+        wanted = [k for k in kinds if k[1] or isinstance(metric, k[0])]
         if getattr(self, "tile_group", None) is not None:
             raise ValueError("evaluate: tile_group sharding is not supported (each rank would have to count its own band against the "
                              "matching rows of the truth); evaluate whole images per rank and call metric.reduce(group)")
-        if boundary and relaxed:
-            raise ValueError("evaluate: relaxed_* and boundary_* (or a metric of the other kind) in one call are not supported: one "
-                             "metric object with both tables is not built; evaluate twice")
-        if objects and (boundary or relaxed):
-            raise ValueError("evaluate: object_* together with boundary_* or relaxed_* (or a metric of another kind) in one call is not "
+        if len(wanted) > 1:
+            raise ValueError(f"evaluate: {' together with '.join(k[2] for k in wanted)} (or a metric of another kind) in one call is not "
                              "supported: one metric object with several tables is not built; evaluate twice")
-        if objects and metric is not None and not isinstance(metric, ObjectMetric):
-            raise TypeError(f"evaluate: object_iou needs an ObjectMetric (or metric=None to have one built), got {type(metric).__name__}")
-        if relaxed and metric is not None and not isinstance(metric, RelaxedMetric):
-            raise TypeError("evaluate: relaxed_px / relaxed_ratio need a RelaxedMetric (or metric=None to have one built), got "
-                            f"{type(metric).__name__}")
-        if boundary and metric is not None and not isinstance(metric, BoundaryIoUMetric):
-            raise TypeError("evaluate: boundary_ratio / boundary_px need a BoundaryIoUMetric (or metric=None to have one built), got "
-                            f"{type(metric).__name__}")
-        if metric is None and boundary:
-            metric = BoundaryIoUMetric(ignore_index=ignore_index, iou_metrics=list(iou_metrics), num_classes=self.num_classes,
-                                       reduce_zero_label=reduce_zero_label, boundary_px=boundary_px,
-                                       **({} if boundary_ratio is None else {"boundary_ratio": boundary_ratio}))
-        elif metric is None and relaxed:
-            metric = RelaxedMetric(ignore_index=ignore_index, iou_metrics=list(iou_metrics), num_classes=self.num_classes,
-                                   reduce_zero_label=reduce_zero_label, mode=relaxed_mode, tolerance_px=relaxed_px,
-                                   **({} if relaxed_ratio is None else {"tolerance_ratio": relaxed_ratio}))
-        elif metric is None and objects:
-            metric = ObjectMetric(ignore_index=ignore_index, iou_metrics=list(iou_metrics), num_classes=self.num_classes,
-                                  reduce_zero_label=reduce_zero_label, object_iou=object_iou, min_area=object_min_area,
-                                  connectivity=getattr(self, "region_connectivity", 4),
-                                  skip_label=None if object_include_bg else int(self.bg_idx))
-        elif metric is None:
-            metric = IoUMetric(ignore_index=ignore_index, iou_metrics=list(iou_metrics), num_classes=self.num_classes,
-                               reduce_zero_label=reduce_zero_label)
+        cls, _, _, needs, own = wanted[0] if wanted else (IoUMetric, False, "", "", {})
+        if wanted and metric is not None and not isinstance(metric, cls):
+            raise TypeError(f"evaluate: {needs} {cls.__name__} (or metric=None to have one built), got {type(metric).__name__}")
+        if metric is None:
+            metric = cls(ignore_index=ignore_index, iou_metrics=list(iou_metrics), num_classes=self.num_classes,
+                         reduce_zero_label=reduce_zero_label, **own)
         elif metric.num_classes is None:
             metric.num_classes = self.num_classes
         elif metric.num_classes != self.num_classes:
@@ -675,23 +661,24 @@ class _HipSegmentorBase(_Base):
             gt_flat = torch.cat([g.reshape(-1).to(dtype) for g in gts]).to(dev)
         else:
             gt_flat = torch.cat([g.reshape(-1).to(device=dev, dtype=dtype) for g in gts])
-        if self.slide_crop <= 0:                                             # whole-image inference has no windows to pack
+
+        def feed(flat, gt, maps):                                            # a metric with a second table needs the sizes of the images
+            if isinstance(metric, _ImageShapeMetric):
+                metric.add_flat(flat, gt, [tuple(x.shape[-2:]) for x in maps])
+            else:
+                metric.add(flat, gt)
+
+        if self.slide_crop <= 0:                                            # whole-image inference has no windows to pack
             labs = self.predict_many(imgs, None, ori_shapes=ori) if at_gt_size else [self.predict(imgs[i][None], None) for i in range(n)]
             for i in range(n):
-                if boundary or relaxed or objects:
-                    metric.add_flat(labs[i].reshape(-1), gt_flat[off[i]:off[i + 1]], [tuple(labs[i].shape[-2:])])
-                else:
-                    metric.add(labs[i].reshape(-1), gt_flat[off[i]:off[i + 1]])
+                feed(labs[i].reshape(-1), gt_flat[off[i]:off[i + 1]], [labs[i]])
             return metric.compute(), metric
         for idx, _, labs, flat in self._pipeline().label_groups(imgs, self.slide_stride, self.slide_crop, want_probs=False, ori_shapes=ori):
             if idx == list(range(idx[0], idx[0] + len(idx))):                # the group's images are neighbours in the call: a slice
                 gt = gt_flat[off[idx[0]]:off[idx[-1] + 1]]
             else:                                                            # tile-size groups interleave images: gather on the device
                 gt = torch.cat([gt_flat[off[k]:off[k + 1]] for k in idx])
-            if boundary or relaxed or objects:
-                metric.add_flat(flat, gt, [tuple(x.shape[-2:]) for x in labs])
-            else:
-                metric.add(flat, gt)
+            feed(flat, gt, labs)
         return metric.compute(), metric
 
     def postprocess_result(self, seg_logits, data_samples):
