@@ -1628,15 +1628,94 @@ extern "C" int sg_cosine_logits_two_plane(const float* tokens, const float* cls,
   return SG_OK;
 }
 
+// ---- what the head entries share on the host -----------------------------------------------------------------------------------------------
+// The entries sg_stitch .. sg_area_relabel_multi (and sg_tta_head for K, bg_idx and the flags) state each argument check and each launch
+// shape once, here.  A check takes the entry's name and says "<entry>: ..."; an entry is its own null-pointer line, these checks under
+// SG_TRY in the order its refusals fire, the kernel choice and one of the two launches.  A new head entry composes them the same way.
+// The checks of K, k and bg_idx come between the shape and the launch limit (rows, blocks), which is why those two are apart.
+static bool head_tiles_ok(int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t, int pad_l) {
+  return T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0;
+}
+static int head_check_rows(const char* who, const char* what, int rows) {       // blockIdx.y counts rows of 4
+  SG_REQUIRE(cdiv(rows, 4) < 65536, "%s: %s too tall for one launch", who, what);
+  return SG_OK;
+}
+static int head_check_stitch(const char* who, int T, int Q, int gh, int gw, int H, int W) {   // bare, and up_h .. pad_l go untested
+  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && H > 0 && W > 0, "%s: bad shape", who);
+  return head_check_rows(who, "canvas", H);
+}
+static int head_check_image(const char* who, int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t, int pad_l, int H, int W) {
+  SG_REQUIRE(head_tiles_ok(T, Q, gh, gw, up_h, up_w, pad_t, pad_l) && H > 0 && W > 0, "%s: bad shape T=%d Q=%d gh=%d gw=%d up=%dx%d H=%d W=%d",
+             who, T, Q, gh, gw, up_h, up_w, H, W);
+  return SG_OK;
+}
+static int head_check_resized_image(const char* who, int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t, int pad_l, int H, int W,
+                                    int out_h, int out_w) {
+  SG_REQUIRE(head_tiles_ok(T, Q, gh, gw, up_h, up_w, pad_t, pad_l) && H > 0 && W > 0 && out_h > 0 && out_w > 0,
+             "%s: bad shape T=%d Q=%d gh=%d gw=%d up=%dx%d H=%d W=%d out=%dx%d", who, T, Q, gh, gw, up_h, up_w, H, W, out_h, out_w);
+  return SG_OK;
+}
+static int head_check_images(const char* who, int T, int Q, int gh, int gw, int up_h, int up_w, int pad_t, int pad_l, int N) {
+  SG_REQUIRE(head_tiles_ok(T, Q, gh, gw, up_h, up_w, pad_t, pad_l) && N > 0 && N <= T, "%s: bad shape T=%d Q=%d gh=%d gw=%d N=%d", who, T, Q,
+             gh, gw, N);
+  return SG_OK;
+}
+// canvas_Q = 0: `size` is out_pixels; the stitch entries pass Q, and `size` is canvas_elems
+static int head_check_blocks(const char* who, int64_t total_blocks, int64_t size, int canvas_Q = 0) {
+  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "%s: total_blocks=%lld outside (0, 2^31)", who, (long long)total_blocks);
+  if (canvas_Q) SG_REQUIRE(size >= canvas_Q, "%s: canvas_elems=%lld holds no canvas", who, (long long)size);
+  else SG_REQUIRE(size > 0, "%s: out_pixels=%lld holds no image", who, (long long)size);
+  return SG_OK;
+}
+static int head_check_K(const char* who, int K, int Q) { SG_REQUIRE(K > 0 && K <= Q, "%s: K=%d must lie in [1, Q=%d]", who, K, Q); return SG_OK; }
+static int head_check_topk(const char* who, int k, int K) {
+  SG_REQUIRE(k >= 1 && k <= SG_TOPK_MAX && k <= K, "%s: k=%d must lie in [1, min(%d, K=%d)]", who, k, SG_TOPK_MAX, K);
+  return SG_OK;
+}
+static int head_check_area_K(const char* who, int K) {
+  SG_REQUIRE(K <= SG_AREA_MAX_K, "%s: K=%d exceeds %d (SG_AREA_MAX_K, the limit of sg_class_area)", who, K, SG_AREA_MAX_K);
+  return SG_OK;
+}
+static int head_check_bg(const char* who, int bg, int K) { SG_REQUIRE(bg >= 0 && bg < K, "%s: bg_idx=%d outside [0, K=%d)", who, bg, K); return SG_OK; }
+// The kernels index the table with min(d, ramp_len - 1) and d >= 0, so a table of ramp_len entries is all they read.
+static int head_check_ramp(const char* who, const float* ramp, int ramp_len) {
+  SG_REQUIRE(ramp, "%s: null ramp", who);
+  SG_REQUIRE(ramp_len >= 1 && ramp_len <= SG_BLEND_MAX_RAMP, "%s: ramp_len=%d outside [1, %d]", who, ramp_len, SG_BLEND_MAX_RAMP);
+  return SG_OK;
+}
+static int head_check_flags(const char* who, int flags) {
+  SG_REQUIRE(flags == SG_RESIZED_AUTO || flags == SG_RESIZED_DIRECT || flags == SG_RESIZED_STAGED, "%s: flags=%d is no SG_RESIZED_* value", who,
+             flags);
+  return SG_OK;
+}
+// SG_RESIZED_STAGED is refused where the footprint of a block does not fit the stage; the multi-image entries cannot see the sizes (they
+// are device arrays), so there a block whose image does not fit runs the direct form and the caller checks beforehand (ops.py does).
+static int head_check_staged_fit(const char* who, int flags, int H, int W, int out_h, int out_w) {
+  SG_REQUIRE(flags != SG_RESIZED_STAGED || rs_fits(H, W, out_h, out_w),
+             "%s: the staged form does not fit: a block's footprint of %lld x %lld canvas pixels exceeds the stage of %d", who,
+             (long long)rs_span(4, H, out_h), (long long)rs_span(64, W, out_w), RS_STAGE_PIX);
+  return SG_OK;
+}
+
+// The two launch shapes: one block per 64 x 4 pixels of a [H, W] image, and the blocks of all images counted up front.
+template <class Kernel, class... Args>
+static int head_launch_image(Kernel kernel, int H, int W, sg_stream s, Args... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)cdiv(W, 64), (unsigned)cdiv(H, 4)), dim3(256), 0, as_stream(s), args...);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+template <class Kernel, class... Args>
+static int head_launch_blocks(Kernel kernel, int64_t total_blocks, sg_stream s, Args... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), args...);
+  SG_LAUNCH_CHECK();
+  return SG_OK;
+}
+
 extern "C" int sg_stitch(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w,
                          int pad_t, int pad_l, int H, int W, float* canvas, sg_stream s) {
   SG_REQUIRE(tile_logits && windows && canvas, "sg_stitch: null pointer");
-  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && H > 0 && W > 0, "sg_stitch: bad shape");
-  SG_REQUIRE(cdiv(H, 4) < 65536, "sg_stitch: canvas too tall for one launch");
-  hipLaunchKernelGGL(stitch_kernel, dim3((unsigned)cdiv(W, 64), (unsigned)cdiv(H, 4)), dim3(256), 0, as_stream(s), tile_logits, windows,
-                     T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, canvas);
-  SG_LAUNCH_CHECK();
-  return SG_OK;
+  SG_TRY(head_check_stitch(__func__, T, Q, gh, gw, H, W));
+  return head_launch_image(stitch_kernel, H, W, s, tile_logits, windows, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, canvas);
 }
 
 extern "C" int sg_resize_bilinear(const float* src, int C, int h, int w, float* dst, int H, int W, sg_stream s) {
@@ -1668,14 +1747,10 @@ extern "C" int sg_stitch_multi(const float* tile_logits, const int32_t* windows,
                                float* canvases, sg_stream s) {
   SG_REQUIRE(tile_logits && windows && tile_image && image_hw && image_tiles && canvas_offset && block_prefix && canvases,
              "sg_stitch_multi: null pointer");
-  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && N > 0 && N <= T,
-             "sg_stitch_multi: bad shape T=%d Q=%d gh=%d gw=%d N=%d", T, Q, gh, gw, N);
-  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "sg_stitch_multi: total_blocks=%lld outside (0, 2^31)", (long long)total_blocks);
-  SG_REQUIRE(canvas_elems >= Q, "sg_stitch_multi: canvas_elems=%lld holds no canvas", (long long)canvas_elems);
-  hipLaunchKernelGGL(stitch_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q, gh, gw,
-                     up_h, up_w, pad_t, pad_l, image_hw, image_tiles, canvas_offset, block_prefix, N, canvas_elems, canvases);
-  SG_LAUNCH_CHECK();
-  return SG_OK;
+  SG_TRY(head_check_images(__func__, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, N));
+  SG_TRY(head_check_blocks(__func__, total_blocks, canvas_elems, Q));
+  return head_launch_blocks(stitch_multi_kernel, total_blocks, s, tile_logits, windows, tile_image, T, Q, gh, gw, up_h, up_w, pad_t, pad_l,
+                            image_hw, image_tiles, canvas_offset, block_prefix, N, canvas_elems, canvases);
 }
 
 extern "C" int sg_postprocess_multi(const float* canvases, const int32_t* canvas_hw, const int64_t* canvas_offset, const int32_t* out_hw,
@@ -1737,14 +1812,11 @@ extern "C" int sg_label_head(const float* tile_logits, const int32_t* windows, i
                              int pad_l, int H, int W, const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx,
                              int64_t* labels, float* conf, sg_stream s) {
   SG_REQUIRE(tile_logits && windows && query_idx && labels, "sg_label_head: null pointer");
-  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && H > 0 && W > 0,
-             "sg_label_head: bad shape T=%d Q=%d gh=%d gw=%d up=%dx%d H=%d W=%d", T, Q, gh, gw, up_h, up_w, H, W);
-  SG_REQUIRE(K > 0 && K <= Q, "sg_label_head: K=%d must lie in [1, Q=%d]", K, Q);
-  SG_REQUIRE(cdiv(H, 4) < 65536, "sg_label_head: canvas too tall for one launch");
-  hipLaunchKernelGGL(label_head_kernel, dim3((unsigned)cdiv(W, 64), (unsigned)cdiv(H, 4)), dim3(256), 0, as_stream(s), tile_logits, windows,
-                     T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, query_idx, K, logit_scale, prob_thd, bg_idx, labels, conf);
-  SG_LAUNCH_CHECK();
-  return SG_OK;
+  SG_TRY(head_check_image(__func__, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W));
+  SG_TRY(head_check_K(__func__, K, Q));
+  SG_TRY(head_check_rows(__func__, "canvas", H));
+  return head_launch_image(label_head_kernel, H, W, s, tile_logits, windows, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, query_idx, K,
+                           logit_scale, prob_thd, bg_idx, labels, conf);
 }
 
 extern "C" int sg_label_head_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh, int gw,
@@ -1754,37 +1826,23 @@ extern "C" int sg_label_head_multi(const float* tile_logits, const int32_t* wind
                                    float* conf, sg_stream s) {
   SG_REQUIRE(tile_logits && windows && tile_image && image_hw && image_tiles && out_offset && block_prefix && query_idx && labels,
              "sg_label_head_multi: null pointer");
-  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && N > 0 && N <= T,
-             "sg_label_head_multi: bad shape T=%d Q=%d gh=%d gw=%d N=%d", T, Q, gh, gw, N);
-  SG_REQUIRE(K > 0 && K <= Q, "sg_label_head_multi: K=%d must lie in [1, Q=%d]", K, Q);
-  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "sg_label_head_multi: total_blocks=%lld outside (0, 2^31)", (long long)total_blocks);
-  SG_REQUIRE(out_pixels > 0, "sg_label_head_multi: out_pixels=%lld holds no image", (long long)out_pixels);
-  hipLaunchKernelGGL(label_head_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q,
-                     gh, gw, up_h, up_w, pad_t, pad_l, image_hw, image_tiles, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale,
-                     prob_thd, bg_idx, labels, conf);
-  SG_LAUNCH_CHECK();
-  return SG_OK;
+  SG_TRY(head_check_images(__func__, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, N));
+  SG_TRY(head_check_K(__func__, K, Q));
+  SG_TRY(head_check_blocks(__func__, total_blocks, out_pixels));
+  return head_launch_blocks(label_head_multi_kernel, total_blocks, s, tile_logits, windows, tile_image, T, Q, gh, gw, up_h, up_w, pad_t, pad_l,
+                            image_hw, image_tiles, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale, prob_thd, bg_idx, labels,
+                            conf);
 }
 
 // ---- weighted window blending: the four entries above with a ramp table (include/segearth_hip.h) ------------------------------------------
-// Each repeats its counterpart's checks under its own name, then the table's; the kernels index the table with min(d, ramp_len - 1) and
-// d >= 0, so a table of ramp_len entries is all they read.
-#define SG_REQUIRE_RAMP(name)                                                                                                         \
-  do {                                                                                                                                \
-    SG_REQUIRE(ramp, name ": null ramp");                                                                                             \
-    SG_REQUIRE(ramp_len >= 1 && ramp_len <= SG_BLEND_MAX_RAMP, name ": ramp_len=%d outside [1, %d]", ramp_len, SG_BLEND_MAX_RAMP);   \
-  } while (0)
-
+// Each checks the table first, then what its counterpart checks.
 extern "C" int sg_stitch_blend(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w,
                                int pad_t, int pad_l, int H, int W, float* canvas, const float* ramp, int ramp_len, sg_stream s) {
   SG_REQUIRE(tile_logits && windows && canvas, "sg_stitch_blend: null pointer");
-  SG_REQUIRE_RAMP("sg_stitch_blend");
-  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && H > 0 && W > 0, "sg_stitch_blend: bad shape");
-  SG_REQUIRE(cdiv(H, 4) < 65536, "sg_stitch_blend: canvas too tall for one launch");
-  hipLaunchKernelGGL(stitch_blend_kernel, dim3((unsigned)cdiv(W, 64), (unsigned)cdiv(H, 4)), dim3(256), 0, as_stream(s), tile_logits,
-                     windows, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, canvas, ramp, ramp_len);
-  SG_LAUNCH_CHECK();
-  return SG_OK;
+  SG_TRY(head_check_ramp(__func__, ramp, ramp_len));
+  SG_TRY(head_check_stitch(__func__, T, Q, gh, gw, H, W));
+  return head_launch_image(stitch_blend_kernel, H, W, s, tile_logits, windows, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, canvas, ramp,
+                           ramp_len);
 }
 
 extern "C" int sg_stitch_blend_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh,
@@ -1793,33 +1851,23 @@ extern "C" int sg_stitch_blend_multi(const float* tile_logits, const int32_t* wi
                                      int64_t canvas_elems, float* canvases, const float* ramp, int ramp_len, sg_stream s) {
   SG_REQUIRE(tile_logits && windows && tile_image && image_hw && image_tiles && canvas_offset && block_prefix && canvases,
              "sg_stitch_blend_multi: null pointer");
-  SG_REQUIRE_RAMP("sg_stitch_blend_multi");
-  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && N > 0 && N <= T,
-             "sg_stitch_blend_multi: bad shape T=%d Q=%d gh=%d gw=%d N=%d", T, Q, gh, gw, N);
-  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "sg_stitch_blend_multi: total_blocks=%lld outside (0, 2^31)",
-             (long long)total_blocks);
-  SG_REQUIRE(canvas_elems >= Q, "sg_stitch_blend_multi: canvas_elems=%lld holds no canvas", (long long)canvas_elems);
-  hipLaunchKernelGGL(stitch_blend_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q,
-                     gh, gw, up_h, up_w, pad_t, pad_l, image_hw, image_tiles, canvas_offset, block_prefix, N, canvas_elems, canvases, ramp,
-                     ramp_len);
-  SG_LAUNCH_CHECK();
-  return SG_OK;
+  SG_TRY(head_check_ramp(__func__, ramp, ramp_len));
+  SG_TRY(head_check_images(__func__, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, N));
+  SG_TRY(head_check_blocks(__func__, total_blocks, canvas_elems, Q));
+  return head_launch_blocks(stitch_blend_multi_kernel, total_blocks, s, tile_logits, windows, tile_image, T, Q, gh, gw, up_h, up_w, pad_t, pad_l,
+                            image_hw, image_tiles, canvas_offset, block_prefix, N, canvas_elems, canvases, ramp, ramp_len);
 }
 
 extern "C" int sg_label_head_blend(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w,
                                    int pad_t, int pad_l, int H, int W, const int32_t* query_idx, int K, float logit_scale, float prob_thd,
                                    int bg_idx, int64_t* labels, float* conf, const float* ramp, int ramp_len, sg_stream s) {
   SG_REQUIRE(tile_logits && windows && query_idx && labels, "sg_label_head_blend: null pointer");
-  SG_REQUIRE_RAMP("sg_label_head_blend");
-  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && H > 0 && W > 0,
-             "sg_label_head_blend: bad shape T=%d Q=%d gh=%d gw=%d up=%dx%d H=%d W=%d", T, Q, gh, gw, up_h, up_w, H, W);
-  SG_REQUIRE(K > 0 && K <= Q, "sg_label_head_blend: K=%d must lie in [1, Q=%d]", K, Q);
-  SG_REQUIRE(cdiv(H, 4) < 65536, "sg_label_head_blend: canvas too tall for one launch");
-  hipLaunchKernelGGL(label_head_blend_kernel, dim3((unsigned)cdiv(W, 64), (unsigned)cdiv(H, 4)), dim3(256), 0, as_stream(s), tile_logits,
-                     windows, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, query_idx, K, logit_scale, prob_thd, bg_idx, labels, conf, ramp,
-                     ramp_len);
-  SG_LAUNCH_CHECK();
-  return SG_OK;
+  SG_TRY(head_check_ramp(__func__, ramp, ramp_len));
+  SG_TRY(head_check_image(__func__, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W));
+  SG_TRY(head_check_K(__func__, K, Q));
+  SG_TRY(head_check_rows(__func__, "canvas", H));
+  return head_launch_image(label_head_blend_kernel, H, W, s, tile_logits, windows, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, query_idx, K,
+                           logit_scale, prob_thd, bg_idx, labels, conf, ramp, ramp_len);
 }
 
 extern "C" int sg_label_head_blend_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh,
@@ -1830,18 +1878,13 @@ extern "C" int sg_label_head_blend_multi(const float* tile_logits, const int32_t
                                          sg_stream s) {
   SG_REQUIRE(tile_logits && windows && tile_image && image_hw && image_tiles && out_offset && block_prefix && query_idx && labels,
              "sg_label_head_blend_multi: null pointer");
-  SG_REQUIRE_RAMP("sg_label_head_blend_multi");
-  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && N > 0 && N <= T,
-             "sg_label_head_blend_multi: bad shape T=%d Q=%d gh=%d gw=%d N=%d", T, Q, gh, gw, N);
-  SG_REQUIRE(K > 0 && K <= Q, "sg_label_head_blend_multi: K=%d must lie in [1, Q=%d]", K, Q);
-  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "sg_label_head_blend_multi: total_blocks=%lld outside (0, 2^31)",
-             (long long)total_blocks);
-  SG_REQUIRE(out_pixels > 0, "sg_label_head_blend_multi: out_pixels=%lld holds no image", (long long)out_pixels);
-  hipLaunchKernelGGL(label_head_blend_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image,
-                     T, Q, gh, gw, up_h, up_w, pad_t, pad_l, image_hw, image_tiles, out_offset, block_prefix, N, out_pixels, query_idx, K,
-                     logit_scale, prob_thd, bg_idx, labels, conf, ramp, ramp_len);
-  SG_LAUNCH_CHECK();
-  return SG_OK;
+  SG_TRY(head_check_ramp(__func__, ramp, ramp_len));
+  SG_TRY(head_check_images(__func__, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, N));
+  SG_TRY(head_check_K(__func__, K, Q));
+  SG_TRY(head_check_blocks(__func__, total_blocks, out_pixels));
+  return head_launch_blocks(label_head_blend_multi_kernel, total_blocks, s, tile_logits, windows, tile_image, T, Q, gh, gw, up_h, up_w, pad_t,
+                            pad_l, image_hw, image_tiles, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale, prob_thd, bg_idx,
+                            labels, conf, ramp, ramp_len);
 }
 
 // QMAX of the probability head: sg_postprocess's two instantiations up to PP_MAX_Q, the three-pass form (0) beyond.
@@ -1852,15 +1895,11 @@ extern "C" int sg_prob_head(const float* tile_logits, const int32_t* windows, in
                             float* probs, int64_t* labels, sg_stream s) {
   SG_REQUIRE(tile_logits && windows && query_idx && labels, "sg_prob_head: null pointer");
   SG_REQUIRE(probs, "sg_prob_head: probs is NULL (labels alone: sg_label_head)");
-  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && H > 0 && W > 0,
-             "sg_prob_head: bad shape T=%d Q=%d gh=%d gw=%d up=%dx%d H=%d W=%d", T, Q, gh, gw, up_h, up_w, H, W);
-  SG_REQUIRE(K > 0 && K <= Q, "sg_prob_head: K=%d must lie in [1, Q=%d]", K, Q);
-  SG_REQUIRE(cdiv(H, 4) < 65536, "sg_prob_head: canvas too tall for one launch");
-  auto kern = SG_PROB_HEAD_DISPATCH(prob_head_kernel, Q);
-  hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(W, 64), (unsigned)cdiv(H, 4)), dim3(256), 0, as_stream(s), tile_logits, windows, T, Q, gh, gw,
-                     up_h, up_w, pad_t, pad_l, H, W, query_idx, K, logit_scale, prob_thd, bg_idx, probs, labels);
-  SG_LAUNCH_CHECK();
-  return SG_OK;
+  SG_TRY(head_check_image(__func__, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W));
+  SG_TRY(head_check_K(__func__, K, Q));
+  SG_TRY(head_check_rows(__func__, "canvas", H));
+  return head_launch_image(SG_PROB_HEAD_DISPATCH(prob_head_kernel, Q), H, W, s, tile_logits, windows, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H,
+                           W, query_idx, K, logit_scale, prob_thd, bg_idx, probs, labels);
 }
 
 extern "C" int sg_prob_head_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh, int gw,
@@ -1871,17 +1910,12 @@ extern "C" int sg_prob_head_multi(const float* tile_logits, const int32_t* windo
   SG_REQUIRE(tile_logits && windows && tile_image && image_hw && image_tiles && out_offset && block_prefix && query_idx && labels,
              "sg_prob_head_multi: null pointer");
   SG_REQUIRE(probs, "sg_prob_head_multi: probs is NULL (labels alone: sg_label_head_multi)");
-  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && N > 0 && N <= T,
-             "sg_prob_head_multi: bad shape T=%d Q=%d gh=%d gw=%d N=%d", T, Q, gh, gw, N);
-  SG_REQUIRE(K > 0 && K <= Q, "sg_prob_head_multi: K=%d must lie in [1, Q=%d]", K, Q);
-  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "sg_prob_head_multi: total_blocks=%lld outside (0, 2^31)", (long long)total_blocks);
-  SG_REQUIRE(out_pixels > 0, "sg_prob_head_multi: out_pixels=%lld holds no image", (long long)out_pixels);
-  auto kern = SG_PROB_HEAD_DISPATCH(prob_head_multi_kernel, Q);
-  hipLaunchKernelGGL(kern, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q, gh, gw, up_h, up_w,
-                     pad_t, pad_l, image_hw, image_tiles, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale, prob_thd, bg_idx,
-                     probs, labels);
-  SG_LAUNCH_CHECK();
-  return SG_OK;
+  SG_TRY(head_check_images(__func__, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, N));
+  SG_TRY(head_check_K(__func__, K, Q));
+  SG_TRY(head_check_blocks(__func__, total_blocks, out_pixels));
+  return head_launch_blocks(SG_PROB_HEAD_DISPATCH(prob_head_multi_kernel, Q), total_blocks, s, tile_logits, windows, tile_image, T, Q, gh, gw,
+                            up_h, up_w, pad_t, pad_l, image_hw, image_tiles, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale,
+                            prob_thd, bg_idx, probs, labels);
 }
 
 // KTOP of the top-k head: the next power of two of k; the kernel writes the first k slots.
@@ -1892,16 +1926,12 @@ extern "C" int sg_topk_head(const float* tile_logits, const int32_t* windows, in
                             int pad_l, int H, int W, const int32_t* query_idx, int K, float logit_scale, int k, int32_t* classes,
                             float* probs, sg_stream s) {
   SG_REQUIRE(tile_logits && windows && query_idx && classes && probs, "sg_topk_head: null pointer");
-  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && H > 0 && W > 0,
-             "sg_topk_head: bad shape T=%d Q=%d gh=%d gw=%d up=%dx%d H=%d W=%d", T, Q, gh, gw, up_h, up_w, H, W);
-  SG_REQUIRE(K > 0 && K <= Q, "sg_topk_head: K=%d must lie in [1, Q=%d]", K, Q);
-  SG_REQUIRE(k >= 1 && k <= SG_TOPK_MAX && k <= K, "sg_topk_head: k=%d must lie in [1, min(%d, K=%d)]", k, SG_TOPK_MAX, K);
-  SG_REQUIRE(cdiv(H, 4) < 65536, "sg_topk_head: canvas too tall for one launch");
-  auto kern = SG_TOPK_HEAD_DISPATCH(topk_head_kernel, k);
-  hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(W, 64), (unsigned)cdiv(H, 4)), dim3(256), 0, as_stream(s), tile_logits, windows, T, Q, gh, gw,
-                     up_h, up_w, pad_t, pad_l, H, W, query_idx, K, logit_scale, k, classes, probs);
-  SG_LAUNCH_CHECK();
-  return SG_OK;
+  SG_TRY(head_check_image(__func__, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W));
+  SG_TRY(head_check_K(__func__, K, Q));
+  SG_TRY(head_check_topk(__func__, k, K));
+  SG_TRY(head_check_rows(__func__, "canvas", H));
+  return head_launch_image(SG_TOPK_HEAD_DISPATCH(topk_head_kernel, k), H, W, s, tile_logits, windows, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H,
+                           W, query_idx, K, logit_scale, k, classes, probs);
 }
 
 extern "C" int sg_topk_head_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh, int gw,
@@ -1910,42 +1940,28 @@ extern "C" int sg_topk_head_multi(const float* tile_logits, const int32_t* windo
                                   const int32_t* query_idx, int K, float logit_scale, int k, int32_t* classes, float* probs, sg_stream s) {
   SG_REQUIRE(tile_logits && windows && tile_image && image_hw && image_tiles && out_offset && block_prefix && query_idx && classes && probs,
              "sg_topk_head_multi: null pointer");
-  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && N > 0 && N <= T,
-             "sg_topk_head_multi: bad shape T=%d Q=%d gh=%d gw=%d N=%d", T, Q, gh, gw, N);
-  SG_REQUIRE(K > 0 && K <= Q, "sg_topk_head_multi: K=%d must lie in [1, Q=%d]", K, Q);
-  SG_REQUIRE(k >= 1 && k <= SG_TOPK_MAX && k <= K, "sg_topk_head_multi: k=%d must lie in [1, min(%d, K=%d)]", k, SG_TOPK_MAX, K);
-  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "sg_topk_head_multi: total_blocks=%lld outside (0, 2^31)", (long long)total_blocks);
-  SG_REQUIRE(out_pixels > 0, "sg_topk_head_multi: out_pixels=%lld holds no image", (long long)out_pixels);
-  auto kern = SG_TOPK_HEAD_DISPATCH(topk_head_multi_kernel, k);
-  hipLaunchKernelGGL(kern, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q, gh, gw, up_h, up_w,
-                     pad_t, pad_l, image_hw, image_tiles, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale, k, classes, probs);
-  SG_LAUNCH_CHECK();
-  return SG_OK;
+  SG_TRY(head_check_images(__func__, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, N));
+  SG_TRY(head_check_K(__func__, K, Q));
+  SG_TRY(head_check_topk(__func__, k, K));
+  SG_TRY(head_check_blocks(__func__, total_blocks, out_pixels));
+  return head_launch_blocks(SG_TOPK_HEAD_DISPATCH(topk_head_multi_kernel, k), total_blocks, s, tile_logits, windows, tile_image, T, Q, gh, gw,
+                            up_h, up_w, pad_t, pad_l, image_hw, image_tiles, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale,
+                            k, classes, probs);
 }
 
 // ---- the label and top-k heads at another ori_shape (segmentor.py:447-449 fused into the heads) ------------------------------------------
-// SG_RESIZED_STAGED is refused where the footprint of a block does not fit the stage; the multi-image entries cannot see the sizes (they
-// are device arrays), so there a block whose image does not fit runs the direct form and the caller checks beforehand (ops.py does).
-#define SG_RESIZED_REQUIRE_FLAGS(name, flags) \
-  SG_REQUIRE((flags) == SG_RESIZED_AUTO || (flags) == SG_RESIZED_DIRECT || (flags) == SG_RESIZED_STAGED, name ": flags=%d is no SG_RESIZED_* value", flags)
-
+// The launch covers the output, so it is the output that can be too tall.
 extern "C" int sg_label_head_resized(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w,
                                      int pad_t, int pad_l, int H, int W, int out_h, int out_w, const int32_t* query_idx, int K,
                                      float logit_scale, float prob_thd, int bg_idx, int64_t* labels, float* conf, int flags, sg_stream s) {
   SG_REQUIRE(tile_logits && windows && query_idx && labels, "sg_label_head_resized: null pointer");
-  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && H > 0 && W > 0 && out_h > 0 && out_w > 0,
-             "sg_label_head_resized: bad shape T=%d Q=%d gh=%d gw=%d up=%dx%d H=%d W=%d out=%dx%d", T, Q, gh, gw, up_h, up_w, H, W, out_h, out_w);
-  SG_REQUIRE(K > 0 && K <= Q, "sg_label_head_resized: K=%d must lie in [1, Q=%d]", K, Q);
-  SG_REQUIRE(cdiv(out_h, 4) < 65536, "sg_label_head_resized: output too tall for one launch");
-  SG_RESIZED_REQUIRE_FLAGS("sg_label_head_resized", flags);
-  SG_REQUIRE(flags != SG_RESIZED_STAGED || rs_fits(H, W, out_h, out_w),
-             "sg_label_head_resized: the staged form does not fit: a block's footprint of %lld x %lld canvas pixels exceeds the stage of %d",
-             (long long)rs_span(4, H, out_h), (long long)rs_span(64, W, out_w), RS_STAGE_PIX);
-  hipLaunchKernelGGL(label_head_resized_kernel, dim3((unsigned)cdiv(out_w, 64), (unsigned)cdiv(out_h, 4)), dim3(256), 0, as_stream(s),
-                     tile_logits, windows, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, out_h, out_w, query_idx, K, logit_scale, prob_thd,
-                     bg_idx, labels, conf, flags);
-  SG_LAUNCH_CHECK();
-  return SG_OK;
+  SG_TRY(head_check_resized_image(__func__, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, out_h, out_w));
+  SG_TRY(head_check_K(__func__, K, Q));
+  SG_TRY(head_check_rows(__func__, "output", out_h));
+  SG_TRY(head_check_flags(__func__, flags));
+  SG_TRY(head_check_staged_fit(__func__, flags, H, W, out_h, out_w));
+  return head_launch_image(label_head_resized_kernel, out_h, out_w, s, tile_logits, windows, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W,
+                           out_h, out_w, query_idx, K, logit_scale, prob_thd, bg_idx, labels, conf, flags);
 }
 
 extern "C" int sg_label_head_resized_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh,
@@ -1956,37 +1972,27 @@ extern "C" int sg_label_head_resized_multi(const float* tile_logits, const int32
                                            float* conf, int flags, sg_stream s) {
   SG_REQUIRE(tile_logits && windows && tile_image && image_hw && image_tiles && out_hw && out_offset && block_prefix && query_idx && labels,
              "sg_label_head_resized_multi: null pointer");
-  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && N > 0 && N <= T,
-             "sg_label_head_resized_multi: bad shape T=%d Q=%d gh=%d gw=%d N=%d", T, Q, gh, gw, N);
-  SG_REQUIRE(K > 0 && K <= Q, "sg_label_head_resized_multi: K=%d must lie in [1, Q=%d]", K, Q);
-  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "sg_label_head_resized_multi: total_blocks=%lld outside (0, 2^31)", (long long)total_blocks);
-  SG_REQUIRE(out_pixels > 0, "sg_label_head_resized_multi: out_pixels=%lld holds no image", (long long)out_pixels);
-  SG_RESIZED_REQUIRE_FLAGS("sg_label_head_resized_multi", flags);
-  hipLaunchKernelGGL(label_head_resized_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows,
-                     tile_image, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, image_hw, image_tiles, out_hw, out_offset, block_prefix, N, out_pixels,
-                     query_idx, K, logit_scale, prob_thd, bg_idx, labels, conf, flags);
-  SG_LAUNCH_CHECK();
-  return SG_OK;
+  SG_TRY(head_check_images(__func__, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, N));
+  SG_TRY(head_check_K(__func__, K, Q));
+  SG_TRY(head_check_blocks(__func__, total_blocks, out_pixels));
+  SG_TRY(head_check_flags(__func__, flags));
+  return head_launch_blocks(label_head_resized_multi_kernel, total_blocks, s, tile_logits, windows, tile_image, T, Q, gh, gw, up_h, up_w, pad_t,
+                            pad_l, image_hw, image_tiles, out_hw, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale, prob_thd,
+                            bg_idx, labels, conf, flags);
 }
 
 extern "C" int sg_topk_head_resized(const float* tile_logits, const int32_t* windows, int T, int Q, int gh, int gw, int up_h, int up_w,
                                     int pad_t, int pad_l, int H, int W, int out_h, int out_w, const int32_t* query_idx, int K,
                                     float logit_scale, int k, int32_t* classes, float* probs, int flags, sg_stream s) {
   SG_REQUIRE(tile_logits && windows && query_idx && classes && probs, "sg_topk_head_resized: null pointer");
-  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && H > 0 && W > 0 && out_h > 0 && out_w > 0,
-             "sg_topk_head_resized: bad shape T=%d Q=%d gh=%d gw=%d up=%dx%d H=%d W=%d out=%dx%d", T, Q, gh, gw, up_h, up_w, H, W, out_h, out_w);
-  SG_REQUIRE(K > 0 && K <= Q, "sg_topk_head_resized: K=%d must lie in [1, Q=%d]", K, Q);
-  SG_REQUIRE(k >= 1 && k <= SG_TOPK_MAX && k <= K, "sg_topk_head_resized: k=%d must lie in [1, min(%d, K=%d)]", k, SG_TOPK_MAX, K);
-  SG_REQUIRE(cdiv(out_h, 4) < 65536, "sg_topk_head_resized: output too tall for one launch");
-  SG_RESIZED_REQUIRE_FLAGS("sg_topk_head_resized", flags);
-  SG_REQUIRE(flags != SG_RESIZED_STAGED || rs_fits(H, W, out_h, out_w),
-             "sg_topk_head_resized: the staged form does not fit: a block's footprint of %lld x %lld canvas pixels exceeds the stage of %d",
-             (long long)rs_span(4, H, out_h), (long long)rs_span(64, W, out_w), RS_STAGE_PIX);
-  auto kern = SG_TOPK_HEAD_DISPATCH(topk_head_resized_kernel, k);
-  hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(out_w, 64), (unsigned)cdiv(out_h, 4)), dim3(256), 0, as_stream(s), tile_logits, windows, T, Q,
-                     gh, gw, up_h, up_w, pad_t, pad_l, H, W, out_h, out_w, query_idx, K, logit_scale, k, classes, probs, flags);
-  SG_LAUNCH_CHECK();
-  return SG_OK;
+  SG_TRY(head_check_resized_image(__func__, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, out_h, out_w));
+  SG_TRY(head_check_K(__func__, K, Q));
+  SG_TRY(head_check_topk(__func__, k, K));
+  SG_TRY(head_check_rows(__func__, "output", out_h));
+  SG_TRY(head_check_flags(__func__, flags));
+  SG_TRY(head_check_staged_fit(__func__, flags, H, W, out_h, out_w));
+  return head_launch_image(SG_TOPK_HEAD_DISPATCH(topk_head_resized_kernel, k), out_h, out_w, s, tile_logits, windows, T, Q, gh, gw, up_h, up_w,
+                           pad_t, pad_l, H, W, out_h, out_w, query_idx, K, logit_scale, k, classes, probs, flags);
 }
 
 extern "C" int sg_topk_head_resized_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh,
@@ -1997,19 +2003,14 @@ extern "C" int sg_topk_head_resized_multi(const float* tile_logits, const int32_
                                           sg_stream s) {
   SG_REQUIRE(tile_logits && windows && tile_image && image_hw && image_tiles && out_hw && out_offset && block_prefix && query_idx && classes &&
                  probs, "sg_topk_head_resized_multi: null pointer");
-  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && N > 0 && N <= T,
-             "sg_topk_head_resized_multi: bad shape T=%d Q=%d gh=%d gw=%d N=%d", T, Q, gh, gw, N);
-  SG_REQUIRE(K > 0 && K <= Q, "sg_topk_head_resized_multi: K=%d must lie in [1, Q=%d]", K, Q);
-  SG_REQUIRE(k >= 1 && k <= SG_TOPK_MAX && k <= K, "sg_topk_head_resized_multi: k=%d must lie in [1, min(%d, K=%d)]", k, SG_TOPK_MAX, K);
-  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "sg_topk_head_resized_multi: total_blocks=%lld outside (0, 2^31)", (long long)total_blocks);
-  SG_REQUIRE(out_pixels > 0, "sg_topk_head_resized_multi: out_pixels=%lld holds no image", (long long)out_pixels);
-  SG_RESIZED_REQUIRE_FLAGS("sg_topk_head_resized_multi", flags);
-  auto kern = SG_TOPK_HEAD_DISPATCH(topk_head_resized_multi_kernel, k);
-  hipLaunchKernelGGL(kern, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q, gh, gw, up_h, up_w,
-                     pad_t, pad_l, image_hw, image_tiles, out_hw, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale, k, classes,
-                     probs, flags);
-  SG_LAUNCH_CHECK();
-  return SG_OK;
+  SG_TRY(head_check_images(__func__, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, N));
+  SG_TRY(head_check_K(__func__, K, Q));
+  SG_TRY(head_check_topk(__func__, k, K));
+  SG_TRY(head_check_blocks(__func__, total_blocks, out_pixels));
+  SG_TRY(head_check_flags(__func__, flags));
+  return head_launch_blocks(SG_TOPK_HEAD_DISPATCH(topk_head_resized_multi_kernel, k), total_blocks, s, tile_logits, windows, tile_image, T, Q,
+                            gh, gw, up_h, up_w, pad_t, pad_l, image_hw, image_tiles, out_hw, out_offset, block_prefix, N, out_pixels, query_idx,
+                            K, logit_scale, k, classes, probs, flags);
 }
 
 // ---- test-time augmentation ---------------------------------------------------------------------------------------------------------------
@@ -2021,11 +2022,11 @@ extern "C" int sg_tta_head(const float* tile_logits, int64_t logit_elems, const 
   SG_REQUIRE(tile_logits && windows && views && query_idx && labels, "sg_tta_head: null pointer");
   SG_REQUIRE(V >= 1 && V <= SG_TTA_MAX_VIEWS, "sg_tta_head: V=%d views, must lie in [1, %d]", V, SG_TTA_MAX_VIEWS);
   SG_REQUIRE(Q > 0 && Q <= PP_MAX_Q, "sg_tta_head: Q=%d must lie in [1, %d] (more queries: sg_tta_accumulate / sg_tta_finish)", Q, PP_MAX_Q);
-  SG_REQUIRE(K > 0 && K <= Q, "sg_tta_head: K=%d must lie in [1, Q=%d]", K, Q);
-  SG_REQUIRE(bg_idx >= 0 && bg_idx < K, "sg_tta_head: bg_idx=%d outside [0, K=%d)", bg_idx, K);
+  SG_TRY(head_check_K(__func__, K, Q));
+  SG_TRY(head_check_bg(__func__, bg_idx, K));
   SG_REQUIRE(out_h > 0 && out_w > 0, "sg_tta_head: bad output size %dx%d", out_h, out_w);
-  SG_REQUIRE(cdiv(out_h, 4) < 65536, "sg_tta_head: output too tall for one launch");
-  SG_RESIZED_REQUIRE_FLAGS("sg_tta_head", flags);
+  SG_TRY(head_check_rows(__func__, "output", out_h));
+  SG_TRY(head_check_flags(__func__, flags));
   TtaViews tv;
   memset(&tv, 0, sizeof(tv));
   int64_t tiles = 0, elems = 0;
@@ -2084,16 +2085,13 @@ extern "C" int sg_area_relabel(const float* tile_logits, const int32_t* windows,
                                int pad_l, int H, int W, const int32_t* query_idx, int K, float logit_scale, float prob_thd, int bg_idx,
                                const int32_t* keep, const float* conf, int64_t* labels, sg_stream s) {
   SG_REQUIRE(tile_logits && windows && query_idx && keep && conf && labels, "sg_area_relabel: null pointer");
-  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && H > 0 && W > 0,
-             "sg_area_relabel: bad shape T=%d Q=%d gh=%d gw=%d up=%dx%d H=%d W=%d", T, Q, gh, gw, up_h, up_w, H, W);
-  SG_REQUIRE(K > 0 && K <= Q, "sg_area_relabel: K=%d must lie in [1, Q=%d]", K, Q);
-  SG_REQUIRE(K <= SG_AREA_MAX_K, "sg_area_relabel: K=%d exceeds %d (SG_AREA_MAX_K, the limit of sg_class_area)", K, SG_AREA_MAX_K);
-  SG_REQUIRE(bg_idx >= 0 && bg_idx < K, "sg_area_relabel: bg_idx=%d outside [0, K=%d)", bg_idx, K);
-  SG_REQUIRE(cdiv(H, 4) < 65536, "sg_area_relabel: canvas too tall for one launch");
-  hipLaunchKernelGGL(area_relabel_kernel, dim3((unsigned)cdiv(W, 64), (unsigned)cdiv(H, 4)), dim3(256), 0, as_stream(s), tile_logits, windows,
-                     T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, query_idx, K, logit_scale, prob_thd, bg_idx, keep, conf, labels);
-  SG_LAUNCH_CHECK();
-  return SG_OK;
+  SG_TRY(head_check_image(__func__, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W));
+  SG_TRY(head_check_K(__func__, K, Q));
+  SG_TRY(head_check_area_K(__func__, K));
+  SG_TRY(head_check_bg(__func__, bg_idx, K));
+  SG_TRY(head_check_rows(__func__, "canvas", H));
+  return head_launch_image(area_relabel_kernel, H, W, s, tile_logits, windows, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, H, W, query_idx, K,
+                           logit_scale, prob_thd, bg_idx, keep, conf, labels);
 }
 
 extern "C" int sg_area_relabel_multi(const float* tile_logits, const int32_t* windows, const int32_t* tile_image, int T, int Q, int gh, int gw,
@@ -2103,16 +2101,12 @@ extern "C" int sg_area_relabel_multi(const float* tile_logits, const int32_t* wi
                                      const float* conf, int64_t* labels, sg_stream s) {
   SG_REQUIRE(tile_logits && windows && tile_image && image_hw && image_tiles && out_offset && block_prefix && query_idx && keep && conf && labels,
              "sg_area_relabel_multi: null pointer");
-  SG_REQUIRE(T > 0 && Q > 0 && gh > 0 && gw > 0 && up_h > 0 && up_w > 0 && pad_t >= 0 && pad_l >= 0 && N > 0 && N <= T,
-             "sg_area_relabel_multi: bad shape T=%d Q=%d gh=%d gw=%d N=%d", T, Q, gh, gw, N);
-  SG_REQUIRE(K > 0 && K <= Q, "sg_area_relabel_multi: K=%d must lie in [1, Q=%d]", K, Q);
-  SG_REQUIRE(K <= SG_AREA_MAX_K, "sg_area_relabel_multi: K=%d exceeds %d (SG_AREA_MAX_K, the limit of sg_class_area)", K, SG_AREA_MAX_K);
-  SG_REQUIRE(bg_idx >= 0 && bg_idx < K, "sg_area_relabel_multi: bg_idx=%d outside [0, K=%d)", bg_idx, K);
-  SG_REQUIRE(total_blocks > 0 && total_blocks <= INT32_MAX, "sg_area_relabel_multi: total_blocks=%lld outside (0, 2^31)", (long long)total_blocks);
-  SG_REQUIRE(out_pixels > 0, "sg_area_relabel_multi: out_pixels=%lld holds no image", (long long)out_pixels);
-  hipLaunchKernelGGL(area_relabel_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(s), tile_logits, windows, tile_image, T, Q,
-                     gh, gw, up_h, up_w, pad_t, pad_l, image_hw, image_tiles, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale,
-                     prob_thd, bg_idx, keep, conf, labels);
-  SG_LAUNCH_CHECK();
-  return SG_OK;
+  SG_TRY(head_check_images(__func__, T, Q, gh, gw, up_h, up_w, pad_t, pad_l, N));
+  SG_TRY(head_check_K(__func__, K, Q));
+  SG_TRY(head_check_area_K(__func__, K));
+  SG_TRY(head_check_bg(__func__, bg_idx, K));
+  SG_TRY(head_check_blocks(__func__, total_blocks, out_pixels));
+  return head_launch_blocks(area_relabel_multi_kernel, total_blocks, s, tile_logits, windows, tile_image, T, Q, gh, gw, up_h, up_w, pad_t, pad_l,
+                            image_hw, image_tiles, out_offset, block_prefix, N, out_pixels, query_idx, K, logit_scale, prob_thd, bg_idx, keep,
+                            conf, labels);
 }

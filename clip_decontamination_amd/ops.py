@@ -275,19 +275,25 @@ def cosine_logits(tokens, cls, text, global_debias_factor: float = 0.0, cls_toke
     return out
 
 
-@on_tensor_device
-def stitch(tile_logits, windows, up_hw, pad_tl, canvas_hw):
-    """tile_logits [T,Q,gh,gw]; windows int32 [T,4] (y1,y2,x1,x2) -> canvas [Q,H,W]."""
+def _stitch(entry, tile_logits, windows, up_hw, pad_tl, canvas_hw, ramp=None):
+    """sg_stitch and sg_stitch_blend.  No window-count check here: the entries have none either."""
     lib = _lib.load()
     tile_logits = _f32(tile_logits)
     windows = windows.to(device=tile_logits.device, dtype=torch.int32).contiguous()
     _require_gpu(tile_logits)
     T, Q, gh, gw = tile_logits.shape
     H, W = canvas_hw
+    tail, ramp = _ramp_args(entry, ramp, tile_logits.device)
     canvas = torch.empty(Q, H, W, dtype=torch.float32, device=tile_logits.device)
-    check(lib.sg_stitch(ptr(tile_logits), ptr(windows), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1], H, W, ptr(canvas),
-                        stream_ptr()), "sg_stitch")
+    check(getattr(lib, entry)(ptr(tile_logits), ptr(windows), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1], H, W, ptr(canvas), *tail,
+                              stream_ptr()), entry)
     return canvas
+
+
+@on_tensor_device
+def stitch(tile_logits, windows, up_hw, pad_tl, canvas_hw):
+    """tile_logits [T,Q,gh,gw]; windows int32 [T,4] (y1,y2,x1,x2) -> canvas [Q,H,W]."""
+    return _stitch("sg_stitch", tile_logits, windows, up_hw, pad_tl, canvas_hw)
 
 
 @on_tensor_device
@@ -377,31 +383,87 @@ def _multi_args(what, tile_logits, windows, tile_image, up_hw, pad_tl, image_hw,
     return dev, lead, qi, pix, (tile_logits, windows, tile_image, i32, i64)
 
 
+def _label_outputs(dev, want_conf: bool, H: int, W: int):
+    """-> (labels int64 [1,H,W], conf f32 [H,W] or None)"""
+    return torch.empty(1, H, W, dtype=torch.int64, device=dev), torch.empty(H, W, dtype=torch.float32, device=dev) if want_conf else None
+
+
+def _label_outputs_multi(dev, want_conf: bool, pixels: int):
+    """-> (labels int64 [pixels], conf f32 [pixels] or None): the images back to back."""
+    return torch.empty(pixels, dtype=torch.int64, device=dev), torch.empty(pixels, dtype=torch.float32, device=dev) if want_conf else None
+
+
+def _label_results_multi(labels, conf, sizes, flat_conf: bool = False):
+    """What the multi-image label heads return: (label maps [1,H,W], the flat buffer they are views of), and with a ``conf`` its maps
+    [H,W] (``flat_conf``: the flat buffer itself) as a third result."""
+    lab = flat_views(labels, 1, sizes)
+    if conf is None:
+        return lab, labels
+    return lab, labels, (conf if flat_conf else [c[0] for c in flat_views(conf, 1, sizes)])
+
+
+def _topk_outputs(dev, k, H: int, W: int):
+    """-> (classes int32, probs f32), both [k,H,W]; a ``k`` below 1 is left for the entry to refuse."""
+    kk = max(int(k), 0)
+    return torch.empty(kk, H, W, dtype=torch.int32, device=dev), torch.empty(kk, H, W, dtype=torch.float32, device=dev)
+
+
+def _topk_outputs_multi(dev, k, pixels: int):
+    """-> (max(k, 0), classes int32, probs f32), both flat with k planes per image, the images back to back."""
+    kk = max(int(k), 0)
+    return kk, torch.empty(kk * pixels, dtype=torch.int32, device=dev), torch.empty(kk * pixels, dtype=torch.float32, device=dev)
+
+
+def _label_head(entry, tile_logits, windows, up_hw, pad_tl, canvas_hw, query_idx, num_classes, logit_scale, prob_thd, bg_idx, want_conf,
+                ramp=None):
+    """sg_label_head and sg_label_head_blend."""
+    lib = _lib.load()
+    dev, lead, qi, hold = _tile_args(entry[3:], tile_logits, windows, up_hw, pad_tl, query_idx)
+    H, W = canvas_hw
+    tail, ramp = _ramp_args(entry, ramp, dev)
+    labels, conf = _label_outputs(dev, want_conf, H, W)
+    check(getattr(lib, entry)(*lead, H, W, ptr(qi), int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx), ptr(labels), ptr(conf),
+                              *tail, stream_ptr()), entry)
+    return (labels, conf) if want_conf else labels
+
+
+def _stitch_multi(entry, tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, ramp=None):
+    """sg_stitch_multi and sg_stitch_blend_multi."""
+    lib = _lib.load()
+    Q = tile_logits.shape[1]
+    dev, lead, _, pix, hold = _multi_args(entry[3:], tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, planes=Q)
+    tail, ramp = _ramp_args(entry, ramp, dev)
+    canvases = torch.empty(Q * pix[-1], dtype=torch.float32, device=dev)
+    check(getattr(lib, entry)(*lead, canvases.numel(), ptr(canvases), *tail, stream_ptr()), entry)
+    return canvases, flat_views(canvases, Q, image_hw)
+
+
+def _label_head_multi(entry, tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, query_idx, num_classes, logit_scale,
+                      prob_thd, bg_idx, want_conf, flat_conf, ramp=None):
+    """sg_label_head_multi and sg_label_head_blend_multi."""
+    lib = _lib.load()
+    dev, lead, qi, pix, hold = _multi_args(entry[3:], tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, query_idx)
+    tail, ramp = _ramp_args(entry, ramp, dev)
+    labels, conf = _label_outputs_multi(dev, want_conf, pix[-1])
+    check(getattr(lib, entry)(*lead, pix[-1], ptr(qi), int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx), ptr(labels),
+                              ptr(conf), *tail, stream_ptr()), entry)
+    return _label_results_multi(labels, conf, image_hw, flat_conf)
+
+
 @on_tensor_device
 def label_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, query_idx, num_classes: int, logit_scale: float, prob_thd: float,
                bg_idx: int, want_conf: bool = False):
     """sg_label_head: ``stitch`` + ``postprocess`` without the canvas, for any Q.  tile_logits [T,Q,gh,gw]; windows int32 [T,4]
     -> labels int64 [1,H,W], or (labels, conf f32 [H,W] = the winning class's probability) with ``want_conf``."""
-    lib = _lib.load()
-    dev, lead, qi, hold = _tile_args("label_head", tile_logits, windows, up_hw, pad_tl, query_idx)
-    H, W = canvas_hw
-    labels = torch.empty(1, H, W, dtype=torch.int64, device=dev)
-    conf = torch.empty(H, W, dtype=torch.float32, device=dev) if want_conf else None
-    check(lib.sg_label_head(*lead, H, W, ptr(qi), int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx), ptr(labels), ptr(conf),
-                            stream_ptr()), "sg_label_head")
-    return (labels, conf) if want_conf else labels
+    return _label_head("sg_label_head", tile_logits, windows, up_hw, pad_tl, canvas_hw, query_idx, num_classes, logit_scale, prob_thd, bg_idx,
+                       want_conf)
 
 
 @on_tensor_device
 def stitch_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles):
     """The canvases of N images in one launch (sg_stitch_multi); the arguments: ``_multi_args``.
     -> (canvases: one flat f32 buffer, list of N views [Q,H,W] into it)."""
-    lib = _lib.load()
-    Q = tile_logits.shape[1]
-    dev, lead, _, pix, hold = _multi_args("stitch_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, planes=Q)
-    canvases = torch.empty(Q * pix[-1], dtype=torch.float32, device=dev)
-    check(lib.sg_stitch_multi(*lead, canvases.numel(), ptr(canvases), stream_ptr()), "sg_stitch_multi")
-    return canvases, flat_views(canvases, Q, image_hw)
+    return _stitch_multi("sg_stitch_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles)
 
 
 @on_tensor_device
@@ -411,16 +473,8 @@ def label_head_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, 
     post-process parameters).  -> (list of labels int64 [1,H,W], the flat int64 buffer they are views of, images back to back), plus
     the list of conf f32 [H,W] maps as a third result with ``want_conf`` (``flat_conf``: the one flat f32 buffer those maps are views
     of instead of the list).  Equals ``label_head`` per image byte for byte."""
-    lib = _lib.load()
-    dev, lead, qi, pix, hold = _multi_args("label_head_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, query_idx)
-    labels = torch.empty(pix[-1], dtype=torch.int64, device=dev)
-    conf = torch.empty(pix[-1], dtype=torch.float32, device=dev) if want_conf else None
-    check(lib.sg_label_head_multi(*lead, pix[-1], ptr(qi), int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx), ptr(labels),
-                                  ptr(conf), stream_ptr()), "sg_label_head_multi")
-    lab = flat_views(labels, 1, image_hw)
-    if want_conf:
-        return lab, labels, (conf if flat_conf else [c[0] for c in flat_views(conf, 1, image_hw)])
-    return lab, labels
+    return _label_head_multi("sg_label_head_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, query_idx, num_classes,
+                             logit_scale, prob_thd, bg_idx, want_conf, flat_conf)
 
 
 BLEND_KINDS = ("uniform", "linear", "hann")
@@ -462,56 +516,36 @@ def blend_table(kind: str, R: int, device) -> torch.Tensor:
     return _BLEND_TABLES[key]
 
 
-def _ramp_arg(what, ramp, device):
-    """A caller's ramp tensor as the entry takes it -> (f32 table on ``device``, its length)."""
+def _ramp_args(entry: str, ramp, device):
+    """What a ``_blend`` entry takes behind its counterpart's arguments, from a caller's ramp tensor -> ((pointer of the f32 table on
+    ``device``, its length), the table: hold it until the launch); ((), None) for every other entry."""
+    if "_blend" not in entry:
+        return (), None
     ramp = _f32(ramp).to(device).reshape(-1)
     if not 1 <= int(ramp.numel()) <= BLEND_MAX_RAMP:
-        raise ValueError(f"{what}: a ramp of {ramp.numel()} entries, must be 1 .. {BLEND_MAX_RAMP}")
-    return ramp, int(ramp.numel())
+        raise ValueError(f"{entry[3:]}: a ramp of {ramp.numel()} entries, must be 1 .. {BLEND_MAX_RAMP}")
+    return (ptr(ramp), int(ramp.numel())), ramp
 
 
 @on_tensor_device
 def stitch_blend(tile_logits, windows, up_hw, pad_tl, canvas_hw, ramp):
     """sg_stitch_blend: ``stitch`` with every tile weighted by ``ramp`` (f32 [L], ``blend_ramp``) of the pixel's distance to the tile's
     own window edges and divided by the sum of the weights -> canvas [Q,H,W]."""
-    lib = _lib.load()
-    tile_logits = _f32(tile_logits)
-    windows = windows.to(device=tile_logits.device, dtype=torch.int32).contiguous()
-    _require_gpu(tile_logits)
-    T, Q, gh, gw = tile_logits.shape
-    H, W = canvas_hw
-    ramp, L = _ramp_arg("stitch_blend", ramp, tile_logits.device)
-    canvas = torch.empty(Q, H, W, dtype=torch.float32, device=tile_logits.device)
-    check(lib.sg_stitch_blend(ptr(tile_logits), ptr(windows), T, Q, gh, gw, up_hw[0], up_hw[1], pad_tl[0], pad_tl[1], H, W, ptr(canvas),
-                              ptr(ramp), L, stream_ptr()), "sg_stitch_blend")
-    return canvas
+    return _stitch("sg_stitch_blend", tile_logits, windows, up_hw, pad_tl, canvas_hw, ramp)
 
 
 @on_tensor_device
 def stitch_blend_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, ramp):
     """sg_stitch_blend_multi: ``stitch_multi`` with the weights of ``stitch_blend``; the same results."""
-    lib = _lib.load()
-    Q = tile_logits.shape[1]
-    dev, lead, _, pix, hold = _multi_args("stitch_blend_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, planes=Q)
-    ramp, L = _ramp_arg("stitch_blend_multi", ramp, dev)
-    canvases = torch.empty(Q * pix[-1], dtype=torch.float32, device=dev)
-    check(lib.sg_stitch_blend_multi(*lead, canvases.numel(), ptr(canvases), ptr(ramp), L, stream_ptr()), "sg_stitch_blend_multi")
-    return canvases, flat_views(canvases, Q, image_hw)
+    return _stitch_multi("sg_stitch_blend_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, ramp)
 
 
 @on_tensor_device
 def label_head_blend(tile_logits, windows, up_hw, pad_tl, canvas_hw, query_idx, num_classes: int, logit_scale: float, prob_thd: float,
                      bg_idx: int, ramp, want_conf: bool = False):
     """sg_label_head_blend: ``label_head`` on the blended stitch (``stitch_blend``'s value per pixel and query); the same results."""
-    lib = _lib.load()
-    dev, lead, qi, hold = _tile_args("label_head_blend", tile_logits, windows, up_hw, pad_tl, query_idx)
-    H, W = canvas_hw
-    ramp, L = _ramp_arg("label_head_blend", ramp, dev)
-    labels = torch.empty(1, H, W, dtype=torch.int64, device=dev)
-    conf = torch.empty(H, W, dtype=torch.float32, device=dev) if want_conf else None
-    check(lib.sg_label_head_blend(*lead, H, W, ptr(qi), int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx), ptr(labels),
-                                  ptr(conf), ptr(ramp), L, stream_ptr()), "sg_label_head_blend")
-    return (labels, conf) if want_conf else labels
+    return _label_head("sg_label_head_blend", tile_logits, windows, up_hw, pad_tl, canvas_hw, query_idx, num_classes, logit_scale, prob_thd,
+                       bg_idx, want_conf, ramp)
 
 
 @on_tensor_device
@@ -519,18 +553,8 @@ def label_head_blend_multi(tile_logits, windows, tile_image, up_hw, pad_tl, imag
                            logit_scale: float, prob_thd: float, bg_idx: int, ramp, want_conf: bool = False, flat_conf: bool = False):
     """sg_label_head_blend_multi: ``label_head_multi`` on the blended stitch; the same results, ``label_head_blend`` per image byte for
     byte."""
-    lib = _lib.load()
-    dev, lead, qi, pix, hold = _multi_args("label_head_blend_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles,
-                                           query_idx)
-    ramp, L = _ramp_arg("label_head_blend_multi", ramp, dev)
-    labels = torch.empty(pix[-1], dtype=torch.int64, device=dev)
-    conf = torch.empty(pix[-1], dtype=torch.float32, device=dev) if want_conf else None
-    check(lib.sg_label_head_blend_multi(*lead, pix[-1], ptr(qi), int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx),
-                                        ptr(labels), ptr(conf), ptr(ramp), L, stream_ptr()), "sg_label_head_blend_multi")
-    lab = flat_views(labels, 1, image_hw)
-    if want_conf:
-        return lab, labels, (conf if flat_conf else [c[0] for c in flat_views(conf, 1, image_hw)])
-    return lab, labels
+    return _label_head_multi("sg_label_head_blend_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, query_idx,
+                             num_classes, logit_scale, prob_thd, bg_idx, want_conf, flat_conf, ramp)
 
 
 @on_tensor_device
@@ -577,9 +601,7 @@ def topk_head(tile_logits, windows, up_hw, pad_tl, canvas_hw, query_idx, num_cla
     lib = _lib.load()
     dev, lead, qi, hold = _tile_args("topk_head", tile_logits, windows, up_hw, pad_tl, query_idx)
     H, W = canvas_hw
-    kk = max(int(k), 0)
-    classes = torch.empty(kk, H, W, dtype=torch.int32, device=dev)
-    probs = torch.empty(kk, H, W, dtype=torch.float32, device=dev)
+    classes, probs = _topk_outputs(dev, k, H, W)
     check(lib.sg_topk_head(*lead, H, W, ptr(qi), int(num_classes), float(logit_scale), int(k), ptr(classes), ptr(probs), stream_ptr()),
           "sg_topk_head")
     return classes, probs
@@ -593,9 +615,7 @@ def topk_head_multi(tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, i
     ``topk_head`` per image byte for byte."""
     lib = _lib.load()
     dev, lead, qi, pix, hold = _multi_args("topk_head_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles, query_idx)
-    kk = max(int(k), 0)
-    classes = torch.empty(kk * pix[-1], dtype=torch.int32, device=dev)
-    probs = torch.empty(kk * pix[-1], dtype=torch.float32, device=dev)
+    kk, classes, probs = _topk_outputs_multi(dev, k, pix[-1])
     check(lib.sg_topk_head_multi(*lead, pix[-1], ptr(qi), int(num_classes), float(logit_scale), int(k), ptr(classes), ptr(probs), stream_ptr()),
           "sg_topk_head_multi")
     return flat_views(classes, kk, image_hw), flat_views(probs, kk, image_hw)
@@ -633,8 +653,7 @@ def label_head_resized(tile_logits, windows, up_hw, pad_tl, canvas_hw, out_hw, q
     lib = _lib.load()
     dev, lead, qi, hold = _tile_args("label_head_resized", tile_logits, windows, up_hw, pad_tl, query_idx)
     (h, w), (H, W) = canvas_hw, out_hw
-    labels = torch.empty(1, H, W, dtype=torch.int64, device=dev)
-    conf = torch.empty(H, W, dtype=torch.float32, device=dev) if want_conf else None
+    labels, conf = _label_outputs(dev, want_conf, H, W)
     check(lib.sg_label_head_resized(*lead, h, w, H, W, ptr(qi), int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx),
                                     ptr(labels), ptr(conf), flags, stream_ptr()), "sg_label_head_resized")
     return (labels, conf) if want_conf else labels
@@ -652,12 +671,10 @@ def label_head_resized_multi(tile_logits, windows, tile_image, up_hw, pad_tl, im
     lib = _lib.load()
     dev, lead, qi, pix, hold = _multi_args("label_head_resized_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles,
                                            query_idx, out_hw)
-    labels = torch.empty(pix[-1], dtype=torch.int64, device=dev)
-    conf = torch.empty(pix[-1], dtype=torch.float32, device=dev) if want_conf else None
+    labels, conf = _label_outputs_multi(dev, want_conf, pix[-1])
     check(lib.sg_label_head_resized_multi(*lead, pix[-1], ptr(qi), int(num_classes), float(logit_scale), float(prob_thd), int(bg_idx),
                                           ptr(labels), ptr(conf), flags, stream_ptr()), "sg_label_head_resized_multi")
-    lab = flat_views(labels, 1, out_hw)
-    return (lab, labels, [c[0] for c in flat_views(conf, 1, out_hw)]) if want_conf else (lab, labels)
+    return _label_results_multi(labels, conf, out_hw)
 
 
 @on_tensor_device
@@ -669,9 +686,7 @@ def topk_head_resized(tile_logits, windows, up_hw, pad_tl, canvas_hw, out_hw, qu
     lib = _lib.load()
     dev, lead, qi, hold = _tile_args("topk_head_resized", tile_logits, windows, up_hw, pad_tl, query_idx)
     (h, w), (H, W) = canvas_hw, out_hw
-    kk = max(int(k), 0)
-    classes = torch.empty(kk, H, W, dtype=torch.int32, device=dev)
-    probs = torch.empty(kk, H, W, dtype=torch.float32, device=dev)
+    classes, probs = _topk_outputs(dev, k, H, W)
     check(lib.sg_topk_head_resized(*lead, h, w, H, W, ptr(qi), int(num_classes), float(logit_scale), int(k), ptr(classes), ptr(probs), flags,
                                    stream_ptr()), "sg_topk_head_resized")
     return classes, probs
@@ -688,9 +703,7 @@ def topk_head_resized_multi(tile_logits, windows, tile_image, up_hw, pad_tl, ima
     lib = _lib.load()
     dev, lead, qi, pix, hold = _multi_args("topk_head_resized_multi", tile_logits, windows, tile_image, up_hw, pad_tl, image_hw, image_tiles,
                                            query_idx, out_hw)
-    kk = max(int(k), 0)
-    classes = torch.empty(kk * pix[-1], dtype=torch.int32, device=dev)
-    probs = torch.empty(kk * pix[-1], dtype=torch.float32, device=dev)
+    kk, classes, probs = _topk_outputs_multi(dev, k, pix[-1])
     check(lib.sg_topk_head_resized_multi(*lead, pix[-1], ptr(qi), int(num_classes), float(logit_scale), int(k), ptr(classes), ptr(probs), flags,
                                          stream_ptr()), "sg_topk_head_resized_multi")
     return flat_views(classes, kk, out_hw), flat_views(probs, kk, out_hw)
